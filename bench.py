@@ -27,6 +27,17 @@ exactly W warm-ups sees; with W >= 80 they are the same measurement.  No number 
 process: the pace controller's start value is measured in-process (`config.pace_start_source`: "calibration");
 a pace cache is used only if the caller names one (CCX_PACE_CACHE -> "user_cache").
 
+A plain run does only what the headline needs: set-up, the warm-up, the timed launches (and the settle / re-timed
+windows above), `--dump-outputs`, the line.  Everything else the bench measures -- the write-bandwidth probe, the
+secondary figures (no-obs / compact rows / K = 1 steps / short launches / a sustained window / the other BASELINE
+workloads and batch sizes) and the CPU baseline -- runs only with `--full` (`--no-secondary` / `--no-cpu-baseline`
+drop parts of it).
+
+`--dump-outputs DIR` writes what the last timed launch handed its caller (obs f32, reward f64, agent / env flag bytes
+as f32) to DIR/<name>.npy, a fixed seeded sample of the envs (and, if need be, of the steps) when the full arrays pass
+60 MB.  The inputs (reset pool, action stream) are seeded, and a re-timed window restarts from the state its first
+try started from, so the same arguments give the same arrays on every run.
+
 Prints ONE JSON line on rank 0.  `value` = env-steps/s over ALL ranks with inputs resident in HBM.
 Weak scaling: every rank owns 4096 envs of a global batch of N*4096; envs are independent, the only
 collective is the 48-byte all-reduce of the device-resident counters after the timed window (plus the
@@ -319,6 +330,47 @@ def rehearse(args) -> int:
     return 0
 
 
+DUMP_BYTES = 60_000_000      # --dump-outputs: array bytes written (the files, headers included, stay below 64 MB)
+
+
+def dump_sample(K: int, E: int, bytes_per_env: int):
+    """(steps, envs): sorted indices of what --dump-outputs writes out of K steps x E envs, seeded: all of them when they
+    fit into DUMP_BYTES, else as many envs as fit, and if one env alone does not fit, one env and as many steps as fit."""
+    import numpy as np
+    rng = np.random.default_rng(0)
+    n_env = int(min(E, max(1, DUMP_BYTES // bytes_per_env)))
+    envs = np.sort(rng.choice(E, n_env, replace=False)) if n_env < E else np.arange(E)
+    n_step = K if bytes_per_env <= DUMP_BYTES else max(1, int(DUMP_BYTES * K // bytes_per_env))
+    steps = np.sort(rng.choice(K, n_step, replace=False)) if n_step < K else np.arange(K)
+    return steps, envs
+
+
+def dump_outputs(torch, env, out, out_dir: str) -> dict:
+    """The outputs of the last launch (a RolloutResult) as float32 / float64 .npy files, sampled by dump_sample."""
+    import numpy as np
+    env.synchronize()
+    if torch.device(env.device).type == "cuda":
+        torch.cuda.synchronize(env.device)
+    fields = {k: getattr(out, k) for k in ("obs", "reward", "agent_flags", "env_flags", "obs_compact")
+              if getattr(out, k) is not None}
+    K, E = next(iter(fields.values())).shape[:2]
+    per_env = sum(t[:, :1].numel() * (8 if t.dtype == torch.float64 else 4) for t in fields.values())
+    steps, envs = dump_sample(K, E, per_env)
+    n_step, n_env = len(steps), len(envs)
+    ei = torch.from_numpy(envs).to(env.device)
+    si = torch.from_numpy(steps).to(env.device)
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    shapes = {}
+    for name, t in fields.items():
+        part = t.index_select(1, ei).index_select(0, si)          # (envs first: never a copy of the whole buffer)
+        part = part.double() if t.dtype == torch.float64 else part.float()
+        np.save(d / f"{name}.npy", part.cpu().numpy())
+        shapes[name] = list(part.shape)
+    return {"dir": str(out_dir), "arrays": shapes, "envs": f"{n_env} of {E}" + (" (seeded sample)" if n_env < E else ""),
+            "steps": f"{n_step} of {K}" + (" (seeded sample)" if n_step < K else "")}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -340,8 +392,13 @@ def parse_args(argv=None):
     ap.add_argument("--epsilon", type=float, default=0.0,
                     help="with --policy greedy: the policy's randomness_factor, drawn on the device "
                          "(ccx_set_policy_epsilon; the reference's create_greedy_policy default is 0.1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the no-obs / K=1 secondary figures")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: write-bandwidth probe, secondary figures, other "
+                         "workloads and batch sizes, CPU baseline (a plain run skips them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed launch's outputs to DIR/<name>.npy (a seeded sample when they pass 60 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the secondary figures")
     ap.add_argument("--no-obs", action="store_true", help="diagnostic: skip the observation output")
     ap.add_argument("--compact-obs", action="store_true",
                     help="diagnostic: CCX_OBS_COMPACT [E][N][4] rows instead of the DefaultObservation rows "
@@ -356,7 +413,10 @@ def parse_args(argv=None):
     ap.add_argument("--tunable", action="append", default=[], metavar="NAME=VALUE",
                     help="diagnostic: ccx_set_tunable(NAME, VALUE) on the handle (repeatable)")
     ap.add_argument("--rehearse", action="store_true", help="N>1 plumbing only, no env stepping (CPU-runnable)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def secondary_figures(torch, env, actions, chunk: int) -> dict:
@@ -725,6 +785,8 @@ def run_rank(args) -> int:
         # not in steady state yet: finish the start-up untimed and measure again
         settle = SETTLE_LAUNCHES - args.warmup - args.steps
         run(settle)
+        # (a re-timed window starts again from here: same state, same actions, so the outputs never depend on a stall)
+        start_state, start_launched = (env.get_state(), launched) if world == 1 else (None, launched)
         elapsed, mine, launch_ms, counters = timed_window()
         # A host that loses the CPU inside the 8-ms window (shared boxes: seen once in ~20 runs, 0.54 instead of 0.38 ms per
         # launch by the wall clock) leaves the GPU idle between launches: the wall clock of the window then exceeds the
@@ -734,19 +796,25 @@ def run_rank(args) -> int:
         if world == 1 and busy_ms > 0 and elapsed * 1e3 > 1.15 * busy_ms:
             retimed = {"first_ms_per_step": elapsed * 1e3 / args.steps, "first_wall_over_kernel_time": elapsed * 1e3 / busy_ms,
                        "why": "wall clock of the window > 1.15 x its summed kernel times: the host stalled, not the GPU"}
+            env.set_state(**start_state)
+            launched = start_launched
             elapsed, mine, launch_ms, counters = timed_window()
     steady = summarize(elapsed, launch_ms)
     per_rank = [args.steps * chunk * E / t for t in sharding.allgather_float(mine)]
 
-    probe = write_bandwidth_probe(torch, dev, traj.obs if traj.obs is not None else traj.reward) if rank == 0 else None
+    dumped = dump_outputs(torch, env, views[(launched - 1) % n_views], args.dump_outputs) if args.dump_outputs and rank == 0 else None
+
+    # ---- --full only: what the headline does not need (the probe overwrites the trajectory buffer: after the dump)
+    probe = (write_bandwidth_probe(torch, dev, traj.obs if traj.obs is not None else traj.reward)
+             if rank == 0 and args.full else None)
     secondary = None
     cpu_line = None
-    if rank == 0 and world == 1 and not args.no_secondary and args.policy == "random" and not args.no_obs:
+    if args.full and rank == 0 and world == 1 and not args.no_secondary and args.policy == "random" and not args.no_obs:
         secondary = secondary_figures(torch, env, actions, chunk)
         if args.workload == "c2" and not args.envs_per_gpu and not os.environ.get("CCX_DIAG_LIB"):
             secondary["short_launches"] = short_launches(torch, env, actions)
             secondary["sustained"] = sustained_window(torch, env, actions, chunk, traj)
-    if rank == 0 and not args.no_cpu_baseline and world == 1 and args.workload == "c2" and args.policy == "random":
+    if args.full and rank == 0 and not args.no_cpu_baseline and world == 1 and args.workload == "c2" and args.policy == "random":
         # (between the GPU legs: the driver's activity sampler sees a busy GPU before AND after these ~7 s)
         cpu_line = cpu_baseline(config, N)
     if secondary is not None and args.workload == "c2" and not args.envs_per_gpu and not os.environ.get("CCX_DIAG_LIB"):
@@ -765,7 +833,7 @@ def run_rank(args) -> int:
             "metric": f"env-steps/sec, random-action rollout, {E} envs x {N} agents per GPU",
             "value": env_sps, "unit": "env-steps/s", "agent_steps_per_sec": env_sps * N,
             "live_agent_steps_per_sec": counters["live_agent_steps"] / elapsed,
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             **sharding.group_info(),
             "counters_allreduce": (f"ccx_rccl_allreduce_counters ({direct.num_ranks} RCCL rank(s))" if direct
                                    else "torch.distributed" if world > 1 else None),
@@ -826,6 +894,8 @@ def run_rank(args) -> int:
                          "achieved_survey_8d_GBs": survey_unit * chunk * E * N / (kern_ms * 1e-3) / 1e9,
                          "survey_8d_bytes_per_agent_step": survey_unit},
         }
+        if dumped:
+            line["dumped_outputs"] = dumped
         if secondary:
             line["secondary"] = secondary
         if cpu_line is not None:

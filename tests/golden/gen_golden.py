@@ -502,6 +502,110 @@ def run_position_only():
     run_random("g13_position_only_terminated_c3", cfg_c3(terminated_config=both["terminated_config"]), seeds=range(1320, 1322), K=50)
 
 
+# ------------------------------------------------------------------------------------ live sample
+# tests/test_oracle_vs_reference_live.py compares the oracle with the reference on fresh fuzz configs.  The reference's side
+# of every case at the default seed base is stored under live_reference/ (one file per test, keys "<case>__<array>"), so
+# the test runs wherever the repository does; CCX_LIVE_SEED=<other base> redraws it live where the reference is present.
+# Rewritten by `python tests/golden/gen_golden.py --only=live`.
+LIVE_BASE = 20260000
+LIVE_DIR = HERE / "live_reference"
+LIVE_RANDOM = range(24)
+LIVE_POLICY = [(i, p) for i in range(8) for p in ("greedy", "waiting")]
+LIVE_HOST_POLICY = [(0, "greedy", 0.3), (1, "waiting", 0.2), (2, "greedy", 0.6),
+                    (3, "waiting", 0.5), (4, "greedy", 0.1), (5, "waiting", 0.9)]
+
+
+def live_random_case(base: int, index: int):
+    """2 envs x 30 steps of random actions (odd cases: shuffled dict order), ~10 % of the agents omitted per step."""
+    cfg = cfg_fuzz(base % 100000 + index)
+    K, seeds = 30, (base + 7 * index, base + 7 * index + 1)
+    rec = Recorder(cfg, len(seeds), K)
+    rng = np.random.default_rng(base + index)
+    for e, seed in enumerate(seeds):
+        env = rec.envs[e]
+        env.reset(seed=int(seed))
+        rec.snapshot_init(e)
+        for s in range(K):
+            ids = list(rec.ids)
+            if index & 1:
+                ids = [ids[i] for i in rng.permutation(len(ids))]
+            rec.step(s, e, {a: int(rng.integers(0, 5)) for a in ids if rng.random() >= 0.1})
+    return cfg, rec.a
+
+
+def live_policy_case(base: int, index: int, policy: str):
+    """1 env x 40 steps driven by the reference's GreedyPolicy / WaitingPolicy (epsilon 0): the actions it chose
+    (255 = agent not in the dict) and the dict order, from the recorded initial state."""
+    from baseline_policies import GreedyPolicy, WaitingPolicy
+    cfg = dict(cfg_fuzz(base % 100000 + 500 + index),
+               truncated_config=dict(truncated_function="max_steps", max_steps=60))
+    K = 40
+    rec = Recorder(cfg, 1, K)
+    env = rec.envs[0]
+    env.reset(seed=base + index)
+    rec.snapshot_init(0)
+    pol = (GreedyPolicy if policy == "greedy" else WaitingPolicy)(randomness_factor=0.0, seed=42)
+    for s in range(K):
+        rec.step(s, 0, {a: int(pol.get_action(a, None, env)) for a in env.agents})
+    keep = ("init_x", "init_y", "init_active", "init_terminated", "init_truncated", "init_step_count", "actions", "order")
+    return cfg, {k: rec.a[k] for k in keep}
+
+
+def live_host_policy_case(base: int, index: int, policy: str, eps: float):
+    """The reference's policy (seed 42, `eps` randomness) on one reference env until __all__ or 45 steps: per step the
+    agents' pre-step state (x, y, active, terminated, truncated by agent slot), the reference's `agents` list (slots,
+    -1 padded) and the action it chose for each of them (same order)."""
+    from baseline_policies import GreedyPolicy, WaitingPolicy
+    from collectivecrossing import CollectiveCrossingEnv as RefEnv
+
+    cfg = dict(cfg_fuzz(base % 100000 + 900 + index),
+               truncated_config=dict(truncated_function="max_steps", max_steps=50))
+    ref_env = RefEnv(config=build_ref_config(cfg))
+    ref_env.reset(seed=base + index)
+    ref_pol = (GreedyPolicy if policy == "greedy" else WaitingPolicy)(randomness_factor=eps, seed=42)
+    ids = ids_of(cfg)
+    slot = {a: i for i, a in enumerate(ids)}
+    rows = {k: [] for k in ("x", "y", "active", "terminated", "truncated", "agents", "actions")}
+    for _ in range(45):
+        ags = [ref_env._agents[a] for a in ids]
+        rows["x"].append([int(ag.position[0]) for ag in ags])
+        rows["y"].append([int(ag.position[1]) for ag in ags])
+        for k in ("active", "terminated", "truncated"):
+            rows[k].append([bool(getattr(ag, k)) for ag in ags])
+        live = list(ref_env.agents)
+        acts = {a: int(ref_pol.get_action(a, None, ref_env)) for a in live}
+        pad = [-1] * (len(ids) - len(live))
+        rows["agents"].append([slot[a] for a in live] + pad)
+        rows["actions"].append([acts[a] for a in live] + [255] * len(pad))
+        _, _, term, trunc, _ = ref_env.step(acts)
+        if term["__all__"] or trunc["__all__"]:
+            break
+    dt = dict(x=np.int32, y=np.int32, active=np.uint8, terminated=np.uint8, truncated=np.uint8, agents=np.int16,
+              actions=np.uint8)
+    return cfg, {k: np.asarray(v, dt[k]).reshape(len(v), len(ids)) for k, v in rows.items()}
+
+
+def live_case_names():
+    return {"random": [f"i{i:02d}" for i in LIVE_RANDOM],
+            "policy": [f"i{i:02d}_{p}" for i, p in LIVE_POLICY],
+            "host_policy": [f"i{i:02d}_{p}" for i, p, _ in LIVE_HOST_POLICY]}
+
+
+def run_live_sample(base: int = LIVE_BASE) -> None:
+    cases = {"random": [live_random_case(base, i) for i in LIVE_RANDOM],
+             "policy": [live_policy_case(base, i, p) for i, p in LIVE_POLICY],
+             "host_policy": [live_host_policy_case(base, i, p, e) for i, p, e in LIVE_HOST_POLICY]}
+    LIVE_DIR.mkdir(exist_ok=True)
+    for kind, names in live_case_names().items():
+        arrays = {}
+        for name, (cfg, a) in zip(names, cases[kind]):
+            arrays[f"{name}__config_json"] = np.array(json.dumps(cfg))
+            arrays.update({f"{name}__{k}": v for k, v in a.items()})
+        out = LIVE_DIR / f"{kind}.npz"
+        np.savez_compressed(out, base=np.int64(base), **arrays)
+        print(f"wrote live_reference/{out.name}: {len(names)} cases {out.stat().st_size / 1024:.0f} KiB")
+
+
 ONLY = [a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--only=")]
 
 
@@ -528,6 +632,8 @@ def main() -> int:
         run_custom_strategies()
     if not ONLY or any("g13_position_only".startswith(p) or p.startswith("g13") for p in ONLY):
         run_position_only()
+    if not ONLY or "live" in ONLY:
+        run_live_sample()
     # G14: policies on a grid without LDS occupancy tables (100 x 100)
     run_greedy("g14_greedy_100x100", cfg_big(), seeds=range(1400, 1402), K=230)
     run_greedy("g14_waiting_100x100", cfg_big(num_boarding_agents=6, num_exiting_agents=5), seeds=range(1410, 1411), K=200, policy="waiting")

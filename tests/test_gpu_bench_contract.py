@@ -25,12 +25,12 @@ def _run(*args, env=None):
 
 
 def test_bench_line_has_the_contract_fields_and_adds_up():
-    d = _run("--steps", "3", "--warmup", "2", "--no-cpu-baseline")
+    d = _run("--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--full")
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
                      ("ms_per_step", float), ("higher_is_better", bool), ("scaling", str), ("dtype", str),
                      ("data", str), ("config", dict), ("roofline", dict)):
         assert isinstance(d[key], typ), key
-    assert d["vs_baseline"] is None and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 2
+    assert d["vs_baseline"] is None and d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 2 and d["full"] is True
     assert d["unit"] == "env-steps/s" and d["higher_is_better"] is True and d["scaling"] == "weak" and d["data"] == "synthetic"
     c, r = d["config"], d["roofline"]
     assert "workload" in c and "model" not in c
@@ -86,6 +86,36 @@ def test_bench_line_has_the_contract_fields_and_adds_up():
     assert sh["k1"]["us_per_launch"] < 5.5 and sec["step_k1_graph"]["us_per_step"] < 5.5
 
 
+def test_plain_run_times_only_the_headline_and_dumps_the_same_outputs_every_time(tmp_path):
+    """Without --full the line carries the headline alone (no probe, secondary figures or CPU baseline), --steps launches
+    are timed, and --dump-outputs writes the last timed launch's outputs: float32 / float64, below 64 MB, and the same
+    arrays from a second process with the same arguments."""
+    import numpy as np
+
+    runs = [_run("--gpus", "1", "--steps", "3", "--warmup", "2", "--dump-outputs", str(tmp_path / name)) for name in "ab"]
+    d = runs[0]
+    c, r = d["config"], d["roofline"]
+    assert d["full"] is False and "secondary" not in d and "cpu_baseline" not in d
+    assert r["achievable_write_GBs_this_box"] is None and 0.2 < r["frac"] < 1.0
+    per_step = c["env_steps_per_step"] * c["envs_per_gpu"]
+    assert d["steps"] == 3 and d["counters"]["env_steps"] == 3 * per_step
+    assert d["value"] == pytest.approx(per_step / (d["ms_per_step"] * 1e-3), rel=1e-9)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["agent_flags.npy", "env_flags.npy", "obs.npy", "reward.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) < 64e6
+    arrays = {}
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype == (np.float64 if f == "reward.npy" else np.float32) and list(x.shape) == d["dumped_outputs"]["arrays"][f[:-4]]
+        np.testing.assert_array_equal(x.view(np.uint8), y.view(np.uint8), err_msg=f)
+        arrays[f[:-4]] = x
+    K, n, N, L = arrays["obs"].shape
+    assert K == c["env_steps_per_step"] and N == c["agents"] and L == c["obs_len"] and 1 <= n <= c["envs_per_gpu"]
+    assert arrays["reward"].shape == arrays["agent_flags"].shape == (K, n, N) and arrays["env_flags"].shape == (K, n)
+    assert np.all(arrays["agent_flags"] == np.round(arrays["agent_flags"])) and arrays["agent_flags"].max() < 256
+    assert np.any(arrays["agent_flags"] != 0) and np.any(arrays["obs"] != 0)
+
+
 def test_bench_with_a_pace_cache_says_so(tmp_path):
     """Opt-in pace memory (CCX_PACE_CACHE names the file; nothing is ever read from or written to $HOME): the first run
     leaves the learned pace there, the second starts from it and labels its numbers accordingly."""
@@ -100,7 +130,7 @@ def test_bench_with_a_pace_cache_says_so(tmp_path):
 
 
 def test_bench_cpu_baseline_leg():
-    d = _run("--steps", "2", "--warmup", "1")
+    d = _run("--steps", "2", "--warmup", "1", "--full")
     b = d["cpu_baseline"]
     assert b["kind"] == "port" and b["unit"] == "env-steps/s" and b["cores"] >= 1 and b["value"] > 1e5
     assert "sample" in b and b["value"] > 0

@@ -1,9 +1,11 @@
-"""LIVE pinning of the oracle where the reference is present (the build container; skipped on the GPU
-box): fresh random reference-valid configs are run through the IMPORTED reference and through the
-oracle in the same process, step by step -- positions, flags, rewards (bit patterns), observations,
-and the scripted policies' actions.  The committed fixtures are a frozen sample of exactly this
-comparison; this test redraws it every run with new seeds per round."""
+"""Pinning of the oracle against the reference on random reference-valid configs, step by step --
+positions, flags, rewards (bit patterns), observations, and the scripted policies' actions.  The reference's side
+of every case at the default seed base is committed data (tests/golden/live_reference/, recorded from the imported
+reference by ``gen_golden.py --only=live``), so the comparison runs wherever the repository does.  With
+CCX_LIVE_SEED set to another base, and the reference present (CCX_REFERENCE), the cases are redrawn and run through
+the IMPORTED reference in the same process instead."""
 
+import json
 import os
 import sys
 from pathlib import Path
@@ -15,27 +17,49 @@ HERE = Path(__file__).resolve().parent
 sys.path.insert(0, str(HERE / "golden"))
 import gen_golden as G  # noqa: E402
 
-pytestmark = pytest.mark.skipif(not (G.REF / "src" / "collectivecrossing").is_dir(),
-                                reason="the reference is only present in the build container")
+# the seed base of the cases (the committed sample is G.LIVE_BASE's)
+BASE = int(os.environ.get("CCX_LIVE_SEED", str(G.LIVE_BASE)))
+
+
+class _Cases:
+    """The reference's side of a case: (config dict, arrays), from the committed sample or from a live draw."""
+
+    def __init__(self, live: bool):
+        self.live, self._files = live, {}
+
+    def case(self, kind: str, name: str, *args):
+        if self.live:
+            return getattr(G, f"live_{kind}_case")(BASE, *args)
+        if kind not in self._files:
+            with np.load(G.LIVE_DIR / f"{kind}.npz") as z:
+                assert int(z["base"]) == G.LIVE_BASE
+                self._files[kind] = {k: z[k] for k in z.files}
+        a, p = self._files[kind], f"{name}__"
+        return (json.loads(str(a[p + "config_json"])),
+                {k[len(p):]: v for k, v in a.items() if k.startswith(p) and k != p + "config_json"})
 
 
 @pytest.fixture(scope="module")
 def reference():
+    if BASE == G.LIVE_BASE:
+        return _Cases(live=False)
+    if not (G.REF / "src" / "collectivecrossing").is_dir():
+        pytest.skip(f"CCX_LIVE_SEED={BASE} redraws the cases through the reference, which is not present (CCX_REFERENCE)")
     G.import_reference()
-    return G
+    return _Cases(live=True)
 
 
 class _Mem:
-    """The arrays of a Recorder with the interface of _fixtures.Golden (no file in between)."""
+    """Recorded arrays with the interface of _fixtures.Golden (no file per case)."""
 
-    def __init__(self, rec, cfg):
+    def __init__(self, a, cfg):
         from _fixtures import config_from_dict
         from collectivecrossing_amd.params import lower_config
 
-        self.a, self.name = rec.a, "live"
+        self.a, self.name = a, "live"
         self.config = config_from_dict(cfg)
         self.params = lower_config(self.config)
-        self.K, self.E, self.N = rec.a["actions"].shape
+        self.K, self.E, self.N = a["actions"].shape
 
     def __getitem__(self, k):
         return self.a[k]
@@ -46,97 +70,56 @@ class _Mem:
                     step_count=self["init_step_count"])
 
 
-# new configs every round of the build, reproducible within one (the seed is printed on failure)
-BASE = int(os.environ.get("CCX_LIVE_SEED", "20260000"))
-
-
-@pytest.mark.parametrize("index", range(24))
+@pytest.mark.parametrize("index", G.LIVE_RANDOM)
 def test_random_config_reference_vs_oracle(reference, oracle, index):
     from _fixtures import assert_step_matches
     from test_oracle_golden import _state
 
-    cfg = G.cfg_fuzz(BASE % 100000 + index)
-    K, seeds = 30, (BASE + 7 * index, BASE + 7 * index + 1)
-    rec = G.Recorder(cfg, len(seeds), K)
-    rng = np.random.default_rng(BASE + index)
-    for e, seed in enumerate(seeds):
-        env = rec.envs[e]
-        env.reset(seed=int(seed))
-        rec.snapshot_init(e)
-        for s in range(K):
-            ids = list(rec.ids)
-            if index & 1:
-                ids = [ids[i] for i in rng.permutation(len(ids))]
-            rec.step(s, e, {a: int(rng.integers(0, 5)) for a in ids if rng.random() >= 0.1})
-    g = _Mem(rec, cfg)
+    cfg, a = reference.case("random", f"i{index:02d}", index)
+    g = _Mem(a, cfg)
     b = oracle.OracleBatch(g.params, g.E)
     b.set_state(**g.init_state())
-    for s in range(K):
+    for s in range(g.K):
         obs, rew, af, ef = b.step(g["actions"][s], g["order"][s])
         assert_step_matches(g, s, obs, rew, af, ef, _state(b), label=f"cfg {cfg}")
 
 
-@pytest.mark.parametrize("index,policy", [(i, p) for i in range(8) for p in ("greedy", "waiting")])
+@pytest.mark.parametrize("index,policy", G.LIVE_POLICY)
 def test_random_config_reference_policy_vs_oracle(reference, oracle, index, policy):
-    from baseline_policies import GreedyPolicy, WaitingPolicy
-
-    cfg = dict(G.cfg_fuzz(BASE % 100000 + 500 + index),
-               truncated_config=dict(truncated_function="max_steps", max_steps=60))
-    K = 40
-    rec = G.Recorder(cfg, 1, K)
-    env = rec.envs[0]
-    env.reset(seed=BASE + index)
-    rec.snapshot_init(0)
-    pol = (GreedyPolicy if policy == "greedy" else WaitingPolicy)(randomness_factor=0.0, seed=42)
-    g = _Mem(rec, cfg)
+    cfg, a = reference.case("policy", f"i{index:02d}_{policy}", index, policy)
+    g = _Mem(a, cfg)
     b = oracle.OracleBatch(g.params, 1)
     b.set_state(**g.init_state())
-    for s in range(K):
-        acts = {a: int(pol.get_action(a, None, env)) for a in env.agents}
+    for s in range(g.K):
+        # the reference policy's actions (255 = agent not in its dict) for the state both envs are in
         mine = b.policy_actions(policy)[0]
-        want = np.full(g.N, 255, np.uint8)
-        for a, v in acts.items():
-            want[rec.ids.index(a)] = v
-        np.testing.assert_array_equal(mine, want, err_msg=f"{policy} step {s} cfg {cfg}")
-        rec.step(s, 0, acts)
-        b.step(rec.a["actions"][s], rec.a["order"][s], want_obs=False)
+        np.testing.assert_array_equal(mine, g["actions"][s][0], err_msg=f"{policy} step {s} cfg {cfg}")
+        b.step(g["actions"][s], g["order"][s], want_obs=False)
 
 
-@pytest.mark.parametrize("index,policy,eps", [(0, "greedy", 0.3), (1, "waiting", 0.2), (2, "greedy", 0.6),
-                                              (3, "waiting", 0.5), (4, "greedy", 0.1), (5, "waiting", 0.9)])
+@pytest.mark.parametrize("index,policy,eps", G.LIVE_HOST_POLICY)
 def test_host_policy_classes_vs_reference_policies_with_epsilon(reference, index, policy, eps):
     """collectivecrossing_amd.baseline_policies next to the reference's classes, both seeded with 42, on
-    the same live reference env (mirrored into a host view each step): same action every call."""
+    the states of one reference env (mirrored into a host view each step): same action every call."""
     from _fixtures import config_from_dict
-    from baseline_policies import GreedyPolicy, WaitingPolicy
 
     from collectivecrossing_amd import baseline_policies as bp
     from collectivecrossing_amd.env import CollectiveCrossingEnv
 
-    cfg = dict(G.cfg_fuzz(BASE % 100000 + 900 + index),
-               truncated_config=dict(truncated_function="max_steps", max_steps=50))
-    from collectivecrossing import CollectiveCrossingEnv as RefEnv
-
-    ref_env = RefEnv(config=G.build_ref_config(cfg))
-    ref_env.reset(seed=BASE + index)
+    cfg, a = reference.case("host_policy", f"i{index:02d}_{policy}", index, policy, eps)
     ours = CollectiveCrossingEnv.host_view(config_from_dict(cfg))
-    ref_pol = (GreedyPolicy if policy == "greedy" else WaitingPolicy)(randomness_factor=eps, seed=42)
     our_pol = (bp.GreedyPolicy if policy == "greedy" else bp.WaitingPolicy)(randomness_factor=eps, seed=42)
     ids = G.ids_of(cfg)
-    for s in range(45):
+    assert len(a["agents"]) >= 1
+    for s in range(len(a["agents"])):
         m = ours._mirror
-        for i, a in enumerate(ids):
-            ag = ref_env._agents[a]
-            m.x[i], m.y[i] = int(ag.position[0]), int(ag.position[1])
-            m.active[i], m.terminated[i], m.truncated[i] = ag.active, ag.terminated, ag.truncated
+        for i in range(len(ids)):
+            m.x[i], m.y[i] = int(a["x"][s, i]), int(a["y"][s, i])
+            m.active[i], m.terminated[i], m.truncated[i] = (bool(a["active"][s, i]), bool(a["terminated"][s, i]),
+                                                            bool(a["truncated"][s, i]))
         m.touch()
-        assert ours.agents == list(ref_env.agents)
-        acts = {}
-        for a in ref_env.agents:
-            want = int(ref_pol.get_action(a, None, ref_env))
-            got = int(our_pol.get_action(a, None, ours))
-            assert got == want, f"{policy} eps {eps} step {s} agent {a} cfg {cfg}"
-            acts[a] = want
-        _, _, term, trunc, _ = ref_env.step(acts)
-        if term["__all__"] or trunc["__all__"]:
-            break
+        live = [ids[i] for i in a["agents"][s] if i >= 0]
+        assert ours.agents == live
+        for aid, want in zip(live, a["actions"][s]):
+            got = int(our_pol.get_action(aid, None, ours))
+            assert got == int(want), f"{policy} eps {eps} step {s} agent {aid} cfg {cfg}"
