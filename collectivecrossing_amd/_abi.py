@@ -102,6 +102,8 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_policy_actions": (C.c_int, [_H, C.c_int32, C.c_void_p]),
     "ccx_observe": (C.c_int, [_H, C.c_void_p]),
     "ccx_expand_observations": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_void_p]),
+    "ccx_render": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "ccx_render_compact": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "ccx_step": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(CcxStepOut)]),
     "ccx_rollout": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                               C.POINTER(CcxRolloutOut)]),

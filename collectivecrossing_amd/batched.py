@@ -52,6 +52,13 @@ def _ptr(t: torch.Tensor | None) -> C.c_void_p:
     return C.c_void_p(None if t is None else t.data_ptr())
 
 
+def _check_cell_px(cell_px) -> int:
+    """Pixels per grid cell of a rendered frame: an integer in 1..64 (ccx_render)."""
+    if isinstance(cell_px, bool) or not isinstance(cell_px, (int, np.integer)) or not 1 <= int(cell_px) <= 64:
+        raise ValueError(f"cell_px must be an integer in 1..64, got {cell_px!r}")
+    return int(cell_px)
+
+
 class BatchedCollectiveCrossing:
     """E envs sharing one config, resident on one GPU for their whole life."""
 
@@ -315,6 +322,74 @@ class BatchedCollectiveCrossing:
         self._order_after_current_stream(c, out)
         check(self._lib.ccx_expand_observations(self._h, _ptr(c), rows, _ptr(out)))
         return out
+
+    # ------------------------------------------------------------------ rendering
+    def frame_shape(self, cell_px: int = 8) -> tuple[int, int, int]:
+        """(H * cell_px, W * cell_px, 3): one rgb_array frame of :meth:`render`."""
+        cp = _check_cell_px(cell_px)
+        return (self.params.height * cp, self.params.width * cp, 3)
+
+    def _frames_out(self, lead: tuple, cell_px: int, out: torch.Tensor | None) -> torch.Tensor:
+        shape = (*lead, *self.frame_shape(cell_px))
+        if out is None:
+            return self._new(shape, torch.uint8)
+        if not isinstance(out, torch.Tensor) or out.dtype is not torch.uint8:
+            raise ValueError("out must be a torch.uint8 tensor")
+        if out.device != self.device:
+            raise ValueError(f"out must live on {self.device}, got {out.device}")
+        if tuple(out.shape) != shape:
+            raise ValueError(f"out must have shape {shape}, got {tuple(out.shape)}")
+        if not out.is_contiguous() or out.data_ptr() % 16:
+            raise ValueError("out must be contiguous and 16-byte aligned")
+        return out
+
+    def render(self, env_ids=None, cell_px: int = 8, out: torch.Tensor | None = None) -> torch.Tensor:
+        """rgb_array frames of the current state (``ccx_render``): ``torch.uint8 [R, H*cell_px, W*cell_px, 3]`` on the
+        device, R = E (``env_ids=None``) or ``len(env_ids)``.  The picture of the reference's rendering.py without text,
+        ticks, title and legend (the frame spec is in include/ccx.h, CCX_RENDER); an id outside [0, E) gives a frame of
+        the static layers only.  Only enqueues work on the handle's stream, so it captures into a graph after ``step``."""
+        cp = _check_cell_px(cell_px)
+        ids = None
+        if env_ids is not None:
+            if isinstance(env_ids, torch.Tensor):
+                if env_ids.is_cuda and env_ids.device != self.device:
+                    raise ValueError(f"env_ids must live on {self.device} or the host, got {env_ids.device}")
+                if env_ids.dtype.is_floating_point or env_ids.dtype is torch.bool or env_ids.is_complex():
+                    raise ValueError(f"env_ids must be integers, got {env_ids.dtype}")
+                ids = env_ids
+            else:
+                arr = np.asarray(env_ids)
+                if arr.size and arr.dtype.kind not in "iu":
+                    raise ValueError(f"env_ids must be integers, got {arr.dtype}")
+                if arr.size and (arr.min() < np.iinfo(np.int32).min or arr.max() > np.iinfo(np.int32).max):
+                    raise ValueError("env_ids must fit int32")
+                ids = torch.from_numpy(np.ascontiguousarray(arr, np.int32))
+            if ids.dim() != 1:
+                raise ValueError(f"env_ids must be 1-D, got shape {tuple(ids.shape)}")
+            ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
+        rows = self.num_envs if ids is None else int(ids.shape[0])
+        frames = self._frames_out((rows,), cp, out)
+        if rows:
+            self._order_after_current_stream(ids, frames)
+            check(self._lib.ccx_render(self._h, _ptr(ids), rows, cp, _ptr(frames)))
+        return frames
+
+    def render_compact(self, obs_compact: torch.Tensor, cell_px: int = 8, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Frames of compact rows ``[..., N, 4]`` (``ccx_render_compact``) -> ``[..., H*cell_px, W*cell_px, 3]`` uint8:
+        a ``[K, E, N, 4]`` trajectory of ``rollout(..., want_compact=True)`` becomes K x E video frames in one launch."""
+        cp = _check_cell_px(cell_px)
+        if not isinstance(obs_compact, torch.Tensor):
+            obs_compact = torch.from_numpy(np.ascontiguousarray(obs_compact, np.float32))
+        if obs_compact.dim() < 2 or tuple(obs_compact.shape[-2:]) != (self.num_agents, 4):
+            raise ValueError(f"expected [..., {self.num_agents}, 4], got {tuple(obs_compact.shape)}")
+        c = obs_compact.to(device=self.device, dtype=torch.float32).contiguous()
+        lead = tuple(c.shape[:-2])
+        rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        frames = self._frames_out(lead, cp, out)
+        if rows:
+            self._order_after_current_stream(c, frames)
+            check(self._lib.ccx_render_compact(self._h, _ptr(c), rows, cp, _ptr(frames)))
+        return frames
 
     def rollout(self, actions, order=None, auto_reset: bool = False,
                 out: RolloutResult | None = None, want_obs: bool = True,

@@ -482,12 +482,49 @@ class CollectiveCrossingEnv(_Base):
         if batch is not None:
             batch.close()
 
+    # rgb_array figure of render(): the reference's Figure(figsize=(12, 8), dpi=100)
+    RENDER_SIZE = (800, 1200)
+    # the board is drawn at the largest integer cell size whose frame fits this box, centred in the white figure
+    RENDER_BOX = (720, 1120)
+
+    def render_cell_px(self) -> int:
+        """Cell size of :meth:`render`'s board: the largest ``cp`` in 1..64 with ``H cp <= 720`` and ``W cp <= 1120``."""
+        c = self._config
+        return max(1, min(64, self.RENDER_BOX[0] // c.height, self.RENDER_BOX[1] // c.width))
+
+    def render_board_origin(self) -> tuple[int, int]:
+        """(top row, left column) of the board inside the 800 x 1200 figure of :meth:`render`."""
+        cp, c = self.render_cell_px(), self._config
+        return ((self.RENDER_SIZE[0] - c.height * cp) // 2, (self.RENDER_SIZE[1] - c.width * cp) // 2)
+
     def render(self, mode: str = "rgb_array"):
-        """Rendering is matplotlib drawing in the reference (rendering.py) and never on the step
-        path; it is out of scope here."""
+        """``mode="rgb_array"``: a uint8 ``(800, 1200, 3)`` NumPy array, the figure size of the reference's
+        rendering.py.  The figure is white; the board (``ccx_render``: the reference's areas, walls, door, agents and
+        grid, without text, ticks, title and legend) is drawn at :meth:`render_cell_px` and centred
+        (:meth:`render_board_origin`).  ``mode="human"`` shows that array with matplotlib when it imports and returns
+        ``None``."""
         if mode not in ("rgb_array", "human"):
             raise NotImplementedError(f"Render mode {mode} not supported")
-        raise NotImplementedError("rendering is out of scope of collectivecrossing_amd (SURVEY 2, row 9)")
+        self._upload()
+        cp = self.render_cell_px()
+        board = self._batch.render(cell_px=cp).cpu().numpy()[0]
+        frame = np.full((*self.RENDER_SIZE, 3), 255, np.uint8)
+        top, left = self.render_board_origin()
+        frame[top:top + board.shape[0], left:left + board.shape[1]] = board
+        if mode == "rgb_array":
+            return frame
+        try:
+            import matplotlib.pyplot as plt
+        except Exception:
+            return None
+        if self._window is None:
+            self._window = plt.figure(figsize=(12, 8), dpi=100)
+            self._window.figimage(frame)
+        else:
+            self._window.images[0].set_data(frame)
+        self._window.canvas.draw_idle()
+        plt.pause(0.001)
+        return None
 
     # ------------------------------------------------------------------ host views used by callers
     def _get_agent(self, agent_id) -> Agent:

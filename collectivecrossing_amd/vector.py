@@ -169,6 +169,11 @@ class VectorCollectiveCrossing:
         self._final = {}
         return out
 
+    def render(self, env_ids=None, cell_px: int = 8) -> torch.Tensor:
+        """rgb_array frames of the current state, ``torch.uint8 [R, H*cell_px, W*cell_px, 3]`` on the device
+        (:meth:`BatchedCollectiveCrossing.render`)."""
+        return self.batch.render(env_ids, cell_px)
+
     def done_mask(self) -> torch.Tensor:
         """u8 [E]: envs whose last step raised ``__all__`` terminated or truncated."""
         if self.last is None:

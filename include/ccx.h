@@ -137,6 +137,54 @@ typedef struct ccx_rollout_out {
 int ccx_expand_observations(ccx_handle* h, const float* obs_compact /* [rows][N][4] */, int64_t rows,
                             float* obs /* [rows][N][L] */);
 
+/*
+ * CCX_RENDER -- rgb_array frames of the board, the picture of the reference's draw_matplotlib (rendering.py) drawn with
+ * integer arithmetic (the same geometry, palette, alpha values and layer order; not matplotlib's anti-aliased pixels).
+ *   Frame of cell size cp = cell_px (1..64): H*cp rows x W*cp columns, HWC RGB u8, covering the axes [0, W] x [0, H];
+ *   row 0 is the top (y = H).  The centre of pixel (r, c) is X = (c + 1/2)/cp, Y = H - (r + 1/2)/cp; in HALF-PIXEL
+ *   units u = 2c + 1 = 2cp X and v = 2cp H - 2r - 1 = 2cp Y every test below is exact.
+ *   Blend: alpha byte a = round(255 alpha) (0.3 -> 77, 0.5 -> 128, 0.7 -> 179, 0.8 -> 204, 0.9 -> 230);
+ *   out = (a src + (255 - a) dst + 127) / 255 per channel, integer division, one layer after another.
+ *   A rectangle [x0, x1) x [y0, y1) covers the pixels with 2cp x0 <= u < 2cp x1 and 2cp y0 <= v < 2cp y1.  Layers, in the
+ *   reference's draw order:
+ *     1. background #f8f9fa;
+ *     2. tram area #e3f2fd a 179: [tram_left, tram_right + 1) x [division_y, H);
+ *     3. waiting area #fff3e0 a 179: [0, W) x [0, division_y);
+ *     4. exit row #f44336 a 204: [0, W) x [exiting_dest_y, +1), only when exiting_dest_y < division_y;
+ *     5. seats row #2196f3 a 204: [tram_left, tram_right + 1) x [y_s, +1), y_s = boarding_dest_y, or H - 1 when
+ *        boarding_dest_y == H; only when boarding_dest_y >= division_y;
+ *     6. walls #424242 a 230, one layer (the union of the pieces, blended once), t = max(1, (cp + 5) / 10) pixels thick
+ *        (0.1 cell rounded, never thinner than 1 px).  Snapping: a wall on the line x = k takes the t columns from
+ *        cp k - t/2, a wall on the line y = division_y the t rows from cp (H - division_y) - t/2, each run shifted
+ *        inside the frame where it would leave it.  Pieces: vertical walls on x = tram_left and x = tram_right + 1 in
+ *        the rows above division_y (r < cp (H - division_y)); horizontal wall rows over [tram_left, door_left + 1/2)
+ *        when door_left > tram_left and over [door_right - 1/2, tram_right + 1) when door_right < tram_right;
+ *     7. door interior #90caf9 a 204: [door_left + 1/2, door_right - 1/2) x [division_y, +1), when
+ *        door_right - door_left - 1 > 0;
+ *     8. agents, every slot whatever its flags (the reference draws all of env._agents), in slot order (boarding
+ *        first): three concentric discs on the GRID POINT (x, y), k = 4, 3, 2 (radius k/10) with a 77, 128, 204, face
+ *        #f44336 boarding / #2196f3 exiting.  With dx = u - 2cp x, dy = v - 2cp y the pixel is inside disc k iff
+ *        25 (dx^2 + dy^2) <= k^2 cp^2, and takes the edge colour #8b0000 / #00008b (same alpha) iff it is inside and
+ *        k cp <= 10 or 25 (dx^2 + dy^2) > (k cp - 10)^2 (a 1-px ring).  Discs are clipped to the frame;
+ *     9. grid lines #808080 a 179, only when cp >= 4: columns c with c % cp == 0 or c == W cp - 1, rows r with
+ *        r % cp == 0 or r == H cp - 1 (1-px lines at the integer coordinates, the lines x = W / y = 0 on the last
+ *        column / row), above the agents (matplotlib's axisbelow = 'line').
+ *   Left out: text labels, agent numbers, title, ticks and legend.
+ *
+ * ccx_render: one frame per row of env_ids (device i32 [rows]; NULL = all E envs, rows == E) from the handle's current
+ *   state.  An id outside [0, E) gives a frame of the static layers only (no agents).
+ * ccx_render_compact: one frame per compact row (CCX_OBS_COMPACT, f32 [rows][N][4], e.g. a [K][E][N][4] trajectory);
+ *   type != 0 draws an exiting agent; an agent whose (x, y) lies outside [0, W] x [0, H] is not drawn, others are
+ *   truncated to integers.
+ * frames: device u8 [rows][H cp][W cp][3], 16-byte aligned.  Both only launch on the handle's stream (no host sync, no
+ * allocation: they capture into a HIP graph after ccx_step).  CCX_EINVAL for tiny frames whose agents do not fit a
+ * workgroup's LDS (a few agents per pixel); a larger cell_px renders them.
+ */
+int ccx_render(ccx_handle* h, const int32_t* env_ids /* [rows] or NULL = all E */, int64_t rows, int cell_px,
+               uint8_t* frames /* [rows][H*cell_px][W*cell_px][3] */);
+int ccx_render_compact(ccx_handle* h, const float* obs_compact /* [rows][N][4] */, int64_t rows, int cell_px,
+                       uint8_t* frames);
+
 /* device-side counters accumulated by ccx_rollout (u64 each; ccx_read_counters copies to host) */
 typedef struct ccx_counters {
     uint64_t env_steps;        /* env-steps executed                                      */
