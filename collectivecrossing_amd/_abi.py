@@ -105,6 +105,8 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_render": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "ccx_render_compact": (C.c_int, [_H, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "ccx_step": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.POINTER(CcxStepOut)]),
+    "ccx_step_begin": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "ccx_step_finish": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(CcxStepOut), C.c_void_p, C.c_int32]),
     "ccx_rollout": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                               C.POINTER(CcxRolloutOut)]),
     "ccx_rollout_policy": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CcxRolloutOut),

@@ -12,6 +12,7 @@ reference is layered on top of this class in :mod:`.env`.
 
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import json
 import os
@@ -24,7 +25,7 @@ import torch
 from . import _abi
 from ._lib import check, load
 from .configs import CollectiveCrossingConfig
-from .params import agent_ids, lower_config, position_only_tables
+from .params import agent_ids, array_form_strategies, lower_config, position_only_tables
 from .reset import build_reset_pool, seeded_positions
 
 
@@ -37,6 +38,7 @@ class StepResult:
     agent_flags: torch.Tensor  # u8 [E, N]  (_abi.AF_*)
     env_flags: torch.Tensor   # u8 [E]     (_abi.EF_*)
     obs_compact: torch.Tensor | None = None   # f32 [E, N, 4]  (x, y, type, active), CCX_OBS_COMPACT
+    term_present: torch.Tensor | None = None  # u8 [E, N]: 1 where terminateds[id] exists (step_finish / array-form strategies)
 
 
 @dataclass
@@ -46,6 +48,7 @@ class RolloutResult:
     agent_flags: torch.Tensor | None  # u8 [K, E, N]
     env_flags: torch.Tensor | None    # u8 [K, E]
     obs_compact: torch.Tensor | None = None   # f32 [K, E, N, 4], CCX_OBS_COMPACT
+    term_present: torch.Tensor | None = None  # u8 [K, E, N]: batches with array-form strategies only
 
 
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
@@ -67,8 +70,13 @@ class BatchedCollectiveCrossing:
         self._lib = load()
         self.config = config
         # (position-only user strategies -- strategies.RewardFunction.position_only -- run inside the kernels as tables)
-        self.params = lower_config(config, allow_position_only=True)
+        # (array-form user strategies -- strategies.ARRAY_METHODS -- run between the halves of the split step)
+        self.params = lower_config(config, allow_position_only=True, allow_array_form=True)
         self._user_tables = position_only_tables(config)
+        self._array_strategies = array_form_strategies(config)
+        self._view = None
+        self._finish_cache: dict = {}
+        self._term_present: torch.Tensor | None = None
         self.num_envs = int(num_envs)
         self.num_agents = self.params.num_agents
         self.obs_len = 6 + 4 * self.num_agents
@@ -263,6 +271,8 @@ class BatchedCollectiveCrossing:
         return out
 
     def step(self, actions, order=None, want_obs: bool = True, want_compact: bool = False) -> StepResult:
+        if self._array_strategies:
+            return self._step_array(actions, order, want_obs, want_compact)
         E, N = self.num_envs, self.num_agents
         a = self._as_dev_u8(actions, (E, N))
         o = None if order is None else self._as_dev_u8(order, (E, N))
@@ -286,6 +296,150 @@ class BatchedCollectiveCrossing:
             self._step_out_cache[key] = cached
         check(self._lib.ccx_step(self._h, a.data_ptr(), None if o is None else o.data_ptr(), cached[1]))
         return cached[2]
+
+    # ------------------------------------------------------------------ the split step / array-form strategies
+    @property
+    def has_array_strategies(self) -> bool:
+        """The config names user strategy classes that run in array form: ``step`` goes begin -> their batched methods ->
+        finish (``ccx_step_begin`` / ``ccx_step_finish``)."""
+        return bool(self._array_strategies)
+
+    def strategy_view(self):
+        """:class:`strategies.StrategyView` over the handle's own state (zero-copy; valid for the life of the batch).  The
+        flag arrays are the state's bytes seen as ``torch.bool``: they hold 0 / 1 only (the kernels write nothing else and
+        ``set_state`` refuses other values, include/ccx.h: ccx_set_state_host)."""
+        if self._view is None:
+            from .strategies import StrategyView
+            st = _abi.CcxState()
+            check(self._lib.ccx_state_view(self._h, C.byref(st)))
+            E, N = self.num_envs, self.num_agents
+            en = E * N
+
+            def dev(ptr, count, typestr, dtype, shape):
+                return torch.as_tensor(_CudaArrayView(ptr, count, typestr), device=self.device).view(dtype).view(shape)
+
+            self._view = StrategyView(
+                self.config, dev(st.x, en, "<i4", torch.int32, (E, N)), dev(st.y, en, "<i4", torch.int32, (E, N)),
+                dev(st.active, en, "|u1", torch.bool, (E, N)), dev(st.terminated, en, "|u1", torch.bool, (E, N)),
+                dev(st.truncated, en, "|u1", torch.bool, (E, N)), dev(st.step_count, E, "<i4", torch.int32, (E,)))
+        return self._view
+
+    def step_begin(self, actions, order=None) -> None:
+        """First half of ``step`` (``ccx_step_begin``, collectivecrossing.py:188-212): the step counter, the ordered moves,
+        deactivation on arrival.  No flag changes and nothing is written out; :meth:`strategy_view` shows the result."""
+        E, N = self.num_envs, self.num_agents
+        a = self._as_dev_u8(actions, (E, N))
+        o = None if order is None else self._as_dev_u8(order, (E, N))
+        check(self._lib.ccx_step_begin(self._h, a.data_ptr(), None if o is None else o.data_ptr()))
+
+    def _user_array(self, name: str, t, dtypes, to_dtype):
+        """A caller's reward / terminated / truncated array for ``step_finish``: a device tensor [E, N] of the C type."""
+        if t is None:
+            return None
+        E, N = self.num_envs, self.num_agents
+        if not isinstance(t, torch.Tensor):
+            t = torch.as_tensor(np.asarray(t))
+        if t.dtype not in dtypes:
+            raise TypeError(f"{name} must be one of {[str(d) for d in dtypes]}, got {t.dtype}")
+        if tuple(t.shape) != (E, N):
+            raise TypeError(f"{name} must have shape {(E, N)}, got {tuple(t.shape)}")
+        t = t.to(self.device).contiguous()
+        if t.dtype is torch.bool:
+            t = t.to(to_dtype) if to_dtype is torch.int8 else t.view(torch.uint8)
+        self._order_after_current_stream(t)
+        return t
+
+    def step_finish(self, reward=None, terminated=None, truncated=None, want_obs: bool = True, want_compact: bool = False,
+                    auto_reset: bool = False) -> StepResult:
+        """Second half of ``step`` (``ccx_step_finish``, collectivecrossing.py:214-259) with the caller's arrays in place of
+        the strategies: ``reward`` f64 [E, N], ``terminated`` bool or int8 [E, N] (-1 = no ``terminateds[id]`` entry),
+        ``truncated`` bool or uint8 [E, N]; ``None`` = the handle's built-in rule.  Reward and truncation values count
+        where the agent was live before the step.  ``begin`` + ``finish()`` is ``step``.  ``auto_reset`` restarts envs
+        whose step raised ``__all__`` from the reset pool (``EF_RESET``), as ``rollout`` does.
+
+        On a batch whose config names array-form classes, an argument left ``None`` is filled by the config's own class of
+        that kind (:meth:`run_array_strategies`), never by the stand-in mode the handle was built with: ``step_begin`` +
+        ``step_finish()`` is ``step`` there too."""
+        r = self._user_array("reward", reward, (torch.float64,), None)
+        t = self._user_array("terminated", terminated, (torch.bool, torch.int8), torch.int8)
+        u = self._user_array("truncated", truncated, (torch.bool, torch.uint8), torch.uint8)
+        if self._array_strategies:
+            kinds = [k for k, v in (("reward", r), ("termination", t), ("truncation", u)) if v is None]
+            own = self.run_array_strategies(kinds)
+            r, t, u = (v if v is not None else o for v, o in zip((r, t, u), own))
+        return self._finish(r, t, u, want_obs, want_compact, auto_reset)
+
+    def _finish(self, r, t, u, want_obs, want_compact, auto_reset) -> StepResult:
+        E, N = self.num_envs, self.num_agents
+        key = (bool(want_obs), bool(want_compact))
+        cached = self._finish_cache.get(key)
+        if cached is None:
+            if self._step_bufs is None:
+                self._step_bufs = StepResult(self._new((E, N, self.obs_len), torch.float32), self._new((E, N), torch.float64),
+                                             self._new((E, N), torch.uint8), self._new((E,), torch.uint8))
+            b = self._step_bufs
+            if want_compact and b.obs_compact is None:
+                b.obs_compact = self._new((E, N, 4), torch.float32)
+            if self._term_present is None:
+                self._term_present = self._new((E, N), torch.uint8)
+            so = _abi.CcxStepOut(_ptr(b.obs if want_obs else None).value, _ptr(b.reward).value, _ptr(b.agent_flags).value,
+                                 _ptr(b.env_flags).value, _ptr(b.obs_compact if want_compact else None).value)
+            cached = (so, C.byref(so), StepResult(b.obs if want_obs else None, b.reward, b.agent_flags, b.env_flags,
+                                                  b.obs_compact if want_compact else None, self._term_present))
+            self._finish_cache[key] = cached
+        check(self._lib.ccx_step_finish(self._h, _ptr(r), _ptr(t), _ptr(u), cached[1], _ptr(self._term_present),
+                                        int(bool(auto_reset))))
+        return cached[2]
+
+    def run_array_strategies(self, kinds=("reward", "termination", "truncation")):
+        """The config's array-form classes on the state ``begin`` left: ``(reward, terminated, truncated)`` device tensors
+        in the C types of ``ccx_step_finish``, ``None`` where the strategy is built-in (or its kind is not in ``kinds``).
+        Runs on the handle's stream."""
+        from .strategies import ARRAY_METHODS, check_batch_result
+        view = self.strategy_view()
+        out = []
+        other = torch._C._cuda_getCurrentRawStream(self.device.index) != self._stream_raw
+        ctx = torch.cuda.stream(self._stream) if other else contextlib.nullcontext()
+        with ctx:
+            for kind in ("reward", "termination", "truncation"):
+                fn = self._array_strategies.get(kind) if kind in kinds else None
+                out.append(None if fn is None else check_batch_result(kind, fn, getattr(fn, ARRAY_METHODS[kind])(view), view))
+        return out
+
+    def _step_array(self, actions, order, want_obs, want_compact, auto_reset: bool = False) -> StepResult:
+        self.step_begin(actions, order)
+        r, t, u = self.run_array_strategies()
+        return self._finish(r, t, u, want_obs, want_compact, auto_reset)
+
+    def _finish_into(self, r, t, u, out: "RolloutResult | None", s: int, auto_reset: bool) -> None:
+        fields = ("obs", "reward", "agent_flags", "env_flags", "obs_compact", "term_present")
+        ptrs = [_ptr(None if out is None or getattr(out, f) is None else getattr(out, f)[s]) for f in fields]
+        so = _abi.CcxStepOut(*(p.value for p in ptrs[:5]))
+        check(self._lib.ccx_step_finish(self._h, _ptr(r), _ptr(t), _ptr(u), C.byref(so), ptrs[5], int(bool(auto_reset))))
+
+    def _rollout_array(self, K, actions, order, policy, auto_reset, out, want_traj, want_obs, want_compact, actions_out):
+        """``rollout`` / ``rollout_policy`` of a batch with array-form strategies: the split step once per tick (three
+        launches plus the user's tensor code per step: launch-bound, not the fused kernel's speed).  A result allocated
+        here carries ``term_present``; a caller's own ``out`` gets it only if its ``term_present`` is set; without a
+        trajectory (``want_traj=False``) nothing is written out."""
+        E, N = self.num_envs, self.num_agents
+        if auto_reset and self._pool is None:
+            raise ValueError("auto_reset needs a reset pool (set_reset_pool / make_reset_pool)")
+        if out is None and want_traj:
+            out = self.alloc_rollout(K, want_obs, want_compact)
+            out.term_present = self._new((K, E, N), torch.uint8)
+        row_align = 16 if N % 2 == 0 else 8       # (odd agent counts write the rows in 8-byte units)
+        if out is not None and out.obs is not None and K > 1 and (E * N * self.obs_len * 4) % row_align:
+            raise ValueError(f"{E} envs x {N} agents: a step's observation rows are not a multiple of {row_align} bytes")
+        for s in range(K):
+            if policy is None:
+                self.step_begin(actions[s], None if order is None else order[s])
+            else:
+                a = self.policy_actions(policy, out=None if actions_out is None else actions_out[s])
+                self.step_begin(a)
+            r, t, u = self.run_array_strategies()
+            self._finish_into(r, t, u, out, s, auto_reset)
+        return out
 
     def rows_alignment(self) -> int:
         """Smallest batch-size multiple for which one env-step's slab of observation rows ([E][N][L] floats) is a whole number
@@ -394,11 +548,15 @@ class BatchedCollectiveCrossing:
     def rollout(self, actions, order=None, auto_reset: bool = False,
                 out: RolloutResult | None = None, want_obs: bool = True,
                 want_traj: bool = True, want_compact: bool = False) -> RolloutResult | None:
-        """K fused steps (``ccx_rollout``); ``actions`` u8 [K, E, N] on the device."""
+        """K fused steps (``ccx_rollout``); ``actions`` u8 [K, E, N] on the device.  A batch with array-form user
+        strategies runs the split step once per tick instead (launch-bound: three launches plus the user's tensor code per
+        step) into the same preallocated result, with ``term_present`` filled."""
         K = int(actions.shape[0])
         E, N = self.num_envs, self.num_agents
         a = self._as_dev_u8(actions, (K, E, N))
         o = None if order is None else self._as_dev_u8(order, (K, E, N))
+        if self._array_strategies:
+            return self._rollout_array(K, a, o, None, auto_reset, out, want_traj, want_obs, want_compact, None)
         if out is None and want_traj:
             out = self.alloc_rollout(K, want_obs, want_compact)
         if out is not None:
@@ -416,10 +574,12 @@ class BatchedCollectiveCrossing:
         """K fused steps driven by an on-device scripted policy ("greedy" or "waiting",
         ``ccx_rollout_policy``); returns ``(RolloutResult, actions u8 [K, E, N])``."""
         K, E, N = int(num_steps), self.num_envs, self.num_agents
-        if out is None:
-            out = self.alloc_rollout(K, want_obs)
         if actions_out is None and want_actions:
             actions_out = self._new((K, E, N), torch.uint8)
+        if self._array_strategies:
+            return self._rollout_array(K, None, None, policy, auto_reset, out, True, want_obs, False, actions_out), actions_out
+        if out is None:
+            out = self.alloc_rollout(K, want_obs)
         ro = _abi.CcxRolloutOut(_ptr(out.obs).value, _ptr(out.reward).value,
                                 _ptr(out.agent_flags).value, _ptr(out.env_flags).value, _ptr(out.obs_compact).value)
         check(self._lib.ccx_rollout_policy(self._h, K, _abi.POLICIES[policy], int(bool(auto_reset)),
@@ -668,8 +828,8 @@ class BatchedCollectiveCrossing:
 class _CudaArrayView:
     """Minimal ``__cuda_array_interface__`` carrier so torch can wrap library-owned memory."""
 
-    def __init__(self, ptr: int, n: int):
-        self.__cuda_array_interface__ = {"shape": (n,), "typestr": "<i8", "data": (ptr, False),
+    def __init__(self, ptr: int, n: int, typestr: str = "<i8"):
+        self.__cuda_array_interface__ = {"shape": (n,), "typestr": typestr, "data": (ptr, False),
                                          "version": 3, "strides": None}
 
 

@@ -1121,6 +1121,50 @@ int ccx_step(ccx_handle* h, const uint8_t* actions, const uint8_t* order, const 
     return run_rollout(h, 1, actions, order, 0, ko);
 }
 
+int ccx_step_begin(ccx_handle* h, const uint8_t* actions, const uint8_t* order) {
+    if (!h || !actions) return fail(CCX_EINVAL, "NULL argument");
+    CCX_HIP(hipSetDevice(h->device));
+    if (h->check_inputs) {
+        hipError_t ce = ccx::launch_check_inputs(h->stream, actions, order, (size_t)h->E, h->N, h->input_errors);
+        if (ce != hipSuccess) return fail(CCX_EHIP, "input check kernel launch failed: %s", hipGetErrorString(ce));
+    }
+    int rc = begin_timed(h);
+    if (rc) return rc;
+    hipError_t e = ccx::launch_step_begin(h->stream, h->kp, h->st, ceil_log2(h->N), actions, order, h->counters);
+    if (e != hipSuccess) return fail(CCX_EHIP, "step_begin kernel launch failed: %s", hipGetErrorString(e));
+    return end_timed(h);
+}
+
+int ccx_step_finish(ccx_handle* h, const double* reward, const int8_t* terminated, const uint8_t* truncated,
+                    const ccx_step_out* out, uint8_t* term_present, int32_t auto_reset) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (auto_reset && (!h->pool || h->pool_size <= 0))
+        return fail(CCX_EINVAL, "auto_reset needs a reset pool (ccx_set_reset_pool)");
+    ccx::KOut ko{};
+    if (out) {
+        ko.obs = out->obs;
+        ko.reward = out->reward;
+        ko.agent_flags = out->agent_flags;
+        ko.env_flags = out->env_flags;
+        ko.obs_compact = out->obs_compact;
+    }
+    // (odd agent counts write the rows in 8-byte units: csrc/ccx_split_step.hip, PAIR = false)
+    const uintptr_t obs_align = (h->N % 2) == 0 ? 15u : 7u;
+    if (ko.obs && (reinterpret_cast<uintptr_t>(ko.obs) & obs_align))
+        return fail(CCX_EINVAL, "obs buffer must be %d-byte aligned", (int)obs_align + 1);
+    if ((ko.reward && (reinterpret_cast<uintptr_t>(ko.reward) & 7u)) || (reward && (reinterpret_cast<uintptr_t>(reward) & 7u)))
+        return fail(CCX_EINVAL, "reward buffers must be 8-byte aligned");
+    if (ko.obs_compact && (reinterpret_cast<uintptr_t>(ko.obs_compact) & 15u))
+        return fail(CCX_EINVAL, "obs_compact buffer must be 16-byte aligned");
+    CCX_HIP(hipSetDevice(h->device));
+    int rc = begin_timed(h);
+    if (rc) return rc;
+    hipError_t e = ccx::launch_step_finish(h->shape, h->stream, h->kp, h->st, h->cell_info, reward, terminated, truncated, ko,
+                                           term_present, auto_reset ? 1 : 0, h->pool, h->counters);
+    if (e != hipSuccess) return fail(CCX_EHIP, "step_finish kernel launch failed: %s", hipGetErrorString(e));
+    return end_timed(h);
+}
+
 int ccx_rollout(ccx_handle* h, int32_t num_steps, const uint8_t* actions, const uint8_t* order,
                 int32_t auto_reset, const ccx_rollout_out* out) {
     if (!h || !actions) return fail(CCX_EINVAL, "NULL argument");

@@ -221,6 +221,15 @@ hipError_t launch_step(const StepShape& ss, hipStream_t stream, const KParams& p
                        const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K, int auto_reset,
                        const uint8_t* pool, const KOut& out, unsigned long long* counters);
 
+// the split step (ccx_split_step.hip): collectivecrossing.py:188-212, then :214-259 with the caller's reward / terminated /
+// truncated arrays (null = the handle's built-in rule); finish takes the lane layout of the observe kernel (ls, p)
+hipError_t launch_step_begin(hipStream_t stream, const KParams& p, const KState& st, int glog, const uint8_t* actions,
+                             const uint8_t* order, unsigned long long* counters);
+hipError_t launch_step_finish(const LaunchShape& ls, hipStream_t stream, const KParams& p, const KState& st,
+                              const unsigned long long* cell_info, const double* reward, const int8_t* terminated,
+                              const uint8_t* truncated, const KOut& out, uint8_t* term_present, int auto_reset,
+                              const uint8_t* pool, unsigned long long* counters);
+
 hipError_t launch_rollout(const LaunchShape& ls, hipStream_t stream, const KParams& p,
                           const KState& st, const unsigned long long* cell_info,
                           const uint8_t* actions, const uint8_t* order, int K,

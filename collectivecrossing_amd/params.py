@@ -47,12 +47,18 @@ def _user_strategy(kind: str, name: str):
     return table.get(name)
 
 
-def lower_config(config: CollectiveCrossingConfig, *, allow_position_only: bool = False) -> CcxParams:
+def lower_config(config: CollectiveCrossingConfig, *, allow_position_only: bool = False,
+                 allow_array_form: bool = False) -> CcxParams:
     """Config -> ``ccx_params`` (what ``CollectiveCrossingEnv.__init__`` resolves at :59-78).
 
     ``allow_position_only``: a registered user reward / terminated class that declares ``position_only = True`` is
     accepted -- the params carry a built-in stand-in for it and the caller installs the class's table
-    (:func:`position_only_tables`); any other user class keeps raising, with a message that names the single-env path."""
+    (:func:`position_only_tables`); any other user class keeps raising, with a message that names the single-env path.
+
+    ``allow_array_form``: a registered user reward / terminated / truncated class that defines the batched method of its
+    kind (``strategies.ARRAY_METHODS``) is accepted with a built-in stand-in mode as well; the caller runs the class
+    between the halves of the split step (:func:`array_form_strategies`).  Position-only tables win when a class offers
+    both."""
     tb = calculate_tram_boundaries(config)
     obs_name = config.observation_config.get_observation_function_name()
     if obs_name != "default":
@@ -65,10 +71,15 @@ def lower_config(config: CollectiveCrossingConfig, *, allow_position_only: bool 
     p.num_boarding, p.num_exiting = config.num_boarding_agents, config.num_exiting_agents
     p.boarding_dest_y = config.boarding_destination_area_y
     p.exiting_dest_y = config.exiting_destination_area_y
-    p.reward_mode = _mode_or_stand_in("reward", rc.get_reward_function_name(), REWARD_MODES, "constant_negative", allow_position_only)
+    p.reward_mode = _mode_or_stand_in("reward", rc.get_reward_function_name(), REWARD_MODES, "constant_negative", allow_position_only,
+                                      allow_array_form)
     p.terminated_mode = _mode_or_stand_in("termination", tc.get_terminated_function_name(), TERMINATED_MODES,
-                                          "individual_at_destination", allow_position_only)
-    p.truncated_mode = _lookup("truncation", uc.get_truncated_function_name(), TRUNCATED_MODES)
+                                          "individual_at_destination", allow_position_only, allow_array_form)
+    uname = uc.get_truncated_function_name()
+    if allow_array_form and uname not in TRUNCATED_MODES and _array_form_class("truncation", uname) is not None:
+        p.truncated_mode = TRUNCATED_MODES["max_steps"]       # stand-in: the class's batched method decides
+    else:
+        p.truncated_mode = _lookup("truncation", uname, TRUNCATED_MODES)
     p.max_steps = int(getattr(uc, "max_steps"))
     # defaults of the strategy configs that the selected strategy does not read
     p.boarding_destination_reward = float(getattr(rc, "boarding_destination_reward", 15.0))
@@ -81,7 +92,36 @@ def lower_config(config: CollectiveCrossingConfig, *, allow_position_only: bool 
     return p
 
 
-def _mode_or_stand_in(kind: str, name: str, table: dict[str, int], stand_in: str, allow_position_only: bool) -> int:
+def _array_form_class(kind: str, name: str):
+    """The registered user class behind `name` if it defines the batched method of its kind, else None."""
+    from . import strategies
+    table = {"reward": strategies.REWARD_FUNCTIONS, "termination": strategies.TERMINATED_FUNCTIONS,
+             "truncation": strategies.TRUNCATED_FUNCTIONS}[kind]
+    cls = table.get(name)
+    if cls is None or getattr(cls, "kernel_mode", None) is not None:
+        return None
+    return cls if strategies.is_array_form(cls, kind) else None
+
+
+def array_form_strategies(config: CollectiveCrossingConfig) -> dict:
+    """``{"reward" | "termination" | "truncation": strategy object}`` for the config's user classes that the batch path
+    runs in array form (an empty dict: everything is built-in or a position-only table)."""
+    out = {}
+    for kind, cfg, name in (("reward", config.reward_config, config.reward_config.get_reward_function_name()),
+                            ("termination", config.terminated_config, config.terminated_config.get_terminated_function_name()),
+                            ("truncation", config.truncated_config, config.truncated_config.get_truncated_function_name())):
+        modes = {"reward": REWARD_MODES, "termination": TERMINATED_MODES, "truncation": TRUNCATED_MODES}[kind]
+        if name in modes and (kind == "truncation" or name != "custom"):
+            continue
+        cls = _array_form_class(kind, name)
+        if cls is None or (kind != "truncation" and getattr(cls, "position_only", False)):
+            continue
+        out[kind] = cls(cfg)
+    return out
+
+
+def _mode_or_stand_in(kind: str, name: str, table: dict[str, int], stand_in: str, allow_position_only: bool,
+                      allow_array_form: bool = False) -> int:
     if name in table and name != "custom":
         return table[name]
     cls = _user_strategy(kind, name)
@@ -90,6 +130,8 @@ def _mode_or_stand_in(kind: str, name: str, table: dict[str, int], stand_in: str
     if getattr(cls, "kernel_mode", None) is not None:
         return int(cls.kernel_mode)
     if allow_position_only and getattr(cls, "position_only", False):
+        return table[stand_in]
+    if allow_array_form and _array_form_class(kind, name) is not None:
         return table[stand_in]
     raise ValueError(
         f"{kind} function '{name}' is a user-registered class ({cls.__name__}): the batched GPU path runs the built-in "

@@ -72,7 +72,11 @@ class BatchedMultiAgentEnv(_Base):
     ids (every agent of the env) and the finished episode's own five dicts (local ids) under ``infos["<e>/__final__"]``
     -- gymnasium's same-step convention, what ``VectorCollectiveCrossing.step_dicts(auto_reset=True)`` does per env;
     RLlib restarts each env when its ``__all__`` rises (examples/training_script.py:26-29, 69-86), and the flat
-    ``"__all__"`` flags stay False."""
+    ``"__all__"`` flags stay False.
+
+    Array-form user strategies (``strategies.ARRAY_METHODS``) are not supported here: the flat dicts are built from the
+    flag bytes alone and would invent ``terminateds`` entries a strategy left out.  Such a config raises ``ValueError``;
+    use :class:`VectorCollectiveCrossing` or :class:`BatchedCollectiveCrossing`."""
 
     metadata = {"render_modes": [], "render_fps": 4}
 
@@ -80,6 +84,10 @@ class BatchedMultiAgentEnv(_Base):
                  seed0: int = 0, *, _host_only: bool = False):
         # (_host_only: the id / dict plumbing without a GPU batch behind it -- CPU tests of `_encode` / `_dicts`; such an
         # object cannot reset or step)
+        from .params import array_form_strategies
+        if array_form_strategies(config):
+            raise ValueError("BatchedMultiAgentEnv does not run array-form user strategies; use VectorCollectiveCrossing "
+                             "or BatchedCollectiveCrossing (step / step_dicts)")
         self.vector = None if _host_only else VectorCollectiveCrossing(config, int(num_envs), device=device)
         self.config = config
         self.num_envs = int(num_envs)

@@ -229,3 +229,98 @@ get_reward_function = _getter("reward", REWARD_FUNCTIONS, "get_reward_function_n
 get_terminated_function = _getter("termination", TERMINATED_FUNCTIONS, "get_terminated_function_name")
 get_truncated_function = _getter("truncation", TRUNCATED_FUNCTIONS, "get_truncated_function_name")
 get_observation_function = _getter("observation", OBSERVATION_FUNCTIONS, "get_observation_function_name")
+
+
+# ------------------------------------------------------------------------------------- array-form plugins
+# A user class may define, NEXT TO its per-agent method, a batched one that evaluates every agent of every env at once on
+# torch tensors:
+#     RewardFunction.calculate_rewards_batch(self, view)          -> float64 [E, N]
+#     TerminatedFunction.calculate_terminateds_batch(self, view)  -> bool or int8 [E, N]   (int8: 1 / 0 / -1, -1 = None)
+#     TruncatedFunction.calculate_truncateds_batch(self, view)    -> bool [E, N]
+# The batched classes then run it between the two halves of the split step (ccx_step_begin / ccx_step_finish) on the
+# handle's stream -- no host synchronisation, any number of envs.  `view` shows the state AFTER the moves and the
+# deactivation of this step with the flags of BEFORE it, which is what the reference's step() hands to its strategies
+# (collectivecrossing.py:214-227).  Reward and truncation values count for agents that were live before the step only
+# (the `None` convention of every built-in class, rewards.py:64, truncateds.py:56): what the method returns elsewhere is
+# ignored.  The per-agent method stays the definition for the single-env class.
+ARRAY_METHODS = {"reward": "calculate_rewards_batch", "termination": "calculate_terminateds_batch",
+                 "truncation": "calculate_truncateds_batch"}
+
+
+def is_array_form(cls, kind: str) -> bool:
+    """Does the strategy class define the batched method of its kind?"""
+    return cls is not None and callable(getattr(cls, ARRAY_METHODS[kind], None))
+
+
+class StrategyView:
+    """What an array-form strategy sees: torch tensors over the state of E envs x N agent slots (boarding slots first),
+    the config, and the reference's predicates as tensor methods.  On a GPU batch the tensors are zero-copy views of the
+    handle's own state; CPU tensors work as well (plugins are testable without a GPU).
+
+    ``x``, ``y`` int32 [E, N]; ``active``, ``terminated``, ``truncated`` bool [E, N]; ``step_count`` int32 [E];
+    ``is_boarding`` bool [N].  Treat them as read-only."""
+
+    def __init__(self, config, x, y, active, terminated, truncated, step_count):
+        import torch
+
+        from .params import calculate_tram_boundaries
+        self.config = config
+        self.x, self.y = x, y
+        self.active, self.terminated, self.truncated = active, terminated, truncated
+        self.step_count = step_count
+        E, N = (int(v) for v in x.shape)
+        nb, ne = config.num_boarding_agents, config.num_exiting_agents
+        if N != nb + ne:
+            raise ValueError(f"x has {N} agent slots, the config {nb + ne}")
+        for name, t, dt, shape in (("x", x, torch.int32, (E, N)), ("y", y, torch.int32, (E, N)),
+                                   ("active", active, torch.bool, (E, N)), ("terminated", terminated, torch.bool, (E, N)),
+                                   ("truncated", truncated, torch.bool, (E, N)), ("step_count", step_count, torch.int32, (E,))):
+            if t.dtype is not dt or tuple(t.shape) != shape or t.device != x.device:
+                raise TypeError(f"StrategyView.{name}: expected {dt} {shape} on {x.device}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+        self.num_envs, self.num_agents = E, N
+        self.device = x.device
+        tb = calculate_tram_boundaries(config)
+        self.tram_left, self.tram_right = tb.tram_left, tb.tram_right
+        self.tram_door_left, self.tram_door_right = tb.tram_door_left, tb.tram_door_right
+        self.is_boarding = torch.arange(N, device=x.device) < nb
+        self._dest_y = torch.where(self.is_boarding, config.boarding_destination_area_y,
+                                   config.exiting_destination_area_y).to(torch.int32)
+
+    @property
+    def live(self):
+        """Not terminated and not truncated before this step: the agents rewards / truncations are handed out for."""
+        return ~(self.terminated | self.truncated)
+
+    # the reference's predicates (collectivecrossing.py:551-563, 663-683), bit-equal to the CCX_AF_* flag bits
+    def in_tram_area(self):
+        return (self.y >= self.config.division_y) & (self.x >= self.tram_left) & (self.x <= self.tram_right)
+
+    def at_door(self):
+        return (self.y == self.config.division_y) & ((self.x == self.tram_door_left - 1) | (self.x == self.tram_door_right + 1))
+
+    def at_destination(self):
+        return self.y == self._dest_y
+
+    def in_exiting_destination_area(self):
+        return self.y == self.config.exiting_destination_area_y
+
+
+def check_batch_result(kind: str, fn, value, view: StrategyView):
+    """Shape / dtype / device check of what an array-form method returned (host-side, no synchronisation); returns the
+    tensor in the form ccx_step_finish reads: f64 rewards, int8 terminateds (1 / 0 / -1), uint8 truncateds."""
+    import torch
+    what = f"{type(fn).__name__}.{ARRAY_METHODS[kind]}"
+    shape = (view.num_envs, view.num_agents)
+    allowed = {"reward": (torch.float64,), "termination": (torch.bool, torch.int8), "truncation": (torch.bool,)}[kind]
+    if not isinstance(value, torch.Tensor):
+        raise TypeError(f"{what} must return a torch.Tensor, got {type(value).__name__}")
+    if value.dtype not in allowed:
+        raise TypeError(f"{what} must return {' or '.join(str(d) for d in allowed)}, got {value.dtype}")
+    if tuple(value.shape) != shape:
+        raise TypeError(f"{what} must return shape {shape}, got {tuple(value.shape)}")
+    if value.device != view.device:
+        raise TypeError(f"{what} must return a tensor on {view.device}, got {value.device}")
+    value = value.contiguous()
+    if value.dtype is torch.bool:
+        value = value.to(torch.int8) if kind == "termination" else value.view(torch.uint8)
+    return value

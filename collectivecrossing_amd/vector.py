@@ -134,6 +134,13 @@ class VectorCollectiveCrossing:
         # envs restarted by step_dicts(auto_reset=True) after the last step: their rows in `last.obs` are the NEW
         # episode's first observations and every agent's row counts as handed out (policy_inputs' mask)
         self._restarted = torch.zeros((E,), dtype=torch.bool, device=dev)
+        # array-form user strategies (strategies.ARRAY_METHODS): which terminateds[id] entries exist (the strategy may
+        # return None), device + pinned host copy next to the main buffer
+        self._tp_dev = self._tp_host = None
+        if self.batch.has_array_strategies:
+            self._tp_dev = torch.ones((E, N), dtype=torch.uint8, device=dev)
+            self._tp_host = torch.ones((E, N), dtype=torch.uint8).pin_memory()
+            self._out.term_present = self._tp_dev
 
     # ------------------------------------------------------------------ batch API (device)
     def reset(self, seeds, env_mask=None) -> torch.Tensor:
@@ -160,7 +167,13 @@ class VectorCollectiveCrossing:
                              out.env_flags.data_ptr())
         import ctypes as C
         from ._lib import check
-        check(b._lib.ccx_step(b._h, C.c_void_p(a.data_ptr()), C.c_void_p(None if o is None else o.data_ptr()), C.byref(so)))
+        if b.has_array_strategies:      # begin -> the user's batched methods -> finish, all on the handle's stream
+            b.step_begin(a, o)
+            r, t, u = b.run_array_strategies()
+            check(b._lib.ccx_step_finish(b._h, *(C.c_void_p(None if v is None else v.data_ptr()) for v in (r, t, u)),
+                                         C.byref(so), C.c_void_p(self._tp_dev.data_ptr()), 0))
+        else:
+            check(b._lib.ccx_step(b._h, C.c_void_p(a.data_ptr()), C.c_void_p(None if o is None else o.data_ptr()), C.byref(so)))
         self.last = out
         with torch.cuda.stream(b._stream):
             self._done |= (out.agent_flags & (_abi.AF_TERMINATED | _abi.AF_TRUNCATED)) != 0
@@ -264,6 +277,8 @@ class VectorCollectiveCrossing:
             raise RuntimeError("no step yet")
         with torch.cuda.stream(self.batch._stream):
             self._host.copy_(self._dev, non_blocking=True)
+            if self._tp_dev is not None:
+                self._tp_host.copy_(self._tp_dev, non_blocking=True)
             self._copied.record(self.batch._stream)
         self._copied.synchronize()
         self._host_valid = True
@@ -275,7 +290,12 @@ class VectorCollectiveCrossing:
         return self._done_host
 
     def _decode(self, e: int):
-        return decode_step(self.agent_ids, self._h_obs[e], self._h_rew[e], self._h_af[e], int(self._h_ef[e]), self._types)
+        dicts = decode_step(self.agent_ids, self._h_obs[e], self._h_rew[e], self._h_af[e], int(self._h_ef[e]), self._types)
+        if self._tp_host is not None:                  # a strategy that returned None left no terminateds[id] entry
+            for aid, present in zip(self.agent_ids, self._tp_host[e].tolist()):
+                if not present:
+                    del dicts[2][aid]
+        return dicts
 
     def view(self, env_index: int):
         """The five reference dicts of env ``env_index`` for the last step."""

@@ -283,6 +283,39 @@ int ccx_observe(ccx_handle* h, float* obs /* [E][N][L] */);
 int ccx_step(ccx_handle* h, const uint8_t* actions, const uint8_t* order, const ccx_step_out* out);
 
 /*
+ * The SPLIT step: ccx_step cut at the reference's own seam, for callers that evaluate reward / termination / truncation
+ * strategies THEMSELVES as batched array code between the halves (collectivecrossing_amd/strategies.py: the array-form
+ * plugin interface; the reference accepts any registered class, rewards.py:16-38, terminateds.py:86-114,
+ * truncateds.py:64-128).  Both calls only enqueue one kernel on the handle's stream: no host synchronisation, no
+ * allocation, and they capture into a HIP graph.  They serve every config ccx_create accepts (no LDS tables).
+ *
+ * ccx_step_begin = collectivecrossing.py:188-212: step_count += 1, the ordered move resolution with exactly the semantics
+ *   of ccx_step (same actions / order contract, CCX_ACTION_ABSENT, ccx_set_check_inputs counting), deactivation on
+ *   arrival.  Writes x, y, active, step_count of the state; touches no flag and no output.
+ * ccx_step_finish = :214-259 on the state begin left.
+ *   reward      device f64 [E][N] or NULL;  terminated  device i8 [E][N]: 1 / 0 / -1 (-1 = the strategy returned None:
+ *   no dict entry) or NULL;  truncated  device u8 [E][N] or NULL.  NULL = the handle's built-in rule (including installed
+ *   position-only tables), computed in the kernel.
+ *   LIVE = not terminated and not truncated BEFORE the step (the state's flags, which begin does not touch).  Reward and
+ *   truncation entries exist exactly for LIVE agents (the convention of every built-in class); values at other agents
+ *   are ignored.  Termination entries exist where the value is not -1.
+ *   Effects, in the reference's order: terminated |= (t == 1); truncated |= (LIVE and u != 0); CCX_AF_TERMINATED /
+ *   CCX_AF_TRUNCATED = those two values of this step; CCX_AF_OBS for agents not done, or done in this step; the other
+ *   flag bits as ccx_step defines them; CCX_EF_ALL_TERMINATED = every termination entry that exists is true and at least
+ *   one exists; CCX_EF_ALL_TRUNCATED likewise over the LIVE agents; out->reward = the caller's value where LIVE, +0.0
+ *   elsewhere; obs / obs_compact rows as ccx_step writes them; env_steps, agent_steps and live_agent_steps count the step
+ *   (moves and arrivals were counted by begin).
+ *   out: as for ccx_step (NULL members are skipped); obs must be 16-byte aligned, 8-byte for an odd number of agents.  term_present (device u8 [E][N], may be NULL) receives 1 where a
+ *   termination entry exists.
+ *   auto_reset != 0: an env whose step raised either __all__ flag restarts from the reset pool after its outputs are
+ *   written: CCX_EF_RESET, episode += 1, the cursor of ccx_set_reset_pool -- what ccx_rollout does.
+ * ccx_step_begin + ccx_step_finish(NULL, NULL, NULL) leaves the state and writes the bytes ccx_step does.
+ */
+int ccx_step_begin(ccx_handle* h, const uint8_t* actions, const uint8_t* order);
+int ccx_step_finish(ccx_handle* h, const double* reward, const int8_t* terminated, const uint8_t* truncated,
+                    const ccx_step_out* out, uint8_t* term_present, int32_t auto_reset);
+
+/*
  * K fused steps in one launch (state stays in registers between steps).
  *   actions u8 [K][E][N]; order u8 [K][E][N] or NULL.
  *   auto_reset != 0: an env whose step raised terminateds["__all__"] or truncateds["__all__"] is
