@@ -29,7 +29,8 @@
 // OWN wave index.  The two kernels cut the batch into waves differently (begin: ceil_log2(N) lane groups, 64 >> glog envs
 // per wave; finish: the handle's launch shape), so a slot does not belong to one env group -- the slots are only summed.
 // A malformed move order (only reachable with invalid input, counted by ccx_set_check_inputs): a slot named twice moves
-// once, a slot index >= N names a lane without an agent and moves nothing.
+// at most once (named again after it was blocked it tries again), an order byte >= N names no agent and moves nothing
+// (whatever its low bits are).  The other envs of the wave are not affected.
 #include "ccx_rollout_dev.h"
 
 namespace ccx {
@@ -83,9 +84,11 @@ step_begin_kernel(const KParams p, const KState st, const uint8_t* __restrict__ 
     uint32_t moved = 0u;
 
     for (int k = 0; k < N; ++k) {                                // :197-202 in the order of action_dict
-        int src = gbase + k;
-        if (order) src = gbase + (int)((uint32_t)__shfl((int)o, gbase + k, 64) & (uint32_t)(G - 1));
-        const uint32_t pk = (uint32_t)__shfl((int)(prop | (ok << 16)), src, 64);
+        const uint32_t slot = order ? (uint32_t)__shfl((int)o, gbase + k, 64) : (uint32_t)k;
+        const bool named = slot < (uint32_t)N;                   // (a bad order byte >= N names no agent: nothing moves)
+        const int src = gbase + (named ? (int)slot : 0);
+        uint32_t pk = (uint32_t)__shfl((int)(prop | (ok << 16)), src, 64);
+        if (!named) pk = 0u;
         const uint32_t target = pk & 0xFFFFu;
         const bool occupied_by_me = act != 0u && cur == target && lane != src;   // :536-541: any OTHER ACTIVE agent
         const uint64_t occ = __builtin_amdgcn_ballot_w64(occupied_by_me) & gm;

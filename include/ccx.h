@@ -291,7 +291,11 @@ int ccx_step(ccx_handle* h, const uint8_t* actions, const uint8_t* order, const 
  *
  * ccx_step_begin = collectivecrossing.py:188-212: step_count += 1, the ordered move resolution with exactly the semantics
  *   of ccx_step (same actions / order contract, CCX_ACTION_ABSENT, ccx_set_check_inputs counting), deactivation on
- *   arrival.  Writes x, y, active, step_count of the state; touches no flag and no output.
+ *   arrival.  Writes x, y, active, step_count of the state; touches no flag and no output.  A move-order row that is not a
+ *   permutation is invalid input, but its effect is defined here and confined to its own env: an order byte >= N names
+ *   no agent and moves nothing, a slot named twice moves at most once (named again after it was blocked it tries again).
+ *   That rule is ccx_step_begin's alone: for such a row ccx_step and ccx_rollout step an undefined order (see
+ *   ccx_set_check_inputs, which counts the row on every path), so begin + finish and ccx_step agree for valid rows only.
  * ccx_step_finish = :214-259 on the state begin left.
  *   reward      device f64 [E][N] or NULL;  terminated  device i8 [E][N]: 1 / 0 / -1 (-1 = the strategy returned None:
  *   no dict entry) or NULL;  truncated  device u8 [E][N] or NULL.  NULL = the handle's built-in rule (including installed
