@@ -111,6 +111,8 @@ PROTOTYPES: dict[str, tuple] = {
                               C.POINTER(CcxRolloutOut)]),
     "ccx_rollout_policy": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(CcxRolloutOut),
                                      C.c_void_p]),
+    "ccx_rollout_mixed": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32,
+                                    C.POINTER(CcxRolloutOut), C.c_void_p]),
     "ccx_set_check_inputs": (C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),

@@ -62,6 +62,48 @@ def _check_cell_px(cell_px) -> int:
     return int(cell_px)
 
 
+def scripted_slot_mask(config: CollectiveCrossingConfig, scripted) -> int:
+    """Which agent slots a mixed-control step scripts, as the 64-bit mask of ``ccx_rollout_mixed`` (bit a = slot a,
+    boarding slots first).  ``scripted`` is ``"exiting"``, ``"boarding"``, ``"all"``, an iterable of slot indices and / or
+    agent ids (``"exiting_0"``), or an int mask.  Pure: needs no GPU.  Unknown ids, slots outside 0..N-1 and mask bits at
+    or above N raise ``ValueError``."""
+    nb, ne = int(config.num_boarding_agents), int(config.num_exiting_agents)
+    n = nb + ne
+    full = (1 << n) - 1
+    if isinstance(scripted, str):
+        sides = {"boarding": (1 << nb) - 1, "exiting": full & ~((1 << nb) - 1), "all": full}
+        if scripted in sides:
+            return sides[scripted]
+        scripted = [scripted]                      # (one agent id)
+    if isinstance(scripted, bool):
+        raise ValueError(f"scripted must name agent slots, got {scripted!r}")
+    if isinstance(scripted, (int, np.integer)):
+        mask = int(scripted)
+        if mask < 0 or mask & ~full:
+            raise ValueError(f"scripted mask {mask:#x} has bits outside the {n} agent slots")
+        return mask
+    try:
+        items = list(scripted)
+    except TypeError:
+        raise ValueError(f"scripted must be 'exiting', 'boarding', 'all', slot indices / agent ids or an int mask, "
+                         f"got {scripted!r}") from None
+    ids = {aid: i for i, aid in enumerate(agent_ids(config))}
+    mask = 0
+    for it in items:
+        if isinstance(it, str):
+            if it not in ids:
+                raise ValueError(f"unknown agent id {it!r}")
+            slot = ids[it]
+        elif isinstance(it, (int, np.integer)) and not isinstance(it, bool):
+            slot = int(it)
+            if not 0 <= slot < n:
+                raise ValueError(f"agent slot {slot} outside 0..{n - 1}")
+        else:
+            raise ValueError(f"scripted entries are slot indices or agent ids, got {it!r}")
+        mask |= 1 << slot
+    return mask
+
+
 class BatchedCollectiveCrossing:
     """E envs sharing one config, resident on one GPU for their whole life."""
 
@@ -276,26 +318,100 @@ class BatchedCollectiveCrossing:
         E, N = self.num_envs, self.num_agents
         a = self._as_dev_u8(actions, (E, N))
         o = None if order is None else self._as_dev_u8(order, (E, N))
-        if self._step_bufs is None:
-            self._step_bufs = StepResult(self._new((E, N, self.obs_len), torch.float32),
-                                         self._new((E, N), torch.float64),
-                                         self._new((E, N), torch.uint8), self._new((E,), torch.uint8))
-        b = self._step_bufs
-        if want_compact and b.obs_compact is None:
-            b.obs_compact = self._new((E, N, 4), torch.float32)
-        # (the output buffers are static: their ccx_step_out struct and the result tuple are built once per output
-        # selection -- this is the per-step path of a policy-in-the-loop caller, a few microseconds end to end)
-        key = (bool(want_obs), bool(want_compact))
+        cached = self._step_out(_abi.CcxStepOut, want_obs, want_compact)
+        check(self._lib.ccx_step(self._h, a.data_ptr(), None if o is None else o.data_ptr(), cached[1]))
+        return cached[2]
+
+    def _step_out(self, struct, want_obs, want_compact):
+        """(output struct, its byref, StepResult) over the env's static one-step buffers, built once per struct type and
+        output selection -- this is the per-step path of a policy-in-the-loop caller, a few microseconds end to end."""
+        key = (struct, bool(want_obs), bool(want_compact))
         cached = self._step_out_cache.get(key)
         if cached is None:
-            so = _abi.CcxStepOut(_ptr(b.obs if want_obs else None).value, _ptr(b.reward).value,
-                                 _ptr(b.agent_flags).value, _ptr(b.env_flags).value,
-                                 _ptr(b.obs_compact if want_compact else None).value)
+            E, N = self.num_envs, self.num_agents
+            if self._step_bufs is None:
+                self._step_bufs = StepResult(self._new((E, N, self.obs_len), torch.float32),
+                                             self._new((E, N), torch.float64),
+                                             self._new((E, N), torch.uint8), self._new((E,), torch.uint8))
+            b = self._step_bufs
+            if want_compact and b.obs_compact is None:
+                b.obs_compact = self._new((E, N, 4), torch.float32)
+            so = struct(_ptr(b.obs if want_obs else None).value, _ptr(b.reward).value,
+                        _ptr(b.agent_flags).value, _ptr(b.env_flags).value,
+                        _ptr(b.obs_compact if want_compact else None).value)
             cached = (so, C.byref(so), StepResult(b.obs if want_obs else None, b.reward, b.agent_flags, b.env_flags,
                                                   b.obs_compact if want_compact else None))
             self._step_out_cache[key] = cached
-        check(self._lib.ccx_step(self._h, a.data_ptr(), None if o is None else o.data_ptr(), cached[1]))
+        return cached
+
+    # ------------------------------------------------------------------ mixed control
+    def _mixed_args(self, scripted, policy):
+        if self._array_strategies:
+            raise NotImplementedError("mixed-control steps are not combined with array-form strategy classes (the split "
+                                      "step): use policy_actions + step on such a batch")
+        if policy not in ("greedy", "waiting"):
+            raise ValueError(f"a mixed-control step scripts 'greedy' or 'waiting', got {policy!r}")
+        return scripted_slot_mask(self.config, scripted), _abi.POLICIES[policy]
+
+    def step_mixed(self, actions, scripted, policy: str = "greedy", order=None, want_obs: bool = True,
+                   want_compact: bool = False, actions_out: torch.Tensor | None = None) -> StepResult:
+        """One step in which the ``scripted`` slots (:func:`scripted_slot_mask`) take the on-device ``policy``'s action
+        and the others the bytes of ``actions`` -- ``policy_actions`` + ``torch.where`` + ``step`` in ONE launch
+        (``ccx_rollout_mixed``).  Bytes of ``actions`` in scripted slots are ignored; ``actions`` may be ``None`` when every
+        slot is scripted; ``actions_out`` (u8 [E, N]) receives the merged actions.  Returns the views :meth:`step` returns."""
+        mask, pol = self._mixed_args(scripted, policy)
+        E, N = self.num_envs, self.num_agents
+        if actions is None and mask != (1 << N) - 1:
+            raise ValueError("actions may be None only when every slot is scripted")
+        a = None if actions is None else self._as_dev_u8(actions, (E, N))
+        o = None if order is None else self._as_dev_u8(order, (E, N))
+        if actions_out is not None:
+            self._check_actions_out(actions_out, (E, N))
+        cached = self._step_out(_abi.CcxRolloutOut, want_obs, want_compact)
+        check(self._lib.ccx_rollout_mixed(self._h, 1, pol, mask, None if a is None else a.data_ptr(),
+                                          None if o is None else o.data_ptr(), 0, cached[1],
+                                          None if actions_out is None else actions_out.data_ptr()))
         return cached[2]
+
+    def _check_actions_out(self, t, shape) -> None:
+        if not isinstance(t, torch.Tensor) or t.dtype is not torch.uint8 or t.device != self.device:
+            raise ValueError(f"actions_out must be a torch.uint8 tensor on {self.device}")
+        if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError(f"actions_out must be contiguous with shape {tuple(shape)}, got {tuple(t.shape)}")
+
+    def rollout_mixed(self, actions, scripted, policy: str = "greedy", order=None, auto_reset: bool = False,
+                      out: RolloutResult | None = None, actions_out: torch.Tensor | None = None, num_steps: int | None = None,
+                      want_obs: bool = True, want_traj: bool = True, want_compact: bool = False) -> RolloutResult | None:
+        """K mixed-control steps (``ccx_rollout_mixed``; launches of at most 16 steps): ``actions`` u8 [K, E, N], or
+        ``None`` with ``num_steps`` when every slot is scripted.  Mirrors :meth:`rollout`; ``actions_out`` (u8 [K, E, N])
+        receives the merged actions."""
+        mask, pol = self._mixed_args(scripted, policy)
+        E, N = self.num_envs, self.num_agents
+        if actions is None:
+            if mask != (1 << N) - 1:
+                raise ValueError("actions may be None only when every slot is scripted")
+            if num_steps is None:
+                raise ValueError("num_steps is needed when actions is None")
+            K, a = int(num_steps), None
+        else:
+            K = int(actions.shape[0])
+            if num_steps is not None and int(num_steps) != K:
+                raise ValueError(f"num_steps = {num_steps} but actions holds {K} steps")
+            a = self._as_dev_u8(actions, (K, E, N))
+        o = None if order is None else self._as_dev_u8(order, (K, E, N))
+        if auto_reset and self._pool is None:
+            raise ValueError("auto_reset needs a reset pool (set_reset_pool / make_reset_pool)")
+        if actions_out is not None:
+            self._check_actions_out(actions_out, (K, E, N))
+        if out is None and want_traj:
+            out = self.alloc_rollout(K, want_obs, want_compact)
+        ro = None
+        if out is not None:
+            ro = C.byref(_abi.CcxRolloutOut(_ptr(out.obs).value, _ptr(out.reward).value, _ptr(out.agent_flags).value,
+                                            _ptr(out.env_flags).value, _ptr(out.obs_compact).value))
+        check(self._lib.ccx_rollout_mixed(self._h, K, pol, mask, _ptr(a), _ptr(o), int(bool(auto_reset)), ro,
+                                          _ptr(actions_out)))
+        return out
 
     # ------------------------------------------------------------------ the split step / array-form strategies
     @property

@@ -623,7 +623,7 @@ int calibrate_pace(ccx_handle* h, float* obs, size_t obs_bytes) {
 }
 
 int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* order, int auto_reset,
-                const ccx::KOut& out, int policy = 0, uint8_t* actions_out = nullptr) {
+                const ccx::KOut& out, int policy = 0, uint8_t* actions_out = nullptr, bool inputs_checked = false) {
     // The writer waves address the small output streams (rewards, flag bytes, compact rows, chosen actions) with 32-bit
     // byte offsets from the stream's base: one launch must stay below 4 GiB per stream.  Longer rollouts are cut into
     // launches on the same stream (bit-identical: an env's trajectory does not depend on how a rollout is split).
@@ -654,7 +654,7 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
                 if (o.obs_compact) o.obs_compact += (size_t)k0 * EN * 4u;
                 const int rc = run_rollout(h, kk, actions ? actions + (size_t)k0 * EN : nullptr,
                                            order ? order + (size_t)k0 * EN : nullptr, auto_reset, o, policy,
-                                           actions_out ? actions_out + (size_t)k0 * EN : nullptr);
+                                           actions_out ? actions_out + (size_t)k0 * EN : nullptr, inputs_checked);
                 if (rc) return rc;
             }
             return CCX_OK;
@@ -669,7 +669,7 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
     CCX_HIP(hipSetDevice(h->device));
     if (K <= ccx::kStepMaxK && actions && policy == 0 && !actions_out && h->step_shape.ok && h->tun_step_kernel != 0) {
         // the short-launch kernel (ccx_step.hip): CollectiveCrossingEnv.step itself, no pacing, no controller state
-        if (h->check_inputs) {
+        if (h->check_inputs && !inputs_checked) {
             hipError_t ce = ccx::launch_check_inputs(h->stream, actions, order, (size_t)K * (size_t)h->E, h->N, h->input_errors);
             if (ce != hipSuccess) return fail(CCX_EHIP, "input check kernel launch failed: %s", hipGetErrorString(ce));
         }
@@ -730,7 +730,7 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
         }
     }
     h->kp.pace_slot = h->pace_slot;
-    if (h->check_inputs && actions) {
+    if (h->check_inputs && actions && !inputs_checked) {
         hipError_t ce = ccx::launch_check_inputs(h->stream, actions, order, (size_t)K * (size_t)h->E, h->N,
                                                  h->input_errors);
         if (ce != hipSuccess) return fail(CCX_EHIP, "input check kernel launch failed: %s", hipGetErrorString(ce));
@@ -814,6 +814,66 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
     // the kernel collected the votes for the next pace in the other slot (same condition as in the kernel)
     if (adaptive && !capturing) h->pace_slot ^= 1u;
     return end_timed(h);
+}
+
+// ---- loops that step ONE env-step per launch (the MT19937 policy loop, the unfused mixed-control step) -----------------
+ccx::KOut kout_of(const ccx_rollout_out* out) {
+    ccx::KOut ko{};
+    if (out) {
+        ko.obs = out->obs;
+        ko.reward = out->reward;
+        ko.agent_flags = out->agent_flags;
+        ko.env_flags = out->env_flags;
+        ko.obs_compact = out->obs_compact;
+    }
+    return ko;
+}
+
+// the outputs of step s of a [K][...] trajectory
+ccx::KOut kout_at(const ccx_handle* h, const ccx::KOut& ko, int s) {
+    const size_t EN = (size_t)h->E * h->N, L = (size_t)(6 + 4 * h->N);
+    ccx::KOut o = ko;
+    if (o.obs) o.obs += (size_t)s * EN * L;
+    if (o.reward) o.reward += (size_t)s * EN;
+    if (o.agent_flags) o.agent_flags += (size_t)s * EN;
+    if (o.env_flags) o.env_flags += (size_t)s * (size_t)h->E;
+    if (o.obs_compact) o.obs_compact += (size_t)s * EN * 4u;
+    return o;
+}
+
+// The scratch buffers of such a loop, allocated on first use and never inside a stream capture: one step's actions
+// (unless the caller's actions_out takes them) and, where a step's slice of the observation tensor is not 16-byte aligned
+// (E x N x L x 4 not a multiple of 16), an aligned staging slab.
+int stepwise_scratch(ccx_handle* h, bool own_actions, const ccx::KOut& ko, int num_steps, const char* what) {
+    const size_t EN = (size_t)h->E * h->N, L = (size_t)(6 + 4 * h->N);
+    const bool misaligned_steps = ko.obs && ((EN * L * sizeof(float)) & 15u) && num_steps > 1;
+    if ((own_actions && !h->stream_actions) || (misaligned_steps && !h->stream_obs)) {
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing(h->stream, &cap) != hipSuccess) (void)hipGetLastError();
+        else if (cap != hipStreamCaptureStatusNone)
+            return fail(CCX_EINVAL, "%s allocates scratch buffers on first use: run one eager call of this shape before "
+                        "capturing it into a graph", what);
+        if (own_actions && !h->stream_actions) CCX_HIP(hipMalloc(&h->stream_actions, EN));
+        if (misaligned_steps && !h->stream_obs) CCX_HIP(hipMalloc(&h->stream_obs, EN * L * sizeof(float)));
+    }
+    return CCX_OK;
+}
+
+// step s of such a loop through the ordinary step path, its observation rows staged where their slice is misaligned
+int stepwise_step(ccx_handle* h, const ccx::KOut& ko, int s, const uint8_t* acts, const uint8_t* order, int auto_reset,
+                  bool inputs_checked) {
+    const size_t EN = (size_t)h->E * h->N, L = (size_t)(6 + 4 * h->N);
+    ccx::KOut o = kout_at(h, ko, s);
+    float* const obs_dst = o.obs;
+    const bool staged = obs_dst && (reinterpret_cast<uintptr_t>(obs_dst) & 15u);
+    if (staged) {
+        if (!h->stream_obs) return fail(CCX_EINVAL, "obs buffer must be 16-byte aligned");   // (a misaligned BASE)
+        o.obs = h->stream_obs;
+    }
+    const int rc = run_rollout(h, 1, acts, order, auto_reset, o, 0, nullptr, inputs_checked);
+    if (rc) return rc;
+    if (staged) CCX_HIP(hipMemcpyAsync(obs_dst, h->stream_obs, EN * L * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    return CCX_OK;
 }
 
 }  // namespace
@@ -1203,46 +1263,90 @@ int ccx_rollout_policy(ccx_handle* h, int32_t num_steps, int32_t policy, int32_t
         // -> policy ..., each a launch on the handle's stream) instead of inside the fused one.  Meant for replaying the
         // reference's epsilon episodes action for action, not for throughput.
         CCX_HIP(hipSetDevice(h->device));
-        const size_t EN = (size_t)h->E * h->N, L = (size_t)(6 + 4 * h->N);
-        // (the loop's scratch buffers are allocated on first use: never inside a stream capture)
-        const bool misaligned_steps = ko.obs && ((EN * L * sizeof(float)) & 15u) && num_steps > 1;
-        if ((!actions_out && !h->stream_actions) || (misaligned_steps && !h->stream_obs)) {
-            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-            if (hipStreamIsCapturing(h->stream, &cap) != hipSuccess) (void)hipGetLastError();
-            else if (cap != hipStreamCaptureStatusNone)
-                return fail(CCX_EINVAL, "the stepwise policy loop allocates scratch buffers on first use: run one eager "
-                            "policy rollout of this shape before capturing it into a graph");
-            if (!actions_out && !h->stream_actions) CCX_HIP(hipMalloc(&h->stream_actions, EN));
-            if (misaligned_steps && !h->stream_obs) CCX_HIP(hipMalloc(&h->stream_obs, EN * L * sizeof(float)));
-        }
+        const size_t EN = (size_t)h->E * h->N;
+        int rc = stepwise_scratch(h, !actions_out, ko, num_steps, "the stepwise policy loop");
+        if (rc) return rc;
         for (int s = 0; s < num_steps; ++s) {
             uint8_t* acts = actions_out ? actions_out + (size_t)s * EN : h->stream_actions;
             hipError_t e = ccx::launch_policy_stream_actions(h->stream, h->kp, h->st, h->cell_info, acts, policy, h->mt_state,
                                                              h->epsilon);
             if (e != hipSuccess) return fail(CCX_EHIP, "policy kernel launch failed: %s", hipGetErrorString(e));
-            ccx::KOut o = ko;
-            if (o.obs) o.obs += (size_t)s * EN * L;
-            if (o.reward) o.reward += (size_t)s * EN;
-            if (o.agent_flags) o.agent_flags += (size_t)s * EN;
-            if (o.env_flags) o.env_flags += (size_t)s * (size_t)h->E;
-            if (o.obs_compact) o.obs_compact += (size_t)s * EN * 4u;
-            // (a step's slice of the observation tensor starts on a 16-byte boundary only if E x N x L x 4 is a multiple of
-            // 16: the others go through an aligned staging slab and a device-to-device copy)
-            float* const obs_dst = o.obs;
-            const bool staged = obs_dst && (reinterpret_cast<uintptr_t>(obs_dst) & 15u);
-            if (staged) {
-                if (!h->stream_obs) return fail(CCX_EINVAL, "obs buffer must be 16-byte aligned");   // (a misaligned BASE)
-                o.obs = h->stream_obs;
-            }
-            const int rc = run_rollout(h, 1, acts, nullptr, auto_reset ? 1 : 0, o);
+            rc = stepwise_step(h, ko, s, acts, nullptr, auto_reset ? 1 : 0, false);
             if (rc) return rc;
-            if (staged)
-                CCX_HIP(hipMemcpyAsync(obs_dst, h->stream_obs, EN * L * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
         }
         return CCX_OK;
     }
     // (grids whose occupancy tables exceed the LDS run the in-kernel policies through the all-pairs exchange: round 4)
     return run_rollout(h, num_steps, nullptr, nullptr, auto_reset ? 1 : 0, ko, policy, actions_out);
+}
+
+int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t scripted_slots,
+                      const uint8_t* actions, const uint8_t* order, int32_t auto_reset,
+                      const ccx_rollout_out* out, uint8_t* actions_out) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (num_steps < 1) return fail(CCX_EINVAL, "num_steps must be >= 1");
+    if (policy != CCX_POLICY_GREEDY && policy != CCX_POLICY_WAITING)
+        return fail(CCX_EINVAL, "a mixed-control step scripts CCX_POLICY_GREEDY or CCX_POLICY_WAITING (got policy %d)", policy);
+    const uint64_t all_slots = h->N >= 64 ? ~0ull : ((1ull << h->N) - 1ull);
+    if (scripted_slots & ~all_slots)
+        return fail(CCX_EINVAL, "scripted_slots 0x%llx names agent slots at or above N = %d",
+                    (unsigned long long)scripted_slots, h->N);
+    if (!actions && scripted_slots != all_slots)
+        return fail(CCX_EINVAL, "actions may be NULL only when scripted_slots covers all %d slots (got 0x%llx)", h->N,
+                    (unsigned long long)scripted_slots);
+    if (auto_reset && (!h->pool || h->pool_size <= 0))
+        return fail(CCX_EINVAL, "auto_reset needs a reset pool (ccx_set_reset_pool)");
+    if (h->eps_stream == CCX_EPS_STREAM_MT19937 && h->epsilon > 0.0)
+        return fail(CCX_EINVAL, "a mixed-control step cannot draw from the MT19937 exploration stream: that stream is "
+                    "sequential per env and walked by a kernel of its own (ccx_policy_actions); select "
+                    "CCX_EPS_STREAM_COUNTER or set epsilon to 0");
+    const ccx::KOut ko = kout_of(out);
+    if (ko.obs && (reinterpret_cast<uintptr_t>(ko.obs) & 15u)) return fail(CCX_EINVAL, "obs buffer must be 16-byte aligned");
+    if (ko.reward && (reinterpret_cast<uintptr_t>(ko.reward) & 7u)) return fail(CCX_EINVAL, "reward buffer must be 8-byte aligned");
+    if (ko.obs_compact && (reinterpret_cast<uintptr_t>(ko.obs_compact) & 15u))
+        return fail(CCX_EINVAL, "obs_compact buffer must be 16-byte aligned");
+    CCX_HIP(hipSetDevice(h->device));
+    const size_t EN = (size_t)h->E * h->N;
+    const bool fused = h->step_shape.ok && h->tun_step_kernel != 0;
+    // ccx_set_check_inputs: the caller's bytes outside the mask and the order rows, once, on either path
+    if (h->check_inputs && (actions || order)) {
+        hipError_t ce = ccx::launch_check_inputs(h->stream, actions, order, (size_t)num_steps * (size_t)h->E, h->N,
+                                                 h->input_errors, scripted_slots);
+        if (ce != hipSuccess) return fail(CCX_EHIP, "input check kernel launch failed: %s", hipGetErrorString(ce));
+    }
+    if (fused) {
+        // the short-launch kernel's policy instantiations (ccx_step.hip, POL): policy + merge + step in ONE launch per
+        // <= 16 steps (16 is even: every sub-launch's slice of the observation tensor stays 16-byte aligned)
+        for (int k0 = 0; k0 < num_steps; k0 += ccx::kStepMaxK) {
+            const int kk = std::min(ccx::kStepMaxK, num_steps - k0);
+            const ccx::StepPolicy pol{scripted_slots, policy, actions_out ? actions_out + (size_t)k0 * EN : nullptr};
+            int rc = begin_timed(h);
+            if (rc) return rc;
+            hipError_t e = ccx::launch_step(h->step_shape, h->stream, h->kp, h->st_slab, h->cell_info,
+                                            actions ? actions + (size_t)k0 * EN : nullptr, order ? order + (size_t)k0 * EN : nullptr,
+                                            kk, auto_reset ? 1 : 0, h->pool, kout_at(h, ko, k0), h->counters, &pol);
+            if (e != hipSuccess) return fail(CCX_EHIP, "step kernel launch failed: %s", hipGetErrorString(e));
+            rc = end_timed(h);
+            if (rc) return rc;
+        }
+        return CCX_OK;
+    }
+    // Handles whose short launches cannot use the step kernel (tables beyond the LDS, or the tunable): the composition
+    // itself, step by step on the handle's stream -- policy kernel, merge kernel, the existing step path.
+    int rc = stepwise_scratch(h, !actions_out, ko, num_steps, "the unfused mixed-control step");
+    if (rc) return rc;
+    for (int s = 0; s < num_steps; ++s) {
+        uint8_t* acts = actions_out ? actions_out + (size_t)s * EN : h->stream_actions;
+        hipError_t e = ccx::launch_greedy_actions(h->stream, h->kp, h->st, h->cell_info, acts, policy);
+        if (e != hipSuccess) return fail(CCX_EHIP, "policy kernel launch failed: %s", hipGetErrorString(e));
+        if (scripted_slots != all_slots) {
+            e = ccx::launch_merge_actions(h->stream, acts, actions + (size_t)s * EN, scripted_slots, h->N, EN);
+            if (e != hipSuccess) return fail(CCX_EHIP, "merge kernel launch failed: %s", hipGetErrorString(e));
+        }
+        rc = stepwise_step(h, ko, s, acts, order ? order + (size_t)s * EN : nullptr, auto_reset ? 1 : 0, true);
+        if (rc) return rc;
+    }
+    return CCX_OK;
 }
 
 namespace {

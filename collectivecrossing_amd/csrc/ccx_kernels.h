@@ -217,9 +217,17 @@ struct StepShape {
 };
 constexpr int kStepMaxK = 16;   // env-steps per launch of the short-launch kernel (one burst of action loads)
 size_t step_lds_bytes(int glog, int ew, int N, int cells, bool reward_table);
+// mixed control (ccx_rollout_mixed): the slots of `scripted` (bit a = slot a) take the action of the scripted policy
+// `policy` (CCX_K_POLICY_GREEDY / _WAITING, epsilon and seed from KParams) instead of the tensor's; actions_out (u8
+// [K][E][N] or null) receives the actions taken.  `actions` may be null when the mask covers every slot.
+struct StepPolicy {
+    unsigned long long scripted;
+    int policy;
+    uint8_t* actions_out;
+};
 hipError_t launch_step(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
                        const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K, int auto_reset,
-                       const uint8_t* pool, const KOut& out, unsigned long long* counters);
+                       const uint8_t* pool, const KOut& out, unsigned long long* counters, const StepPolicy* pol = nullptr);
 
 // the split step (ccx_split_step.hip): collectivecrossing.py:188-212, then :214-259 with the caller's reward / terminated /
 // truncated arrays (null = the handle's built-in rule); finish takes the lane layout of the observe kernel (ls, p)
@@ -249,8 +257,14 @@ hipError_t launch_write_probe(hipStream_t stream, void* dst, size_t bytes, int b
 
 // CCX_CHECK_INPUTS: counts action bytes outside {0..4, 255} into bad[0] and move-order rows that are not a
 // permutation of 0..N-1 into bad[1] (collectivecrossing.py:685-711), one thread per (step, env) row
+// (skip_slots: action bytes of these slots are not looked at -- the scripted slots of a mixed-control step; actions may be
+//  null when only the order rows are to be checked)
 hipError_t launch_check_inputs(hipStream_t stream, const uint8_t* actions, const uint8_t* order, size_t rows,
-                               int N, unsigned long long* bad);
+                               int N, unsigned long long* bad, unsigned long long skip_slots = 0ull);
+// dst[t] = actions[t] for the slots that are NOT in `scripted` (dst holds the policy's actions): the merge of the
+// unfused mixed-control step (grids whose tables exceed the LDS)
+hipError_t launch_merge_actions(hipStream_t stream, uint8_t* dst, const uint8_t* actions, unsigned long long scripted,
+                                int N, size_t total);
 hipError_t launch_greedy_actions(hipStream_t stream, const KParams& p, const KState& st,
                                  const unsigned long long* cell_info, uint8_t* actions, int policy);
 // the reference's own epsilon stream (ccx_policy.hip): per env numpy RandomState = MT19937 key[624] + pos, u32 [E][625]

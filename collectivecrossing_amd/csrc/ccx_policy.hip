@@ -215,12 +215,16 @@ hipError_t launch_greedy_actions(hipStream_t stream, const KParams& p, const KSt
 // call; a separate elementwise kernel so that the hot kernel carries none of it.
 // ---------------------------------------------------------------------------------------------
 __global__ void check_inputs_kernel(const uint8_t* __restrict__ actions, const uint8_t* __restrict__ order,
-                                    const size_t rows, const int N, unsigned long long* bad) {
+                                    const size_t rows, const int N, unsigned long long* bad,
+                                    const unsigned long long skip_slots) {
     const size_t r = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     uint32_t bad_a = 0, bad_o = 0;
     if (r < rows) {
-        const uint8_t* a = actions + r * (size_t)N;
-        for (int i = 0; i < N; ++i) bad_a += (a[i] > 4u && a[i] != (uint8_t)CCX_K_ABSENT) ? 1u : 0u;
+        if (actions) {   // (null: every slot is scripted, only the order rows are looked at)
+            const uint8_t* a = actions + r * (size_t)N;
+            for (int i = 0; i < N; ++i)
+                bad_a += (a[i] > 4u && a[i] != (uint8_t)CCX_K_ABSENT && !((skip_slots >> i) & 1ull)) ? 1u : 0u;
+        }
         if (order) {
             const uint8_t* o = order + r * (size_t)N;
             unsigned long long seen = 0;
@@ -243,10 +247,29 @@ __global__ void check_inputs_kernel(const uint8_t* __restrict__ actions, const u
 }
 
 hipError_t launch_check_inputs(hipStream_t stream, const uint8_t* actions, const uint8_t* order, size_t rows,
-                               int N, unsigned long long* bad) {
+                               int N, unsigned long long* bad, unsigned long long skip_slots) {
     if (rows == 0) return hipSuccess;
     const unsigned blocks = (unsigned)((rows + 255) / 256);
-    hipLaunchKernelGGL(check_inputs_kernel, dim3(blocks), dim3(256), 0, stream, actions, order, rows, N, bad);
+    hipLaunchKernelGGL(check_inputs_kernel, dim3(blocks), dim3(256), 0, stream, actions, order, rows, N, bad, skip_slots);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------
+// The merge of the UNFUSED mixed-control step (include/ccx.h: ccx_rollout_mixed on grids whose tables exceed the LDS):
+// dst holds ccx_policy_actions' bytes; the slots outside the mask take the caller's.
+// ---------------------------------------------------------------------------------------------
+__global__ void merge_actions_kernel(uint8_t* __restrict__ dst, const uint8_t* __restrict__ actions,
+                                     const unsigned long long scripted, const int N, const size_t total) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= total) return;
+    if (!((scripted >> (uint32_t)(t % (size_t)N)) & 1ull)) dst[t] = actions[t];
+}
+
+hipError_t launch_merge_actions(hipStream_t stream, uint8_t* dst, const uint8_t* actions, unsigned long long scripted,
+                                int N, size_t total) {
+    if (total == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((total + 255) / 256);
+    hipLaunchKernelGGL(merge_actions_kernel, dim3(blocks), dim3(256), 0, stream, dst, actions, scripted, N, total);
     return hipGetLastError();
 }
 

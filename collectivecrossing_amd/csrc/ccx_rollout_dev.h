@@ -74,6 +74,37 @@ template <int GLOG> __device__ __forceinline__ constexpr typename GroupMask<GLOG
     else return (T(1) << (1 << GLOG)) - T(1);
 }
 
+// The scripted policies' choice for this lane's agent from the PRE-step state in registers (greedy_policy.py:33-449,
+// waiting_policy.py:74-131; ccx_policy.hip is the same rule with one thread per agent).  `ilo` is the low word of the
+// agent's cell, `busy` the directions whose neighbour cell holds another ACTIVE agent, `asked` whether the agent is in
+// env.agents; `step` the episode's step index BEFORE this step.  Called by every lane of the wave (the waiting rule is a
+// ballot over the env's lane group); policy and eps_thr are wave-uniform.
+// (The rollout kernel's step 0 in ccx_rollout_body.inc states the same lines inline: moving it onto this helper changes the
+// register allocation of its policy instantiations, whose budgets tests/test_kernel_resources.py pins, so that belongs
+// to a change that can time them.)
+template <int GLOG, typename Geo>
+__device__ __forceinline__ uint32_t scripted_pick(const Geo& geo, int policy, bool boarding, uint32_t ilo, uint32_t asked,
+                                                  uint32_t busy, int lane, uint32_t eps_thr, uint32_t rng_lo, uint32_t rng_hi,
+                                                  uint32_t genv, uint32_t episode, uint32_t step, uint32_t slot) {
+    const uint32_t free4 = ilo & 0xFu & ~busy;
+    const uint32_t cand = greedy_candidates(geo, boarding, (int)((ilo >> 16) & 0xFFu), (int)(ilo >> 24));
+    uint32_t pick = greedy_pick(cand, free4);
+    if (policy == CCX_K_POLICY_WAITING) {
+        // waiting_policy.py:74-131: boarding agents outside the tram area wait while
+        // a live exiting agent is not on its destination row yet
+        const uint32_t pend = (boarding ? 0u : asked) & (((ilo >> 12) & 1u) ^ 1u);
+        const auto pend_bits = group_bits<GLOG>(__builtin_amdgcn_ballot_w64(pend != 0), lane);
+        if (boarding && !(ilo & kCellInTram) && pend_bits != 0) pick = 4u;
+    }
+    if (eps_thr) {
+        // epsilon-greedy (greedy_policy.py:48-59): with probability epsilon one of the VALID actions
+        // of the pre-step state, uniformly; counter-based draws (ccx_kernels.h: explore_action)
+        const uint32_t u = random_word(rng_lo, rng_hi ^ kEpsStream, genv, episode, step, slot);
+        if (u < eps_thr) pick = explore_action(u, free4);
+    }
+    return pick;
+}
+
 typedef float v4f __attribute__((ext_vector_type(4)));
 
 // Streaming stores of observation vectors (written once, never re-read by the kernel).  Cache policy

@@ -19,9 +19,14 @@
 //   * state write-back behind the last hand-off: everything drains together.
 // Tiles are smaller than the rollout's (a short launch is bound by latency, not by issue).
 //
-// Scope: actions from a tensor with or without a move order (no in-kernel policy), K <= 16 (one burst of action loads), LDS
+// Scope: actions from a tensor with or without a move order, K <= 16 (one burst of action loads), LDS
 // occupancy tables (grids whose tables do not fit take the rollout kernel: ccx_api.hip decides).  Auto-reset from the
 // pool is supported (ccx_rollout with few steps).
+// POL (ccx_rollout_mixed: mixed control): the slots of a 64-bit mask take their action from the reference's scripted
+// GreedyPolicy / WaitingPolicy (ccx_greedy.h) instead of the tensor.  Per step the sim wave publishes the active agents'
+// occupancy bits first, reads its four neighbour entries, evaluates the rule from the state in registers, selects per
+// lane between that and the loaded byte, and enters the move resolution with its occupancy bit already in the table.
+// Policy id, epsilon and the RNG words are run-time kernel arguments behind the preloaded ones.
 // The first 14 argument dwords (state slab, actions, both tables, obs, E, shape words, max_steps) are preloaded into SGPRs
 // (csrc/Makefile: -amdgpu-kernarg-preload-count=14): -0.05 us per step, measured on this kernel.
 #include "ccx_rollout_dev.h"
@@ -57,6 +62,9 @@ __device__ __forceinline__ void step_store_obs(v2f v, const char* base, uint32_t
     asm volatile("global_store_dwordx2 %0, %1, %2 " CCX_STEP_STORE_BITS ::"v"(voff), "v"(v), "s"(base) : "memory");
 }
 
+// what greedy_candidates reads of the geometry (ccx_greedy.h)
+struct GreedyGeo { int div, dc, bdy, edy; };
+
 // store iterations of a row wave whose table words / LDS reads are in flight together: 8 for small lane groups (C2: a row
 // wave has ~5 iterations), 16 for the large ones (C3 / C5: 10-11 iterations per row wave, one batch instead of two -- the
 // second batch's table words would be a memory round trip of their own)
@@ -64,7 +72,9 @@ template <int GLOG> struct RowBatch { static constexpr int value = GLOG <= 3 ? 8
 
 // K1: the launch is ONE env-step (ccx_step): one action load per lane instead of a burst of sixteen
 // ORD: the caller passed a move order (collectivecrossing.py:197: agents move in the order of `action_dict`)
-template <int GLOG, bool PAIR, bool K1, bool ORD>
+// POL: mixed control -- the slots of `scripted` are driven by the scripted policy `policy` (the trailing arguments are read
+//      by these instantiations only)
+template <int GLOG, bool PAIR, bool K1, bool ORD, bool POL = false>
 __global__ void __launch_bounds__(512)
 step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab layout
             const uint8_t* __restrict__ actions,                // u8 [K][E][N]
@@ -82,7 +92,13 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
             const int term_all, const int auto_reset,
             const double rA, const double rB, const double rC, const double rF,
             const double* __restrict__ reward_table,                   // user reward table f64 [2][cells] or null
-            const uint8_t* __restrict__ order) {                       // u8 [K][E][N]: slot of the agent that moves k-th, or null
+            const uint8_t* __restrict__ order,                         // u8 [K][E][N]: slot of the agent that moves k-th, or null
+            const unsigned long long scripted,                         // POL: bit a = slot a takes the scripted policy's action
+            const int policy,                                          // POL: CCX_K_POLICY_GREEDY / CCX_K_POLICY_WAITING
+            const uint32_t rng_lo, const uint32_t rng_hi, const uint32_t eps_thr,   // POL: epsilon draws (ccx_kernels.h: explore_action)
+            const uint32_t genv0,                                      // POL: global index of env 0 (low word)
+            const int bdy, const int edy,                              // POL: destination rows
+            uint8_t* __restrict__ actions_out) {                       // POL: u8 [K][E][N] the actions taken, or null
     using mask_t = typename GroupMask<GLOG>::type;
     constexpr int G = 1 << GLOG;
     constexpr uint32_t msz = sizeof(mask_t);
@@ -208,7 +224,21 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
     const int s_stepc = reinterpret_cast<const int32_t*>(st_base + sl.step_count)[env_ld];
     const int s_episode = reinterpret_cast<const int32_t*>(st_base + sl.episode)[env_ld];
     uint32_t araw[kActBatch];
-    if constexpr (K1) {
+    if constexpr (POL) {
+        // (a mask that covers every slot comes without a tensor: nothing is loaded, the bytes are never looked at)
+#pragma unroll
+        for (int d = 0; d < kActBatch; ++d) araw[d] = 4u;
+        if (actions != nullptr) {
+            uint32_t off = idx_ld;
+            const uint32_t lim = idx_ld + (uint32_t)(K - 1) * EN;
+#pragma unroll
+            for (int d = 0; d < (K1 ? 1 : kActBatch); ++d) {
+                araw[d] = (uint32_t)actions[off];
+                const uint32_t nx = off + EN;
+                off = nx < lim ? nx : lim;
+            }
+        }
+    } else if constexpr (K1) {
         araw[0] = (uint32_t)actions[idx_ld];
 #pragma unroll
         for (int d = 1; d < kActBatch; ++d) araw[d] = 4u;
@@ -354,9 +384,20 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
     gchar* b_af = (gchar*)agent_flags;
     gchar* b_ef = (gchar*)env_flags;
     gchar* b_cmp = (gchar*)obs_compact;
+    gchar* b_ao = (gchar*)actions_out;                                 // (POL)
+    const bool has_ao = POL && actions_out != nullptr;
+    const uint32_t sbit = POL ? (uint32_t)((scripted >> i) & 1ull) : 0u;   // my slot is scripted
+    const GreedyGeo geo{div, dc, bdy, edy};
 
-    unsigned long long acur = 0;
-    {
+    unsigned long long acur = 0, araw_hi = 0;
+    if constexpr (POL) {
+        // the caller's bytes as they are, 8 bits per step (acur: steps 0-7, araw_hi: 8-15): actions_out hands them back
+#pragma unroll
+        for (int d = 0; d < (K1 ? 1 : kActBatch); ++d) {
+            if (d < 8) acur |= (unsigned long long)(araw[d] & 0xFFu) << (8 * d);
+            else araw_hi |= (unsigned long long)(araw[d] & 0xFFu) << (8 * (d - 8));
+        }
+    } else {
         uint32_t apk[2] = {0, 0};
 #pragma unroll
         for (int d = 0; d < kActBatch; ++d) {
@@ -368,14 +409,26 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
     CCX_ST(3);
 
     for (int s = 0; s < K; ++s) {
-        const uint32_t a = (uint32_t)acur & 0xFu;
-        acur >>= 4;
+        uint32_t a, a_raw = 0;
+        if constexpr (POL) {
+            a_raw = (uint32_t)acur & 0xFFu;
+            acur = (acur >> 8) | (araw_hi << 56);
+            araw_hi >>= 8;
+            a = a_raw < 4u ? a_raw : 4u;
+        } else {
+            a = (uint32_t)acur & 0xFu;
+            acur >>= 4;
+        }
         const uint32_t tt_before = tt;
         left1 -= 1;                                                    // collectivecrossing.py:188
         // ---- 1. proposal (:371-376, 509-534): legality is bit a of the current cell's word
-        const int np8 = c8 + (int)(int16_t)(uint16_t)(lut64 >> ((a & 3u) << 4));     // (wait / absent: any neighbour, never entered -- its legality bit 4 is 0)
-        const uint32_t ok = (ilo >> a) & act;
-        const uint32_t nok = ok ^ 1u;
+        int np8 = 0;
+        uint32_t ok = 0, nok = 0;
+        if constexpr (!POL) {
+            np8 = c8 + (int)(int16_t)(uint16_t)(lut64 >> ((a & 3u) << 4));     // (wait / absent: any neighbour, never entered -- its legality bit 4 is 0)
+            ok = (ilo >> a) & act;
+            nok = ok ^ 1u;
+        }
         // ---- move rank of this agent (dict order of action_dict, collectivecrossing.py:197); identity without ORD
         int rank = i;
         uint32_t src_lane = (uint32_t)lane;            // the lane whose agent has move rank i (= my lane index in the group)
@@ -396,10 +449,35 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
         }
         // ---- 2. conflict masks from the occupancy / proposal tables (:536-541 in O(1) per agent), bits = move ranks
         const uint32_t ca = act ? tab_rel + ((uint32_t)c8 << TS) : dump_addr;
+        if constexpr (POL) {
+            // ---- 0. the scripted policy from the PRE-step state (ccx_policy.hip: the same rule, one thread per agent): the
+            //         occupancy bits go into the table first -- the move resolution below needs them there anyway -- and a
+            //         direction is free if the cell's word says the neighbour can be entered and no active agent's bit sits
+            //         on it (env._is_move_valid, collectivecrossing.py:345-369)
+            auto lds_mask_ld = [](uint32_t addr) -> mask_t { return *(__attribute__((address_space(3))) const mask_t*)(uintptr_t)addr; };
+            lds_or(ca, my_rbit);
+            wave_lds_sync();
+            const uint32_t cb = tab_rel + ((uint32_t)c8 << TS);
+            const uint32_t rowb = (uint32_t)(Wp * 8) << TS, colb = 8u << TS;
+            const mask_t o0 = lds_mask_ld(cb + colb), o1 = lds_mask_ld(cb + rowb), o2 = lds_mask_ld(cb - colb),
+                         o3 = lds_mask_ld(cb - rowb);
+            wave_lds_sync();
+            const uint32_t busy = (o0 != 0 ? 1u : 0u) | (o1 != 0 ? 2u : 0u) | (o2 != 0 ? 4u : 0u) | (o3 != 0 ? 8u : 0u);
+            const uint32_t asked = tt == 0u ? 1u : 0u;                 // the policy is asked for env.agents only
+            // (left1 has been decremented: the episode's step index BEFORE this step is max_steps_m1 - left1 - 1)
+            const uint32_t pick = scripted_pick<GLOG>(geo, policy, boarding, ilo, asked, busy, lane, eps_thr, rng_lo, rng_hi,
+                                                      genv0 + (uint32_t)env, (uint32_t)episode,
+                                                      (uint32_t)(max_steps_m1 - left1 - 1), (uint32_t)i);
+            a = sbit ? (asked ? pick : 4u) : a;
+            a_raw = sbit ? (asked ? pick : (uint32_t)CCX_K_ABSENT) : a_raw;
+            np8 = c8 + (int)(int16_t)(uint16_t)(lut64 >> ((a & 3u) << 4));
+            ok = (ilo >> a) & act;
+            nok = ok ^ 1u;
+        }
         const uint32_t ta = tab_rel + ((uint32_t)np8 << TS);
         const uint32_t qa = (ok ? ta : dump_addr) + msz;
         const unsigned long long pci = lds_cell(np8);
-        lds_or(ca, my_rbit);
+        if constexpr (!POL) lds_or(ca, my_rbit);
         lds_or(qa, my_rbit);
         wave_lds_sync();
         const mask2_t tt2 = *(__attribute__((address_space(3))) const mask2_t*)(uintptr_t)ta;
@@ -500,7 +578,11 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
             if (has_af) *(__attribute__((address_space(1))) uint8_t*)(b_af + o_af) = (uint8_t)af;
             if (has_ef && i == 0) *(__attribute__((address_space(1))) uint8_t*)(b_ef + o_ef) = (uint8_t)efw;
             if (has_cmp) *(__attribute__((address_space(1))) v4f*)(b_cmp + o_cmp) = v4f{me.x, me.y, me.z, me.w};
+            if constexpr (POL) {
+                if (has_ao) *(__attribute__((address_space(1))) uint8_t*)(b_ao + o_af) = (uint8_t)a_raw;
+            }
         }
+        if constexpr (POL) b_ao += EN;
         b_rew += (size_t)EN * 8u;
         b_af += EN;
         b_ef += (uint32_t)E;
@@ -576,16 +658,18 @@ size_t step_lds_bytes(int glog, int ew, int N, int cells, bool reward_table) {
 template <int GLOG>
 static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
                                 const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K,
-                                int auto_reset, const uint8_t* pool, const KOut& out, unsigned long long* counters) {
+                                int auto_reset, const uint8_t* pool, const KOut& out, unsigned long long* counters,
+                                const StepPolicy* pol) {
     const bool pair = (p.N % 2) == 0;
-    auto pick = [&](auto ord_c) -> const void* {
-        constexpr bool ORD = decltype(ord_c)::value;
-        return K == 1 ? (pair ? reinterpret_cast<const void*>(&step_kernel<GLOG, true, true, ORD>)
-                              : reinterpret_cast<const void*>(&step_kernel<GLOG, false, true, ORD>))
-                      : (pair ? reinterpret_cast<const void*>(&step_kernel<GLOG, true, false, ORD>)
-                              : reinterpret_cast<const void*>(&step_kernel<GLOG, false, false, ORD>));
+    auto pick = [&](auto ord_c, auto pol_c) -> const void* {
+        constexpr bool ORD = decltype(ord_c)::value, POL = decltype(pol_c)::value;
+        return K == 1 ? (pair ? reinterpret_cast<const void*>(&step_kernel<GLOG, true, true, ORD, POL>)
+                              : reinterpret_cast<const void*>(&step_kernel<GLOG, false, true, ORD, POL>))
+                      : (pair ? reinterpret_cast<const void*>(&step_kernel<GLOG, true, false, ORD, POL>)
+                              : reinterpret_cast<const void*>(&step_kernel<GLOG, false, false, ORD, POL>));
     };
-    const void* entry = order ? pick(std::true_type{}) : pick(std::false_type{});
+    const void* entry = pol ? (order ? pick(std::true_type{}, std::true_type{}) : pick(std::false_type{}, std::true_type{}))
+                            : (order ? pick(std::true_type{}, std::false_type{}) : pick(std::false_type{}, std::false_type{}));
     int E = p.E;
     const int row_waves = out.obs ? ss.row_waves : 0;
     uint32_t shape = (uint32_t)p.N | ((uint32_t)p.Nb << 8) | ((uint32_t)ss.envs_per_wave << 16) | ((uint32_t)K << 24);
@@ -604,9 +688,16 @@ static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const K
     double rA = p.reward_mode == CCX_K_REWARD_BINARY ? p.r_nogoal
                 : p.reward_mode == CCX_K_REWARD_CONSTANT_NEGATIVE ? p.r_pen : p.r_dest;
     double rB = p.r_door, rC = p.r_area, rF = p.r_f;
+    // mixed control (read by the POL instantiations only)
+    unsigned long long scripted = pol ? pol->scripted : 0ull;
+    int policy = pol ? pol->policy : 0;
+    uint32_t rng_lo = p.rng_lo, rng_hi = p.rng_hi, eps_thr = p.eps_thr, genv0 = (uint32_t)p.env_offset;
+    int bdy = p.bdy, edy = p.edy;
+    uint8_t* actions_out = pol ? pol->actions_out : nullptr;
     void* args[] = {&st_base, &actions, &cell_info, &obs_table, &obs, &E, &shape, &grid_w, &max_steps,
                     &reward, &af, &ef, &cmp, &counters, &pool, &pool_size, &pool_stride, &env_offset_mod_pool,
-                    &dc, &div, &dl, &dr, &term_all, &auto_reset, &rA, &rB, &rC, &rF, &reward_table, &order};
+                    &dc, &div, &dl, &dr, &term_all, &auto_reset, &rA, &rB, &rC, &rF, &reward_table, &order,
+                    &scripted, &policy, &rng_lo, &rng_hi, &eps_thr, &genv0, &bdy, &edy, &actions_out};
     if (ss.lds_bytes > 60 * 1024) {
         hipError_t e = hipFuncSetAttribute(entry, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
@@ -616,15 +707,15 @@ static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const K
 
 hipError_t launch_step(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
                        const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K, int auto_reset,
-                       const uint8_t* pool, const KOut& out, unsigned long long* counters) {
+                       const uint8_t* pool, const KOut& out, unsigned long long* counters, const StepPolicy* pol) {
     switch (ss.glog) {
-    case 0: return launch_step_g<0>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters);
-    case 1: return launch_step_g<1>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters);
-    case 2: return launch_step_g<2>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters);
-    case 3: return launch_step_g<3>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters);
-    case 4: return launch_step_g<4>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters);
-    case 5: return launch_step_g<5>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters);
-    case 6: return launch_step_g<6>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters);
+    case 0: return launch_step_g<0>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
+    case 1: return launch_step_g<1>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
+    case 2: return launch_step_g<2>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
+    case 3: return launch_step_g<3>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
+    case 4: return launch_step_g<4>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
+    case 5: return launch_step_g<5>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
+    case 6: return launch_step_g<6>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
     }
     return hipErrorInvalidValue;
 }

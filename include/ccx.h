@@ -340,6 +340,35 @@ int ccx_rollout(ccx_handle* h, int32_t num_steps, const uint8_t* actions, const 
 int ccx_rollout_policy(ccx_handle* h, int32_t num_steps, int32_t policy, int32_t auto_reset,
                        const ccx_rollout_out* out, uint8_t* actions_out);
 /*
+ * MIXED CONTROL: K steps in which the agent slots of a mask are driven by a scripted policy and the others by the caller's
+ * tensor -- training one side against a scripted other side.  The reference serves that per agent
+ * (policy.get_action(agent_id, obs, env), greedy_policy.py / waiting_policy.py; the loop of
+ * scripts/run_greedy_policy_demo.py:67-109 with a network answering for some ids); here it is ONE launch per <= 16 steps.
+ *   policy          CCX_POLICY_GREEDY or CCX_POLICY_WAITING
+ *   scripted_slots  bit a = agent slot a (boarding slots first), the same for every env of the handle; a bit at or
+ *                   above N is CCX_EINVAL
+ *   actions         u8 [K][E][N]; bytes in scripted slots are ignored (and not counted by ccx_set_check_inputs); may be
+ *                   NULL when scripted_slots covers all N slots
+ *   order           u8 [K][E][N] or NULL, as for ccx_step
+ *   actions_out     u8 [K][E][N] or NULL: receives the merged actions
+ * Every step is, bit for bit, this composition of existing calls:
+ *     pa      = ccx_policy_actions(h, policy)        from the pre-step state; honours ccx_set_policy_epsilon
+ *     merged  = scripted_slots has bit a ? pa[e][a] : actions[e][a]
+ *     ccx_step(h, merged, order, out)                (with auto_reset: ccx_rollout of one step)
+ * so a scripted agent that is terminated or truncated gets CCX_ACTION_ABSENT, and epsilon > 0 takes the counter-based
+ * draws keyed on the env's own counters (the draws of the composition).  With CCX_EPS_STREAM_MT19937 selected AND
+ * epsilon > 0 the call returns CCX_EINVAL: that stream is sequential per env and walked by a kernel of its own; with
+ * epsilon = 0 the stream kind does not matter.  num_steps above 16 is cut into launches of at most 16 on the handle's
+ * stream (an env's trajectory does not depend on the cut).  Handles whose short launches cannot use the step kernel
+ * (ccx_get_step_shape: ok = 0, e.g. 100 x 100 grids) run the composition inside the library, step by step, through a
+ * scratch action buffer allocated by the first such call.  The call only enqueues on the handle's stream: no host
+ * synchronisation, no allocation after the first call, and it captures into a HIP graph (the unfused path after one
+ * eager call).
+ */
+int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t scripted_slots,
+                      const uint8_t* actions, const uint8_t* order, int32_t auto_reset,
+                      const ccx_rollout_out* out, uint8_t* actions_out);
+/*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
  * `rng_seed` of ccx_rollout).  The action of agent slot a of global env g at step t (0-based) of its episode j is
