@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "ccx_internal.h"
+#include "ccx_plan.h"
 
 namespace {
 
@@ -21,12 +22,6 @@ namespace {
 constexpr size_t kMaxObsUnits = 64u * (3u + 2u * 64u) + 2u;
 
 thread_local char g_err[512] = "";
-
-int ceil_log2(int n) {
-    int g = 0;
-    while ((1 << g) < n) ++g;
-    return g;
-}
 
 }  // namespace
 
@@ -40,6 +35,7 @@ int fail(int code, const char* fmt, ...) {
 }
 }  // namespace ccxi
 using ccxi::fail;
+using ccxp::ceil_log2;
 
 namespace {
 
@@ -91,379 +87,34 @@ std::vector<unsigned long long> build_cell_table(const ccx_params& p, const std:
     return tab;
 }
 
-// Default launch shape.  A tile (EW envs) is served by a sim wave and, when outputs are written,
-// a writer wave on another SIMD; one step of a tile is a latency chain of ~1.5k cycles whatever
-// EW is, so the batch should be cut into at least ~512 tiles (1024 waves = one per SIMD of the
-// 256 CUs) before tiles are made fuller.  Measured on 4096 envs x 8 agents: 64 lanes/wave
-// (512 tiles) 0.252 ms per 250 steps, 32 lanes 0.280 ms, 16 lanes 0.344 ms.
-// rows: the shape of launches that write observation rows (h->shape / h->kp: paced, sized for the row stream);
-// !rows: the shape of launches without them (h->shape_small / h->kp_small: rewards, flag bytes, compact rows -- bound by
-// the sim chain and by how many tiles are resident, profiles/r04_shape_sweep.json).
-int derive_shape(ccx_handle* h, const bool rows, ccx::LaunchShape& s, ccx::KParams& k) {
-    const int glog = ceil_log2(h->N);
-    const int G = 1 << glog;
-    const int max_ew = 64 / G;
-    int ew;
-    bool drop_tables = false;
-    if (h->lanes_per_wave > 0) {
-        ew = h->lanes_per_wave / G;
-    } else {
-        const int target_tiles = 512;
-        ew = max_ew;
-        while (ew > 1 && (h->E + ew - 1) / ew < target_tiles) ew >>= 1;
-    }
-    if (ew < 1) ew = 1;
-    if (ew > max_ew) ew = max_ew;
-    if (h->lanes_per_wave == 0) {
-        // Prefer the O(1) occupancy-table conflict masks: carry fewer envs per wave when that makes
-        // the per-env tables fit in LDS (only grids too large even for one env per wave fall back
-        // to the all-pairs compare).
-        auto up = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-        const size_t cells_ = (size_t)(h->params.width + 3) * (size_t)(h->params.height + 3);
-        const size_t msz_ = (glog == 6) ? 8u : 4u;
-        auto need = [&](int e) {
-            const size_t units_ = (size_t)e * h->N * (3 + 2 * h->N);
-            return up(cells_ * 8u) + (h->reward_table ? up(cells_ * 16u) : 0u) +
-                   up(ccx::tile_head_bytes(16) + 7u * 1056u + up((size_t)e * 2u * (cells_ + 1u) * msz_)) + up((units_ + 2u) * 2u);
-        };
-        // The tables cost LDS -- one per env, (cells + 1) x 8 bytes -- and LDS is what bounds how many tiles a CU holds: a 24 x 16
-        // grid keeps three 8-env tiles per CU where five fit without tables, a 64 x 48 grid ONE two-env tile; single-agent envs
-        // on 12 x 8 one 64-env tile.  A batch that needs more ROUNDS because of them pays a round's time for each (64 x 48,
-        // 8 agents: 0.18-0.24 of the HBM peak with tables, 0.51-0.63 without; 24 x 16, 16 384 envs: 0.69 vs 0.93;
-        // profiles/r04_big_grid_scan.txt).  The all-pairs masks cost the sim chain ~5.5 % per lane of the group (8 agents:
-        // 0.47 vs 0.34 us per env-step; 32: 2.8 x).  For groups of <= 16 lanes the tables go (and the tile keeps its lanes)
-        // where the rounds saved outweigh that (16 agents on 64 x 48: 0.25-0.35 of the peak with tables -- one 16-lane tile per
-        // CU --, 0.77-0.88 without).
-        const int ew_fit = [&] { int e = ew; if (need(1) <= 96u * 1024u) while (e > 1 && need(e) > 96u * 1024u) e >>= 1; return e; }();
-        if (glog <= 4 && h->tun_occ_tables < 0) {
-            auto rounds = [&](int e, size_t bytes_per_tile) {
-                const size_t per_cu = std::max<size_t>(1, std::min<size_t>(160u * 1024u / std::max<size_t>(bytes_per_tile, 1), 5u));
-                const size_t tiles_ = (size_t)(h->E + e - 1) / (size_t)e;
-                return (tiles_ + per_cu * h->num_cus - 1) / (per_cu * h->num_cus);
-            };
-            const size_t with_tables = rounds(ew_fit, need(ew_fit));
-            const size_t without = rounds(ew, need(ew) - up((size_t)ew * 2u * (cells_ + 1u) * msz_));
-            if ((double)without * (1.0 + 0.055 * G) < (double)with_tables) drop_tables = true;
-        }
-        if (!drop_tables) ew = ew_fit;
-    }
-    // Batches too small to be memory-bound (round 2): one env-step of a tile takes the sim chain's ~0.5 us
-    // whatever the tile holds, so what counts is that no writer wave takes longer than that and that every
-    // wave has a SIMD of its own.  Full 64-lane tiles with TWO writer waves each do both as long as
-    // 3 waves x tiles stays near the 1024 SIMDs: C2 geometry, us per env-step, full tiles + 2 writers vs the
-    // half-empty single-writer tiles chosen before: 1024 envs 0.53 vs 0.58, 2048 envs 0.54 vs 0.59 (0.63 vs
-    // 0.58 of the HBM peak), 3072 envs 0.63 vs 0.72 (0.81 vs 0.70).
-    bool small_batch = false, half_tiles = false;
-    if (h->lanes_per_wave == 0 && h->writers != 1 && h->waves_per_block == 0) {
-        const long long full_tiles = (h->E + max_ew - 1) / max_ew;
-        const int full_n4 = max_ew * h->N * (3 + 2 * h->N) / ((h->N % 2 == 0) ? 2 : 1);
-        if (full_n4 <= 64 * 12 && full_tiles * (1 + (h->writers > 0 ? h->writers : 2)) <= 1400 && full_tiles * max_ew >= 256) {
-            auto up = [](size_t v) { return (v + 15u) & ~(size_t)15u; };   // (only if the LDS tables of a full tile fit)
-            const size_t cells_ = (size_t)(h->params.width + 3) * (size_t)(h->params.height + 3);
-            const size_t msz_ = (glog == 6) ? 8u : 4u;
-            const size_t units_ = (size_t)max_ew * h->N * (3 + 2 * h->N);
-            // (with the writer slots of the writer count chosen below -- up to four for small batches: a check against
-            // two let a 6 x 16 grid with one agent per env through whose full tile then lost its occupancy tables, and
-            // with them the in-kernel policies; found by the round-3 hypothesis soak)
-            const size_t wslots_ = (size_t)(h->writers > 0 ? h->writers : 4) * 1056u;
-            if (up(cells_ * 8u) + (h->reward_table ? up(cells_ * 16u) : 0u) +
-                    up(ccx::tile_head_bytes(16) + wslots_ + up((size_t)max_ew * 2u * (cells_ + 1u) * msz_)) +
-                    up((units_ + 2u) * 2u) <= 96u * 1024u) {
-                small_batch = true;
-                ew = max_ew;
-                // Up to 128 full tiles (C2 geometry: 1024 envs) half the CUs would stand idle: HALF tiles with four writers
-                // each put a tile on every CU and halve each writer's share (round 3, us per env-step with full outputs:
-                // 1024 envs 0.355 vs 0.398-0.402 with full tiles and 3-4 writers, 512 envs 0.353 vs 0.395).  What remains
-                // is the step's own latency chain sim -> hand-off -> writer (~0.35 us), not bytes.
-                // (round 4 sweep: only where a full tile has >= 9 store iterations per step -- with fewer the row work is too
-                // small to be worth two half-width sim waves: 3 agents, 256-2048 envs 0.37-0.39 vs 0.34 us per env-step)
-                if (full_tiles <= 128 && max_ew >= 2 && h->writers == 0 && (!rows || full_n4 >= 64 * 9)) {
-                    ew = max_ew / 2;
-                    half_tiles = true;
-                }
-            }
-        }
-    }
-    const int tiles = (h->E + ew - 1) / ew;
-    // writer waves per tile: enough that a writer handles <= ~6 store iterations per step
-    const int units = ew * h->N * (3 + 2 * h->N);
-    const int n4 = (h->N % 2 == 0) ? units / 2 : units;
-    // Small tiles (<= 12 store iterations per step, e.g. C2's 9.5): ONE writer wave whose stores in
-    // flight are bounded (many small tiles oversubscribe the HBM write queues; the bound is the
-    // regulator when step pacing is off and a safety net when it is on).
-    // Larger tiles: 2-3 writers, no throttle (measured: no effect).
-    const bool small_tiles = n4 <= 64 * 12;
-    // small batches: writer 0 = small outputs, the others share the observation rows (KParams::writer0_small);
-    // three writers while 4 waves x tiles still fit the 1024 SIMDs (2048-env C2: 0.54 -> 0.485 us per step); round 3, with
-    // the sim chain at 0.27 us and the writer loops compiled per role: four writers up to 160 tiles (1024 envs 0.39 -> 0.41 of
-    // the peak), three beyond (2048 envs: 0.81-0.82 with three, 0.80-0.81 with four)
-    // Small tiles beyond that (C2's 4096 x 8: 9.5 store iterations per tile and step): TWO writers split by role
-    // as well, as long as 3 waves per tile fit one round (16 wavefronts per CU).  With everything on one writer
-    // that wave had 1580 clocks of work per step next to the sim's 1200 and held the tile at ~0.72 us per step --
-    // C2 was bound by its writer wave, not by memory; with two the pace follows the memory side down to
-    // ~0.70 us: 0.86 -> 0.92 of the HBM peak in one call (round 2; round 1 measured two writers as no gain,
-    // but its sim wave was 20 % slower and hid the difference).
-    // Writer waves per tile (round 4: re-derived from the E x N x output-mode sweep, profiles/r04_shape_sweep.json, which
-    // measures every (lanes, writers) candidate per point; the tables of DESIGN.md 4 are that file):
-    //   launches WITHOUT observation rows (rewards / flag bytes / compact rows: bound by the sim chain and by how many tiles
-    //     are resident): two writers split by role, ONE from 1024 tiles on (8 agents, 16 384 envs: 0.55 vs 0.91 us per
-    //     env-step with two; 32 agents, 32 768 envs: 4.1 vs 6.3) -- lane groups of 32 / 64 only from 16 384 tiles on (their
-    //     compact rows keep a second writer busy), single-agent envs never (one writer: +30-40 %); with 257-512 tiles -- one
-    //     per two SIMDs, C2's 4096 envs -- FOUR writers in one-tile workgroups (the two spare waves only poll): every agent
-    //     count of the sweep is 4-6 % faster than with two (8 agents, 4096 envs: 0.319 vs 0.338 us per env-step;
-    //     profiles/scratch/calls/r04_call19.sh, r04_call21.sh);
-    //   small batches (unpaced, full or half tiles): 3-4 writers split by role, as measured in round 3;
-    //   large tiles (> 24 store iterations per step): 3;
-    //   small tiles (<= 12 iterations): with <= 8 iterations per tile (1-3 agents) THREE writers whatever the batch (3
-    //     agents, 8192 envs 0.38 vs 0.47 us with two; N = 1, 65 536 envs: 1.17 vs 2.40 us with the single throttled writer of
-    //     rounds 1-3); with 9-12 iterations (C2's class) two writers split by role up to four tiles per CU (two six-wave
-    //     workgroups; the rule used to read "while 3 waves per tile fit one round", i.e. up to 1365 tiles, and every batch of
-    //     8193 .. 10 920 envs of C2 ran at 0.49 of the peak with a third workgroup on some CUs: profiles/r04_ragged_c2.txt) --
-    //     in pairs up to two tiles per CU (C2's 4096 envs), THREE in one-tile workgroups from there to four (5000 .. 8192 envs:
-    //     0.92-0.94 vs 0.89-0.93 with two, two runs of that table) --, beyond that ONE throttled writer as before: the sweep's short launches put three within 2 % of it, but the bench's settled
-    //     launches do not (C2 geometry, secondary.workloads: 16 384 envs 0.881 vs 0.845 of the peak with three, 65 536 envs
-    //     0.818 vs 0.747).  TWO writers are a cliff in several rounds (6-wave workgroups: +35-80 %);
-    //   tiles in between: 2, or 1 + four tiles per workgroup when that makes the batch fit one round (C3, below).
-    const long long cap_waves = 16ll * h->num_cus;
-    int writers = h->writers > 0 ? h->writers
-                  : !rows ? ((tiles > 256 && tiles <= 512) ? 4   // one tile per two SIMDs: five-wave workgroups, one tile each (below)
-                             : glog <= 2 ? 2 : glog <= 4 ? (tiles > 1280 ? 1 : 2) : (tiles >= 1500 ? 1 : 2))
-                  : small_batch ? (half_tiles || tiles <= 160 ? 4 : 3)
-                  : n4 > 64 * 24 ? 3
-                  : small_tiles ? (n4 <= 64 * 8 ? 3 : tiles <= 2 * h->num_cus ? 2 : tiles <= 4 * h->num_cus ? 3 : 1) : 2;
-    if (writers > 7) writers = 7;
-    // tiles per workgroup: two small tiles share one cell table / one CU slot (with the throttle:
-    // 4.43e9 vs 4.23e9 env-steps/s on C2; 3 or 4 per workgroup leave CUs idle and lose 5-10 %)
-    int tpb = h->waves_per_block > 0 ? h->waves_per_block
-              : small_batch ? 1 : (!rows && writers == 4) ? 1
-              // without rows (profiles/r04_noobs_scan.txt): two-writer tiles NEVER in pairs (six-wave workgroups: 0.45 vs 0.36 us
-              // per env-step from 375 tiles on -- every batch between 2049 and 8191 envs of C2 but 4096), one-writer tiles in
-              // pairs from 1500 tiles on (32 agents, 8192 envs: 1.07 vs 1.31 us)
-              : (!rows && writers == 2) ? 1
-              : (!rows && writers == 1) ? (tiles >= 1500 ? 2 : 1)
-              : (rows && small_tiles && writers == 1 && tiles <= 8 * h->num_cus) ? 1   // (one round of two-wave workgroups: +1-3 % over pairs, 10 000 .. 16 384 envs of C2)
-              : (rows && small_tiles && n4 > 64 * 8 && writers == 3) ? 1
-              : ((tiles > 8192 && writers != 2) || (small_tiles && tiles >= 512)) ? 2 : 1;   // (never two writers in pairs: six-wave workgroups, 16 agents x 36 032 envs ran at 0.47)
-    // One round beats two (round 2): a CU holds 16 wavefronts of this kernel (4 per SIMD at its ~100
-    // VGPRs).  If the batch needs more than that with the writer count above but fits with ONE writer
-    // wave per tile, and that writer's share stays <= 36 store iterations per step, every tile is
-    // resident for the whole launch and the tiles of a step sweep the slab exactly once -- C3 (4096 x 32:
-    // 2048 tiles x 4 waves = two rounds) 0.84 -> 0.87 of the HBM peak with 1 writer and 4 tiles per
-    // workgroup.  (C5, 67 KB per tile, already fits one round with 3 writers; one writer is too slow there.)
-    if (rows && h->writers == 0 && h->waves_per_block == 0 && !small_tiles) {
-        const long long cap = cap_waves;
-        if ((long long)tiles * (1 + writers) > cap && (long long)tiles * 2 <= cap && n4 <= 64 * 36) {
-            writers = 1;
-            tpb = 4;
-        } else if ((long long)tiles * (1 + writers) > cap && writers == 3 && n4 <= 64 * 36) {
-            // several rounds anyway: two writers in one-tile workgroups keep five tiles per CU resident instead of four (C3
-            // geometry, 8192 envs: 21.7 vs 25.2 us per env-step; 32 768 envs 1.01).  NOT with two tiles per workgroup:
-            // six-wave workgroups leave a quarter of a CU's 16 wave slots empty (+40 % at 32 768 envs)
-            // From 8192 tiles on ONE writer (eight tiles per CU resident): 16 384 envs 44.2 vs 49.3 us, 32 768 envs 90 vs 100.
-            if (tiles < 8192) {
-                writers = 2;
-                tpb = 1;
-            } else {
-                writers = 1;
-            }
-        } else if (writers == 2 && tiles >= 8192 && n4 <= 64 * 36) {
-            // the two-writer class (13-24 store iterations per tile: 12-20 agents) in many rounds: the same one writer, in
-            // pairs (20 agents on 24 x 16, 32 768 envs: 0.74 vs 0.42 of the peak; 40 x 30: 0.70 vs 0.65;
-            // profiles/r04_big_grid_scan.txt)
-            writers = 1;
-            tpb = 2;
-        }
-    }
-    while (tpb > 1 && tpb * (1 + writers) > 8) --tpb;   // <= 512 threads per workgroup
-    s.glog = glog;
-    s.envs_per_wave = ew;
-    s.waves_per_block = tpb;
-    s.writers = writers;
-    // with step pacing (the default) the throttle is only a safety net against a collapse of the
-    // drain rate when the pace is too fast; without pacing it is the regulator (16, see above)
-    s.store_throttle = h->store_throttle > 0 ? h->store_throttle
-                       : (h->store_throttle == 0 && small_tiles && writers == 1)
-                             ? (h->step_pace_ns == -1 ? 16 : 48) : 0;
-    s.num_blocks = (tiles + tpb - 1) / tpb;
+// ---- launch-shape selection: the rules are the pure planner of ccx_plan.hip; everything that touches the handle or the
+// device is here ------------------------------------------------------------------------------------------------------
+ccxp::PlanIn plan_in_of(const ccx_handle* h, bool rows) {
+    ccxp::PlanIn in{};
+    in.E = h->E; in.N = h->N; in.width = h->params.width; in.height = h->params.height; in.num_cus = h->num_cus;
+    in.reward_table = h->reward_table ? 1 : 0;
+    in.term_table = (!h->term_table[0].empty() || !h->term_table[1].empty()) ? 1 : 0;
+    in.lanes_per_wave = h->lanes_per_wave; in.waves_per_block = h->waves_per_block; in.writers = h->writers;
+    in.store_throttle = h->store_throttle; in.step_pace_ns = h->step_pace_ns; in.pace_start_ns = h->pace_start_ns;
+    in.occ_tables = h->tun_occ_tables; in.pair_rows = h->tun_pair_rows; in.writer_roles = h->tun_writer_roles;
+    in.pace_phase = h->tun_pace_phase; in.tile_map = h->tun_tile_map;
+    in.step_lanes = h->tun_step_lanes; in.step_rows = h->tun_step_rows;
+    in.rows = rows ? 1 : 0;
+    return in;
+}
 
-    // LDS carve-up (see ccx_kernels.hip): [cell table][tiles][u16 obs table]
-    auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-    const size_t cells = (size_t)(h->params.width + 3) * (size_t)(h->params.height + 3);
-    const size_t msz = (glog == 6) ? 8u : 4u;
-    const size_t occ_bytes = up16((size_t)ew * 2u * (cells + 1u) * msz);
-    const size_t table = up16((size_t)(units + 2) * 2u);
-    const size_t rtab_bytes = h->reward_table ? up16(cells * 16u) : 0u;        // user reward table behind the cell table
-    const size_t off_tiles = up16(cells * 8u) + rtab_bytes;
-    // The hand-off ring takes 32 slots (8 KB) -- or 16 where that costs a CU a resident workgroup: LDS is what bounds the
-    // residency of the big-tile shapes (C5-64: 40 KB per workgroup with 4 KB of ring, four per CU; with 8 KB only three).
-    // (The sim wave proves "slot free" from a progress value it reads once per 16-step burst: 16 slots are the minimum
-    // for which that stale value suffices almost always.)
-    const size_t lds_cu = 160u * 1024u;
-    size_t off_ws = 0, off_occ = 0, tile_stride = 0, total = 0;
-    uint32_t slots = ccx::kMaxStageSlots;
-    // Small batches (unpaced, writers split by role): a second staging slot per writer lets a row writer take TWO steps
-    // per iteration whenever the sim wave is that far ahead (ccx_rollout_body.inc) -- if the LDS has the room.
-    size_t wsw = 1;
-    auto lay_out = [&](uint32_t nslots, int tiles_pb, bool with_occ) {
-        off_ws = ccx::tile_head_bytes(nslots);                   // xch + hand-off words + stage ring
-        off_occ = off_ws + (size_t)writers * wsw * 1056u;        // WSlot(s) per writer
-        tile_stride = up16(off_occ + (with_occ ? occ_bytes : 0));
-        total = off_tiles + (size_t)tiles_pb * tile_stride + table;
-    };
-    // Tile PAIRS hold fewer tiles per CU than single tiles where the waves are what bounds them (three writers: two
-    // eight-wave workgroups = 4 tiles against five four-wave ones): a batch that fits one round of singles but not of pairs
-    // takes singles (4 agents x 17 776 envs: 0.94 vs 1.40 us per env-step; profiles/r04_rows_456.txt).
-    if (h->writers == 0 && h->waves_per_block == 0 && tpb == 2 && off_tiles < 24u * 1024u) {
-        auto rounds_tpb = [&](int t_) {
-            lay_out(16, t_, !drop_tables);
-            const size_t blocks = std::max<size_t>(1, std::min<size_t>(lds_cu / std::max<size_t>(total, 1), (size_t)(20 / (t_ * (1 + writers)))));
-            const size_t at_once = blocks * (size_t)t_ * (size_t)h->num_cus;
-            return ((size_t)tiles + at_once - 1) / at_once;
-        };
-        if (rounds_tpb(1) < rounds_tpb(2)) {
-            tpb = 1;
-            s.waves_per_block = tpb;
-            s.num_blocks = tiles;
-        }
-    }
-    // A CELL table that fills much of the LDS by itself (64 x 48: 27 KB, 80 x 60: 39 KB, 100 x 100: 85 KB -- one per
-    // workgroup) limits the workgroups per CU, and then the tiles per workgroup decide how much of the batch is resident:
-    // 100 x 100, 8 agents, 16 384 envs in one-tile workgroups = 256 tiles at a time, 0.35 of the HBM peak and 3.9 us per
-    // env-step without rows; four one-writer tiles per workgroup = 1024 at a time, 0.85 and 0.90 us
-    // (profiles/r04_big_grid_scan.txt).  Among the rule's own (writers, tiles) and the fuller workgroups -- the same writers
-    // with more tiles, ONE writer with up to four -- the one that needs the fewest rounds is taken (ties: the rule's writers,
-    // then fewer tiles per workgroup).
-    if (h->writers == 0 && h->waves_per_block == 0 && off_tiles >= 24u * 1024u) {
-        auto rounds_with = [&](int w_, int t_) {
-            const int w_saved = writers;
-            writers = w_;
-            lay_out(16, t_, !drop_tables);
-            if (total > 96u * 1024u) lay_out(16, t_, false);      // (tables that do not fit are not kept: below)
-            writers = w_saved;
-            const size_t blocks = std::max<size_t>(1, std::min<size_t>(lds_cu / std::max<size_t>(total, 1), (size_t)(16 / (t_ * (1 + w_)))));
-            const size_t at_once = blocks * (size_t)t_ * (size_t)h->num_cus;
-            return total > lds_cu ? (size_t)1 << 30 : ((size_t)tiles + at_once - 1) / at_once;
-        };
-        int best_w = writers, best_t = tpb;
-        size_t best = rounds_with(writers, tpb);
-        for (int pass = 0; pass < 2; ++pass) {
-            const int w_ = pass == 0 ? writers : 1;
-            for (int t_ = (pass == 0 ? tpb + 1 : 2); t_ * (1 + w_) <= 8; ++t_) {
-                const size_t r_ = rounds_with(w_, t_);
-                if (r_ < best) { best = r_; best_w = w_; best_t = t_; }
-            }
-        }
-        writers = best_w;
-        tpb = best_t;
-        s.waves_per_block = tpb;
-        s.writers = writers;
-        s.num_blocks = (tiles + tpb - 1) / tpb;
-        s.store_throttle = h->store_throttle > 0 ? h->store_throttle
-                           : (h->store_throttle == 0 && small_tiles && writers == 1) ? (h->step_pace_ns == -1 ? 16 : 48) : 0;
-    }
-    // (by default only with half tiles, <= 1024 envs of the C2 geometry: +3 % there; at 2048 envs the unpaced write stream is
-    // the limit and two steps' stores back to back cost it 5-7 %: tunable pair_rows = 1 forces it for every small batch)
-    if (small_batch && writers >= 2 && (h->tun_pair_rows == 1 || (h->tun_pair_rows < 0 && half_tiles))) {
-        wsw = 2;
-        lay_out(16, tpb, !drop_tables);
-        if (total > 96u * 1024u) wsw = 1;
-    }
-    lay_out(16, 1, !drop_tables);
-    const bool tables_can_fit = total <= 96u * 1024u;    // (with one tile per workgroup; a 100 x 100 grid: never)
-    lay_out(16, tpb, !drop_tables);
-    if (h->waves_per_block == 0 && tables_can_fit)        // a default never costs the occupancy tables their LDS
-        while (tpb > 1 && total > 96u * 1024u) {
-            --tpb;
-            lay_out(16, tpb, !drop_tables);
-        }
-    s.waves_per_block = tpb;
-    s.num_blocks = (tiles + tpb - 1) / tpb;
-    s.occ = 1;
-    if (total > 96u * 1024u || h->tun_occ_tables == 0 || drop_tables) {          // tables too big (or switched off, or given up for residency): all-pairs conflict masks instead
-        s.occ = 0;
-        lay_out(16, tpb, false);
-    }
-    // Single-agent envs: a table of (cells + 1) entries per env, 64 envs per wave -- 73 KB for a 12 x 8 grid, ONE tile per CU:
-    // a batch of more than 64 x CUs envs ran in rounds at twice the time per env-step (17 768 envs: 0.83 us against 0.43 at
-    // 15 800).  An agent alone in its env collides with nobody; the all-pairs masks cost it three VALU ops (+4 % while the
-    // tables fit one round, half the time when they do not: profiles/r04_occ_tables.txt).
-    if (s.occ && h->tun_occ_tables < 0 && (drop_tables || (glog == 0 && (size_t)s.num_blocks > (lds_cu / total) * (size_t)h->num_cus))) {
-        s.occ = 0;
-        lay_out(16, tpb, false);
-    }
-    const size_t fit16 = std::min<size_t>(lds_cu / total, 16u);
-    lay_out(slots, tpb, s.occ != 0);
-    if (total > 150u * 1024u || std::min<size_t>(lds_cu / total, 16u) < fit16) slots = 16;
-    lay_out(slots, tpb, s.occ != 0);
-    s.lds_bytes = total;
-    s.lds_bytes_observe = up16((size_t)tpb * 1056u + table);
-
+// the KParams fields that come from the handle's config, not from the launch shape
+void fill_config(const ccx_handle* h, ccx::KParams& k) {
     const ccx_params& p = h->params;
     k.W = p.width; k.H = p.height; k.div = p.division_y;
     k.tl = p.tram_left; k.tr = p.tram_right; k.dl = p.door_left; k.dr = p.door_right;
     k.dc = (p.door_left + p.door_right) / 2;  // observations.py:70-71, rewards.py:81
     k.Nb = p.num_boarding; k.N = h->N; k.bdy = p.boarding_dest_y; k.edy = p.exiting_dest_y;
     k.reward_mode = p.reward_mode; k.term_mode = p.terminated_mode; k.max_steps = p.max_steps;
-    k.E = h->E; k.EW = ew; k.waves_per_block = tpb; k.units_per_wave = units; k.writers = writers;
-    k.off_tiles = (uint32_t)off_tiles; k.tile_stride = (uint32_t)tile_stride;
+    k.E = h->E;
     k.reward_table = h->reward_table;
-    k.off_rtab = h->reward_table ? (uint32_t)up16(cells * 8u) : 0u;
+    k.off_rtab = h->reward_table ? (uint32_t)ccxp::up16((size_t)(p.width + 3) * (size_t)(p.height + 3) * 8u) : 0u;
     k.user_tables = (h->reward_table || !h->term_table[0].empty() || !h->term_table[1].empty()) ? 1u : 0u;
-    k.off_ws = (uint32_t)off_ws; k.off_occ = (uint32_t)off_occ;
-    k.occ_words = s.occ ? (uint32_t)(occ_bytes / 4u) : 0u;
-    k.off_table = (uint32_t)(off_tiles + (size_t)tpb * tile_stride);
-    k.stage_slots = slots;
-    k.ws_per_writer = (uint32_t)wsw;
-    k.wp_magic = (uint32_t)((0x100000000ull + (unsigned long long)(p.width + 3) - 1ull) / (unsigned long long)(p.width + 3));
-    k.writer_vmcnt = (uint32_t)s.store_throttle;
-    k.writer0_small = (h->tun_writer_roles >= 0 ? h->tun_writer_roles != 0 : (small_batch || small_tiles)) && writers >= 2 ? 1u : 0u;
-
-    // Step pacing (ccx_kernels.hip).  The schedule limits the rate at which the resident
-    // workgroups inject observation stores; its start value assumes a drain rate of 6.8 TB/s and the
-    // kernel retunes it after every long launch (bounds: 7.8 TB/s .. a sixth of the start rate).
-    CCX_HIP(hipSetDevice(h->device));
-    int per_cu = ccx::rollout_blocks_per_cu(s, h->N);
-    if (per_cu < 1) per_cu = 1;
-    s.resident_blocks = std::min(s.num_blocks, per_cu * h->num_cus);
-    const double tile_bytes = (double)ew * h->N * (4.0 * (6 + 4 * h->N) + 10.0) + ew;
-    s.step_bytes = tile_bytes * tpb * s.resident_blocks;
-    auto to_fp = [](double ns) { double v = ns / 10.0 * 256.0; return (uint32_t)(v < 1.0 ? 1.0 : (v > 4.0e9 ? 4.0e9 : v)); };
-    // A batch whose resident tiles cannot even fill the drain rate at a fast 0.40 us per env-step is
-    // bound by the step chain, not by memory: pacing could only cost it (a clock read per step).  (0.45 us until the end of
-    // round 4: the chain has become faster than that, and C2 batches of 2160 .. 2430 envs ran unpaced INTO the cliff -- 2304
-    // envs at 0.62 of the peak between 0.82 at 2048 and 0.83 at 2500; profiles/r04_small_batch.txt.)
-    const bool can_saturate = s.step_bytes / 7000.0 >= 400.0;
-    k.pace_state = (!rows || h->step_pace_ns == -1 || (h->step_pace_ns == 0 && !can_saturate)) ? nullptr : h->pace_state;
-    if (rows) h->ring_when_paced = s.step_bytes / 7000.0 < 550.0;
-    k.pace_adapt = (h->step_pace_ns == 0) ? 1u : 0u;
-    {   // how many steps make a launch worth pacing (~12 us) / long enough to judge its lateness (~50 us), at the assumed rate
-        const double step_ns = s.step_bytes / 6800.0;
-        const double a = std::ceil(50000.0 / (step_ns > 1.0 ? step_ns : 1.0));
-        k.adapt_min_k = (uint32_t)(a < 4.0 ? 4.0 : a > 64.0 ? 64.0 : a);
-        k.pace_min_k = k.adapt_min_k / 4u < 2u ? 2u : k.adapt_min_k / 4u;
-    }
-    k.resident_blocks = (uint32_t)s.resident_blocks;
-
-    // observation address table of this shape (ccx_kernels.h: obs_unit_addr).  Shape changes are rare and
-    // never happen inside a graph capture: wait for launches that still read the old table, then copy.
-    if (rows) {
-        h->obs_table_host.assign((size_t)units + 2u, 0);
-        for (int w = 0; w < units; ++w) h->obs_table_host[(size_t)w] = ccx::obs_unit_addr((uint32_t)w, h->N, glog);
-        CCX_HIP(hipStreamSynchronize(h->stream));
-        CCX_HIP(hipMemcpy(h->obs_table, h->obs_table_host.data(), h->obs_table_host.size() * sizeof(uint16_t),
-                          hipMemcpyHostToDevice));
-    }
-    k.obs_table = h->obs_table;
-    k.pace_min_fp = to_fp(s.step_bytes / 8000.0);    // (the spec peak; round 2 stopped at 7.8 TB/s, which multi-tile-per-CU shapes now reach)
-    k.pace_max_fp = to_fp(s.step_bytes / 1100.0);
-    if (rows) {
-        h->pace_init_fp = h->step_pace_ns > 0 ? to_fp((double)h->step_pace_ns)
-                          : h->pace_start_ns > 0.0f ? to_fp((double)h->pace_start_ns) : to_fp(s.step_bytes / 6800.0);
-        h->pace_start_source = h->step_pace_ns > 0 ? CCX_PACE_START_FIXED
-                               : h->pace_start_ns > 0.0f ? CCX_PACE_START_CALLER : CCX_PACE_START_ASSUMED;
-        h->pace_dirty = true;
-        h->pace_needs_calibration = false;
-    }
     k.r_dest = p.boarding_destination_reward; k.r_door = p.tram_door_reward;
     k.r_area = p.tram_area_reward; k.r_f = p.distance_penalty_factor;
     k.r_nogoal = p.no_goal_reward; k.r_pen = p.step_penalty;
@@ -474,71 +125,51 @@ int derive_shape(ccx_handle* h, const bool rows, ccx::LaunchShape& s, ccx::KPara
     // would restart from ONE placement forever, so the stride is 1 then (env e walks e, e+1, e+2, ...)
     k.pool_stride = h->pool_size > 0 ? (long long)(h->total_envs % h->pool_size) : 0;
     if (h->pool_size > 0 && k.pool_stride == 0) k.pool_stride = 1 % h->pool_size;
-    // Write-window defaults (measured round 2).  Large tiles (tens of KB per tile and step:
-    // C3, C5) drain 5-10 % faster when the tiles of a round are phased over the step
-    // period in tile order and groups of 16 adjacent tiles go to one XCD, dealt round-robin: the chip then
-    // writes one window that sweeps through the slab instead of 1000+ regions at once (C3 0.80 -> 0.86,
-    // C5-64 0.79 -> 0.89, C5-50 0.77 -> 0.83 of the HBM peak in one call).  Small tiles (C2: 10 KB per tile
-    // and step) show no difference while there are two of them per CU (4096 envs) and keep the common phase and
-    // the XCD-contiguous mapping; LARGER batches of small tiles are 1000+ regions at once again and gain the same
-    // way (C2 geometry, one call: 16 384 envs 0.879 -> 0.908, 32 768 envs in two rounds 0.830 -> 0.882).
-    const bool big_tiles = !small_tiles || (long long)tiles >= 4ll * h->num_cus;
-    k.pace_phase = (uint32_t)(h->tun_pace_phase >= 0 ? h->tun_pace_phase : (big_tiles ? 1 : 0));
-    // groups of ~1 MiB of one step's slab per XCD: g workgroups with g * (bytes a workgroup writes per step)
-    // closest to 1 MiB, a power of two in 1..32 (C5-64: 16 x 67 KB, C3: 8 x 137 KB)
-    int auto_map = 0;
-    if (big_tiles) {
-        const double wg_bytes = tile_bytes * tpb;
-        int g = 1;
-        while (g < 32 && wg_bytes * g * 1.41 < 1048576.0) g <<= 1;
-        auto_map = 1;
-        while ((1 << (auto_map - 1)) < g) ++auto_map;
-    }
-    k.tile_map = (uint32_t)(h->tun_tile_map >= 0 ? h->tun_tile_map : auto_map);
+}
 
-    if (!rows) return CCX_OK;
-    // Short launches (<= 16 steps, ccx_step.hip): a workgroup = one tile = a sim wave + row waves, as many tiles as the
-    // batch fills, halved only while there are fewer than one per two CUs (a one-step launch is bound by how fast its waves are
-    // dispatched and drained: with the row waves' table words preloaded, 512 tiles of 64 lanes + 2 row waves step C2's 4096 envs
-    // in 3.64 us, 1024 tiles of 32 + 1 in 3.72; 512 envs: 128 tiles of 32 lanes 3.04 us, 512 tiles of 8 lanes 3.30;
-    // profiles/r04_step_k1_shapes_*.txt, r04_step_scan.txt), never more envs per wave than the rollout shape (the observation address
-    // table of a smaller tile is a prefix of the rollout's).  Row waves: enough that one handles <= ~6 store iterations per step
-    // (small tiles) or 10-14 (large ones), at most 5 (C5-64: 14.9 us with five, 15.5 with seven).  Grids whose tables exceed
-    // the LDS keep the rollout kernel.
-    {
-        ccx::StepShape& ss = h->step_shape;
-        int sew = ew;
-        if (h->tun_step_lanes > 0) sew = std::max(1, std::min(ew, h->tun_step_lanes / G));
-        else while (sew > 1 && ((h->E + sew - 1) / sew < h->num_cus / 2 ||      // (profiles/r04_step_scan.txt)
-                                ccx::step_lds_bytes(glog, sew, h->N, (int)cells, h->reward_table != nullptr) > 96u * 1024u))
-            sew >>= 1;                                                          // (... and until the tile's tables fit: 40 x 30, 4096 envs took the rollout kernel for 8 KB)
-        ss.glog = glog;
-        ss.envs_per_wave = sew;
-        ss.lds_bytes = ccx::step_lds_bytes(glog, sew, h->N, (int)cells, h->reward_table != nullptr);
-        const int sunits = sew * h->N * (3 + 2 * h->N);
-        const int sits = ((h->N % 2 == 0 ? sunits / 2 : sunits) + 63) / 64;
-        ss.row_waves = h->tun_step_rows > 0 ? h->tun_step_rows
-                       : sits <= 6 ? 1 : sits <= 12 ? 2 : sits <= 33 ? 3 : sits <= 45 ? 4 : 5;
-        ss.num_blocks = (h->E + sew - 1) / sew;
-        // (the step kernel carries its own tables whatever the rollout shape does about its; EVERY workgroup stages the cell
-        //  table and zeroes its tables per launch: past ~24 MB of that per step the rollout kernel is the faster one -- 40 x 30,
-        //  4096 envs: 60 MB, 10.2 vs 5.8 us per step; 80 x 60: 113 vs 6.8; profiles/r04_step_big_grid.txt)
-        //  -- or three times the step's rows where those are the larger part: 20 agents on 40 x 30, 4096 envs: 11.9 vs 16.4 us)
-        const double step_rows_bytes = (double)h->E * h->N * (6.0 + 4.0 * h->N) * 4.0;
-        ss.ok = (ss.lds_bytes <= 96u * 1024u &&
-                 (double)ss.num_blocks * (double)ss.lds_bytes <= std::max(24.0e6, 3.0 * step_rows_bytes)) ? 1 : 0;
+// THE place that writes a plan into the handle: h->shape* / h->kp*, h->step_shape and the pace_* fields; it also uploads the
+// observation address table of the rows shape (ccx_kernels.h: obs_unit_addr).  Shape changes are rare and never happen
+// inside a graph capture: wait for launches that still read the old table, then copy.
+int apply(ccx_handle* h, bool rows, const ccxp::ShapePlan& sp, const ccxp::PacePlan& pp) {
+    ccx::LaunchShape& s = rows ? h->shape : h->shape_small;
+    ccx::KParams& k = rows ? h->kp : h->kp_small;
+    ccxp::materialize(sp, pp, s, k);
+    fill_config(h, k);
+    k.pace_state = pp.paced ? h->pace_state : nullptr;
+    if (rows) {
+        h->ring_when_paced = pp.ring_when_paced;
+        h->obs_table_host.assign((size_t)k.units_per_wave + 2u, 0);
+        for (int w = 0; w < k.units_per_wave; ++w) h->obs_table_host[(size_t)w] = ccx::obs_unit_addr((uint32_t)w, h->N, s.glog);
+        CCX_HIP(hipStreamSynchronize(h->stream));
+        CCX_HIP(hipMemcpy(h->obs_table, h->obs_table_host.data(), h->obs_table_host.size() * sizeof(uint16_t),
+                          hipMemcpyHostToDevice));
+        h->pace_init_fp = pp.pace_init_fp;
+        h->pace_start_source = pp.pace_start_source;
+        h->pace_dirty = true;
+        h->pace_needs_calibration = false;
+        h->step_shape = sp.step;
     }
+    k.obs_table = h->obs_table;
     return CCX_OK;
 }
 
 int choose_shape(ccx_handle* h) {
-    // (seeds / epsilon live in h->kp and survive a re-derivation)
-    const uint32_t rng_lo = h->kp.rng_lo, rng_hi = h->kp.rng_hi, eps_thr = h->kp.eps_thr;
-    int rc = derive_shape(h, true, h->shape, h->kp);
-    if (rc) return rc;
-    rc = derive_shape(h, false, h->shape_small, h->kp_small);
-    h->kp.rng_lo = rng_lo; h->kp.rng_hi = rng_hi; h->kp.eps_thr = eps_thr;
-    return rc;
+    CCX_HIP(hipSetDevice(h->device));
+    for (const bool rows : {true, false}) {
+        const ccxp::PlanIn in = plan_in_of(h, rows);
+        const ccxp::ShapePlan sp = ccxp::plan_shape(in);
+        const int per_cu = ccx::rollout_blocks_per_cu(sp.shape, h->N);
+        const int rc = apply(h, rows, sp, ccxp::plan_pacing(in, sp, per_cu));
+        if (rc) return rc;
+    }
+    return CCX_OK;
+}
+
+// the kernel parameters of a launch: the planned template of a shape plus the handle's run-time policy state
+ccx::KParams launch_params(const ccx_handle* h, bool small_shape = false) {
+    ccx::KParams kp = small_shape ? h->kp_small : h->kp;
+    kp.rng_lo = h->rng_lo; kp.rng_hi = h->rng_hi; kp.eps_thr = h->eps_thr;
+    return kp;
 }
 
 int validate_params(const ccx_params* p) {
@@ -614,9 +245,8 @@ int calibrate_pace(ccx_handle* h, float* obs, size_t obs_bytes) {
     (void)hipEventDestroy(e1);
     if (rc) return rc;
     if (best_gbs > 1000.0 && best_gbs < 12000.0) {            // (a sane measurement; else keep the assumption)
-        auto to_fp = [](double ns) { double v = ns / 10.0 * 256.0; return (uint32_t)(v < 1.0 ? 1.0 : (v > 4.0e9 ? 4.0e9 : v)); };
         h->pace_probe_gbs = (float)best_gbs;
-        h->pace_init_fp = std::min(std::max(to_fp(h->shape.step_bytes / (best_gbs * 1.05)), h->kp.pace_min_fp), h->kp.pace_max_fp);
+        h->pace_init_fp = std::min(std::max(ccxp::to_fp(h->shape.step_bytes / (best_gbs * 1.05)), h->kp.pace_min_fp), h->kp.pace_max_fp);
         h->pace_start_source = CCX_PACE_START_CALIBRATED;
     }
     return CCX_OK;
@@ -675,7 +305,7 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
         }
         int rc = begin_timed(h);
         if (rc) return rc;
-        hipError_t e = ccx::launch_step(h->step_shape, h->stream, h->kp, h->st_slab, h->cell_info, actions, order, K, auto_reset,
+        hipError_t e = ccx::launch_step(h->step_shape, h->stream, launch_params(h), h->st_slab, h->cell_info, actions, order, K, auto_reset,
                                         h->pool, out, h->counters);
         if (e != hipSuccess) return fail(CCX_EHIP, "step kernel launch failed: %s", hipGetErrorString(e));
         return end_timed(h);
@@ -740,8 +370,7 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
     // at the pace in effect and neither votes nor touches the controller's state.
     const bool small_launch = !writes_obs && h->tun_small_shape != 0;      // rewards / flag bytes / compact rows only
     const ccx::LaunchShape& shape = small_launch ? h->shape_small : h->shape;
-    ccx::KParams kp = small_launch ? h->kp_small : h->kp;
-    kp.rng_lo = h->kp.rng_lo; kp.rng_hi = h->kp.rng_hi; kp.eps_thr = h->kp.eps_thr;
+    ccx::KParams kp = launch_params(h, small_launch);
     kp.pace_slot = h->pace_slot;
     kp.launch_flags = 0u;
     // launches the kernel will not pace hand steps to the writer waves through sequence words (ccx_kernels.h: one
@@ -1132,8 +761,8 @@ int ccx_policy_actions(ccx_handle* h, int32_t policy, uint8_t* actions) {
     if (policy != CCX_POLICY_GREEDY && policy != CCX_POLICY_WAITING) return fail(CCX_EINVAL, "unknown policy %d", policy);
     CCX_HIP(hipSetDevice(h->device));
     hipError_t e = h->eps_stream == CCX_EPS_STREAM_MT19937
-        ? ccx::launch_policy_stream_actions(h->stream, h->kp, h->st, h->cell_info, actions, policy, h->mt_state, h->epsilon)
-        : ccx::launch_greedy_actions(h->stream, h->kp, h->st, h->cell_info, actions, policy);
+        ? ccx::launch_policy_stream_actions(h->stream, launch_params(h), h->st, h->cell_info, actions, policy, h->mt_state, h->epsilon)
+        : ccx::launch_greedy_actions(h->stream, launch_params(h), h->st, h->cell_info, actions, policy);
     if (e != hipSuccess) return fail(CCX_EHIP, "policy kernel launch failed: %s", hipGetErrorString(e));
     return CCX_OK;
 }
@@ -1141,7 +770,7 @@ int ccx_policy_actions(ccx_handle* h, int32_t policy, uint8_t* actions) {
 int ccx_greedy_actions(ccx_handle* h, uint8_t* actions) {
     if (!h || !actions) return fail(CCX_EINVAL, "NULL argument");
     CCX_HIP(hipSetDevice(h->device));
-    ccx::KParams kp = h->kp;
+    ccx::KParams kp = launch_params(h);
     kp.eps_thr = 0u;                               // (always the deterministic policy; ccx_policy_actions has the epsilon)
     hipError_t e = ccx::launch_greedy_actions(h->stream, kp, h->st, h->cell_info, actions, CCX_POLICY_GREEDY);
     if (e != hipSuccess) return fail(CCX_EHIP, "greedy kernel launch failed: %s", hipGetErrorString(e));
@@ -1268,7 +897,7 @@ int ccx_rollout_policy(ccx_handle* h, int32_t num_steps, int32_t policy, int32_t
         if (rc) return rc;
         for (int s = 0; s < num_steps; ++s) {
             uint8_t* acts = actions_out ? actions_out + (size_t)s * EN : h->stream_actions;
-            hipError_t e = ccx::launch_policy_stream_actions(h->stream, h->kp, h->st, h->cell_info, acts, policy, h->mt_state,
+            hipError_t e = ccx::launch_policy_stream_actions(h->stream, launch_params(h), h->st, h->cell_info, acts, policy, h->mt_state,
                                                              h->epsilon);
             if (e != hipSuccess) return fail(CCX_EHIP, "policy kernel launch failed: %s", hipGetErrorString(e));
             rc = stepwise_step(h, ko, s, acts, nullptr, auto_reset ? 1 : 0, false);
@@ -1322,7 +951,7 @@ int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t
             const ccx::StepPolicy pol{scripted_slots, policy, actions_out ? actions_out + (size_t)k0 * EN : nullptr};
             int rc = begin_timed(h);
             if (rc) return rc;
-            hipError_t e = ccx::launch_step(h->step_shape, h->stream, h->kp, h->st_slab, h->cell_info,
+            hipError_t e = ccx::launch_step(h->step_shape, h->stream, launch_params(h), h->st_slab, h->cell_info,
                                             actions ? actions + (size_t)k0 * EN : nullptr, order ? order + (size_t)k0 * EN : nullptr,
                                             kk, auto_reset ? 1 : 0, h->pool, kout_at(h, ko, k0), h->counters, &pol);
             if (e != hipSuccess) return fail(CCX_EHIP, "step kernel launch failed: %s", hipGetErrorString(e));
@@ -1337,7 +966,7 @@ int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t
     if (rc) return rc;
     for (int s = 0; s < num_steps; ++s) {
         uint8_t* acts = actions_out ? actions_out + (size_t)s * EN : h->stream_actions;
-        hipError_t e = ccx::launch_greedy_actions(h->stream, h->kp, h->st, h->cell_info, acts, policy);
+        hipError_t e = ccx::launch_greedy_actions(h->stream, launch_params(h), h->st, h->cell_info, acts, policy);
         if (e != hipSuccess) return fail(CCX_EHIP, "policy kernel launch failed: %s", hipGetErrorString(e));
         if (scripted_slots != all_slots) {
             e = ccx::launch_merge_actions(h->stream, acts, actions + (size_t)s * EN, scripted_slots, h->N, EN);
@@ -1377,6 +1006,13 @@ int ccx_set_reward_table(ccx_handle* h, const double* boarding_per_cell, const d
     }
     const int W1 = h->params.width + 1, H1 = h->params.height + 1, Wp = h->params.width + 3, Hp = h->params.height + 3;
     const size_t cells = (size_t)Wp * (size_t)Hp;
+    if (!ccxp::reward_table_fits(plan_in_of(h, true))) {    // (asked before anything is uploaded; a table set earlier goes)
+        (void)hipFree(h->reward_table);
+        h->reward_table = nullptr;
+        (void)choose_shape(h);
+        return fail(CCX_EINVAL, "the reward table of a %d x %d grid (%zu bytes of LDS) does not fit next to the kernel's tables",
+                    h->params.width, h->params.height, cells * 16u);
+    }
     std::vector<double> tab(2u * cells, 0.0);                // padded grid, border cells 0 (never occupied)
     const double* src[2] = {boarding_per_cell, exiting_per_cell};
     for (int t = 0; t < 2; ++t)
@@ -1385,16 +1021,7 @@ int ccx_set_reward_table(ccx_handle* h, const double* boarding_per_cell, const d
                 tab[(size_t)t * cells + (size_t)(y + 1) * Wp + (size_t)(x + 1)] = src[t][(size_t)y * W1 + x];
     if (!h->reward_table) CCX_HIP(hipMalloc(&h->reward_table, tab.size() * sizeof(double)));
     CCX_HIP(hipMemcpy(h->reward_table, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-    const int rc = choose_shape(h);
-    if (rc) return rc;
-    if (h->shape.lds_bytes > 150u * 1024u || h->shape_small.lds_bytes > 150u * 1024u) {
-        (void)hipFree(h->reward_table);
-        h->reward_table = nullptr;
-        (void)choose_shape(h);
-        return fail(CCX_EINVAL, "the reward table of a %d x %d grid (%zu bytes of LDS) does not fit next to the kernel's tables",
-                    h->params.width, h->params.height, cells * 16u);
-    }
-    return CCX_OK;
+    return choose_shape(h);
 }
 
 int ccx_set_terminated_table(ccx_handle* h, const uint8_t* boarding_per_cell, const uint8_t* exiting_per_cell) {
@@ -1431,8 +1058,8 @@ int ccx_check_inputs(ccx_handle* h) {
 
 int ccx_set_rng_seed(ccx_handle* h, uint64_t seed) {
     if (!h) return fail(CCX_EINVAL, "NULL handle");
-    h->kp.rng_lo = (uint32_t)seed;
-    h->kp.rng_hi = (uint32_t)(seed >> 32);
+    h->rng_lo = (uint32_t)seed;
+    h->rng_hi = (uint32_t)(seed >> 32);
     return CCX_OK;
 }
 
@@ -1440,7 +1067,7 @@ int ccx_set_policy_epsilon(ccx_handle* h, double epsilon) {
     if (!h) return fail(CCX_EINVAL, "NULL handle");
     if (!(epsilon >= 0.0 && epsilon <= 1.0)) return fail(CCX_EINVAL, "epsilon must be in [0, 1] (got %g)", epsilon);
     const double t = epsilon * 4294967296.0;
-    h->kp.eps_thr = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+    h->eps_thr = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
     h->epsilon = epsilon;
     return CCX_OK;
 }
@@ -1708,6 +1335,23 @@ int ccx_synchronize(ccx_handle* h) {
     CCX_HIP(hipSetDevice(h->device));
     CCX_HIP(hipStreamSynchronize(h->stream));
     return report_input_errors(h);
+}
+
+// ---- internal (ccx_plan.h): what a live handle launches with, for the tests of the launch-shape planner ---------------
+int ccxi_handle_plan(const ccx_handle* h, int rows, ccxi_plan_out* out, int* blocks_per_cu) {
+    if (!h || !out) return fail(CCX_EINVAL, "NULL argument");
+    const ccx::LaunchShape& s = rows ? h->shape : h->shape_small;
+    const ccx::KParams& k = rows ? h->kp : h->kp_small;
+    ccxp::PacePlan pp{};
+    pp.paced = k.pace_state != nullptr;
+    if (rows) {
+        pp.ring_when_paced = h->ring_when_paced;
+        pp.pace_init_fp = h->pace_init_fp;
+        pp.pace_start_source = h->pace_start_source;
+    }
+    ccxp::plan_out(s, k, rows ? h->step_shape : ccx::StepShape{}, pp, out);
+    if (blocks_per_cu) *blocks_per_cu = ccx::rollout_blocks_per_cu(s, h->N);   // (the query choose_shape made for this shape)
+    return CCX_OK;
 }
 
 #ifdef CCX_LAG_TRACE

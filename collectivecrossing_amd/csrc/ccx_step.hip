@@ -647,13 +647,8 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-size_t step_lds_bytes(int glog, int ew, int N, int cells, bool reward_table) {
-    auto up16 = [](size_t v) { return (v + 15u) & ~(size_t)15u; };
-    const size_t msz = glog == 6 ? 8u : 4u;
-    (void)N;
-    return up16((size_t)cells * 8u) + (reward_table ? (size_t)cells * 16u : 0u) +
-           up16((size_t)ew * 2u * ((size_t)cells + 1u) * msz) + 2u * sizeof(WSlot) + 256u /* move-order exchange */;
-}
+// (step_lds_bytes, the LDS of this kernel, lives next to the rollout kernel's size model: ccx_plan.hip)
+static_assert(sizeof(WSlot) == 1056, "ccx_plan.hip: kWSlotBytes");
 
 template <int GLOG>
 static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
