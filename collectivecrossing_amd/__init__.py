@@ -11,7 +11,7 @@ from .configs import CollectiveCrossingConfig  # noqa: F401
 
 __version__ = "0.4.0"
 __all__ = ["CollectiveCrossingConfig", "CollectiveCrossingEnv", "BatchedCollectiveCrossing", "VectorCollectiveCrossing",
-           "BatchedMultiAgentEnv"]
+           "BatchedMultiAgentEnv", "unpack_action_masks"]
 
 
 def __getattr__(name):  # lazy: importing the configs must not pull in torch
@@ -27,6 +27,9 @@ def __getattr__(name):  # lazy: importing the configs must not pull in torch
     if name == "BatchedMultiAgentEnv":
         from .rllib import BatchedMultiAgentEnv
         return BatchedMultiAgentEnv
+    if name == "unpack_action_masks":
+        from .batched import unpack_action_masks
+        return unpack_action_masks
     raise AttributeError(name)
 
 

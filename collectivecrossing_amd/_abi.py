@@ -113,6 +113,9 @@ PROTOTYPES: dict[str, tuple] = {
                                      C.c_void_p]),
     "ccx_rollout_mixed": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int32,
                                     C.POINTER(CcxRolloutOut), C.c_void_p]),
+    "ccx_action_masks": (C.c_int, [_H, C.c_void_p]),
+    "ccx_bind_action_masks": (C.c_int, [_H, C.c_void_p]),
+    "ccx_get_masks_fused": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ccx_set_check_inputs": (C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),

@@ -39,6 +39,7 @@ class StepResult:
     env_flags: torch.Tensor   # u8 [E]     (_abi.EF_*)
     obs_compact: torch.Tensor | None = None   # f32 [E, N, 4]  (x, y, type, active), CCX_OBS_COMPACT
     term_present: torch.Tensor | None = None  # u8 [E, N]: 1 where terminateds[id] exists (step_finish / array-form strategies)
+    action_masks: torch.Tensor | None = None  # u8 [E, N]: legal actions of the state behind the step (want_masks; unpack_action_masks)
 
 
 @dataclass
@@ -60,6 +61,34 @@ def _check_cell_px(cell_px) -> int:
     if isinstance(cell_px, bool) or not isinstance(cell_px, (int, np.integer)) or not 1 <= int(cell_px) <= 64:
         raise ValueError(f"cell_px must be an integer in 1..64, got {cell_px!r}")
     return int(cell_px)
+
+
+ACTION_MASK_WAIT_ONLY = 0x10   # the mask byte of an agent that is terminated or truncated
+
+
+def unpack_action_masks(masks):
+    """Mask bytes (``ccx_action_masks``: bit a = action a is legal, bit 4 = wait, always set) -> ``bool [..., 5]`` indexed
+    by action id, for ``logits.masked_fill(~mask, -inf)``.  Takes a torch tensor (the result lives on its device) or
+    anything numpy converts; needs no GPU.  On a device tensor it only launches kernels, so it captures into a graph."""
+    if isinstance(masks, torch.Tensor):
+        if masks.dtype is not torch.uint8:
+            raise TypeError(f"action masks are uint8, got {masks.dtype}")
+        # (built on the device, without a host-to-device copy: the call may sit inside a graph capture)
+        one = torch.ones(5, dtype=torch.uint8, device=masks.device)
+        bits = torch.bitwise_left_shift(one, torch.arange(5, dtype=torch.uint8, device=masks.device))
+        return (masks.unsqueeze(-1) & bits) != 0
+    arr = np.asarray(masks)
+    if arr.dtype != np.uint8:
+        raise TypeError(f"action masks are uint8, got {arr.dtype}")
+    return (arr[..., None] & np.array([1, 2, 4, 8, 16], np.uint8)) != 0
+
+
+def pack_action_masks(mask5) -> np.ndarray:
+    """Inverse of :func:`unpack_action_masks` on the host: ``bool [..., 5]`` -> ``uint8 [...]``."""
+    m = np.asarray(mask5.cpu() if isinstance(mask5, torch.Tensor) else mask5).astype(bool)
+    if m.shape[-1:] != (5,):
+        raise ValueError(f"expected [..., 5], got {m.shape}")
+    return (m * np.array([1, 2, 4, 8, 16], np.uint8)).sum(-1).astype(np.uint8)
 
 
 def scripted_slot_mask(config: CollectiveCrossingConfig, scripted) -> int:
@@ -142,6 +171,8 @@ class BatchedCollectiveCrossing:
         self._pool: torch.Tensor | None = None
         self._step_bufs: StepResult | None = None
         self._step_out_cache: dict = {}
+        self._masks_buf: torch.Tensor | None = None      # u8 [E, N] behind StepResult.action_masks
+        self._masks_bound = 0                            # the pointer ccx_bind_action_masks holds (0 = none)
         self._rollouts_with_obs = 0
         if check_inputs is None:
             check_inputs = os.environ.get("CCX_CHECK_INPUTS", "0") not in ("", "0")
@@ -305,6 +336,46 @@ class BatchedCollectiveCrossing:
         check(self._lib.ccx_greedy_actions(self._h, _ptr(out)))
         return out
 
+    # ------------------------------------------------------------------ legal-action masks
+    def _check_masks(self, t) -> torch.Tensor:
+        E, N = self.num_envs, self.num_agents
+        if not isinstance(t, torch.Tensor) or t.dtype is not torch.uint8 or t.device != self.device:
+            raise ValueError(f"action masks go to a torch.uint8 tensor on {self.device}")
+        if tuple(t.shape) != (E, N) or not t.is_contiguous():
+            raise ValueError(f"action masks need a contiguous tensor of shape {(E, N)}, got {tuple(t.shape)}")
+        return t
+
+    def _bind_masks(self, t: torch.Tensor | None) -> None:
+        """While a tensor is bound every launch that advances the state leaves the masks of its final state there
+        (``ccx_bind_action_masks``); only a CHANGE of the pointer reaches the library (this is on the per-step path)."""
+        ptr = 0 if t is None else t.data_ptr()
+        if ptr != self._masks_bound:
+            check(self._lib.ccx_bind_action_masks(self._h, C.c_void_p(ptr or None)))
+            self._masks_bound = ptr
+
+    def _step_masks(self, want_masks: bool) -> None:
+        if want_masks and self._masks_buf is None:
+            self._masks_buf = self._new((self.num_envs, self.num_agents), torch.uint8)
+        self._bind_masks(self._masks_buf if want_masks else None)
+
+    def action_masks(self, out: torch.Tensor | None = None) -> torch.Tensor:
+        """Legal actions of every agent slot in the CURRENT state, u8 [E, N] (``ccx_action_masks``): bit a = action a
+        would move the agent (the reference's ``_is_valid_action``: bounds, walls, door row, no other active agent on the
+        target), bit 4 = wait, always set; 0x10 for agents that are terminated or truncated.
+        :func:`unpack_action_masks` turns the bytes into ``bool [E, N, 5]``.  Only enqueues on the handle's stream."""
+        out = self._new((self.num_envs, self.num_agents), torch.uint8) if out is None else self._check_masks(out)
+        self._order_after_current_stream(out)
+        check(self._lib.ccx_action_masks(self._h, _ptr(out)))
+        return out
+
+    def masks_fused(self, num_steps: int = 1, order: bool = False, mixed: bool = False) -> bool:
+        """Whether such a call writes its masks from the step's own launch (``ccx_get_masks_fused``) -- one env-step
+        without a move order on a handle whose short launches take the step kernel -- or is followed by the stand-alone
+        mask kernel on the same stream.  The bytes are the same either way."""
+        v = C.c_int32()
+        check(self._lib.ccx_get_masks_fused(self._h, int(num_steps), int(bool(order)), int(bool(mixed)), C.byref(v)))
+        return bool(v.value)
+
     # ------------------------------------------------------------------ compute
     def observe(self, out: torch.Tensor | None = None) -> torch.Tensor:
         if out is None:
@@ -312,20 +383,26 @@ class BatchedCollectiveCrossing:
         check(self._lib.ccx_observe(self._h, _ptr(out)))
         return out
 
-    def step(self, actions, order=None, want_obs: bool = True, want_compact: bool = False) -> StepResult:
+    def step(self, actions, order=None, want_obs: bool = True, want_compact: bool = False,
+             want_masks: bool = False) -> StepResult:
+        """One env-step (``ccx_step``).  ``want_masks``: ``StepResult.action_masks`` (u8 [E, N]) holds the legal actions
+        of the state BEHIND the step, written by the same launch where :meth:`masks_fused` says so."""
+        self._step_masks(want_masks)
         if self._array_strategies:
-            return self._step_array(actions, order, want_obs, want_compact)
+            res = self._step_array(actions, order, want_obs, want_compact)
+            return res if not want_masks else StepResult(res.obs, res.reward, res.agent_flags, res.env_flags, res.obs_compact,
+                                                         res.term_present, self._masks_buf)
         E, N = self.num_envs, self.num_agents
         a = self._as_dev_u8(actions, (E, N))
         o = None if order is None else self._as_dev_u8(order, (E, N))
-        cached = self._step_out(_abi.CcxStepOut, want_obs, want_compact)
+        cached = self._step_out(_abi.CcxStepOut, want_obs, want_compact, want_masks)
         check(self._lib.ccx_step(self._h, a.data_ptr(), None if o is None else o.data_ptr(), cached[1]))
         return cached[2]
 
-    def _step_out(self, struct, want_obs, want_compact):
+    def _step_out(self, struct, want_obs, want_compact, want_masks=False):
         """(output struct, its byref, StepResult) over the env's static one-step buffers, built once per struct type and
         output selection -- this is the per-step path of a policy-in-the-loop caller, a few microseconds end to end."""
-        key = (struct, bool(want_obs), bool(want_compact))
+        key = (struct, bool(want_obs), bool(want_compact), bool(want_masks))
         cached = self._step_out_cache.get(key)
         if cached is None:
             E, N = self.num_envs, self.num_agents
@@ -340,7 +417,8 @@ class BatchedCollectiveCrossing:
                         _ptr(b.agent_flags).value, _ptr(b.env_flags).value,
                         _ptr(b.obs_compact if want_compact else None).value)
             cached = (so, C.byref(so), StepResult(b.obs if want_obs else None, b.reward, b.agent_flags, b.env_flags,
-                                                  b.obs_compact if want_compact else None))
+                                                  b.obs_compact if want_compact else None,
+                                                  action_masks=self._masks_buf if want_masks else None))
             self._step_out_cache[key] = cached
         return cached
 
@@ -354,12 +432,15 @@ class BatchedCollectiveCrossing:
         return scripted_slot_mask(self.config, scripted), _abi.POLICIES[policy]
 
     def step_mixed(self, actions, scripted, policy: str = "greedy", order=None, want_obs: bool = True,
-                   want_compact: bool = False, actions_out: torch.Tensor | None = None) -> StepResult:
+                   want_compact: bool = False, actions_out: torch.Tensor | None = None,
+                   want_masks: bool = False) -> StepResult:
         """One step in which the ``scripted`` slots (:func:`scripted_slot_mask`) take the on-device ``policy``'s action
         and the others the bytes of ``actions`` -- ``policy_actions`` + ``torch.where`` + ``step`` in ONE launch
         (``ccx_rollout_mixed``).  Bytes of ``actions`` in scripted slots are ignored; ``actions`` may be ``None`` when every
-        slot is scripted; ``actions_out`` (u8 [E, N]) receives the merged actions.  Returns the views :meth:`step` returns."""
+        slot is scripted; ``actions_out`` (u8 [E, N]) receives the merged actions.  Returns the views :meth:`step` returns;
+        ``want_masks`` as for :meth:`step`."""
         mask, pol = self._mixed_args(scripted, policy)
+        self._step_masks(want_masks)
         E, N = self.num_envs, self.num_agents
         if actions is None and mask != (1 << N) - 1:
             raise ValueError("actions may be None only when every slot is scripted")
@@ -367,7 +448,7 @@ class BatchedCollectiveCrossing:
         o = None if order is None else self._as_dev_u8(order, (E, N))
         if actions_out is not None:
             self._check_actions_out(actions_out, (E, N))
-        cached = self._step_out(_abi.CcxRolloutOut, want_obs, want_compact)
+        cached = self._step_out(_abi.CcxRolloutOut, want_obs, want_compact, want_masks)
         check(self._lib.ccx_rollout_mixed(self._h, 1, pol, mask, None if a is None else a.data_ptr(),
                                           None if o is None else o.data_ptr(), 0, cached[1],
                                           None if actions_out is None else actions_out.data_ptr()))
@@ -381,11 +462,13 @@ class BatchedCollectiveCrossing:
 
     def rollout_mixed(self, actions, scripted, policy: str = "greedy", order=None, auto_reset: bool = False,
                       out: RolloutResult | None = None, actions_out: torch.Tensor | None = None, num_steps: int | None = None,
-                      want_obs: bool = True, want_traj: bool = True, want_compact: bool = False) -> RolloutResult | None:
+                      want_obs: bool = True, want_traj: bool = True, want_compact: bool = False,
+                      masks_out: torch.Tensor | None = None) -> RolloutResult | None:
         """K mixed-control steps (``ccx_rollout_mixed``; launches of at most 16 steps): ``actions`` u8 [K, E, N], or
         ``None`` with ``num_steps`` when every slot is scripted.  Mirrors :meth:`rollout`; ``actions_out`` (u8 [K, E, N])
-        receives the merged actions."""
+        receives the merged actions; ``masks_out`` (u8 [E, N]) the legal actions of the state behind the LAST step."""
         mask, pol = self._mixed_args(scripted, policy)
+        self._bind_masks(None if masks_out is None else self._check_masks(masks_out))
         E, N = self.num_envs, self.num_agents
         if actions is None:
             if mask != (1 << N) - 1:
@@ -476,6 +559,7 @@ class BatchedCollectiveCrossing:
         On a batch whose config names array-form classes, an argument left ``None`` is filled by the config's own class of
         that kind (:meth:`run_array_strategies`), never by the stand-in mode the handle was built with: ``step_begin`` +
         ``step_finish()`` is ``step`` there too."""
+        self._bind_masks(None)
         r = self._user_array("reward", reward, (torch.float64,), None)
         t = self._user_array("terminated", terminated, (torch.bool, torch.int8), torch.int8)
         u = self._user_array("truncated", truncated, (torch.bool, torch.uint8), torch.uint8)
@@ -663,14 +747,17 @@ class BatchedCollectiveCrossing:
 
     def rollout(self, actions, order=None, auto_reset: bool = False,
                 out: RolloutResult | None = None, want_obs: bool = True,
-                want_traj: bool = True, want_compact: bool = False) -> RolloutResult | None:
-        """K fused steps (``ccx_rollout``); ``actions`` u8 [K, E, N] on the device.  A batch with array-form user
+                want_traj: bool = True, want_compact: bool = False,
+                masks_out: torch.Tensor | None = None) -> RolloutResult | None:
+        """K fused steps (``ccx_rollout``); ``actions`` u8 [K, E, N] on the device.  ``masks_out`` (u8 [E, N]) receives the
+        legal actions (:meth:`action_masks`) of the state behind the LAST step, after an auto-reset if one happened.  A batch with array-form user
         strategies runs the split step once per tick instead (launch-bound: three launches plus the user's tensor code per
         step) into the same preallocated result, with ``term_present`` filled."""
         K = int(actions.shape[0])
         E, N = self.num_envs, self.num_agents
         a = self._as_dev_u8(actions, (K, E, N))
         o = None if order is None else self._as_dev_u8(order, (K, E, N))
+        self._bind_masks(None if masks_out is None else self._check_masks(masks_out))
         if self._array_strategies:
             return self._rollout_array(K, a, o, None, auto_reset, out, want_traj, want_obs, want_compact, None)
         if out is None and want_traj:
@@ -686,10 +773,11 @@ class BatchedCollectiveCrossing:
 
     def rollout_greedy(self, num_steps: int, auto_reset: bool = False, out: RolloutResult | None = None,
                        want_obs: bool = True, actions_out: torch.Tensor | None = None,
-                       want_actions: bool = True, policy: str = "greedy"):
+                       want_actions: bool = True, policy: str = "greedy", masks_out: torch.Tensor | None = None):
         """K fused steps driven by an on-device scripted policy ("greedy" or "waiting",
-        ``ccx_rollout_policy``); returns ``(RolloutResult, actions u8 [K, E, N])``."""
+        ``ccx_rollout_policy``); returns ``(RolloutResult, actions u8 [K, E, N])``.  ``masks_out`` as for :meth:`rollout`."""
         K, E, N = int(num_steps), self.num_envs, self.num_agents
+        self._bind_masks(None if masks_out is None else self._check_masks(masks_out))
         if actions_out is None and want_actions:
             actions_out = self._new((K, E, N), torch.uint8)
         if self._array_strategies:

@@ -253,7 +253,8 @@ int calibrate_pace(ccx_handle* h, float* obs, size_t obs_bytes) {
 }
 
 int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* order, int auto_reset,
-                const ccx::KOut& out, int policy = 0, uint8_t* actions_out = nullptr, bool inputs_checked = false) {
+                const ccx::KOut& out, int policy = 0, uint8_t* actions_out = nullptr, bool inputs_checked = false,
+                uint8_t* masks = nullptr, bool* masks_written = nullptr) {
     // The writer waves address the small output streams (rewards, flag bytes, compact rows, chosen actions) with 32-bit
     // byte offsets from the stream's base: one launch must stay below 4 GiB per stream.  Longer rollouts are cut into
     // launches on the same stream (bit-identical: an env's trajectory does not depend on how a rollout is split).
@@ -305,9 +306,12 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
         }
         int rc = begin_timed(h);
         if (rc) return rc;
+        // (bound action masks: this launch writes them itself where an MSK instantiation exists -- ccx_kernels.h)
+        uint8_t* const m = ccx::step_masks_fused(K, order != nullptr) ? masks : nullptr;
         hipError_t e = ccx::launch_step(h->step_shape, h->stream, launch_params(h), h->st_slab, h->cell_info, actions, order, K, auto_reset,
-                                        h->pool, out, h->counters);
+                                        h->pool, out, h->counters, nullptr, m);
         if (e != hipSuccess) return fail(CCX_EHIP, "step kernel launch failed: %s", hipGetErrorString(e));
+        if (m && masks_written) *masks_written = true;
         return end_timed(h);
     }
     const bool writes_obs = out.obs != nullptr;
@@ -443,6 +447,15 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
     // the kernel collected the votes for the next pace in the other slot (same condition as in the kernel)
     if (adaptive && !capturing) h->pace_slot ^= 1u;
     return end_timed(h);
+}
+
+// ccx_bind_action_masks: every call that advanced the state leaves the masks of its final state at the bound pointer --
+// written by the step kernel itself (`written`), or by the stand-alone kernel behind the call's last launch
+int finish_masks(ccx_handle* h, bool written) {
+    if (!h->bound_masks || written) return CCX_OK;
+    hipError_t e = ccx::launch_action_masks(h->stream, launch_params(h), h->st, h->cell_info, h->bound_masks);
+    if (e != hipSuccess) return fail(CCX_EHIP, "action mask kernel launch failed: %s", hipGetErrorString(e));
+    return CCX_OK;
 }
 
 // ---- loops that step ONE env-step per launch (the MT19937 policy loop, the unfused mixed-control step) -----------------
@@ -807,7 +820,9 @@ int ccx_step(ccx_handle* h, const uint8_t* actions, const uint8_t* order, const 
         ko.env_flags = out->env_flags;
         ko.obs_compact = out->obs_compact;
     }
-    return run_rollout(h, 1, actions, order, 0, ko);
+    bool written = false;
+    const int rc = run_rollout(h, 1, actions, order, 0, ko, 0, nullptr, false, h->bound_masks, &written);
+    return rc ? rc : finish_masks(h, written);
 }
 
 int ccx_step_begin(ccx_handle* h, const uint8_t* actions, const uint8_t* order) {
@@ -851,7 +866,8 @@ int ccx_step_finish(ccx_handle* h, const double* reward, const int8_t* terminate
     hipError_t e = ccx::launch_step_finish(h->shape, h->stream, h->kp, h->st, h->cell_info, reward, terminated, truncated, ko,
                                            term_present, auto_reset ? 1 : 0, h->pool, h->counters);
     if (e != hipSuccess) return fail(CCX_EHIP, "step_finish kernel launch failed: %s", hipGetErrorString(e));
-    return end_timed(h);
+    rc = end_timed(h);
+    return rc ? rc : finish_masks(h, false);
 }
 
 int ccx_rollout(ccx_handle* h, int32_t num_steps, const uint8_t* actions, const uint8_t* order,
@@ -868,7 +884,9 @@ int ccx_rollout(ccx_handle* h, int32_t num_steps, const uint8_t* actions, const 
         ko.env_flags = out->env_flags;
         ko.obs_compact = out->obs_compact;
     }
-    return run_rollout(h, num_steps, actions, order, auto_reset ? 1 : 0, ko);
+    bool written = false;
+    const int rc = run_rollout(h, num_steps, actions, order, auto_reset ? 1 : 0, ko, 0, nullptr, false, h->bound_masks, &written);
+    return rc ? rc : finish_masks(h, written);
 }
 
 int ccx_rollout_policy(ccx_handle* h, int32_t num_steps, int32_t policy, int32_t auto_reset,
@@ -903,10 +921,11 @@ int ccx_rollout_policy(ccx_handle* h, int32_t num_steps, int32_t policy, int32_t
             rc = stepwise_step(h, ko, s, acts, nullptr, auto_reset ? 1 : 0, false);
             if (rc) return rc;
         }
-        return CCX_OK;
+        return finish_masks(h, false);
     }
     // (grids whose occupancy tables exceed the LDS run the in-kernel policies through the all-pairs exchange: round 4)
-    return run_rollout(h, num_steps, nullptr, nullptr, auto_reset ? 1 : 0, ko, policy, actions_out);
+    const int rc = run_rollout(h, num_steps, nullptr, nullptr, auto_reset ? 1 : 0, ko, policy, actions_out);
+    return rc ? rc : finish_masks(h, false);
 }
 
 int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t scripted_slots,
@@ -944,6 +963,7 @@ int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t
         if (ce != hipSuccess) return fail(CCX_EHIP, "input check kernel launch failed: %s", hipGetErrorString(ce));
     }
     if (fused) {
+        uint8_t* const m = ccx::step_masks_fused(num_steps, order != nullptr) ? h->bound_masks : nullptr;
         // the short-launch kernel's policy instantiations (ccx_step.hip, POL): policy + merge + step in ONE launch per
         // <= 16 steps (16 is even: every sub-launch's slice of the observation tensor stays 16-byte aligned)
         for (int k0 = 0; k0 < num_steps; k0 += ccx::kStepMaxK) {
@@ -953,12 +973,12 @@ int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t
             if (rc) return rc;
             hipError_t e = ccx::launch_step(h->step_shape, h->stream, launch_params(h), h->st_slab, h->cell_info,
                                             actions ? actions + (size_t)k0 * EN : nullptr, order ? order + (size_t)k0 * EN : nullptr,
-                                            kk, auto_reset ? 1 : 0, h->pool, kout_at(h, ko, k0), h->counters, &pol);
+                                            kk, auto_reset ? 1 : 0, h->pool, kout_at(h, ko, k0), h->counters, &pol, m);
             if (e != hipSuccess) return fail(CCX_EHIP, "step kernel launch failed: %s", hipGetErrorString(e));
             rc = end_timed(h);
             if (rc) return rc;
         }
-        return CCX_OK;
+        return finish_masks(h, m != nullptr);
     }
     // Handles whose short launches cannot use the step kernel (tables beyond the LDS, or the tunable): the composition
     // itself, step by step on the handle's stream -- policy kernel, merge kernel, the existing step path.
@@ -975,6 +995,28 @@ int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t
         rc = stepwise_step(h, ko, s, acts, order ? order + (size_t)s * EN : nullptr, auto_reset ? 1 : 0, true);
         if (rc) return rc;
     }
+    return finish_masks(h, false);
+}
+
+int ccx_action_masks(ccx_handle* h, uint8_t* masks) {
+    if (!h || !masks) return fail(CCX_EINVAL, "NULL argument");
+    CCX_HIP(hipSetDevice(h->device));
+    hipError_t e = ccx::launch_action_masks(h->stream, launch_params(h), h->st, h->cell_info, masks);
+    if (e != hipSuccess) return fail(CCX_EHIP, "action mask kernel launch failed: %s", hipGetErrorString(e));
+    return CCX_OK;
+}
+
+int ccx_bind_action_masks(ccx_handle* h, uint8_t* masks_or_null) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    h->bound_masks = masks_or_null;
+    return CCX_OK;
+}
+
+int ccx_get_masks_fused(ccx_handle* h, int32_t num_steps, int32_t has_order, int32_t mixed, int32_t* fused) {
+    if (!h || !fused) return fail(CCX_EINVAL, "NULL argument");
+    if (num_steps < 1) return fail(CCX_EINVAL, "num_steps must be >= 1");
+    (void)mixed;      // (both kinds of launch have their MSK instantiations: ccx_step.hip)
+    *fused = (h->step_shape.ok && h->tun_step_kernel != 0 && ccx::step_masks_fused(num_steps, has_order != 0)) ? 1 : 0;
     return CCX_OK;
 }
 

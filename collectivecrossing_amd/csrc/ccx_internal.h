@@ -81,5 +81,6 @@ struct ccx_handle {
     ccx::LaunchShape shape_small{};                             // launches without them (rewards / flag bytes / compact rows)
     ccx::KParams kp_small{};
     uint32_t rng_lo = 0, rng_hi = 0;                            // seed of CCX_POLICY_RANDOM and of the epsilon draws (ccx_set_rng_seed)
+    uint8_t* bound_masks = nullptr;                             // ccx_bind_action_masks: device u8 [E][N] (the caller's), null = not bound
     uint32_t eps_thr = 0;                                       // epsilon * 2^32 of the scripted policies (ccx_set_policy_epsilon); the launchers copy the three into their KParams
 };

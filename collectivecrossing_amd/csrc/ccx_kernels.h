@@ -227,7 +227,14 @@ struct StepPolicy {
 };
 hipError_t launch_step(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
                        const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K, int auto_reset,
-                       const uint8_t* pool, const KOut& out, unsigned long long* counters, const StepPolicy* pol = nullptr);
+                       const uint8_t* pool, const KOut& out, unsigned long long* counters, const StepPolicy* pol = nullptr,
+                       uint8_t* masks = nullptr);
+// Legal-action masks (include/ccx.h: CCX_ACTION_MASKS), u8 [E][N] of the handle's current state.  launch_step writes them
+// itself (`masks`) where step_masks_fused says so -- the MSK instantiations of ccx_step.hip: ONE env-step without a move
+// order, with or without a scripted policy; every other launch is followed by launch_action_masks on the same stream.
+constexpr bool step_masks_fused(int K, bool has_order) { return K == 1 && !has_order; }
+hipError_t launch_action_masks(hipStream_t stream, const KParams& p, const KState& st,
+                               const unsigned long long* cell_info, uint8_t* masks);
 
 // the split step (ccx_split_step.hip): collectivecrossing.py:188-212, then :214-259 with the caller's reward / terminated /
 // truncated arrays (null = the handle's built-in rule); finish takes the lane layout of the observe kernel (ls, p)

@@ -198,6 +198,45 @@ hipError_t launch_policy_stream_actions(hipStream_t stream, const KParams& p, co
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------------------------
+// Legal-action masks of the current state (include/ccx.h: CCX_ACTION_MASKS), one thread per (env, agent): what the
+// reference's policies ask per agent and action (greedy_policy.py:238-264 _is_valid_action -> env._is_move_valid,
+// collectivecrossing.py:345-369; the epsilon branch enumerates the same set, greedy_policy.py:51-57).  Walls, the door
+// row and the grid's edge are the four neighbour bits of the agent's cell word; occupancy is ONE pass over the env's
+// agents -- an ACTIVE agent (whatever its terminated / truncated flags: _is_position_occupied) one cell away takes the
+// direction that leads to it.  Works from global memory alone, so any legal grid is served (100 x 100 included).
+// ---------------------------------------------------------------------------------------------
+__global__ void action_masks_kernel(const KParams p, const KState st, const unsigned long long* __restrict__ cell_info,
+                                    uint8_t* __restrict__ masks) {
+    const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t total = (size_t)p.E * p.N;
+    if (t >= total) return;
+    uint32_t m = 0x10u;                                   // wait is always legal (greedy_policy.py:253)
+    if (!(st.terminated[t] || st.truncated[t])) {         // done agents are not in env.agents: wait only
+        const int env = (int)(t / p.N), i = (int)(t % p.N);
+        const size_t base = (size_t)env * p.N;
+        const int cx = st.x[t], cy = st.y[t];
+        uint32_t busy = 0u;
+        for (int b = 0; b < p.N; ++b) {
+            const int dx = st.x[base + b] - cx, dy = st.y[base + b] - cy;
+            const uint32_t hit = (dx == 1 && dy == 0 ? 1u : 0u) | (dx == 0 && dy == 1 ? 2u : 0u) |
+                                 (dx == -1 && dy == 0 ? 4u : 0u) | (dx == 0 && dy == -1 ? 8u : 0u);
+            busy |= (b != i && st.active[base + b]) ? hit : 0u;
+        }
+        m |= (uint32_t)cell_info[(cy + 1) * (p.W + 3) + cx + 1] & 0xFu & ~busy;
+    }
+    masks[t] = (uint8_t)m;
+}
+
+hipError_t launch_action_masks(hipStream_t stream, const KParams& p, const KState& st,
+                               const unsigned long long* cell_info, uint8_t* masks) {
+    const size_t total = (size_t)p.E * p.N;
+    if (total == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)((total + 255) / 256);
+    hipLaunchKernelGGL(action_masks_kernel, dim3(blocks), dim3(256), 0, stream, p, st, cell_info, masks);
+    return hipGetLastError();
+}
+
 hipError_t launch_greedy_actions(hipStream_t stream, const KParams& p, const KState& st,
                                  const unsigned long long* cell_info, uint8_t* actions, int policy) {
     const size_t total = (size_t)p.E * p.N;

@@ -27,6 +27,9 @@
 // occupancy bits first, reads its four neighbour entries, evaluates the rule from the state in registers, selects per
 // lane between that and the loaded byte, and enters the move resolution with its occupancy bit already in the table.
 // Policy id, epsilon and the RNG words are run-time kernel arguments behind the preloaded ones.
+// MSK (ccx_bind_action_masks): behind the launch's last step the sim wave leaves the legal-action byte of every agent slot
+// for the state it writes back (include/ccx.h: CCX_ACTION_MASKS) -- one more round on the occupancy table, once per launch.
+// The output pointer is the LAST kernel argument; the other instantiations never look at it.
 // The first 14 argument dwords (state slab, actions, both tables, obs, E, shape words, max_steps) are preloaded into SGPRs
 // (csrc/Makefile: -amdgpu-kernarg-preload-count=14): -0.05 us per step, measured on this kernel.
 #include "ccx_rollout_dev.h"
@@ -74,7 +77,8 @@ template <int GLOG> struct RowBatch { static constexpr int value = GLOG <= 3 ? 8
 // ORD: the caller passed a move order (collectivecrossing.py:197: agents move in the order of `action_dict`)
 // POL: mixed control -- the slots of `scripted` are driven by the scripted policy `policy` (the trailing arguments are read
 //      by these instantiations only)
-template <int GLOG, bool PAIR, bool K1, bool ORD, bool POL = false>
+// MSK: the launch also writes the legal-action masks of its final state (`masks`, the last argument)
+template <int GLOG, bool PAIR, bool K1, bool ORD, bool POL = false, bool MSK = false>
 __global__ void __launch_bounds__(512)
 step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab layout
             const uint8_t* __restrict__ actions,                // u8 [K][E][N]
@@ -98,7 +102,8 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
             const uint32_t rng_lo, const uint32_t rng_hi, const uint32_t eps_thr,   // POL: epsilon draws (ccx_kernels.h: explore_action)
             const uint32_t genv0,                                      // POL: global index of env 0 (low word)
             const int bdy, const int edy,                              // POL: destination rows
-            uint8_t* __restrict__ actions_out) {                       // POL: u8 [K][E][N] the actions taken, or null
+            uint8_t* __restrict__ actions_out,                         // POL: u8 [K][E][N] the actions taken, or null
+            uint8_t* __restrict__ masks) {                             // MSK: u8 [E][N] legal-action masks of the final state
     using mask_t = typename GroupMask<GLOG>::type;
     constexpr int G = 1 << GLOG;
     constexpr uint32_t msz = sizeof(mask_t);
@@ -613,6 +618,22 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
         }
     }
     CCX_ST(4);
+    // ---- legal-action masks of the state that goes back (greedy_policy.py:238-264 -> env._is_move_valid,
+    //      collectivecrossing.py:345-369): the table is clean behind the last step, so ONE more round on it -- the active
+    //      agents' bits at their final cells, my four neighbour entries -- gives `busy` exactly as the policy's round does
+    //      (POL, step 0).  The wave ends here: nothing is cleared.
+    uint32_t mask_byte = 0x10u;                                        // wait is always legal (greedy_policy.py:253)
+    if constexpr (MSK) {
+        auto lds_mask_ld = [](uint32_t addr) -> mask_t { return *(__attribute__((address_space(3))) const mask_t*)(uintptr_t)addr; };
+        lds_or(act ? tab_rel + ((uint32_t)c8 << TS) : dump_addr, mybit);
+        wave_lds_sync();
+        const uint32_t cb = tab_rel + ((uint32_t)c8 << TS);
+        const uint32_t rowb = (uint32_t)(Wp * 8) << TS, colb = 8u << TS;
+        const mask_t o0 = lds_mask_ld(cb + colb), o1 = lds_mask_ld(cb + rowb), o2 = lds_mask_ld(cb - colb),
+                     o3 = lds_mask_ld(cb - rowb);
+        const uint32_t busy = (o0 != 0 ? 1u : 0u) | (o1 != 0 ? 2u : 0u) | (o2 != 0 ? 4u : 0u) | (o3 != 0 ? 8u : 0u);
+        mask_byte |= tt == 0u ? (ilo & 0xFu & ~busy) : 0u;             // done agents: wait only
+    }
     // ---- registers -> state --------------------------------------------------------------------------------------
     if (valid) {
         reinterpret_cast<int32_t*>(st_base + sl.x)[idx] = (int)((ilo >> 16) & 0xFFu);
@@ -620,6 +641,7 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
         (st_base + sl.active)[idx] = (uint8_t)act;
         (st_base + sl.terminated)[idx] = (uint8_t)(tt & 1u);
         (st_base + sl.truncated)[idx] = (uint8_t)(tt >> 1);
+        if constexpr (MSK) masks[idx] = (uint8_t)mask_byte;
     }
     if (valid_env && i == 0) {
         reinterpret_cast<int32_t*>(st_base + sl.step_count)[env] = max_steps_m1 - left1;
@@ -654,8 +676,14 @@ template <int GLOG>
 static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
                                 const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K,
                                 int auto_reset, const uint8_t* pool, const KOut& out, unsigned long long* counters,
-                                const StepPolicy* pol) {
+                                const StepPolicy* pol, uint8_t* masks) {
     const bool pair = (p.N % 2) == 0;
+    // the instantiations that also write the masks: one env-step without a move order (step_masks_fused)
+    auto pick_msk = [&](auto pol_c) -> const void* {
+        constexpr bool POL = decltype(pol_c)::value;
+        return pair ? reinterpret_cast<const void*>(&step_kernel<GLOG, true, true, false, POL, true>)
+                    : reinterpret_cast<const void*>(&step_kernel<GLOG, false, true, false, POL, true>);
+    };
     auto pick = [&](auto ord_c, auto pol_c) -> const void* {
         constexpr bool ORD = decltype(ord_c)::value, POL = decltype(pol_c)::value;
         return K == 1 ? (pair ? reinterpret_cast<const void*>(&step_kernel<GLOG, true, true, ORD, POL>)
@@ -663,7 +691,9 @@ static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const K
                       : (pair ? reinterpret_cast<const void*>(&step_kernel<GLOG, true, false, ORD, POL>)
                               : reinterpret_cast<const void*>(&step_kernel<GLOG, false, false, ORD, POL>));
     };
-    const void* entry = pol ? (order ? pick(std::true_type{}, std::true_type{}) : pick(std::false_type{}, std::true_type{}))
+    if (masks && !step_masks_fused(K, order != nullptr)) return hipErrorInvalidValue;
+    const void* entry = masks ? (pol ? pick_msk(std::true_type{}) : pick_msk(std::false_type{}))
+                      : pol ? (order ? pick(std::true_type{}, std::true_type{}) : pick(std::false_type{}, std::true_type{}))
                             : (order ? pick(std::true_type{}, std::false_type{}) : pick(std::false_type{}, std::false_type{}));
     int E = p.E;
     const int row_waves = out.obs ? ss.row_waves : 0;
@@ -692,7 +722,7 @@ static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const K
     void* args[] = {&st_base, &actions, &cell_info, &obs_table, &obs, &E, &shape, &grid_w, &max_steps,
                     &reward, &af, &ef, &cmp, &counters, &pool, &pool_size, &pool_stride, &env_offset_mod_pool,
                     &dc, &div, &dl, &dr, &term_all, &auto_reset, &rA, &rB, &rC, &rF, &reward_table, &order,
-                    &scripted, &policy, &rng_lo, &rng_hi, &eps_thr, &genv0, &bdy, &edy, &actions_out};
+                    &scripted, &policy, &rng_lo, &rng_hi, &eps_thr, &genv0, &bdy, &edy, &actions_out, &masks};
     if (ss.lds_bytes > 60 * 1024) {
         hipError_t e = hipFuncSetAttribute(entry, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
@@ -702,15 +732,15 @@ static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const K
 
 hipError_t launch_step(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
                        const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K, int auto_reset,
-                       const uint8_t* pool, const KOut& out, unsigned long long* counters, const StepPolicy* pol) {
+                       const uint8_t* pool, const KOut& out, unsigned long long* counters, const StepPolicy* pol, uint8_t* masks) {
     switch (ss.glog) {
-    case 0: return launch_step_g<0>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
-    case 1: return launch_step_g<1>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
-    case 2: return launch_step_g<2>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
-    case 3: return launch_step_g<3>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
-    case 4: return launch_step_g<4>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
-    case 5: return launch_step_g<5>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
-    case 6: return launch_step_g<6>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol);
+    case 0: return launch_step_g<0>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
+    case 1: return launch_step_g<1>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
+    case 2: return launch_step_g<2>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
+    case 3: return launch_step_g<3>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
+    case 4: return launch_step_g<4>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
+    case 5: return launch_step_g<5>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
+    case 6: return launch_step_g<6>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
     }
     return hipErrorInvalidValue;
 }

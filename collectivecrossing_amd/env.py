@@ -576,6 +576,20 @@ class CollectiveCrossingEnv(_Base):
                 not self._is_position_occupied(new_pos, exclude_agent=agent_id) and
                 not self._would_hit_tram_wall(current_pos, new_pos))
 
+    def action_masks(self) -> dict[str, np.ndarray]:
+        """``{agent_id: int8 (5,)}`` for ``env.agents``: entry a is 1 iff the reference's
+        ``GreedyPolicy._is_valid_action(id, a, env)`` holds on the current state (greedy_policy.py:238-264 ->
+        ``_is_move_valid``), wait (4) always.  Evaluated on the host mirror -- the state itself -- so it works on a
+        :meth:`host_view` too; the batch path (``BatchedCollectiveCrossing.action_masks``) gives the same bits."""
+        out = {}
+        for aid in self.agents:
+            pos = self._get_agent_position(aid)
+            m = np.ones(5, np.int8)
+            for a in range(4):
+                m[a] = self._is_move_valid(aid, pos, pos + self._action_to_direction[a])
+            out[aid] = m
+        return out
+
     def _calculate_new_position(self, agent_id, action) -> np.ndarray:
         return self._get_agent_position(agent_id) + self._action_to_direction[action]
 

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import _abi
-from .batched import BatchedCollectiveCrossing, StepResult
+from .batched import BatchedCollectiveCrossing, StepResult, unpack_action_masks
 from .configs import CollectiveCrossingConfig
 from .env import decode_step, encode_actions
 from .spaces import Box, Discrete
@@ -134,6 +134,10 @@ class VectorCollectiveCrossing:
         # envs restarted by step_dicts(auto_reset=True) after the last step: their rows in `last.obs` are the NEW
         # episode's first observations and every agent's row counts as handed out (policy_inputs' mask)
         self._restarted = torch.zeros((E,), dtype=torch.bool, device=dev)
+        # legal actions of the CURRENT state (BatchedCollectiveCrossing.action_masks), kept up to date by reset, step (the
+        # step's own launch writes them) and the device restart of step_dicts(auto_reset=True); None until the first of those
+        self._masks = torch.full((E, N), 0x10, dtype=torch.uint8, device=dev)
+        self._masks_valid = False
         # array-form user strategies (strategies.ARRAY_METHODS): which terminateds[id] entries exist (the strategy may
         # return None), device + pinned host copy next to the main buffer
         self._tp_dev = self._tp_host = None
@@ -146,6 +150,8 @@ class VectorCollectiveCrossing:
     def reset(self, seeds, env_mask=None) -> torch.Tensor:
         """``reset(seed=seeds[e])`` of the (masked) envs on the device; obs tensor [E, N, L]."""
         obs = self.batch.reset(seeds, env_mask)
+        self.batch.action_masks(out=self._masks)
+        self._masks_valid = True
         if env_mask is None:
             self._done.zero_()
         else:
@@ -167,6 +173,9 @@ class VectorCollectiveCrossing:
                              out.env_flags.data_ptr())
         import ctypes as C
         from ._lib import check
+        b._bind_masks(self._masks)      # this step's launch leaves the masks of the new state there
+        self._masks_valid = True
+        out.action_masks = self._masks
         if b.has_array_strategies:      # begin -> the user's batched methods -> finish, all on the handle's stream
             b.step_begin(a, o)
             r, t, u = b.run_array_strategies()
@@ -197,6 +206,7 @@ class VectorCollectiveCrossing:
         """Restart exactly the envs that finished (seeded, on the device); returns the done mask."""
         m = self.done_mask()
         self.batch.reset(seeds, env_mask=m)
+        self.batch.action_masks(out=self._masks)
         with torch.cuda.stream(self.batch._stream):
             self._done[m.bool()] = False
         self._done_host = None
@@ -214,7 +224,10 @@ class VectorCollectiveCrossing:
         """Observation rows grouped the way the reference's callers feed its two policies
         (evaluation_script.py:45-87: rows of ids containing "boarding" / "exiting", stacked):
         ``{"boarding": {"obs": [E, Nb, L], "mask": [E, Nb]}, "exiting": {...}}`` on the device; ``mask`` marks
-        the rows the reference would have handed out (agents not done before the step, CCX_AF_OBS)."""
+        the rows the reference would have handed out (agents not done before the step, CCX_AF_OBS).  ``action_mask``
+        (``bool [E, Nb|Ne, 5]``, index = action id) says which actions would move the agent in the CURRENT state (the
+        reference's ``_is_valid_action``; wait is always legal, done agents may only wait): valid after ``reset``, ``step``
+        and ``step_dicts``, recomputed behind the device restart of ``step_dicts(auto_reset=True)``."""
         if obs is None:
             if self.last is None:
                 raise RuntimeError("no step yet")
@@ -223,8 +236,13 @@ class VectorCollectiveCrossing:
         else:
             emitted = torch.ones(obs.shape[:2], dtype=torch.bool, device=obs.device)
         nb = self.num_boarding
-        return {"boarding": {"obs": obs[:, :nb], "mask": emitted[:, :nb]},
-                "exiting": {"obs": obs[:, nb:], "mask": emitted[:, nb:]}}
+        if not self._masks_valid:
+            self.batch.action_masks(out=self._masks)
+            self._masks_valid = True
+        with torch.cuda.stream(self.batch._stream):
+            legal = unpack_action_masks(self._masks)
+        return {"boarding": {"obs": obs[:, :nb], "mask": emitted[:, :nb], "action_mask": legal[:, :nb]},
+                "exiting": {"obs": obs[:, nb:], "mask": emitted[:, nb:], "action_mask": legal[:, nb:]}}
 
     # ------------------------------------------------------------------ dict API
     def step_dicts(self, action_dicts, auto_reset: bool = False, seed0: int = 0):
@@ -252,6 +270,7 @@ class VectorCollectiveCrossing:
                 self._episodes[done] += 1
                 seeds = (seed0 + self._episodes * E + np.arange(E)).astype(np.uint64)
                 obs = self.batch.reset(seeds, env_mask=done.astype(np.uint8))
+                self.batch.action_masks(out=self._masks)         # (the restarted envs stand somewhere else now)
                 with torch.cuda.stream(self.batch._stream):
                     m = torch.from_numpy(done).to(self._done.device)
                     self._done[m] = False

@@ -369,6 +369,42 @@ int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t
                       const uint8_t* actions, const uint8_t* order, int32_t auto_reset,
                       const ccx_rollout_out* out, uint8_t* actions_out);
 /*
+ * CCX_ACTION_MASKS: which of its five actions would actually move an agent -- what a masked policy needs once per step,
+ * on the device, next to the observations.  The reference answers it per agent and action through
+ * GreedyPolicy._is_valid_action -> env._is_move_valid (baseline_policies/greedy_policy.py:238-264,
+ * collectivecrossing.py:345-369); the policies' epsilon branch enumerates exactly that set (greedy_policy.py:51-57).
+ *
+ * `masks` is u8 [E][N], one byte per agent slot, and describes the state the handle holds when the call returns: behind
+ * the launch's last step, and behind an auto-reset if one happened.
+ *   - Agents the reference lists in env.agents (neither terminated nor truncated): bit a (a = 0..3: right, up, left,
+ *     down, the action ids) is set iff _is_valid_action(id, a, env) is true on that state -- the target cell passes
+ *     _is_valid_position (inclusive bounds, door row, tram walls) and no OTHER ACTIVE agent stands on it.  Bit 4 (wait)
+ *     is always set.
+ *   - Agents that are done: the byte is 0x10, wait only.  Done agents still block others according to their own `active`
+ *     flag, as in _is_position_occupied: truncated agents block, arrived ones do not.
+ *   - Bits 5-7 are zero.
+ * Tied to the step itself: for a live agent i that is still ACTIVE, bit a is set <=> a step whose action tensor is
+ * CCX_ACTION_ABSENT everywhere except actions[i] = a changes agent i's position, or a = 4.  (A live agent that has
+ * arrived -- inactive, kept in env.agents by all_at_destination until everyone is there -- is answered as the reference
+ * answers: _is_valid_action looks at the target cell only, while _move_agent, collectivecrossing.py:397-399, leaves an
+ * inactive agent where it is.  Its bits follow _is_valid_action.)
+ *
+ * ccx_action_masks       the masks of the current state, by a kernel of its own (any legal grid; one pass over an env's
+ *                        agents per thread).  Only enqueues on the handle's stream: it captures into a HIP graph.
+ * ccx_bind_action_masks  while a pointer is bound (NULL unbinds), every call that advances the state also leaves the
+ *                        masks of its final state there: ccx_step, ccx_rollout, ccx_rollout_policy, ccx_rollout_mixed and
+ *                        ccx_step_finish.  One env-step without a move order on a handle whose short launches take the
+ *                        step kernel (ccx_get_step_shape: ok = 1) writes them from that very launch (its sim wave does one
+ *                        more round on the occupancy table behind the step); every other call is followed by the
+ *                        stand-alone kernel on the same stream.  The bytes are the same either way.  The buffer is the
+ *                        caller's and must stay valid while bound.
+ * ccx_get_masks_fused    fused = 1 when such a call (num_steps, with / without a move order, mixed = through
+ *                        ccx_rollout_mixed) is ONE kernel with the masks bound, 0 when the stand-alone kernel follows it.
+ */
+int ccx_action_masks(ccx_handle* h, uint8_t* masks);
+int ccx_bind_action_masks(ccx_handle* h, uint8_t* masks_or_null);
+int ccx_get_masks_fused(ccx_handle* h, int32_t num_steps, int32_t has_order, int32_t mixed, int32_t* fused);
+/*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
  * `rng_seed` of ccx_rollout).  The action of agent slot a of global env g at step t (0-based) of its episode j is
