@@ -76,6 +76,15 @@ class CcxCounters(C.Structure):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
+class CcxEpisodeStats(C.Structure):
+    """``ccx_episode_stats``: device pointers of a handle's episode statistics (CCX_EPISODE_STATS)."""
+
+    _fields_ = [(name, C.c_void_p) for name in (
+        "ret", "live_steps", "steps", "closed", "finished", "last_ret", "last_live_steps", "last_steps", "last_end",
+        "log_env", "log_episode", "log_steps", "log_end", "log_ret", "log_live_steps", "log_count")] + [
+        ("log_capacity", C.c_int64)]
+
+
 COUNTER_FIELDS = tuple(name for name, _ in CcxCounters._fields_)
 
 _H = C.c_void_p  # ccx_handle*
@@ -116,6 +125,13 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_action_masks": (C.c_int, [_H, C.c_void_p]),
     "ccx_bind_action_masks": (C.c_int, [_H, C.c_void_p]),
     "ccx_get_masks_fused": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "ccx_episode_stats_enable": (C.c_int, [_H, C.c_int64]),
+    "ccx_episode_stats_disable": (C.c_int, [_H]),
+    "ccx_episode_stats_view": (C.c_int, [_H, C.POINTER(CcxEpisodeStats)]),
+    "ccx_episode_stats_launches": (C.c_int, [_H, C.POINTER(C.c_int32)]),
+    "ccx_episode_stats_update": (C.c_int, [_H, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ccx_episode_stats_reset": (C.c_int, [_H, C.c_void_p]),
+    "ccx_episode_log_clear": (C.c_int, [_H]),
     "ccx_set_check_inputs": (C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),

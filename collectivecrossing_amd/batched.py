@@ -52,6 +52,42 @@ class RolloutResult:
     term_present: torch.Tensor | None = None  # u8 [K, E, N]: batches with array-form strategies only
 
 
+@dataclass
+class EpisodeStats:
+    """Zero-copy device views of a batch's episode statistics (``ccx_episode_stats``, include/ccx.h CCX_EPISODE_STATS):
+    they change with every tracked call.  ``ret`` / ``live_steps`` / ``steps`` belong to the episode in progress (``closed``
+    = it has ended and the env has not been restarted), ``last_*`` to the most recent finished one (zero before the
+    first), ``finished`` counts the finished episodes of every env since tracking was enabled."""
+
+    ret: torch.Tensor              # f64 [E, N]
+    live_steps: torch.Tensor       # i32 [E, N]
+    steps: torch.Tensor            # i32 [E]
+    closed: torch.Tensor           # u8  [E]
+    finished: torch.Tensor         # i32 [E]
+    last_ret: torch.Tensor         # f64 [E, N]
+    last_live_steps: torch.Tensor  # i32 [E, N]
+    last_steps: torch.Tensor       # i32 [E]
+    last_end: torch.Tensor         # u8  [E]: EF_ALL_TERMINATED | EF_ALL_TRUNCATED of the step that ended it
+    log_count: torch.Tensor        # i64 [2]: records stored, records dropped (the library's u64 pair)
+    log_capacity: int
+
+
+@dataclass
+class FinishedEpisodes:
+    """The stored records of the finished-episode log as NumPy arrays, in log order (:meth:`finished_episodes`)."""
+
+    env: np.ndarray         # i64 [R]: GLOBAL env index (env_offset + e): logs of shards concatenate
+    episode: np.ndarray     # i32 [R]: ordinal of the episode within its env since tracking was enabled
+    steps: np.ndarray       # i32 [R]
+    end: np.ndarray         # u8  [R]: 1 terminated, 2 truncated, 3 both
+    ret: np.ndarray         # f64 [R, N]
+    live_steps: np.ndarray  # i32 [R, N]
+    dropped: int            # records that found the log full
+
+    def __len__(self) -> int:
+        return len(self.env)
+
+
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
     return C.c_void_p(None if t is None else t.data_ptr())
 
@@ -174,6 +210,9 @@ class BatchedCollectiveCrossing:
         self._masks_buf: torch.Tensor | None = None      # u8 [E, N] behind StepResult.action_masks
         self._masks_bound = 0                            # the pointer ccx_bind_action_masks holds (0 = none)
         self._rollouts_with_obs = 0
+        self._tracking = False                           # track_episodes: every result-producing call updates the stats
+        self._stats_view: EpisodeStats | None = None
+        self._stats_raw = None
         if check_inputs is None:
             check_inputs = os.environ.get("CCX_CHECK_INPUTS", "0") not in ("", "0")
         if check_inputs:
@@ -376,6 +415,134 @@ class BatchedCollectiveCrossing:
         check(self._lib.ccx_get_masks_fused(self._h, int(num_steps), int(bool(order)), int(bool(mixed)), C.byref(v)))
         return bool(v.value)
 
+    # ------------------------------------------------------------------ episode statistics
+    def track_episodes(self, log_capacity: int | bool = 0) -> None:
+        """Episode returns and lengths on the device (``ccx_episode_stats_enable``, include/ccx.h CCX_EPISODE_STATS).
+        From now on every call that hands out rewards and flags -- ``step``, ``step_mixed``, ``step_finish``, ``rollout``,
+        ``rollout_mixed``, ``rollout_greedy`` / ``rollout_policy``, also on batches with array-form strategies -- is followed
+        by the update kernel on the buffers it hands out, on the handle's stream; a call that writes no trajectory
+        (``want_traj=False`` without ``out``) raises ``ValueError``.  ``log_capacity`` > 0 also keeps a log of that many
+        finished episodes (:meth:`finished_episodes`).  Calling it again starts from zero; ``track_episodes(False)`` turns
+        tracking off.  Synchronous."""
+        self._stats_view = self._stats_raw = None
+        if log_capacity is False:
+            if self._tracking:
+                self._tracking = False
+                check(self._lib.ccx_episode_stats_disable(self._h))
+            return
+        cap = 0 if log_capacity is True else int(log_capacity)
+        if cap < 0:
+            raise ValueError(f"log_capacity must be >= 0, got {log_capacity!r}")
+        check(self._lib.ccx_episode_stats_enable(self._h, cap))
+        self._tracking = True
+
+    def _need_tracking(self) -> None:
+        if not self._tracking:
+            raise RuntimeError("episode statistics are not tracked: call track_episodes() first")
+
+    def _stats_struct(self):
+        if self._stats_raw is None:
+            self._need_tracking()
+            raw = _abi.CcxEpisodeStats()
+            check(self._lib.ccx_episode_stats_view(self._h, C.byref(raw)))
+            self._stats_raw = raw
+        return self._stats_raw
+
+    def _dev_view(self, ptr, count, typestr, dtype, shape) -> torch.Tensor:
+        return torch.as_tensor(_CudaArrayView(ptr, count, typestr), device=self.device).view(dtype).view(shape)
+
+    def episode_stats(self) -> EpisodeStats:
+        """:class:`EpisodeStats`: zero-copy views of the handle's own buffers (valid until tracking is turned off or
+        enabled again).  Reading them needs the handle's stream to be done (``synchronize()``, or work on that stream)."""
+        if self._stats_view is None:
+            v = self._stats_struct()
+            E, N = self.num_envs, self.num_agents
+            en, dv = E * N, self._dev_view
+            self._stats_view = EpisodeStats(
+                dv(v.ret, en, "<f8", torch.float64, (E, N)), dv(v.live_steps, en, "<i4", torch.int32, (E, N)),
+                dv(v.steps, E, "<i4", torch.int32, (E,)), dv(v.closed, E, "|u1", torch.uint8, (E,)),
+                dv(v.finished, E, "<i4", torch.int32, (E,)), dv(v.last_ret, en, "<f8", torch.float64, (E, N)),
+                dv(v.last_live_steps, en, "<i4", torch.int32, (E, N)), dv(v.last_steps, E, "<i4", torch.int32, (E,)),
+                dv(v.last_end, E, "|u1", torch.uint8, (E,)), dv(v.log_count, 2, "<i8", torch.int64, (2,)),
+                int(v.log_capacity))
+        return self._stats_view
+
+    def episode_stats_launches(self) -> int:
+        """Kernels one update enqueues (``ccx_episode_stats_launches``): 1 without a log, 3 with one."""
+        n = C.c_int32()
+        check(self._lib.ccx_episode_stats_launches(self._h, C.byref(n)))
+        return int(n.value)
+
+    def update_episode_stats(self, reward: torch.Tensor, agent_flags: torch.Tensor, env_flags: torch.Tensor) -> None:
+        """Feed a trajectory the caller holds (``ccx_episode_stats_update``): ``reward`` f64 [K, E, N], ``agent_flags`` u8
+        [K, E, N], ``env_flags`` u8 [K, E] (or one step without the leading axis), contiguous device tensors.  Only
+        enqueues on the handle's stream."""
+        self._need_tracking()
+        E, N = self.num_envs, self.num_agents
+        for name, t, dt in (("reward", reward, torch.float64), ("agent_flags", agent_flags, torch.uint8),
+                            ("env_flags", env_flags, torch.uint8)):
+            if not isinstance(t, torch.Tensor) or t.dtype is not dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dt} tensor on {self.device}")
+        if reward.dim() == 2:
+            reward, agent_flags, env_flags = reward[None], agent_flags[None], env_flags[None]
+        K = int(reward.shape[0]) if reward.dim() == 3 else 0
+        if K < 1 or tuple(reward.shape) != (K, E, N) or tuple(agent_flags.shape) != (K, E, N) or tuple(env_flags.shape) != (K, E):
+            raise ValueError(f"expected reward / agent_flags [K, {E}, {N}] and env_flags [K, {E}], got {tuple(reward.shape)}, "
+                             f"{tuple(agent_flags.shape)}, {tuple(env_flags.shape)}")
+        self._order_after_current_stream(reward, agent_flags, env_flags)
+        check(self._lib.ccx_episode_stats_update(self._h, K, reward.data_ptr(), agent_flags.data_ptr(), env_flags.data_ptr()))
+
+    def _track(self, K: int, res) -> None:
+        """The update behind a tracked call, on the buffers that call hands out."""
+        if res is None or res.reward is None or res.agent_flags is None or res.env_flags is None:
+            raise ValueError("episode statistics are tracked (track_episodes): this call must write rewards and flags "
+                             "(want_traj=True, or an `out` with reward, agent_flags and env_flags)")
+        check(self._lib.ccx_episode_stats_update(self._h, K, res.reward.data_ptr(), res.agent_flags.data_ptr(),
+                                                 res.env_flags.data_ptr()))
+
+    def _track_check(self, out, want_traj: bool) -> None:
+        """Refuse BEFORE the state advances: a tracked call without a trajectory would lose its steps."""
+        if self._tracking and ((out is None and not want_traj) or
+                               (out is not None and (out.reward is None or out.agent_flags is None or out.env_flags is None))):
+            raise ValueError("episode statistics are tracked (track_episodes): this call must write rewards and flags "
+                             "(want_traj=True, or an `out` with reward, agent_flags and env_flags)")
+
+    def reset_episode_stats(self, env_mask=None) -> None:
+        """Forget the episode in progress of the masked envs (all by default): running return, lengths and the latch go
+        to zero; no record is written, ``finished`` and ``last_*`` stay (``ccx_episode_stats_reset``).  ``reset`` and
+        ``reset_from_pool`` do this for the envs they restart.  Only enqueues."""
+        self._need_tracking()
+        m = None if env_mask is None else self._as_dev_u8(env_mask, (self.num_envs,))
+        check(self._lib.ccx_episode_stats_reset(self._h, _ptr(m)))
+
+    def finished_episodes(self, clear: bool = True) -> FinishedEpisodes:
+        """Synchronise and return the stored records of the log (:class:`FinishedEpisodes`; needs
+        ``track_episodes(log_capacity > 0)``).  One update's records follow those of earlier updates in env-major order.
+        ``clear=True`` empties the log afterwards (``ccx_episode_log_clear``)."""
+        v = self._stats_struct()
+        cap, N = int(v.log_capacity), self.num_agents
+        if cap <= 0:
+            raise RuntimeError("no finished-episode log: call track_episodes(log_capacity=...) with a capacity")
+        self.synchronize()
+        stored, dropped = (int(x) for x in self.episode_stats().log_count.cpu().numpy())
+        dv = self._dev_view
+
+        def host(ptr, count, typestr, dtype, shape):
+            return dv(ptr, count, typestr, dtype, shape)[:stored].cpu().numpy()
+
+        rec = FinishedEpisodes(host(v.log_env, cap, "<i8", torch.int64, (cap,)), host(v.log_episode, cap, "<i4", torch.int32, (cap,)),
+                               host(v.log_steps, cap, "<i4", torch.int32, (cap,)), host(v.log_end, cap, "|u1", torch.uint8, (cap,)),
+                               host(v.log_ret, cap * N, "<f8", torch.float64, (cap, N)),
+                               host(v.log_live_steps, cap * N, "<i4", torch.int32, (cap, N)), dropped)
+        if clear:
+            self.clear_episode_log()
+        return rec
+
+    def clear_episode_log(self) -> None:
+        """Empty the finished-episode log: stored = dropped = 0 (``ccx_episode_log_clear``).  Only enqueues."""
+        self._need_tracking()
+        check(self._lib.ccx_episode_log_clear(self._h))
+
     # ------------------------------------------------------------------ compute
     def observe(self, out: torch.Tensor | None = None) -> torch.Tensor:
         if out is None:
@@ -390,6 +557,8 @@ class BatchedCollectiveCrossing:
         self._step_masks(want_masks)
         if self._array_strategies:
             res = self._step_array(actions, order, want_obs, want_compact)
+            if self._tracking:
+                self._track(1, res)
             return res if not want_masks else StepResult(res.obs, res.reward, res.agent_flags, res.env_flags, res.obs_compact,
                                                          res.term_present, self._masks_buf)
         E, N = self.num_envs, self.num_agents
@@ -397,6 +566,8 @@ class BatchedCollectiveCrossing:
         o = None if order is None else self._as_dev_u8(order, (E, N))
         cached = self._step_out(_abi.CcxStepOut, want_obs, want_compact, want_masks)
         check(self._lib.ccx_step(self._h, a.data_ptr(), None if o is None else o.data_ptr(), cached[1]))
+        if self._tracking:
+            self._track(1, cached[2])
         return cached[2]
 
     def _step_out(self, struct, want_obs, want_compact, want_masks=False):
@@ -452,6 +623,8 @@ class BatchedCollectiveCrossing:
         check(self._lib.ccx_rollout_mixed(self._h, 1, pol, mask, None if a is None else a.data_ptr(),
                                           None if o is None else o.data_ptr(), 0, cached[1],
                                           None if actions_out is None else actions_out.data_ptr()))
+        if self._tracking:
+            self._track(1, cached[2])
         return cached[2]
 
     def _check_actions_out(self, t, shape) -> None:
@@ -486,6 +659,7 @@ class BatchedCollectiveCrossing:
             raise ValueError("auto_reset needs a reset pool (set_reset_pool / make_reset_pool)")
         if actions_out is not None:
             self._check_actions_out(actions_out, (K, E, N))
+        self._track_check(out, want_traj)
         if out is None and want_traj:
             out = self.alloc_rollout(K, want_obs, want_compact)
         ro = None
@@ -494,6 +668,8 @@ class BatchedCollectiveCrossing:
                                             _ptr(out.env_flags).value, _ptr(out.obs_compact).value))
         check(self._lib.ccx_rollout_mixed(self._h, K, pol, mask, _ptr(a), _ptr(o), int(bool(auto_reset)), ro,
                                           _ptr(actions_out)))
+        if self._tracking:
+            self._track(K, out)
         return out
 
     # ------------------------------------------------------------------ the split step / array-form strategies
@@ -567,7 +743,10 @@ class BatchedCollectiveCrossing:
             kinds = [k for k, v in (("reward", r), ("termination", t), ("truncation", u)) if v is None]
             own = self.run_array_strategies(kinds)
             r, t, u = (v if v is not None else o for v, o in zip((r, t, u), own))
-        return self._finish(r, t, u, want_obs, want_compact, auto_reset)
+        res = self._finish(r, t, u, want_obs, want_compact, auto_reset)
+        if self._tracking:
+            self._track(1, res)
+        return res
 
     def _finish(self, r, t, u, want_obs, want_compact, auto_reset) -> StepResult:
         E, N = self.num_envs, self.num_agents
@@ -625,6 +804,7 @@ class BatchedCollectiveCrossing:
         E, N = self.num_envs, self.num_agents
         if auto_reset and self._pool is None:
             raise ValueError("auto_reset needs a reset pool (set_reset_pool / make_reset_pool)")
+        self._track_check(out, want_traj)
         if out is None and want_traj:
             out = self.alloc_rollout(K, want_obs, want_compact)
             out.term_present = self._new((K, E, N), torch.uint8)
@@ -639,6 +819,8 @@ class BatchedCollectiveCrossing:
                 self.step_begin(a)
             r, t, u = self.run_array_strategies()
             self._finish_into(r, t, u, out, s, auto_reset)
+        if self._tracking:
+            self._track(K, out)
         return out
 
     def rows_alignment(self) -> int:
@@ -760,6 +942,7 @@ class BatchedCollectiveCrossing:
         self._bind_masks(None if masks_out is None else self._check_masks(masks_out))
         if self._array_strategies:
             return self._rollout_array(K, a, o, None, auto_reset, out, want_traj, want_obs, want_compact, None)
+        self._track_check(out, want_traj)
         if out is None and want_traj:
             out = self.alloc_rollout(K, want_obs, want_compact)
         if out is not None:
@@ -767,6 +950,8 @@ class BatchedCollectiveCrossing:
                                     _ptr(out.agent_flags).value, _ptr(out.env_flags).value, _ptr(out.obs_compact).value)
             check(self._lib.ccx_rollout(self._h, K, _ptr(a), _ptr(o), int(bool(auto_reset)), C.byref(ro)))
             self._rollouts_with_obs += int(out.obs is not None and K >= 64)
+            if self._tracking:
+                self._track(K, out)
         else:
             check(self._lib.ccx_rollout(self._h, K, _ptr(a), _ptr(o), int(bool(auto_reset)), None))
         return out
@@ -782,6 +967,7 @@ class BatchedCollectiveCrossing:
             actions_out = self._new((K, E, N), torch.uint8)
         if self._array_strategies:
             return self._rollout_array(K, None, None, policy, auto_reset, out, True, want_obs, False, actions_out), actions_out
+        self._track_check(out, True)
         if out is None:
             out = self.alloc_rollout(K, want_obs)
         ro = _abi.CcxRolloutOut(_ptr(out.obs).value, _ptr(out.reward).value,
@@ -789,6 +975,8 @@ class BatchedCollectiveCrossing:
         check(self._lib.ccx_rollout_policy(self._h, K, _abi.POLICIES[policy], int(bool(auto_reset)),
                                            C.byref(ro), _ptr(actions_out)))
         self._rollouts_with_obs += int(out.obs is not None and K >= 64)
+        if self._tracking:
+            self._track(K, out)
         return out, actions_out
 
     def rollout_policy(self, num_steps: int, policy: str, auto_reset: bool = False, **kw):

@@ -643,6 +643,7 @@ void ccx_destroy(ccx_handle* h) {
     (void)hipFree(h->mt_state);
     (void)hipFree(h->stream_actions);
     (void)hipFree(h->stream_obs);
+    ccxi::episode_stats_destroy(h);
     if (h->ev_start) (void)hipEventDestroy(h->ev_start);
     if (h->ev_stop) (void)hipEventDestroy(h->ev_stop);
     delete h;
@@ -732,6 +733,7 @@ int ccx_reset_from_pool(ccx_handle* h, const uint8_t* env_mask) {
     CCX_HIP(hipSetDevice(h->device));
     hipError_t e = ccx::launch_reset_from_pool(h->stream, h->kp, h->st, env_mask, h->pool);
     if (e != hipSuccess) return fail(CCX_EHIP, "reset kernel launch failed: %s", hipGetErrorString(e));
+    if (h->stats_on) return ccxi::episode_stats_reset(h, env_mask);
     return CCX_OK;
 }
 
@@ -766,6 +768,10 @@ int ccx_reset_seeded(ccx_handle* h, const uint64_t* seeds, const uint8_t* env_ma
     hipError_t e = ccx::launch_seeded_placement(h->stream, h->kp, h->E, seeds, 0, nullptr, h->st, env_mask,
                                                 h->placement_scratch, 1 << 16, h->counters + 7);
     if (e != hipSuccess) return fail(CCX_EHIP, "placement kernel launch failed: %s", hipGetErrorString(e));
+    if (h->stats_on) {
+        const int rc = ccxi::episode_stats_reset(h, env_mask);
+        if (rc != CCX_OK) return rc;
+    }
     return finish_placement(h, "ccx_reset_seeded");
 }
 
@@ -1270,6 +1276,7 @@ int ccx_set_tunable(ccx_handle* h, const char* name, int32_t value) {
         {"step_kernel", &h->tun_step_kernel, -1, 1},
         {"step_rows", &h->tun_step_rows, 0, 7},
         {"step_lanes", &h->tun_step_lanes, 0, 64},
+        {"stats_naive", &h->tun_stats_naive, 0, 1},
     };
     for (auto& t : table)
         if (strcmp(name, t.name) == 0) {
@@ -1278,7 +1285,7 @@ int ccx_set_tunable(ccx_handle* h, const char* name, int32_t value) {
             *t.slot = value;
             return choose_shape(h);
         }
-    return fail(CCX_EINVAL, "unknown tunable '%s' (pace_phase, tile_map, hand2, writer_roles, max_launch_steps, pair_rows, small_shape, round_launches, occ_tables, step_kernel, step_rows, step_lanes)", name);
+    return fail(CCX_EINVAL, "unknown tunable '%s' (pace_phase, tile_map, hand2, writer_roles, max_launch_steps, pair_rows, small_shape, round_launches, occ_tables, step_kernel, step_rows, step_lanes, stats_naive)", name);
 }
 
 int ccx_get_step_pace(ccx_handle* h, float* ns_per_env_step) {

@@ -14,6 +14,11 @@ namespace ccxi {
 // records the thread-local message returned by ccx_last_error() and hands the code back
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// CCX_EPISODE_STATS (ccx_episode_stats.hip): zero the running accumulators and the latch of the masked envs on the handle's
+// stream (the resets call it while tracking is on); free the buffers (ccx_destroy)
+int episode_stats_reset(struct ::ccx_handle* h, const uint8_t* env_mask);
+void episode_stats_destroy(struct ::ccx_handle* h);
+
 }  // namespace ccxi
 
 #define CCX_HIP(call)                                                                         \
@@ -82,5 +87,11 @@ struct ccx_handle {
     ccx::KParams kp_small{};
     uint32_t rng_lo = 0, rng_hi = 0;                            // seed of CCX_POLICY_RANDOM and of the epsilon draws (ccx_set_rng_seed)
     uint8_t* bound_masks = nullptr;                             // ccx_bind_action_masks: device u8 [E][N] (the caller's), null = not bound
+    bool stats_on = false;                                      // CCX_EPISODE_STATS: ccx_episode_stats_enable .. _disable
+    uint8_t* stats_slab = nullptr;                              // ONE allocation behind every array of `stats` and the two work arrays
+    ccx_episode_stats stats{};                                  // what ccx_episode_stats_view hands out
+    int32_t* stats_count = nullptr;                             // device i32 [E]: records of the current update per env (log only)
+    long long* stats_base = nullptr;                            // device i64 [E]: log slot of each env's first record of the update
+    int tun_stats_naive = 0;                                    // 1: the accumulate kernel with one dependent load per step (timing table only)
     uint32_t eps_thr = 0;                                       // epsilon * 2^32 of the scripted policies (ccx_set_policy_epsilon); the launchers copy the three into their KParams
 };

@@ -405,6 +405,82 @@ int ccx_action_masks(ccx_handle* h, uint8_t* masks);
 int ccx_bind_action_masks(ccx_handle* h, uint8_t* masks_or_null);
 int ccx_get_masks_fused(ccx_handle* h, int32_t num_steps, int32_t has_order, int32_t mixed, int32_t* fused);
 /*
+ * CCX_EPISODE_STATS: how the episodes went -- per-agent episode returns and episode lengths, accumulated on the device from
+ * the reward / flag arrays a step or a rollout wrote, plus an optional log of finished episodes.  The reference's demos end
+ * with exactly this: examples/waiting_policy_demo.py:52-85 (`total_reward += reward`, the step count) and
+ * examples/training_script.py:95-97 (episode_return_min / mean / max).  Opt-in per handle; nothing else changes behaviour.
+ *
+ * Per env e the handle keeps
+ *   running accumulators  ret f64 [E][N], live_steps i32 [E][N], steps i32 [E];
+ *   a latch               closed u8 [E];
+ *   finished i32 [E]      records this env has emitted since enable;
+ *   the most recent finished episode: last_ret f64 [E][N], last_live_steps i32 [E][N], last_steps i32 [E], last_end u8 [E]
+ *                         (all zero before the first finished episode).
+ * ccx_episode_stats_update walks the steps s = 0 .. num_steps - 1 of its arrays in order, with af = agent_flags[s][e][a]
+ * and ef = env_flags[s][e]:
+ *   1. if not closed: steps += 1, and for every agent with af & CCX_AF_LIVE: ret = ret + reward[s][e][a], live_steps += 1.
+ *      ONE f64 add per step, in step order: no reassociation, no compensation -- the bits of the reference's left-to-right
+ *      `total += reward`.  Reward values of agents that are not live are never read into the sum.
+ *   2. if ef & (CCX_EF_ALL_TERMINATED | CCX_EF_ALL_TRUNCATED) and not closed: emit a record (global env index
+ *      env_offset + e, episode ordinal = finished, steps, end = ef & 3, ret[.], live_steps[.]), copy it into last_*,
+ *      finished += 1, closed = 1.
+ *   3. if ef & CCX_EF_RESET: ret, live_steps, steps = 0 and closed = 0.
+ * The latch is what makes step-wise loops without auto-reset right: `__all__` stays raised step after step once an env is
+ * done and not restarted, and only the first raise ends the episode.
+ *
+ * Log (optional, log_capacity = C records, struct of arrays): log_env i64 [C], log_episode i32 [C], log_steps i32 [C],
+ * log_end u8 [C], log_ret f64 [C][N], log_live_steps i32 [C][N], and log_count u64 [2] = { stored, dropped }.  The records
+ * of ONE update are appended behind those of earlier updates in env-major order (ascending e, then ascending s): counted per
+ * env, placed by an exclusive scan, then written -- no atomic decides the order.  Records that would land at or beyond C
+ * are dropped and counted exactly.  The log pointers are NULL when C = 0 (log_count stays { 0, 0 }).
+ *
+ * ccx_episode_stats_enable   synchronous; allocates the buffers and zeroes everything; log_capacity 0 = no log; calling it
+ *                            again reallocates (and zeroes).
+ * ccx_episode_stats_disable  turns tracking off and frees the buffers (synchronises the handle's stream).
+ * ccx_episode_stats_view     the device pointers of the handle's own buffers (valid until disable / enable / destroy).
+ * ccx_episode_stats_update   reward f64 [K][E][N], agent_flags u8 [K][E][N], env_flags u8 [K][E] (what ccx_rollout_out /
+ *                            ccx_step_out hold).  Only enqueues on the handle's stream: no host synchronisation, no allocation,
+ *                            and it captures into a HIP graph.  A pure function of its three arrays and the accumulators -- it
+ *                            never reads the env state -- so the same bytes cut into any sequence of calls leave the same
+ *                            accumulators and the same set of records.  A NULL array, num_steps < 1, or tracking that is
+ *                            not enabled: CCX_EINVAL.  Offsets are 64-bit (K E N may exceed 2^31).
+ * ccx_episode_stats_launches kernels one update enqueues: 1 without a log (accumulate + last_*), 3 with one (records per
+ *                            env from env_flags and the latch; exclusive scan + log fill level; accumulate + write records).
+ * ccx_episode_stats_reset    env_mask device u8 [E], NULL = all envs: zeroes ret, live_steps, steps and the latch of the
+ *                            masked envs; writes no record; leaves finished and last_* alone.  Only enqueues.
+ * ccx_episode_log_clear      stored = dropped = 0.  Only enqueues.
+ * While tracking is enabled ccx_reset_from_pool and ccx_reset_seeded call ccx_episode_stats_reset with their own mask (a
+ * restarted env starts a new episode); ccx_set_state_host does NOT (it overwrites any part of the state, an episode
+ * boundary is the caller's to declare).
+ */
+typedef struct ccx_episode_stats {
+    double*   ret;              /* [E][N] */
+    int32_t*  live_steps;       /* [E][N] */
+    int32_t*  steps;            /* [E]    */
+    uint8_t*  closed;           /* [E]    */
+    int32_t*  finished;         /* [E]    */
+    double*   last_ret;         /* [E][N] */
+    int32_t*  last_live_steps;  /* [E][N] */
+    int32_t*  last_steps;       /* [E]    */
+    uint8_t*  last_end;         /* [E]    */
+    int64_t*  log_env;          /* [C]    */
+    int32_t*  log_episode;      /* [C]    */
+    int32_t*  log_steps;        /* [C]    */
+    uint8_t*  log_end;          /* [C]    */
+    double*   log_ret;          /* [C][N] */
+    int32_t*  log_live_steps;   /* [C][N] */
+    uint64_t* log_count;        /* [2] = { stored, dropped } */
+    int64_t   log_capacity;     /* C */
+} ccx_episode_stats;
+int ccx_episode_stats_enable(ccx_handle* h, int64_t log_capacity);
+int ccx_episode_stats_disable(ccx_handle* h);
+int ccx_episode_stats_view(ccx_handle* h, ccx_episode_stats* out);
+int ccx_episode_stats_launches(ccx_handle* h, int32_t* launches);
+int ccx_episode_stats_update(ccx_handle* h, int32_t num_steps, const double* reward /* [K][E][N] */,
+                             const uint8_t* agent_flags /* [K][E][N] */, const uint8_t* env_flags /* [K][E] */);
+int ccx_episode_stats_reset(ccx_handle* h, const uint8_t* env_mask);
+int ccx_episode_log_clear(ccx_handle* h);
+/*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
  * `rng_seed` of ccx_rollout).  The action of agent slot a of global env g at step t (0-based) of its episode j is
@@ -576,6 +652,8 @@ int ccx_get_pace_start(ccx_handle* h, float* ns_per_env_step, int32_t* source, f
  *                  that are not paced use a ring of hand-off words with a sequence word and per-writer progress words in
  *                  LDS (no barrier; paced launches keep one workgroup barrier per step, which regularises their store
  *                  stream), 0 = a barrier per step always, 2 = the ring always
+ *   "stats_naive"  1 = ccx_episode_stats_update runs its accumulate kernel with one dependent load per step (what the
+ *                  pipelined loads are measured against, profiles/episode_stats_timing.py); 0 (default) = pipelined
  *   "max_launch_steps"  > 0: ccx_rollout cuts a rollout into kernel launches of at most this many env-steps (the library
  *                  does so by itself where one launch would exceed 4 GiB per small output stream); 0 = automatic
  *   "pair_rows"    in small batches (role-split writers, launches that are not paced) every writer can get a second
