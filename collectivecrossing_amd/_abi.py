@@ -125,6 +125,9 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_action_masks": (C.c_int, [_H, C.c_void_p]),
     "ccx_bind_action_masks": (C.c_int, [_H, C.c_void_p]),
     "ccx_get_masks_fused": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "ccx_set_reset_obs": (C.c_int, [_H, C.c_int32]),
+    "ccx_bind_final_obs": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
+    "ccx_get_reset_obs_fused": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "ccx_episode_stats_enable": (C.c_int, [_H, C.c_int64]),
     "ccx_episode_stats_disable": (C.c_int, [_H]),
     "ccx_episode_stats_view": (C.c_int, [_H, C.POINTER(CcxEpisodeStats)]),

@@ -40,6 +40,8 @@ class StepResult:
     obs_compact: torch.Tensor | None = None   # f32 [E, N, 4]  (x, y, type, active), CCX_OBS_COMPACT
     term_present: torch.Tensor | None = None  # u8 [E, N]: 1 where terminateds[id] exists (step_finish / array-form strategies)
     action_masks: torch.Tensor | None = None  # u8 [E, N]: legal actions of the state behind the step (want_masks; unpack_action_masks)
+    final_obs: torch.Tensor | None = None     # f32 [E, N, L]: reset_obs="next": terminal rows of the envs with EF_RESET (other rows: untouched)
+    final_compact: torch.Tensor | None = None  # f32 [E, N, 4]: likewise
 
 
 @dataclass
@@ -50,6 +52,8 @@ class RolloutResult:
     env_flags: torch.Tensor | None    # u8 [K, E]
     obs_compact: torch.Tensor | None = None   # f32 [K, E, N, 4], CCX_OBS_COMPACT
     term_present: torch.Tensor | None = None  # u8 [K, E, N]: batches with array-form strategies only
+    final_obs: torch.Tensor | None = None     # f32 [K, E, N, L]: reset_obs="next": terminal rows at the (s, e) with EF_RESET (alloc_rollout(want_final=True))
+    final_compact: torch.Tensor | None = None  # f32 [K, E, N, 4]: likewise; rows of (s, e) without EF_RESET are never written
 
 
 @dataclass
@@ -99,6 +103,7 @@ def _check_cell_px(cell_px) -> int:
     return int(cell_px)
 
 
+RESET_OBS_MODES = {"terminal": 0, "next": 1}   # CCX_RESET_OBS_TERMINAL / CCX_RESET_OBS_NEXT (include/ccx.h: CCX_RESET_OBS)
 ACTION_MASK_WAIT_ONLY = 0x10   # the mask byte of an agent that is terminated or truncated
 
 
@@ -209,6 +214,10 @@ class BatchedCollectiveCrossing:
         self._step_out_cache: dict = {}
         self._masks_buf: torch.Tensor | None = None      # u8 [E, N] behind StepResult.action_masks
         self._masks_bound = 0                            # the pointer ccx_bind_action_masks holds (0 = none)
+        self._reset_obs_mode = 0                         # what ccx_set_reset_obs holds
+        self._final_bound = (0, 0)                       # the pointers ccx_bind_final_obs holds
+        self._final_keep: list = [None, None]            # ... and the tensors behind them, alive while bound
+        self._final_bufs: list = [None, None]            # f32 [E, N, L] / [E, N, 4] behind StepResult.final_* (step_finish)
         self._rollouts_with_obs = 0
         self._tracking = False                           # track_episodes: every result-producing call updates the stats
         self._stats_view: EpisodeStats | None = None
@@ -413,6 +422,62 @@ class BatchedCollectiveCrossing:
         mask kernel on the same stream.  The bytes are the same either way."""
         v = C.c_int32()
         check(self._lib.ccx_get_masks_fused(self._h, int(num_steps), int(bool(order)), int(bool(mixed)), C.byref(v)))
+        return bool(v.value)
+
+    # ------------------------------------------------------------------ reset-observation mode
+    def _reset_obs(self, mode: str, final_obs: torch.Tensor | None = None, final_compact: torch.Tensor | None = None,
+                   like=(None, None)) -> None:
+        """Select what the rows of a restarted env hold for the next call (``ccx_set_reset_obs``) and bind the side buffers
+        of its terminal rows (``ccx_bind_final_obs``); only CHANGES reach the library (this is on the per-step path)."""
+        try:
+            m = RESET_OBS_MODES[mode]
+        except (KeyError, TypeError):
+            raise ValueError(f"reset_obs must be 'terminal' or 'next', got {mode!r}") from None
+        if m != self._reset_obs_mode:
+            check(self._lib.ccx_set_reset_obs(self._h, m))
+            self._reset_obs_mode = m
+        # The mode and the two pointers are STICKY on the handle (include/ccx.h) and only the paths that take `reset_obs=`
+        # refresh them: every such call rebinds (a "terminal" call unbinds), and the batch holds the bound tensors
+        # (_final_keep) so that the handle never keeps a pointer into freed memory.  A new caller of ccx_step_finish /
+        # ccx_rollout_mixed / ccx_rollout with auto_reset=1 must come through here first.
+        ptrs, keep = [0, 0], [None, None]
+        if m:
+            for n, (t, ref, name) in enumerate(((final_obs, like[0], "final_obs"), (final_compact, like[1], "final_compact"))):
+                if t is None or ref is None:
+                    continue
+                if (not isinstance(t, torch.Tensor) or t.dtype is not torch.float32 or t.device != self.device
+                        or tuple(t.shape) != tuple(ref.shape) or not t.is_contiguous()):
+                    raise ValueError(f"{name} must be a contiguous torch.float32 tensor of shape {tuple(ref.shape)} on {self.device}")
+                ptrs[n], keep[n] = t.data_ptr(), t
+        self._final_keep = keep
+        if tuple(ptrs) != self._final_bound:
+            check(self._lib.ccx_bind_final_obs(self._h, C.c_void_p(ptrs[0] or None), C.c_void_p(ptrs[1] or None)))
+            self._final_bound = tuple(ptrs)
+
+    def _reset_obs_out(self, mode: str, out) -> None:
+        if out is None:
+            self._reset_obs(mode)
+        else:
+            self._reset_obs(mode, out.final_obs, out.final_compact, (out.obs, out.obs_compact))
+
+    def step_final_buffers(self, want_obs: bool = True, want_compact: bool = False):
+        """The batch's own one-step side buffers ``(final_obs f32 [E, N, L], final_compact f32 [E, N, 4])`` that
+        ``step_finish(reset_obs="next", want_final=True)`` fills at restarted envs and hands out as
+        ``StepResult.final_obs`` / ``final_compact`` (``None`` where not asked for here or earlier).  Allocated (zeroed) on
+        first use; rows of envs without ``EF_RESET`` are never written, so whatever the caller puts there stays."""
+        E, N = self.num_envs, self.num_agents
+        if want_obs and self._final_bufs[0] is None:
+            self._final_bufs[0] = self._new((E, N, self.obs_len), torch.float32).zero_()
+        if want_compact and self._final_bufs[1] is None:
+            self._final_bufs[1] = self._new((E, N, 4), torch.float32).zero_()
+        return tuple(self._final_bufs)
+
+    def reset_obs_fused(self, num_steps: int = 1, order: bool = False, mixed: bool = False) -> bool:
+        """Whether such a call with ``reset_obs="next"`` redirects the rows of restarted envs inside the step's own launch
+        (``ccx_get_reset_obs_fused``) -- one env-step from an action tensor without a move order on a batch whose short
+        launches take the step kernel -- or is followed by the fix-up kernel on the same stream.  Same bytes either way."""
+        v = C.c_int32(0)
+        check(self._lib.ccx_get_reset_obs_fused(self._h, int(num_steps), int(bool(order)), int(bool(mixed)), C.byref(v)))
         return bool(v.value)
 
     # ------------------------------------------------------------------ episode statistics
@@ -636,10 +701,11 @@ class BatchedCollectiveCrossing:
     def rollout_mixed(self, actions, scripted, policy: str = "greedy", order=None, auto_reset: bool = False,
                       out: RolloutResult | None = None, actions_out: torch.Tensor | None = None, num_steps: int | None = None,
                       want_obs: bool = True, want_traj: bool = True, want_compact: bool = False,
-                      masks_out: torch.Tensor | None = None) -> RolloutResult | None:
+                      masks_out: torch.Tensor | None = None, reset_obs: str = "terminal") -> RolloutResult | None:
         """K mixed-control steps (``ccx_rollout_mixed``; launches of at most 16 steps): ``actions`` u8 [K, E, N], or
         ``None`` with ``num_steps`` when every slot is scripted.  Mirrors :meth:`rollout`; ``actions_out`` (u8 [K, E, N])
-        receives the merged actions; ``masks_out`` (u8 [E, N]) the legal actions of the state behind the LAST step."""
+        receives the merged actions; ``masks_out`` (u8 [E, N]) the legal actions of the state behind the LAST step;
+        ``reset_obs`` as for :meth:`rollout`."""
         mask, pol = self._mixed_args(scripted, policy)
         self._bind_masks(None if masks_out is None else self._check_masks(masks_out))
         E, N = self.num_envs, self.num_agents
@@ -662,6 +728,7 @@ class BatchedCollectiveCrossing:
         self._track_check(out, want_traj)
         if out is None and want_traj:
             out = self.alloc_rollout(K, want_obs, want_compact)
+        self._reset_obs_out(reset_obs, out)
         ro = None
         if out is not None:
             ro = C.byref(_abi.CcxRolloutOut(_ptr(out.obs).value, _ptr(out.reward).value, _ptr(out.agent_flags).value,
@@ -725,12 +792,14 @@ class BatchedCollectiveCrossing:
         return t
 
     def step_finish(self, reward=None, terminated=None, truncated=None, want_obs: bool = True, want_compact: bool = False,
-                    auto_reset: bool = False) -> StepResult:
+                    auto_reset: bool = False, reset_obs: str = "terminal", want_final: bool = False) -> StepResult:
         """Second half of ``step`` (``ccx_step_finish``, collectivecrossing.py:214-259) with the caller's arrays in place of
         the strategies: ``reward`` f64 [E, N], ``terminated`` bool or int8 [E, N] (-1 = no ``terminateds[id]`` entry),
         ``truncated`` bool or uint8 [E, N]; ``None`` = the handle's built-in rule.  Reward and truncation values count
         where the agent was live before the step.  ``begin`` + ``finish()`` is ``step``.  ``auto_reset`` restarts envs
-        whose step raised ``__all__`` from the reset pool (``EF_RESET``), as ``rollout`` does.
+        whose step raised ``__all__`` from the reset pool (``EF_RESET``), as ``rollout`` does; ``reset_obs="next"`` then
+        leaves the restarted state's rows at those envs (:meth:`rollout`), and with ``want_final`` their terminal rows in
+        ``StepResult.final_obs`` / ``final_compact`` (rows of other envs there are never written).
 
         On a batch whose config names array-form classes, an argument left ``None`` is filled by the config's own class of
         that kind (:meth:`run_array_strategies`), never by the stand-in mode the handle was built with: ``step_begin`` +
@@ -743,14 +812,15 @@ class BatchedCollectiveCrossing:
             kinds = [k for k, v in (("reward", r), ("termination", t), ("truncation", u)) if v is None]
             own = self.run_array_strategies(kinds)
             r, t, u = (v if v is not None else o for v, o in zip((r, t, u), own))
-        res = self._finish(r, t, u, want_obs, want_compact, auto_reset)
+        res = self._finish(r, t, u, want_obs, want_compact, auto_reset, reset_obs, want_final)
         if self._tracking:
             self._track(1, res)
         return res
 
-    def _finish(self, r, t, u, want_obs, want_compact, auto_reset) -> StepResult:
+    def _finish(self, r, t, u, want_obs, want_compact, auto_reset, reset_obs: str = "terminal", want_final: bool = False) -> StepResult:
         E, N = self.num_envs, self.num_agents
-        key = (bool(want_obs), bool(want_compact))
+        want_final = bool(want_final) and reset_obs == "next"
+        key = (bool(want_obs), bool(want_compact), want_final)
         cached = self._finish_cache.get(key)
         if cached is None:
             if self._step_bufs is None:
@@ -763,9 +833,15 @@ class BatchedCollectiveCrossing:
                 self._term_present = self._new((E, N), torch.uint8)
             so = _abi.CcxStepOut(_ptr(b.obs if want_obs else None).value, _ptr(b.reward).value, _ptr(b.agent_flags).value,
                                  _ptr(b.env_flags).value, _ptr(b.obs_compact if want_compact else None).value)
+            if want_final:
+                self.step_final_buffers(want_obs, want_compact)
             cached = (so, C.byref(so), StepResult(b.obs if want_obs else None, b.reward, b.agent_flags, b.env_flags,
-                                                  b.obs_compact if want_compact else None, self._term_present))
+                                                  b.obs_compact if want_compact else None, self._term_present,
+                                                  final_obs=self._final_bufs[0] if want_final and want_obs else None,
+                                                  final_compact=self._final_bufs[1] if want_final and want_compact else None))
             self._finish_cache[key] = cached
+        res = cached[2]
+        self._reset_obs(reset_obs, res.final_obs, res.final_compact, (res.obs, res.obs_compact))
         check(self._lib.ccx_step_finish(self._h, _ptr(r), _ptr(t), _ptr(u), cached[1], _ptr(self._term_present),
                                         int(bool(auto_reset))))
         return cached[2]
@@ -790,13 +866,19 @@ class BatchedCollectiveCrossing:
         r, t, u = self.run_array_strategies()
         return self._finish(r, t, u, want_obs, want_compact, auto_reset)
 
-    def _finish_into(self, r, t, u, out: "RolloutResult | None", s: int, auto_reset: bool) -> None:
+    def _finish_into(self, r, t, u, out: "RolloutResult | None", s: int, auto_reset: bool, reset_obs: str = "terminal") -> None:
         fields = ("obs", "reward", "agent_flags", "env_flags", "obs_compact", "term_present")
+        if out is None:
+            self._reset_obs(reset_obs)
+        else:       # (the side buffers of step s: the slices of the result's own)
+            at = [None if v is None else v[s] for v in (out.final_obs, out.final_compact, out.obs, out.obs_compact)]
+            self._reset_obs(reset_obs, at[0], at[1], (at[2], at[3]))
         ptrs = [_ptr(None if out is None or getattr(out, f) is None else getattr(out, f)[s]) for f in fields]
         so = _abi.CcxStepOut(*(p.value for p in ptrs[:5]))
         check(self._lib.ccx_step_finish(self._h, _ptr(r), _ptr(t), _ptr(u), C.byref(so), ptrs[5], int(bool(auto_reset))))
 
-    def _rollout_array(self, K, actions, order, policy, auto_reset, out, want_traj, want_obs, want_compact, actions_out):
+    def _rollout_array(self, K, actions, order, policy, auto_reset, out, want_traj, want_obs, want_compact, actions_out,
+                       reset_obs: str = "terminal"):
         """``rollout`` / ``rollout_policy`` of a batch with array-form strategies: the split step once per tick (three
         launches plus the user's tensor code per step: launch-bound, not the fused kernel's speed).  A result allocated
         here carries ``term_present``; a caller's own ``out`` gets it only if its ``term_present`` is set; without a
@@ -818,7 +900,7 @@ class BatchedCollectiveCrossing:
                 a = self.policy_actions(policy, out=None if actions_out is None else actions_out[s])
                 self.step_begin(a)
             r, t, u = self.run_array_strategies()
-            self._finish_into(r, t, u, out, s, auto_reset)
+            self._finish_into(r, t, u, out, s, auto_reset, reset_obs)
         if self._tracking:
             self._track(K, out)
         return out
@@ -833,7 +915,10 @@ class BatchedCollectiveCrossing:
             m *= 2
         return m
 
-    def alloc_rollout(self, num_steps: int, want_obs: bool = True, want_compact: bool = False) -> RolloutResult:
+    def alloc_rollout(self, num_steps: int, want_obs: bool = True, want_compact: bool = False,
+                      want_final: bool = False) -> RolloutResult:
+        """Output tensors of a K-step rollout.  ``want_final``: also the side buffers ``final_obs`` / ``final_compact`` that
+        a ``reset_obs="next"`` call fills with the terminal rows of restarted envs (zeroed here; only those rows are written)."""
         K, E, N = num_steps, self.num_envs, self.num_agents
         if want_obs and K >= 32 and E % self.rows_alignment() and not getattr(self, "_warned_alignment", False):
             import warnings
@@ -844,7 +929,9 @@ class BatchedCollectiveCrossing:
         return RolloutResult(self._new((K, E, N, self.obs_len), torch.float32) if want_obs else None,
                              self._new((K, E, N), torch.float64), self._new((K, E, N), torch.uint8),
                              self._new((K, E), torch.uint8),
-                             self._new((K, E, N, 4), torch.float32) if want_compact else None)
+                             self._new((K, E, N, 4), torch.float32) if want_compact else None,
+                             final_obs=self._new((K, E, N, self.obs_len), torch.float32).zero_() if want_final and want_obs else None,
+                             final_compact=self._new((K, E, N, 4), torch.float32).zero_() if want_final and want_compact else None)
 
     def expand_observations(self, obs_compact: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
         """Compact rows ``[..., N, 4]`` -> DefaultObservation rows ``[..., N, L]`` on the device
@@ -930,9 +1017,14 @@ class BatchedCollectiveCrossing:
     def rollout(self, actions, order=None, auto_reset: bool = False,
                 out: RolloutResult | None = None, want_obs: bool = True,
                 want_traj: bool = True, want_compact: bool = False,
-                masks_out: torch.Tensor | None = None) -> RolloutResult | None:
+                masks_out: torch.Tensor | None = None, reset_obs: str = "terminal") -> RolloutResult | None:
         """K fused steps (``ccx_rollout``); ``actions`` u8 [K, E, N] on the device.  ``masks_out`` (u8 [E, N]) receives the
-        legal actions (:meth:`action_masks`) of the state behind the LAST step, after an auto-reset if one happened.  A batch with array-form user
+        legal actions (:meth:`action_masks`) of the state behind the LAST step, after an auto-reset if one happened.
+        ``reset_obs="next"`` (with ``auto_reset``): wherever ``env_flags`` carries ``EF_RESET``, ``obs`` / ``obs_compact``
+        hold the first observation of the episode that step opened -- what a policy fed from ``out.obs`` needs -- and the
+        terminal rows go to ``out.final_obs`` / ``out.final_compact`` when the result has them
+        (``alloc_rollout(want_final=True)``); rewards and flags keep describing the finished step (include/ccx.h:
+        CCX_RESET_OBS).  The default "terminal" writes the finished step's own rows.  A batch with array-form user
         strategies runs the split step once per tick instead (launch-bound: three launches plus the user's tensor code per
         step) into the same preallocated result, with ``term_present`` filled."""
         K = int(actions.shape[0])
@@ -941,10 +1033,11 @@ class BatchedCollectiveCrossing:
         o = None if order is None else self._as_dev_u8(order, (K, E, N))
         self._bind_masks(None if masks_out is None else self._check_masks(masks_out))
         if self._array_strategies:
-            return self._rollout_array(K, a, o, None, auto_reset, out, want_traj, want_obs, want_compact, None)
+            return self._rollout_array(K, a, o, None, auto_reset, out, want_traj, want_obs, want_compact, None, reset_obs)
         self._track_check(out, want_traj)
         if out is None and want_traj:
             out = self.alloc_rollout(K, want_obs, want_compact)
+        self._reset_obs_out(reset_obs, out)
         if out is not None:
             ro = _abi.CcxRolloutOut(_ptr(out.obs).value, _ptr(out.reward).value,
                                     _ptr(out.agent_flags).value, _ptr(out.env_flags).value, _ptr(out.obs_compact).value)
@@ -958,18 +1051,22 @@ class BatchedCollectiveCrossing:
 
     def rollout_greedy(self, num_steps: int, auto_reset: bool = False, out: RolloutResult | None = None,
                        want_obs: bool = True, actions_out: torch.Tensor | None = None,
-                       want_actions: bool = True, policy: str = "greedy", masks_out: torch.Tensor | None = None):
+                       want_actions: bool = True, policy: str = "greedy", masks_out: torch.Tensor | None = None,
+                       reset_obs: str = "terminal"):
         """K fused steps driven by an on-device scripted policy ("greedy" or "waiting",
-        ``ccx_rollout_policy``); returns ``(RolloutResult, actions u8 [K, E, N])``.  ``masks_out`` as for :meth:`rollout`."""
+        ``ccx_rollout_policy``); returns ``(RolloutResult, actions u8 [K, E, N])``.  ``masks_out`` and ``reset_obs`` as for
+        :meth:`rollout`."""
         K, E, N = int(num_steps), self.num_envs, self.num_agents
         self._bind_masks(None if masks_out is None else self._check_masks(masks_out))
         if actions_out is None and want_actions:
             actions_out = self._new((K, E, N), torch.uint8)
         if self._array_strategies:
-            return self._rollout_array(K, None, None, policy, auto_reset, out, True, want_obs, False, actions_out), actions_out
+            return self._rollout_array(K, None, None, policy, auto_reset, out, True, want_obs, False, actions_out,
+                                       reset_obs), actions_out
         self._track_check(out, True)
         if out is None:
             out = self.alloc_rollout(K, want_obs)
+        self._reset_obs_out(reset_obs, out)
         ro = _abi.CcxRolloutOut(_ptr(out.obs).value, _ptr(out.reward).value,
                                 _ptr(out.agent_flags).value, _ptr(out.env_flags).value, _ptr(out.obs_compact).value)
         check(self._lib.ccx_rollout_policy(self._h, K, _abi.POLICIES[policy], int(bool(auto_reset)),

@@ -254,7 +254,8 @@ int calibrate_pace(ccx_handle* h, float* obs, size_t obs_bytes) {
 
 int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* order, int auto_reset,
                 const ccx::KOut& out, int policy = 0, uint8_t* actions_out = nullptr, bool inputs_checked = false,
-                uint8_t* masks = nullptr, bool* masks_written = nullptr) {
+                uint8_t* masks = nullptr, bool* masks_written = nullptr, const ccx::StepResetObs* rso = nullptr,
+                bool* rso_written = nullptr) {
     // The writer waves address the small output streams (rewards, flag bytes, compact rows, chosen actions) with 32-bit
     // byte offsets from the stream's base: one launch must stay below 4 GiB per stream.  Longer rollouts are cut into
     // launches on the same stream (bit-identical: an env's trajectory does not depend on how a rollout is split).
@@ -283,6 +284,8 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
                 if (o.agent_flags) o.agent_flags += (size_t)k0 * EN;
                 if (o.env_flags) o.env_flags += (size_t)k0 * (size_t)h->E;
                 if (o.obs_compact) o.obs_compact += (size_t)k0 * EN * 4u;
+                // (the sub-launches get neither `masks` nor `rso`: a call that is cut leaves both to the stand-alone kernels
+                //  behind its LAST launch -- finish_masks, finish_reset_obs -- also where it is cut into single steps; same bytes)
                 const int rc = run_rollout(h, kk, actions ? actions + (size_t)k0 * EN : nullptr,
                                            order ? order + (size_t)k0 * EN : nullptr, auto_reset, o, policy,
                                            actions_out ? actions_out + (size_t)k0 * EN : nullptr, inputs_checked);
@@ -308,10 +311,14 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
         if (rc) return rc;
         // (bound action masks: this launch writes them itself where an MSK instantiation exists -- ccx_kernels.h)
         uint8_t* const m = ccx::step_masks_fused(K, order != nullptr) ? masks : nullptr;
+        // (CCX_RESET_OBS_NEXT: likewise where an RSO instantiation exists; finish_reset_obs serves the rest)
+        const ccx::StepResetObs* const r =
+            (h->tun_reset_obs_fused != 0 && ccx::step_reset_obs_fused(K, order != nullptr, false)) ? rso : nullptr;
         hipError_t e = ccx::launch_step(h->step_shape, h->stream, launch_params(h), h->st_slab, h->cell_info, actions, order, K, auto_reset,
-                                        h->pool, out, h->counters, nullptr, m);
+                                        h->pool, out, h->counters, nullptr, m, r);
         if (e != hipSuccess) return fail(CCX_EHIP, "step kernel launch failed: %s", hipGetErrorString(e));
         if (m && masks_written) *masks_written = true;
+        if (r && rso_written) *rso_written = true;
         return end_timed(h);
     }
     const bool writes_obs = out.obs != nullptr;
@@ -455,6 +462,36 @@ int finish_masks(ccx_handle* h, bool written) {
     if (!h->bound_masks || written) return CCX_OK;
     hipError_t e = ccx::launch_action_masks(h->stream, launch_params(h), h->st, h->cell_info, h->bound_masks);
     if (e != hipSuccess) return fail(CCX_EHIP, "action mask kernel launch failed: %s", hipGetErrorString(e));
+    return CCX_OK;
+}
+
+// CCX_RESET_OBS: does this call have rows to redirect at all?  (Without auto-reset or a pool no step raises CCX_EF_RESET.)
+bool reset_obs_on(const ccx_handle* h, const ccx::KOut& ko, int auto_reset) {
+    return h->reset_obs == CCX_RESET_OBS_NEXT && auto_reset != 0 && h->pool != nullptr && h->pool_size > 0 &&
+           (ko.obs != nullptr || ko.obs_compact != nullptr);
+}
+
+int check_reset_obs(const ccx_handle* h, const ccx::KOut& ko, int auto_reset) {
+    if (!reset_obs_on(h, ko, auto_reset)) return CCX_OK;
+    if (!ko.env_flags)
+        return fail(CCX_EINVAL, "CCX_RESET_OBS_NEXT: a call with auto-reset that asks for obs or obs_compact must pass env_flags "
+                    "too (the restarted envs are found there)");
+    const uintptr_t align = (h->N % 2) == 0 ? 15u : 7u;
+    if (ko.obs && h->bound_final_obs && (reinterpret_cast<uintptr_t>(h->bound_final_obs) & align))
+        return fail(CCX_EINVAL, "final_obs buffer must be %d-byte aligned", (int)align + 1);
+    if (ko.obs_compact && h->bound_final_compact && (reinterpret_cast<uintptr_t>(h->bound_final_compact) & 15u))
+        return fail(CCX_EINVAL, "final_compact buffer must be 16-byte aligned");
+    return CCX_OK;
+}
+
+// ... every call that wrote K steps of rows with auto-reset leaves the restarted rows at the CCX_EF_RESET pairs: written by
+// the step kernel itself (`written`), or by the fix-up kernel behind the call's last launch -- once for the whole call, from
+// the episode counters that launch left (ccx_reset_obs.hip)
+int finish_reset_obs(ccx_handle* h, int K, const ccx::KOut& ko, int auto_reset, bool written) {
+    if (written || !reset_obs_on(h, ko, auto_reset)) return CCX_OK;
+    hipError_t e = ccx::launch_reset_obs(h->stream, launch_params(h), h->st, K, ko.env_flags, h->pool, ko.obs, ko.obs_compact,
+                                         ko.obs ? h->bound_final_obs : nullptr, ko.obs_compact ? h->bound_final_compact : nullptr);
+    if (e != hipSuccess) return fail(CCX_EHIP, "reset-observation kernel launch failed: %s", hipGetErrorString(e));
     return CCX_OK;
 }
 
@@ -866,14 +903,17 @@ int ccx_step_finish(ccx_handle* h, const double* reward, const int8_t* terminate
         return fail(CCX_EINVAL, "reward buffers must be 8-byte aligned");
     if (ko.obs_compact && (reinterpret_cast<uintptr_t>(ko.obs_compact) & 15u))
         return fail(CCX_EINVAL, "obs_compact buffer must be 16-byte aligned");
+    int rc = check_reset_obs(h, ko, auto_reset);
+    if (rc) return rc;
     CCX_HIP(hipSetDevice(h->device));
-    int rc = begin_timed(h);
+    rc = begin_timed(h);
     if (rc) return rc;
     hipError_t e = ccx::launch_step_finish(h->shape, h->stream, h->kp, h->st, h->cell_info, reward, terminated, truncated, ko,
                                            term_present, auto_reset ? 1 : 0, h->pool, h->counters);
     if (e != hipSuccess) return fail(CCX_EHIP, "step_finish kernel launch failed: %s", hipGetErrorString(e));
     rc = end_timed(h);
-    return rc ? rc : finish_masks(h, false);
+    if (!rc) rc = finish_masks(h, false);
+    return rc ? rc : finish_reset_obs(h, 1, ko, auto_reset, false);
 }
 
 int ccx_rollout(ccx_handle* h, int32_t num_steps, const uint8_t* actions, const uint8_t* order,
@@ -890,9 +930,14 @@ int ccx_rollout(ccx_handle* h, int32_t num_steps, const uint8_t* actions, const 
         ko.env_flags = out->env_flags;
         ko.obs_compact = out->obs_compact;
     }
-    bool written = false;
-    const int rc = run_rollout(h, num_steps, actions, order, auto_reset ? 1 : 0, ko, 0, nullptr, false, h->bound_masks, &written);
-    return rc ? rc : finish_masks(h, written);
+    int rc = check_reset_obs(h, ko, auto_reset);
+    if (rc) return rc;
+    const ccx::StepResetObs rso{ko.obs ? h->bound_final_obs : nullptr, ko.obs_compact ? h->bound_final_compact : nullptr};
+    bool written = false, rso_written = false;
+    rc = run_rollout(h, num_steps, actions, order, auto_reset ? 1 : 0, ko, 0, nullptr, false, h->bound_masks, &written,
+                     reset_obs_on(h, ko, auto_reset) ? &rso : nullptr, &rso_written);
+    if (!rc) rc = finish_masks(h, written);
+    return rc ? rc : finish_reset_obs(h, num_steps, ko, auto_reset, rso_written);
 }
 
 int ccx_rollout_policy(ccx_handle* h, int32_t num_steps, int32_t policy, int32_t auto_reset,
@@ -911,6 +956,10 @@ int ccx_rollout_policy(ccx_handle* h, int32_t num_steps, int32_t policy, int32_t
         ko.env_flags = out->env_flags;
         ko.obs_compact = out->obs_compact;
     }
+    {
+        const int rc = check_reset_obs(h, ko, auto_reset);
+        if (rc) return rc;
+    }
     if (h->eps_stream == CCX_EPS_STREAM_MT19937 && policy != CCX_POLICY_RANDOM && h->epsilon > 0.0) {
         // The reference's stream is sequential per env: the policy runs as its own kernel between the steps (policy -> step
         // -> policy ..., each a launch on the handle's stream) instead of inside the fused one.  Meant for replaying the
@@ -927,11 +976,13 @@ int ccx_rollout_policy(ccx_handle* h, int32_t num_steps, int32_t policy, int32_t
             rc = stepwise_step(h, ko, s, acts, nullptr, auto_reset ? 1 : 0, false);
             if (rc) return rc;
         }
-        return finish_masks(h, false);
+        rc = finish_masks(h, false);
+        return rc ? rc : finish_reset_obs(h, num_steps, ko, auto_reset, false);
     }
     // (grids whose occupancy tables exceed the LDS run the in-kernel policies through the all-pairs exchange: round 4)
-    const int rc = run_rollout(h, num_steps, nullptr, nullptr, auto_reset ? 1 : 0, ko, policy, actions_out);
-    return rc ? rc : finish_masks(h, false);
+    int rc = run_rollout(h, num_steps, nullptr, nullptr, auto_reset ? 1 : 0, ko, policy, actions_out);
+    if (!rc) rc = finish_masks(h, false);
+    return rc ? rc : finish_reset_obs(h, num_steps, ko, auto_reset, false);
 }
 
 int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t scripted_slots,
@@ -959,6 +1010,10 @@ int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t
     if (ko.reward && (reinterpret_cast<uintptr_t>(ko.reward) & 7u)) return fail(CCX_EINVAL, "reward buffer must be 8-byte aligned");
     if (ko.obs_compact && (reinterpret_cast<uintptr_t>(ko.obs_compact) & 15u))
         return fail(CCX_EINVAL, "obs_compact buffer must be 16-byte aligned");
+    {
+        const int rc = check_reset_obs(h, ko, auto_reset);
+        if (rc) return rc;
+    }
     CCX_HIP(hipSetDevice(h->device));
     const size_t EN = (size_t)h->E * h->N;
     const bool fused = h->step_shape.ok && h->tun_step_kernel != 0;
@@ -984,7 +1039,8 @@ int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t
             rc = end_timed(h);
             if (rc) return rc;
         }
-        return finish_masks(h, m != nullptr);
+        const int rc = finish_masks(h, m != nullptr);
+        return rc ? rc : finish_reset_obs(h, num_steps, ko, auto_reset, false);
     }
     // Handles whose short launches cannot use the step kernel (tables beyond the LDS, or the tunable): the composition
     // itself, step by step on the handle's stream -- policy kernel, merge kernel, the existing step path.
@@ -1001,7 +1057,8 @@ int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t
         rc = stepwise_step(h, ko, s, acts, order ? order + (size_t)s * EN : nullptr, auto_reset ? 1 : 0, true);
         if (rc) return rc;
     }
-    return finish_masks(h, false);
+    rc = finish_masks(h, false);
+    return rc ? rc : finish_reset_obs(h, num_steps, ko, auto_reset, false);
 }
 
 int ccx_action_masks(ccx_handle* h, uint8_t* masks) {
@@ -1023,6 +1080,29 @@ int ccx_get_masks_fused(ccx_handle* h, int32_t num_steps, int32_t has_order, int
     if (num_steps < 1) return fail(CCX_EINVAL, "num_steps must be >= 1");
     (void)mixed;      // (both kinds of launch have their MSK instantiations: ccx_step.hip)
     *fused = (h->step_shape.ok && h->tun_step_kernel != 0 && ccx::step_masks_fused(num_steps, has_order != 0)) ? 1 : 0;
+    return CCX_OK;
+}
+
+int ccx_set_reset_obs(ccx_handle* h, int32_t mode) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (mode != CCX_RESET_OBS_TERMINAL && mode != CCX_RESET_OBS_NEXT)
+        return fail(CCX_EINVAL, "unknown reset-observation mode %d (CCX_RESET_OBS_TERMINAL, CCX_RESET_OBS_NEXT)", mode);
+    h->reset_obs = mode;
+    return CCX_OK;
+}
+
+int ccx_bind_final_obs(ccx_handle* h, float* final_obs_or_null, float* final_compact_or_null) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    h->bound_final_obs = final_obs_or_null;
+    h->bound_final_compact = final_compact_or_null;
+    return CCX_OK;
+}
+
+int ccx_get_reset_obs_fused(ccx_handle* h, int32_t num_steps, int32_t has_order, int32_t mixed, int32_t* fused) {
+    if (!h || !fused) return fail(CCX_EINVAL, "NULL argument");
+    if (num_steps < 1) return fail(CCX_EINVAL, "num_steps must be >= 1");
+    *fused = (h->step_shape.ok && h->tun_step_kernel != 0 && h->tun_reset_obs_fused != 0 &&
+              ccx::step_reset_obs_fused(num_steps, has_order != 0, mixed != 0)) ? 1 : 0;
     return CCX_OK;
 }
 
@@ -1277,6 +1357,7 @@ int ccx_set_tunable(ccx_handle* h, const char* name, int32_t value) {
         {"step_rows", &h->tun_step_rows, 0, 7},
         {"step_lanes", &h->tun_step_lanes, 0, 64},
         {"stats_naive", &h->tun_stats_naive, 0, 1},
+        {"reset_obs_fused", &h->tun_reset_obs_fused, 0, 1},
     };
     for (auto& t : table)
         if (strcmp(name, t.name) == 0) {
@@ -1285,7 +1366,7 @@ int ccx_set_tunable(ccx_handle* h, const char* name, int32_t value) {
             *t.slot = value;
             return choose_shape(h);
         }
-    return fail(CCX_EINVAL, "unknown tunable '%s' (pace_phase, tile_map, hand2, writer_roles, max_launch_steps, pair_rows, small_shape, round_launches, occ_tables, step_kernel, step_rows, step_lanes, stats_naive)", name);
+    return fail(CCX_EINVAL, "unknown tunable '%s' (pace_phase, tile_map, hand2, writer_roles, max_launch_steps, pair_rows, small_shape, round_launches, occ_tables, step_kernel, step_rows, step_lanes, stats_naive, reset_obs_fused)", name);
 }
 
 int ccx_get_step_pace(ccx_handle* h, float* ns_per_env_step) {

@@ -87,6 +87,10 @@ struct ccx_handle {
     ccx::KParams kp_small{};
     uint32_t rng_lo = 0, rng_hi = 0;                            // seed of CCX_POLICY_RANDOM and of the epsilon draws (ccx_set_rng_seed)
     uint8_t* bound_masks = nullptr;                             // ccx_bind_action_masks: device u8 [E][N] (the caller's), null = not bound
+    int reset_obs = 0;                                          // CCX_RESET_OBS_*: what obs[s][e] of a restarted env holds (ccx_set_reset_obs)
+    float* bound_final_obs = nullptr;                           // ccx_bind_final_obs: the caller's side buffers for the terminal rows, null = dropped
+    float* bound_final_compact = nullptr;
+    int tun_reset_obs_fused = 1;                                // 0: NEXT-mode single steps take the fix-up kernel too (timing table only)
     bool stats_on = false;                                      // CCX_EPISODE_STATS: ccx_episode_stats_enable .. _disable
     uint8_t* stats_slab = nullptr;                              // ONE allocation behind every array of `stats` and the two work arrays
     ccx_episode_stats stats{};                                  // what ccx_episode_stats_view hands out

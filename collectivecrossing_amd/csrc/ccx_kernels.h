@@ -225,16 +225,31 @@ struct StepPolicy {
     int policy;
     uint8_t* actions_out;
 };
+// CCX_RESET_OBS_NEXT inside the step launch (the RSO instantiations of ccx_step.hip): ONE env-step from a tensor, slot
+// order.  `rso` not null selects them: restarted envs get the rows of the restarted state, the terminal rows go to the
+// side buffers (null = dropped).  Every other launch is followed by launch_reset_obs.
+struct StepResetObs {
+    float* final_obs;
+    float* final_compact;
+};
+constexpr bool step_reset_obs_fused(int K, bool has_order, bool has_policy) { return K == 1 && !has_order && !has_policy; }
 hipError_t launch_step(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
                        const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K, int auto_reset,
                        const uint8_t* pool, const KOut& out, unsigned long long* counters, const StepPolicy* pol = nullptr,
-                       uint8_t* masks = nullptr);
+                       uint8_t* masks = nullptr, const struct StepResetObs* rso = nullptr);
 // Legal-action masks (include/ccx.h: CCX_ACTION_MASKS), u8 [E][N] of the handle's current state.  launch_step writes them
 // itself (`masks`) where step_masks_fused says so -- the MSK instantiations of ccx_step.hip: ONE env-step without a move
 // order, with or without a scripted policy; every other launch is followed by launch_action_masks on the same stream.
 constexpr bool step_masks_fused(int K, bool has_order) { return K == 1 && !has_order; }
 hipError_t launch_action_masks(hipStream_t stream, const KParams& p, const KState& st,
                                const unsigned long long* cell_info, uint8_t* masks);
+
+// CCX_RESET_OBS (include/ccx.h), the stand-alone fix-up kernel (ccx_reset_obs.hip): behind launches that wrote K steps of
+// rows / compact rows with auto-reset, the pairs (s, e) with CCX_EF_RESET in env_flags [K][E] get the rows of the restarted
+// state (pool entry of the episode that restart opened, worked back from st.episode AFTER the launches); the terminal
+// rows move to final_obs / final_compact where those are not null.  64-bit offsets.
+hipError_t launch_reset_obs(hipStream_t stream, const KParams& p, const KState& st, int K, const uint8_t* env_flags,
+                            const uint8_t* pool, float* obs, float* obs_compact, float* final_obs, float* final_compact);
 
 // the split step (ccx_split_step.hip): collectivecrossing.py:188-212, then :214-259 with the caller's reward / terminated /
 // truncated arrays (null = the handle's built-in rule); finish takes the lane layout of the observe kernel (ls, p)

@@ -29,7 +29,16 @@
 // Policy id, epsilon and the RNG words are run-time kernel arguments behind the preloaded ones.
 // MSK (ccx_bind_action_masks): behind the launch's last step the sim wave leaves the legal-action byte of every agent slot
 // for the state it writes back (include/ccx.h: CCX_ACTION_MASKS) -- one more round on the occupancy table, once per launch.
-// The output pointer is the LAST kernel argument; the other instantiations never look at it.
+// The output pointer is a trailing kernel argument; the other instantiations never look at it.
+// RSO (ccx_set_reset_obs: CCX_RESET_OBS_NEXT, K1 without ORD / POL): an env that restarts in this step gets the rows of its
+// RESTARTED state at obs / obs_compact, and the terminal rows go to final_obs / final_compact (the last two arguments; null
+// = dropped).  The sim wave stages the step's float4s in slot 0 as always but holds the hand-off barrier back until it has
+// been through the auto-reset: it then stages the state it carries on with in slot 1 (the idle half of the double buffer:
+// K = 1), leaves the ballot of the restarting lanes in that slot's pad words, and meets the row waves at the SAME single
+// barrier.  A row wave picks the destination of every unit BEFORE it stores: units of a restarted env (a unit never
+// straddles two envs: an env's rows are a whole number of units, 16 bytes for even N, 8 for odd) send the slot-0 value to
+// final_obs and the slot-1 value to obs; no address is stored twice.  Tiles without a restart -- nearly all of them -- see a
+// zero ballot and run the ordinary loop.
 // The first 14 argument dwords (state slab, actions, both tables, obs, E, shape words, max_steps) are preloaded into SGPRs
 // (csrc/Makefile: -amdgpu-kernarg-preload-count=14): -0.05 us per step, measured on this kernel.
 #include "ccx_rollout_dev.h"
@@ -78,7 +87,7 @@ template <int GLOG> struct RowBatch { static constexpr int value = GLOG <= 3 ? 8
 // POL: mixed control -- the slots of `scripted` are driven by the scripted policy `policy` (the trailing arguments are read
 //      by these instantiations only)
 // MSK: the launch also writes the legal-action masks of its final state (`masks`, the last argument)
-template <int GLOG, bool PAIR, bool K1, bool ORD, bool POL = false, bool MSK = false>
+template <int GLOG, bool PAIR, bool K1, bool ORD, bool POL = false, bool MSK = false, bool RSO = false>
 __global__ void __launch_bounds__(512)
 step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab layout
             const uint8_t* __restrict__ actions,                // u8 [K][E][N]
@@ -103,7 +112,10 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
             const uint32_t genv0,                                      // POL: global index of env 0 (low word)
             const int bdy, const int edy,                              // POL: destination rows
             uint8_t* __restrict__ actions_out,                         // POL: u8 [K][E][N] the actions taken, or null
-            uint8_t* __restrict__ masks) {                             // MSK: u8 [E][N] legal-action masks of the final state
+            uint8_t* __restrict__ masks,                               // MSK: u8 [E][N] legal-action masks of the final state
+            float* __restrict__ final_obs,                             // RSO: f32 [E][N][L] terminal rows of restarted envs, or null
+            float* __restrict__ final_compact) {                       // RSO: f32 [E][N][4] likewise, or null
+    static_assert(!RSO || (K1 && !ORD && !POL), "RSO: one env-step from a tensor, slot order");
     using mask_t = typename GroupMask<GLOG>::type;
     constexpr int G = 1 << GLOG;
     constexpr uint32_t msz = sizeof(mask_t);
@@ -175,6 +187,24 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
             lds_barrier();                                             // the sim wave has staged step s
             if (w == 0) CCX_ST(7);
             typedef __attribute__((address_space(3))) const v2f lds_f2;
+            // RSO: ballot of the sim wave's restarting lanes (pad words of slot 1), the side buffer's base, and
+            // ceil(2^32 / units per env) for "which env is unit q in" (exact: a tile has far fewer than 2^16 units)
+            unsigned long long rmask = 0;
+            uint32_t upe_magic = 0;
+            const char* fin_base = nullptr;
+            if constexpr (RSO) {
+                typedef __attribute__((address_space(3))) const uint32_t lds_u32;
+                const uint32_t ra = lds0 + off_ws + (uint32_t)sizeof(WSlot) + kObsCstOff + 24u;
+                const uint32_t r_lo = __builtin_amdgcn_readfirstlane((int)*(lds_u32*)(uintptr_t)ra);
+                const uint32_t r_hi = __builtin_amdgcn_readfirstlane((int)*(lds_u32*)(uintptr_t)(ra + 4u));
+                rmask = (unsigned long long)r_lo | ((unsigned long long)r_hi << 32);
+                if (rmask != 0) {
+                    const uint32_t upe = (uint32_t)(N * (3 + 2 * N)) >> (PAIR ? 1 : 0);
+                    upe_magic = 0xFFFFFFFFu / upe + 1u;
+                    if (final_obs != nullptr)
+                        fin_base = reinterpret_cast<const char*>(final_obs) + (size_t)env0 * (size_t)N * (size_t)L * 4u - lead * vbytes;
+                }
+            }
             for (uint32_t itb = it0; itb < it_end; itb += kRowBatch) {
                 uint32_t q[kRowBatch], tw[kRowBatch];
                 const bool cached = itb == it0 && lead == lead0;       // wave-uniform
@@ -193,6 +223,20 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
                 for (int j = 0; j < kRowBatch; ++j) {
                     if (itb + j < it_end && q[j] < n4) {
                         const uint32_t voff = ((uint32_t)lane + 64u * (itb + j)) * vbytes;
+                        if constexpr (RSO) {
+                            if (rmask != 0) {                           // (wave-uniform, rare)
+                                const uint32_t el = __umulhi(q[j], upe_magic);
+                                if ((rmask >> (el << GLOG)) & 1ull) {
+                                    if (fin_base != nullptr) {
+                                        if constexpr (PAIR) step_store_obs(v4f{va[j].x, va[j].y, vb[j].x, vb[j].y}, fin_base, voff);
+                                        else step_store_obs(va[j], fin_base, voff);
+                                    }
+                                    const uint32_t w1 = wl_abs + (uint32_t)sizeof(WSlot);
+                                    va[j] = *(lds_f2*)(uintptr_t)(w1 + (tw[j] & 0xFFFFu));
+                                    if constexpr (PAIR) vb[j] = *(lds_f2*)(uintptr_t)(w1 + (tw[j] >> 16));
+                                }
+                            }
+                        }
                         if constexpr (PAIR) step_store_obs(v4f{va[j].x, va[j].y, vb[j].x, vb[j].y}, base, voff);
                         else step_store_obs(va[j], base, voff);
                     }
@@ -545,7 +589,7 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
         const float4 me = make_float4((float)((ilo >> 16) & 0xFFu), (float)(ilo >> 24), type_f, (float)act);
         if (want_obs) {
             wl[s & 1].slot[lane] = me;
-            lds_barrier();
+            if constexpr (!RSO) lds_barrier();                         // (RSO: behind the auto-reset, below)
         }
         const uint32_t tind = (ilo >> (tsh + kCellTermShift)) & 1u;            // terminateds[id] as the cell says (ccx_kernels.h)
         const uint64_t ndest_b = __builtin_amdgcn_ballot_w64((validbit & ~tind) != 0);
@@ -582,7 +626,9 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
             }
             if (has_af) *(__attribute__((address_space(1))) uint8_t*)(b_af + o_af) = (uint8_t)af;
             if (has_ef && i == 0) *(__attribute__((address_space(1))) uint8_t*)(b_ef + o_ef) = (uint8_t)efw;
-            if (has_cmp) *(__attribute__((address_space(1))) v4f*)(b_cmp + o_cmp) = v4f{me.x, me.y, me.z, me.w};
+            if constexpr (!RSO) {
+                if (has_cmp) *(__attribute__((address_space(1))) v4f*)(b_cmp + o_cmp) = v4f{me.x, me.y, me.z, me.w};
+            }
             if constexpr (POL) {
                 if (has_ao) *(__attribute__((address_space(1))) uint8_t*)(b_ao + o_af) = (uint8_t)a_raw;
             }
@@ -614,6 +660,23 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
                     act = 1;
                     tt = 0;
                 }
+            }
+        }
+        if constexpr (RSO) {
+            // the state the env carries on with (the step's own for an env that did not restart): slot 1 and the ballot of
+            // the restarting lanes for the row waves, then the step's one hand-off barrier; the compact rows likewise, the
+            // destination chosen before anything is stored
+            const float4 nx = make_float4((float)((ilo >> 16) & 0xFFu), (float)(ilo >> 24), type_f, (float)act);
+            if (want_obs) {
+                wl[1].slot[lane] = nx;
+                if (lane == 0) *reinterpret_cast<unsigned long long*>(&wl[1].cst[6]) = reset_b;
+                lds_barrier();
+            }
+            if (valid && has_cmp) {
+                gchar* const c0 = (gchar*)obs_compact;
+                if (((reset_b >> lane) & 1ull) != 0 && final_compact != nullptr)
+                    *(__attribute__((address_space(1))) v4f*)((gchar*)final_compact + o_cmp) = v4f{me.x, me.y, me.z, me.w};
+                *(__attribute__((address_space(1))) v4f*)(c0 + o_cmp) = v4f{nx.x, nx.y, nx.z, nx.w};
             }
         }
     }
@@ -676,8 +739,14 @@ template <int GLOG>
 static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
                                 const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K,
                                 int auto_reset, const uint8_t* pool, const KOut& out, unsigned long long* counters,
-                                const StepPolicy* pol, uint8_t* masks) {
+                                const StepPolicy* pol, uint8_t* masks, const StepResetObs* rso) {
     const bool pair = (p.N % 2) == 0;
+    // the instantiations that also redirect the rows of restarted envs (step_reset_obs_fused), with or without the masks
+    auto pick_rso = [&](auto msk_c) -> const void* {
+        constexpr bool MSK = decltype(msk_c)::value;
+        return pair ? reinterpret_cast<const void*>(&step_kernel<GLOG, true, true, false, false, MSK, true>)
+                    : reinterpret_cast<const void*>(&step_kernel<GLOG, false, true, false, false, MSK, true>);
+    };
     // the instantiations that also write the masks: one env-step without a move order (step_masks_fused)
     auto pick_msk = [&](auto pol_c) -> const void* {
         constexpr bool POL = decltype(pol_c)::value;
@@ -692,7 +761,9 @@ static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const K
                               : reinterpret_cast<const void*>(&step_kernel<GLOG, false, false, ORD, POL>));
     };
     if (masks && !step_masks_fused(K, order != nullptr)) return hipErrorInvalidValue;
-    const void* entry = masks ? (pol ? pick_msk(std::true_type{}) : pick_msk(std::false_type{}))
+    if (rso && !step_reset_obs_fused(K, order != nullptr, pol != nullptr)) return hipErrorInvalidValue;
+    const void* entry = rso ? (masks ? pick_rso(std::true_type{}) : pick_rso(std::false_type{}))
+                      : masks ? (pol ? pick_msk(std::true_type{}) : pick_msk(std::false_type{}))
                       : pol ? (order ? pick(std::true_type{}, std::true_type{}) : pick(std::false_type{}, std::true_type{}))
                             : (order ? pick(std::true_type{}, std::false_type{}) : pick(std::false_type{}, std::false_type{}));
     int E = p.E;
@@ -719,10 +790,12 @@ static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const K
     uint32_t rng_lo = p.rng_lo, rng_hi = p.rng_hi, eps_thr = p.eps_thr, genv0 = (uint32_t)p.env_offset;
     int bdy = p.bdy, edy = p.edy;
     uint8_t* actions_out = pol ? pol->actions_out : nullptr;
+    float* final_obs = rso ? rso->final_obs : nullptr;
+    float* final_compact = rso ? rso->final_compact : nullptr;
     void* args[] = {&st_base, &actions, &cell_info, &obs_table, &obs, &E, &shape, &grid_w, &max_steps,
                     &reward, &af, &ef, &cmp, &counters, &pool, &pool_size, &pool_stride, &env_offset_mod_pool,
                     &dc, &div, &dl, &dr, &term_all, &auto_reset, &rA, &rB, &rC, &rF, &reward_table, &order,
-                    &scripted, &policy, &rng_lo, &rng_hi, &eps_thr, &genv0, &bdy, &edy, &actions_out, &masks};
+                    &scripted, &policy, &rng_lo, &rng_hi, &eps_thr, &genv0, &bdy, &edy, &actions_out, &masks, &final_obs, &final_compact};
     if (ss.lds_bytes > 60 * 1024) {
         hipError_t e = hipFuncSetAttribute(entry, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
@@ -732,15 +805,16 @@ static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const K
 
 hipError_t launch_step(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
                        const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K, int auto_reset,
-                       const uint8_t* pool, const KOut& out, unsigned long long* counters, const StepPolicy* pol, uint8_t* masks) {
+                       const uint8_t* pool, const KOut& out, unsigned long long* counters, const StepPolicy* pol, uint8_t* masks,
+                       const StepResetObs* rso) {
     switch (ss.glog) {
-    case 0: return launch_step_g<0>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
-    case 1: return launch_step_g<1>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
-    case 2: return launch_step_g<2>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
-    case 3: return launch_step_g<3>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
-    case 4: return launch_step_g<4>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
-    case 5: return launch_step_g<5>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
-    case 6: return launch_step_g<6>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks);
+    case 0: return launch_step_g<0>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
+    case 1: return launch_step_g<1>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
+    case 2: return launch_step_g<2>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
+    case 3: return launch_step_g<3>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
+    case 4: return launch_step_g<4>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
+    case 5: return launch_step_g<5>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
+    case 6: return launch_step_g<6>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
     }
     return hipErrorInvalidValue;
 }

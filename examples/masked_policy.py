@@ -46,7 +46,8 @@ with torch.cuda.stream(side), torch.no_grad():
         noise.exponential_()                                          # Gumbel-max sampling: graph-capturable
         actions[0].copy_((logits - noise.log()).argmax(-1).to(torch.uint8))
         wasted.add_((~legal.gather(-1, actions[0].long().unsqueeze(-1))).sum())
-        env.rollout(actions, auto_reset=True, out=out, masks_out=masks)   # masks of the NEW state, after restarts
+        # reset_obs="next": the rows of a restarted env are those of its NEW episode, the state the masks describe
+        env.rollout(actions, auto_reset=True, out=out, masks_out=masks, reset_obs="next")   # masks of the NEW state, after restarts
         obs.copy_(out.obs[0])
 
     body()                                                            # warm-up (allocations)

@@ -38,7 +38,9 @@ with torch.cuda.stream(side), torch.no_grad():
 
     def body():
         actions[0].copy_(policy(obs).argmax(-1).to(torch.uint8))      # greedy w.r.t. the network
-        env.rollout(actions, auto_reset=True, out=out)                # one step; finished envs restart from the pool
+        # reset_obs="next": where an env restarted, out.obs already holds the NEW episode's first observation (the default
+        # writes the finished episode's last one, which is not what the next action should be chosen from)
+        env.rollout(actions, auto_reset=True, out=out, reset_obs="next")   # one step; finished envs restart from the pool
         obs.copy_(out.obs[0])
 
     body()                                                            # warm-up (allocations)

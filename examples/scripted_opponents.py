@@ -41,7 +41,7 @@ with torch.cuda.stream(side), torch.no_grad():
 
     def body():
         actions[0].copy_(policy(obs).argmax(-1).to(torch.uint8))      # the network answers for every slot ...
-        env.rollout_mixed(actions, scripted, "greedy", auto_reset=True, out=out, actions_out=taken)   # ... the exiting ones are scripted
+        env.rollout_mixed(actions, scripted, "greedy", auto_reset=True, out=out, actions_out=taken, reset_obs="next")   # ... the exiting ones are scripted
         obs.copy_(out.obs[0])
 
     body()                                                            # warm-up (allocations)

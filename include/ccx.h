@@ -405,6 +405,48 @@ int ccx_action_masks(ccx_handle* h, uint8_t* masks);
 int ccx_bind_action_masks(ccx_handle* h, uint8_t* masks_or_null);
 int ccx_get_masks_fused(ccx_handle* h, int32_t num_steps, int32_t has_order, int32_t mixed, int32_t* fused);
 /*
+ * CCX_RESET_OBS: what the observation rows of a step that RESTARTED its env hold.  A learner on the device feeds the rows of
+ * step t into its network to pick the actions of step t + 1; on the step where an env auto-resets, the rows it needs are
+ * those of the NEW episode's first state (the reference's loop: `if done: obs, _ = env.reset(seed=...)`,
+ * scripts/run_greedy_policy_demo.py:67-109; Gymnasium's SAME_STEP autoreset with `final_obs`).  Opt-in per handle.
+ *
+ *   CCX_RESET_OBS_TERMINAL (default)  obs[s][e] / obs_compact[s][e] are the rows of the step itself, also where the env
+ *                                     restarted behind it: the bytes every earlier version wrote.
+ *   CCX_RESET_OBS_NEXT                for every (step s, env e) whose env-flag byte carries CCX_EF_RESET:
+ *     1. obs[s][e][a][:] for ALL N slots = the DefaultObservation rows of the restarted state: the placement of pool entry
+ *        (global_env + episode * stride) mod P (the cursor of ccx_set_reset_pool) for the episode that restart opened,
+ *        every agent active -- the bytes ccx_observe would write immediately after that restart;
+ *     2. obs_compact[s][e][a] = (x, y, type, 1) of the same state;
+ *     3. the rows TERMINAL mode writes at obs[s][e] / obs_compact[s][e] go to final_obs[s][e] / final_compact[s][e] where a
+ *        side buffer is bound (ccx_bind_final_obs).  The side buffers have the shape and indexing of the call's own obs /
+ *        obs_compact ([K][E][N][L] / [K][E][N][4] for a rollout of K steps) and the alignment asked of those.  Rows of
+ *        (s, e) WITHOUT CCX_EF_RESET are not written at all: the caller's bytes stay.  A NULL side buffer drops the rows.
+ *     4. nothing else changes: rewards, agent_flags (CCX_AF_OBS keeps describing the finished step), env_flags, the state,
+ *        the counters, bound masks and episode statistics are bit for bit those of TERMINAL mode.
+ *   Only steps with auto-reset and a reset pool raise CCX_EF_RESET: every other call is untouched by the mode.
+ *
+ * Serves ccx_rollout, ccx_rollout_policy, ccx_rollout_mixed and ccx_step_finish(auto_reset = 1) on every config ccx_create
+ * accepts.  With auto-reset in NEXT mode, a call that asks for obs or obs_compact but passes no env_flags returns
+ * CCX_EINVAL (the restarted envs are found there).  One env-step from an action tensor without a move order, on a handle
+ * whose short launches take the step kernel, redirects the rows inside that very launch; every other call is followed, on
+ * the same stream, by ONE fix-up kernel for the whole call that walks env_flags per env, works each restart's episode
+ * ordinal out of the handle's episode counter (episode[e] after the call minus the restarts later in the call), moves the
+ * terminal rows to the side buffers and writes the restarted rows in place -- it touches the rows of restarted envs only.
+ * The bytes are the same either way.  Every call only enqueues on the handle's stream, allocates nothing and captures into
+ * a HIP graph.
+ *
+ * ccx_set_reset_obs        CCX_RESET_OBS_TERMINAL or CCX_RESET_OBS_NEXT.
+ * ccx_bind_final_obs       the side buffers, bound like ccx_bind_action_masks: the caller's, valid while bound, NULL unbinds
+ *                          (either one on its own).
+ * ccx_get_reset_obs_fused  fused = 1 when such a call (num_steps, with / without a move order, mixed = through
+ *                          ccx_rollout_mixed) redirects the rows in the step's own launch, 0 when the fix-up kernel follows.
+ */
+#define CCX_RESET_OBS_TERMINAL 0
+#define CCX_RESET_OBS_NEXT     1
+int ccx_set_reset_obs(ccx_handle* h, int32_t mode);
+int ccx_bind_final_obs(ccx_handle* h, float* final_obs_or_null, float* final_compact_or_null);
+int ccx_get_reset_obs_fused(ccx_handle* h, int32_t num_steps, int32_t has_order, int32_t mixed, int32_t* fused);
+/*
  * CCX_EPISODE_STATS: how the episodes went -- per-agent episode returns and episode lengths, accumulated on the device from
  * the reward / flag arrays a step or a rollout wrote, plus an optional log of finished episodes.  The reference's demos end
  * with exactly this: examples/waiting_policy_demo.py:52-85 (`total_reward += reward`, the step count) and
@@ -659,7 +701,9 @@ int ccx_get_pace_start(ccx_handle* h, float* ns_per_env_step, int32_t* source, f
  *   "pair_rows"    in small batches (role-split writers, launches that are not paced) every writer can get a second
  *                  staging slot in LDS and a row writer then takes TWO env-steps per iteration whenever the simulating
  *                  wavefront is that far ahead: -1 (default) = where it pays (half-tile shapes: up to 128 full tiles),
- *                  1 = in every small batch, 0 = never */
+ *                  1 = in every small batch, 0 = never
+ *   "reset_obs_fused"  0 = CCX_RESET_OBS_NEXT single steps take the fix-up kernel too (what the fused rows are measured
+ *                  against, profiles/reset_obs_timing.py); 1 (default) = inside the step launch where it applies */
 int ccx_set_tunable(ccx_handle* h, const char* name, int32_t value);
 /* workgroups of a rollout launch with outputs, and how many of them the device holds at once (a grid
  * larger than that runs in rounds; the pace of a partial last round is scaled accordingly) */

@@ -1,0 +1,166 @@
+"""NumPy spec of CCX_RESET_OBS_NEXT (include/ccx.h) and the cases its tests share.
+
+Written from the header alone: the cursor of ``ccx_set_reset_pool`` walked FORWARD from the episode counters before the
+launch, and a plain DefaultObservation gather (observations.py:43-94).  Nothing here looks at a kernel."""
+
+import numpy as np
+from _fixtures import config_from_dict
+
+EF_RESET, AF_ACTIVE = 0x04, 0x40
+SENTINEL = 0xA5          # byte the side buffers are filled with before a call
+
+
+def pool_entry(global_env: int, episode: int, pool_size: int, total_envs: int) -> int:
+    """``(g + j * stride) mod P`` with ``stride = total_envs mod P, or 1 when P divides total_envs``."""
+    stride = total_envs % pool_size or 1
+    return (global_env + episode * stride) % pool_size
+
+
+def default_observation(x, y, active, num_boarding: int, consts) -> np.ndarray:
+    """Rows [N, 6 + 4N] of one env: (x_i, y_i, door centre, division_y, door_left, door_right), then for every agent j
+    (x_j, y_j, type_j, active_j), or four times -1 for j == i."""
+    n = len(x)
+    rows = np.empty((n, 6 + 4 * n), np.float32)
+    for i in range(n):
+        rows[i, 0:2] = (x[i], y[i])
+        rows[i, 2:6] = consts
+        for j in range(n):
+            rows[i, 6 + 4 * j:10 + 4 * j] = -1.0 if j == i else (x[j], y[j], 0.0 if j < num_boarding else 1.0, active[j])
+    return rows
+
+
+def row_consts(params):
+    return ((params.door_left + params.door_right) // 2, params.division_y, params.door_left, params.door_right)
+
+
+def compact_of(obs: np.ndarray, agent_flags: np.ndarray, num_boarding: int) -> np.ndarray:
+    """The CCX_OBS_COMPACT rows of a TERMINAL-mode trajectory: (x, y, type, active) per agent slot."""
+    n = obs.shape[-2]
+    c = np.empty(obs.shape[:-1] + (4,), np.float32)
+    c[..., 0:2] = obs[..., 0:2]
+    c[..., 2] = (np.arange(n) >= num_boarding).astype(np.float32)
+    c[..., 3] = ((agent_flags & AF_ACTIVE) != 0).astype(np.float32)
+    return c
+
+
+def next_mode(obs, compact, env_flags, pool, env_offset, total_envs, episode_before, params, final_obs, final_compact):
+    """TERMINAL-mode ``obs [K, E, N, L]`` / ``compact [K, E, N, 4]`` of one launch -> the NEXT-mode arrays and the side
+    buffers (given with the caller's bytes; only the rows of restarted pairs change).  Returns also the episode counters
+    behind the launch."""
+    obs, compact = obs.copy(), compact.copy()
+    final_obs, final_compact = final_obs.copy(), final_compact.copy()
+    K, E, N, _ = obs.shape
+    nb, consts, ones = params.num_boarding, row_consts(params), np.ones(N, np.float32)
+    episode = np.asarray(episode_before, np.int64).copy()
+    for s in range(K):
+        for e in range(E):
+            if not env_flags[s, e] & EF_RESET:
+                continue
+            episode[e] += 1
+            xy = pool[pool_entry(env_offset + e, int(episode[e]), len(pool), total_envs)]
+            final_obs[s, e], final_compact[s, e] = obs[s, e], compact[s, e]
+            obs[s, e] = default_observation(xy[:, 0], xy[:, 1], ones, nb, consts)
+            compact[s, e] = np.stack([xy[:, 0], xy[:, 1], (np.arange(N) >= nb), ones], -1).astype(np.float32)
+    return obs, compact, final_obs, final_compact, episode
+
+
+# ---------------------------------------------------------------------------------------------------- shared cases
+def make_config(N, max_steps=5, big=False, individual=True):
+    nb = {1: 1, 3: 2, 5: 3, 8: 5}.get(N, N // 2)
+    if big:        # 100 x 100: the occupancy tables exceed the LDS, short launches take the rollout kernel
+        geo = dict(width=100, height=100, division_y=50, tram_door_left=25, tram_door_right=35, tram_length=60,
+                   boarding_destination_area_y=100)
+    elif N <= 8:
+        geo = dict(width=12, height=8, division_y=4, tram_door_left=5, tram_door_right=7, tram_length=9,
+                   boarding_destination_area_y=8)
+    else:
+        geo = dict(width=32, height=16, division_y=8, tram_door_left=10, tram_door_right=16, tram_length=26,
+                   boarding_destination_area_y=16)
+    return config_from_dict(dict(geo, num_boarding_agents=nb, num_exiting_agents=N - nb, exiting_destination_area_y=0,
+                                 truncated_config=dict(truncated_function="max_steps", max_steps=max_steps),
+                                 terminated_config=dict(terminated_function="individual_at_destination" if individual
+                                                        else "all_at_destination")))
+
+
+# name -> N, E, max_steps, launch lengths, and what drives the steps
+CASES = {
+    "k1_n1": dict(N=1, chunks=[1] * 7),
+    "k1_n5": dict(N=5, chunks=[1] * 7),
+    "k1_n8": dict(N=8, chunks=[1] * 7),
+    "k1_n33": dict(N=33, chunks=[1] * 7),
+    "k16_n8_five_restarts": dict(N=8, max_steps=3, chunks=[16, 16]),
+    "k16_n5": dict(N=5, chunks=[16, 3]),
+    "k40_n8": dict(N=8, chunks=[40, 40]),
+    "k40_n33": dict(N=33, chunks=[40]),
+    "order_n8": dict(N=8, chunks=[1, 1, 4, 1], order=True),
+    "shard_n5": dict(N=5, chunks=[1, 1, 16, 40], env_offset=1000, total_envs=5000),
+    "greedy_n1": dict(N=1, max_steps=9, chunks=[16, 40, 9], drive="greedy"),   # individual termination: __all__ terminated too
+    "mixed_n8": dict(N=8, chunks=[1, 1, 16, 5], drive="mixed"),
+    "finish_n5": dict(N=5, chunks=[1] * 6, drive="finish"),
+    "big_n3": dict(N=3, E=5, big=True, chunks=[1, 1, 1, 16]),
+}
+POOL_SIZE = 37           # E = 67 > P and P does not divide E: the cursor's modulo and stride are live
+
+
+class Case:
+    """One case on the CPU: config, pool, staggered start state, inputs of every launch, and the oracle's TERMINAL-mode
+    trajectory where the oracle has the path (``oracle_chunks``: one dict per launch)."""
+
+    def __init__(self, name, oracle_mod):
+        from collectivecrossing_amd.params import lower_config
+        from collectivecrossing_amd.reset import build_reset_pool
+        c = dict(E=67, max_steps=5, big=False, order=False, env_offset=0, total_envs=None, drive="tensor")
+        c.update(CASES[name])
+        self.__dict__.update(c)
+        self.name = name
+        self.total_envs = self.total_envs or self.E
+        self.config = make_config(self.N, self.max_steps, self.big)
+        self.params = lower_config(self.config)
+        self.pool = build_reset_pool(self.config, 7, POOL_SIZE)
+        E, N = self.E, self.N
+        rng = np.random.default_rng(sum(map(ord, name)))
+        # step counters staggered over the episode length: restarts fall on first, middle and last steps of a launch
+        self.step_count0 = (np.arange(E) % self.max_steps).astype(np.int32)
+        self.actions = [rng.integers(0, 5, size=(k, E, N), dtype=np.uint8) for k in self.chunks]
+        self.orders = [np.argsort(rng.random((k, E, N)), axis=-1).astype(np.uint8) if self.order else None for k in self.chunks]
+        self.oracle_chunks = None
+        if self.drive in ("tensor", "greedy"):
+            ob = self.new_oracle(oracle_mod)
+            self.oracle_chunks = []
+            for k, a, o in zip(self.chunks, self.actions, self.orders):
+                ep0 = ob.episode.copy()
+                if self.drive == "greedy":
+                    _, obs, rew, af, ef = ob.rollout_greedy(k, auto_reset=True)
+                else:
+                    obs, rew, af, ef = ob.rollout(a, o, auto_reset=True)
+                self.oracle_chunks.append(dict(obs=obs, reward=rew, agent_flags=af, env_flags=ef, episode_before=ep0,
+                                               episode_after=ob.episode.copy(), observe_after=ob.observe()))
+
+    def new_oracle(self, oracle_mod):
+        ob = oracle_mod.OracleBatch(self.params, self.E, self.env_offset, self.total_envs)
+        ob.set_reset_pool(self.pool)
+        ob.reset_from_pool()
+        ob.set_state(step_count=self.step_count0)
+        return ob
+
+    def spec(self, chunk, sentinel=True):
+        """NEXT-mode arrays of a launch from its TERMINAL-mode dict (obs, agent_flags, env_flags, episode_before)."""
+        obs = chunk["obs"]
+        compact = chunk.get("obs_compact")
+        if compact is None:
+            compact = compact_of(obs, chunk["agent_flags"], self.params.num_boarding)
+        fo = np.frombuffer(bytes([SENTINEL]) * obs.nbytes, np.float32).reshape(obs.shape) if sentinel else np.zeros_like(obs)
+        fc = np.frombuffer(bytes([SENTINEL]) * compact.nbytes, np.float32).reshape(compact.shape) if sentinel else np.zeros_like(compact)
+        return next_mode(obs, compact, chunk["env_flags"], self.pool, self.env_offset, self.total_envs,
+                         chunk["episode_before"], self.params, fo, fc)
+
+
+def restart_conditions(name, env_flags_per_chunk):
+    """What the issue asks of every case, from the env-flag bytes alone."""
+    ef = np.concatenate(env_flags_per_chunk, 0)
+    r = (ef & EF_RESET) != 0
+    assert r.mean() >= 0.1, (name, r.mean())
+    assert any(((c[-1] & EF_RESET) != 0).any() for c in env_flags_per_chunk), name
+    if "five_restarts" in name:
+        per_launch = max(int(((c & EF_RESET) != 0).sum(0).max()) for c in env_flags_per_chunk)
+        assert per_launch >= 5, (name, per_launch)
