@@ -460,6 +460,25 @@ class BatchedCollectiveCrossing:
         else:
             self._reset_obs(mode, out.final_obs, out.final_compact, (out.obs, out.obs_compact))
 
+    @contextlib.contextmanager
+    def _rollout_call(self, K, auto_reset, out, want_traj, want_obs, want_compact, reset_obs, check_pool=False):
+        """Head and tail of every rollout wrapper.  Before the call: the pool an auto-reset needs (``check_pool``; the other
+        wrappers leave that refusal to the library), the refusal of a tracked call without a trajectory, the result
+        (allocated unless the caller's, ``None`` without a trajectory) and the reset-observation mode with that result's
+        side buffers.  Yields ``(result, byref of its CcxRolloutOut or None)``; behind the body the tracked update."""
+        if check_pool and auto_reset and self._pool is None:
+            raise ValueError("auto_reset needs a reset pool (set_reset_pool / make_reset_pool)")
+        self._track_check(out, want_traj)
+        if out is None and want_traj:
+            out = self.alloc_rollout(K, want_obs, want_compact)
+        self._reset_obs_out(reset_obs, out)
+        ro = None if out is None else C.byref(_abi.CcxRolloutOut(
+            _ptr(out.obs).value, _ptr(out.reward).value, _ptr(out.agent_flags).value, _ptr(out.env_flags).value,
+            _ptr(out.obs_compact).value))
+        yield out, ro
+        if self._tracking:
+            self._track(K, out)
+
     def step_final_buffers(self, want_obs: bool = True, want_compact: bool = False):
         """The batch's own one-step side buffers ``(final_obs f32 [E, N, L], final_compact f32 [E, N, 4])`` that
         ``step_finish(reset_obs="next", want_final=True)`` fills at restarted envs and hands out as
@@ -641,14 +660,7 @@ class BatchedCollectiveCrossing:
         key = (struct, bool(want_obs), bool(want_compact), bool(want_masks))
         cached = self._step_out_cache.get(key)
         if cached is None:
-            E, N = self.num_envs, self.num_agents
-            if self._step_bufs is None:
-                self._step_bufs = StepResult(self._new((E, N, self.obs_len), torch.float32),
-                                             self._new((E, N), torch.float64),
-                                             self._new((E, N), torch.uint8), self._new((E,), torch.uint8))
-            b = self._step_bufs
-            if want_compact and b.obs_compact is None:
-                b.obs_compact = self._new((E, N, 4), torch.float32)
+            b = self._step_buffers(want_compact)
             so = struct(_ptr(b.obs if want_obs else None).value, _ptr(b.reward).value,
                         _ptr(b.agent_flags).value, _ptr(b.env_flags).value,
                         _ptr(b.obs_compact if want_compact else None).value)
@@ -657,6 +669,16 @@ class BatchedCollectiveCrossing:
                                                   action_masks=self._masks_buf if want_masks else None))
             self._step_out_cache[key] = cached
         return cached
+
+    def _step_buffers(self, want_compact) -> StepResult:
+        """The env's static one-step output buffers, allocated on first use (the compact rows when first asked for)."""
+        E, N = self.num_envs, self.num_agents
+        if self._step_bufs is None:
+            self._step_bufs = StepResult(self._new((E, N, self.obs_len), torch.float32), self._new((E, N), torch.float64),
+                                         self._new((E, N), torch.uint8), self._new((E,), torch.uint8))
+        if want_compact and self._step_bufs.obs_compact is None:
+            self._step_bufs.obs_compact = self._new((E, N, 4), torch.float32)
+        return self._step_bufs
 
     # ------------------------------------------------------------------ mixed control
     def _mixed_args(self, scripted, policy):
@@ -721,22 +743,11 @@ class BatchedCollectiveCrossing:
                 raise ValueError(f"num_steps = {num_steps} but actions holds {K} steps")
             a = self._as_dev_u8(actions, (K, E, N))
         o = None if order is None else self._as_dev_u8(order, (K, E, N))
-        if auto_reset and self._pool is None:
-            raise ValueError("auto_reset needs a reset pool (set_reset_pool / make_reset_pool)")
         if actions_out is not None:
             self._check_actions_out(actions_out, (K, E, N))
-        self._track_check(out, want_traj)
-        if out is None and want_traj:
-            out = self.alloc_rollout(K, want_obs, want_compact)
-        self._reset_obs_out(reset_obs, out)
-        ro = None
-        if out is not None:
-            ro = C.byref(_abi.CcxRolloutOut(_ptr(out.obs).value, _ptr(out.reward).value, _ptr(out.agent_flags).value,
-                                            _ptr(out.env_flags).value, _ptr(out.obs_compact).value))
-        check(self._lib.ccx_rollout_mixed(self._h, K, pol, mask, _ptr(a), _ptr(o), int(bool(auto_reset)), ro,
-                                          _ptr(actions_out)))
-        if self._tracking:
-            self._track(K, out)
+        with self._rollout_call(K, auto_reset, out, want_traj, want_obs, want_compact, reset_obs, check_pool=True) as (out, ro):
+            check(self._lib.ccx_rollout_mixed(self._h, K, pol, mask, _ptr(a), _ptr(o), int(bool(auto_reset)), ro,
+                                              _ptr(actions_out)))
         return out
 
     # ------------------------------------------------------------------ the split step / array-form strategies
@@ -823,12 +834,7 @@ class BatchedCollectiveCrossing:
         key = (bool(want_obs), bool(want_compact), want_final)
         cached = self._finish_cache.get(key)
         if cached is None:
-            if self._step_bufs is None:
-                self._step_bufs = StepResult(self._new((E, N, self.obs_len), torch.float32), self._new((E, N), torch.float64),
-                                             self._new((E, N), torch.uint8), self._new((E,), torch.uint8))
-            b = self._step_bufs
-            if want_compact and b.obs_compact is None:
-                b.obs_compact = self._new((E, N, 4), torch.float32)
+            b = self._step_buffers(want_compact)
             if self._term_present is None:
                 self._term_present = self._new((E, N), torch.uint8)
             so = _abi.CcxStepOut(_ptr(b.obs if want_obs else None).value, _ptr(b.reward).value, _ptr(b.agent_flags).value,
@@ -884,25 +890,21 @@ class BatchedCollectiveCrossing:
         here carries ``term_present``; a caller's own ``out`` gets it only if its ``term_present`` is set; without a
         trajectory (``want_traj=False``) nothing is written out."""
         E, N = self.num_envs, self.num_agents
-        if auto_reset and self._pool is None:
-            raise ValueError("auto_reset needs a reset pool (set_reset_pool / make_reset_pool)")
-        self._track_check(out, want_traj)
-        if out is None and want_traj:
-            out = self.alloc_rollout(K, want_obs, want_compact)
-            out.term_present = self._new((K, E, N), torch.uint8)
-        row_align = 16 if N % 2 == 0 else 8       # (odd agent counts write the rows in 8-byte units)
-        if out is not None and out.obs is not None and K > 1 and (E * N * self.obs_len * 4) % row_align:
-            raise ValueError(f"{E} envs x {N} agents: a step's observation rows are not a multiple of {row_align} bytes")
-        for s in range(K):
-            if policy is None:
-                self.step_begin(actions[s], None if order is None else order[s])
-            else:
-                a = self.policy_actions(policy, out=None if actions_out is None else actions_out[s])
-                self.step_begin(a)
-            r, t, u = self.run_array_strategies()
-            self._finish_into(r, t, u, out, s, auto_reset, reset_obs)
-        if self._tracking:
-            self._track(K, out)
+        own = out is None and want_traj
+        with self._rollout_call(K, auto_reset, out, want_traj, want_obs, want_compact, reset_obs, check_pool=True) as (out, _):
+            if own:
+                out.term_present = self._new((K, E, N), torch.uint8)
+            row_align = 16 if N % 2 == 0 else 8       # (odd agent counts write the rows in 8-byte units)
+            if out is not None and out.obs is not None and K > 1 and (E * N * self.obs_len * 4) % row_align:
+                raise ValueError(f"{E} envs x {N} agents: a step's observation rows are not a multiple of {row_align} bytes")
+            for s in range(K):
+                if policy is None:
+                    self.step_begin(actions[s], None if order is None else order[s])
+                else:
+                    a = self.policy_actions(policy, out=None if actions_out is None else actions_out[s])
+                    self.step_begin(a)
+                r, t, u = self.run_array_strategies()
+                self._finish_into(r, t, u, out, s, auto_reset, reset_obs)
         return out
 
     def rows_alignment(self) -> int:
@@ -1034,19 +1036,9 @@ class BatchedCollectiveCrossing:
         self._bind_masks(None if masks_out is None else self._check_masks(masks_out))
         if self._array_strategies:
             return self._rollout_array(K, a, o, None, auto_reset, out, want_traj, want_obs, want_compact, None, reset_obs)
-        self._track_check(out, want_traj)
-        if out is None and want_traj:
-            out = self.alloc_rollout(K, want_obs, want_compact)
-        self._reset_obs_out(reset_obs, out)
-        if out is not None:
-            ro = _abi.CcxRolloutOut(_ptr(out.obs).value, _ptr(out.reward).value,
-                                    _ptr(out.agent_flags).value, _ptr(out.env_flags).value, _ptr(out.obs_compact).value)
-            check(self._lib.ccx_rollout(self._h, K, _ptr(a), _ptr(o), int(bool(auto_reset)), C.byref(ro)))
-            self._rollouts_with_obs += int(out.obs is not None and K >= 64)
-            if self._tracking:
-                self._track(K, out)
-        else:
-            check(self._lib.ccx_rollout(self._h, K, _ptr(a), _ptr(o), int(bool(auto_reset)), None))
+        with self._rollout_call(K, auto_reset, out, want_traj, want_obs, want_compact, reset_obs) as (out, ro):
+            check(self._lib.ccx_rollout(self._h, K, _ptr(a), _ptr(o), int(bool(auto_reset)), ro))    # (no trajectory: NULL)
+            self._rollouts_with_obs += int(out is not None and out.obs is not None and K >= 64)
         return out
 
     def rollout_greedy(self, num_steps: int, auto_reset: bool = False, out: RolloutResult | None = None,
@@ -1063,17 +1055,9 @@ class BatchedCollectiveCrossing:
         if self._array_strategies:
             return self._rollout_array(K, None, None, policy, auto_reset, out, True, want_obs, False, actions_out,
                                        reset_obs), actions_out
-        self._track_check(out, True)
-        if out is None:
-            out = self.alloc_rollout(K, want_obs)
-        self._reset_obs_out(reset_obs, out)
-        ro = _abi.CcxRolloutOut(_ptr(out.obs).value, _ptr(out.reward).value,
-                                _ptr(out.agent_flags).value, _ptr(out.env_flags).value, _ptr(out.obs_compact).value)
-        check(self._lib.ccx_rollout_policy(self._h, K, _abi.POLICIES[policy], int(bool(auto_reset)),
-                                           C.byref(ro), _ptr(actions_out)))
-        self._rollouts_with_obs += int(out.obs is not None and K >= 64)
-        if self._tracking:
-            self._track(K, out)
+        with self._rollout_call(K, auto_reset, out, True, want_obs, False, reset_obs) as (out, ro):
+            check(self._lib.ccx_rollout_policy(self._h, K, _abi.POLICIES[policy], int(bool(auto_reset)), ro, _ptr(actions_out)))
+            self._rollouts_with_obs += int(out.obs is not None and K >= 64)
         return out, actions_out
 
     def rollout_policy(self, num_steps: int, policy: str, auto_reset: bool = False, **kw):

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "ccx_internal.h"
@@ -252,130 +253,154 @@ int calibrate_pace(ccx_handle* h, float* obs, size_t obs_bytes) {
     return CCX_OK;
 }
 
-int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* order, int auto_reset,
-                const ccx::KOut& out, int policy = 0, uint8_t* actions_out = nullptr, bool inputs_checked = false,
-                uint8_t* masks = nullptr, bool* masks_written = nullptr, const ccx::StepResetObs* rso = nullptr,
-                bool* rso_written = nullptr) {
-    // The writer waves address the small output streams (rewards, flag bytes, compact rows, chosen actions) with 32-bit
-    // byte offsets from the stream's base: one launch must stay below 4 GiB per stream.  Longer rollouts are cut into
-    // launches on the same stream (bit-identical: an env's trajectory does not depend on how a rollout is split).
-    {
-        const unsigned long long per_step = (unsigned long long)h->E * (unsigned long long)h->N * 16ull;   // the widest stream
-        const unsigned long long fit = 0xFFFFFFFFull / per_step;
-        int max_k = (int)std::min<unsigned long long>(fit > 1 ? fit - 1 : 1, 0x7FFFFFFFull);
-        if (h->tun_max_launch_steps > 0) max_k = std::min(max_k, h->tun_max_launch_steps);   // (tests: force the cut)
-        // L = 6 + 4N is 2 mod 4: one step's observation slab (E x N x L floats) is a multiple of 16 bytes only when E x N is
-        // even; with E x N odd every sub-launch must start on an EVEN step so that its slice of the tensor stays 16-byte
-        // aligned (an odd cut failed on "obs buffer must be 16-byte aligned" after the first sub-launch had
-        // already advanced the state)
-        const bool odd_slab = out.obs && ((((size_t)h->E * h->N * (size_t)(6 + 4 * h->N) * sizeof(float)) & 15u) != 0);
-        if (odd_slab && max_k > 1) max_k &= ~1;
-        if (K > max_k && odd_slab && max_k == 1)
-            return fail(CCX_EINVAL, "a rollout of an odd number of agent slots (E x N = %lld) cannot be cut into launches of "
-                        "one step: its per-step observation slabs are not 16-byte aligned (raise max_launch_steps to >= 2)",
-                        (long long)h->E * h->N);
-        if (K > max_k) {
-            const size_t EN = (size_t)h->E * h->N, L = (size_t)(6 + 4 * h->N);
-            for (int k0 = 0; k0 < K; k0 += max_k) {
-                const int kk = std::min(max_k, K - k0);
-                ccx::KOut o = out;
-                if (o.obs) o.obs += (size_t)k0 * EN * L;
-                if (o.reward) o.reward += (size_t)k0 * EN;
-                if (o.agent_flags) o.agent_flags += (size_t)k0 * EN;
-                if (o.env_flags) o.env_flags += (size_t)k0 * (size_t)h->E;
-                if (o.obs_compact) o.obs_compact += (size_t)k0 * EN * 4u;
-                // (the sub-launches get neither `masks` nor `rso`: a call that is cut leaves both to the stand-alone kernels
-                //  behind its LAST launch -- finish_masks, finish_reset_obs -- also where it is cut into single steps; same bytes)
-                const int rc = run_rollout(h, kk, actions ? actions + (size_t)k0 * EN : nullptr,
-                                           order ? order + (size_t)k0 * EN : nullptr, auto_reset, o, policy,
-                                           actions_out ? actions_out + (size_t)k0 * EN : nullptr, inputs_checked);
-                if (rc) return rc;
-            }
-            return CCX_OK;
-        }
+// ---- one stepping call: what ccx_step, ccx_rollout, ccx_rollout_policy and ccx_rollout_mixed hand to the launch code ----
+struct StepCall {     // (the first five fields in the order of ccx_rollout's arguments: the entry points fill them by position)
+    int K = 1;                             // env-steps
+    const uint8_t* actions = nullptr;      // u8 [K][E][N]; null where `policy` drives every slot
+    const uint8_t* order = nullptr;        // u8 [K][E][N] or null
+    int auto_reset = 0;
+    ccx::KOut out{};
+    int policy = 0;                        // in-kernel policy of the rollout kernel (0 = the action tensor)
+    uint8_t* actions_out = nullptr;        // ... and where its actions go
+    bool inputs_checked = false;           // the entry point has enqueued the input check of the whole call itself
+    // what the step kernel may do in its own launch instead of leaving it to finish_call (never given to a sub-launch of a cut)
+    uint8_t* masks = nullptr;
+    const ccx::StepResetObs* rso = nullptr;
+};
+
+// how a call's launches went: the status, and what the launch did itself of the epilogue's work (finish_call does the rest)
+struct Launched {
+    int rc;
+    bool masks_written = false, reset_obs_written = false;
+    Launched(int rc_ = CCX_OK) : rc(rc_) {}
+};
+
+// ---- the prologue: every check and query the entry points share, each stated once -----------------------------------
+template <class Out>   // (ccx_step_out, ccx_rollout_out: the same five pointers)
+ccx::KOut kout_of(const Out* out) {
+    return out ? ccx::KOut{out->obs, out->reward, out->agent_flags, out->env_flags, out->obs_compact} : ccx::KOut{};
+}
+
+// the outputs of step s of a [K][...] trajectory
+ccx::KOut kout_at(const ccx_handle* h, const ccx::KOut& ko, int s) {
+    const size_t EN = (size_t)h->E * h->N, L = (size_t)(6 + 4 * h->N);
+    ccx::KOut o = ko;
+    if (o.obs) o.obs += (size_t)s * EN * L;
+    if (o.reward) o.reward += (size_t)s * EN;
+    if (o.agent_flags) o.agent_flags += (size_t)s * EN;
+    if (o.env_flags) o.env_flags += (size_t)s * (size_t)h->E;
+    if (o.obs_compact) o.obs_compact += (size_t)s * EN * 4u;
+    return o;
+}
+
+bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1u)) != 0; }
+
+// the kernels store rows in 16-byte units (ccx_step_finish with an odd agent count: 8) and rewards as doubles
+int check_out_align(const ccx::KOut& ko, unsigned obs_align = 16, const char* reward_what = "reward buffer") {
+    if (misaligned(ko.obs, obs_align)) return fail(CCX_EINVAL, "obs buffer must be %u-byte aligned", obs_align);
+    if (misaligned(ko.reward, 8)) return fail(CCX_EINVAL, "%s must be 8-byte aligned", reward_what);
+    if (misaligned(ko.obs_compact, 16)) return fail(CCX_EINVAL, "obs_compact buffer must be 16-byte aligned");
+    return CCX_OK;
+}
+
+int need_pool_for_auto_reset(const ccx_handle* h, int auto_reset) {
+    if (auto_reset && (!h->pool || h->pool_size <= 0))
+        return fail(CCX_EINVAL, "auto_reset needs a reset pool (ccx_set_reset_pool)");
+    return CCX_OK;
+}
+
+// ccx_set_check_inputs: count the bad bytes of `steps` steps of a caller's tensors (skip_slots: slots a policy scripts)
+int enqueue_input_check(ccx_handle* h, int steps, const uint8_t* actions, const uint8_t* order, unsigned long long skip_slots = 0ull) {
+    if (!h->check_inputs || (!actions && !order)) return CCX_OK;
+    hipError_t ce = ccx::launch_check_inputs(h->stream, actions, order, (size_t)steps * (size_t)h->E, h->N, h->input_errors, skip_slots);
+    if (ce != hipSuccess) return fail(CCX_EHIP, "input check kernel launch failed: %s", hipGetErrorString(ce));
+    return CCX_OK;
+}
+
+bool stream_is_capturing(const ccx_handle* h) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(h->stream, &cap) == hipSuccess) return cap != hipStreamCaptureStatusNone;
+    (void)hipGetLastError();
+    return false;
+}
+
+// ---- the short launch: the step kernel (ccx_step.hip), CollectiveCrossingEnv.step itself -- no pacing, no controller state,
+// no capture query.  `pol`: the kernel's mixed-control instantiations (ccx_rollout_mixed)
+Launched launch_short(ccx_handle* h, const StepCall& c, const ccx::StepPolicy* pol = nullptr) {
+    int rc = c.inputs_checked ? CCX_OK : enqueue_input_check(h, c.K, c.actions, c.order);
+    if (!rc) rc = begin_timed(h);
+    if (rc) return rc;
+    // (bound action masks: this launch writes them itself where an MSK instantiation exists -- ccx_kernels.h)
+    uint8_t* const m = ccx::step_masks_fused(c.K, c.order != nullptr) ? c.masks : nullptr;
+    // (CCX_RESET_OBS_NEXT: likewise where an RSO instantiation exists; finish_call serves the rest)
+    const ccx::StepResetObs* const r =
+        (h->tun_reset_obs_fused != 0 && ccx::step_reset_obs_fused(c.K, c.order != nullptr, pol != nullptr)) ? c.rso : nullptr;
+    hipError_t e = ccx::launch_step(h->step_shape, h->stream, launch_params(h), h->st_slab, h->cell_info, c.actions, c.order, c.K,
+                                    c.auto_reset, h->pool, c.out, h->counters, pol, m, r);
+    if (e != hipSuccess) return fail(CCX_EHIP, "step kernel launch failed: %s", hipGetErrorString(e));
+    Launched l(end_timed(h));
+    l.masks_written = m != nullptr, l.reset_obs_written = r != nullptr;
+    return l;
+}
+
+// ---- the paced launch: the rollout kernel.  First its controller: (re)start and calibration, ahead of the launch ---------
+int restart_pace(ccx_handle* h, const StepCall& c, bool capturing) {
+    const int K = c.K;
+    const bool writes_obs = c.out.obs != nullptr;
+    // (re)start the pace controller: new handle, new launch shape or new setting
+    // Never inside a stream capture: the memsets would become graph nodes and every replay would re-zero the
+    // controller's state, and the calibration must synchronise.  Only a launch that would actually run them
+    // is refused while capturing; a controller that has been started (by ANY eager paced launch of the shape) and merely
+    // waits for its calibration captures fine and runs at the pace in effect (K = 16..63 on the C2 shape).
+    const bool paced_launch = ccx::launch_is_paced(h->kp.pace_state != nullptr, writes_obs, K, h->kp.pace_min_k);
+    const bool adaptive_launch =
+        ccx::launch_is_adaptive(h->kp.pace_state != nullptr, h->kp.pace_adapt != 0u, writes_obs, K, h->kp.pace_min_k, h->kp.adapt_min_k);
+    if (h->pace_dirty && !h->kp.pace_state) {
+        h->pace_dirty = false;              // rollouts of this shape are not paced at all
+        h->pace_needs_calibration = false;
     }
-    if (out.obs && (reinterpret_cast<uintptr_t>(out.obs) & 15u))
-        return fail(CCX_EINVAL, "obs buffer must be 16-byte aligned");
-    if (out.reward && (reinterpret_cast<uintptr_t>(out.reward) & 7u))
-        return fail(CCX_EINVAL, "reward buffer must be 8-byte aligned");
-    if (out.obs_compact && (reinterpret_cast<uintptr_t>(out.obs_compact) & 15u))
-        return fail(CCX_EINVAL, "obs_compact buffer must be 16-byte aligned");
-    CCX_HIP(hipSetDevice(h->device));
-    if (K <= ccx::kStepMaxK && actions && policy == 0 && !actions_out && h->step_shape.ok && h->tun_step_kernel != 0) {
-        // the short-launch kernel (ccx_step.hip): CollectiveCrossingEnv.step itself, no pacing, no controller state
-        if (h->check_inputs && !inputs_checked) {
-            hipError_t ce = ccx::launch_check_inputs(h->stream, actions, order, (size_t)K * (size_t)h->E, h->N, h->input_errors);
-            if (ce != hipSuccess) return fail(CCX_EHIP, "input check kernel launch failed: %s", hipGetErrorString(ce));
-        }
-        int rc = begin_timed(h);
-        if (rc) return rc;
-        // (bound action masks: this launch writes them itself where an MSK instantiation exists -- ccx_kernels.h)
-        uint8_t* const m = ccx::step_masks_fused(K, order != nullptr) ? masks : nullptr;
-        // (CCX_RESET_OBS_NEXT: likewise where an RSO instantiation exists; finish_reset_obs serves the rest)
-        const ccx::StepResetObs* const r =
-            (h->tun_reset_obs_fused != 0 && ccx::step_reset_obs_fused(K, order != nullptr, false)) ? rso : nullptr;
-        hipError_t e = ccx::launch_step(h->step_shape, h->stream, launch_params(h), h->st_slab, h->cell_info, actions, order, K, auto_reset,
-                                        h->pool, out, h->counters, nullptr, m, r);
-        if (e != hipSuccess) return fail(CCX_EHIP, "step kernel launch failed: %s", hipGetErrorString(e));
-        if (m && masks_written) *masks_written = true;
-        if (r && rso_written) *rso_written = true;
-        return end_timed(h);
+    if (h->pace_dirty && paced_launch) {    // (launches that are not paced never look at the controller: nothing to do yet)
+        if (capturing)
+            return fail(CCX_EINVAL, "the pace controller of this handle must be (re)started (new handle, launch shape or "
+                        "setting): run one eager rollout of this shape (any paced length: >= %u steps) before capturing it "
+                        "into a graph, or switch pacing off (ccx_set_step_pace(h, -1))", h->kp.pace_min_k);
+        h->pace_needs_calibration = h->kp.pace_adapt != 0u && h->pace_calibrate && h->pace_start_ns <= 0.0f;
     }
-    const bool writes_obs = out.obs != nullptr;
-    bool capturing = false;
-    {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(h->stream, &cap) != hipSuccess) (void)hipGetLastError();
-        else capturing = cap != hipStreamCaptureStatusNone;
-    }
-    {   // (re)start the pace controller: new handle, new launch shape or new setting
-        // Never inside a stream capture: the memsets would become graph nodes and every replay would re-zero the
-        // controller's state, and the calibration must synchronise.  Only a launch that would actually run them
-        // is refused while capturing; a controller that has been started (by ANY eager paced launch of the shape) and merely
-        // waits for its calibration captures fine and runs at the pace in effect (K = 16..63 on the C2 shape).
-        const bool paced_launch = ccx::launch_is_paced(h->kp.pace_state != nullptr, writes_obs, K, h->kp.pace_min_k);
-        const bool adaptive_launch =
-            ccx::launch_is_adaptive(h->kp.pace_state != nullptr, h->kp.pace_adapt != 0u, writes_obs, K, h->kp.pace_min_k, h->kp.adapt_min_k);
-        if (h->pace_dirty && !h->kp.pace_state) {
-            h->pace_dirty = false;              // rollouts of this shape are not paced at all
+    const bool calibrate_now = h->pace_needs_calibration && adaptive_launch && !capturing;
+    if ((h->pace_dirty && paced_launch) || calibrate_now) {
+        if (calibrate_now) {
+            const size_t obs_bytes = (size_t)K * (size_t)h->E * h->N * (size_t)(6 + 4 * h->N) * sizeof(float);
+            const int rc = calibrate_pace(h, c.out.obs, obs_bytes);
+            if (rc) return rc;
             h->pace_needs_calibration = false;
         }
-        if (h->pace_dirty && paced_launch) {    // (launches that are not paced never look at the controller: nothing to do yet)
-            if (capturing)
-                return fail(CCX_EINVAL, "the pace controller of this handle must be (re)started (new handle, launch shape or "
-                            "setting): run one eager rollout of this shape (any paced length: >= %u steps) before capturing it "
-                            "into a graph, or switch pacing off (ccx_set_step_pace(h, -1))", h->kp.pace_min_k);
-            h->pace_needs_calibration = h->kp.pace_adapt != 0u && h->pace_calibrate && h->pace_start_ns <= 0.0f;
-        }
-        const bool calibrate_now = h->pace_needs_calibration && adaptive_launch && !capturing;
-        if ((h->pace_dirty && paced_launch) || calibrate_now) {
-            if (calibrate_now) {
-                const size_t obs_bytes = (size_t)K * (size_t)h->E * h->N * (size_t)(6 + 4 * h->N) * sizeof(float);
-                const int rc = calibrate_pace(h, out.obs, obs_bytes);
-                if (rc) return rc;
-                h->pace_needs_calibration = false;
-            }
-            CCX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->pace_state), 0, 8, h->stream));   // floor, cliff memory = 0
-            CCX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->pace_state + h->pace_slot),
-                                      (int)h->pace_init_fp, 1, h->stream));
-            // A start value from the caller (ccx_set_step_pace_start: the pace a previous handle of this shape settled at)
-            // is also the controller's first FLOOR: a process that already knows its pace skips the descent into a first
-            // collapse; the floor decays as always.  A CALIBRATED start gets no floor: the probe is a lower bound of what
-            // the paced stream reaches (measured: the paced rollouts settle 5-15 % above a plain fill of the same buffer),
-            // so the controller descends from it at its fast rate (1.6 % per launch) until the memory side says stop.
-            if (h->step_pace_ns == 0 && h->pace_start_ns > 0.0f)
-                CCX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->pace_state + 2), (int)h->pace_init_fp, 1, h->stream));
-            // (a paced launch too short to calibrate on runs from the assumption; the first adaptive eager one calibrates
-            // and restarts: pace_needs_calibration)
-            h->pace_dirty = false;
-        }
+        CCX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->pace_state), 0, 8, h->stream));   // floor, cliff memory = 0
+        CCX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->pace_state + h->pace_slot),
+                                  (int)h->pace_init_fp, 1, h->stream));
+        // A start value from the caller (ccx_set_step_pace_start: the pace a previous handle of this shape settled at)
+        // is also the controller's first FLOOR: a process that already knows its pace skips the descent into a first
+        // collapse; the floor decays as always.  A CALIBRATED start gets no floor: the probe is a lower bound of what
+        // the paced stream reaches (measured: the paced rollouts settle 5-15 % above a plain fill of the same buffer),
+        // so the controller descends from it at its fast rate (1.6 % per launch) until the memory side says stop.
+        if (h->step_pace_ns == 0 && h->pace_start_ns > 0.0f)
+            CCX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->pace_state + 2), (int)h->pace_init_fp, 1, h->stream));
+        // (a paced launch too short to calibrate on runs from the assumption; the first adaptive eager one calibrates
+        // and restarts: pace_needs_calibration)
+        h->pace_dirty = false;
     }
+    return CCX_OK;
+}
+
+// ... then the launch itself, round by round where the grid exceeds the device
+int launch_paced(ccx_handle* h, const StepCall& c) {
+    const int K = c.K;
+    const bool writes_obs = c.out.obs != nullptr;
+    const bool capturing = stream_is_capturing(h);
+    int rc = restart_pace(h, c, capturing);
+    if (rc) return rc;
     h->kp.pace_slot = h->pace_slot;
-    if (h->check_inputs && actions && !inputs_checked) {
-        hipError_t ce = ccx::launch_check_inputs(h->stream, actions, order, (size_t)K * (size_t)h->E, h->N,
-                                                 h->input_errors);
-        if (ce != hipSuccess) return fail(CCX_EHIP, "input check kernel launch failed: %s", hipGetErrorString(ce));
-    }
+    if (!c.inputs_checked) rc = enqueue_input_check(h, K, c.actions, c.order);
+    if (rc) return rc;
     // A launch that is being captured into a HIP graph is replayed with these very arguments: the controller
     // cannot adapt across replays (the slot flip below happens once, at capture time), so such a launch runs
     // at the pace in effect and neither votes nor touches the controller's state.
@@ -405,7 +430,7 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
 #endif
     const bool adaptive = ccx::launch_is_adaptive(kp.pace_state != nullptr, kp.pace_adapt != 0u, writes_obs, K, kp.pace_min_k, kp.adapt_min_k);
     if (adaptive && capturing) kp.pace_adapt = 0u;
-    int rc = begin_timed(h);
+    rc = begin_timed(h);
     if (rc) return rc;
     // A grid of more workgroups than the device holds is launched ROUND BY ROUND: one launch per `resident_blocks`
     // workgroups, back to back on the stream.  In ONE launch the workgroups of the second round start as slots come free, each on
@@ -443,12 +468,12 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
         for (int b0 = 0; b0 < shape.num_blocks && e == hipSuccess; b0 += per_round) {
             round.num_blocks = std::min(per_round, shape.num_blocks - b0);
             kp.block_base = (uint32_t)b0;
-            e = ccx::launch_rollout(round, h->stream, kp, h->st, h->cell_info, actions,
-                                    order, K, auto_reset, h->pool, out, h->counters, policy, actions_out);
+            e = ccx::launch_rollout(round, h->stream, kp, h->st, h->cell_info, c.actions,
+                                    c.order, K, c.auto_reset, h->pool, c.out, h->counters, c.policy, c.actions_out);
         }
     } else {
-        e = ccx::launch_rollout(shape, h->stream, kp, h->st, h->cell_info, actions,
-                                order, K, auto_reset, h->pool, out, h->counters, policy, actions_out);
+        e = ccx::launch_rollout(shape, h->stream, kp, h->st, h->cell_info, c.actions,
+                                c.order, K, c.auto_reset, h->pool, c.out, h->counters, c.policy, c.actions_out);
     }
     if (e != hipSuccess) return fail(CCX_EHIP, "rollout kernel launch failed: %s", hipGetErrorString(e));
     // the kernel collected the votes for the next pace in the other slot (same condition as in the kernel)
@@ -456,12 +481,51 @@ int run_rollout(ccx_handle* h, int K, const uint8_t* actions, const uint8_t* ord
     return end_timed(h);
 }
 
-// ccx_bind_action_masks: every call that advanced the state leaves the masks of its final state at the bound pointer --
-// written by the step kernel itself (`written`), or by the stand-alone kernel behind the call's last launch
-int finish_masks(ccx_handle* h, bool written) {
-    if (!h->bound_masks || written) return CCX_OK;
-    hipError_t e = ccx::launch_action_masks(h->stream, launch_params(h), h->st, h->cell_info, h->bound_masks);
-    if (e != hipSuccess) return fail(CCX_EHIP, "action mask kernel launch failed: %s", hipGetErrorString(e));
+// one launch of a call: the step kernel where it applies, else the rollout kernel
+Launched launch_one(ccx_handle* h, const StepCall& c) {
+    const int rc = check_out_align(c.out);
+    if (rc) return rc;
+    CCX_HIP(hipSetDevice(h->device));
+    if (c.K <= ccx::kStepMaxK && c.actions && c.policy == 0 && !c.actions_out && h->step_shape.ok && h->tun_step_kernel != 0)
+        return launch_short(h, c);
+    return launch_paced(h, c);
+}
+
+// ---- the cutter: a call as one launch, or as several below 4 GiB per stream --------------------------------------------
+Launched run_rollout(ccx_handle* h, const StepCall& c) {
+    // The writer waves address the small output streams (rewards, flag bytes, compact rows, chosen actions) with 32-bit
+    // byte offsets from the stream's base: one launch must stay below 4 GiB per stream.  Longer rollouts are cut into
+    // launches on the same stream (bit-identical: an env's trajectory does not depend on how a rollout is split).
+    const unsigned long long per_step = (unsigned long long)h->E * (unsigned long long)h->N * 16ull;   // the widest stream
+    const unsigned long long fit = 0xFFFFFFFFull / per_step;
+    int max_k = (int)std::min<unsigned long long>(fit > 1 ? fit - 1 : 1, 0x7FFFFFFFull);
+    if (h->tun_max_launch_steps > 0) max_k = std::min(max_k, h->tun_max_launch_steps);   // (tests: force the cut)
+    // L = 6 + 4N is 2 mod 4: one step's observation slab (E x N x L floats) is a multiple of 16 bytes only when E x N is
+    // even; with E x N odd every sub-launch must start on an EVEN step so that its slice of the tensor stays 16-byte
+    // aligned (an odd cut failed on "obs buffer must be 16-byte aligned" after the first sub-launch had
+    // already advanced the state)
+    const bool odd_slab = c.out.obs && ((((size_t)h->E * h->N * (size_t)(6 + 4 * h->N) * sizeof(float)) & 15u) != 0);
+    if (odd_slab && max_k > 1) max_k &= ~1;
+    if (c.K <= max_k) return launch_one(h, c);
+    if (odd_slab && max_k == 1)
+        return fail(CCX_EINVAL, "a rollout of an odd number of agent slots (E x N = %lld) cannot be cut into launches of "
+                    "one step: its per-step observation slabs are not 16-byte aligned (raise max_launch_steps to >= 2)",
+                    (long long)h->E * h->N);
+    const size_t EN = (size_t)h->E * h->N;
+    for (int k0 = 0; k0 < c.K; k0 += max_k) {
+        StepCall sub = c;
+        sub.K = std::min(max_k, c.K - k0);
+        if (c.actions) sub.actions = c.actions + (size_t)k0 * EN;
+        if (c.order) sub.order = c.order + (size_t)k0 * EN;
+        if (c.actions_out) sub.actions_out = c.actions_out + (size_t)k0 * EN;
+        sub.out = kout_at(h, c.out, k0);
+        // (the sub-launches get neither `masks` nor `rso`: a call that is cut leaves both to the stand-alone kernels
+        //  behind its LAST launch -- finish_call -- also where it is cut into single steps; same bytes)
+        sub.masks = nullptr;
+        sub.rso = nullptr;
+        const Launched l = launch_one(h, sub);
+        if (l.rc) return l;
+    }
     return CCX_OK;
 }
 
@@ -476,83 +540,69 @@ int check_reset_obs(const ccx_handle* h, const ccx::KOut& ko, int auto_reset) {
     if (!ko.env_flags)
         return fail(CCX_EINVAL, "CCX_RESET_OBS_NEXT: a call with auto-reset that asks for obs or obs_compact must pass env_flags "
                     "too (the restarted envs are found there)");
-    const uintptr_t align = (h->N % 2) == 0 ? 15u : 7u;
-    if (ko.obs && h->bound_final_obs && (reinterpret_cast<uintptr_t>(h->bound_final_obs) & align))
-        return fail(CCX_EINVAL, "final_obs buffer must be %d-byte aligned", (int)align + 1);
-    if (ko.obs_compact && h->bound_final_compact && (reinterpret_cast<uintptr_t>(h->bound_final_compact) & 15u))
+    const unsigned align = (h->N % 2) == 0 ? 16u : 8u;
+    if (ko.obs && misaligned(h->bound_final_obs, align)) return fail(CCX_EINVAL, "final_obs buffer must be %u-byte aligned", align);
+    if (ko.obs_compact && misaligned(h->bound_final_compact, 16))
         return fail(CCX_EINVAL, "final_compact buffer must be 16-byte aligned");
     return CCX_OK;
 }
 
-// ... every call that wrote K steps of rows with auto-reset leaves the restarted rows at the CCX_EF_RESET pairs: written by
-// the step kernel itself (`written`), or by the fix-up kernel behind the call's last launch -- once for the whole call, from
-// the episode counters that launch left (ccx_reset_obs.hip)
-int finish_reset_obs(ccx_handle* h, int K, const ccx::KOut& ko, int auto_reset, bool written) {
-    if (written || !reset_obs_on(h, ko, auto_reset)) return CCX_OK;
-    hipError_t e = ccx::launch_reset_obs(h->stream, launch_params(h), h->st, K, ko.env_flags, h->pool, ko.obs, ko.obs_compact,
-                                         ko.obs ? h->bound_final_obs : nullptr, ko.obs_compact ? h->bound_final_compact : nullptr);
-    if (e != hipSuccess) return fail(CCX_EHIP, "reset-observation kernel launch failed: %s", hipGetErrorString(e));
-    return CCX_OK;
-}
-
-// ---- loops that step ONE env-step per launch (the MT19937 policy loop, the unfused mixed-control step) -----------------
-ccx::KOut kout_of(const ccx_rollout_out* out) {
-    ccx::KOut ko{};
-    if (out) {
-        ko.obs = out->obs;
-        ko.reward = out->reward;
-        ko.agent_flags = out->agent_flags;
-        ko.env_flags = out->env_flags;
-        ko.obs_compact = out->obs_compact;
+// ---- the epilogue of EVERY call that advanced the state by K steps, behind its last launch, for what `l` did not do itself:
+// ccx_bind_action_masks -- the masks of the final state at the bound pointer (the stand-alone mask kernel);
+// CCX_RESET_OBS_NEXT -- the restarted rows at the CCX_EF_RESET pairs of a call that wrote rows with auto-reset (the fix-up
+// kernel, once for the whole call, from the episode counters the last launch left: ccx_reset_obs.hip)
+int finish_call(ccx_handle* h, int K, const ccx::KOut& ko, int auto_reset, const Launched& l) {
+    if (l.rc) return l.rc;
+    if (h->bound_masks && !l.masks_written) {
+        hipError_t e = ccx::launch_action_masks(h->stream, launch_params(h), h->st, h->cell_info, h->bound_masks);
+        if (e != hipSuccess) return fail(CCX_EHIP, "action mask kernel launch failed: %s", hipGetErrorString(e));
     }
-    return ko;
-}
-
-// the outputs of step s of a [K][...] trajectory
-ccx::KOut kout_at(const ccx_handle* h, const ccx::KOut& ko, int s) {
-    const size_t EN = (size_t)h->E * h->N, L = (size_t)(6 + 4 * h->N);
-    ccx::KOut o = ko;
-    if (o.obs) o.obs += (size_t)s * EN * L;
-    if (o.reward) o.reward += (size_t)s * EN;
-    if (o.agent_flags) o.agent_flags += (size_t)s * EN;
-    if (o.env_flags) o.env_flags += (size_t)s * (size_t)h->E;
-    if (o.obs_compact) o.obs_compact += (size_t)s * EN * 4u;
-    return o;
-}
-
-// The scratch buffers of such a loop, allocated on first use and never inside a stream capture: one step's actions
-// (unless the caller's actions_out takes them) and, where a step's slice of the observation tensor is not 16-byte aligned
-// (E x N x L x 4 not a multiple of 16), an aligned staging slab.
-int stepwise_scratch(ccx_handle* h, bool own_actions, const ccx::KOut& ko, int num_steps, const char* what) {
-    const size_t EN = (size_t)h->E * h->N, L = (size_t)(6 + 4 * h->N);
-    const bool misaligned_steps = ko.obs && ((EN * L * sizeof(float)) & 15u) && num_steps > 1;
-    if ((own_actions && !h->stream_actions) || (misaligned_steps && !h->stream_obs)) {
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        if (hipStreamIsCapturing(h->stream, &cap) != hipSuccess) (void)hipGetLastError();
-        else if (cap != hipStreamCaptureStatusNone)
-            return fail(CCX_EINVAL, "%s allocates scratch buffers on first use: run one eager call of this shape before "
-                        "capturing it into a graph", what);
-        if (own_actions && !h->stream_actions) CCX_HIP(hipMalloc(&h->stream_actions, EN));
-        if (misaligned_steps && !h->stream_obs) CCX_HIP(hipMalloc(&h->stream_obs, EN * L * sizeof(float)));
+    if (!l.reset_obs_written && reset_obs_on(h, ko, auto_reset)) {
+        hipError_t e = ccx::launch_reset_obs(h->stream, launch_params(h), h->st, K, ko.env_flags, h->pool, ko.obs, ko.obs_compact,
+                                             ko.obs ? h->bound_final_obs : nullptr, ko.obs_compact ? h->bound_final_compact : nullptr);
+        if (e != hipSuccess) return fail(CCX_EHIP, "reset-observation kernel launch failed: %s", hipGetErrorString(e));
     }
     return CCX_OK;
 }
 
-// step s of such a loop through the ordinary step path, its observation rows staged where their slice is misaligned
-int stepwise_step(ccx_handle* h, const ccx::KOut& ko, int s, const uint8_t* acts, const uint8_t* order, int auto_reset,
-                  bool inputs_checked) {
+// ---- the loop that steps ONE env-step per launch (the MT19937 policy loop, the unfused mixed-control step) ---------------
+// Its scratch buffers, allocated on first use and never inside a stream capture: one step's actions (unless the caller's
+// actions_out takes them) and, where a step's slice of the observation tensor is not 16-byte aligned (E x N x L x 4 not a
+// multiple of 16), an aligned staging slab.
+int stepwise_scratch(ccx_handle* h, const StepCall& c, const char* what) {
     const size_t EN = (size_t)h->E * h->N, L = (size_t)(6 + 4 * h->N);
-    ccx::KOut o = kout_at(h, ko, s);
-    float* const obs_dst = o.obs;
-    const bool staged = obs_dst && (reinterpret_cast<uintptr_t>(obs_dst) & 15u);
-    if (staged) {
-        if (!h->stream_obs) return fail(CCX_EINVAL, "obs buffer must be 16-byte aligned");   // (a misaligned BASE)
-        o.obs = h->stream_obs;
-    }
-    const int rc = run_rollout(h, 1, acts, order, auto_reset, o, 0, nullptr, inputs_checked);
-    if (rc) return rc;
-    if (staged) CCX_HIP(hipMemcpyAsync(obs_dst, h->stream_obs, EN * L * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    const bool own_actions = !c.actions_out && !h->stream_actions;
+    const bool staging = c.out.obs && ((EN * L * sizeof(float)) & 15u) && c.K > 1 && !h->stream_obs;
+    if (!own_actions && !staging) return CCX_OK;
+    if (stream_is_capturing(h))
+        return fail(CCX_EINVAL, "%s allocates scratch buffers on first use: run one eager call of this shape before "
+                    "capturing it into a graph", what);
+    if (own_actions) CCX_HIP(hipMalloc(&h->stream_actions, EN));
+    if (staging) CCX_HIP(hipMalloc(&h->stream_obs, EN * L * sizeof(float)));
     return CCX_OK;
+}
+
+// `produce_actions(s, acts)` enqueues what leaves step s's actions at `acts`; the step goes through the ordinary launch
+// path, its observation rows staged where their slice is misaligned
+template <class Produce>
+Launched run_stepwise(ccx_handle* h, const StepCall& c, const char* what, Produce produce_actions) {
+    const size_t EN = (size_t)h->E * h->N, L = (size_t)(6 + 4 * h->N);
+    int rc = stepwise_scratch(h, c, what);
+    for (int s = 0; s < c.K && !rc; ++s) {
+        uint8_t* const acts = c.actions_out ? c.actions_out + (size_t)s * EN : h->stream_actions;
+        StepCall step{1, acts, c.order ? c.order + (size_t)s * EN : nullptr, c.auto_reset, kout_at(h, c.out, s)};
+        step.inputs_checked = c.inputs_checked;
+        float* const obs_dst = step.out.obs;
+        const bool staged = misaligned(obs_dst, 16);
+        if (staged) {
+            if (!h->stream_obs) return fail(CCX_EINVAL, "obs buffer must be 16-byte aligned");   // (a misaligned BASE)
+            step.out.obs = h->stream_obs;
+        }
+        rc = produce_actions(s, acts);
+        if (!rc) rc = run_rollout(h, step).rc;
+        if (!rc && staged) CCX_HIP(hipMemcpyAsync(obs_dst, h->stream_obs, EN * L * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+    }
+    return rc;
 }
 
 }  // namespace
@@ -855,27 +905,16 @@ int ccx_expand_observations(ccx_handle* h, const float* obs_compact, int64_t row
 
 int ccx_step(ccx_handle* h, const uint8_t* actions, const uint8_t* order, const ccx_step_out* out) {
     if (!h || !actions) return fail(CCX_EINVAL, "NULL argument");
-    ccx::KOut ko{};
-    if (out) {
-        ko.obs = out->obs;
-        ko.reward = out->reward;
-        ko.agent_flags = out->agent_flags;
-        ko.env_flags = out->env_flags;
-        ko.obs_compact = out->obs_compact;
-    }
-    bool written = false;
-    const int rc = run_rollout(h, 1, actions, order, 0, ko, 0, nullptr, false, h->bound_masks, &written);
-    return rc ? rc : finish_masks(h, written);
+    StepCall c{1, actions, order, 0, kout_of(out)};
+    c.masks = h->bound_masks;
+    return finish_call(h, 1, c.out, 0, run_rollout(h, c));
 }
 
 int ccx_step_begin(ccx_handle* h, const uint8_t* actions, const uint8_t* order) {
     if (!h || !actions) return fail(CCX_EINVAL, "NULL argument");
     CCX_HIP(hipSetDevice(h->device));
-    if (h->check_inputs) {
-        hipError_t ce = ccx::launch_check_inputs(h->stream, actions, order, (size_t)h->E, h->N, h->input_errors);
-        if (ce != hipSuccess) return fail(CCX_EHIP, "input check kernel launch failed: %s", hipGetErrorString(ce));
-    }
-    int rc = begin_timed(h);
+    int rc = enqueue_input_check(h, 1, actions, order);
+    if (!rc) rc = begin_timed(h);
     if (rc) return rc;
     hipError_t e = ccx::launch_step_begin(h->stream, h->kp, h->st, ceil_log2(h->N), actions, order, h->counters);
     if (e != hipSuccess) return fail(CCX_EHIP, "step_begin kernel launch failed: %s", hipGetErrorString(e));
@@ -885,25 +924,13 @@ int ccx_step_begin(ccx_handle* h, const uint8_t* actions, const uint8_t* order) 
 int ccx_step_finish(ccx_handle* h, const double* reward, const int8_t* terminated, const uint8_t* truncated,
                     const ccx_step_out* out, uint8_t* term_present, int32_t auto_reset) {
     if (!h) return fail(CCX_EINVAL, "NULL handle");
-    if (auto_reset && (!h->pool || h->pool_size <= 0))
-        return fail(CCX_EINVAL, "auto_reset needs a reset pool (ccx_set_reset_pool)");
-    ccx::KOut ko{};
-    if (out) {
-        ko.obs = out->obs;
-        ko.reward = out->reward;
-        ko.agent_flags = out->agent_flags;
-        ko.env_flags = out->env_flags;
-        ko.obs_compact = out->obs_compact;
-    }
+    int rc = need_pool_for_auto_reset(h, auto_reset);
+    if (rc) return rc;
+    const ccx::KOut ko = kout_of(out);
     // (odd agent counts write the rows in 8-byte units: csrc/ccx_split_step.hip, PAIR = false)
-    const uintptr_t obs_align = (h->N % 2) == 0 ? 15u : 7u;
-    if (ko.obs && (reinterpret_cast<uintptr_t>(ko.obs) & obs_align))
-        return fail(CCX_EINVAL, "obs buffer must be %d-byte aligned", (int)obs_align + 1);
-    if ((ko.reward && (reinterpret_cast<uintptr_t>(ko.reward) & 7u)) || (reward && (reinterpret_cast<uintptr_t>(reward) & 7u)))
-        return fail(CCX_EINVAL, "reward buffers must be 8-byte aligned");
-    if (ko.obs_compact && (reinterpret_cast<uintptr_t>(ko.obs_compact) & 15u))
-        return fail(CCX_EINVAL, "obs_compact buffer must be 16-byte aligned");
-    int rc = check_reset_obs(h, ko, auto_reset);
+    rc = check_out_align(ko, (h->N % 2) == 0 ? 16 : 8, "reward buffers");
+    if (!rc && misaligned(reward, 8)) rc = fail(CCX_EINVAL, "reward buffers must be 8-byte aligned");
+    if (!rc) rc = check_reset_obs(h, ko, auto_reset);
     if (rc) return rc;
     CCX_HIP(hipSetDevice(h->device));
     rc = begin_timed(h);
@@ -911,33 +938,22 @@ int ccx_step_finish(ccx_handle* h, const double* reward, const int8_t* terminate
     hipError_t e = ccx::launch_step_finish(h->shape, h->stream, h->kp, h->st, h->cell_info, reward, terminated, truncated, ko,
                                            term_present, auto_reset ? 1 : 0, h->pool, h->counters);
     if (e != hipSuccess) return fail(CCX_EHIP, "step_finish kernel launch failed: %s", hipGetErrorString(e));
-    rc = end_timed(h);
-    if (!rc) rc = finish_masks(h, false);
-    return rc ? rc : finish_reset_obs(h, 1, ko, auto_reset, false);
+    return finish_call(h, 1, ko, auto_reset, end_timed(h));
 }
 
 int ccx_rollout(ccx_handle* h, int32_t num_steps, const uint8_t* actions, const uint8_t* order,
                 int32_t auto_reset, const ccx_rollout_out* out) {
     if (!h || !actions) return fail(CCX_EINVAL, "NULL argument");
     if (num_steps < 1) return fail(CCX_EINVAL, "num_steps must be >= 1");
-    if (auto_reset && (!h->pool || h->pool_size <= 0))
-        return fail(CCX_EINVAL, "auto_reset needs a reset pool (ccx_set_reset_pool)");
-    ccx::KOut ko{};
-    if (out) {
-        ko.obs = out->obs;
-        ko.reward = out->reward;
-        ko.agent_flags = out->agent_flags;
-        ko.env_flags = out->env_flags;
-        ko.obs_compact = out->obs_compact;
-    }
-    int rc = check_reset_obs(h, ko, auto_reset);
+    int rc = need_pool_for_auto_reset(h, auto_reset);
     if (rc) return rc;
-    const ccx::StepResetObs rso{ko.obs ? h->bound_final_obs : nullptr, ko.obs_compact ? h->bound_final_compact : nullptr};
-    bool written = false, rso_written = false;
-    rc = run_rollout(h, num_steps, actions, order, auto_reset ? 1 : 0, ko, 0, nullptr, false, h->bound_masks, &written,
-                     reset_obs_on(h, ko, auto_reset) ? &rso : nullptr, &rso_written);
-    if (!rc) rc = finish_masks(h, written);
-    return rc ? rc : finish_reset_obs(h, num_steps, ko, auto_reset, rso_written);
+    StepCall c{num_steps, actions, order, auto_reset ? 1 : 0, kout_of(out)};
+    rc = check_reset_obs(h, c.out, auto_reset);
+    if (rc) return rc;
+    const ccx::StepResetObs rso{c.out.obs ? h->bound_final_obs : nullptr, c.out.obs_compact ? h->bound_final_compact : nullptr};
+    c.masks = h->bound_masks;
+    c.rso = reset_obs_on(h, c.out, auto_reset) ? &rso : nullptr;
+    return finish_call(h, num_steps, c.out, auto_reset, run_rollout(h, c));
 }
 
 int ccx_rollout_policy(ccx_handle* h, int32_t num_steps, int32_t policy, int32_t auto_reset,
@@ -946,43 +962,25 @@ int ccx_rollout_policy(ccx_handle* h, int32_t num_steps, int32_t policy, int32_t
     if (num_steps < 1) return fail(CCX_EINVAL, "num_steps must be >= 1");
     if (policy != CCX_POLICY_GREEDY && policy != CCX_POLICY_WAITING && policy != CCX_POLICY_RANDOM)
         return fail(CCX_EINVAL, "unknown policy %d", policy);
-    if (auto_reset && (!h->pool || h->pool_size <= 0))
-        return fail(CCX_EINVAL, "auto_reset needs a reset pool (ccx_set_reset_pool)");
-    ccx::KOut ko{};
-    if (out) {
-        ko.obs = out->obs;
-        ko.reward = out->reward;
-        ko.agent_flags = out->agent_flags;
-        ko.env_flags = out->env_flags;
-        ko.obs_compact = out->obs_compact;
-    }
-    {
-        const int rc = check_reset_obs(h, ko, auto_reset);
-        if (rc) return rc;
-    }
+    int rc = need_pool_for_auto_reset(h, auto_reset);
+    if (rc) return rc;
+    const StepCall c{num_steps, nullptr, nullptr, auto_reset ? 1 : 0, kout_of(out), policy, actions_out};
+    rc = check_reset_obs(h, c.out, auto_reset);
+    if (rc) return rc;
     if (h->eps_stream == CCX_EPS_STREAM_MT19937 && policy != CCX_POLICY_RANDOM && h->epsilon > 0.0) {
         // The reference's stream is sequential per env: the policy runs as its own kernel between the steps (policy -> step
         // -> policy ..., each a launch on the handle's stream) instead of inside the fused one.  Meant for replaying the
         // reference's epsilon episodes action for action, not for throughput.
         CCX_HIP(hipSetDevice(h->device));
-        const size_t EN = (size_t)h->E * h->N;
-        int rc = stepwise_scratch(h, !actions_out, ko, num_steps, "the stepwise policy loop");
-        if (rc) return rc;
-        for (int s = 0; s < num_steps; ++s) {
-            uint8_t* acts = actions_out ? actions_out + (size_t)s * EN : h->stream_actions;
+        auto mt_policy = [&](int, uint8_t* acts) {
             hipError_t e = ccx::launch_policy_stream_actions(h->stream, launch_params(h), h->st, h->cell_info, acts, policy, h->mt_state,
                                                              h->epsilon);
-            if (e != hipSuccess) return fail(CCX_EHIP, "policy kernel launch failed: %s", hipGetErrorString(e));
-            rc = stepwise_step(h, ko, s, acts, nullptr, auto_reset ? 1 : 0, false);
-            if (rc) return rc;
-        }
-        rc = finish_masks(h, false);
-        return rc ? rc : finish_reset_obs(h, num_steps, ko, auto_reset, false);
+            return e == hipSuccess ? (int)CCX_OK : fail(CCX_EHIP, "policy kernel launch failed: %s", hipGetErrorString(e));
+        };
+        return finish_call(h, num_steps, c.out, auto_reset, run_stepwise(h, c, "the stepwise policy loop", mt_policy));
     }
     // (grids whose occupancy tables exceed the LDS run the in-kernel policies through the all-pairs exchange: round 4)
-    int rc = run_rollout(h, num_steps, nullptr, nullptr, auto_reset ? 1 : 0, ko, policy, actions_out);
-    if (!rc) rc = finish_masks(h, false);
-    return rc ? rc : finish_reset_obs(h, num_steps, ko, auto_reset, false);
+    return finish_call(h, num_steps, c.out, auto_reset, run_rollout(h, c));
 }
 
 int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t scripted_slots,
@@ -999,66 +997,49 @@ int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t
     if (!actions && scripted_slots != all_slots)
         return fail(CCX_EINVAL, "actions may be NULL only when scripted_slots covers all %d slots (got 0x%llx)", h->N,
                     (unsigned long long)scripted_slots);
-    if (auto_reset && (!h->pool || h->pool_size <= 0))
-        return fail(CCX_EINVAL, "auto_reset needs a reset pool (ccx_set_reset_pool)");
+    int rc = need_pool_for_auto_reset(h, auto_reset);
+    if (rc) return rc;
     if (h->eps_stream == CCX_EPS_STREAM_MT19937 && h->epsilon > 0.0)
         return fail(CCX_EINVAL, "a mixed-control step cannot draw from the MT19937 exploration stream: that stream is "
                     "sequential per env and walked by a kernel of its own (ccx_policy_actions); select "
                     "CCX_EPS_STREAM_COUNTER or set epsilon to 0");
-    const ccx::KOut ko = kout_of(out);
-    if (ko.obs && (reinterpret_cast<uintptr_t>(ko.obs) & 15u)) return fail(CCX_EINVAL, "obs buffer must be 16-byte aligned");
-    if (ko.reward && (reinterpret_cast<uintptr_t>(ko.reward) & 7u)) return fail(CCX_EINVAL, "reward buffer must be 8-byte aligned");
-    if (ko.obs_compact && (reinterpret_cast<uintptr_t>(ko.obs_compact) & 15u))
-        return fail(CCX_EINVAL, "obs_compact buffer must be 16-byte aligned");
-    {
-        const int rc = check_reset_obs(h, ko, auto_reset);
-        if (rc) return rc;
-    }
+    const StepCall c{num_steps, actions, order, auto_reset ? 1 : 0, kout_of(out), 0, actions_out, /*inputs_checked=*/true};
+    rc = check_out_align(c.out);
+    if (!rc) rc = check_reset_obs(h, c.out, auto_reset);
+    if (rc) return rc;
     CCX_HIP(hipSetDevice(h->device));
     const size_t EN = (size_t)h->E * h->N;
-    const bool fused = h->step_shape.ok && h->tun_step_kernel != 0;
     // ccx_set_check_inputs: the caller's bytes outside the mask and the order rows, once, on either path
-    if (h->check_inputs && (actions || order)) {
-        hipError_t ce = ccx::launch_check_inputs(h->stream, actions, order, (size_t)num_steps * (size_t)h->E, h->N,
-                                                 h->input_errors, scripted_slots);
-        if (ce != hipSuccess) return fail(CCX_EHIP, "input check kernel launch failed: %s", hipGetErrorString(ce));
-    }
-    if (fused) {
-        uint8_t* const m = ccx::step_masks_fused(num_steps, order != nullptr) ? h->bound_masks : nullptr;
+    rc = enqueue_input_check(h, num_steps, actions, order, scripted_slots);
+    if (rc) return rc;
+    if (h->step_shape.ok && h->tun_step_kernel != 0) {
         // the short-launch kernel's policy instantiations (ccx_step.hip, POL): policy + merge + step in ONE launch per
         // <= 16 steps (16 is even: every sub-launch's slice of the observation tensor stays 16-byte aligned)
-        for (int k0 = 0; k0 < num_steps; k0 += ccx::kStepMaxK) {
-            const int kk = std::min(ccx::kStepMaxK, num_steps - k0);
+        Launched l;
+        for (int k0 = 0; k0 < num_steps && !l.rc; k0 += ccx::kStepMaxK) {
             const ccx::StepPolicy pol{scripted_slots, policy, actions_out ? actions_out + (size_t)k0 * EN : nullptr};
-            int rc = begin_timed(h);
-            if (rc) return rc;
-            hipError_t e = ccx::launch_step(h->step_shape, h->stream, launch_params(h), h->st_slab, h->cell_info,
-                                            actions ? actions + (size_t)k0 * EN : nullptr, order ? order + (size_t)k0 * EN : nullptr,
-                                            kk, auto_reset ? 1 : 0, h->pool, kout_at(h, ko, k0), h->counters, &pol, m);
-            if (e != hipSuccess) return fail(CCX_EHIP, "step kernel launch failed: %s", hipGetErrorString(e));
-            rc = end_timed(h);
-            if (rc) return rc;
+            StepCall sub = c;
+            sub.K = std::min(ccx::kStepMaxK, num_steps - k0);
+            if (actions) sub.actions = actions + (size_t)k0 * EN;
+            if (order) sub.order = order + (size_t)k0 * EN;
+            sub.out = kout_at(h, c.out, k0);
+            sub.masks = ccx::step_masks_fused(num_steps, order != nullptr) ? h->bound_masks : nullptr;   // (only a call of ONE step)
+            l = launch_short(h, sub, &pol);
         }
-        const int rc = finish_masks(h, m != nullptr);
-        return rc ? rc : finish_reset_obs(h, num_steps, ko, auto_reset, false);
+        return finish_call(h, num_steps, c.out, auto_reset, l);
     }
     // Handles whose short launches cannot use the step kernel (tables beyond the LDS, or the tunable): the composition
     // itself, step by step on the handle's stream -- policy kernel, merge kernel, the existing step path.
-    int rc = stepwise_scratch(h, !actions_out, ko, num_steps, "the unfused mixed-control step");
-    if (rc) return rc;
-    for (int s = 0; s < num_steps; ++s) {
-        uint8_t* acts = actions_out ? actions_out + (size_t)s * EN : h->stream_actions;
+    auto policy_then_merge = [&](int s, uint8_t* acts) {
         hipError_t e = ccx::launch_greedy_actions(h->stream, launch_params(h), h->st, h->cell_info, acts, policy);
         if (e != hipSuccess) return fail(CCX_EHIP, "policy kernel launch failed: %s", hipGetErrorString(e));
         if (scripted_slots != all_slots) {
             e = ccx::launch_merge_actions(h->stream, acts, actions + (size_t)s * EN, scripted_slots, h->N, EN);
             if (e != hipSuccess) return fail(CCX_EHIP, "merge kernel launch failed: %s", hipGetErrorString(e));
         }
-        rc = stepwise_step(h, ko, s, acts, order ? order + (size_t)s * EN : nullptr, auto_reset ? 1 : 0, true);
-        if (rc) return rc;
-    }
-    rc = finish_masks(h, false);
-    return rc ? rc : finish_reset_obs(h, num_steps, ko, auto_reset, false);
+        return (int)CCX_OK;
+    };
+    return finish_call(h, num_steps, c.out, auto_reset, run_stepwise(h, c, "the unfused mixed-control step", policy_then_merge));
 }
 
 int ccx_action_masks(ccx_handle* h, uint8_t* masks) {
@@ -1335,7 +1316,7 @@ int ccx_set_pace_calibration(ccx_handle* h, int32_t enabled) {
 
 int ccx_get_pace_start(ccx_handle* h, float* ns_per_env_step, int32_t* source, float* probe_gbs) {
     if (!h) return fail(CCX_EINVAL, "NULL handle");
-    if (ns_per_env_step) *ns_per_env_step = h->kp.pace_state ? (float)((double)h->pace_init_fp / 256.0 * 10.0) : 0.0f;
+    if (ns_per_env_step) *ns_per_env_step = h->kp.pace_state ? ccxp::fp_to_ns(h->pace_init_fp) : 0.0f;
     if (source) *source = h->kp.pace_state ? h->pace_start_source : CCX_PACE_START_UNPACED;
     if (probe_gbs) *probe_gbs = h->pace_probe_gbs;
     return CCX_OK;
@@ -1366,7 +1347,9 @@ int ccx_set_tunable(ccx_handle* h, const char* name, int32_t value) {
             *t.slot = value;
             return choose_shape(h);
         }
-    return fail(CCX_EINVAL, "unknown tunable '%s' (pace_phase, tile_map, hand2, writer_roles, max_launch_steps, pair_rows, small_shape, round_launches, occ_tables, step_kernel, step_rows, step_lanes, stats_naive, reset_obs_fused)", name);
+    std::string names;
+    for (auto& t : table) names.append(names.empty() ? "" : ", ").append(t.name);
+    return fail(CCX_EINVAL, "unknown tunable '%s' (%s)", name, names.c_str());
 }
 
 int ccx_get_step_pace(ccx_handle* h, float* ns_per_env_step) {
@@ -1381,7 +1364,7 @@ int ccx_get_step_pace(ccx_handle* h, float* ns_per_env_step) {
         CCX_HIP(hipMemcpy(st, h->pace_state, sizeof(st), hipMemcpyDeviceToHost));
         fp = st[h->pace_slot] > st[2] ? st[h->pace_slot] : st[2];
     }
-    *ns_per_env_step = (float)((double)fp / 256.0 * 10.0);
+    *ns_per_env_step = ccxp::fp_to_ns(fp);
     return CCX_OK;
 }
 
@@ -1391,7 +1374,7 @@ int ccx_get_pace_state(ccx_handle* h, float* out6) {
     CCX_HIP(hipStreamSynchronize(h->stream));
     uint32_t st[8];
     CCX_HIP(hipMemcpy(st, h->pace_state, sizeof(st), hipMemcpyDeviceToHost));
-    auto ns = [](uint32_t fp) { return (float)((double)fp / 256.0 * 10.0); };
+    const auto ns = ccxp::fp_to_ns;
     out6[0] = h->pace_dirty ? ns(h->pace_init_fp) : ns(st[h->pace_slot]);   // the vote the next launch reads
     out6[1] = h->pace_dirty ? 0.0f : ns(st[2]);                             // floor
     out6[2] = h->pace_dirty ? 0.0f : (float)st[3];                          // launches since the last collapse

@@ -78,6 +78,7 @@ struct LdsLayout { size_t off_tiles, off_ws, off_occ, tile_stride, total, occ_by
 inline size_t up16(size_t v) { return (v + 15u) & ~(size_t)15u; }
 int ceil_log2(int n);
 uint32_t to_fp(double ns);   // ns per env-step -> ticks of the 100 MHz clock x 256, clamped to 1 .. 4e9
+inline float fp_to_ns(uint32_t fp) { return (float)((double)fp / 256.0 * 10.0); }   // ... and back
 
 // THE LDS size model of the rollout kernel: a ring of `ring_slots`, `writer_slots` staging slots per tile, `tiles_per_block`
 // tiles of `ew` envs, with or without the occupancy tables; the reward table comes from `in`.
