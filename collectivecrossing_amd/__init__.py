@@ -11,7 +11,7 @@ from .configs import CollectiveCrossingConfig  # noqa: F401
 
 __version__ = "0.4.0"
 __all__ = ["CollectiveCrossingConfig", "CollectiveCrossingEnv", "BatchedCollectiveCrossing", "VectorCollectiveCrossing",
-           "BatchedMultiAgentEnv", "unpack_action_masks"]
+           "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult"]
 
 
 def __getattr__(name):  # lazy: importing the configs must not pull in torch
@@ -30,6 +30,9 @@ def __getattr__(name):  # lazy: importing the configs must not pull in torch
     if name == "unpack_action_masks":
         from .batched import unpack_action_masks
         return unpack_action_masks
+    if name == "GaeResult":
+        from .batched import GaeResult
+        return GaeResult
     raise AttributeError(name)
 
 

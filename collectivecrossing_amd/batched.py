@@ -92,6 +92,16 @@ class FinishedEpisodes:
         return len(self.env)
 
 
+@dataclass
+class GaeResult:
+    """Advantages and value targets of a trajectory (:meth:`BatchedCollectiveCrossing.compute_gae`, include/ccx.h CCX_GAE).
+    Every element is written: +0.0 / 0 where the agent had no step (``valid`` = 0)."""
+
+    advantages: torch.Tensor  # f32 [K, E, N]
+    returns: torch.Tensor     # f32 [K, E, N]: advantages + values, the critic's regression target
+    valid: torch.Tensor | None  # u8 [K, E, N]: 1 where the agent was live in the step (a loss averages over these)
+
+
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
     return C.c_void_p(None if t is None else t.data_ptr())
 
@@ -626,6 +636,63 @@ class BatchedCollectiveCrossing:
         """Empty the finished-episode log: stored = dropped = 0 (``ccx_episode_log_clear``).  Only enqueues."""
         self._need_tracking()
         check(self._lib.ccx_episode_log_clear(self._h))
+
+    # ------------------------------------------------------------------ advantages
+    def alloc_gae(self, num_steps: int, want_valid: bool = True) -> GaeResult:
+        """Output tensors of :meth:`compute_gae` for a K-step trajectory (static buffers for a captured graph)."""
+        shape = (int(num_steps), self.num_envs, self.num_agents)
+        return GaeResult(self._new(shape, torch.float32), self._new(shape, torch.float32),
+                         self._new(shape, torch.uint8) if want_valid else None)
+
+    def compute_gae(self, traj, values: torch.Tensor, last_values: torch.Tensor, final_values: torch.Tensor | None = None,
+                    gamma: float = 0.99, lam: float = 0.95, out: GaeResult | None = None) -> GaeResult:
+        """Generalised advantage estimates and value targets on the device (``ccx_gae``, include/ccx.h CCX_GAE): one
+        kernel on the handle's stream, bit-defined (f32, one rounding per operation, the steps walked backwards).
+
+        ``traj`` is a :class:`RolloutResult` or a ``(reward f64 [K, E, N], agent_flags u8 [K, E, N], env_flags u8 [K, E])``
+        tuple; ``values`` f32 [K, E, N] holds the critic's value of the observation each step ACTED ON, ``last_values`` f32
+        [E, N] that of the state behind the last step, ``final_values`` f32 [K, E, N] (optional) that of the observation a
+        step ENDED ON -- read only where an episode is cut without termination (truncation, ``EF_RESET``); evaluate the
+        critic on ``final_obs`` there (``reset_obs="next"``).  Without it a cut bootstraps from 0.  Termination never
+        bootstraps.  ``out`` reuses a :class:`GaeResult` (``out.valid`` may be ``None``).  All tensors: contiguous, on the
+        batch's device; anything else raises ``ValueError`` before the library is called.  Only enqueues."""
+        if isinstance(traj, RolloutResult):
+            reward, agent_flags, env_flags = traj.reward, traj.agent_flags, traj.env_flags
+        else:
+            try:
+                reward, agent_flags, env_flags = traj
+            except (TypeError, ValueError):
+                raise ValueError("traj must be a RolloutResult or a (reward, agent_flags, env_flags) tuple") from None
+        E, N = self.num_envs, self.num_agents
+        K = int(reward.shape[0]) if isinstance(reward, torch.Tensor) and reward.dim() == 3 else 0
+        if K < 1:
+            raise ValueError(f"reward must be a torch.float64 tensor [K, {E}, {N}] with K >= 1")
+        gamma, lam = float(gamma), float(lam)
+        for name, x in (("gamma", gamma), ("lam", lam)):
+            if not 0.0 <= x <= 1.0:                                  # (false for NaN)
+                raise ValueError(f"{name} must be in [0, 1], got {x!r}")
+        if out is None:
+            out = self.alloc_gae(K)
+        elif not isinstance(out, GaeResult):
+            raise ValueError("out must be a GaeResult (alloc_gae)")
+        KEN = (K, E, N)
+        for name, t, dt, shape, optional in (
+                ("reward", reward, torch.float64, KEN, False), ("agent_flags", agent_flags, torch.uint8, KEN, False),
+                ("env_flags", env_flags, torch.uint8, (K, E), False), ("values", values, torch.float32, KEN, False),
+                ("last_values", last_values, torch.float32, (E, N), False),
+                ("final_values", final_values, torch.float32, KEN, True),
+                ("out.advantages", out.advantages, torch.float32, KEN, False),
+                ("out.returns", out.returns, torch.float32, KEN, False), ("out.valid", out.valid, torch.uint8, KEN, True)):
+            if t is None and optional:
+                continue
+            if (not isinstance(t, torch.Tensor) or t.dtype is not dt or t.device != self.device or tuple(t.shape) != shape
+                    or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
+        self._order_after_current_stream(reward, agent_flags, env_flags, values, last_values, final_values,
+                                         out.advantages, out.returns, out.valid)
+        check(self._lib.ccx_gae(self._h, K, _ptr(reward), _ptr(agent_flags), _ptr(env_flags), _ptr(values), _ptr(last_values),
+                                _ptr(final_values), gamma, lam, _ptr(out.advantages), _ptr(out.returns), _ptr(out.valid)))
+        return out
 
     # ------------------------------------------------------------------ compute
     def observe(self, out: torch.Tensor | None = None) -> torch.Tensor:

@@ -523,6 +523,66 @@ int ccx_episode_stats_update(ccx_handle* h, int32_t num_steps, const double* rew
 int ccx_episode_stats_reset(ccx_handle* h, const uint8_t* env_mask);
 int ccx_episode_log_clear(ccx_handle* h);
 /*
+ * CCX_GAE: generalised advantage estimates and value targets from the arrays a rollout left on the device plus a critic's
+ * values -- the step between ccx_rollout_out and a policy-gradient update (the reference trains with PPO,
+ * examples/training_script.py).  ccx_episode_stats_update is the forward pass over reward / agent_flags / env_flags; this is
+ * the backward pass over the same three arrays.
+ *
+ * A pure function of its arrays: it never reads the env state; E and N come from the handle.  All arithmetic is IEEE
+ * binary32: every operation named below is ONE correctly rounded f32 operation, nothing is fused (no fma), nothing is
+ * reassociated, subnormals are kept.
+ *
+ * Inputs (device pointers):
+ *   reward        f64 [K][E][N]   what ccx_rollout_out / ccx_step_out hold
+ *   agent_flags   u8  [K][E][N]   likewise
+ *   env_flags     u8  [K][E]      likewise
+ *   values        f32 [K][E][N]   values[s] = the critic's value of the observation the agent ACTED ON in step s (the state
+ *                                 before step s)
+ *   last_values   f32 [E][N]      value of the state behind step K - 1
+ *   final_values  f32 [K][E][N] or NULL: value of the observation step s ENDED ON, read only at cut steps (below).  NULL: a
+ *                                 cut bootstraps from +0.0, the usual "truncation = termination" shortcut
+ *   gamma, lam    float, by value, each in [0, 1] and not NaN (else CCX_EINVAL); gl = gamma * lam is one f32 multiply on the
+ *                                 host
+ * Outputs: advantages f32 [K][E][N], returns f32 [K][E][N] (every element of both is written), valid u8 [K][E][N] or NULL.
+ *
+ * For every column (e, a) independently, the steps walked BACKWARDS:
+ *     carry = +0.0f
+ *     for s = K-1 .. 0:
+ *         af = agent_flags[s][e][a];  ef = env_flags[s][e]
+ *         if !(af & CCX_AF_LIVE):            (no reward entry exists for this agent-step)
+ *             advantages = returns = +0.0f; valid = 0; carry = +0.0f; continue
+ *         v = values[s][e][a];  r = (float)reward[s][e][a]                    (round to nearest even)
+ *         cut = (af & CCX_AF_TRUNCATED) || (ef & (CCX_EF_ALL_TERMINATED | CCX_EF_ALL_TRUNCATED | CCX_EF_RESET))
+ *         if   af & CCX_AF_TERMINATED:  nv = +0.0f;                                           c = +0.0f
+ *         elif cut:                     nv = final_values ? final_values[s][e][a] : +0.0f;    c = +0.0f
+ *         elif s == K-1:                nv = last_values[e][a];                               c = +0.0f
+ *         else:                         nv = values[s+1][e][a];                               c = carry
+ *         delta = (r + gamma * nv) - v        (mul, add, sub)
+ *         adv   = delta + gl * c              (mul, add: the same two operations in every case)
+ *         advantages[s][e][a] = adv;  returns[s][e][a] = adv + v;  valid = 1;  carry = adv
+ * The pseudo-code is the contract, also for arrays no kernel of this library writes (a live step followed by a step that is
+ * not live with no cut between them reads values[s+1] all the same).  Values at places the rule does not read never reach
+ * a result: they are selected away, never multiplied by zero (a NaN there stays there).
+ *
+ * Termination does not bootstrap.  Truncation, the end of an episode of the whole env and an auto-reset do, from the value of
+ * the rows the step ENDED ON: with CCX_RESET_OBS_NEXT those are the final_obs rows, not the next episode's rows that took
+ * their place in obs -- the caller evaluates the critic on final_obs at the steps with CCX_EF_RESET and hands the result
+ * in as final_values.  Agents of one env finish on different steps (CCX_AF_LIVE drops per agent while the env goes on),
+ * several episodes of one env may start and end inside one array (CCX_EF_RESET), and without auto-reset the `__all__` flags
+ * stay raised step after step: each such step is a cut of its own.
+ * lam = 1 with values = 0 (and last_values = 0, final_values NULL) gives the discounted rewards-to-go of every episode:
+ * adv[s] = r[s] + gamma * adv[s+1] inside an episode.  lam = 0 gives the one-step TD errors: adv[s] = (r + gamma * nv) - v,
+ * plus gl * c = +0.0 * c.
+ *
+ * ccx_gae only enqueues ONE kernel on the handle's stream: no host synchronisation, no allocation, and it captures into a
+ * HIP graph.  A NULL required pointer, num_steps < 1, or gamma / lam outside [0, 1] (NaN included): CCX_EINVAL with a
+ * ccx_last_error message.  Offsets are 64-bit (K E N may exceed 2^31).
+ */
+int ccx_gae(ccx_handle* h, int32_t num_steps, const double* reward /* [K][E][N] */, const uint8_t* agent_flags /* [K][E][N] */,
+            const uint8_t* env_flags /* [K][E] */, const float* values /* [K][E][N] */, const float* last_values /* [E][N] */,
+            const float* final_values_or_null /* [K][E][N] */, float gamma, float lam, float* advantages /* [K][E][N] */,
+            float* returns /* [K][E][N] */, uint8_t* valid_or_null /* [K][E][N] */);
+/*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
  * `rng_seed` of ccx_rollout).  The action of agent slot a of global env g at step t (0-based) of its episode j is
