@@ -633,7 +633,8 @@ int ccx_create(const ccx_params* params, int32_t num_envs, int64_t env_offset, i
         return fail(CCX_EINVAL, "num_envs x agents = %lld exceeds 2^28 (per-lane byte offsets are 32-bit)",
                     (long long)num_envs * (params->num_boarding + params->num_exiting));
     if (total_envs <= 0) total_envs = num_envs;
-    if (env_offset < 0 || env_offset + num_envs > total_envs)
+    // (as a difference: env_offset + num_envs overflows for offsets near INT64_MAX and would let a bad shard through)
+    if (env_offset < 0 || total_envs < num_envs || env_offset > total_envs - num_envs)
         return fail(CCX_EINVAL, "env_offset %lld + num_envs %d exceeds total_envs %lld",
                     (long long)env_offset, num_envs, (long long)total_envs);
     int ndev = 0;

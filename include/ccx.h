@@ -240,6 +240,9 @@ int ccx_get_state_host(ccx_handle* h, ccx_state* dst);
  * Cursor: env e (global index g = env_offset + e) starts episode j from entry (g + j * stride) mod P
  * with stride = total_envs mod P, or 1 when P divides total_envs (so that every env still walks
  * through the pool instead of restarting from one placement forever).
+ * Supported range: 0 <= env_offset, env_offset + num_envs <= total_envs <= INT64_MAX (g and total_envs are taken
+ * as 64-bit integers), P < 2^31, and episode counters 0 <= j <= INT32_MAX (the state keeps j as int32: set
+ * episode counters so that no restart takes one past INT32_MAX; beyond it the entry is undefined).
  */
 int ccx_set_reset_pool(ccx_handle* h, const uint8_t* pool_xy, int64_t pool_size);
 

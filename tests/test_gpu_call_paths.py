@@ -26,11 +26,16 @@ def ccx():
     return BatchedCollectiveCrossing
 
 
-def _new(ccx, cfg, pool, drive, max_launch_steps=0):
-    b = ccx(cfg, E)
+def _new(ccx, cfg, pool, drive, max_launch_steps=0, E=E, env_offset=0, total_envs=None, episode=None, tunables=()):
+    """A batch at the start of a case.  The harness serves other test files too (tests/test_gpu_far_shards.py): a shard of
+    `E` envs at `env_offset` of `total_envs`, start episode counters `episode` (set before the placement, which depends on
+    them), further `tunables` as (name, value) pairs.  The step counters are staggered by GLOBAL env index."""
+    b = ccx(cfg, E, env_offset=env_offset, total_envs=total_envs)
     b.set_reset_pool(pool)
+    if episode is not None:
+        b.set_state(episode=episode)
     b.reset_from_pool()
-    b.set_state(step_count=(np.arange(E) % MAX_STEPS).astype(np.int32))     # restarts on every step of a launch
+    b.set_state(step_count=((env_offset + np.arange(E)) % MAX_STEPS).astype(np.int32))     # restarts on every step of a launch
     b.track_episodes()
     b.set_check_inputs(True)
     if drive == "mixed_unfused":
@@ -40,6 +45,8 @@ def _new(ccx, cfg, pool, drive, max_launch_steps=0):
         b.set_policy_epsilon(0.3)
     if max_launch_steps:
         b.set_tunable("max_launch_steps", max_launch_steps)
+    for name, value in tunables:
+        b.set_tunable(name, value)
     return b
 
 
@@ -51,7 +58,7 @@ def _alloc(b, k):
     return out
 
 
-def _call(b, drive, res, acts_out, masks, acts, orders, s0, s1):
+def _call(b, drive, res, acts_out, masks, acts, orders, s0, s1, policy="greedy"):
     """Steps s0 .. s1 of the case into res[s0:s1].  A slice whose observation rows do not start on 16 bytes (odd E x N, odd
     s0) is refused by the library by design: such a call goes into buffers of its own and is copied into the slice."""
     from collectivecrossing_amd.batched import RolloutResult
@@ -63,9 +70,9 @@ def _call(b, drive, res, acts_out, masks, acts, orders, s0, s1):
     if drive in ("tensor", "order"):
         b.rollout(acts[sl], orders[sl] if drive == "order" else None, **kw)
     elif drive in ("greedy", "mt"):
-        b.rollout_greedy(k, actions_out=acts_out[sl], **kw)
+        b.rollout_greedy(k, actions_out=acts_out[sl], policy=policy, **kw)
     else:
-        b.rollout_mixed(acts[sl], "exiting", actions_out=acts_out[sl], **kw)
+        b.rollout_mixed(acts[sl], "exiting", policy, actions_out=acts_out[sl], **kw)
     if out is not dst:
         for f in FIELDS:
             getattr(dst, f).copy_(getattr(out, f))
