@@ -11,7 +11,7 @@ from .configs import CollectiveCrossingConfig  # noqa: F401
 
 __version__ = "0.4.0"
 __all__ = ["CollectiveCrossingConfig", "CollectiveCrossingEnv", "BatchedCollectiveCrossing", "VectorCollectiveCrossing",
-           "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult"]
+           "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult", "SampleResult"]
 
 
 def __getattr__(name):  # lazy: importing the configs must not pull in torch
@@ -33,6 +33,9 @@ def __getattr__(name):  # lazy: importing the configs must not pull in torch
     if name == "GaeResult":
         from .batched import GaeResult
         return GaeResult
+    if name == "SampleResult":
+        from .batched import SampleResult
+        return SampleResult
     raise AttributeError(name)
 
 

@@ -102,6 +102,16 @@ class GaeResult:
     valid: torch.Tensor | None  # u8 [K, E, N]: 1 where the agent was live in the step (a loss averages over these)
 
 
+@dataclass
+class SampleResult:
+    """Actions sampled from a policy's logits (:meth:`BatchedCollectiveCrossing.sample_actions`, include/ccx.h CCX_SAMPLE).
+    Every element is written: 255 / +0.0 / +0.0 for agents that are terminated or truncated."""
+
+    actions: torch.Tensor         # u8 [E, N]: what step / rollout consume
+    logp: torch.Tensor | None     # f32 [E, N]: log pi(action | state) under the masked distribution
+    entropy: torch.Tensor | None  # f32 [E, N]: entropy of the masked distribution
+
+
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
     return C.c_void_p(None if t is None else t.data_ptr())
 
@@ -692,6 +702,49 @@ class BatchedCollectiveCrossing:
                                          out.advantages, out.returns, out.valid)
         check(self._lib.ccx_gae(self._h, K, _ptr(reward), _ptr(agent_flags), _ptr(env_flags), _ptr(values), _ptr(last_values),
                                 _ptr(final_values), gamma, lam, _ptr(out.advantages), _ptr(out.returns), _ptr(out.valid)))
+        return out
+
+    # ------------------------------------------------------------------ sampling from a learned policy
+    def alloc_sample(self, want_logp: bool = True, want_entropy: bool = False) -> SampleResult:
+        """Output tensors of :meth:`sample_actions` (static buffers for a captured graph)."""
+        shape = (self.num_envs, self.num_agents)
+        return SampleResult(self._new(shape, torch.uint8), self._new(shape, torch.float32) if want_logp else None,
+                            self._new(shape, torch.float32) if want_entropy else None)
+
+    def sample_actions(self, logits: torch.Tensor, masks: torch.Tensor | None = None, deterministic: bool = False,
+                       want_logp: bool = True, want_entropy: bool = False, out: SampleResult | None = None) -> SampleResult:
+        """Masked categorical actions from a network's logits on the device (``ccx_sample_actions``, include/ccx.h
+        CCX_SAMPLE): one kernel on the handle's stream, bit-defined, drawn with the library's counter-based key (global env,
+        episode, step of the episode, agent slot; :meth:`set_rng_seed`) -- the same actions for any split into calls, any
+        world size, eager or captured.
+
+        ``logits`` f32 [E, N, 5] (index = action id); ``masks`` u8 [E, N] (``action_masks`` / ``masks_out``; ``None`` =
+        everything legal); ``deterministic`` takes the masked argmax (lowest index on ties) and draws nothing.  ``logp`` is
+        ``log pi(action)`` under the masked distribution, ``entropy`` that distribution's entropy.  Agents that are
+        terminated or truncated get action 255, ``logp`` = ``entropy`` = 0.  ``out`` reuses a :class:`SampleResult` (its
+        ``logp`` / ``entropy`` may be ``None``; ``want_*`` is then ignored): ``out.actions`` may be a ``[E, N]`` view of the
+        ``[1, E, N]`` tensor :meth:`rollout` reads.  All tensors: contiguous, on the batch's device; anything else raises
+        ``ValueError`` before the library is called.  Not here: bf16 / f16 logits (cast first), a temperature (scale the
+        logits first).  Only enqueues."""
+        E, N = self.num_envs, self.num_agents
+        if out is None:
+            out = self.alloc_sample(want_logp, want_entropy)
+        elif not isinstance(out, SampleResult):
+            raise ValueError("out must be a SampleResult (alloc_sample)")
+        for name, t, dt, shape, optional in (
+                ("logits", logits, torch.float32, (E, N, 5), False), ("masks", masks, torch.uint8, (E, N), True),
+                ("out.actions", out.actions, torch.uint8, (E, N), False), ("out.logp", out.logp, torch.float32, (E, N), True),
+                ("out.entropy", out.entropy, torch.float32, (E, N), True)):
+            if t is None and optional:
+                continue
+            if (not isinstance(t, torch.Tensor) or t.dtype is not dt or t.device != self.device or tuple(t.shape) != shape
+                    or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
+        if logits.data_ptr() % 16:
+            raise ValueError("logits must be 16-byte aligned (a view at an odd offset of its storage is not)")
+        self._order_after_current_stream(logits, masks, out.actions, out.logp, out.entropy)
+        check(self._lib.ccx_sample_actions(self._h, _ptr(logits), _ptr(masks), int(bool(deterministic)), _ptr(out.actions),
+                                           _ptr(out.logp), _ptr(out.entropy)))
         return out
 
     # ------------------------------------------------------------------ compute

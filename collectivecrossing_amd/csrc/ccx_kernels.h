@@ -33,6 +33,9 @@ __host__ __device__ inline uint32_t random_action(uint32_t seed_lo, uint32_t see
 // and the exploring action is the k-th (ascending) of the valid actions -- the free directions plus wait --
 // with k = mix32(u + 0x9E3779B9) * count >> 32.
 enum : uint32_t { kEpsStream = 0x5BD1E995u };
+// CCX_SAMPLE (include/ccx.h, ccx_sample.hip): the draw of a learned policy's action comes from the same word with
+// seed_hi ^ kSampleStream -- a third stream beside CCX_POLICY_RANDOM's (0) and the epsilon draws'.
+enum : uint32_t { kSampleStream = 0x2545F491u };
 __host__ __device__ inline uint32_t explore_action(uint32_t u, uint32_t free_dirs) {
     uint32_t vm = (free_dirs & 0xFu) | 0x10u;          // wait is always valid (greedy_policy.py:251)
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -586,6 +586,64 @@ int ccx_gae(ccx_handle* h, int32_t num_steps, const double* reward /* [K][E][N] 
             const float* final_values_or_null /* [K][E][N] */, float gamma, float lam, float* advantages /* [K][E][N] */,
             float* returns /* [K][E][N] */, uint8_t* valid_or_null /* [K][E][N] */);
 /*
+ * CCX_SAMPLE: from a network's logits to the action tensor ccx_step consumes -- masked categorical sampling on the device,
+ * with the log-probability a policy-gradient update needs later and the entropy of the masked distribution.  The draw is
+ * the library's own counter-based word (ccx_set_rng_seed below), keyed by (global env, episode, step of the episode, agent
+ * slot): the same actions for any split of a run into calls, any world size, eager or captured.  Every output is
+ * bit-defined.
+ *
+ * Inputs (device pointers): logits f32 [E][N][5] (index = action id; 16-byte aligned), masks u8 [E][N] or NULL (the bytes of
+ * CCX_ACTION_MASKS; NULL = everything legal), deterministic (0 = sample, otherwise the masked argmax).  Outputs: actions u8
+ * [E][N], logp f32 [E][N] or NULL, entropy f32 [E][N] or NULL; every element of every output given is written.  The call
+ * reads the handle's terminated, truncated, step_count and episode arrays and the seed of ccx_set_rng_seed; it writes
+ * nothing but its outputs.
+ *
+ * All arithmetic is IEEE binary32: every operation named below is ONE correctly rounded f32 operation (+ - * /), nothing is
+ * fused (no fma), nothing is reassociated, subnormals are kept.  For every slot (e, a) on its own, with g = env_offset + e,
+ * j = episode[e], t = step_count[e], l_k = logits[e][a][k]:
+ *   1. dead slot (terminated[e][a] or truncated[e][a]): actions = CCX_ACTION_ABSENT, logp = +0.0f, entropy = +0.0f; its
+ *      logits and its mask byte are not read into any result.
+ *   2. m = ((masks ? masks[e][a] : 0x1F) & 0x1F) | 0x10: action k is legal iff bit k of m is set; wait always is.  A logit
+ *      at an illegal k is selected away, never multiplied by zero (a NaN there stays there).
+ *   3. mx = -inf; for legal k ascending: if (l_k > mx) mx = l_k.
+ *   4. the slot is degenerate if a legal l_k is NaN or +inf, or mx == -inf.  Then d_k = +0.0f for every legal k (uniform
+ *      over the legal set).  Otherwise d_k = l_k - mx (a legal -inf gives d_k = -inf and is fine).
+ *   5. w_k = (d_k < D_MIN) ? +0.0f : exp_spec(d_k) for legal k, +0.0f for illegal k.  D_MIN = -80.0f: every nonzero weight
+ *      is a normal number, and the weight of the maximum is exactly 1.
+ *   6. c_0 = w_0, c_k = c_(k-1) + w_k, S = c_4 (1 <= S <= 5).
+ *   7. u = word(seed_lo, seed_hi ^ 0x2545F491; g, j, t, a): the k of ccx_set_rng_seed's formula before "* 5", with g, j, t
+ *      reduced to u32.  r = (float)(u >> 8) * 0x1p-24f (exact, in [0, 1)); thr = r * S.
+ *   8. action = the lowest legal k with c_k > thr (none: k = 4; a k with w_k = 0 is never chosen).  deterministic: the
+ *      lowest legal k with l_k == mx, in a degenerate slot the lowest legal k; no draw is made.
+ *   9. logp = d_action - log_spec(S).
+ *  10. entropy = log_spec(S) - T / S, T = (((t_0 + t_1) + t_2) + t_3) + t_4 with t_k = (w_k == 0) ? +0.0f : w_k * d_k.
+ *
+ * exp_spec(x), x in [-80, 0]:
+ *     n = rint(x * 0x1.715476p+0f)                              (round to nearest even)
+ *     r = (x - n * 0x1.62e4p-1f) - n * 0x1.7f7d1cp-20f           (the first product is exact)
+ *     p = 0x1.a01a02p-13f;  then p = p * r + C, one multiply and one add each, for C = 0x1.6c16c2p-10f, 0x1.111112p-7f,
+ *         0x1.555556p-5f, 0x1.555556p-3f, 0x1p-1f, 0x1p+0f, 0x1p+0f                 (1/7! .. 1/2!, 1, 1)
+ *     exp_spec = p * 2^n                                         (exact; n >= -116)
+ * log_spec(s), s in [1, 5]:
+ *     s = m * 2^e with m in [0.5, 1) (exact); if (m < 0x1.6a09e6p-1f) { m = m + m; e = e - 1; }
+ *     t = m - 0x1p+0f;  q = t / (0x1p+1f + t);  z = q * q
+ *     p = 0x1.c71c72p-4f;  then p = p * z + C for C = 0x1.24924ap-3f, 0x1.99999ap-3f, 0x1.555556p-2f        (1/9 .. 1/3)
+ *     u = q + q;  lf = u + u * (z * p)
+ *     log_spec = (float)e * 0x1.62e4p-1f + (lf + (float)e * 0x1.7f7d1cp-20f)
+ * exp_spec(+0.0f) == 1.0f and log_spec(1.0f) == +0.0f exactly: a slot with one legal action has logp = entropy = +0.0f.
+ * Against IEEE f64 (measured on the CPU, tests/test_sample_spec.py, maxima doubled): exp_spec within 2.0e-7 relative on
+ * [-80, 0]; logp within 9.2e-7 and entropy within 4.3e-7 absolute of the f64 masked log-softmax and entropy of the same
+ * f32 logits, over the adversarial generator's slots that are not degenerate.
+ *
+ * ccx_sample_actions only enqueues ONE kernel on the handle's stream: no host synchronisation, no allocation, and it
+ * captures into a HIP graph next to ccx_step.  A NULL handle, NULL logits or NULL actions, or logits that are not 16-byte
+ * aligned: CCX_EINVAL with a ccx_last_error message.  Not here: bf16 / f16 logits (cast first), a temperature (scale the
+ * logits first).
+ */
+int ccx_sample_actions(ccx_handle* h, const float* logits /* [E][N][5] */, const uint8_t* masks_or_null /* [E][N] */,
+                       int32_t deterministic, uint8_t* actions /* [E][N] */, float* logp_or_null /* [E][N] */,
+                       float* entropy_or_null /* [E][N] */);
+/*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
  * `rng_seed` of ccx_rollout).  The action of agent slot a of global env g at step t (0-based) of its episode j is
