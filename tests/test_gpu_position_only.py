@@ -100,7 +100,13 @@ def test_large_batches_equal_the_oracle_with_the_same_tables(oracle, ccx, name, 
     res = env.rollout(actions[:5], auto_reset=True)
     o_obs, o_rew, o_af, o_ef = ob.rollout(actions[:5], auto_reset=True)
     np.testing.assert_array_equal(_np(res.agent_flags), o_af)
+    np.testing.assert_array_equal(_np(res.env_flags), o_ef)
     np.testing.assert_array_equal(_np(res.reward).view(np.uint64), o_rew.view(np.uint64))
+    np.testing.assert_array_equal(_np(res.obs).view(np.uint32), o_obs.view(np.uint32))
+    st = env.get_state()
+    for k in ("x", "y", "active", "terminated", "truncated", "step_count", "episode"):
+        np.testing.assert_array_equal(st[k], getattr(ob, k), err_msg=f"built-in strategies: {k}")
+    assert env.counters() == ob.counters.as_dict()
     env.close()
 
 
