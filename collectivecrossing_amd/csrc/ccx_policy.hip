@@ -18,42 +18,38 @@
 
 namespace ccx {
 
+// Which of the four neighbour cells of agent i of the env whose agents start at `base` hold another ACTIVE agent
+// (whatever its terminated / truncated flags: env._is_move_valid -> _is_position_occupied, collectivecrossing.py:345-369,
+// :536-541), bits 0-3 = right, up, left, down: ONE pass over the env's agents, an agent one cell away takes the direction
+// that leads to it.  (The thread-per-agent form of ccx_rollout_dev.h: neighbours_busy.)
+__device__ __forceinline__ uint32_t neighbours_busy_scan(const KParams& p, const KState& st, const size_t base, const int i) {
+    const int cx = st.x[base + i], cy = st.y[base + i];
+    uint32_t busy = 0u;
+    for (int b = 0; b < p.N; ++b) {
+        const int dx = st.x[base + b] - cx, dy = st.y[base + b] - cy;
+        const uint32_t hit = (dx == 1 && dy == 0 ? 1u : 0u) | (dx == 0 && dy == 1 ? 2u : 0u) |
+                             (dx == -1 && dy == 0 ? 4u : 0u) | (dx == 0 && dy == -1 ? 8u : 0u);
+        busy |= (b != i && st.active[base + b]) ? hit : 0u;
+    }
+    return busy;
+}
+
 // The scripted policy's own choice for live agent i of env `env` (epsilon aside) and, in free_dirs, the directions it
-// could move in: the neighbour bit of its cell and no other ACTIVE agent on the target (env._is_move_valid,
-// collectivecrossing.py:345-369) -- what both the policy's fallback list and an epsilon draw choose from.
+// could move in: the neighbour bit of its cell and no other ACTIVE agent on the target -- what both the policy's
+// fallback list and an epsilon draw choose from.
 __device__ __forceinline__ uint32_t scripted_choice(const KParams& p, const KState& st,
                                                     const unsigned long long* __restrict__ cell_info, const int env,
                                                     const int i, const int policy, uint32_t& free_dirs) {
     const size_t base = (size_t)env * p.N, t = base + (size_t)i;
     const int cx = st.x[t], cy = st.y[t];
-    const int Wp = p.W + 3;
-    const uint32_t cw = (uint32_t)cell_info[(cy + 1) * Wp + cx + 1];
-    const uint32_t nv = cw & 0xFu;   // enterable neighbours
-    const uint32_t cand = greedy_candidates(p, i < p.Nb, cx, cy);
+    const uint32_t cw = (uint32_t)cell_info[(cy + 1) * (p.W + 3) + cx + 1];
+    free_dirs = cw & 0xFu & ~neighbours_busy_scan(p, st, base, i);
     bool waits = false;
     if (policy == CCX_K_POLICY_WAITING && i < p.Nb && !(cw & kCellInTram)) {   // waiting_policy.py:92-100
         for (int b = p.Nb; b < p.N; ++b)                                  // :119-129
             waits |= !(st.terminated[base + b] || st.truncated[base + b]) && st.y[base + b] != p.edy;
     }
-    free_dirs = 0u;
-    for (uint32_t a = 0; a < 4u; ++a) {
-        if (!((nv >> a) & 1u)) continue;
-        const int nx = cx + (a == 0u) - (a == 2u), ny = cy + (a == 1u) - (a == 3u);
-        bool taken = false;
-        for (int b = 0; b < p.N; ++b)
-            taken |= (b != i) && st.active[base + b] && st.x[base + b] == nx && st.y[base + b] == ny;
-        if (!taken) free_dirs |= 1u << a;
-    }
-    uint32_t chosen = 4u;
-    for (int k = 0; k < 6 && !waits; ++k) {   // candidate 0 = primary, 1..4 preference list, 5 = wait
-        const uint32_t a = k < 5 ? ((cand >> (4 * k)) & 0xFu) : 4u;
-        if (a == 4u) break;
-        if ((free_dirs >> a) & 1u) {
-            chosen = a;
-            break;
-        }
-    }
-    return chosen;
+    return waits ? 4u : greedy_pick(greedy_candidates(p, i < p.Nb, cx, cy), free_dirs);
 }
 
 // policy: CCX_K_POLICY_GREEDY, or CCX_K_POLICY_WAITING = WaitingPolicy(epsilon = 0)
@@ -202,9 +198,8 @@ hipError_t launch_policy_stream_actions(hipStream_t stream, const KParams& p, co
 // Legal-action masks of the current state (include/ccx.h: CCX_ACTION_MASKS), one thread per (env, agent): what the
 // reference's policies ask per agent and action (greedy_policy.py:238-264 _is_valid_action -> env._is_move_valid,
 // collectivecrossing.py:345-369; the epsilon branch enumerates the same set, greedy_policy.py:51-57).  Walls, the door
-// row and the grid's edge are the four neighbour bits of the agent's cell word; occupancy is ONE pass over the env's
-// agents -- an ACTIVE agent (whatever its terminated / truncated flags: _is_position_occupied) one cell away takes the
-// direction that leads to it.  Works from global memory alone, so any legal grid is served (100 x 100 included).
+// row and the grid's edge are the four neighbour bits of the agent's cell word; occupancy is neighbours_busy_scan.
+// Works from global memory alone, so any legal grid is served (100 x 100 included).
 // ---------------------------------------------------------------------------------------------
 __global__ void action_masks_kernel(const KParams p, const KState st, const unsigned long long* __restrict__ cell_info,
                                     uint8_t* __restrict__ masks) {
@@ -213,17 +208,9 @@ __global__ void action_masks_kernel(const KParams p, const KState st, const unsi
     if (t >= total) return;
     uint32_t m = 0x10u;                                   // wait is always legal (greedy_policy.py:253)
     if (!(st.terminated[t] || st.truncated[t])) {         // done agents are not in env.agents: wait only
-        const int env = (int)(t / p.N), i = (int)(t % p.N);
-        const size_t base = (size_t)env * p.N;
-        const int cx = st.x[t], cy = st.y[t];
-        uint32_t busy = 0u;
-        for (int b = 0; b < p.N; ++b) {
-            const int dx = st.x[base + b] - cx, dy = st.y[base + b] - cy;
-            const uint32_t hit = (dx == 1 && dy == 0 ? 1u : 0u) | (dx == 0 && dy == 1 ? 2u : 0u) |
-                                 (dx == -1 && dy == 0 ? 4u : 0u) | (dx == 0 && dy == -1 ? 8u : 0u);
-            busy |= (b != i && st.active[base + b]) ? hit : 0u;
-        }
-        m |= (uint32_t)cell_info[(cy + 1) * (p.W + 3) + cx + 1] & 0xFu & ~busy;
+        const int i = (int)(t % p.N);
+        const uint32_t busy = neighbours_busy_scan(p, st, t - (size_t)i, i);
+        m |= (uint32_t)cell_info[(st.y[t] + 1) * (p.W + 3) + st.x[t] + 1] & 0xFu & ~busy;
     }
     masks[t] = (uint8_t)m;
 }

@@ -648,7 +648,6 @@
         __hip_atomic_fetch_or((__attribute__((address_space(3))) mask_t*)(uintptr_t)addr, bits, __ATOMIC_RELAXED,
                               __HIP_MEMORY_SCOPE_WAVEFRONT);
     };
-    auto lds_mask_ld = [](uint32_t addr) { return *(__attribute__((address_space(3))) const mask_t*)(uintptr_t)addr; };
     auto lds_mask_st = [](uint32_t addr, mask_t v) { *(__attribute__((address_space(3))) mask_t*)(uintptr_t)addr = v; };
     auto lds_cell = [](int addr) { return *(__attribute__((address_space(3))) const unsigned long long*)(uintptr_t)(uint32_t)addr; };
 
@@ -704,7 +703,7 @@
     // (kernel arguments the step loop needs are read HERE, once: a scalar load inside the loop shares the LDS wait counter)
     const uint32_t rng_lo = p.rng_lo, rng_hi = p.rng_hi, eps_thr = p.eps_thr, genv = (uint32_t)(p.env_offset + env);
     const int max_steps_m1 = p.max_steps - 1;
-    struct { int div, dc, bdy, edy; } const geo = {p.div, p.dc, p.bdy, p.edy};   // what greedy_candidates reads
+    const GreedyGeo geo{p.div, p.dc, p.bdy, p.edy};
     const bool has_order = PLAIN ? false : KA.order != nullptr;   // wave-uniform
     const uint8_t* ord_p = KA.order + idx;
 
@@ -915,10 +914,7 @@
                 if constexpr (OCC) {
                     lds_or(ca, mybit);
                     wave_lds_sync();
-                    const uint32_t cb = tab_rel + ((uint32_t)c8 << TS);
-                    const uint32_t rowb = (uint32_t)(Wp * 8) << TS, colb = 8u << TS;
-                    busy = (lds_mask_ld(cb + colb) != 0 ? 1u : 0u) | (lds_mask_ld(cb + rowb) != 0 ? 2u : 0u) |
-                           (lds_mask_ld(cb - colb) != 0 ? 4u : 0u) | (lds_mask_ld(cb - rowb) != 0 ? 8u : 0u);
+                    busy = neighbours_busy<mask_t, TS>(tab_rel + ((uint32_t)c8 << TS), Wp);
                     wave_lds_sync();
                 } else {
                     // grids whose occupancy tables exceed the LDS (round 4: policy rollouts no longer need them): every agent

@@ -74,16 +74,35 @@ template <int GLOG> __device__ __forceinline__ constexpr typename GroupMask<GLOG
     else return (T(1) << (1 << GLOG)) - T(1);
 }
 
+template <typename M> __device__ __forceinline__ M lds_mask_ld(uint32_t addr) {   // a mask word of an LDS occupancy table
+    return *(__attribute__((address_space(3))) const M*)(uintptr_t)addr;
+}
+
+// Which of an agent's four neighbour cells hold another ACTIVE agent (env._is_move_valid -> _is_position_occupied,
+// collectivecrossing.py:345-369, :536-541), from the env's occupancy table in LDS: `cb` is the table entry of the agent's
+// own cell, M the mask type of the lane group, TS = 1 for 16-byte entries (64-bit masks).  Bits 0-3 = right, up, left,
+// down.  The active agents' bits must be in the table (the caller publishes them, and places the wave_lds_sync()s).
+template <typename M, uint32_t TS>
+__device__ __forceinline__ uint32_t neighbours_busy(uint32_t cb, int Wp) {
+    const uint32_t rowb = (uint32_t)(Wp * 8) << TS, colb = 8u << TS;
+    const M o0 = lds_mask_ld<M>(cb + colb), o1 = lds_mask_ld<M>(cb + rowb), o2 = lds_mask_ld<M>(cb - colb),
+            o3 = lds_mask_ld<M>(cb - rowb);
+    return (o0 != 0 ? 1u : 0u) | (o1 != 0 ? 2u : 0u) | (o2 != 0 ? 4u : 0u) | (o3 != 0 ? 8u : 0u);
+}
+
+// what greedy_candidates reads of the geometry (ccx_greedy.h)
+struct GreedyGeo { int div, dc, bdy, edy; };
+
 // The scripted policies' choice for this lane's agent from the PRE-step state in registers (greedy_policy.py:33-449,
 // waiting_policy.py:74-131; ccx_policy.hip is the same rule with one thread per agent).  `ilo` is the low word of the
 // agent's cell, `busy` the directions whose neighbour cell holds another ACTIVE agent, `asked` whether the agent is in
 // env.agents; `step` the episode's step index BEFORE this step.  Called by every lane of the wave (the waiting rule is a
 // ballot over the env's lane group); policy and eps_thr are wave-uniform.
-// (The rollout kernel's step 0 in ccx_rollout_body.inc states the same lines inline: moving it onto this helper changes the
-// register allocation of its policy instantiations, whose budgets tests/test_kernel_resources.py pins, so that belongs
-// to a change that can time them.)
-template <int GLOG, typename Geo>
-__device__ __forceinline__ uint32_t scripted_pick(const Geo& geo, int policy, bool boarding, uint32_t ilo, uint32_t asked,
+// (The rollout kernel's step 0 in ccx_rollout_body.inc still states these lines inline: called from there, this helper took
+// v128<6,1,1,1,0> -- C5's greedy rollout -- from 87 to 88 VGPRs and most other policy instantiations up by 1-3, and the
+// all-pairs 32-lane ones from 24 to 28 bytes of scratch)
+template <int GLOG>
+__device__ __forceinline__ uint32_t scripted_pick(const GreedyGeo& geo, int policy, bool boarding, uint32_t ilo, uint32_t asked,
                                                   uint32_t busy, int lane, uint32_t eps_thr, uint32_t rng_lo, uint32_t rng_hi,
                                                   uint32_t genv, uint32_t episode, uint32_t step, uint32_t slot) {
     const uint32_t free4 = ilo & 0xFu & ~busy;

@@ -74,9 +74,6 @@ __device__ __forceinline__ void step_store_obs(v2f v, const char* base, uint32_t
     asm volatile("global_store_dwordx2 %0, %1, %2 " CCX_STEP_STORE_BITS ::"v"(voff), "v"(v), "s"(base) : "memory");
 }
 
-// what greedy_candidates reads of the geometry (ccx_greedy.h)
-struct GreedyGeo { int div, dc, bdy, edy; };
-
 // store iterations of a row wave whose table words / LDS reads are in flight together: 8 for small lane groups (C2: a row
 // wave has ~5 iterations), 16 for the large ones (C3 / C5: 10-11 iterations per row wave, one batch instead of two -- the
 // second batch's table words would be a memory round trip of their own)
@@ -272,49 +269,35 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
     const uint32_t s_trunc = (st_base + sl.truncated)[idx_ld];
     const int s_stepc = reinterpret_cast<const int32_t*>(st_base + sl.step_count)[env_ld];
     const int s_episode = reinterpret_cast<const int32_t*>(st_base + sl.episode)[env_ld];
+    // A burst of loads from a u8 [K][E][N] stream (actions, move order): this lane's byte of every step of the launch, all in
+    // flight together -- stride EN, offsets clamped to the last step (K < kActBatch reads that byte again instead of running
+    // past the tensor); K1: ONE load.  (A macro: handed to a function, the destination array stops being a plain local of
+    // the kernel early enough, and the instantiations with K > 1 come out with another schedule.)
+    constexpr int kBurst = K1 ? 1 : kActBatch;
+#define CCX_BURST_LD(dst, ptr)                                      \
+    do {                                                            \
+        uint32_t off_ = idx_ld;                                     \
+        const uint32_t lim_ = idx_ld + (uint32_t)(K - 1) * EN;      \
+        if constexpr (K1) (dst)[0] = (uint32_t)(ptr)[off_];         \
+        else _Pragma("unroll") for (int d_ = 0; d_ < kBurst; ++d_) { \
+            (dst)[d_] = (uint32_t)(ptr)[off_];                      \
+            const uint32_t nx_ = off_ + EN;                         \
+            off_ = nx_ < lim_ ? nx_ : lim_;                         \
+        }                                                           \
+    } while (0)
     uint32_t araw[kActBatch];
-    if constexpr (POL) {
-        // (a mask that covers every slot comes without a tensor: nothing is loaded, the bytes are never looked at)
 #pragma unroll
-        for (int d = 0; d < kActBatch; ++d) araw[d] = 4u;
-        if (actions != nullptr) {
-            uint32_t off = idx_ld;
-            const uint32_t lim = idx_ld + (uint32_t)(K - 1) * EN;
-#pragma unroll
-            for (int d = 0; d < (K1 ? 1 : kActBatch); ++d) {
-                araw[d] = (uint32_t)actions[off];
-                const uint32_t nx = off + EN;
-                off = nx < lim ? nx : lim;
-            }
-        }
-    } else if constexpr (K1) {
-        araw[0] = (uint32_t)actions[idx_ld];
-#pragma unroll
-        for (int d = 1; d < kActBatch; ++d) araw[d] = 4u;
-    } else {
-        uint32_t off = idx_ld;
-        const uint32_t lim = idx_ld + (uint32_t)(K - 1) * EN;
-#pragma unroll
-        for (int d = 0; d < kActBatch; ++d) {
-            araw[d] = (uint32_t)actions[off];
-            const uint32_t nx = off + EN;
-            off = nx < lim ? nx : lim;
-        }
-    }
+    for (int d = POL ? 0 : kBurst; d < kActBatch; ++d) araw[d] = 4u;
+    // (POL: a mask that covers every slot comes without a tensor: nothing is loaded, the bytes are never looked at)
+    if (!POL || actions != nullptr) CCX_BURST_LD(araw, actions);
     // move order: one byte per step and lane, packed 8 bits per step like the actions (16 steps = two 64-bit words)
     unsigned long long ord_lo = 0, ord_hi = 0;
     if constexpr (ORD) {
         uint32_t oraw[kActBatch];
-        uint32_t off = idx_ld;
-        const uint32_t lim = idx_ld + (uint32_t)(K - 1) * EN;
+        CCX_BURST_LD(oraw, order);
+#undef CCX_BURST_LD
 #pragma unroll
-        for (int d = 0; d < (K1 ? 1 : kActBatch); ++d) {
-            oraw[d] = (uint32_t)order[off];
-            const uint32_t nx = off + EN;
-            off = nx < lim ? nx : lim;
-        }
-#pragma unroll
-        for (int d = 0; d < (K1 ? 1 : kActBatch); ++d) {
+        for (int d = 0; d < kBurst; ++d) {
             if (d < 8) ord_lo |= (unsigned long long)(oraw[d] & 0xFFu) << (8 * d);
             else ord_hi |= (unsigned long long)(oraw[d] & 0xFFu) << (8 * (d - 8));
         }
@@ -442,7 +425,7 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
     if constexpr (POL) {
         // the caller's bytes as they are, 8 bits per step (acur: steps 0-7, araw_hi: 8-15): actions_out hands them back
 #pragma unroll
-        for (int d = 0; d < (K1 ? 1 : kActBatch); ++d) {
+        for (int d = 0; d < kBurst; ++d) {
             if (d < 8) acur |= (unsigned long long)(araw[d] & 0xFFu) << (8 * d);
             else araw_hi |= (unsigned long long)(araw[d] & 0xFFu) << (8 * (d - 8));
         }
@@ -503,13 +486,14 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
             //         occupancy bits go into the table first -- the move resolution below needs them there anyway -- and a
             //         direction is free if the cell's word says the neighbour can be entered and no active agent's bit sits
             //         on it (env._is_move_valid, collectivecrossing.py:345-369)
-            auto lds_mask_ld = [](uint32_t addr) -> mask_t { return *(__attribute__((address_space(3))) const mask_t*)(uintptr_t)addr; };
             lds_or(ca, my_rbit);
             wave_lds_sync();
+            // (neighbours_busy's four reads, spelled out: with the nibble built in FRONT of the sync, as the helper has it, the
+            //  GLOG 0 instantiations with K > 1 spill one more SGPR)
             const uint32_t cb = tab_rel + ((uint32_t)c8 << TS);
             const uint32_t rowb = (uint32_t)(Wp * 8) << TS, colb = 8u << TS;
-            const mask_t o0 = lds_mask_ld(cb + colb), o1 = lds_mask_ld(cb + rowb), o2 = lds_mask_ld(cb - colb),
-                         o3 = lds_mask_ld(cb - rowb);
+            const mask_t o0 = lds_mask_ld<mask_t>(cb + colb), o1 = lds_mask_ld<mask_t>(cb + rowb),
+                         o2 = lds_mask_ld<mask_t>(cb - colb), o3 = lds_mask_ld<mask_t>(cb - rowb);
             wave_lds_sync();
             const uint32_t busy = (o0 != 0 ? 1u : 0u) | (o1 != 0 ? 2u : 0u) | (o2 != 0 ? 4u : 0u) | (o3 != 0 ? 8u : 0u);
             const uint32_t asked = tt == 0u ? 1u : 0u;                 // the policy is asked for env.agents only
@@ -687,14 +671,9 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
     //      (POL, step 0).  The wave ends here: nothing is cleared.
     uint32_t mask_byte = 0x10u;                                        // wait is always legal (greedy_policy.py:253)
     if constexpr (MSK) {
-        auto lds_mask_ld = [](uint32_t addr) -> mask_t { return *(__attribute__((address_space(3))) const mask_t*)(uintptr_t)addr; };
         lds_or(act ? tab_rel + ((uint32_t)c8 << TS) : dump_addr, mybit);
         wave_lds_sync();
-        const uint32_t cb = tab_rel + ((uint32_t)c8 << TS);
-        const uint32_t rowb = (uint32_t)(Wp * 8) << TS, colb = 8u << TS;
-        const mask_t o0 = lds_mask_ld(cb + colb), o1 = lds_mask_ld(cb + rowb), o2 = lds_mask_ld(cb - colb),
-                     o3 = lds_mask_ld(cb - rowb);
-        const uint32_t busy = (o0 != 0 ? 1u : 0u) | (o1 != 0 ? 2u : 0u) | (o2 != 0 ? 4u : 0u) | (o3 != 0 ? 8u : 0u);
+        const uint32_t busy = neighbours_busy<mask_t, TS>(tab_rel + ((uint32_t)c8 << TS), Wp);
         mask_byte |= tt == 0u ? (ilo & 0xFu & ~busy) : 0u;             // done agents: wait only
     }
     // ---- registers -> state --------------------------------------------------------------------------------------
