@@ -11,7 +11,7 @@ from .configs import CollectiveCrossingConfig  # noqa: F401
 
 __version__ = "0.4.0"
 __all__ = ["CollectiveCrossingConfig", "CollectiveCrossingEnv", "BatchedCollectiveCrossing", "VectorCollectiveCrossing",
-           "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult", "SampleResult"]
+           "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult", "SampleResult", "EvalResult"]
 
 
 def __getattr__(name):  # lazy: importing the configs must not pull in torch
@@ -36,6 +36,9 @@ def __getattr__(name):  # lazy: importing the configs must not pull in torch
     if name == "SampleResult":
         from .batched import SampleResult
         return SampleResult
+    if name == "EvalResult":
+        from .batched import EvalResult
+        return EvalResult
     raise AttributeError(name)
 
 

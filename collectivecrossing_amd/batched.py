@@ -112,6 +112,15 @@ class SampleResult:
     entropy: torch.Tensor | None  # f32 [E, N]: entropy of the masked distribution
 
 
+@dataclass
+class EvalResult:
+    """Stored actions evaluated under new logits (:meth:`BatchedCollectiveCrossing.evaluate_actions`, include/ccx.h
+    CCX_EVALUATE).  Every element is written: +0.0 / +0.0 for rows whose stored action is 255."""
+
+    logp: torch.Tensor            # f32 [...]: log pi_new(stored action | state) under the masked distribution; -inf: not a legal action
+    entropy: torch.Tensor | None  # f32 [...]: entropy of the masked distribution
+
+
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
     return C.c_void_p(None if t is None else t.data_ptr())
 
@@ -745,6 +754,103 @@ class BatchedCollectiveCrossing:
         self._order_after_current_stream(logits, masks, out.actions, out.logp, out.entropy)
         check(self._lib.ccx_sample_actions(self._h, _ptr(logits), _ptr(masks), int(bool(deterministic)), _ptr(out.actions),
                                            _ptr(out.logp), _ptr(out.entropy)))
+        return out
+
+    # ------------------------------------------------------------------ stored actions under new logits
+    def alloc_evaluate(self, shape, want_entropy: bool = True) -> EvalResult:
+        """Output tensors of :meth:`evaluate_actions` for rows of the leading shape ``shape`` (static buffers for a
+        captured graph)."""
+        shape = tuple(int(x) for x in shape)
+        return EvalResult(self._new(shape, torch.float32), self._new(shape, torch.float32) if want_entropy else None)
+
+    def _check_evaluate(self, logits, actions, masks, extra=()):
+        """The input checks :meth:`evaluate_actions` and :meth:`evaluate_actions_backward` share; returns the leading shape."""
+        if (not isinstance(logits, torch.Tensor) or logits.dtype is not torch.float32 or logits.device != self.device
+                or logits.dim() < 1 or logits.shape[-1] != 5 or not logits.is_contiguous()):
+            raise ValueError(f"logits must be a contiguous torch.float32 tensor of shape [..., 5] on {self.device}")
+        lead = tuple(logits.shape[:-1])
+        for name, t, dt, shape, optional in (("actions", actions, torch.uint8, lead, False), ("masks", masks, torch.uint8, lead, True),
+                                             *extra):
+            if t is None and optional:
+                continue
+            if (not isinstance(t, torch.Tensor) or t.dtype is not dt or t.device != self.device or tuple(t.shape) != shape
+                    or not t.is_contiguous()):
+                hint = " (cast stored actions to torch.uint8 first)" if name == "actions" else ""
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {self.device}{hint}")
+        if logits.data_ptr() % 16:
+            raise ValueError("logits must be 16-byte aligned (a view at an odd offset of its storage is not)")
+        return lead
+
+    def _evaluate_forward(self, logits, actions, masks, out: EvalResult) -> None:
+        self._order_after_current_stream(logits, actions, masks, out.logp, out.entropy)
+        check(self._lib.ccx_evaluate_actions(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks), _ptr(out.logp),
+                                             _ptr(out.entropy)))
+
+    def _current_stream_waits(self) -> None:
+        """Results of a launch on the handle's stream that torch ops consume at once on torch's CURRENT stream: when that
+        is another stream, it waits for the handle's stream."""
+        if torch._C._cuda_getCurrentRawStream(self.device.index) != self._stream_raw:
+            torch.cuda.current_stream(self.device).wait_stream(self._stream)
+
+    def evaluate_actions(self, logits: torch.Tensor, actions: torch.Tensor, masks: torch.Tensor | None = None,
+                         want_entropy: bool = True, out: EvalResult | None = None) -> EvalResult:
+        """``log pi_new(stored action | state)`` and the entropy of the masked distribution under new logits, on the device
+        (``ccx_evaluate_actions``, include/ccx.h CCX_EVALUATE): one kernel on the handle's stream, bit-defined, and the very
+        distribution :meth:`sample_actions` draws from -- on the logits an action was sampled from, ``logp`` and
+        ``entropy`` equal the sampler's bit for bit.
+
+        ``logits`` f32 [..., 5] (contiguous, 16-byte aligned); ``actions`` u8 [...] (what :meth:`sample_actions` stored; cast
+        int64 actions first); ``masks`` u8 [...] or ``None`` (everything legal).  Rows whose action is 255 give ``logp`` =
+        ``entropy`` = +0.0 whatever their logits hold; an action that is out of range or illegal under its mask gives
+        ``logp`` = -inf.  Anything else than the tensors described raises ``ValueError`` before the library is called;
+        zero rows return empty tensors without calling it.
+
+        When ``logits.requires_grad`` and grad mode is on, the call is a ``torch.autograd.Function``: its backward is
+        ``ccx_evaluate_actions_backward`` (one kernel; illegal places, 255 rows and degenerate rows get exactly +0.0, selected,
+        so a NaN there never reaches a gradient), an output the loss did not use is passed as NULL, and ``out=`` is refused.
+        Otherwise this is the plain forward and ``out=`` reuses an :class:`EvalResult` (:meth:`alloc_evaluate`).  Only
+        enqueues."""
+        lead = self._check_evaluate(logits, actions, masks)
+        if logits.requires_grad and torch.is_grad_enabled():
+            if out is not None:
+                raise ValueError("out= cannot be used when logits require a gradient (the autograd path allocates its outputs)")
+            if logits.numel() == 0:
+                zero = logits.sum(-1) * 0.0
+                return EvalResult(zero, zero.clone() if want_entropy else None)
+            logp, entropy = _EvaluateActions.apply(self, logits, actions, masks, bool(want_entropy))
+            return EvalResult(logp, entropy)
+        if out is None:
+            out = self.alloc_evaluate(lead, want_entropy)
+        elif not isinstance(out, EvalResult):
+            raise ValueError("out must be an EvalResult (alloc_evaluate)")
+        self._check_evaluate(logits, actions, masks, (("out.logp", out.logp, torch.float32, lead, False),
+                                                      ("out.entropy", out.entropy, torch.float32, lead, True)))
+        if logits.numel():
+            self._evaluate_forward(logits, actions, masks, out)
+        return out
+
+    def evaluate_actions_backward(self, logits: torch.Tensor, actions: torch.Tensor, masks: torch.Tensor | None,
+                                  grad_logp: torch.Tensor | None, grad_entropy: torch.Tensor | None,
+                                  out: torch.Tensor | None = None) -> torch.Tensor:
+        """The gradient of :meth:`evaluate_actions` with respect to ``logits`` from the gradients of its two outputs
+        (``ccx_evaluate_actions_backward``): one kernel that recomputes the forward quantities from the logits.  Either of
+        ``grad_logp`` / ``grad_entropy`` (f32, the leading shape of ``logits``) may be ``None``, not both.  ``out`` reuses a
+        f32 tensor of the shape of ``logits`` (16-byte aligned): with :meth:`evaluate_actions` ``(out=)`` the static-buffer
+        pair for a captured graph.  Only enqueues."""
+        if grad_logp is None and grad_entropy is None:
+            raise ValueError("at least one of grad_logp and grad_entropy is required")
+        if out is None and isinstance(logits, torch.Tensor):
+            out = torch.empty_like(logits, requires_grad=False)
+        lead = tuple(logits.shape[:-1]) if isinstance(logits, torch.Tensor) else ()
+        self._check_evaluate(logits, actions, masks, (
+            ("grad_logp", grad_logp, torch.float32, lead, True), ("grad_entropy", grad_entropy, torch.float32, lead, True),
+            ("out", out, torch.float32, lead + (5,), False)))
+        if out.data_ptr() % 16:
+            raise ValueError("out must be 16-byte aligned (a view at an odd offset of its storage is not)")
+        if logits.numel():
+            self._order_after_current_stream(logits, actions, masks, grad_logp, grad_entropy, out)
+            check(self._lib.ccx_evaluate_actions_backward(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks),
+                                                          _ptr(grad_logp), _ptr(grad_entropy), _ptr(out)))
         return out
 
     # ------------------------------------------------------------------ compute
@@ -1428,3 +1534,31 @@ class _CudaArrayView:
 
 def _device_view_i64(ptr: int, n: int, device: torch.device) -> torch.Tensor:
     return torch.as_tensor(_CudaArrayView(ptr, n), device=device)
+
+
+class _EvaluateActions(torch.autograd.Function):
+    """:meth:`BatchedCollectiveCrossing.evaluate_actions` for logits that require a gradient: forward and backward are
+    the two kernels of CCX_EVALUATE; nothing is saved but the inputs."""
+
+    @staticmethod
+    def forward(ctx, batch, logits, actions, masks, want_entropy):
+        logits = logits.detach()
+        out = batch.alloc_evaluate(logits.shape[:-1], want_entropy)
+        batch._evaluate_forward(logits, actions, masks, out)
+        batch._current_stream_waits()
+        ctx.batch, ctx.actions, ctx.masks = batch, actions, masks
+        ctx.save_for_backward(logits)
+        ctx.set_materialize_grads(False)                # an output the loss did not use arrives as None and is passed as NULL
+        return out.logp, out.entropy
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_logp, grad_entropy):
+        (logits,) = ctx.saved_tensors
+        grad_logp = None if grad_logp is None else grad_logp.contiguous()
+        grad_entropy = None if grad_entropy is None else grad_entropy.contiguous()
+        if grad_logp is None and grad_entropy is None:
+            return None, None, None, None, None
+        grad = ctx.batch.evaluate_actions_backward(logits, ctx.actions, ctx.masks, grad_logp, grad_entropy)
+        ctx.batch._current_stream_waits()
+        return None, grad, None, None, None

@@ -11,12 +11,18 @@
 // pieces repeat the last valid ones), so all of a lane's loads are in flight before its first wait.  5 E N floats need not
 // be a multiple of 4: the up to three floats behind the last whole piece belong to the array's last slot, whose lane
 // fetches them as dwords.  logits must be 16-byte aligned.
-// Arithmetic.  exp_spec / log_spec are the header's sequences, one f32 operation per line (-ffp-contract=off; `/` is the
-// correctly rounded division, asked for on this unit's compile line).  Everything the rule does not read is SELECTED away
-// before any arithmetic: a NaN at an illegal place or in a dead slot never reaches a result.
+// Arithmetic.  exp_spec / log_spec and steps 2-6 are ccx_softmax.h's (shared with ccx_evaluate.hip): the header's sequences,
+// one f32 operation per line (-ffp-contract=off; `/` is the correctly rounded division, asked for on this unit's compile
+// line).  Everything the rule does not read is SELECTED away before any arithmetic: a NaN at an illegal place or in a dead
+// slot never reaches a result.
 #include "ccx_internal.h"
+#include "ccx_softmax.h"
 
 using ccxi::fail;
+using ccx_softmax::entropy_spec;
+using ccx_softmax::legal_max_d;
+using ccx_softmax::log_spec;
+using ccx_softmax::weights;
 
 namespace {
 
@@ -35,65 +41,14 @@ struct SampleArgs {
     uint32_t N, genv0, seed_lo, seed_hi;   // genv0: low word of env_offset; seed_hi already carries kSampleStream
 };
 
-constexpr float kLog2e = 0x1.715476p+0f, kLn2Hi = 0x1.62e4p-1f, kLn2Lo = 0x1.7f7d1cp-20f, kSqrtHalf = 0x1.6a09e6p-1f;
-constexpr float kDMin = -80.0f;
-
-// x in [-80, 0]
-__host__ __device__ __forceinline__ float exp_spec(float x) {
-    const float n = rintf(x * kLog2e);
-    const float r = (x - n * kLn2Hi) - n * kLn2Lo;
-    float p = 0x1.a01a02p-13f;
-    p = p * r + 0x1.6c16c2p-10f;
-    p = p * r + 0x1.111112p-7f;
-    p = p * r + 0x1.555556p-5f;
-    p = p * r + 0x1.555556p-3f;
-    p = p * r + 0x1p-1f;
-    p = p * r + 1.0f;
-    p = p * r + 1.0f;
-    return p * __builtin_bit_cast(float, ((int)n + 127) << 23);           // exact: n >= -116, the product is a normal number
-}
-
-// s in [1, 5]
-__host__ __device__ __forceinline__ float log_spec(float s) {
-    const int bits = __builtin_bit_cast(int, s);
-    float m = __builtin_bit_cast(float, (bits & 0x007FFFFF) | 0x3F000000);  // s = m * 2^e, m in [0.5, 1)
-    int e = (bits >> 23) - 126;
-    const bool small = m < kSqrtHalf;
-    m = small ? m + m : m;
-    e = small ? e - 1 : e;
-    const float ef = (float)e;
-    const float t = m - 1.0f;
-    const float q = t / (2.0f + t);
-    const float z = q * q;
-    float p = 0x1.c71c72p-4f;
-    p = p * z + 0x1.24924ap-3f;
-    p = p * z + 0x1.99999ap-3f;
-    p = p * z + 0x1.555556p-2f;
-    const float u = q + q;
-    const float lf = u + u * (z * p);
-    return ef * kLn2Hi + (lf + ef * kLn2Lo);
-}
-
 // The rule of one live slot (steps 2-10 of the header paragraph) from its five logits, its legal set m and its draw u.
 // Host and device: the same source can be run on the CPU against tests/_sample_spec.py.
 template <bool DET, bool STATS>
 __host__ __device__ __forceinline__ void sample_slot(float (&l)[5], uint32_t m, uint32_t u, bool want_logp, bool want_entropy,
                                                      uint32_t& action, float& logp, float& entropy) {
-    const float ninf = -__builtin_inff();
-    bool legal[5];
-    float mx = ninf;
-    bool bad = false;
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        legal[k] = (m >> k) & 1u;
-        l[k] = legal[k] ? l[k] : ninf;                                  // illegal logits leave here
-        mx = l[k] > mx ? l[k] : mx;
-        bad = bad || l[k] != l[k] || l[k] == __builtin_inff();
-    }
-    const bool degenerate = bad || mx == ninf;
-    float d[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) d[k] = (legal[k] && !degenerate) ? l[k] - mx : 0.0f;
+    bool legal[5], degenerate;
+    float mx, d[5];
+    legal_max_d(l, m, legal, mx, degenerate, d);
     action = 4u;
     float S = 1.0f, w[5];
     if (DET) {
@@ -102,13 +57,7 @@ __host__ __device__ __forceinline__ void sample_slot(float (&l)[5], uint32_t m, 
     }
     if (!DET || STATS) {
         float c[5];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) {
-            const bool cut = d[k] < kDMin;
-            w[k] = (legal[k] && !cut) ? exp_spec(cut ? 0.0f : d[k]) : 0.0f;
-            c[k] = k ? c[k - 1] + w[k] : w[0];
-        }
-        S = c[4];
+        S = weights(legal, d, w, c);
         if (!DET) {
             const float thr = ((float)(u >> 8) * 0x1p-24f) * S;
 #pragma unroll
@@ -124,13 +73,7 @@ __host__ __device__ __forceinline__ void sample_slot(float (&l)[5], uint32_t m, 
             logp = da - ls;
         }
         if (want_entropy) {
-            float T = 0.0f;
-#pragma unroll
-            for (int k = 0; k < 5; ++k) {
-                const float term = w[k] == 0.0f ? 0.0f : w[k] * d[k];
-                T = k ? T + term : term;
-            }
-            entropy = ls - T / S;
+            entropy = entropy_spec(w, d, S, ls);
         }
     }
 }

@@ -644,6 +644,68 @@ int ccx_sample_actions(ccx_handle* h, const float* logits /* [E][N][5] */, const
                        int32_t deterministic, uint8_t* actions /* [E][N] */, float* logp_or_null /* [E][N] */,
                        float* entropy_or_null /* [E][N] */);
 /*
+ * CCX_EVALUATE: the learning side of CCX_SAMPLE -- log pi_new(a_stored | s) and the entropy of the masked distribution under
+ * NEW logits for STORED actions, and the gradient of both with respect to those logits: what every epoch of a PPO update
+ * needs after collection.  The distribution is CCX_SAMPLE's own (its steps 2-6 and 9-10, exp_spec and log_spec), so on the
+ * logits an action was sampled from, logp and entropy equal ccx_sample_actions' outputs bit for bit: the ratio
+ * exp(logp_new - logp_old) is exactly 1 before the first update.  Every output of both passes is bit-defined.
+ *
+ * A pure function of its arrays: it never reads the env state; the handle supplies only device and stream.  Rows are flat:
+ * M >= 1 rows (any leading shape on the caller's side).  All arithmetic follows the discipline of CCX_SAMPLE: IEEE binary32,
+ * every operation named below is ONE correctly rounded f32 operation (+ - * /), nothing is fused (no fma), nothing is
+ * reassociated, subnormals are kept.
+ *
+ * Forward.  Inputs (device pointers): logits f32 [M][5] (index = action id; 16-byte aligned), actions u8 [M] (what
+ * ccx_sample_actions wrote), masks u8 [M] or NULL (the bytes of CCX_ACTION_MASKS; NULL = everything legal).  Outputs: logp f32
+ * [M], entropy f32 [M] or NULL; every element of every output given is written.  For every row i on its own, with
+ * a = actions[i], l_k = logits[i][k]:
+ *   - a == CCX_ACTION_ABSENT (255): logp = +0.0f, entropy = +0.0f; the row's logits and its mask byte are not read into any
+ *     result (a NaN there stays there).
+ *   - otherwise m, the legal set, mx, degenerate, d_k, w_k, c_k and S are exactly steps 2-6 of CCX_SAMPLE (a degenerate row
+ *     is uniform over its legal set: d_k = +0.0f, w_k = 1 for every legal k), and
+ *       entropy = log_spec(S) - T / S                      exactly step 10
+ *       logp    = d_a - log_spec(S)                        if a <= 4 and a is legal under m: step 9.  A legal a with w_a = 0
+ *                                                          gives a large negative or -inf logp; that follows from the rule
+ *       logp    = -inf                                     if a is in 5..254, or a is illegal under m
+ *
+ * Backward.  Inputs: the forward's three inputs, grad_logp f32 [M] or NULL, grad_entropy f32 [M] or NULL (at least one of
+ * the two is given).  Output: grad_logits f32 [M][5] (16-byte aligned), every element written.  The forward quantities are
+ * recomputed from the logits; nothing is saved between the passes but the inputs.  For every row i on its own:
+ *   - absent row (a == 255) or degenerate row: grad_logits[i][k] = +0.0f for all five k.
+ *   - illegal k: grad_logits[i][k] = +0.0f, SELECTED, whatever the logit or the incoming gradients hold.
+ *   - legal k of any other row, in this order of operations:
+ *       p_k  = w_k / S                                     (one division)
+ *       ls   = log_spec(S);  lp_k = d_k - ls
+ *       H    = the forward's entropy, the same operation sequence
+ *       t1_k = (k == a ? 1.0f : 0.0f) - p_k
+ *       A_k  = grad_logp[i] * t1_k;  or +0.0f, selected, for every k when a is in 5..254 or illegal under m (logp = -inf
+ *              has no gradient; a NaN in grad_logp[i] stays there)
+ *       t2_k = (w_k == 0) ? +0.0f : p_k * (lp_k + H)       (one add, one multiply; lp_k may be -inf where w_k = 0: selected)
+ *       B_k  = grad_entropy[i] * t2_k
+ *       grad_logits[i][k] = A_k - B_k;   with grad_entropy NULL: A_k;   with grad_logp NULL: 0.0f - B_k
+ *   These are d logp / d l_k = [k == a] - p_k and d entropy / d l_k = -p_k (log p_k + H) of the masked softmax.  A row with
+ *   one legal action has logp = entropy = +0.0f and gradients +-0.  Incoming gradients at absent and degenerate rows are
+ *   selected away, never multiplied by zero: the library's rule holds in the backward pass too.
+ *
+ * Against IEEE f64 (measured on the CPU, tests/test_evaluate_spec.py, maxima doubled), as max |err| / max(1, |f64 value|)
+ * over the adversarial generator's rows that are not absent, not degenerate and whose stored action is legal with w_a > 0:
+ * logp within 4.0e-7, entropy within 4.0e-7, the Jacobian of logp (grad_logp = 1 alone) within 4.1e-7 and the Jacobian of
+ * the entropy (grad_entropy = 1 alone) within 3.7e-7 of the f64 masked log-softmax, its entropy and their f64 autograd
+ * gradients on the same f32 logits.  logp carries its own bound, relative to its size: a sampled action sits near d = 0, a
+ * stored one may sit at d near -80, where one rounding of l_a - mx is already 3.8e-6 absolute.
+ *
+ * Each entry point only enqueues ONE kernel on the handle's stream: no host synchronisation, no allocation, and it captures
+ * into a HIP graph.  A NULL handle or a NULL required pointer (logits, actions, logp / grad_logits), rows < 1, rows so large
+ * that the grid would pass 2^31 - 1 workgroups of 64 rows, logits or grad_logits that are not 16-byte aligned, or both
+ * gradients NULL: CCX_EINVAL with a ccx_last_error message.  Offsets are 64-bit (5 M may exceed 2^31).  Not here: bf16 / f16
+ * logits (cast first), a temperature (scale the logits first), the PPO loss itself.
+ */
+int ccx_evaluate_actions(ccx_handle* h, int64_t rows, const float* logits /* [M][5] */, const uint8_t* actions /* [M] */,
+                         const uint8_t* masks_or_null /* [M] */, float* logp /* [M] */, float* entropy_or_null /* [M] */);
+int ccx_evaluate_actions_backward(ccx_handle* h, int64_t rows, const float* logits /* [M][5] */, const uint8_t* actions /* [M] */,
+                                  const uint8_t* masks_or_null /* [M] */, const float* grad_logp_or_null /* [M] */,
+                                  const float* grad_entropy_or_null /* [M] */, float* grad_logits /* [M][5] */);
+/*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
  * `rng_seed` of ccx_rollout).  The action of agent slot a of global env g at step t (0-based) of its episode j is
