@@ -11,7 +11,8 @@ from .configs import CollectiveCrossingConfig  # noqa: F401
 
 __version__ = "0.4.0"
 __all__ = ["CollectiveCrossingConfig", "CollectiveCrossingEnv", "BatchedCollectiveCrossing", "VectorCollectiveCrossing",
-           "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult", "SampleResult", "EvalResult"]
+           "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult", "SampleResult", "EvalResult",
+           "PpoLossResult"]
 
 
 def __getattr__(name):  # lazy: importing the configs must not pull in torch
@@ -39,6 +40,9 @@ def __getattr__(name):  # lazy: importing the configs must not pull in torch
     if name == "EvalResult":
         from .batched import EvalResult
         return EvalResult
+    if name == "PpoLossResult":
+        from .batched import PpoLossResult
+        return PpoLossResult
     raise AttributeError(name)
 
 

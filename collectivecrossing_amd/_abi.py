@@ -141,6 +141,10 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_evaluate_actions": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ccx_evaluate_actions_backward": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                 C.c_void_p]),
+    "ccx_ppo_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "ccx_masked_moments": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ccx_ppo_loss": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 9 + [C.c_float] * 4 + [C.c_void_p, C.c_void_p]),
+    "ccx_ppo_loss_backward": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 9 + [C.c_float] * 4 + [C.c_void_p] * 4),
     "ccx_set_check_inputs": (C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),

@@ -121,6 +121,26 @@ class EvalResult:
     entropy: torch.Tensor | None  # f32 [...]: entropy of the masked distribution
 
 
+@dataclass
+class PpoLossResult:
+    """The PPO loss over the rows that count (:meth:`BatchedCollectiveCrossing.ppo_loss`, include/ccx.h CCX_PPO_LOSS).
+    ``stats`` = {loss, policy, value, entropy, approx_kl, clip_frac, count, 0}; the named accessors are 0-dim views of it.
+    ``workspace`` / ``grad_logits`` / ``grad_values`` are the static buffers of :meth:`alloc_ppo_loss` (else ``None``)."""
+
+    loss: torch.Tensor                        # f32 0-dim: stats[0]; carries the autograd graph when an input required grad
+    stats: torch.Tensor                       # f32 [8]
+    workspace: torch.Tensor | None = None     # u8 [ccx_ppo_workspace_bytes(rows)]
+    grad_logits: torch.Tensor | None = None   # f32 [..., 5]
+    grad_values: torch.Tensor | None = None   # f32 [...]
+
+    policy = property(lambda self: self.stats[1])
+    value = property(lambda self: self.stats[2])
+    entropy = property(lambda self: self.stats[3])
+    approx_kl = property(lambda self: self.stats[4])
+    clip_frac = property(lambda self: self.stats[5])
+    count = property(lambda self: self.stats[6])
+
+
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
     return C.c_void_p(None if t is None else t.data_ptr())
 
@@ -853,6 +873,185 @@ class BatchedCollectiveCrossing:
                                                           _ptr(grad_logp), _ptr(grad_entropy), _ptr(out)))
         return out
 
+    # ------------------------------------------------------------------ the PPO loss over the rows that count
+    def _ppo_workspace(self, rows: int) -> torch.Tensor:
+        """A workspace from torch's allocator (so a call inside a graph capture stays capturable)."""
+        return self._new((max(8, int(self._lib.ccx_ppo_workspace_bytes(int(rows)))),), torch.uint8)
+
+    def alloc_ppo_loss(self, shape, want_logits_grad: bool = True, want_values_grad: bool = True) -> PpoLossResult:
+        """Static buffers of :meth:`ppo_loss` / :meth:`ppo_loss_backward` for rows of the leading shape ``shape``: stats,
+        the workspace and the two gradients (for a captured graph)."""
+        shape = tuple(int(x) for x in shape)
+        rows = int(np.prod(shape)) if shape else 1
+        stats = torch.zeros((8,), dtype=torch.float32, device=self.device)
+        return PpoLossResult(stats[0], stats, self._ppo_workspace(rows),
+                             self._new(shape + (5,), torch.float32) if want_logits_grad else None,
+                             self._new(shape, torch.float32) if want_values_grad else None)
+
+    @staticmethod
+    def _check_ppo_hyper(clip, vf_coef, ent_coef, adv_eps):
+        clip, vf_coef, ent_coef, adv_eps = float(clip), float(vf_coef), float(ent_coef), float(adv_eps)
+        if not 0.0 < clip < 1.0:                                     # (false for NaN)
+            raise ValueError(f"clip must lie in (0, 1), got {clip!r}")
+        for name, x in (("vf_coef", vf_coef), ("ent_coef", ent_coef), ("adv_eps", adv_eps)):
+            if not 0.0 <= x < float("inf"):
+                raise ValueError(f"{name} must be finite and not negative, got {x!r}")
+        return clip, vf_coef, ent_coef, adv_eps
+
+    def _check_flat(self, name, t, dtype, shape, optional=False):
+        if t is None and optional:
+            return
+        if (not isinstance(t, torch.Tensor) or t.dtype is not dtype or t.device != self.device or tuple(t.shape) != tuple(shape)
+                or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {self.device}")
+
+    def _check_ppo(self, logits, values, actions, logp_old, advantages, returns, masks, valid, norm):
+        """The input checks of :meth:`ppo_loss` and :meth:`ppo_loss_backward`; returns (leading shape, norm f32 [2] or None)."""
+        lead = self._check_evaluate(logits, actions, masks, (
+            ("values", values, torch.float32, tuple(logits.shape[:-1]) if isinstance(logits, torch.Tensor) else (), False),))
+        for name, t, dt in (("logp_old", logp_old, torch.float32), ("advantages", advantages, torch.float32),
+                            ("returns", returns, torch.float32), ("valid", valid, torch.uint8)):
+            self._check_flat(name, t, dt, lead, optional=name == "valid")
+        if norm is not None:
+            if (not isinstance(norm, torch.Tensor) or norm.dtype is not torch.float32 or norm.device != self.device
+                    or tuple(norm.shape) not in ((2,), (4,)) or not norm.is_contiguous()):
+                raise ValueError(f"norm must be a contiguous torch.float32 tensor on {self.device}: masked_moments' [4] "
+                                 "(n, mean, std, 0) or [2] (mean, std)")
+            if norm.shape[0] == 4:
+                norm = norm[1:3]
+        return lead, norm
+
+    def masked_moments(self, x: torch.Tensor, valid: torch.Tensor | None = None, out: torch.Tensor | None = None,
+                       workspace: torch.Tensor | None = None) -> torch.Tensor:
+        """``[n, mean, std, 0]`` (f32 [4] on the device) of ``x`` f32 [...] over the elements where ``valid`` u8 [...] is not
+        zero (``None``: all), by ``ccx_masked_moments`` (include/ccx.h CCX_PPO_LOSS): two kernels on the handle's stream, a
+        fixed f64 tree, bit-defined, no host synchronisation.  ``std`` is the unbiased one; ``n < 2`` gives mean 0, std 1.
+        Hand the result to :meth:`ppo_loss` as ``norm=``.  ``out`` / ``workspace`` reuse buffers (a captured graph).  Zero
+        elements return ``[0, 0, 1, 0]`` without calling the library.  Only enqueues."""
+        if (not isinstance(x, torch.Tensor) or x.dtype is not torch.float32 or x.device != self.device or not x.is_contiguous()):
+            raise ValueError(f"x must be a contiguous torch.float32 tensor on {self.device}")
+        self._check_flat("valid", valid, torch.uint8, x.shape, optional=True)
+        if out is None:
+            out = self._new((4,), torch.float32)
+        self._check_flat("out", out, torch.float32, (4,))
+        rows = x.numel()
+        if rows == 0:
+            out.copy_(torch.tensor([0.0, 0.0, 1.0, 0.0], dtype=torch.float32))
+            return out
+        workspace = self._ppo_workspace_arg(workspace, rows)
+        self._order_after_current_stream(x, valid, out, workspace)
+        check(self._lib.ccx_masked_moments(self._h, rows, _ptr(x), _ptr(valid), _ptr(workspace), _ptr(out)))
+        self._current_stream_waits()
+        return out
+
+    def _ppo_workspace_arg(self, workspace, rows: int) -> torch.Tensor:
+        if workspace is None:
+            return self._ppo_workspace(rows)
+        need = int(self._lib.ccx_ppo_workspace_bytes(int(rows)))
+        if (not isinstance(workspace, torch.Tensor) or workspace.dtype is not torch.uint8 or workspace.device != self.device
+                or workspace.dim() != 1 or workspace.numel() < need or not workspace.is_contiguous() or workspace.data_ptr() % 8):
+            raise ValueError(f"workspace must be a contiguous, 8-byte aligned torch.uint8 tensor of at least {need} bytes on "
+                             f"{self.device} (alloc_ppo_loss)")
+        return workspace
+
+    def _ppo_forward(self, logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper, workspace, stats):
+        self._order_after_current_stream(logits, values, actions, logp_old, advantages, returns, masks, valid, norm, workspace, stats)
+        check(self._lib.ccx_ppo_loss(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks), _ptr(logp_old),
+                                     _ptr(advantages), _ptr(returns), _ptr(values), _ptr(valid), _ptr(norm), *hyper,
+                                     _ptr(workspace), _ptr(stats)))
+        self._current_stream_waits()
+
+    def ppo_loss(self, logits: torch.Tensor, values: torch.Tensor, actions: torch.Tensor, logp_old: torch.Tensor,
+                 advantages: torch.Tensor, returns: torch.Tensor, masks: torch.Tensor | None = None,
+                 valid: torch.Tensor | None = None, norm: torch.Tensor | None = None, clip: float = 0.2, vf_coef: float = 0.5,
+                 ent_coef: float = 0.01, adv_eps: float = 1e-8, out: PpoLossResult | None = None) -> PpoLossResult:
+        """The clipped-surrogate PPO loss ``policy + vf_coef * value - ent_coef * entropy`` over the rows that count, on
+        the device (``ccx_ppo_loss``, include/ccx.h CCX_PPO_LOSS): two kernels on the handle's stream, bit-defined (the
+        reduction is a fixed f64 tree), shapes static -- ``valid`` is a selection inside the kernel, so nothing is
+        compacted, nothing synchronises with the host, and the whole update captures into a graph.
+
+        ``logits`` f32 [..., 5] (contiguous, 16-byte aligned), everything else [...]: ``values`` f32 (the critic's, new
+        weights), ``actions`` u8 and ``masks`` u8 or ``None`` as in :meth:`evaluate_actions`, ``logp_old`` f32
+        (:meth:`sample_actions`' logp), ``advantages`` / ``returns`` f32 and ``valid`` u8 (:meth:`compute_gae`'s).  A row
+        counts iff its ``valid`` byte is not zero and its action is not 255.  ``norm``: :meth:`masked_moments`' result
+        (or a [2] = mean, std): advantages enter as ``(a - mean) / (std + adv_eps)``.  The result's ``stats`` holds loss,
+        policy, value, entropy, approx_kl (mean of ``ratio - 1 - log ratio``), clip_frac, count, 0.
+
+        When ``logits`` or ``values`` requires grad and grad mode is on, the call is a ``torch.autograd.Function``:
+        ``r.loss.backward()`` reaches both through ``ccx_ppo_loss_backward`` (one kernel; rows that do not count get exactly
+        +0.0), ``None`` goes to the one that does not require grad, ``out=`` is refused, and the workspace comes from
+        torch's allocator, so the call captures.  Otherwise ``out=`` reuses a result of :meth:`alloc_ppo_loss`.  A wrong
+        dtype, shape or device, a non-contiguous tensor, a misaligned pointer or a bad hyperparameter raises ``ValueError``
+        before the library is called; zero rows return zeros without calling it.  Only enqueues."""
+        hyper = self._check_ppo_hyper(clip, vf_coef, ent_coef, adv_eps)
+        lead, norm = self._check_ppo(logits, values, actions, logp_old, advantages, returns, masks, valid, norm)
+        needs = [t.requires_grad for t in (logits, values)]
+        if any(needs) and torch.is_grad_enabled():
+            if out is not None:
+                raise ValueError("out= cannot be used when logits or values require a gradient (the autograd path allocates its outputs)")
+            if logits.numel() == 0:
+                stats = torch.cat([(logits.sum() + values.sum()).reshape(1) * 0.0, torch.zeros(7, device=self.device)])
+            else:
+                stats = _PpoLoss.apply(self, logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper)
+            return PpoLossResult(stats[0], stats.detach())
+        if out is None:
+            stats = torch.zeros((8,), dtype=torch.float32, device=self.device)
+            out = PpoLossResult(stats[0], stats)
+            workspace = None
+        elif not isinstance(out, PpoLossResult):
+            raise ValueError("out must be a PpoLossResult (alloc_ppo_loss)")
+        else:
+            self._check_flat("out.stats", out.stats, torch.float32, (8,))
+            workspace = out.workspace
+        if logits.numel() == 0:
+            out.stats.zero_()
+            return out
+        workspace = self._ppo_workspace_arg(workspace, actions.numel())
+        self._ppo_forward(logits.detach(), values.detach(), actions, logp_old, advantages, returns, masks, valid, norm, hyper,
+                          workspace, out.stats)
+        return out
+
+    def ppo_loss_backward(self, logits: torch.Tensor, values: torch.Tensor, actions: torch.Tensor, logp_old: torch.Tensor,
+                          advantages: torch.Tensor, returns: torch.Tensor, masks: torch.Tensor | None = None,
+                          valid: torch.Tensor | None = None, norm: torch.Tensor | None = None, clip: float = 0.2,
+                          vf_coef: float = 0.5, ent_coef: float = 0.01, adv_eps: float = 1e-8, *, stats: torch.Tensor,
+                          grad_loss: torch.Tensor | None = None, want_logits_grad: bool = True, want_values_grad: bool = True,
+                          out: PpoLossResult | None = None):
+        """``(grad_logits, grad_values)`` of :meth:`ppo_loss`'s ``loss`` (``ccx_ppo_loss_backward``: one kernel that recomputes
+        the forward terms from the same inputs and the forward's ``stats``).  ``grad_loss`` f32 [1] or 0-dim on the device
+        (``None`` = 1).  ``want_*`` choose the outputs (at least one; the other is returned as ``None`` and not computed);
+        ``out`` reuses the gradients of an :meth:`alloc_ppo_loss` result instead (one of them may be ``None``).  Only
+        enqueues."""
+        hyper = self._check_ppo_hyper(clip, vf_coef, ent_coef, adv_eps)
+        lead, norm = self._check_ppo(logits, values, actions, logp_old, advantages, returns, masks, valid, norm)
+        self._check_flat("stats", stats, torch.float32, (8,))
+        if grad_loss is not None:
+            if (not isinstance(grad_loss, torch.Tensor) or grad_loss.dtype is not torch.float32 or grad_loss.device != self.device
+                    or grad_loss.numel() < 1 or grad_loss.dim() > 1 or not grad_loss.is_contiguous()):
+                raise ValueError(f"grad_loss must be a torch.float32 tensor with one element (0-dim or [1]) on {self.device}")
+        if out is None:
+            gl = torch.empty_like(logits, requires_grad=False) if want_logits_grad else None
+            gv = torch.empty_like(values, requires_grad=False) if want_values_grad else None
+        elif not isinstance(out, PpoLossResult):
+            raise ValueError("out must be a PpoLossResult (alloc_ppo_loss)")
+        else:
+            gl, gv = out.grad_logits, out.grad_values
+        if gl is None and gv is None:
+            raise ValueError("at least one of the two gradients is required")
+        self._check_flat("grad_logits", gl, torch.float32, lead + (5,), optional=True)
+        self._check_flat("grad_values", gv, torch.float32, lead, optional=True)
+        if gl is not None and gl.data_ptr() % 16:
+            raise ValueError("grad_logits must be 16-byte aligned (a view at an odd offset of its storage is not)")
+        if logits.numel():
+            logits, values = logits.detach(), values.detach()
+            self._order_after_current_stream(logits, values, actions, logp_old, advantages, returns, masks, valid, norm, stats,
+                                             grad_loss, gl, gv)
+            check(self._lib.ccx_ppo_loss_backward(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks),
+                                                  _ptr(logp_old), _ptr(advantages), _ptr(returns), _ptr(values), _ptr(valid),
+                                                  _ptr(norm), *hyper, _ptr(stats), _ptr(grad_loss), _ptr(gl), _ptr(gv)))
+            self._current_stream_waits()
+        return gl, gv
+
     # ------------------------------------------------------------------ compute
     def observe(self, out: torch.Tensor | None = None) -> torch.Tensor:
         if out is None:
@@ -1562,3 +1761,31 @@ class _EvaluateActions(torch.autograd.Function):
         grad = ctx.batch.evaluate_actions_backward(logits, ctx.actions, ctx.masks, grad_logp, grad_entropy)
         ctx.batch._current_stream_waits()
         return None, grad, None, None, None
+
+
+class _PpoLoss(torch.autograd.Function):
+    """:meth:`BatchedCollectiveCrossing.ppo_loss` for logits or values that require a gradient: the forward is the two
+    kernels of ``ccx_ppo_loss``, the backward the one of ``ccx_ppo_loss_backward``; nothing is saved but the inputs and
+    ``stats``.  Only ``stats[0]``, the loss, is differentiable: the gradient arriving at the other seven is not read."""
+
+    @staticmethod
+    def forward(ctx, batch, logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper):
+        logits, values = logits.detach(), values.detach()
+        stats = torch.zeros((8,), dtype=torch.float32, device=batch.device)
+        batch._ppo_forward(logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper,
+                           batch._ppo_workspace(actions.numel()), stats)
+        ctx.batch, ctx.hyper = batch, hyper
+        ctx.rest = (actions, logp_old, advantages, returns, masks, valid, norm)
+        ctx.save_for_backward(logits, values, stats)
+        return stats
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_stats):
+        logits, values, stats = ctx.saved_tensors
+        actions, logp_old, advantages, returns, masks, valid, norm = ctx.rest
+        want_l, want_v = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        gl, gv = ctx.batch.ppo_loss_backward(logits, values, actions, logp_old, advantages, returns, masks, valid, norm,
+                                             *ctx.hyper, stats=stats, grad_loss=grad_stats.contiguous(),
+                                             want_logits_grad=want_l, want_values_grad=want_v)
+        return (None, gl, gv) + (None,) * 8

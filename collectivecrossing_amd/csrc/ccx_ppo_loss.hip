@@ -1,0 +1,323 @@
+// ccx_ppo_loss.hip -- CCX_PPO_LOSS (include/ccx.h): the clipped-surrogate PPO loss over the rows that count, its statistics
+// and its gradient with respect to logits and values, plus the masked moments that normalise the advantages.  The per-row
+// rule, the pieces of the reduction tree and the final values are ccx_ppo.h (which calls ccx_softmax.h's evaluate_row*); the
+// logits travel through LDS by ccx_rows.h.  `valid` is a selection inside the kernels: shapes stay static, nothing is
+// compacted, nothing synchronises with the host.
+//
+// Forward: two launches.  ppo_partial_kernel: a workgroup of four waves takes 256 consecutive rows, one lane one row; each
+// wave reduces its 64 rows' six f64 terms by a butterfly (a group of the tree), lane 0 leaves them in LDS, and the first six
+// threads add the four groups and write the block's six partials to the workspace ([6][B] f64).  ppo_final_kernel: ONE wave
+// adds the partials lane-strided, runs the same butterfly and writes the eight f32 of `stats`.  There is no atomic and no
+// last-block-done counter: a kernel boundary orders the partials, and two plain launches cannot hang.
+// Backward: one launch, ppo_bwd_kernel, one lane one row, a workgroup is one wave (ccx_evaluate.hip's shape); it recomputes
+// the forward terms from the inputs and reads nothing else but `stats`.
+// The masked moments: moments_partial_kernel / moments_final_kernel, the same tree over three sums.
+#include "ccx_internal.h"
+#include "ccx_ppo.h"
+#include "ccx_rows.h"
+
+using ccxi::fail;
+
+namespace {
+
+struct PpoArgs {
+    const float* logits;
+    const uint8_t* actions;
+    const uint8_t* masks;              // read only where MASK
+    const float* logp_old;
+    const float* advantages;
+    const float* returns;
+    const float* values;
+    const uint8_t* valid;              // or null
+    const float* norm;                 // or null: {mean, std}
+    const float* stats_in;             // backward: the forward's stats
+    const float* grad_loss;            // backward, or null (= 1.0f)
+    float* grad_logits;                // backward, written only where GL
+    float* grad_values;                // backward, written only where GV
+    double* partials;                  // forward: [6][B]
+    float* stats;                      // forward
+    float lo, hi, vf_coef, ent_coef, adv_eps;
+    long long M, B;
+};
+
+struct MomentArgs {
+    const float* x;
+    const uint8_t* valid;              // or null
+    double* partials;                  // [3][B]
+    float* out;
+    long long M, B;
+};
+
+// a group of the tree: for o = 32 .. 1 every lane takes s + (lane ^ o)'s s; f64 addition commutes, so all lanes agree
+__device__ __forceinline__ double halve_wave(double s) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s = s + __shfl_xor(s, o, 64);
+    return s;
+}
+
+template <bool MASK>
+__global__ __launch_bounds__(256) void ppo_partial_kernel(const PpoArgs A) {
+    __shared__ float4 pieces[ccx_ppo::kBlockGroups][80];
+    __shared__ double groups[ccx_ppo::kSums][ccx_ppo::kBlockGroups];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const long long wave = (long long)blockIdx.x * ccx_ppo::kBlockGroups + w;
+    const long long row = wave * 64 + lane;
+    const long long rl = row < A.M ? row : A.M - 1;                     // surplus lanes load what the last row loads
+    const uint32_t a = A.actions[rl];
+    const uint32_t mbyte = MASK ? (uint32_t)A.masks[rl] : 0x1Fu;
+    const bool has_valid = A.valid != nullptr, has_norm = A.norm != nullptr;
+    const uint32_t vbyte = has_valid ? (uint32_t)A.valid[rl] : 1u;
+    const float lpo = A.logp_old[rl], adv = A.advantages[rl], ret = A.returns[rl], val = A.values[rl];
+    float mean = 0.0f, denom = 1.0f;
+    if (has_norm) {
+        mean = A.norm[0];
+        denom = A.norm[1] + A.adv_eps;
+    }
+    const long long floats = A.M * 5, last_piece = floats / 4 - 1;      // M >= 1: at least one whole piece
+    float l[5];
+    ccx_rows::load_rows(A.logits, A.M, pieces[w], lane, wave, row, floats, last_piece, l);
+    const bool counts = row < A.M && ccx_ppo::row_counts(has_valid, vbyte, a);
+    const float an = ccx_ppo::normalised(has_norm, adv, mean, denom);
+    ccx_ppo::Row t;
+    ccx_ppo::forward_row(l, mbyte, a, lpo, an, ret, val, A.lo, A.hi, t);
+    // rows that do not count and rows >= M enter as +0.0, selected
+    double s[ccx_ppo::kSums] = {counts ? 1.0 : 0.0,           counts ? (double)t.surr : 0.0, counts ? (double)t.vl : 0.0,
+                                counts ? (double)t.H : 0.0,   counts ? (double)t.kl : 0.0,   counts ? (double)t.cf : 0.0};
+#pragma unroll
+    for (int q = 0; q < ccx_ppo::kSums; ++q) {
+        s[q] = halve_wave(s[q]);
+        if (lane == 0u) groups[q][w] = s[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)ccx_ppo::kSums) {
+        const uint32_t q = threadIdx.x;
+        A.partials[(long long)q * A.B + blockIdx.x] = ccx_ppo::block_partial(groups[q][0], groups[q][1], groups[q][2], groups[q][3]);
+    }
+}
+
+__global__ __launch_bounds__(64) void ppo_final_kernel(const PpoArgs A) {
+    const int lane = (int)threadIdx.x;
+    double s[ccx_ppo::kSums];
+    ccx_ppo::strided_partials(A.partials, A.B, lane, s);
+#pragma unroll
+    for (int q = 0; q < ccx_ppo::kSums; ++q) s[q] = halve_wave(s[q]);
+    if (lane == 0) {
+        float st[8];
+        ccx_ppo::loss_finals(s, A.vf_coef, A.ent_coef, st);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) A.stats[k] = st[k];
+    }
+}
+
+template <bool MASK, bool GL, bool GV>
+__global__ __launch_bounds__(64) void ppo_bwd_kernel(const PpoArgs A) {
+    __shared__ float4 pieces[GL ? 80 : 1];
+    const uint32_t lane = threadIdx.x;
+    const long long row = (long long)blockIdx.x * 64 + lane;
+    const long long rl = row < A.M ? row : A.M - 1;
+    const uint32_t a = A.actions[rl];
+    const bool has_valid = A.valid != nullptr;
+    const uint32_t vbyte = has_valid ? (uint32_t)A.valid[rl] : 1u;
+    const float ret = A.returns[rl], val = A.values[rl];
+    const float n = A.stats_in[6];
+    const float g = A.grad_loss ? A.grad_loss[0] : 1.0f;
+    const float sc = g / n;
+    const bool counts = n != 0.0f && ccx_ppo::row_counts(has_valid, vbyte, a);      // n == 0: every gradient +0.0f, selected
+    if constexpr (GL) {
+        const uint32_t mbyte = MASK ? (uint32_t)A.masks[rl] : 0x1Fu;
+        const bool has_norm = A.norm != nullptr;
+        const float lpo = A.logp_old[rl], adv = A.advantages[rl];
+        float mean = 0.0f, denom = 1.0f;
+        if (has_norm) {
+            mean = A.norm[0];
+            denom = A.norm[1] + A.adv_eps;
+        }
+        const float se = sc * A.ent_coef;
+        const float gent = 0.0f - se;
+        const long long floats = A.M * 5, last_piece = floats / 4 - 1;
+        float l[5], gr[5];
+        ccx_rows::load_rows(A.logits, A.M, pieces, lane, blockIdx.x, row, floats, last_piece, l);
+        const float an = ccx_ppo::normalised(has_norm, adv, mean, denom);
+        ccx_ppo::backward_row_logits(l, mbyte, a, lpo, an, ret, val, A.lo, A.hi, sc, gent, gr);
+#pragma unroll
+        for (int k = 0; k < 5; ++k) gr[k] = counts ? gr[k] : 0.0f;
+        ccx_rows::store_rows(A.grad_logits, A.M, pieces, lane, blockIdx.x, row, floats, last_piece, gr);
+    }
+    if constexpr (GV) {
+        const float scv = sc * A.vf_coef;
+        const float gv = ccx_ppo::backward_row_value(ret, val, scv);
+        if (row < A.M) A.grad_values[row] = counts ? gv : 0.0f;
+    }
+}
+
+__global__ __launch_bounds__(256) void moments_partial_kernel(const MomentArgs A) {
+    __shared__ double groups[ccx_ppo::kMomentSums][ccx_ppo::kBlockGroups];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const long long row = (long long)blockIdx.x * ccx_ppo::kBlockRows + threadIdx.x;
+    const long long rl = row < A.M ? row : A.M - 1;
+    const bool counts = row < A.M && (A.valid == nullptr || A.valid[rl] != 0);
+    const double x = (double)A.x[rl];                                   // exact
+    const double xx = x * x;                                            // exact: 48 significant bits at most
+    double s[ccx_ppo::kMomentSums] = {counts ? 1.0 : 0.0, counts ? x : 0.0, counts ? xx : 0.0};
+#pragma unroll
+    for (int q = 0; q < ccx_ppo::kMomentSums; ++q) {
+        s[q] = halve_wave(s[q]);
+        if (lane == 0u) groups[q][w] = s[q];
+    }
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)ccx_ppo::kMomentSums) {
+        const uint32_t q = threadIdx.x;
+        A.partials[(long long)q * A.B + blockIdx.x] = ccx_ppo::block_partial(groups[q][0], groups[q][1], groups[q][2], groups[q][3]);
+    }
+}
+
+__global__ __launch_bounds__(64) void moments_final_kernel(const MomentArgs A) {
+    const int lane = (int)threadIdx.x;
+    double s[ccx_ppo::kMomentSums];
+    ccx_ppo::strided_partials(A.partials, A.B, lane, s);
+#pragma unroll
+    for (int q = 0; q < ccx_ppo::kMomentSums; ++q) s[q] = halve_wave(s[q]);
+    if (lane == 0) {
+        float o[4];
+        ccx_ppo::moments_finals(s, o);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) A.out[k] = o[k];
+    }
+}
+
+int check_rows(const char* who, int64_t rows, int64_t per_block, unsigned& blocks) {
+    if (rows < 1) return fail(CCX_EINVAL, "%s: rows must be at least 1, got %lld", who, (long long)rows);
+    const int64_t b = (rows + per_block - 1) / per_block;
+    if (b > 0x7FFFFFFFll) return fail(CCX_EINVAL, "%s: %lld rows need more than 2^31 - 1 workgroups", who, (long long)rows);
+    blocks = (unsigned)b;
+    return CCX_OK;
+}
+
+bool finite_nonneg(float v) { return v >= 0.0f && v < __builtin_inff(); }                // (false for NaN)
+
+int check_hyper(const char* who, float clip, float vf_coef, float ent_coef, float adv_eps) {
+    if (!(clip > 0.0f && clip < 1.0f)) return fail(CCX_EINVAL, "%s: clip must lie in (0, 1), got %g", who, (double)clip);
+    if (!finite_nonneg(vf_coef)) return fail(CCX_EINVAL, "%s: vf_coef must be finite and not negative, got %g", who, (double)vf_coef);
+    if (!finite_nonneg(ent_coef)) return fail(CCX_EINVAL, "%s: ent_coef must be finite and not negative, got %g", who, (double)ent_coef);
+    if (!finite_nonneg(adv_eps)) return fail(CCX_EINVAL, "%s: adv_eps must be finite and not negative, got %g", who, (double)adv_eps);
+    return CCX_OK;
+}
+
+void fill_hyper(PpoArgs& A, float clip, float vf_coef, float ent_coef, float adv_eps) {
+    A.lo = 1.0f - clip;                                                 // computed once, one f32 operation each
+    A.hi = 1.0f + clip;
+    A.vf_coef = vf_coef;
+    A.ent_coef = ent_coef;
+    A.adv_eps = adv_eps;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t ccx_ppo_workspace_bytes(int64_t rows) {
+    if (rows < 1) return 0;
+    return (int64_t)ccx_ppo::blocks_of(rows) * ccx_ppo::kSums * (int64_t)sizeof(double);
+}
+
+int ccx_masked_moments(ccx_handle* h, int64_t rows, const float* x, const uint8_t* valid_or_null, void* workspace, float* out) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (!x || !workspace || !out) return fail(CCX_EINVAL, "ccx_masked_moments: NULL argument (x, workspace and out are required)");
+    unsigned blocks = 0;
+    if (int rc = check_rows("ccx_masked_moments", rows, ccx_ppo::kBlockRows, blocks)) return rc;
+    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "ccx_masked_moments: workspace must be 8-byte aligned");
+    CCX_HIP(hipSetDevice(h->device));
+    MomentArgs A{};
+    A.x = x;
+    A.valid = valid_or_null;
+    A.partials = static_cast<double*>(workspace);
+    A.out = out;
+    A.M = rows;
+    A.B = blocks;
+    hipLaunchKernelGGL(moments_partial_kernel, dim3(blocks), dim3(256), 0, h->stream, A);
+    hipLaunchKernelGGL(moments_final_kernel, dim3(1), dim3(64), 0, h->stream, A);
+    CCX_HIP(hipGetLastError());
+    return CCX_OK;
+}
+
+int ccx_ppo_loss(ccx_handle* h, int64_t rows, const float* logits, const uint8_t* actions, const uint8_t* masks_or_null,
+                 const float* logp_old, const float* advantages, const float* returns, const float* values,
+                 const uint8_t* valid_or_null, const float* norm_or_null, float clip, float vf_coef, float ent_coef, float adv_eps,
+                 void* workspace, float* stats) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (!logits || !actions || !logp_old || !advantages || !returns || !values || !workspace || !stats)
+        return fail(CCX_EINVAL, "ccx_ppo_loss: NULL argument (only masks, valid and norm may be NULL)");
+    unsigned blocks = 0;
+    if (int rc = check_rows("ccx_ppo_loss", rows, ccx_ppo::kBlockRows, blocks)) return rc;
+    if (reinterpret_cast<uintptr_t>(logits) & 15u) return fail(CCX_EINVAL, "ccx_ppo_loss: logits must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "ccx_ppo_loss: workspace must be 8-byte aligned");
+    if (int rc = check_hyper("ccx_ppo_loss", clip, vf_coef, ent_coef, adv_eps)) return rc;
+    CCX_HIP(hipSetDevice(h->device));
+    PpoArgs A{};
+    A.logits = logits;
+    A.actions = actions;
+    A.masks = masks_or_null;
+    A.logp_old = logp_old;
+    A.advantages = advantages;
+    A.returns = returns;
+    A.values = values;
+    A.valid = valid_or_null;
+    A.norm = norm_or_null;
+    A.partials = static_cast<double*>(workspace);
+    A.stats = stats;
+    A.M = rows;
+    A.B = blocks;
+    fill_hyper(A, clip, vf_coef, ent_coef, adv_eps);
+    if (masks_or_null) hipLaunchKernelGGL((ppo_partial_kernel<true>), dim3(blocks), dim3(256), 0, h->stream, A);
+    else hipLaunchKernelGGL((ppo_partial_kernel<false>), dim3(blocks), dim3(256), 0, h->stream, A);
+    hipLaunchKernelGGL(ppo_final_kernel, dim3(1), dim3(64), 0, h->stream, A);
+    CCX_HIP(hipGetLastError());
+    return CCX_OK;
+}
+
+int ccx_ppo_loss_backward(ccx_handle* h, int64_t rows, const float* logits, const uint8_t* actions, const uint8_t* masks_or_null,
+                          const float* logp_old, const float* advantages, const float* returns, const float* values,
+                          const uint8_t* valid_or_null, const float* norm_or_null, float clip, float vf_coef, float ent_coef,
+                          float adv_eps, const float* stats, const float* grad_loss_or_null, float* grad_logits_or_null,
+                          float* grad_values_or_null) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (!logits || !actions || !logp_old || !advantages || !returns || !values || !stats)
+        return fail(CCX_EINVAL, "ccx_ppo_loss_backward: NULL argument (only masks, valid, norm, grad_loss and one gradient output may be NULL)");
+    if (!grad_logits_or_null && !grad_values_or_null)
+        return fail(CCX_EINVAL, "ccx_ppo_loss_backward: both gradient outputs are NULL (at least one of grad_logits, grad_values is required)");
+    unsigned blocks = 0;
+    if (int rc = check_rows("ccx_ppo_loss_backward", rows, 64, blocks)) return rc;
+    if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(grad_logits_or_null)) & 15u)
+        return fail(CCX_EINVAL, "ccx_ppo_loss_backward: logits and grad_logits must be 16-byte aligned");
+    if (int rc = check_hyper("ccx_ppo_loss_backward", clip, vf_coef, ent_coef, adv_eps)) return rc;
+    CCX_HIP(hipSetDevice(h->device));
+    PpoArgs A{};
+    A.logits = logits;
+    A.actions = actions;
+    A.masks = masks_or_null;
+    A.logp_old = logp_old;
+    A.advantages = advantages;
+    A.returns = returns;
+    A.values = values;
+    A.valid = valid_or_null;
+    A.norm = norm_or_null;
+    A.stats_in = stats;
+    A.grad_loss = grad_loss_or_null;
+    A.grad_logits = grad_logits_or_null;
+    A.grad_values = grad_values_or_null;
+    A.M = rows;
+    fill_hyper(A, clip, vf_coef, ent_coef, adv_eps);
+    const dim3 grid(blocks), block(64);
+    if (!grad_logits_or_null) hipLaunchKernelGGL((ppo_bwd_kernel<false, false, true>), grid, block, 0, h->stream, A);
+    else if (masks_or_null) {
+        if (grad_values_or_null) hipLaunchKernelGGL((ppo_bwd_kernel<true, true, true>), grid, block, 0, h->stream, A);
+        else hipLaunchKernelGGL((ppo_bwd_kernel<true, true, false>), grid, block, 0, h->stream, A);
+    } else {
+        if (grad_values_or_null) hipLaunchKernelGGL((ppo_bwd_kernel<false, true, true>), grid, block, 0, h->stream, A);
+        else hipLaunchKernelGGL((ppo_bwd_kernel<false, true, false>), grid, block, 0, h->stream, A);
+    }
+    CCX_HIP(hipGetLastError());
+    return CCX_OK;
+}
+
+}  // extern "C"

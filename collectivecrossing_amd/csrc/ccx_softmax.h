@@ -1,6 +1,6 @@
 // ccx_softmax.h -- the masked five-way distribution of CCX_SAMPLE / CCX_EVALUATE (include/ccx.h) as inline functions of one
 // row: exp_spec, log_spec, steps 2-6 of CCX_SAMPLE (legal set, maximum, degenerate, d, w, c, S), its entropy (step 10), and
-// the per-row forward and backward rules of CCX_EVALUATE.  Included by ccx_sample.hip and ccx_evaluate.hip; it also compiles
+// the per-row forward and backward rules of CCX_EVALUATE.  Included by ccx_sample.hip, ccx_evaluate.hip and ccx_ppo.h; it also compiles
 // with a plain host C++ compiler (tests/test_evaluate_host_rule.py runs it against the NumPy specs bit for bit).
 // Every line is ONE f32 operation: the units that include this are compiled with -ffp-contract=off, and `/` must be the
 // correctly rounded division.  What a rule does not read is SELECTED away before any arithmetic, never multiplied by zero.
@@ -20,7 +20,7 @@ constexpr float kLog2e = 0x1.715476p+0f, kLn2Hi = 0x1.62e4p-1f, kLn2Lo = 0x1.7f7
 constexpr float kDMin = -80.0f;
 constexpr uint32_t kActionAbsent = 255u;                                  // CCX_ACTION_ABSENT
 
-// x in [-80, 0]
+// x in [-80, 80] (CCX_SAMPLE / CCX_EVALUATE use [-80, 0], CCX_PPO_LOSS the whole of it)
 CCX_HD float exp_spec(float x) {
     const float n = rintf(x * kLog2e);
     const float r = (x - n * kLn2Hi) - n * kLn2Lo;
@@ -32,7 +32,7 @@ CCX_HD float exp_spec(float x) {
     p = p * r + 0x1p-1f;
     p = p * r + 1.0f;
     p = p * r + 1.0f;
-    return p * __builtin_bit_cast(float, ((int)n + 127) << 23);           // exact: n >= -116, the product is a normal number
+    return p * __builtin_bit_cast(float, ((int)n + 127) << 23);           // exact: |n| <= 116, the product is a normal number
 }
 
 // s in [1, 5]

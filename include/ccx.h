@@ -618,12 +618,12 @@ int ccx_gae(ccx_handle* h, int32_t num_steps, const double* reward /* [K][E][N] 
  *   9. logp = d_action - log_spec(S).
  *  10. entropy = log_spec(S) - T / S, T = (((t_0 + t_1) + t_2) + t_3) + t_4 with t_k = (w_k == 0) ? +0.0f : w_k * d_k.
  *
- * exp_spec(x), x in [-80, 0]:
+ * exp_spec(x), x in [-80, 0] here and in CCX_EVALUATE, in [-80, 80] in CCX_PPO_LOSS:
  *     n = rint(x * 0x1.715476p+0f)                              (round to nearest even)
  *     r = (x - n * 0x1.62e4p-1f) - n * 0x1.7f7d1cp-20f           (the first product is exact)
  *     p = 0x1.a01a02p-13f;  then p = p * r + C, one multiply and one add each, for C = 0x1.6c16c2p-10f, 0x1.111112p-7f,
  *         0x1.555556p-5f, 0x1.555556p-3f, 0x1p-1f, 0x1p+0f, 0x1p+0f                 (1/7! .. 1/2!, 1, 1)
- *     exp_spec = p * 2^n                                         (exact; n >= -116)
+ *     exp_spec = p * 2^n                                         (exact; |n| <= 116)
  * log_spec(s), s in [1, 5]:
  *     s = m * 2^e with m in [0.5, 1) (exact); if (m < 0x1.6a09e6p-1f) { m = m + m; e = e - 1; }
  *     t = m - 0x1p+0f;  q = t / (0x1p+1f + t);  z = q * q
@@ -698,13 +698,117 @@ int ccx_sample_actions(ccx_handle* h, const float* logits /* [E][N][5] */, const
  * into a HIP graph.  A NULL handle or a NULL required pointer (logits, actions, logp / grad_logits), rows < 1, rows so large
  * that the grid would pass 2^31 - 1 workgroups of 64 rows, logits or grad_logits that are not 16-byte aligned, or both
  * gradients NULL: CCX_EINVAL with a ccx_last_error message.  Offsets are 64-bit (5 M may exceed 2^31).  Not here: bf16 / f16
- * logits (cast first), a temperature (scale the logits first), the PPO loss itself.
+ * logits (cast first), a temperature (scale the logits first).  The PPO loss over these quantities: CCX_PPO_LOSS below.
  */
 int ccx_evaluate_actions(ccx_handle* h, int64_t rows, const float* logits /* [M][5] */, const uint8_t* actions /* [M] */,
                          const uint8_t* masks_or_null /* [M] */, float* logp /* [M] */, float* entropy_or_null /* [M] */);
 int ccx_evaluate_actions_backward(ccx_handle* h, int64_t rows, const float* logits /* [M][5] */, const uint8_t* actions /* [M] */,
                                   const uint8_t* masks_or_null /* [M] */, const float* grad_logp_or_null /* [M] */,
                                   const float* grad_entropy_or_null /* [M] */, float* grad_logits /* [M][5] */);
+/*
+ * CCX_PPO_LOSS: the clipped-surrogate PPO loss over the agent-steps that count, its statistics, and its gradient with respect
+ * to the logits and the values -- the last link of an iteration (ccx_step / ccx_sample_actions / ccx_gae /
+ * ccx_evaluate_actions being the others).  `valid` (ccx_gae's output) is a SELECTION inside the kernels: nothing is
+ * compacted, shapes are static, there is no host synchronisation, and the whole update captures into a HIP graph.  Every
+ * output is bit-defined, the reduction included.
+ *
+ * Pure functions of their arrays: the handle supplies device and stream only.  Rows are flat: M >= 1 rows.  The discipline
+ * is CCX_SAMPLE's: every f32 operation named below is ONE correctly rounded f32 operation (+ - * /), nothing is fused (no
+ * fma), nothing is reassociated, subnormals are kept; every f64 operation named below is likewise ONE correctly rounded f64
+ * operation.  What a rule does not read is selected away, never multiplied by zero.
+ *
+ * Inputs (device pointers): logits f32 [M][5] (16-byte aligned), actions u8 [M], masks u8 [M] or NULL -- CCX_EVALUATE's
+ * three; logp_old f32 [M] (ccx_sample_actions' logp), advantages f32 [M], returns f32 [M] (ccx_gae's), values f32 [M] (the
+ * critic's, under the new weights), valid u8 [M] or NULL, norm f32 [2] = {mean, std} on the device or NULL (elements 1 and 2
+ * of ccx_masked_moments' output), and by value clip in (0, 1), vf_coef >= 0, ent_coef >= 0, adv_eps >= 0 (all finite).
+ *
+ * Which rows count.  For the loss: row i counts iff (valid == NULL || valid[i] != 0) && actions[i] != 255.  For the
+ * moments: iff valid == NULL || valid[i] != 0.  A row that does not count contributes to no sum and gets +0.0f in every
+ * gradient, whatever its logits, values, advantages, logp_old or the incoming gradient hold (NaN included).  A NaN at a
+ * row that counts propagates: that is the caller's data.
+ *
+ * Forward, per row that counts (f32, one operation each), with lo = 1.0f - clip, hi = 1.0f + clip and, where norm is given,
+ * den = norm[1] + adv_eps computed once:
+ *   1. logp, H = CCX_EVALUATE's forward for the row (the same operation sequence: its logp and entropy).
+ *   2. x = logp - logp_old[i];  xc = x < -80.0f ? -80.0f : (x > 80.0f ? 80.0f : x);  ratio = exp_spec(xc)  (a NaN xc is
+ *      passed through as the ratio and never enters exp_spec).  exp_spec is CCX_SAMPLE's, unchanged, on [-80, 80]: the first
+ *      product of its reduction stays exact (|n| <= 115), the result is a normal number, exp_spec(+0.0f) == 1.0f.  On the
+ *      logits an action was sampled from, x is +0.0f and ratio exactly 1.  An illegal stored action (logp = -inf) gives
+ *      xc = -80, not a NaN.
+ *   3. an = norm ? (advantages[i] - norm[0]) / den : advantages[i].
+ *   4. s1 = ratio * an;  rc = ratio < lo ? lo : (ratio > hi ? hi : ratio);  s2 = rc * an;  surr = s2 < s1 ? s2 : s1.
+ *   5. ve = values[i] - returns[i];  vl = ve * ve.
+ *   6. kl = (ratio - 1.0f) - xc;  cf = (ratio < lo || ratio > hi) ? 1.0f : 0.0f.
+ *
+ * Reduction.  Six sums over the rows that count -- 1 (the count n), surr, vl, H, kl, cf -- in f64, each f32 term converted
+ * exactly.  The tree is fixed by M alone (not by the CU count, a launch shape or a tunable); there is no floating-point
+ * atomic:
+ *   - rows are cut into B = ceil(M / 256) blocks of 256 consecutive rows, a block into four groups of 64 consecutive rows;
+ *     rows that do not count and rows >= M enter as +0.0;
+ *   - a group is reduced by halving: for o = 32, 16, 8, 4, 2, 1, at once for all 64 places j: s[j] = s[j] + s[j ^ o].  Every
+ *     place ends with the same bits; G = s[0];
+ *   - a block's partial is ((G0 + G1) + G2) + G3;
+ *   - the final step takes the B partials P of a quantity: place j of 64 starts from +0.0 and adds P[j], P[j + 64], P[j + 128],
+ *     ... in ascending order; the 64 places are then reduced by the same halving.
+ * Final values, all in f64, each output rounded to f32 once (round to nearest even):
+ *     policy = -(S_surr / n);  value = S_vl / n;  entropy = S_H / n
+ *     loss   = (policy + (double)vf_coef * value) - (double)ent_coef * entropy
+ *     stats  = {loss, policy, value, entropy, S_kl / n, S_cf / n, (float)n, +0.0f};   n == 0: all eight are +0.0f
+ * ccx_masked_moments runs the same tree over 1, x and x * x (x converted to f64 exactly, the product exact) and gives, all
+ * in f64 until the one rounding of each output:
+ *     mean = S_x / n;  q = (S_xx - S_x * mean) / (n - 1);  var = q < 0 ? 0 : q;  std = sqrt(var)  (the correctly rounded f64
+ *     square root, taken on the device: tests/test_gpu_ppo_loss.py compares its bits with IEEE sqrt on the host)
+ *     out = {(float)n, (float)mean, (float)std, +0.0f};   n < 2: {(float)n, +0.0f, 1.0f, +0.0f} (no normalisation)
+ * std is the unbiased (Bessel) standard deviation, torch.std's definition.
+ *
+ * Backward: one elementwise pass; nothing is saved but the inputs and stats.  g = grad_loss ? grad_loss[0] : 1.0f;
+ * sc = g / stats[6];  gent = 0.0f - sc * ent_coef;  scv = sc * vf_coef, each computed once.  stats[6] == 0: every gradient is
+ * +0.0f, selected.  For a row that counts, steps 1-5 are recomputed, then
+ *     pass = !(ratio < lo || ratio > hi) || s1 < s2
+ *     glp  = (pass && x == xc) ? 0.0f - sc * s1 : +0.0f       (d(-surr)/d logp = -an ratio = -s1 where the unclipped branch is
+ *                                                              active and the clamp of x is not)
+ *     grad_logits[i][.] = CCX_EVALUATE's backward for the row with grad_logp = glp, grad_entropy = gent: illegal places,
+ *                         degenerate rows and an illegal stored action get exactly +0.0f by that rule
+ *     grad_values[i]    = scv * (ve + ve)
+ * At least one of grad_logits (16-byte aligned) and grad_values is given; a NULL one is not computed.  Every element of
+ * every output given is written.
+ *
+ * Against IEEE f64 (measured on the CPU, tests/test_ppo_loss_spec.py, maxima doubled), as max |err| / max(1, |f64 value|)
+ * against the textbook composition in f64 on the same f32 inputs (masked log-softmax, gather, guarded entropy, exp, clamp,
+ * minimum, means over the rows that count, and their autograd gradients): exp_spec within 2.1e-7 relative on [-80, 80];
+ * loss within 9.9e-8, policy 2.2e-8, value 6.7e-8, entropy 5.0e-8, approx_kl 2.4e-8; grad_values (times n) within 2.6e-7;
+ * grad_logits (times n) within 2.2e-6 over rows with logp >= -10 and within 6.1e-5 over all rows (a stored action far down
+ * the tail has a logp of size 80 and more, whose rounding -- 3.8e-6 absolute and up -- exp(logp - logp_old) turns into a
+ * relative error of that row's gradient; the means average it away); the masked mean within 3.6e-8 and std within 8.3e-8.
+ * The comparison leaves out rows where the two sides legitimately differ (ratio within one ulp of lo / hi, s1 == s2 outside
+ * the range, |x| > 80, logp = -inf, and degenerate rows, which f64 softmax has no answer for): under 10 % of the generator's
+ * counted rows, asserted.
+ *
+ * Launches: ccx_masked_moments and ccx_ppo_loss enqueue TWO kernels each on the handle's stream (block partials, then one
+ * final wave), ccx_ppo_loss_backward ONE.  The final step is a launch of its own, not a last-block-done counter inside the
+ * first: two plain launches cannot hang.  No host synchronisation, no allocation: the caller owns the workspace
+ * (ccx_ppo_workspace_bytes(rows) bytes, 8-byte aligned, enough for either forward call; its contents mean nothing between
+ * calls).  Everything captures into a HIP graph.  Offsets are 64-bit.  A NULL handle or a NULL required pointer, rows < 1 (or
+ * so many that a grid would pass 2^31 - 1 workgroups), logits or grad_logits that are not 16-byte aligned, a workspace that
+ * is not 8-byte aligned, a clip that is not finite or lies outside (0, 1), a negative or non-finite vf_coef, ent_coef or
+ * adv_eps, or both gradient outputs NULL: CCX_EINVAL with a ccx_last_error message, before any launch.
+ * ccx_ppo_workspace_bytes returns 0 for rows < 1.  Not here: value clipping, a KL penalty term, dual clipping, bf16 / f16
+ * inputs, the optimiser, minibatch shuffling (a minibatch is whatever contiguous rows the caller hands in).
+ */
+int64_t ccx_ppo_workspace_bytes(int64_t rows);
+int ccx_masked_moments(ccx_handle* h, int64_t rows, const float* x /* [M] */, const uint8_t* valid_or_null /* [M] */,
+                       void* workspace, float* out /* [4] */);
+int ccx_ppo_loss(ccx_handle* h, int64_t rows, const float* logits /* [M][5] */, const uint8_t* actions /* [M] */,
+                 const uint8_t* masks_or_null /* [M] */, const float* logp_old /* [M] */, const float* advantages /* [M] */,
+                 const float* returns /* [M] */, const float* values /* [M] */, const uint8_t* valid_or_null /* [M] */,
+                 const float* norm_or_null /* [2] */, float clip, float vf_coef, float ent_coef, float adv_eps, void* workspace,
+                 float* stats /* [8] */);
+int ccx_ppo_loss_backward(ccx_handle* h, int64_t rows, const float* logits /* [M][5] */, const uint8_t* actions /* [M] */,
+                          const uint8_t* masks_or_null /* [M] */, const float* logp_old /* [M] */,
+                          const float* advantages /* [M] */, const float* returns /* [M] */, const float* values /* [M] */,
+                          const uint8_t* valid_or_null /* [M] */, const float* norm_or_null /* [2] */, float clip, float vf_coef,
+                          float ent_coef, float adv_eps, const float* stats /* [8] */, const float* grad_loss_or_null /* [1] */,
+                          float* grad_logits_or_null /* [M][5] */, float* grad_values_or_null /* [M] */);
 /*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
