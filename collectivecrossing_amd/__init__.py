@@ -12,7 +12,7 @@ from .configs import CollectiveCrossingConfig  # noqa: F401
 __version__ = "0.4.0"
 __all__ = ["CollectiveCrossingConfig", "CollectiveCrossingEnv", "BatchedCollectiveCrossing", "VectorCollectiveCrossing",
            "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult", "SampleResult", "EvalResult",
-           "PpoLossResult"]
+           "PpoLossResult", "MlpHead"]
 
 
 def __getattr__(name):  # lazy: importing the configs must not pull in torch
@@ -43,6 +43,9 @@ def __getattr__(name):  # lazy: importing the configs must not pull in torch
     if name == "PpoLossResult":
         from .batched import PpoLossResult
         return PpoLossResult
+    if name == "MlpHead":
+        from .batched import MlpHead
+        return MlpHead
     raise AttributeError(name)
 
 

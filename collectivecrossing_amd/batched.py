@@ -776,6 +776,58 @@ class BatchedCollectiveCrossing:
                                            _ptr(out.logp), _ptr(out.entropy)))
         return out
 
+    # ------------------------------------------------------------------ the policy head: observation rows to logits
+    def mlp_head(self, H: int, O: int = 5, activation: str = "tanh", L: int | None = None) -> "MlpHead":
+        """A two-layer perceptron ``Linear(L, H) -> tanh | relu -> Linear(H, O)`` whose forward is ONE kernel with bit-defined
+        outputs (:class:`MlpHead`, include/ccx.h CCX_MLP).  ``L`` defaults to ``obs_len``; ``H`` is a multiple of 16 in
+        16..256, ``O`` in 1..8.  ``O = 5`` is an actor for :meth:`mlp_sample_actions`, ``O = 1`` a critic."""
+        return MlpHead(self, H, O, activation, L)
+
+    def _mlp_forward(self, head: "MlpHead", x: torch.Tensor, y: torch.Tensor, hidden: torch.Tensor | None) -> None:
+        self._order_after_current_stream(x, head.w1t, head.b1, head.w2, head.b2, y, hidden)
+        check(self._lib.ccx_mlp_forward(self._h, x.numel() // head.L, head.L, head.H, head.O, head.activation_id, _ptr(x),
+                                        _ptr(head.w1t), _ptr(head.b1), _ptr(head.w2), _ptr(head.b2), _ptr(y), _ptr(hidden)))
+
+    def mlp_sample_actions(self, head: "MlpHead", obs: torch.Tensor, masks: torch.Tensor | None = None,
+                           deterministic: bool = False, want_logp: bool = True, want_entropy: bool = False,
+                           logits_out: torch.Tensor | None = None, out: SampleResult | None = None) -> SampleResult:
+        """Observation rows to actions in ONE launch (``ccx_mlp_sample_actions``): by definition
+        ``sample_actions(head(obs), ...)`` -- the same key, the same rule for terminated or truncated agents, the same bits
+        in ``actions``, ``logp`` and ``entropy`` -- without the logits' round trip through memory and without the second
+        launch.  ``head`` is an :class:`MlpHead` with ``O == 5`` and ``L == obs_len``; ``obs`` f32 [E, N, L] (contiguous,
+        16-byte aligned: the ``obs`` of :meth:`step` / :meth:`rollout`); ``logits_out`` f32 [E, N, 5] receives the logits of
+        every slot, dead ones included.  ``masks``, ``deterministic``, ``want_*`` and ``out`` are :meth:`sample_actions`'.
+        No gradient flows through this call (the update re-evaluates stored rows with ``head(rows)``).  Anything else than
+        the tensors described raises ``ValueError`` before the library is called.  Only enqueues."""
+        E, N = self.num_envs, self.num_agents
+        if not isinstance(head, MlpHead) or head.batch is not self:
+            raise ValueError("head must be an MlpHead of this batch (mlp_head)")
+        if head.O != 5 or head.L != self.obs_len:
+            raise ValueError(f"mlp_sample_actions needs a head with O == 5 and L == obs_len == {self.obs_len}, got O = {head.O}, L = {head.L}")
+        head._check_parameters()
+        if out is None:
+            out = self.alloc_sample(want_logp, want_entropy)
+        elif not isinstance(out, SampleResult):
+            raise ValueError("out must be a SampleResult (alloc_sample)")
+        for name, t, dt, shape, optional in (
+                ("obs", obs, torch.float32, (E, N, self.obs_len), False), ("masks", masks, torch.uint8, (E, N), True),
+                ("logits_out", logits_out, torch.float32, (E, N, 5), True),
+                ("out.actions", out.actions, torch.uint8, (E, N), False), ("out.logp", out.logp, torch.float32, (E, N), True),
+                ("out.entropy", out.entropy, torch.float32, (E, N), True)):
+            if t is None and optional:
+                continue
+            if (not isinstance(t, torch.Tensor) or t.dtype is not dt or t.device != self.device or tuple(t.shape) != shape
+                    or not t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
+        if obs.data_ptr() % 16:
+            raise ValueError("obs must be 16-byte aligned (a view at an odd offset of its storage is not)")
+        self._order_after_current_stream(obs, head.w1t, head.b1, head.w2, head.b2, masks, logits_out, out.actions, out.logp,
+                                         out.entropy)
+        check(self._lib.ccx_mlp_sample_actions(self._h, head.H, head.activation_id, _ptr(obs), _ptr(head.w1t), _ptr(head.b1),
+                                               _ptr(head.w2), _ptr(head.b2), _ptr(masks), int(bool(deterministic)),
+                                               _ptr(out.actions), _ptr(out.logp), _ptr(out.entropy), _ptr(logits_out)))
+        return out
+
     # ------------------------------------------------------------------ stored actions under new logits
     def alloc_evaluate(self, shape, want_entropy: bool = True) -> EvalResult:
         """Output tensors of :meth:`evaluate_actions` for rows of the leading shape ``shape`` (static buffers for a
@@ -1789,3 +1841,139 @@ class _PpoLoss(torch.autograd.Function):
                                              *ctx.hyper, stats=stats, grad_loss=grad_stats.contiguous(),
                                              want_logits_grad=want_l, want_values_grad=want_v)
         return (None, gl, gv) + (None,) * 8
+
+
+MLP_ACTIVATIONS = {"tanh": 0, "relu": 1}
+
+
+class MlpHead(torch.nn.Module):
+    """``Linear(L, H) -> tanh | relu -> Linear(H, O)`` on the batch's device, forward in ONE kernel on the handle's stream
+    (``ccx_mlp_forward``, include/ccx.h CCX_MLP).  The outputs of a row are a fixed sequence of f32 operations on that row:
+    they do not depend on how many rows the call holds or where the row sits, so ``head(rows)`` on a ``[K, E, N, L]``
+    minibatch reproduces, bit for bit, the logits :meth:`BatchedCollectiveCrossing.mlp_sample_actions` drew an action from.
+
+    The parameters are stored in the kernel's layout -- ``w1t`` [L, H] (the first layer INPUT-major:
+    ``Linear(L, H).weight.t()``), ``b1`` [H], ``w2`` [O, H], ``b2`` [O] -- so an optimiser updates what the kernel reads and
+    no packing launch sits in the loop.  They are initialised as ``torch.nn.Linear`` initialises (the two layers drawn in
+    order from torch's generator); :meth:`from_linear` and :meth:`to_sequential` convert by exact copies.
+
+    ``head(x, out=None)``: ``x`` f32 [..., L], contiguous, 16-byte aligned, on the batch's device; returns f32 [..., O].
+    Without grad this is the one launch, and ``out=`` reuses a tensor (static buffers for a captured graph).  When grad mode
+    is on and a parameter or ``x`` requires a gradient, the call is a ``torch.autograd.Function``: the forward is the same
+    kernel -- the same bits -- with the hidden activations saved, ``out=`` is refused, and the backward is a torch
+    composition on those activations (matrix products and sums in ordinary f32: correct to rounding, NOT bit-defined).
+    Anything else than the tensors described raises ``ValueError`` before the library is called; zero rows return an empty
+    tensor without calling it."""
+
+    def __init__(self, batch: BatchedCollectiveCrossing, H: int, O: int = 5, activation: str = "tanh", L: int | None = None):
+        super().__init__()
+        L = batch.obs_len if L is None else L
+        for name, v, lo, hi in (("L", L, 1, 512), ("H", H, 16, 256), ("O", O, 1, 8)):
+            if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
+                raise ValueError(f"{name} must be an int in {lo}..{hi}, got {v!r}")
+        if H % 16:
+            raise ValueError(f"H must be a multiple of 16, got {H}")
+        if activation not in MLP_ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(MLP_ACTIVATIONS)}, got {activation!r}")
+        object.__setattr__(self, "batch", batch)                          # (not a submodule, not part of the state dict)
+        self.L, self.H, self.O, self.activation = L, H, O, activation
+        self.activation_id = MLP_ACTIVATIONS[activation]
+        lin1, lin2 = torch.nn.Linear(L, H), torch.nn.Linear(H, O)
+        dev = batch.device
+        self.w1t = torch.nn.Parameter(lin1.weight.detach().t().contiguous().to(dev))
+        self.b1 = torch.nn.Parameter(lin1.bias.detach().clone().to(dev))
+        self.w2 = torch.nn.Parameter(lin2.weight.detach().clone().to(dev))
+        self.b2 = torch.nn.Parameter(lin2.bias.detach().clone().to(dev))
+
+    @classmethod
+    def from_linear(cls, batch: BatchedCollectiveCrossing, lin1: torch.nn.Linear, lin2: torch.nn.Linear,
+                    activation: str = "tanh") -> "MlpHead":
+        """The head that computes ``lin2(act(lin1(x)))``: exact copies of the two layers' f32 parameters."""
+        if (not isinstance(lin1, torch.nn.Linear) or not isinstance(lin2, torch.nn.Linear) or lin1.bias is None
+                or lin2.bias is None or lin1.out_features != lin2.in_features or lin1.weight.dtype is not torch.float32
+                or lin2.weight.dtype is not torch.float32):
+            raise ValueError("from_linear needs two f32 torch.nn.Linear layers with biases, lin1.out_features == lin2.in_features")
+        head = cls(batch, lin1.out_features, lin2.out_features, activation, lin1.in_features)
+        with torch.no_grad():
+            head.w1t.copy_(lin1.weight.t())
+            head.b1.copy_(lin1.bias)
+            head.w2.copy_(lin2.weight)
+            head.b2.copy_(lin2.bias)
+        return head
+
+    def to_sequential(self, dtype: torch.dtype = torch.float32) -> torch.nn.Sequential:
+        """``Sequential(Linear(L, H), Tanh | ReLU, Linear(H, O))`` with exact copies of the parameters (cast to ``dtype``)."""
+        lin1 = torch.nn.Linear(self.L, self.H, device=self.w1t.device, dtype=dtype)
+        lin2 = torch.nn.Linear(self.H, self.O, device=self.w1t.device, dtype=dtype)
+        with torch.no_grad():
+            lin1.weight.copy_(self.w1t.t())
+            lin1.bias.copy_(self.b1)
+            lin2.weight.copy_(self.w2)
+            lin2.bias.copy_(self.b2)
+        return torch.nn.Sequential(lin1, torch.nn.Tanh() if self.activation == "tanh" else torch.nn.ReLU(), lin2)
+
+    def extra_repr(self) -> str:
+        return f"L={self.L}, H={self.H}, O={self.O}, activation={self.activation}"
+
+    def _check_parameters(self) -> None:
+        for name, shape in (("w1t", (self.L, self.H)), ("b1", (self.H,)), ("w2", (self.O, self.H)), ("b2", (self.O,))):
+            t = getattr(self, name)
+            if (t.dtype is not torch.float32 or t.device != self.batch.device or tuple(t.shape) != shape or not t.is_contiguous()):
+                raise ValueError(f"{name} must stay a contiguous torch.float32 tensor of shape {shape} on {self.batch.device}")
+
+    def forward(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        b = self.batch
+        if (not isinstance(x, torch.Tensor) or x.dtype is not torch.float32 or x.device != b.device or x.dim() < 1
+                or x.shape[-1] != self.L or not x.is_contiguous()):
+            raise ValueError(f"x must be a contiguous torch.float32 tensor of shape [..., {self.L}] on {b.device}")
+        if x.data_ptr() % 16:
+            raise ValueError("x must be 16-byte aligned (a view at an odd offset of its storage is not)")
+        self._check_parameters()
+        shape = tuple(x.shape[:-1]) + (self.O,)
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            if out is not None:
+                raise ValueError("out= cannot be used when a gradient is required (the autograd path allocates its outputs)")
+            if x.numel() == 0:
+                return x.new_zeros(shape) + self.b2 * 0.0
+            return _MlpForward.apply(self, x, self.w1t, self.b1, self.w2, self.b2)
+        if out is None:
+            out = b._new(shape, torch.float32)
+        elif (not isinstance(out, torch.Tensor) or out.dtype is not torch.float32 or out.device != b.device
+              or tuple(out.shape) != shape or not out.is_contiguous()):
+            raise ValueError(f"out must be a contiguous torch.float32 tensor of shape {shape} on {b.device}")
+        if x.numel():
+            b._mlp_forward(self, x.detach(), out, None)
+        return out
+
+
+class _MlpForward(torch.autograd.Function):
+    """:class:`MlpHead` when a gradient is required: the forward is the kernel of CCX_MLP with the activations saved; the
+    backward is ordinary f32 torch on them (not bit-defined)."""
+
+    @staticmethod
+    def forward(ctx, head, x, w1t, b1, w2, b2):
+        x = x.detach()
+        b = head.batch
+        y = b._new(tuple(x.shape[:-1]) + (head.O,), torch.float32)
+        hidden = b._new(tuple(x.shape[:-1]) + (head.H,), torch.float32)
+        b._mlp_forward(head, x, y, hidden)
+        b._current_stream_waits()
+        ctx.relu = head.activation == "relu"
+        ctx.save_for_backward(x, w1t.detach(), w2.detach(), hidden)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gy):
+        x, w1t, w2, hidden = ctx.saved_tensors
+        L, H, O = x.shape[-1], hidden.shape[-1], gy.shape[-1]
+        gy, h, x2 = gy.contiguous().reshape(-1, O), hidden.reshape(-1, H), x.reshape(-1, L)
+        gh = gy @ w2
+        ga = gh * (h > 0) if ctx.relu else gh * (1.0 - h * h)
+        need = ctx.needs_input_grad
+        gx = (ga @ w1t.t()).reshape(x.shape) if need[1] else None
+        gw1t = x2.t() @ ga if need[2] else None
+        gb1 = ga.sum(0) if need[3] else None
+        gw2 = gy.t() @ h if need[4] else None
+        gb2 = gy.sum(0) if need[5] else None
+        return None, gx, gw1t, gb1, gw2, gb2

@@ -11,8 +11,8 @@
 // pieces repeat the last valid ones), so all of a lane's loads are in flight before its first wait.  5 E N floats need not
 // be a multiple of 4: the up to three floats behind the last whole piece belong to the array's last slot, whose lane
 // fetches them as dwords.  logits must be 16-byte aligned.
-// Arithmetic.  exp_spec / log_spec and steps 2-6 are ccx_softmax.h's (shared with ccx_evaluate.hip): the header's sequences,
-// one f32 operation per line (-ffp-contract=off; `/` is the correctly rounded division, asked for on this unit's compile
+// Arithmetic.  exp_spec / log_spec, steps 2-6 and the rule of one live slot (sample_slot) are ccx_softmax.h's (shared with
+// ccx_evaluate.hip and ccx_mlp.hip): the header's sequences, one f32 operation per line (-ffp-contract=off; `/` is the correctly rounded division, asked for on this unit's compile
 // line).  Everything the rule does not read is SELECTED away before any arithmetic: a NaN at an illegal place or in a dead
 // slot never reaches a result.
 #include "ccx_internal.h"
@@ -22,6 +22,7 @@ using ccxi::fail;
 using ccx_softmax::entropy_spec;
 using ccx_softmax::legal_max_d;
 using ccx_softmax::log_spec;
+using ccx_softmax::sample_slot;
 using ccx_softmax::weights;
 
 namespace {
@@ -40,43 +41,6 @@ struct SampleArgs {
     int32_t E;
     uint32_t N, genv0, seed_lo, seed_hi;   // genv0: low word of env_offset; seed_hi already carries kSampleStream
 };
-
-// The rule of one live slot (steps 2-10 of the header paragraph) from its five logits, its legal set m and its draw u.
-// Host and device: the same source can be run on the CPU against tests/_sample_spec.py.
-template <bool DET, bool STATS>
-__host__ __device__ __forceinline__ void sample_slot(float (&l)[5], uint32_t m, uint32_t u, bool want_logp, bool want_entropy,
-                                                     uint32_t& action, float& logp, float& entropy) {
-    bool legal[5], degenerate;
-    float mx, d[5];
-    legal_max_d(l, m, legal, mx, degenerate, d);
-    action = 4u;
-    float S = 1.0f, w[5];
-    if (DET) {
-#pragma unroll
-        for (int k = 4; k >= 0; --k) action = (legal[k] && (degenerate || l[k] == mx)) ? (uint32_t)k : action;
-    }
-    if (!DET || STATS) {
-        float c[5];
-        S = weights(legal, d, w, c);
-        if (!DET) {
-            const float thr = ((float)(u >> 8) * 0x1p-24f) * S;
-#pragma unroll
-            for (int k = 4; k >= 0; --k) action = (legal[k] && c[k] > thr) ? (uint32_t)k : action;
-        }
-    }
-    if (STATS) {
-        const float ls = log_spec(S);
-        if (want_logp) {
-            float da = d[4];
-#pragma unroll
-            for (int k = 3; k >= 0; --k) da = action == (uint32_t)k ? d[k] : da;
-            logp = da - ls;
-        }
-        if (want_entropy) {
-            entropy = entropy_spec(w, d, S, ls);
-        }
-    }
-}
 
 template <bool MASK, bool DET, bool STATS>
 __global__ __launch_bounds__(64) void sample_kernel(const SampleArgs A) {

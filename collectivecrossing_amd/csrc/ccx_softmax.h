@@ -1,5 +1,6 @@
 // ccx_softmax.h -- the masked five-way distribution of CCX_SAMPLE / CCX_EVALUATE (include/ccx.h) as inline functions of one
-// row: exp_spec, log_spec, steps 2-6 of CCX_SAMPLE (legal set, maximum, degenerate, d, w, c, S), its entropy (step 10), and
+// row: exp_spec, log_spec, steps 2-6 of CCX_SAMPLE (legal set, maximum, degenerate, d, w, c, S), its entropy (step 10), the rule
+// of one live slot (sample_slot, steps 2-10: shared by ccx_sample.hip and the fused kernel of ccx_mlp.hip), and
 // the per-row forward and backward rules of CCX_EVALUATE.  Included by ccx_sample.hip, ccx_evaluate.hip and ccx_ppo.h; it also compiles
 // with a plain host C++ compiler (tests/test_evaluate_host_rule.py runs it against the NumPy specs bit for bit).
 // Every line is ONE f32 operation: the units that include this are compiled with -ffp-contract=off, and `/` must be the
@@ -94,6 +95,43 @@ CCX_HD float entropy_spec(const float (&w)[5], const float (&d)[5], float S, flo
         T = k ? T + term : term;
     }
     return ls - T / S;
+}
+
+// The rule of one live slot (steps 2-10 of the header paragraph) from its five logits, its legal set m and its draw u.
+// Shared by ccx_sample.hip and the fused kernel of ccx_mlp.hip.
+template <bool DET, bool STATS>
+CCX_HD void sample_slot(float (&l)[5], uint32_t m, uint32_t u, bool want_logp, bool want_entropy,
+                        uint32_t& action, float& logp, float& entropy) {
+    bool legal[5], degenerate;
+    float mx, d[5];
+    legal_max_d(l, m, legal, mx, degenerate, d);
+    action = 4u;
+    float S = 1.0f, w[5];
+    if (DET) {
+#pragma unroll
+        for (int k = 4; k >= 0; --k) action = (legal[k] && (degenerate || l[k] == mx)) ? (uint32_t)k : action;
+    }
+    if (!DET || STATS) {
+        float c[5];
+        S = weights(legal, d, w, c);
+        if (!DET) {
+            const float thr = ((float)(u >> 8) * 0x1p-24f) * S;
+#pragma unroll
+            for (int k = 4; k >= 0; --k) action = (legal[k] && c[k] > thr) ? (uint32_t)k : action;
+        }
+    }
+    if (STATS) {
+        const float ls = log_spec(S);
+        if (want_logp) {
+            float da = d[4];
+#pragma unroll
+            for (int k = 3; k >= 0; --k) da = action == (uint32_t)k ? d[k] : da;
+            logp = da - ls;
+        }
+        if (want_entropy) {
+            entropy = entropy_spec(w, d, S, ls);
+        }
+    }
 }
 
 // CCX_EVALUATE, forward, one row: its five logits (changed: illegal ones become -inf), its mask byte and its stored action.

@@ -810,6 +810,58 @@ int ccx_ppo_loss_backward(ccx_handle* h, int64_t rows, const float* logits /* [M
                           float ent_coef, float adv_eps, const float* stats /* [8] */, const float* grad_loss_or_null /* [1] */,
                           float* grad_logits_or_null /* [M][5] */, float* grad_values_or_null /* [M] */);
 /*
+ * CCX_MLP: the network between the observation rows and the logits -- a two-layer perceptron whose forward is a fixed
+ * sequence of f32 operations per row.  The logits of a row depend on (L, H, O, activation), the row and the parameters only:
+ * never on the number of rows, the row's index, the launch shape or the entry point.  So the logits an action was sampled
+ * from are reproduced bit for bit by a later call on any batch that holds the row, and the ratio of CCX_EVALUATE on them is
+ * exactly 1 for minibatches of any shape.  Every output is bit-defined.
+ *
+ * A pure function of its arrays (ccx_mlp_forward never reads the env state).  Inputs (device pointers), per row: x f32 [L];
+ * shared: w1t f32 [L][H], the first layer INPUT-major (torch.nn.Linear(L, H).weight.t().contiguous(): for one k the H
+ * weights are contiguous), b1 f32 [H], w2 f32 [O][H] (torch's layout), b2 f32 [O].  Limits: 1 <= L <= 512, H a multiple of
+ * 16 with 16 <= H <= 256, 1 <= O <= 8, activation 0 = tanh, 1 = relu.  Outputs: y f32 [rows][O], hidden f32 [rows][H] or
+ * NULL (the activations, for a backward pass); every element of every output given is written.
+ *
+ * All arithmetic follows the discipline of CCX_SAMPLE: IEEE binary32, every operation named below is ONE correctly rounded
+ * f32 operation (+ - * /), nothing is fused (no fma), nothing is reassociated, subnormals are kept.  For every row on its own:
+ *   1. layer 1, for every hidden unit j: a = b1[j]; for k = 0 .. L-1 in this order: a = a + x[k] * w1t[k][j]  (one multiply,
+ *      one add).
+ *   2. activation, h[j] = act(a):
+ *        relu(a)      = (a < 0) ? +0.0f : a                       (NaN stays NaN, -0.0f stays -0.0f)
+ *        tanh_spec(a) : m = (|a| < 40.0f) ? |a| : 40.0f
+ *                       t = exp_spec(-(m + m))                     (CCX_SAMPLE's exp_spec, on its own domain [-80, 0])
+ *                       r = (1.0f - t) / (1.0f + t)                (one subtraction, one addition, one division)
+ *                       tanh_spec = (a != a) ? a : copysign(r, a)  (a select: a NaN pre-activation reaches the logits, where
+ *                                                                  CCX_SAMPLE's degenerate-row rule takes over)
+ *      tanh_spec(+-0.0f) = +-0.0f, and tanh_spec(a) = +-1.0f exactly from |a| = 8.67 on.  A NaN that an operation produces or
+ *      passes on is a NaN in the outputs; its sign and payload are not defined (IEEE 754 leaves them to the implementation).
+ *   3. layer 2.  The hidden units form G = H / 16 groups of 16 consecutive units.  For output o, the partial of group g is
+ *      p_g = h[16g] * w2[o][16g]; then for i = 1 .. 15 in order p_g = p_g + h[16g + i] * w2[o][16g + i].  Then y[o] = b2[o];
+ *      for g = 0 .. G-1 in order y[o] = y[o] + p_g.  (The groups exist so that an implementation may give the hidden units of
+ *      one row to several lanes or waves and still have exactly one defined order.)
+ * Against IEEE f64 (measured on the CPU, tests/test_mlp_spec.py, maxima doubled): tanh_spec within 1.9e-7 absolute of
+ * tanh; the logits of L = 38, H = 64, O = 5 with torch.nn.Linear's initial weights on observation-like rows within
+ * 1.5e-6 absolute of the f64 composition on the same f32 inputs.
+ *
+ * ccx_mlp_forward only enqueues ONE kernel on the handle's stream: no host synchronisation, no allocation, and it captures
+ * into a HIP graph.  ccx_mlp_sample_actions is by definition ccx_sample_actions applied to what ccx_mlp_forward with
+ * L = ccx_obs_len(N), O = 5 writes for the same obs [E][N][L] -- the same key, the same stream constant, the same rule for
+ * terminated or truncated slots (255 / +0.0f / +0.0f), the same bits -- in ONE kernel; logits_or_null receives those logits
+ * for every slot, dead ones included.  A NULL handle or a NULL required pointer (everything but hidden, masks, logp, entropy,
+ * logits_or_null), rows < 1, rows beyond 2^31 - 1 workgroups of 64 rows, a size outside the limits, x / obs or hidden not
+ * 16-byte aligned, or any other f32 array not 4-byte aligned: CCX_EINVAL with a ccx_last_error message, before any launch.
+ * Offsets are 64-bit.  Not here: deeper or wider networks, bf16 / f16, a bit-defined backward pass (the Python layer's is
+ * ordinary f32 torch on the saved activations).
+ */
+int ccx_mlp_forward(ccx_handle* h, int64_t rows, int32_t L, int32_t H, int32_t O, int32_t activation, const float* x /* [rows][L] */,
+                    const float* w1t /* [L][H] */, const float* b1 /* [H] */, const float* w2 /* [O][H] */, const float* b2 /* [O] */,
+                    float* y /* [rows][O] */, float* hidden_or_null /* [rows][H] */);
+int ccx_mlp_sample_actions(ccx_handle* h, int32_t H, int32_t activation, const float* obs /* [E][N][ccx_obs_len(N)] */,
+                           const float* w1t /* [L][H] */, const float* b1 /* [H] */, const float* w2 /* [5][H] */,
+                           const float* b2 /* [5] */, const uint8_t* masks_or_null /* [E][N] */, int32_t deterministic,
+                           uint8_t* actions /* [E][N] */, float* logp_or_null /* [E][N] */, float* entropy_or_null /* [E][N] */,
+                           float* logits_or_null /* [E][N][5] */);
+/*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
  * `rng_seed` of ccx_rollout).  The action of agent slot a of global env g at step t (0-based) of its episode j is
