@@ -15,38 +15,16 @@ __all__ = ["CollectiveCrossingConfig", "CollectiveCrossingEnv", "BatchedCollecti
            "PpoLossResult", "MlpHead"]
 
 
+_LAZY = {"CollectiveCrossingEnv": "env", "BatchedCollectiveCrossing": "batched", "VectorCollectiveCrossing": "vector",
+         "BatchedMultiAgentEnv": "rllib", "unpack_action_masks": "batched", "GaeResult": "learner", "SampleResult": "learner",
+         "EvalResult": "learner", "PpoLossResult": "learner", "MlpHead": "learner"}
+
+
 def __getattr__(name):  # lazy: importing the configs must not pull in torch
-    if name == "CollectiveCrossingEnv":
-        from .env import CollectiveCrossingEnv
-        return CollectiveCrossingEnv
-    if name == "BatchedCollectiveCrossing":
-        from .batched import BatchedCollectiveCrossing
-        return BatchedCollectiveCrossing
-    if name == "VectorCollectiveCrossing":
-        from .vector import VectorCollectiveCrossing
-        return VectorCollectiveCrossing
-    if name == "BatchedMultiAgentEnv":
-        from .rllib import BatchedMultiAgentEnv
-        return BatchedMultiAgentEnv
-    if name == "unpack_action_masks":
-        from .batched import unpack_action_masks
-        return unpack_action_masks
-    if name == "GaeResult":
-        from .batched import GaeResult
-        return GaeResult
-    if name == "SampleResult":
-        from .batched import SampleResult
-        return SampleResult
-    if name == "EvalResult":
-        from .batched import EvalResult
-        return EvalResult
-    if name == "PpoLossResult":
-        from .batched import PpoLossResult
-        return PpoLossResult
-    if name == "MlpHead":
-        from .batched import MlpHead
-        return MlpHead
-    raise AttributeError(name)
+    if name not in _LAZY:
+        raise AttributeError(name)
+    from importlib import import_module
+    return getattr(import_module("." + _LAZY[name], __name__), name)
 
 
 def _register_with_gymnasium() -> None:

@@ -25,6 +25,8 @@ import torch
 from . import _abi
 from ._lib import check, load
 from .configs import CollectiveCrossingConfig
+from .learner import (MLP_ACTIVATIONS, EvalResult, GaeResult, LearnerOps, MlpHead, PpoLossResult,  # noqa: F401 (re-exported)
+                      SampleResult, _EvaluateActions, _MlpForward, _PpoLoss, _ptr, _require)
 from .params import agent_ids, array_form_strategies, lower_config, position_only_tables
 from .reset import build_reset_pool, seeded_positions
 
@@ -90,59 +92,6 @@ class FinishedEpisodes:
 
     def __len__(self) -> int:
         return len(self.env)
-
-
-@dataclass
-class GaeResult:
-    """Advantages and value targets of a trajectory (:meth:`BatchedCollectiveCrossing.compute_gae`, include/ccx.h CCX_GAE).
-    Every element is written: +0.0 / 0 where the agent had no step (``valid`` = 0)."""
-
-    advantages: torch.Tensor  # f32 [K, E, N]
-    returns: torch.Tensor     # f32 [K, E, N]: advantages + values, the critic's regression target
-    valid: torch.Tensor | None  # u8 [K, E, N]: 1 where the agent was live in the step (a loss averages over these)
-
-
-@dataclass
-class SampleResult:
-    """Actions sampled from a policy's logits (:meth:`BatchedCollectiveCrossing.sample_actions`, include/ccx.h CCX_SAMPLE).
-    Every element is written: 255 / +0.0 / +0.0 for agents that are terminated or truncated."""
-
-    actions: torch.Tensor         # u8 [E, N]: what step / rollout consume
-    logp: torch.Tensor | None     # f32 [E, N]: log pi(action | state) under the masked distribution
-    entropy: torch.Tensor | None  # f32 [E, N]: entropy of the masked distribution
-
-
-@dataclass
-class EvalResult:
-    """Stored actions evaluated under new logits (:meth:`BatchedCollectiveCrossing.evaluate_actions`, include/ccx.h
-    CCX_EVALUATE).  Every element is written: +0.0 / +0.0 for rows whose stored action is 255."""
-
-    logp: torch.Tensor            # f32 [...]: log pi_new(stored action | state) under the masked distribution; -inf: not a legal action
-    entropy: torch.Tensor | None  # f32 [...]: entropy of the masked distribution
-
-
-@dataclass
-class PpoLossResult:
-    """The PPO loss over the rows that count (:meth:`BatchedCollectiveCrossing.ppo_loss`, include/ccx.h CCX_PPO_LOSS).
-    ``stats`` = {loss, policy, value, entropy, approx_kl, clip_frac, count, 0}; the named accessors are 0-dim views of it.
-    ``workspace`` / ``grad_logits`` / ``grad_values`` are the static buffers of :meth:`alloc_ppo_loss` (else ``None``)."""
-
-    loss: torch.Tensor                        # f32 0-dim: stats[0]; carries the autograd graph when an input required grad
-    stats: torch.Tensor                       # f32 [8]
-    workspace: torch.Tensor | None = None     # u8 [ccx_ppo_workspace_bytes(rows)]
-    grad_logits: torch.Tensor | None = None   # f32 [..., 5]
-    grad_values: torch.Tensor | None = None   # f32 [...]
-
-    policy = property(lambda self: self.stats[1])
-    value = property(lambda self: self.stats[2])
-    entropy = property(lambda self: self.stats[3])
-    approx_kl = property(lambda self: self.stats[4])
-    clip_frac = property(lambda self: self.stats[5])
-    count = property(lambda self: self.stats[6])
-
-
-def _ptr(t: torch.Tensor | None) -> C.c_void_p:
-    return C.c_void_p(None if t is None else t.data_ptr())
 
 
 def _check_cell_px(cell_px) -> int:
@@ -223,7 +172,7 @@ def scripted_slot_mask(config: CollectiveCrossingConfig, scripted) -> int:
     return mask
 
 
-class BatchedCollectiveCrossing:
+class BatchedCollectiveCrossing(LearnerOps):
     """E envs sharing one config, resident on one GPU for their whole life."""
 
     def __init__(self, config: CollectiveCrossingConfig, num_envs: int, device: int | str | None = None,
@@ -494,9 +443,7 @@ class BatchedCollectiveCrossing:
             for n, (t, ref, name) in enumerate(((final_obs, like[0], "final_obs"), (final_compact, like[1], "final_compact"))):
                 if t is None or ref is None:
                     continue
-                if (not isinstance(t, torch.Tensor) or t.dtype is not torch.float32 or t.device != self.device
-                        or tuple(t.shape) != tuple(ref.shape) or not t.is_contiguous()):
-                    raise ValueError(f"{name} must be a contiguous torch.float32 tensor of shape {tuple(ref.shape)} on {self.device}")
+                _require(name, t, torch.float32, ref.shape, self.device)
                 ptrs[n], keep[n] = t.data_ptr(), t
         self._final_keep = keep
         if tuple(ptrs) != self._final_bound:
@@ -614,8 +561,7 @@ class BatchedCollectiveCrossing:
         E, N = self.num_envs, self.num_agents
         for name, t, dt in (("reward", reward, torch.float64), ("agent_flags", agent_flags, torch.uint8),
                             ("env_flags", env_flags, torch.uint8)):
-            if not isinstance(t, torch.Tensor) or t.dtype is not dt or t.device != self.device or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous {dt} tensor on {self.device}")
+            _require(name, t, dt, None, self.device)
         if reward.dim() == 2:
             reward, agent_flags, env_flags = reward[None], agent_flags[None], env_flags[None]
         K = int(reward.shape[0]) if reward.dim() == 3 else 0
@@ -675,434 +621,6 @@ class BatchedCollectiveCrossing:
         """Empty the finished-episode log: stored = dropped = 0 (``ccx_episode_log_clear``).  Only enqueues."""
         self._need_tracking()
         check(self._lib.ccx_episode_log_clear(self._h))
-
-    # ------------------------------------------------------------------ advantages
-    def alloc_gae(self, num_steps: int, want_valid: bool = True) -> GaeResult:
-        """Output tensors of :meth:`compute_gae` for a K-step trajectory (static buffers for a captured graph)."""
-        shape = (int(num_steps), self.num_envs, self.num_agents)
-        return GaeResult(self._new(shape, torch.float32), self._new(shape, torch.float32),
-                         self._new(shape, torch.uint8) if want_valid else None)
-
-    def compute_gae(self, traj, values: torch.Tensor, last_values: torch.Tensor, final_values: torch.Tensor | None = None,
-                    gamma: float = 0.99, lam: float = 0.95, out: GaeResult | None = None) -> GaeResult:
-        """Generalised advantage estimates and value targets on the device (``ccx_gae``, include/ccx.h CCX_GAE): one
-        kernel on the handle's stream, bit-defined (f32, one rounding per operation, the steps walked backwards).
-
-        ``traj`` is a :class:`RolloutResult` or a ``(reward f64 [K, E, N], agent_flags u8 [K, E, N], env_flags u8 [K, E])``
-        tuple; ``values`` f32 [K, E, N] holds the critic's value of the observation each step ACTED ON, ``last_values`` f32
-        [E, N] that of the state behind the last step, ``final_values`` f32 [K, E, N] (optional) that of the observation a
-        step ENDED ON -- read only where an episode is cut without termination (truncation, ``EF_RESET``); evaluate the
-        critic on ``final_obs`` there (``reset_obs="next"``).  Without it a cut bootstraps from 0.  Termination never
-        bootstraps.  ``out`` reuses a :class:`GaeResult` (``out.valid`` may be ``None``).  All tensors: contiguous, on the
-        batch's device; anything else raises ``ValueError`` before the library is called.  Only enqueues."""
-        if isinstance(traj, RolloutResult):
-            reward, agent_flags, env_flags = traj.reward, traj.agent_flags, traj.env_flags
-        else:
-            try:
-                reward, agent_flags, env_flags = traj
-            except (TypeError, ValueError):
-                raise ValueError("traj must be a RolloutResult or a (reward, agent_flags, env_flags) tuple") from None
-        E, N = self.num_envs, self.num_agents
-        K = int(reward.shape[0]) if isinstance(reward, torch.Tensor) and reward.dim() == 3 else 0
-        if K < 1:
-            raise ValueError(f"reward must be a torch.float64 tensor [K, {E}, {N}] with K >= 1")
-        gamma, lam = float(gamma), float(lam)
-        for name, x in (("gamma", gamma), ("lam", lam)):
-            if not 0.0 <= x <= 1.0:                                  # (false for NaN)
-                raise ValueError(f"{name} must be in [0, 1], got {x!r}")
-        if out is None:
-            out = self.alloc_gae(K)
-        elif not isinstance(out, GaeResult):
-            raise ValueError("out must be a GaeResult (alloc_gae)")
-        KEN = (K, E, N)
-        for name, t, dt, shape, optional in (
-                ("reward", reward, torch.float64, KEN, False), ("agent_flags", agent_flags, torch.uint8, KEN, False),
-                ("env_flags", env_flags, torch.uint8, (K, E), False), ("values", values, torch.float32, KEN, False),
-                ("last_values", last_values, torch.float32, (E, N), False),
-                ("final_values", final_values, torch.float32, KEN, True),
-                ("out.advantages", out.advantages, torch.float32, KEN, False),
-                ("out.returns", out.returns, torch.float32, KEN, False), ("out.valid", out.valid, torch.uint8, KEN, True)):
-            if t is None and optional:
-                continue
-            if (not isinstance(t, torch.Tensor) or t.dtype is not dt or t.device != self.device or tuple(t.shape) != shape
-                    or not t.is_contiguous()):
-                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
-        self._order_after_current_stream(reward, agent_flags, env_flags, values, last_values, final_values,
-                                         out.advantages, out.returns, out.valid)
-        check(self._lib.ccx_gae(self._h, K, _ptr(reward), _ptr(agent_flags), _ptr(env_flags), _ptr(values), _ptr(last_values),
-                                _ptr(final_values), gamma, lam, _ptr(out.advantages), _ptr(out.returns), _ptr(out.valid)))
-        return out
-
-    # ------------------------------------------------------------------ sampling from a learned policy
-    def alloc_sample(self, want_logp: bool = True, want_entropy: bool = False) -> SampleResult:
-        """Output tensors of :meth:`sample_actions` (static buffers for a captured graph)."""
-        shape = (self.num_envs, self.num_agents)
-        return SampleResult(self._new(shape, torch.uint8), self._new(shape, torch.float32) if want_logp else None,
-                            self._new(shape, torch.float32) if want_entropy else None)
-
-    def sample_actions(self, logits: torch.Tensor, masks: torch.Tensor | None = None, deterministic: bool = False,
-                       want_logp: bool = True, want_entropy: bool = False, out: SampleResult | None = None) -> SampleResult:
-        """Masked categorical actions from a network's logits on the device (``ccx_sample_actions``, include/ccx.h
-        CCX_SAMPLE): one kernel on the handle's stream, bit-defined, drawn with the library's counter-based key (global env,
-        episode, step of the episode, agent slot; :meth:`set_rng_seed`) -- the same actions for any split into calls, any
-        world size, eager or captured.
-
-        ``logits`` f32 [E, N, 5] (index = action id); ``masks`` u8 [E, N] (``action_masks`` / ``masks_out``; ``None`` =
-        everything legal); ``deterministic`` takes the masked argmax (lowest index on ties) and draws nothing.  ``logp`` is
-        ``log pi(action)`` under the masked distribution, ``entropy`` that distribution's entropy.  Agents that are
-        terminated or truncated get action 255, ``logp`` = ``entropy`` = 0.  ``out`` reuses a :class:`SampleResult` (its
-        ``logp`` / ``entropy`` may be ``None``; ``want_*`` is then ignored): ``out.actions`` may be a ``[E, N]`` view of the
-        ``[1, E, N]`` tensor :meth:`rollout` reads.  All tensors: contiguous, on the batch's device; anything else raises
-        ``ValueError`` before the library is called.  Not here: bf16 / f16 logits (cast first), a temperature (scale the
-        logits first).  Only enqueues."""
-        E, N = self.num_envs, self.num_agents
-        if out is None:
-            out = self.alloc_sample(want_logp, want_entropy)
-        elif not isinstance(out, SampleResult):
-            raise ValueError("out must be a SampleResult (alloc_sample)")
-        for name, t, dt, shape, optional in (
-                ("logits", logits, torch.float32, (E, N, 5), False), ("masks", masks, torch.uint8, (E, N), True),
-                ("out.actions", out.actions, torch.uint8, (E, N), False), ("out.logp", out.logp, torch.float32, (E, N), True),
-                ("out.entropy", out.entropy, torch.float32, (E, N), True)):
-            if t is None and optional:
-                continue
-            if (not isinstance(t, torch.Tensor) or t.dtype is not dt or t.device != self.device or tuple(t.shape) != shape
-                    or not t.is_contiguous()):
-                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
-        if logits.data_ptr() % 16:
-            raise ValueError("logits must be 16-byte aligned (a view at an odd offset of its storage is not)")
-        self._order_after_current_stream(logits, masks, out.actions, out.logp, out.entropy)
-        check(self._lib.ccx_sample_actions(self._h, _ptr(logits), _ptr(masks), int(bool(deterministic)), _ptr(out.actions),
-                                           _ptr(out.logp), _ptr(out.entropy)))
-        return out
-
-    # ------------------------------------------------------------------ the policy head: observation rows to logits
-    def mlp_head(self, H: int, O: int = 5, activation: str = "tanh", L: int | None = None) -> "MlpHead":
-        """A two-layer perceptron ``Linear(L, H) -> tanh | relu -> Linear(H, O)`` whose forward is ONE kernel with bit-defined
-        outputs (:class:`MlpHead`, include/ccx.h CCX_MLP).  ``L`` defaults to ``obs_len``; ``H`` is a multiple of 16 in
-        16..256, ``O`` in 1..8.  ``O = 5`` is an actor for :meth:`mlp_sample_actions`, ``O = 1`` a critic."""
-        return MlpHead(self, H, O, activation, L)
-
-    def _mlp_forward(self, head: "MlpHead", x: torch.Tensor, y: torch.Tensor, hidden: torch.Tensor | None) -> None:
-        self._order_after_current_stream(x, head.w1t, head.b1, head.w2, head.b2, y, hidden)
-        check(self._lib.ccx_mlp_forward(self._h, x.numel() // head.L, head.L, head.H, head.O, head.activation_id, _ptr(x),
-                                        _ptr(head.w1t), _ptr(head.b1), _ptr(head.w2), _ptr(head.b2), _ptr(y), _ptr(hidden)))
-
-    def mlp_sample_actions(self, head: "MlpHead", obs: torch.Tensor, masks: torch.Tensor | None = None,
-                           deterministic: bool = False, want_logp: bool = True, want_entropy: bool = False,
-                           logits_out: torch.Tensor | None = None, out: SampleResult | None = None) -> SampleResult:
-        """Observation rows to actions in ONE launch (``ccx_mlp_sample_actions``): by definition
-        ``sample_actions(head(obs), ...)`` -- the same key, the same rule for terminated or truncated agents, the same bits
-        in ``actions``, ``logp`` and ``entropy`` -- without the logits' round trip through memory and without the second
-        launch.  ``head`` is an :class:`MlpHead` with ``O == 5`` and ``L == obs_len``; ``obs`` f32 [E, N, L] (contiguous,
-        16-byte aligned: the ``obs`` of :meth:`step` / :meth:`rollout`); ``logits_out`` f32 [E, N, 5] receives the logits of
-        every slot, dead ones included.  ``masks``, ``deterministic``, ``want_*`` and ``out`` are :meth:`sample_actions`'.
-        No gradient flows through this call (the update re-evaluates stored rows with ``head(rows)``).  Anything else than
-        the tensors described raises ``ValueError`` before the library is called.  Only enqueues."""
-        E, N = self.num_envs, self.num_agents
-        if not isinstance(head, MlpHead) or head.batch is not self:
-            raise ValueError("head must be an MlpHead of this batch (mlp_head)")
-        if head.O != 5 or head.L != self.obs_len:
-            raise ValueError(f"mlp_sample_actions needs a head with O == 5 and L == obs_len == {self.obs_len}, got O = {head.O}, L = {head.L}")
-        head._check_parameters()
-        if out is None:
-            out = self.alloc_sample(want_logp, want_entropy)
-        elif not isinstance(out, SampleResult):
-            raise ValueError("out must be a SampleResult (alloc_sample)")
-        for name, t, dt, shape, optional in (
-                ("obs", obs, torch.float32, (E, N, self.obs_len), False), ("masks", masks, torch.uint8, (E, N), True),
-                ("logits_out", logits_out, torch.float32, (E, N, 5), True),
-                ("out.actions", out.actions, torch.uint8, (E, N), False), ("out.logp", out.logp, torch.float32, (E, N), True),
-                ("out.entropy", out.entropy, torch.float32, (E, N), True)):
-            if t is None and optional:
-                continue
-            if (not isinstance(t, torch.Tensor) or t.dtype is not dt or t.device != self.device or tuple(t.shape) != shape
-                    or not t.is_contiguous()):
-                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {self.device}")
-        if obs.data_ptr() % 16:
-            raise ValueError("obs must be 16-byte aligned (a view at an odd offset of its storage is not)")
-        self._order_after_current_stream(obs, head.w1t, head.b1, head.w2, head.b2, masks, logits_out, out.actions, out.logp,
-                                         out.entropy)
-        check(self._lib.ccx_mlp_sample_actions(self._h, head.H, head.activation_id, _ptr(obs), _ptr(head.w1t), _ptr(head.b1),
-                                               _ptr(head.w2), _ptr(head.b2), _ptr(masks), int(bool(deterministic)),
-                                               _ptr(out.actions), _ptr(out.logp), _ptr(out.entropy), _ptr(logits_out)))
-        return out
-
-    # ------------------------------------------------------------------ stored actions under new logits
-    def alloc_evaluate(self, shape, want_entropy: bool = True) -> EvalResult:
-        """Output tensors of :meth:`evaluate_actions` for rows of the leading shape ``shape`` (static buffers for a
-        captured graph)."""
-        shape = tuple(int(x) for x in shape)
-        return EvalResult(self._new(shape, torch.float32), self._new(shape, torch.float32) if want_entropy else None)
-
-    def _check_evaluate(self, logits, actions, masks, extra=()):
-        """The input checks :meth:`evaluate_actions` and :meth:`evaluate_actions_backward` share; returns the leading shape."""
-        if (not isinstance(logits, torch.Tensor) or logits.dtype is not torch.float32 or logits.device != self.device
-                or logits.dim() < 1 or logits.shape[-1] != 5 or not logits.is_contiguous()):
-            raise ValueError(f"logits must be a contiguous torch.float32 tensor of shape [..., 5] on {self.device}")
-        lead = tuple(logits.shape[:-1])
-        for name, t, dt, shape, optional in (("actions", actions, torch.uint8, lead, False), ("masks", masks, torch.uint8, lead, True),
-                                             *extra):
-            if t is None and optional:
-                continue
-            if (not isinstance(t, torch.Tensor) or t.dtype is not dt or t.device != self.device or tuple(t.shape) != shape
-                    or not t.is_contiguous()):
-                hint = " (cast stored actions to torch.uint8 first)" if name == "actions" else ""
-                raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {self.device}{hint}")
-        if logits.data_ptr() % 16:
-            raise ValueError("logits must be 16-byte aligned (a view at an odd offset of its storage is not)")
-        return lead
-
-    def _evaluate_forward(self, logits, actions, masks, out: EvalResult) -> None:
-        self._order_after_current_stream(logits, actions, masks, out.logp, out.entropy)
-        check(self._lib.ccx_evaluate_actions(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks), _ptr(out.logp),
-                                             _ptr(out.entropy)))
-
-    def _current_stream_waits(self) -> None:
-        """Results of a launch on the handle's stream that torch ops consume at once on torch's CURRENT stream: when that
-        is another stream, it waits for the handle's stream."""
-        if torch._C._cuda_getCurrentRawStream(self.device.index) != self._stream_raw:
-            torch.cuda.current_stream(self.device).wait_stream(self._stream)
-
-    def evaluate_actions(self, logits: torch.Tensor, actions: torch.Tensor, masks: torch.Tensor | None = None,
-                         want_entropy: bool = True, out: EvalResult | None = None) -> EvalResult:
-        """``log pi_new(stored action | state)`` and the entropy of the masked distribution under new logits, on the device
-        (``ccx_evaluate_actions``, include/ccx.h CCX_EVALUATE): one kernel on the handle's stream, bit-defined, and the very
-        distribution :meth:`sample_actions` draws from -- on the logits an action was sampled from, ``logp`` and
-        ``entropy`` equal the sampler's bit for bit.
-
-        ``logits`` f32 [..., 5] (contiguous, 16-byte aligned); ``actions`` u8 [...] (what :meth:`sample_actions` stored; cast
-        int64 actions first); ``masks`` u8 [...] or ``None`` (everything legal).  Rows whose action is 255 give ``logp`` =
-        ``entropy`` = +0.0 whatever their logits hold; an action that is out of range or illegal under its mask gives
-        ``logp`` = -inf.  Anything else than the tensors described raises ``ValueError`` before the library is called;
-        zero rows return empty tensors without calling it.
-
-        When ``logits.requires_grad`` and grad mode is on, the call is a ``torch.autograd.Function``: its backward is
-        ``ccx_evaluate_actions_backward`` (one kernel; illegal places, 255 rows and degenerate rows get exactly +0.0, selected,
-        so a NaN there never reaches a gradient), an output the loss did not use is passed as NULL, and ``out=`` is refused.
-        Otherwise this is the plain forward and ``out=`` reuses an :class:`EvalResult` (:meth:`alloc_evaluate`).  Only
-        enqueues."""
-        lead = self._check_evaluate(logits, actions, masks)
-        if logits.requires_grad and torch.is_grad_enabled():
-            if out is not None:
-                raise ValueError("out= cannot be used when logits require a gradient (the autograd path allocates its outputs)")
-            if logits.numel() == 0:
-                zero = logits.sum(-1) * 0.0
-                return EvalResult(zero, zero.clone() if want_entropy else None)
-            logp, entropy = _EvaluateActions.apply(self, logits, actions, masks, bool(want_entropy))
-            return EvalResult(logp, entropy)
-        if out is None:
-            out = self.alloc_evaluate(lead, want_entropy)
-        elif not isinstance(out, EvalResult):
-            raise ValueError("out must be an EvalResult (alloc_evaluate)")
-        self._check_evaluate(logits, actions, masks, (("out.logp", out.logp, torch.float32, lead, False),
-                                                      ("out.entropy", out.entropy, torch.float32, lead, True)))
-        if logits.numel():
-            self._evaluate_forward(logits, actions, masks, out)
-        return out
-
-    def evaluate_actions_backward(self, logits: torch.Tensor, actions: torch.Tensor, masks: torch.Tensor | None,
-                                  grad_logp: torch.Tensor | None, grad_entropy: torch.Tensor | None,
-                                  out: torch.Tensor | None = None) -> torch.Tensor:
-        """The gradient of :meth:`evaluate_actions` with respect to ``logits`` from the gradients of its two outputs
-        (``ccx_evaluate_actions_backward``): one kernel that recomputes the forward quantities from the logits.  Either of
-        ``grad_logp`` / ``grad_entropy`` (f32, the leading shape of ``logits``) may be ``None``, not both.  ``out`` reuses a
-        f32 tensor of the shape of ``logits`` (16-byte aligned): with :meth:`evaluate_actions` ``(out=)`` the static-buffer
-        pair for a captured graph.  Only enqueues."""
-        if grad_logp is None and grad_entropy is None:
-            raise ValueError("at least one of grad_logp and grad_entropy is required")
-        if out is None and isinstance(logits, torch.Tensor):
-            out = torch.empty_like(logits, requires_grad=False)
-        lead = tuple(logits.shape[:-1]) if isinstance(logits, torch.Tensor) else ()
-        self._check_evaluate(logits, actions, masks, (
-            ("grad_logp", grad_logp, torch.float32, lead, True), ("grad_entropy", grad_entropy, torch.float32, lead, True),
-            ("out", out, torch.float32, lead + (5,), False)))
-        if out.data_ptr() % 16:
-            raise ValueError("out must be 16-byte aligned (a view at an odd offset of its storage is not)")
-        if logits.numel():
-            self._order_after_current_stream(logits, actions, masks, grad_logp, grad_entropy, out)
-            check(self._lib.ccx_evaluate_actions_backward(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks),
-                                                          _ptr(grad_logp), _ptr(grad_entropy), _ptr(out)))
-        return out
-
-    # ------------------------------------------------------------------ the PPO loss over the rows that count
-    def _ppo_workspace(self, rows: int) -> torch.Tensor:
-        """A workspace from torch's allocator (so a call inside a graph capture stays capturable)."""
-        return self._new((max(8, int(self._lib.ccx_ppo_workspace_bytes(int(rows)))),), torch.uint8)
-
-    def alloc_ppo_loss(self, shape, want_logits_grad: bool = True, want_values_grad: bool = True) -> PpoLossResult:
-        """Static buffers of :meth:`ppo_loss` / :meth:`ppo_loss_backward` for rows of the leading shape ``shape``: stats,
-        the workspace and the two gradients (for a captured graph)."""
-        shape = tuple(int(x) for x in shape)
-        rows = int(np.prod(shape)) if shape else 1
-        stats = torch.zeros((8,), dtype=torch.float32, device=self.device)
-        return PpoLossResult(stats[0], stats, self._ppo_workspace(rows),
-                             self._new(shape + (5,), torch.float32) if want_logits_grad else None,
-                             self._new(shape, torch.float32) if want_values_grad else None)
-
-    @staticmethod
-    def _check_ppo_hyper(clip, vf_coef, ent_coef, adv_eps):
-        clip, vf_coef, ent_coef, adv_eps = float(clip), float(vf_coef), float(ent_coef), float(adv_eps)
-        if not 0.0 < clip < 1.0:                                     # (false for NaN)
-            raise ValueError(f"clip must lie in (0, 1), got {clip!r}")
-        for name, x in (("vf_coef", vf_coef), ("ent_coef", ent_coef), ("adv_eps", adv_eps)):
-            if not 0.0 <= x < float("inf"):
-                raise ValueError(f"{name} must be finite and not negative, got {x!r}")
-        return clip, vf_coef, ent_coef, adv_eps
-
-    def _check_flat(self, name, t, dtype, shape, optional=False):
-        if t is None and optional:
-            return
-        if (not isinstance(t, torch.Tensor) or t.dtype is not dtype or t.device != self.device or tuple(t.shape) != tuple(shape)
-                or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {self.device}")
-
-    def _check_ppo(self, logits, values, actions, logp_old, advantages, returns, masks, valid, norm):
-        """The input checks of :meth:`ppo_loss` and :meth:`ppo_loss_backward`; returns (leading shape, norm f32 [2] or None)."""
-        lead = self._check_evaluate(logits, actions, masks, (
-            ("values", values, torch.float32, tuple(logits.shape[:-1]) if isinstance(logits, torch.Tensor) else (), False),))
-        for name, t, dt in (("logp_old", logp_old, torch.float32), ("advantages", advantages, torch.float32),
-                            ("returns", returns, torch.float32), ("valid", valid, torch.uint8)):
-            self._check_flat(name, t, dt, lead, optional=name == "valid")
-        if norm is not None:
-            if (not isinstance(norm, torch.Tensor) or norm.dtype is not torch.float32 or norm.device != self.device
-                    or tuple(norm.shape) not in ((2,), (4,)) or not norm.is_contiguous()):
-                raise ValueError(f"norm must be a contiguous torch.float32 tensor on {self.device}: masked_moments' [4] "
-                                 "(n, mean, std, 0) or [2] (mean, std)")
-            if norm.shape[0] == 4:
-                norm = norm[1:3]
-        return lead, norm
-
-    def masked_moments(self, x: torch.Tensor, valid: torch.Tensor | None = None, out: torch.Tensor | None = None,
-                       workspace: torch.Tensor | None = None) -> torch.Tensor:
-        """``[n, mean, std, 0]`` (f32 [4] on the device) of ``x`` f32 [...] over the elements where ``valid`` u8 [...] is not
-        zero (``None``: all), by ``ccx_masked_moments`` (include/ccx.h CCX_PPO_LOSS): two kernels on the handle's stream, a
-        fixed f64 tree, bit-defined, no host synchronisation.  ``std`` is the unbiased one; ``n < 2`` gives mean 0, std 1.
-        Hand the result to :meth:`ppo_loss` as ``norm=``.  ``out`` / ``workspace`` reuse buffers (a captured graph).  Zero
-        elements return ``[0, 0, 1, 0]`` without calling the library.  Only enqueues."""
-        if (not isinstance(x, torch.Tensor) or x.dtype is not torch.float32 or x.device != self.device or not x.is_contiguous()):
-            raise ValueError(f"x must be a contiguous torch.float32 tensor on {self.device}")
-        self._check_flat("valid", valid, torch.uint8, x.shape, optional=True)
-        if out is None:
-            out = self._new((4,), torch.float32)
-        self._check_flat("out", out, torch.float32, (4,))
-        rows = x.numel()
-        if rows == 0:
-            out.copy_(torch.tensor([0.0, 0.0, 1.0, 0.0], dtype=torch.float32))
-            return out
-        workspace = self._ppo_workspace_arg(workspace, rows)
-        self._order_after_current_stream(x, valid, out, workspace)
-        check(self._lib.ccx_masked_moments(self._h, rows, _ptr(x), _ptr(valid), _ptr(workspace), _ptr(out)))
-        self._current_stream_waits()
-        return out
-
-    def _ppo_workspace_arg(self, workspace, rows: int) -> torch.Tensor:
-        if workspace is None:
-            return self._ppo_workspace(rows)
-        need = int(self._lib.ccx_ppo_workspace_bytes(int(rows)))
-        if (not isinstance(workspace, torch.Tensor) or workspace.dtype is not torch.uint8 or workspace.device != self.device
-                or workspace.dim() != 1 or workspace.numel() < need or not workspace.is_contiguous() or workspace.data_ptr() % 8):
-            raise ValueError(f"workspace must be a contiguous, 8-byte aligned torch.uint8 tensor of at least {need} bytes on "
-                             f"{self.device} (alloc_ppo_loss)")
-        return workspace
-
-    def _ppo_forward(self, logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper, workspace, stats):
-        self._order_after_current_stream(logits, values, actions, logp_old, advantages, returns, masks, valid, norm, workspace, stats)
-        check(self._lib.ccx_ppo_loss(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks), _ptr(logp_old),
-                                     _ptr(advantages), _ptr(returns), _ptr(values), _ptr(valid), _ptr(norm), *hyper,
-                                     _ptr(workspace), _ptr(stats)))
-        self._current_stream_waits()
-
-    def ppo_loss(self, logits: torch.Tensor, values: torch.Tensor, actions: torch.Tensor, logp_old: torch.Tensor,
-                 advantages: torch.Tensor, returns: torch.Tensor, masks: torch.Tensor | None = None,
-                 valid: torch.Tensor | None = None, norm: torch.Tensor | None = None, clip: float = 0.2, vf_coef: float = 0.5,
-                 ent_coef: float = 0.01, adv_eps: float = 1e-8, out: PpoLossResult | None = None) -> PpoLossResult:
-        """The clipped-surrogate PPO loss ``policy + vf_coef * value - ent_coef * entropy`` over the rows that count, on
-        the device (``ccx_ppo_loss``, include/ccx.h CCX_PPO_LOSS): two kernels on the handle's stream, bit-defined (the
-        reduction is a fixed f64 tree), shapes static -- ``valid`` is a selection inside the kernel, so nothing is
-        compacted, nothing synchronises with the host, and the whole update captures into a graph.
-
-        ``logits`` f32 [..., 5] (contiguous, 16-byte aligned), everything else [...]: ``values`` f32 (the critic's, new
-        weights), ``actions`` u8 and ``masks`` u8 or ``None`` as in :meth:`evaluate_actions`, ``logp_old`` f32
-        (:meth:`sample_actions`' logp), ``advantages`` / ``returns`` f32 and ``valid`` u8 (:meth:`compute_gae`'s).  A row
-        counts iff its ``valid`` byte is not zero and its action is not 255.  ``norm``: :meth:`masked_moments`' result
-        (or a [2] = mean, std): advantages enter as ``(a - mean) / (std + adv_eps)``.  The result's ``stats`` holds loss,
-        policy, value, entropy, approx_kl (mean of ``ratio - 1 - log ratio``), clip_frac, count, 0.
-
-        When ``logits`` or ``values`` requires grad and grad mode is on, the call is a ``torch.autograd.Function``:
-        ``r.loss.backward()`` reaches both through ``ccx_ppo_loss_backward`` (one kernel; rows that do not count get exactly
-        +0.0), ``None`` goes to the one that does not require grad, ``out=`` is refused, and the workspace comes from
-        torch's allocator, so the call captures.  Otherwise ``out=`` reuses a result of :meth:`alloc_ppo_loss`.  A wrong
-        dtype, shape or device, a non-contiguous tensor, a misaligned pointer or a bad hyperparameter raises ``ValueError``
-        before the library is called; zero rows return zeros without calling it.  Only enqueues."""
-        hyper = self._check_ppo_hyper(clip, vf_coef, ent_coef, adv_eps)
-        lead, norm = self._check_ppo(logits, values, actions, logp_old, advantages, returns, masks, valid, norm)
-        needs = [t.requires_grad for t in (logits, values)]
-        if any(needs) and torch.is_grad_enabled():
-            if out is not None:
-                raise ValueError("out= cannot be used when logits or values require a gradient (the autograd path allocates its outputs)")
-            if logits.numel() == 0:
-                stats = torch.cat([(logits.sum() + values.sum()).reshape(1) * 0.0, torch.zeros(7, device=self.device)])
-            else:
-                stats = _PpoLoss.apply(self, logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper)
-            return PpoLossResult(stats[0], stats.detach())
-        if out is None:
-            stats = torch.zeros((8,), dtype=torch.float32, device=self.device)
-            out = PpoLossResult(stats[0], stats)
-            workspace = None
-        elif not isinstance(out, PpoLossResult):
-            raise ValueError("out must be a PpoLossResult (alloc_ppo_loss)")
-        else:
-            self._check_flat("out.stats", out.stats, torch.float32, (8,))
-            workspace = out.workspace
-        if logits.numel() == 0:
-            out.stats.zero_()
-            return out
-        workspace = self._ppo_workspace_arg(workspace, actions.numel())
-        self._ppo_forward(logits.detach(), values.detach(), actions, logp_old, advantages, returns, masks, valid, norm, hyper,
-                          workspace, out.stats)
-        return out
-
-    def ppo_loss_backward(self, logits: torch.Tensor, values: torch.Tensor, actions: torch.Tensor, logp_old: torch.Tensor,
-                          advantages: torch.Tensor, returns: torch.Tensor, masks: torch.Tensor | None = None,
-                          valid: torch.Tensor | None = None, norm: torch.Tensor | None = None, clip: float = 0.2,
-                          vf_coef: float = 0.5, ent_coef: float = 0.01, adv_eps: float = 1e-8, *, stats: torch.Tensor,
-                          grad_loss: torch.Tensor | None = None, want_logits_grad: bool = True, want_values_grad: bool = True,
-                          out: PpoLossResult | None = None):
-        """``(grad_logits, grad_values)`` of :meth:`ppo_loss`'s ``loss`` (``ccx_ppo_loss_backward``: one kernel that recomputes
-        the forward terms from the same inputs and the forward's ``stats``).  ``grad_loss`` f32 [1] or 0-dim on the device
-        (``None`` = 1).  ``want_*`` choose the outputs (at least one; the other is returned as ``None`` and not computed);
-        ``out`` reuses the gradients of an :meth:`alloc_ppo_loss` result instead (one of them may be ``None``).  Only
-        enqueues."""
-        hyper = self._check_ppo_hyper(clip, vf_coef, ent_coef, adv_eps)
-        lead, norm = self._check_ppo(logits, values, actions, logp_old, advantages, returns, masks, valid, norm)
-        self._check_flat("stats", stats, torch.float32, (8,))
-        if grad_loss is not None:
-            if (not isinstance(grad_loss, torch.Tensor) or grad_loss.dtype is not torch.float32 or grad_loss.device != self.device
-                    or grad_loss.numel() < 1 or grad_loss.dim() > 1 or not grad_loss.is_contiguous()):
-                raise ValueError(f"grad_loss must be a torch.float32 tensor with one element (0-dim or [1]) on {self.device}")
-        if out is None:
-            gl = torch.empty_like(logits, requires_grad=False) if want_logits_grad else None
-            gv = torch.empty_like(values, requires_grad=False) if want_values_grad else None
-        elif not isinstance(out, PpoLossResult):
-            raise ValueError("out must be a PpoLossResult (alloc_ppo_loss)")
-        else:
-            gl, gv = out.grad_logits, out.grad_values
-        if gl is None and gv is None:
-            raise ValueError("at least one of the two gradients is required")
-        self._check_flat("grad_logits", gl, torch.float32, lead + (5,), optional=True)
-        self._check_flat("grad_values", gv, torch.float32, lead, optional=True)
-        if gl is not None and gl.data_ptr() % 16:
-            raise ValueError("grad_logits must be 16-byte aligned (a view at an odd offset of its storage is not)")
-        if logits.numel():
-            logits, values = logits.detach(), values.detach()
-            self._order_after_current_stream(logits, values, actions, logp_old, advantages, returns, masks, valid, norm, stats,
-                                             grad_loss, gl, gv)
-            check(self._lib.ccx_ppo_loss_backward(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks),
-                                                  _ptr(logp_old), _ptr(advantages), _ptr(returns), _ptr(values), _ptr(valid),
-                                                  _ptr(norm), *hyper, _ptr(stats), _ptr(grad_loss), _ptr(gl), _ptr(gv)))
-            self._current_stream_waits()
-        return gl, gv
 
     # ------------------------------------------------------------------ compute
     def observe(self, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -1785,195 +1303,3 @@ class _CudaArrayView:
 
 def _device_view_i64(ptr: int, n: int, device: torch.device) -> torch.Tensor:
     return torch.as_tensor(_CudaArrayView(ptr, n), device=device)
-
-
-class _EvaluateActions(torch.autograd.Function):
-    """:meth:`BatchedCollectiveCrossing.evaluate_actions` for logits that require a gradient: forward and backward are
-    the two kernels of CCX_EVALUATE; nothing is saved but the inputs."""
-
-    @staticmethod
-    def forward(ctx, batch, logits, actions, masks, want_entropy):
-        logits = logits.detach()
-        out = batch.alloc_evaluate(logits.shape[:-1], want_entropy)
-        batch._evaluate_forward(logits, actions, masks, out)
-        batch._current_stream_waits()
-        ctx.batch, ctx.actions, ctx.masks = batch, actions, masks
-        ctx.save_for_backward(logits)
-        ctx.set_materialize_grads(False)                # an output the loss did not use arrives as None and is passed as NULL
-        return out.logp, out.entropy
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_logp, grad_entropy):
-        (logits,) = ctx.saved_tensors
-        grad_logp = None if grad_logp is None else grad_logp.contiguous()
-        grad_entropy = None if grad_entropy is None else grad_entropy.contiguous()
-        if grad_logp is None and grad_entropy is None:
-            return None, None, None, None, None
-        grad = ctx.batch.evaluate_actions_backward(logits, ctx.actions, ctx.masks, grad_logp, grad_entropy)
-        ctx.batch._current_stream_waits()
-        return None, grad, None, None, None
-
-
-class _PpoLoss(torch.autograd.Function):
-    """:meth:`BatchedCollectiveCrossing.ppo_loss` for logits or values that require a gradient: the forward is the two
-    kernels of ``ccx_ppo_loss``, the backward the one of ``ccx_ppo_loss_backward``; nothing is saved but the inputs and
-    ``stats``.  Only ``stats[0]``, the loss, is differentiable: the gradient arriving at the other seven is not read."""
-
-    @staticmethod
-    def forward(ctx, batch, logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper):
-        logits, values = logits.detach(), values.detach()
-        stats = torch.zeros((8,), dtype=torch.float32, device=batch.device)
-        batch._ppo_forward(logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper,
-                           batch._ppo_workspace(actions.numel()), stats)
-        ctx.batch, ctx.hyper = batch, hyper
-        ctx.rest = (actions, logp_old, advantages, returns, masks, valid, norm)
-        ctx.save_for_backward(logits, values, stats)
-        return stats
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_stats):
-        logits, values, stats = ctx.saved_tensors
-        actions, logp_old, advantages, returns, masks, valid, norm = ctx.rest
-        want_l, want_v = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        gl, gv = ctx.batch.ppo_loss_backward(logits, values, actions, logp_old, advantages, returns, masks, valid, norm,
-                                             *ctx.hyper, stats=stats, grad_loss=grad_stats.contiguous(),
-                                             want_logits_grad=want_l, want_values_grad=want_v)
-        return (None, gl, gv) + (None,) * 8
-
-
-MLP_ACTIVATIONS = {"tanh": 0, "relu": 1}
-
-
-class MlpHead(torch.nn.Module):
-    """``Linear(L, H) -> tanh | relu -> Linear(H, O)`` on the batch's device, forward in ONE kernel on the handle's stream
-    (``ccx_mlp_forward``, include/ccx.h CCX_MLP).  The outputs of a row are a fixed sequence of f32 operations on that row:
-    they do not depend on how many rows the call holds or where the row sits, so ``head(rows)`` on a ``[K, E, N, L]``
-    minibatch reproduces, bit for bit, the logits :meth:`BatchedCollectiveCrossing.mlp_sample_actions` drew an action from.
-
-    The parameters are stored in the kernel's layout -- ``w1t`` [L, H] (the first layer INPUT-major:
-    ``Linear(L, H).weight.t()``), ``b1`` [H], ``w2`` [O, H], ``b2`` [O] -- so an optimiser updates what the kernel reads and
-    no packing launch sits in the loop.  They are initialised as ``torch.nn.Linear`` initialises (the two layers drawn in
-    order from torch's generator); :meth:`from_linear` and :meth:`to_sequential` convert by exact copies.
-
-    ``head(x, out=None)``: ``x`` f32 [..., L], contiguous, 16-byte aligned, on the batch's device; returns f32 [..., O].
-    Without grad this is the one launch, and ``out=`` reuses a tensor (static buffers for a captured graph).  When grad mode
-    is on and a parameter or ``x`` requires a gradient, the call is a ``torch.autograd.Function``: the forward is the same
-    kernel -- the same bits -- with the hidden activations saved, ``out=`` is refused, and the backward is a torch
-    composition on those activations (matrix products and sums in ordinary f32: correct to rounding, NOT bit-defined).
-    Anything else than the tensors described raises ``ValueError`` before the library is called; zero rows return an empty
-    tensor without calling it."""
-
-    def __init__(self, batch: BatchedCollectiveCrossing, H: int, O: int = 5, activation: str = "tanh", L: int | None = None):
-        super().__init__()
-        L = batch.obs_len if L is None else L
-        for name, v, lo, hi in (("L", L, 1, 512), ("H", H, 16, 256), ("O", O, 1, 8)):
-            if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
-                raise ValueError(f"{name} must be an int in {lo}..{hi}, got {v!r}")
-        if H % 16:
-            raise ValueError(f"H must be a multiple of 16, got {H}")
-        if activation not in MLP_ACTIVATIONS:
-            raise ValueError(f"activation must be one of {sorted(MLP_ACTIVATIONS)}, got {activation!r}")
-        object.__setattr__(self, "batch", batch)                          # (not a submodule, not part of the state dict)
-        self.L, self.H, self.O, self.activation = L, H, O, activation
-        self.activation_id = MLP_ACTIVATIONS[activation]
-        lin1, lin2 = torch.nn.Linear(L, H), torch.nn.Linear(H, O)
-        dev = batch.device
-        self.w1t = torch.nn.Parameter(lin1.weight.detach().t().contiguous().to(dev))
-        self.b1 = torch.nn.Parameter(lin1.bias.detach().clone().to(dev))
-        self.w2 = torch.nn.Parameter(lin2.weight.detach().clone().to(dev))
-        self.b2 = torch.nn.Parameter(lin2.bias.detach().clone().to(dev))
-
-    @classmethod
-    def from_linear(cls, batch: BatchedCollectiveCrossing, lin1: torch.nn.Linear, lin2: torch.nn.Linear,
-                    activation: str = "tanh") -> "MlpHead":
-        """The head that computes ``lin2(act(lin1(x)))``: exact copies of the two layers' f32 parameters."""
-        if (not isinstance(lin1, torch.nn.Linear) or not isinstance(lin2, torch.nn.Linear) or lin1.bias is None
-                or lin2.bias is None or lin1.out_features != lin2.in_features or lin1.weight.dtype is not torch.float32
-                or lin2.weight.dtype is not torch.float32):
-            raise ValueError("from_linear needs two f32 torch.nn.Linear layers with biases, lin1.out_features == lin2.in_features")
-        head = cls(batch, lin1.out_features, lin2.out_features, activation, lin1.in_features)
-        with torch.no_grad():
-            head.w1t.copy_(lin1.weight.t())
-            head.b1.copy_(lin1.bias)
-            head.w2.copy_(lin2.weight)
-            head.b2.copy_(lin2.bias)
-        return head
-
-    def to_sequential(self, dtype: torch.dtype = torch.float32) -> torch.nn.Sequential:
-        """``Sequential(Linear(L, H), Tanh | ReLU, Linear(H, O))`` with exact copies of the parameters (cast to ``dtype``)."""
-        lin1 = torch.nn.Linear(self.L, self.H, device=self.w1t.device, dtype=dtype)
-        lin2 = torch.nn.Linear(self.H, self.O, device=self.w1t.device, dtype=dtype)
-        with torch.no_grad():
-            lin1.weight.copy_(self.w1t.t())
-            lin1.bias.copy_(self.b1)
-            lin2.weight.copy_(self.w2)
-            lin2.bias.copy_(self.b2)
-        return torch.nn.Sequential(lin1, torch.nn.Tanh() if self.activation == "tanh" else torch.nn.ReLU(), lin2)
-
-    def extra_repr(self) -> str:
-        return f"L={self.L}, H={self.H}, O={self.O}, activation={self.activation}"
-
-    def _check_parameters(self) -> None:
-        for name, shape in (("w1t", (self.L, self.H)), ("b1", (self.H,)), ("w2", (self.O, self.H)), ("b2", (self.O,))):
-            t = getattr(self, name)
-            if (t.dtype is not torch.float32 or t.device != self.batch.device or tuple(t.shape) != shape or not t.is_contiguous()):
-                raise ValueError(f"{name} must stay a contiguous torch.float32 tensor of shape {shape} on {self.batch.device}")
-
-    def forward(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
-        b = self.batch
-        if (not isinstance(x, torch.Tensor) or x.dtype is not torch.float32 or x.device != b.device or x.dim() < 1
-                or x.shape[-1] != self.L or not x.is_contiguous()):
-            raise ValueError(f"x must be a contiguous torch.float32 tensor of shape [..., {self.L}] on {b.device}")
-        if x.data_ptr() % 16:
-            raise ValueError("x must be 16-byte aligned (a view at an odd offset of its storage is not)")
-        self._check_parameters()
-        shape = tuple(x.shape[:-1]) + (self.O,)
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            if out is not None:
-                raise ValueError("out= cannot be used when a gradient is required (the autograd path allocates its outputs)")
-            if x.numel() == 0:
-                return x.new_zeros(shape) + self.b2 * 0.0
-            return _MlpForward.apply(self, x, self.w1t, self.b1, self.w2, self.b2)
-        if out is None:
-            out = b._new(shape, torch.float32)
-        elif (not isinstance(out, torch.Tensor) or out.dtype is not torch.float32 or out.device != b.device
-              or tuple(out.shape) != shape or not out.is_contiguous()):
-            raise ValueError(f"out must be a contiguous torch.float32 tensor of shape {shape} on {b.device}")
-        if x.numel():
-            b._mlp_forward(self, x.detach(), out, None)
-        return out
-
-
-class _MlpForward(torch.autograd.Function):
-    """:class:`MlpHead` when a gradient is required: the forward is the kernel of CCX_MLP with the activations saved; the
-    backward is ordinary f32 torch on them (not bit-defined)."""
-
-    @staticmethod
-    def forward(ctx, head, x, w1t, b1, w2, b2):
-        x = x.detach()
-        b = head.batch
-        y = b._new(tuple(x.shape[:-1]) + (head.O,), torch.float32)
-        hidden = b._new(tuple(x.shape[:-1]) + (head.H,), torch.float32)
-        b._mlp_forward(head, x, y, hidden)
-        b._current_stream_waits()
-        ctx.relu = head.activation == "relu"
-        ctx.save_for_backward(x, w1t.detach(), w2.detach(), hidden)
-        return y
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gy):
-        x, w1t, w2, hidden = ctx.saved_tensors
-        L, H, O = x.shape[-1], hidden.shape[-1], gy.shape[-1]
-        gy, h, x2 = gy.contiguous().reshape(-1, O), hidden.reshape(-1, H), x.reshape(-1, L)
-        gh = gy @ w2
-        ga = gh * (h > 0) if ctx.relu else gh * (1.0 - h * h)
-        need = ctx.needs_input_grad
-        gx = (ga @ w1t.t()).reshape(x.shape) if need[1] else None
-        gw1t = x2.t() @ ga if need[2] else None
-        gb1 = ga.sum(0) if need[3] else None
-        gw2 = gy.t() @ h if need[4] else None
-        gb2 = gy.sum(0) if need[5] else None
-        return None, gx, gw1t, gb1, gw2, gb2

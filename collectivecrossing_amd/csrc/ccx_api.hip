@@ -34,6 +34,14 @@ int fail(int code, const char* fmt, ...) {
     va_end(ap);
     return code;
 }
+
+int row_blocks(const char* who, int64_t rows, int64_t rows_per_block, unsigned& blocks) {
+    if (rows < 1) return fail(CCX_EINVAL, "%s: rows must be at least 1, got %lld", who, (long long)rows);
+    const int64_t b = (rows + rows_per_block - 1) / rows_per_block;
+    if (b > 0x7FFFFFFFll) return fail(CCX_EINVAL, "%s: %lld rows need more than 2^31 - 1 workgroups", who, (long long)rows);
+    blocks = (unsigned)b;
+    return CCX_OK;
+}
 }  // namespace ccxi
 using ccxi::fail;
 using ccxp::ceil_log2;

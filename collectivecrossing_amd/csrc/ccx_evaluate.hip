@@ -60,14 +60,6 @@ __global__ __launch_bounds__(64) void evaluate_bwd_kernel(const EvalArgs A) {
     ccx_rows::store_rows(A.grad_logits, A.M, pieces, lane, blockIdx.x, row, floats, last_piece, g);
 }
 
-int check_rows(const char* who, int64_t rows, unsigned& blocks) {
-    if (rows < 1) return fail(CCX_EINVAL, "%s: rows must be at least 1, got %lld", who, (long long)rows);
-    const int64_t b = (rows + 63) / 64;
-    if (b > 0x7FFFFFFFll) return fail(CCX_EINVAL, "%s: %lld rows need more than 2^31 - 1 workgroups", who, (long long)rows);
-    blocks = (unsigned)b;
-    return CCX_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -78,7 +70,7 @@ int ccx_evaluate_actions(ccx_handle* h, int64_t rows, const float* logits, const
     if (!logits || !actions || !logp)
         return fail(CCX_EINVAL, "ccx_evaluate_actions: NULL argument (logits, actions and logp are required)");
     unsigned blocks = 0;
-    if (int rc = check_rows("ccx_evaluate_actions", rows, blocks)) return rc;
+    if (int rc = ccxi::row_blocks("ccx_evaluate_actions", rows, 64, blocks)) return rc;
     if (reinterpret_cast<uintptr_t>(logits) & 15u) return fail(CCX_EINVAL, "ccx_evaluate_actions: logits must be 16-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     EvalArgs A{};
@@ -109,7 +101,7 @@ int ccx_evaluate_actions_backward(ccx_handle* h, int64_t rows, const float* logi
     if (!grad_logp_or_null && !grad_entropy_or_null)
         return fail(CCX_EINVAL, "ccx_evaluate_actions_backward: both gradients are NULL (at least one of grad_logp, grad_entropy is required)");
     unsigned blocks = 0;
-    if (int rc = check_rows("ccx_evaluate_actions_backward", rows, blocks)) return rc;
+    if (int rc = ccxi::row_blocks("ccx_evaluate_actions_backward", rows, 64, blocks)) return rc;
     if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(grad_logits)) & 15u)
         return fail(CCX_EINVAL, "ccx_evaluate_actions_backward: logits and grad_logits must be 16-byte aligned");
     CCX_HIP(hipSetDevice(h->device));

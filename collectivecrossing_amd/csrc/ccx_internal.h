@@ -14,6 +14,9 @@ namespace ccxi {
 // records the thread-local message returned by ccx_last_error() and hands the code back
 int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// the grid of a launch over `rows` rows, rows_per_block to a workgroup: CCX_EINVAL for rows < 1 or more than 2^31 - 1 workgroups
+int row_blocks(const char* who, int64_t rows, int64_t rows_per_block, unsigned& blocks);
+
 // CCX_EPISODE_STATS (ccx_episode_stats.hip): zero the running accumulators and the latch of the masked envs on the handle's
 // stream (the resets call it while tracking is on); free the buffers (ccx_destroy)
 int episode_stats_reset(struct ::ccx_handle* h, const uint8_t* env_mask);

@@ -18,9 +18,10 @@
 // ccx_softmax.h's sample_slot on its lane's five logits: the same code ccx_sample.hip runs on logits read from memory.
 // Arithmetic.  ccx_mlp.h's functions, one f32 operation per line (-ffp-contract=off; `/` is the correctly rounded division,
 // asked for on this unit's compile line).
-#include "ccx_internal.h"
+#include "ccx_draw.h"
 #include "ccx_mlp.h"
 
+using ccx_draw::DrawArgs;
 using ccxi::fail;
 
 namespace {
@@ -35,19 +36,6 @@ struct MlpArgs {
     float* hidden;                     // [rows][H] or null
     long long rows;
     int32_t L, H, O, activation;
-};
-
-struct DrawArgs {
-    const uint8_t* masks;              // may be null
-    const uint8_t* terminated;
-    const uint8_t* truncated;
-    const int32_t* step_count;
-    const int32_t* episode;
-    uint8_t* actions;
-    float* logp;                       // STATS: either may be null
-    float* entropy;
-    int32_t E;
-    uint32_t N, genv0, seed_lo, seed_hi;   // as ccx_sample.hip's SampleArgs
 };
 
 // LDS floats a workgroup needs: the x tile at its odd row stride, later overlaid by the partials (and y in the fused kernel)
@@ -136,49 +124,23 @@ __global__ __launch_bounds__(1024) void mlp_forward_kernel(const MlpArgs A) {
     mlp_tile<false>(A, lds);
 }
 
-// ccx_sample.hip's kernel with the logits taken from the tile instead of from memory: 64 rows = 64 slots = wave 0's lanes.
+// ccx_sample.hip's kernel with the logits taken from the tile instead of from memory: 64 rows = 64 slots = wave 0's lanes,
+// under ccx_draw.h's slot rule.
 template <bool DET, bool STATS>
 __global__ __launch_bounds__(1024) void mlp_draw_kernel(const MlpArgs A, const DrawArgs D) {
     extern __shared__ float lds[];
     const uint32_t lane = threadIdx.x & 63u;
     const bool first = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0;
-    const long long slot = (long long)blockIdx.x * 64 + lane;
-    const long long sl = slot < A.rows ? slot : A.rows - 1;
-    // e = slot / N without a 64-bit division, as in ccx_sample.hip
-    const uint32_t bq = blockIdx.x / D.N, br = blockIdx.x - bq * D.N;
-    const uint32_t rest = br * 64u + lane, rq = rest / D.N;
-    const long long e = (long long)bq * 64 + rq;
-    const uint32_t agent = rest - rq * D.N;
-    uint8_t term = 0, trunc = 0;
-    uint32_t mbyte = 0x1Fu, episode = 0, step = 0;
-    if (first) {                                                          // wave 0's small loads, in flight under the layers
-        term = D.terminated[sl];
-        trunc = D.truncated[sl];
-        if (D.masks) mbyte = (uint32_t)D.masks[sl];
-        if (!DET) {
-            const long long el = e < D.E ? e : D.E - 1;
-            episode = (uint32_t)D.episode[el];
-            step = (uint32_t)D.step_count[el];
-        }
-    }
+    const ccx_draw::Slot s = ccx_draw::slot_of(D, lane);
+    ccx_draw::Small v;
+    if (first) v = ccx_draw::small_loads<DET>(D, s, D.masks != nullptr);   // wave 0's small loads, in flight under the layers
     const float* y = mlp_tile<true>(A, lds);
     __syncthreads();
-    if (!first || slot >= A.rows) return;
+    if (!first || s.slot >= D.EN) return;
     float l[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k) l[k] = y[5 * lane + k];
-    const bool dead = (term | trunc) != 0;
-    const uint32_t m = (mbyte & 0x1Fu) | 0x10u;
-    uint32_t u = 0;
-    if (!DET) u = ccx::random_word(D.seed_lo, D.seed_hi, D.genv0 + (uint32_t)e, episode, step, agent);
-    uint32_t action;
-    float logp = 0.0f, entropy = 0.0f;
-    ccx_softmax::sample_slot<DET, STATS>(l, m, u, STATS && D.logp != nullptr, STATS && D.entropy != nullptr, action, logp, entropy);
-    D.actions[slot] = dead ? (uint8_t)CCX_ACTION_ABSENT : (uint8_t)action;
-    if (STATS) {
-        if (D.logp) D.logp[slot] = dead ? 0.0f : logp;
-        if (D.entropy) D.entropy[slot] = dead ? 0.0f : entropy;
-    }
+    ccx_draw::finish<DET, STATS>(D, s, v, l);
 }
 
 // Workgroups of more than 64 KB of LDS (L > 255) are opted into before the launch.
@@ -236,20 +198,7 @@ int ccx_mlp_sample_actions(ccx_handle* h, int32_t H, int32_t activation, const f
         return fail(CCX_EINVAL, "ccx_mlp_sample_actions: w1t, b1, w2, b2, logp, entropy and logits must be 4-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     const MlpArgs A{obs, w1t, b1, w2, b2, logits_or_null, nullptr, (long long)rows, L, H, 5, activation};
-    DrawArgs D;
-    D.masks = masks_or_null;
-    D.terminated = h->st.terminated;
-    D.truncated = h->st.truncated;
-    D.step_count = h->st.step_count;
-    D.episode = h->st.episode;
-    D.actions = actions;
-    D.logp = logp_or_null;
-    D.entropy = entropy_or_null;
-    D.E = h->E;
-    D.N = (uint32_t)h->N;
-    D.genv0 = (uint32_t)h->env_offset;
-    D.seed_lo = h->rng_lo;
-    D.seed_hi = h->rng_hi ^ ccx::kSampleStream;
+    const DrawArgs D = ccx_draw::draw_args(h, masks_or_null, actions, logp_or_null, entropy_or_null);
     const size_t bytes = lds_floats(L, H, 5, true) * sizeof(float);
     const dim3 grid((unsigned)((rows + 63) / 64)), block(64 * (H / ccx_mlp::kGroup));
     const bool stats = logp_or_null || entropy_or_null, det = deterministic != 0;

@@ -185,14 +185,6 @@ __global__ __launch_bounds__(64) void moments_final_kernel(const MomentArgs A) {
     }
 }
 
-int check_rows(const char* who, int64_t rows, int64_t per_block, unsigned& blocks) {
-    if (rows < 1) return fail(CCX_EINVAL, "%s: rows must be at least 1, got %lld", who, (long long)rows);
-    const int64_t b = (rows + per_block - 1) / per_block;
-    if (b > 0x7FFFFFFFll) return fail(CCX_EINVAL, "%s: %lld rows need more than 2^31 - 1 workgroups", who, (long long)rows);
-    blocks = (unsigned)b;
-    return CCX_OK;
-}
-
 bool finite_nonneg(float v) { return v >= 0.0f && v < __builtin_inff(); }                // (false for NaN)
 
 int check_hyper(const char* who, float clip, float vf_coef, float ent_coef, float adv_eps) {
@@ -224,7 +216,7 @@ int ccx_masked_moments(ccx_handle* h, int64_t rows, const float* x, const uint8_
     if (!h) return fail(CCX_EINVAL, "NULL handle");
     if (!x || !workspace || !out) return fail(CCX_EINVAL, "ccx_masked_moments: NULL argument (x, workspace and out are required)");
     unsigned blocks = 0;
-    if (int rc = check_rows("ccx_masked_moments", rows, ccx_ppo::kBlockRows, blocks)) return rc;
+    if (int rc = ccxi::row_blocks("ccx_masked_moments", rows, ccx_ppo::kBlockRows, blocks)) return rc;
     if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "ccx_masked_moments: workspace must be 8-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     MomentArgs A{};
@@ -248,7 +240,7 @@ int ccx_ppo_loss(ccx_handle* h, int64_t rows, const float* logits, const uint8_t
     if (!logits || !actions || !logp_old || !advantages || !returns || !values || !workspace || !stats)
         return fail(CCX_EINVAL, "ccx_ppo_loss: NULL argument (only masks, valid and norm may be NULL)");
     unsigned blocks = 0;
-    if (int rc = check_rows("ccx_ppo_loss", rows, ccx_ppo::kBlockRows, blocks)) return rc;
+    if (int rc = ccxi::row_blocks("ccx_ppo_loss", rows, ccx_ppo::kBlockRows, blocks)) return rc;
     if (reinterpret_cast<uintptr_t>(logits) & 15u) return fail(CCX_EINVAL, "ccx_ppo_loss: logits must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "ccx_ppo_loss: workspace must be 8-byte aligned");
     if (int rc = check_hyper("ccx_ppo_loss", clip, vf_coef, ent_coef, adv_eps)) return rc;
@@ -286,7 +278,7 @@ int ccx_ppo_loss_backward(ccx_handle* h, int64_t rows, const float* logits, cons
     if (!grad_logits_or_null && !grad_values_or_null)
         return fail(CCX_EINVAL, "ccx_ppo_loss_backward: both gradient outputs are NULL (at least one of grad_logits, grad_values is required)");
     unsigned blocks = 0;
-    if (int rc = check_rows("ccx_ppo_loss_backward", rows, 64, blocks)) return rc;
+    if (int rc = ccxi::row_blocks("ccx_ppo_loss_backward", rows, 64, blocks)) return rc;
     if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(grad_logits_or_null)) & 15u)
         return fail(CCX_EINVAL, "ccx_ppo_loss_backward: logits and grad_logits must be 16-byte aligned");
     if (int rc = check_hyper("ccx_ppo_loss_backward", clip, vf_coef, ent_coef, adv_eps)) return rc;

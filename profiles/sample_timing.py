@@ -98,6 +98,7 @@ def measure(wl, E, calls, replays):
                 side.synchronize()
                 times[name].append((time.perf_counter() - t0) / (replays * calls) * 1e6)
         # the torch compositions sample from the same distribution: a wrong yardstick would be no yardstick
+        env.reset_from_pool()                   # the step variant ran every episode to its end: a dead slot's 255 is no index to gather with
         gumbel()
         bodies["sample"]()
         side.synchronize()
