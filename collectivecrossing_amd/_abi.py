@@ -147,6 +147,8 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_ppo_loss_backward": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 9 + [C.c_float] * 4 + [C.c_void_p] * 4),
     "ccx_mlp_forward": (C.c_int, [_H, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p] * 7),
     "ccx_mlp_sample_actions": (C.c_int, [_H, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 4),
+    "ccx_mlp_backward_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "ccx_mlp_backward": (C.c_int, [_H, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p] * 10),
     "ccx_set_check_inputs": (C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),

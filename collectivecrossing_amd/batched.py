@@ -25,8 +25,8 @@ import torch
 from . import _abi
 from ._lib import check, load
 from .configs import CollectiveCrossingConfig
-from .learner import (MLP_ACTIVATIONS, EvalResult, GaeResult, LearnerOps, MlpHead, PpoLossResult,  # noqa: F401 (re-exported)
-                      SampleResult, _EvaluateActions, _MlpForward, _PpoLoss, _ptr, _require)
+from .learner import (MLP_ACTIVATIONS, EvalResult, GaeResult, LearnerOps, MlpGradResult, MlpHead,  # noqa: F401 (re-exported)
+                      PpoLossResult, SampleResult, _EvaluateActions, _MlpForward, _PpoLoss, _ptr, _require)
 from .params import agent_ids, array_form_strategies, lower_config, position_only_tables
 from .reset import build_reset_pool, seeded_positions
 

@@ -1,5 +1,6 @@
 """The learner's half of the loop on the device: advantages (CCX_GAE), masked sampling (CCX_SAMPLE), stored actions under
-new logits (CCX_EVALUATE), the PPO loss (CCX_PPO_LOSS) and the two-layer policy head (CCX_MLP) of ``include/ccx.h``.
+new logits (CCX_EVALUATE), the PPO loss (CCX_PPO_LOSS) and the two-layer policy head with its backward pass (CCX_MLP) of
+``include/ccx.h``.
 
 :class:`LearnerOps` carries the methods and is mixed into :class:`~collectivecrossing_amd.batched.BatchedCollectiveCrossing`;
 the result dataclasses, :class:`MlpHead` and the three ``torch.autograd.Function`` classes live here with it.  What a tensor
@@ -64,6 +65,21 @@ class PpoLossResult:
     approx_kl = property(lambda self: self.stats[4])
     clip_frac = property(lambda self: self.stats[5])
     count = property(lambda self: self.stats[6])
+
+
+@dataclass
+class MlpGradResult:
+    """The parameter gradients of an :class:`MlpHead` (:meth:`BatchedCollectiveCrossing.mlp_backward`, include/ccx.h
+    CCX_MLP, backward): every element of every tensor is written, and every bit follows the written rule.  ``grad_a`` is the
+    gradient at the pre-activations (``None`` unless asked for); ``workspace`` is the static buffer of
+    :meth:`alloc_mlp_backward` (else ``None``)."""
+
+    w1t: torch.Tensor                         # f32 [L, H]
+    b1: torch.Tensor                          # f32 [H]
+    w2: torch.Tensor                          # f32 [O, H]
+    b2: torch.Tensor                          # f32 [O]
+    grad_a: torch.Tensor | None = None        # f32 [..., H]
+    workspace: torch.Tensor | None = None     # u8 [ccx_mlp_backward_workspace_bytes(rows, L, H, O)]
 
 
 def _ptr(t: torch.Tensor | None) -> C.c_void_p:
@@ -212,16 +228,94 @@ class LearnerOps:
         return out
 
     # ------------------------------------------------------------------ the policy head: observation rows to logits
-    def mlp_head(self, H: int, O: int = 5, activation: str = "tanh", L: int | None = None) -> "MlpHead":
+    def mlp_head(self, H: int, O: int = 5, activation: str = "tanh", L: int | None = None, backward: str = "torch") -> "MlpHead":
         """A two-layer perceptron ``Linear(L, H) -> tanh | relu -> Linear(H, O)`` whose forward is ONE kernel with bit-defined
         outputs (:class:`MlpHead`, include/ccx.h CCX_MLP).  ``L`` defaults to ``obs_len``; ``H`` is a multiple of 16 in
-        16..256, ``O`` in 1..8.  ``O = 5`` is an actor for :meth:`mlp_sample_actions`, ``O = 1`` a critic."""
-        return MlpHead(self, H, O, activation, L)
+        16..256, ``O`` in 1..8.  ``O = 5`` is an actor for :meth:`mlp_sample_actions`, ``O = 1`` a critic.  ``backward``:
+        ``"torch"`` (ordinary f32 torch on the saved activations) or ``"device"`` (:meth:`mlp_backward`: bit-defined)."""
+        return MlpHead(self, H, O, activation, L, backward)
 
     def _mlp_forward(self, head: "MlpHead", x: torch.Tensor, y: torch.Tensor, hidden: torch.Tensor | None) -> None:
         self._order_after_current_stream(x, head.w1t, head.b1, head.w2, head.b2, y, hidden)
         check(self._lib.ccx_mlp_forward(self._h, x.numel() // head.L, head.L, head.H, head.O, head.activation_id, _ptr(x),
                                         _ptr(head.w1t), _ptr(head.b1), _ptr(head.w2), _ptr(head.b2), _ptr(y), _ptr(hidden)))
+
+    def _mlp_backward_workspace(self, dims, rows: int, workspace: torch.Tensor | None) -> torch.Tensor:
+        """The workspace of a backward over ``rows`` rows: the caller's, checked, or one from torch's allocator (so a call
+        inside a graph capture stays capturable)."""
+        need = int(self._lib.ccx_mlp_backward_workspace_bytes(int(rows), *dims[:3]))
+        if workspace is None:
+            return self._new((max(8, need),), torch.uint8)
+        # (inline: a minimum length, not a shape, and the alignment is part of the one message)
+        if (not isinstance(workspace, torch.Tensor) or workspace.dtype is not torch.uint8 or workspace.device != self.device
+                or workspace.dim() != 1 or workspace.numel() < need or not workspace.is_contiguous() or workspace.data_ptr() % 8):
+            raise ValueError(f"workspace must be a contiguous, 8-byte aligned torch.uint8 tensor of at least {need} bytes on "
+                             f"{self.device} (alloc_mlp_backward)")
+        return workspace
+
+    def _check_head(self, head) -> None:
+        if not isinstance(head, MlpHead) or head.batch is not self:
+            raise ValueError("head must be an MlpHead of this batch (mlp_head)")
+        head._check_parameters()
+
+    def alloc_mlp_backward(self, head: "MlpHead", shape, want_grad_a: bool = False) -> "MlpGradResult":
+        """Static buffers of :meth:`mlp_backward` for rows of the leading shape ``shape``: the four gradients, ``grad_a`` if
+        asked for, and the workspace (for a captured graph)."""
+        self._check_head(head)
+        shape = tuple(int(v) for v in shape)
+        rows = int(np.prod(shape)) if shape else 1
+        f = torch.float32
+        return MlpGradResult(self._new((head.L, head.H), f), self._new((head.H,), f), self._new((head.O, head.H), f),
+                             self._new((head.O,), f), self._new(shape + (head.H,), f) if want_grad_a else None,
+                             self._mlp_backward_workspace(head.dims, max(rows, 1), None))
+
+    def _mlp_backward(self, dims, x, hidden, grad_y, w2, out: "MlpGradResult") -> "MlpGradResult":
+        """:meth:`mlp_backward` on explicit sizes ``dims`` = (L, H, O, activation id) and an explicit ``w2``; ``out`` holds
+        the four gradients, ``grad_a`` or ``None`` and a workspace or ``None``."""
+        L, H, O, act = dims
+        lead = tuple(x.shape[:-1]) if isinstance(x, torch.Tensor) else ()
+        f = torch.float32
+        _require_all(self.device,
+                     ("x", x, f, (..., L), {"align": 16}), ("hidden", hidden, f, lead + (H,), {"align": 16}),
+                     ("grad_y", grad_y, f, lead + (O,)), ("w2", w2, f, (O, H)),
+                     ("out.w1t", out.w1t, f, (L, H)), ("out.b1", out.b1, f, (H,)), ("out.w2", out.w2, f, (O, H)),
+                     ("out.b2", out.b2, f, (O,)), ("out.grad_a", out.grad_a, f, lead + (H,), {"optional": True, "align": 16}))
+        rows = x.numel() // L
+        if rows == 0:
+            for t in (out.w1t, out.b1, out.w2, out.b2):
+                t.zero_()
+            return out
+        workspace = self._mlp_backward_workspace(dims, rows, out.workspace)
+        x, hidden, grad_y, w2 = x.detach(), hidden.detach(), grad_y.detach(), w2.detach()
+        self._order_after_current_stream(x, hidden, grad_y, w2, workspace, out.w1t, out.b1, out.w2, out.b2, out.grad_a)
+        check(self._lib.ccx_mlp_backward(self._h, rows, L, H, O, act, _ptr(x), _ptr(hidden), _ptr(grad_y), _ptr(w2),
+                                         _ptr(workspace), _ptr(out.w1t), _ptr(out.b1), _ptr(out.w2), _ptr(out.b2),
+                                         _ptr(out.grad_a)))
+        self._current_stream_waits()
+        return out
+
+    def mlp_backward(self, head: "MlpHead", x: torch.Tensor, hidden: torch.Tensor, grad_y: torch.Tensor,
+                     want_grad_a: bool = False, out: "MlpGradResult | None" = None) -> "MlpGradResult":
+        """The gradients of ``head``'s four parameter arrays from the gradient of its outputs, on the device
+        (``ccx_mlp_backward``, include/ccx.h CCX_MLP): two kernels on the handle's stream, bit-defined -- f32 per row, then
+        f64 chains over blocks of 256 rows and CCX_PPO_LOSS's final step, a tree fixed by the number of rows alone -- so the
+        same rows give the same gradient bits on any machine, eager or captured.
+
+        ``x`` f32 [..., L] (contiguous, 16-byte aligned), ``hidden`` f32 [..., H] (what the forward saved: ``head(x,
+        hidden_out=)``; 16-byte aligned), ``grad_y`` f32 [..., O].  ``want_grad_a`` also returns the gradient at the
+        pre-activations, f32 [..., H] (``grad_a @ w1t.t()`` is the gradient with respect to ``x``, which the library does not
+        form).  ``out`` reuses a result of :meth:`alloc_mlp_backward` (its ``grad_a`` decides, ``want_grad_a`` is then
+        ignored); otherwise the workspace comes from torch's allocator, so the call captures.  A wrong dtype, shape or
+        device, a non-contiguous tensor, a misaligned pointer or a workspace that is too small raises ``ValueError`` before
+        the library is called; zero rows return zeros without calling it.  Only enqueues."""
+        self._check_head(head)
+        _require_out(out, MlpGradResult, "alloc_mlp_backward")
+        if out is None:
+            f = torch.float32
+            lead = tuple(x.shape[:-1]) if isinstance(x, torch.Tensor) else ()
+            out = MlpGradResult(self._new((head.L, head.H), f), self._new((head.H,), f), self._new((head.O, head.H), f),
+                                self._new((head.O,), f), self._new(lead + (head.H,), f) if want_grad_a else None, None)
+        return self._mlp_backward(head.dims, x, hidden, grad_y, head.w2, out)
 
     def mlp_sample_actions(self, head: "MlpHead", obs: torch.Tensor, masks: torch.Tensor | None = None,
                            deterministic: bool = False, want_logp: bool = True, want_entropy: bool = False,
@@ -565,6 +659,7 @@ class _PpoLoss(torch.autograd.Function):
 
 
 MLP_ACTIVATIONS = {"tanh": 0, "relu": 1}
+MLP_BACKWARDS = ("torch", "device")
 
 
 class MlpHead(torch.nn.Module):
@@ -578,15 +673,19 @@ class MlpHead(torch.nn.Module):
     no packing launch sits in the loop.  They are initialised as ``torch.nn.Linear`` initialises (the two layers drawn in
     order from torch's generator); :meth:`from_linear` and :meth:`to_sequential` convert by exact copies.
 
-    ``head(x, out=None)``: ``x`` f32 [..., L], contiguous, 16-byte aligned, on the batch's device; returns f32 [..., O].
-    Without grad this is the one launch, and ``out=`` reuses a tensor (static buffers for a captured graph).  When grad mode
-    is on and a parameter or ``x`` requires a gradient, the call is a ``torch.autograd.Function``: the forward is the same
-    kernel -- the same bits -- with the hidden activations saved, ``out=`` is refused, and the backward is a torch
-    composition on those activations (matrix products and sums in ordinary f32: correct to rounding, NOT bit-defined).
-    Anything else than the tensors described raises ``ValueError`` before the library is called; zero rows return an empty
-    tensor without calling it."""
+    ``head(x, out=None, hidden_out=None)``: ``x`` f32 [..., L], contiguous, 16-byte aligned, on the batch's device; returns
+    f32 [..., O].  Without grad this is the one launch, ``out=`` reuses a tensor and ``hidden_out=`` (f32 [..., H], 16-byte
+    aligned) receives the activations: with :meth:`BatchedCollectiveCrossing.mlp_backward` ``(out=)`` the static-buffer
+    forward / backward pair for a captured graph.  When grad mode is on and a parameter or ``x`` requires a gradient, the
+    call is a ``torch.autograd.Function``: the forward is the same kernel -- the same bits -- with the hidden activations
+    saved, ``out=`` and ``hidden_out=`` are refused, and the backward is chosen by ``backward``: ``"torch"`` (the default) is
+    a torch composition on those activations (matrix products and sums in ordinary f32: correct to rounding, NOT
+    bit-defined); ``"device"`` is ``ccx_mlp_backward``, whose four parameter gradients are bit-defined (the gradient with
+    respect to ``x``, formed only when ``x`` requires one, stays a torch product).  Anything else than the tensors described
+    raises ``ValueError`` before the library is called; zero rows return an empty tensor without calling it."""
 
-    def __init__(self, batch: BatchedCollectiveCrossing, H: int, O: int = 5, activation: str = "tanh", L: int | None = None):
+    def __init__(self, batch: BatchedCollectiveCrossing, H: int, O: int = 5, activation: str = "tanh", L: int | None = None,
+                 backward: str = "torch"):
         super().__init__()
         L = batch.obs_len if L is None else L
         for name, v, lo, hi in (("L", L, 1, 512), ("H", H, 16, 256), ("O", O, 1, 8)):
@@ -596,9 +695,13 @@ class MlpHead(torch.nn.Module):
             raise ValueError(f"H must be a multiple of 16, got {H}")
         if activation not in MLP_ACTIVATIONS:
             raise ValueError(f"activation must be one of {sorted(MLP_ACTIVATIONS)}, got {activation!r}")
+        if backward not in MLP_BACKWARDS:
+            raise ValueError(f"backward must be one of {list(MLP_BACKWARDS)}, got {backward!r}")
+        self.backward = backward
         object.__setattr__(self, "batch", batch)                          # (not a submodule, not part of the state dict)
         self.L, self.H, self.O, self.activation = L, H, O, activation
         self.activation_id = MLP_ACTIVATIONS[activation]
+        self.dims = (L, H, O, self.activation_id)
         lin1, lin2 = torch.nn.Linear(L, H), torch.nn.Linear(H, O)
         dev = batch.device
         self.w1t = torch.nn.Parameter(lin1.weight.detach().t().contiguous().to(dev))
@@ -608,13 +711,13 @@ class MlpHead(torch.nn.Module):
 
     @classmethod
     def from_linear(cls, batch: BatchedCollectiveCrossing, lin1: torch.nn.Linear, lin2: torch.nn.Linear,
-                    activation: str = "tanh") -> "MlpHead":
+                    activation: str = "tanh", backward: str = "torch") -> "MlpHead":
         """The head that computes ``lin2(act(lin1(x)))``: exact copies of the two layers' f32 parameters."""
         if (not isinstance(lin1, torch.nn.Linear) or not isinstance(lin2, torch.nn.Linear) or lin1.bias is None
                 or lin2.bias is None or lin1.out_features != lin2.in_features or lin1.weight.dtype is not torch.float32
                 or lin2.weight.dtype is not torch.float32):
             raise ValueError("from_linear needs two f32 torch.nn.Linear layers with biases, lin1.out_features == lin2.in_features")
-        head = cls(batch, lin1.out_features, lin2.out_features, activation, lin1.in_features)
+        head = cls(batch, lin1.out_features, lin2.out_features, activation, lin1.in_features, backward)
         with torch.no_grad():
             head.w1t.copy_(lin1.weight.t())
             head.b1.copy_(lin1.bias)
@@ -634,20 +737,21 @@ class MlpHead(torch.nn.Module):
         return torch.nn.Sequential(lin1, torch.nn.Tanh() if self.activation == "tanh" else torch.nn.ReLU(), lin2)
 
     def extra_repr(self) -> str:
-        return f"L={self.L}, H={self.H}, O={self.O}, activation={self.activation}"
+        return f"L={self.L}, H={self.H}, O={self.O}, activation={self.activation}, backward={self.backward}"
 
     def _check_parameters(self) -> None:
         for name, shape in (("w1t", (self.L, self.H)), ("b1", (self.H,)), ("w2", (self.O, self.H)), ("b2", (self.O,))):
             _require(name, getattr(self, name), torch.float32, shape, self.batch.device, verb="stay")
 
-    def forward(self, x: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    def forward(self, x: torch.Tensor, out: torch.Tensor | None = None, hidden_out: torch.Tensor | None = None) -> torch.Tensor:
         b = self.batch
         _require("x", x, torch.float32, (..., self.L), b.device, align=16)
         self._check_parameters()
         shape = tuple(x.shape[:-1]) + (self.O,)
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            if out is not None:
-                raise ValueError("out= cannot be used when a gradient is required (the autograd path allocates its outputs)")
+            if out is not None or hidden_out is not None:
+                raise ValueError("out= and hidden_out= cannot be used when a gradient is required (the autograd path allocates "
+                                 "its outputs)")
             if x.numel() == 0:
                 return x.new_zeros(shape) + self.b2 * 0.0
             return _MlpForward.apply(self, x, self.w1t, self.b1, self.w2, self.b2)
@@ -655,14 +759,16 @@ class MlpHead(torch.nn.Module):
             out = b._new(shape, torch.float32)
         else:
             _require("out", out, torch.float32, shape, b.device)
+        _require("hidden_out", hidden_out, torch.float32, tuple(x.shape[:-1]) + (self.H,), b.device, optional=True, align=16)
         if x.numel():
-            b._mlp_forward(self, x.detach(), out, None)
+            b._mlp_forward(self, x.detach(), out, hidden_out)
         return out
 
 
 class _MlpForward(torch.autograd.Function):
     """:class:`MlpHead` when a gradient is required: the forward is the kernel of CCX_MLP with the activations saved; the
-    backward is ordinary f32 torch on them (not bit-defined)."""
+    backward is ordinary f32 torch on them (``backward="torch"``: not bit-defined) or ``ccx_mlp_backward`` (``"device"``:
+    the four parameter gradients bit-defined; the gradient of ``x``, where required, a torch product on its ``grad_a``)."""
 
     @staticmethod
     def forward(ctx, head, x, w1t, b1, w2, b2):
@@ -673,6 +779,7 @@ class _MlpForward(torch.autograd.Function):
         b._mlp_forward(head, x, y, hidden)
         b._current_stream_waits()
         ctx.relu = head.activation == "relu"
+        ctx.batch, ctx.dims, ctx.device_backward = b, head.dims, head.backward == "device"
         ctx.save_for_backward(x, w1t.detach(), w2.detach(), hidden)
         return y
 
@@ -681,10 +788,18 @@ class _MlpForward(torch.autograd.Function):
     def backward(ctx, gy):
         x, w1t, w2, hidden = ctx.saved_tensors
         L, H, O = x.shape[-1], hidden.shape[-1], gy.shape[-1]
+        need = ctx.needs_input_grad
+        if ctx.device_backward:
+            b, f = ctx.batch, torch.float32
+            out = MlpGradResult(b._new((L, H), f), b._new((H,), f), b._new((O, H), f), b._new((O,), f),
+                                b._new(tuple(hidden.shape), f) if need[1] else None, None)
+            b._mlp_backward(ctx.dims, x, hidden, gy.contiguous(), w2, out)
+            gx = (out.grad_a.reshape(-1, H) @ w1t.t()).reshape(x.shape) if need[1] else None
+            return (None, gx, out.w1t if need[2] else None, out.b1 if need[3] else None, out.w2 if need[4] else None,
+                    out.b2 if need[5] else None)
         gy, h, x2 = gy.contiguous().reshape(-1, O), hidden.reshape(-1, H), x.reshape(-1, L)
         gh = gy @ w2
         ga = gh * (h > 0) if ctx.relu else gh * (1.0 - h * h)
-        need = ctx.needs_input_grad
         gx = (ga @ w1t.t()).reshape(x.shape) if need[1] else None
         gw1t = x2.t() @ ga if need[2] else None
         gb1 = ga.sum(0) if need[3] else None

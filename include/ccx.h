@@ -850,8 +850,50 @@ int ccx_ppo_loss_backward(ccx_handle* h, int64_t rows, const float* logits /* [M
  * for every slot, dead ones included.  A NULL handle or a NULL required pointer (everything but hidden, masks, logp, entropy,
  * logits_or_null), rows < 1, rows beyond 2^31 - 1 workgroups of 64 rows, a size outside the limits, x / obs or hidden not
  * 16-byte aligned, or any other f32 array not 4-byte aligned: CCX_EINVAL with a ccx_last_error message, before any launch.
- * Offsets are 64-bit.  Not here: deeper or wider networks, bf16 / f16, a bit-defined backward pass (the Python layer's is
- * ordinary f32 torch on the saved activations).
+ * Offsets are 64-bit.
+ *
+ * Backward (ccx_mlp_backward): the gradients of the four parameter arrays, bit-defined.  Inputs (device pointers), M >= 1
+ * rows: x f32 [M][L], hidden f32 [M][H] (what ccx_mlp_forward wrote), grad_y f32 [M][O], w2 f32 [O][H], activation; the
+ * limits on L, H, O and activation are the forward's.  The discipline is the forward's and CCX_PPO_LOSS's: every f32
+ * operation named is ONE correctly rounded f32 operation, every f64 operation named ONE correctly rounded f64 operation,
+ * nothing is fused, nothing is reassociated, subnormals are kept.
+ * Per row r, in f32 (a row's values depend on that row and w2 only):
+ *   1. for every hidden unit j: gh = grad_y[r][0] * w2[0][j]; then for o = 1 .. O-1 in order gh = gh + grad_y[r][o] * w2[o][j].
+ *   2. ga[r][j], with h = hidden[r][j]:
+ *        tanh: hh = h * h;  d = 1.0f - hh;  ga = gh * d
+ *        relu: ga = (h > 0.0f) ? gh : +0.0f                        (a select: a NaN h gives +0.0f)
+ *      A NaN that an operation produces propagates; its sign and payload are not defined, as in the forward.
+ * Terms.  Every term is the product of two f32 values converted to f64, which is exact in f64 (so acc + a * b as one f64 fma
+ * and as an exact multiply followed by one add give the same bits; an implementation may use either):
+ *     grad_w1t[k][j] sums (double)x[r][k] * (double)ga[r][j] over r        grad_b1[j] sums (double)ga[r][j]
+ *     grad_w2[o][j]  sums (double)grad_y[r][o] * (double)hidden[r][j]      grad_b2[o] sums (double)grad_y[r][o]
+ * Reduction over rows.  The tree is fixed by M alone (not by the CU count, a launch shape or a tunable); there is no
+ * floating-point atomic:
+ *   - rows are cut into B = ceil(M / 256) blocks of 256 consecutive rows;
+ *   - a block's partial of an output element is a chain: it starts from +0.0 and adds the block's terms in ascending row
+ *     order; rows >= M add nothing.  (A chain, not CCX_PPO_LOSS's halving, because the natural mapping differs: a thread
+ *     owns output elements and walks the rows, a lane does not own a row, so no element needs a reduction across lanes.)
+ *   - the final step over the B partials P of an element is CCX_PPO_LOSS's, unchanged: place j of 64 starts from +0.0 and adds
+ *     P[j], P[j + 64], ... in ascending order; the 64 places are then halved, for o = 32, 16, 8, 4, 2, 1.
+ * Each output is rounded to f32 once; every element of every output is written.  grad_a_or_null f32 [M][H] receives ga of
+ * every row (bit-defined, per row).
+ * Against IEEE f64 (measured on the CPU, tests/test_mlp_backward_spec.py, maxima doubled), as max |err| / max(1, |f64 value|)
+ * against the textbook composition in f64 on the same f32 x, hidden, grad_y and w2 (gh = grad_y w2, ga = gh (1 - h^2) or
+ * gh (h > 0), then matrix products), L = 38, H = 64, O = 5, torch.nn.Linear's initial weights, observation-like rows,
+ * M = 20 000: grad_w1t within 2.9e-5, grad_b1 3.7e-6, grad_w2 1.2e-7, grad_b2 9.2e-8 (both sides read the same hidden, so no
+ * row is left out).
+ * ccx_mlp_backward only enqueues TWO plain launches on the handle's stream (block partials, then the final step; no
+ * last-block-done counter, for the reason CCX_PPO_LOSS gives): no host synchronisation, no allocation, and it captures into
+ * a HIP graph.  The caller owns the workspace: ccx_mlp_backward_workspace_bytes(rows, L, H, O) =
+ * B * (L * H + H + O * H + O) * 8 bytes (46 MB at 524 288 rows of L = 38, H = 64, O = 5; 0 for rows < 1 or a shape outside the
+ * limits), 8-byte aligned; its layout is private and its contents mean nothing between calls.  Offsets are 64-bit.  A NULL
+ * handle or a NULL required pointer (everything but grad_a), rows < 1, B beyond 2^31 - 1, a shape outside the limits, x,
+ * hidden or grad_a not 16-byte aligned, a workspace not 8-byte aligned, or any other f32 array not 4-byte aligned: CCX_EINVAL
+ * with a ccx_last_error message, before any launch.
+ *
+ * Not here: deeper or wider networks, bf16 / f16, the gradient with respect to x (observation rows are inputs and nothing
+ * here learns upstream of them; the Python layer forms ga w1t^T in ordinary f32 torch when x requires a gradient: correct
+ * to rounding, not bit-defined), the optimiser.
  */
 int ccx_mlp_forward(ccx_handle* h, int64_t rows, int32_t L, int32_t H, int32_t O, int32_t activation, const float* x /* [rows][L] */,
                     const float* w1t /* [L][H] */, const float* b1 /* [H] */, const float* w2 /* [O][H] */, const float* b2 /* [O] */,
@@ -861,6 +903,11 @@ int ccx_mlp_sample_actions(ccx_handle* h, int32_t H, int32_t activation, const f
                            const float* b2 /* [5] */, const uint8_t* masks_or_null /* [E][N] */, int32_t deterministic,
                            uint8_t* actions /* [E][N] */, float* logp_or_null /* [E][N] */, float* entropy_or_null /* [E][N] */,
                            float* logits_or_null /* [E][N][5] */);
+int64_t ccx_mlp_backward_workspace_bytes(int64_t rows, int32_t L, int32_t H, int32_t O);
+int ccx_mlp_backward(ccx_handle* h, int64_t rows, int32_t L, int32_t H, int32_t O, int32_t activation, const float* x /* [rows][L] */,
+                     const float* hidden /* [rows][H] */, const float* grad_y /* [rows][O] */, const float* w2 /* [O][H] */,
+                     void* workspace, float* grad_w1t /* [L][H] */, float* grad_b1 /* [H] */, float* grad_w2 /* [O][H] */,
+                     float* grad_b2 /* [O] */, float* grad_a_or_null /* [rows][H] */);
 /*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
