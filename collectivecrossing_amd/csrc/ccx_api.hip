@@ -48,51 +48,22 @@ using ccxp::ceil_log2;
 
 namespace {
 
-// Per-cell geometry table of the padded grid (layout: ccx_kernels.hip, struct CellInfo).  This is
+// Per-cell geometry table of the padded grid (layout and rule: ccx_step_rule.h, cell_word).  This is
 // config lowering, done once per handle: the reference evaluates the same predicates per agent
 // per step (collectivecrossing.py:509-534, 551-563, 663-683; rewards.py:44-182).
 std::vector<unsigned long long> build_cell_table(const ccx_params& p, const std::vector<uint8_t>* term_table = nullptr) {
     const int Wp = p.width + 3, Hp = p.height + 3;
-    const int dc = (p.door_left + p.door_right) / 2;
-    auto cell_ok = [&](int x, int y) {   // collectivecrossing.py:509-534
-        if (!(x >= 0 && x <= p.width && y >= 0 && y <= p.height)) return false;
-        if (y == p.division_y && !(p.door_left < x && x < p.door_right)) return false;
-        if (y >= p.division_y && !(p.tram_left < x && x < p.tram_right)) return false;
-        return true;
+    const ccx::CellGeometry g{p.width, p.height, p.division_y, p.tram_left, p.tram_right, p.door_left, p.door_right,
+                              p.boarding_dest_y, p.exiting_dest_y};
+    // terminateds[id] of agent type t on (x, y) by the user's table (ccx_set_terminated_table), -1 = the built-in rule
+    auto user_term = [&](int t, int x, int y) {
+        if (!term_table || term_table[t].empty() || x < 0 || x > p.width || y < 0 || y > p.height) return -1;
+        return term_table[t][(size_t)y * (size_t)(p.width + 1) + (size_t)x] != 0 ? 1 : 0;
     };
-    static const int DX[4] = {1, 0, -1, 0}, DY[4] = {0, 1, 0, -1};   // actions.py:18-24
     std::vector<unsigned long long> tab((size_t)Wp * Hp, 0ull);
-    for (int y = 0; y <= p.height; ++y)
-        for (int x = 0; x <= p.width; ++x) {   // border cells stay 0: never occupied
-            unsigned nv = 0;
-            for (int a = 0; a < 4; ++a) nv |= (cell_ok(x + DX[a], y + DY[a]) ? 1u : 0u) << a;
-            const bool in_area = y >= p.division_y && p.tram_left <= x && x <= p.tram_right;
-            const bool at_door = y == p.division_y && (x == p.door_left - 1 || x == p.door_right + 1);
-            const bool dest_b = y == p.boarding_dest_y, dest_e = y == p.exiting_dest_y;
-            const int adx = x > dc ? x - dc : dc - x;
-            unsigned cls_b = 1, cls_e = 1;   // binary / constant_negative: always the constant rA
-            int sd_b = 0, sd_e = 0;
-            if (p.reward_mode == CCX_REWARD_DEFAULT) {
-                cls_b = dest_b ? 1 : at_door ? 2 : in_area ? 3 : 0;
-                cls_e = dest_e ? 1 : !in_area ? 3 : 0;
-                sd_b = -(adx + (p.division_y - y));
-                sd_e = adx + (y - p.division_y);
-            } else if (p.reward_mode == CCX_REWARD_SIMPLE_DISTANCE) {
-                cls_b = cls_e = 0;
-                sd_b = -(y > p.boarding_dest_y ? y - p.boarding_dest_y : p.boarding_dest_y - y);
-                sd_e = -(y > p.exiting_dest_y ? y - p.exiting_dest_y : p.exiting_dest_y - y);
-            }
-            // terminateds[id] on this cell (terminateds.py:66-82): the destination row, or the user's table
-            const size_t ci = (size_t)y * (size_t)(p.width + 1) + (size_t)x;
-            const bool term_b = (term_table && !term_table[0].empty()) ? term_table[0][ci] != 0 : dest_b;
-            const bool term_e = (term_table && !term_table[1].empty()) ? term_table[1][ci] != 0 : dest_e;
-            unsigned lo = nv | (in_area ? ccx::kCellInTram : 0u) | (at_door ? ccx::kCellAtDoor : 0u) |
-                          ((dest_b ? 1u : 0u) << 8) | (cls_b << 9) | ((term_b ? 1u : 0u) << (8 + ccx::kCellTermShift)) |
-                          ((dest_e ? 1u : 0u) << 12) | (cls_e << 13) | ((term_e ? 1u : 0u) << (12 + ccx::kCellTermShift)) |
-                          ((unsigned)x << 16) | ((unsigned)y << 24);
-            unsigned hi = ((unsigned)sd_b & 0xFFFFu) | (((unsigned)sd_e & 0xFFFFu) << 16);
-            tab[(size_t)(y + 1) * Wp + (x + 1)] = (unsigned long long)lo | ((unsigned long long)hi << 32);
-        }
+    for (int y = -1; y <= p.height + 1; ++y)
+        for (int x = -1; x <= p.width + 1; ++x)
+            tab[(size_t)ccx::cell_index(x, y, Wp)] = ccx::cell_word(g, p.reward_mode, x, y, user_term(0, x, y), user_term(1, x, y));
     return tab;
 }
 
@@ -132,8 +103,7 @@ void fill_config(const ccx_handle* h, ccx::KParams& k) {
     // cursor stride of the reset pool: entry (global_env + episode * stride) mod P.  total_envs mod P keeps
     // the walk independent of the world size; when P divides total_envs that would be 0 and every env
     // would restart from ONE placement forever, so the stride is 1 then (env e walks e, e+1, e+2, ...)
-    k.pool_stride = h->pool_size > 0 ? (long long)(h->total_envs % h->pool_size) : 0;
-    if (h->pool_size > 0 && k.pool_stride == 0) k.pool_stride = 1 % h->pool_size;
+    k.pool_stride = h->pool_size > 0 ? (long long)ccx::pool_stride_of((unsigned long long)h->total_envs, (unsigned long long)h->pool_size) : 0;
 }
 
 // THE place that writes a plan into the handle: h->shape* / h->kp*, h->step_shape and the pace_* fields; it also uploads the
@@ -1136,7 +1106,7 @@ int ccx_set_reward_table(ccx_handle* h, const double* boarding_per_cell, const d
     for (int t = 0; t < 2; ++t)
         for (int y = 0; y < H1; ++y)
             for (int x = 0; x < W1; ++x)
-                tab[(size_t)t * cells + (size_t)(y + 1) * Wp + (size_t)(x + 1)] = src[t][(size_t)y * W1 + x];
+                tab[(size_t)t * cells + (size_t)ccx::cell_index(x, y, Wp)] = src[t][(size_t)y * W1 + x];
     if (!h->reward_table) CCX_HIP(hipMalloc(&h->reward_table, tab.size() * sizeof(double)));
     CCX_HIP(hipMemcpy(h->reward_table, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     return choose_shape(h);

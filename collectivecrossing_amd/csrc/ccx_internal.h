@@ -40,7 +40,7 @@ struct ccx_handle {
     hipStream_t stream = nullptr;
     ccx::KState st{};
     uint8_t* st_slab = nullptr;              // ONE allocation behind the seven state arrays (ccx_kernels.h: StateSlab)
-    unsigned long long* cell_info = nullptr; // per-cell geometry table (see ccx_kernels.hip: CellInfo)
+    unsigned long long* cell_info = nullptr; // per-cell geometry table (ccx_step_rule.h: cell_word)
     double* reward_table = nullptr;          // device f64 [2][cells of the padded grid]: user reward table (ccx_set_reward_table), null = built-in
     std::vector<uint8_t> term_table[2];      // host u8 [(H+1)(W+1)] per agent type: user terminated table (ccx_set_terminated_table), empty = built-in
     uint8_t* placement_scratch = nullptr;    // u8 [E][N][2] work area of ccx_reset_seeded

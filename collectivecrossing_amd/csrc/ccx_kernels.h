@@ -3,11 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ccx_step_rule.h"   // the cell word, the reward, the flag bytes, the pool cursor (and CCX_K_REWARD_*, CCX_K_EF_*)
+
 namespace ccx {
 
 enum : uint32_t { CCX_K_ABSENT = 255u };
-enum : int { CCX_K_REWARD_DEFAULT = 0, CCX_K_REWARD_SIMPLE_DISTANCE = 1, CCX_K_REWARD_BINARY = 2,
-             CCX_K_REWARD_CONSTANT_NEGATIVE = 3 };
 enum : int { CCX_K_TERM_INDIVIDUAL = 0, CCX_K_TERM_ALL = 1 };
 enum : int { CCX_K_POLICY_GREEDY = 1, CCX_K_POLICY_WAITING = 2, CCX_K_POLICY_RANDOM = 3 };
 
@@ -65,11 +65,6 @@ constexpr uint32_t kHwCellMask = 0x1FFFFu, kHwOut2Shift = 17, kHwActShift = 19, 
 constexpr uint32_t kSyncOff = 256u, kSyncBytes = 64u, kStageOff = kSyncOff + kSyncBytes;
 constexpr uint32_t tile_head_bytes(uint32_t stage_slots) { return kStageOff + stage_slots * kStageSlotBytes; }
 constexpr uint32_t kSyncSeq = 0u, kSyncProg = 4u;          // (kSyncProg + writer index, at most 7 writers)
-// bits of the low word of a cell's geometry entry (ccx_kernels.hip: per-cell geometry table); bit 4 is always 0
-constexpr uint32_t kCellInTram = 0x20u, kCellAtDoor = 0x40u;
-// bits 11 / 15: terminateds[id] of a boarding / exiting agent on this cell (terminateds.py:66-82: = the destination-row
-// bits 8 / 12 for the built-in strategies; ccx_set_terminated_table overrides them)
-constexpr uint32_t kCellTermShift = 3u;    // (relative to the type's destination bit)
 
 // ONE definition of how a launch is driven, shared by the host (run_rollout) and the kernel: a launch is PACED when the
 // handle paces its shape, it writes observation rows and is long enough to be worth the clock reads; the pace controller
@@ -89,7 +84,6 @@ __host__ __device__ inline bool launch_uses_flags(bool handle_paces, bool writes
     return tunable >= 2 || (tunable == 1 && !launch_is_paced(handle_paces, writes_obs, K, pace_min_k));   // 0 = never, 1 = unpaced launches, 2 = always
 }
 enum : uint32_t { CCX_K_LAUNCH_ROUND = 1u };
-enum : uint32_t { CCX_K_EF_ALL_TERM = 1u, CCX_K_EF_ALL_TRUNC = 2u, CCX_K_EF_RESET = 4u };
 
 // kernel parameters (passed by value; lives in SGPRs / the kernarg segment)
 struct KParams {
@@ -120,7 +114,7 @@ struct KParams {
     double r_dest, r_door, r_area, r_f, r_nogoal, r_pen;
     long long env_offset;                // global index of env 0 (sharding)
     long long pool_size;                 // reset-pool entries (0 = none)
-    long long pool_stride;               // cursor stride: total_envs mod pool_size, 1 when that is 0
+    long long pool_stride;               // cursor stride (ccx_step_rule.h: pool_stride_of)
     // tunables (ccx_set_tunable): how the tiles' step schedules are phased, how workgroups map to tiles
     uint32_t pace_phase, tile_map;
     uint32_t wp_magic;                   // ceil(2^32 / (W + 3)): cell index / row length by one multiply-high (exact below 2^17)

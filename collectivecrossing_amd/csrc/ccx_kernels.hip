@@ -26,7 +26,7 @@
 // cell and later agents at their old cell", collectivecrossing.py:197-202,536-541):
 //   1. every lane proposes its target cell in parallel; validity of the target (bounds, walls,
 //      door) and everything else the step needs to know about a cell is ONE ds_read_b64 from a
-//      per-cell table precomputed on the host (see "per-cell geometry table" below);
+//      per-cell table precomputed on the host (ccx_step_rule.h: the cell word);
 //   2. every active agent ORs its move-rank bit into a per-env OCCUPANCY bit table (LDS, one mask
 //      per cell) at its current cell and, if its proposal is legal, into a PROPOSAL table at the
 //      target cell; reading both tables at the target gives, in O(1) per agent,
@@ -118,10 +118,8 @@ __global__ void reset_from_pool_kernel(const KParams p, const KState st,
     if (t >= total) return;
     const int env = (int)(t / p.N), i = (int)(t % p.N);
     if (env_mask && !env_mask[env]) return;
-    const unsigned long long P = (unsigned long long)p.pool_size;
-    const unsigned long long gi = (unsigned long long)(p.env_offset + env) % P;
-    const unsigned long long ep = (unsigned long long)st.episode[env] % P;
-    const unsigned long long pi = (gi + ep * (unsigned long long)p.pool_stride) % P;
+    const unsigned long long pi = pool_entry((unsigned long long)(p.env_offset + env), (unsigned long long)st.episode[env],
+                                             (unsigned long long)p.pool_stride, (unsigned long long)p.pool_size);
     const uint8_t* src = pool + ((size_t)pi * p.N + i) * 2;
     st.x[t] = src[0];
     st.y[t] = src[1];

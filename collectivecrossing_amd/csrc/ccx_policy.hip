@@ -42,8 +42,8 @@ __device__ __forceinline__ uint32_t scripted_choice(const KParams& p, const KSta
                                                     const int i, const int policy, uint32_t& free_dirs) {
     const size_t base = (size_t)env * p.N, t = base + (size_t)i;
     const int cx = st.x[t], cy = st.y[t];
-    const uint32_t cw = (uint32_t)cell_info[(cy + 1) * (p.W + 3) + cx + 1];
-    free_dirs = cw & 0xFu & ~neighbours_busy_scan(p, st, base, i);
+    const uint32_t cw = (uint32_t)cell_info[cell_index(cx, cy, p.W + 3)];
+    free_dirs = cell_legal4(cw) & ~neighbours_busy_scan(p, st, base, i);
     bool waits = false;
     if (policy == CCX_K_POLICY_WAITING && i < p.Nb && !(cw & kCellInTram)) {   // waiting_policy.py:92-100
         for (int b = p.Nb; b < p.N; ++b)                                  // :119-129
@@ -210,7 +210,7 @@ __global__ void action_masks_kernel(const KParams p, const KState st, const unsi
     if (!(st.terminated[t] || st.truncated[t])) {         // done agents are not in env.agents: wait only
         const int i = (int)(t % p.N);
         const uint32_t busy = neighbours_busy_scan(p, st, t - (size_t)i, i);
-        m |= (uint32_t)cell_info[(st.y[t] + 1) * (p.W + 3) + st.x[t] + 1] & 0xFu & ~busy;
+        m |= cell_legal4((uint32_t)cell_info[cell_index(st.x[t], st.y[t], p.W + 3)]) & ~busy;
     }
     masks[t] = (uint8_t)m;
 }

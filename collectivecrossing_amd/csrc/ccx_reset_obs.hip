@@ -56,7 +56,6 @@ reset_obs_kernel(const int E, const int N, const int Nb, const int K, const int 
     const int L = 6 + 4 * N;
     const size_t row_floats = (size_t)N * (size_t)L;             // one env-step's rows
     const int units = N * (3 + 2 * N) >> (PAIR ? 1 : 0);         // vector units of them
-    const unsigned long long gi = (env_offset_mod_pool + (unsigned long long)env) % pool_size;
     uint32_t seen = 0;                                           // restarts at earlier steps
     for (int s0 = 0; s0 < K; s0 += 64) {
         const int sl = s0 + lane;
@@ -67,7 +66,7 @@ reset_obs_kernel(const int E, const int N, const int Nb, const int K, const int 
             b &= b - 1;
             seen += 1u;
             const uint32_t ordinal = ep_after - (total - seen);  // the episode this restart opened
-            const unsigned long long pi = (gi + ((unsigned long long)ordinal % pool_size) * pool_stride) % pool_size;
+            const unsigned long long pi = pool_entry(env_offset_mod_pool + (unsigned long long)env, ordinal, pool_stride, pool_size);
             const size_t se = (size_t)s * (size_t)E + (size_t)env;
             float4 me = make_float4(0.0f, 0.0f, lane < Nb ? 0.0f : 1.0f, 1.0f);
             if (lane < N) {

@@ -53,8 +53,8 @@
     const size_t EN = (size_t)p.E * N;
     const size_t idx = (size_t)env * N + i;
     const bool boarding = i < p.Nb;
-    const uint32_t tsh = boarding ? 8u : 12u;     // type-specific nibble of the cell word
-    const uint32_t tsh2 = boarding ? 0u : 16u;    // type-specific half of the distance word
+    const uint32_t tsh = cell_tsh(boarding);      // type-specific nibble of the cell word (ccx_step_rule.h)
+    const uint32_t tsh2 = cell_tsh2(boarding);    // type-specific half of the distance word
     const int Wp = p.W + 3;
 
     // LDS carve-up: [cell table][tile 0 .. tile tpb-1][u16 obs table]; offsets from the host
@@ -166,9 +166,7 @@
             if (wsw > 1u) init_wave_consts(wl + 1, p, lane);
             const float type_f = boarding ? 0.0f : 1.0f;  // observations.py:85
             // reward constants (rewards.py:44-182): class 1/2/3 -> rA/rB/rC, class 0 -> sd * rF
-            const int rmode = p.reward_mode;
-            const double rA = in_vgpr(rmode == CCX_K_REWARD_BINARY ? p.r_nogoal
-                                      : rmode == CCX_K_REWARD_CONSTANT_NEGATIVE ? p.r_pen : p.r_dest);
+            const double rA = in_vgpr(reward_class_a(p));
             const double rB = in_vgpr(p.r_door);
             const double rC = in_vgpr(p.r_area);
             const double rF = in_vgpr(p.r_f);
@@ -393,23 +391,18 @@
                     } else {
                         const uint32_t cidx = ((hw & kHwCellMask) - lds0) >> 3;         // cell index in the padded grid
                         const uint32_t y1 = __umulhi(cidx, wp_magic), x1 = cidx - y1 * Wp_w;
-                        ilo = ((x1 - 1u) << 16) | ((y1 - 1u) << 24);                     // (bytes 2 and 3, as in the table)
+                        ilo = cell_xy_bytes(x1 - 1u, y1 - 1u);                           // (bytes 2 and 3, as in the table)
                     }
                     CCX_STAMP(0);                        // wait for the sim wave
                     const uint32_t efw = (hw >> kHwEfShift) & 7u, act_w = (hw >> kHwActShift) & 1u;
-                    // The flag byte (CCX_AF_*, collectivecrossing.py:214-254).  From the sim wave: the flags this step raises
-                    // (terminated, truncated), active, the action.  Here: live = neither flag was set BEFORE the step
-                    // (rewards.py:64, truncateds.py:56); obs = live, or a flag is newly set by this step (:243, :763-767); the
-                    // cell's own info bits; the destination bit.
+                    // The flag byte (ccx_step_rule.h: agent_flag_byte).  From the sim wave: the flags this step raises
+                    // (terminated, truncated), active, the action.  Here: this wave's copy of the pair BEFORE the step, the cell word.
                     const uint32_t out2 = (hw >> kHwOut2Shift) & 3u;
-                    const uint32_t live = tt_w == 0u ? 1u : 0u;
-                    const uint32_t emit = (live | (out2 & ~tt_w)) != 0u ? 1u : 0u;
+                    const uint32_t af = agent_flag_byte(out2, tt_w, ilo, tsh, act_w);
                     tt_w = (efw & CCX_K_EF_RESET) ? 0u : (tt_w | out2);
-                    const uint32_t af = out2 | (live << 2) | (emit << 3) | ((ilo >> 1) & 0x30u) | (act_w << 6) |
-                                        (((ilo >> tsh) & 1u) << 7);
                     if (rows_l || has_cmp) {
                         // (x, y) are bytes 2 and 3 of the cell word: v_cvt_f32_ubyte2 / ubyte3
-                        const float4 me = make_float4((float)((ilo >> 16) & 0xFFu), (float)(ilo >> 24), type_f,
+                        const float4 me = make_float4((float)cell_x(ilo), (float)cell_y(ilo), type_f,
                                                       (float)((af >> 6) & 1u));
                         if (rows_l) wl->slot[lane] = me;
                         if constexpr (PAIRS_C) {
@@ -430,8 +423,9 @@
                         // rewards.py:44-182.  Distances are integers and the reference negates the
                         // INTEGER before the one f64 multiply, so d == 0 gives +0.0 (never -0.0).
                         if (has_rew) {
-                            const uint32_t cls = (ilo >> (tsh + 1u)) & 3u;
-                            const int sd = (int)(int16_t)(uint16_t)(ihi >> tsh2);
+                            // (= cell_reward, inline: the call took <3,1,2,1,1> from 7 to 8 SGPR spills, <3,0,2,0,1> from 7 to 9)
+                            const uint32_t cls = cell_class(ilo, tsh);
+                            const int sd = cell_distance(ihi, tsh2);
                             double r = (double)sd * rF;
                             r = (cls == 1u) ? rA : r;
                             r = (cls == 2u) ? rB : r;
@@ -440,7 +434,7 @@
                                 if (rt_add)   // position-only user reward: one f64 per (type, cell)
                                     r = *(__attribute__((address_space(3))) const double*)(uintptr_t)((hw & kHwCellMask) + rt_add);
                             }
-                            r = (af & 0x04u) ? r : 0.0;      // rewards.py:64: None unless live
+                            r = reward_if_live(r, af & 0x04u);
                             if (valid) *(__attribute__((address_space(1))) double*)(PLAIN ? (gchar*)a_rew : b_rew + rew_off) = r;
                         }
                         if (valid) {
@@ -654,12 +648,12 @@
     // ---- state -> registers ------------------------------------------------------------------
     // position = byte offset of the agent's cell in the per-cell geometry table (cell index x 8): the cell word, the
     // table entry and the target of a move are all one add away
-    int c8 = (int)lds0 + (Wp + 1) * 8;        // LDS address of the word of cell (0,0)
+    int c8 = (int)lds0 + cell_origin(Wp) * 8;   // LDS address of the word of cell (0,0)
     int stepc = 0, episode = 0;
     uint32_t act = 0;                         // 0/1
     uint32_t tt = 1u;                         // terminated | truncated << 1; lanes without an agent count as done
     if (valid) {   // (loaded in front of the prologue's barrier)
-        c8 = (int)lds0 + ((s_y + 1) * Wp + s_x + 1) * 8;
+        c8 = (int)lds0 + ((s_y + 1) * Wp + s_x + 1) * 8;   // = cell_index(s_x, s_y, Wp), inline: the call changed all 32 <3,..> instantiations
         act = s_active != 0u;
         tt = tt_entry;
     }
@@ -684,15 +678,13 @@
     // total mod P per episode; the NEXT placement is prefetched right after every reset and only
     // decoded when it is consumed (so no wait sits behind the load).
     uint32_t pool_idx = 0, pnext = 0;
-    int pcell8 = (int)lds0 + (Wp + 1) * 8;
+    int pcell8 = (int)lds0 + cell_origin(Wp) * 8;
     bool pnext_pending = false;   // pnext holds a load that has not been decoded into pcell8 yet
     const bool use_pool = KA.auto_reset && KA.pool != nullptr && p.pool_size > 0;
     const uint32_t pool_size = (uint32_t)p.pool_size, pool_stride = (uint32_t)p.pool_stride;
     if (use_pool && valid) {
-        unsigned long long P = (unsigned long long)p.pool_size;
-        unsigned long long gi = (unsigned long long)(p.env_offset + env) % P;
-        unsigned long long ep = (unsigned long long)(episode + 1) % P;
-        pool_idx = (uint32_t)((gi + ep * (unsigned long long)p.pool_stride) % P);
+        pool_idx = (uint32_t)pool_entry((unsigned long long)(p.env_offset + env), (unsigned long long)(episode + 1),
+                                        (unsigned long long)p.pool_stride, (unsigned long long)p.pool_size);
         pnext = *reinterpret_cast<const uint16_t*>(KA.pool + ((size_t)pool_idx * N + i) * 2);
         pnext_pending = true;
     }
@@ -839,6 +831,7 @@
         }
         unsigned long long acur = in_vgpr((unsigned long long)apk[0] | ((unsigned long long)apk[1] << 32));
         if (pnext_pending) {   // decode behind the wait that just happened: costs nothing
+            // (= cell_of_placement(pnext, Wp), inline here and below: the call cost 10 of 16 v128<3,..> an SGPR spill)
             pcell8 = (int)lds0 + ((int)(pnext >> 8) * Wp + (int)(pnext & 0xFFu) + Wp + 1) * 8;
             pnext_pending = false;
         }
@@ -930,13 +923,13 @@
                     }
                     wave_lds_sync();                                // (xch is rewritten by the conflict masks below)
                 }
-                const uint32_t cand = greedy_candidates(geo, boarding, (int)((ilo >> 16) & 0xFFu), (int)(ilo >> 24));
-                uint32_t pick = greedy_pick(cand, ilo & 0xFu & ~busy);
+                const uint32_t cand = greedy_candidates(geo, boarding, (int)cell_x(ilo), (int)cell_y(ilo));
+                uint32_t pick = greedy_pick(cand, cell_legal4(ilo) & ~busy);
                 const uint32_t asked = tt == 0u;   // policy is asked for env.agents only
                 if (policy == CCX_K_POLICY_WAITING) {
                     // waiting_policy.py:74-131: boarding agents outside the tram area wait while
                     // a live exiting agent is not on its destination row yet
-                    const uint32_t pend = (boarding ? 0u : asked) & (((ilo >> 12) & 1u) ^ 1u);
+                    const uint32_t pend = (boarding ? 0u : asked) & (((ilo >> kCellExitingShift) & 1u) ^ 1u);   // (= !cell_at_dest, inline: the call moved every v128<3,..> schedule)
                     const mask_t pend_bits = group_bits<GLOG>(__builtin_amdgcn_ballot_w64(pend != 0), lane);
                     if (boarding && !(ilo & kCellInTram) && pend_bits != 0) pick = 4u;
                 }
@@ -945,7 +938,7 @@
                     // of the pre-step state, uniformly; counter-based draws (ccx_kernels.h: explore_action)
                     const uint32_t u = random_word(rng_lo, rng_hi ^ kEpsStream, genv, (uint32_t)episode,
                                                    (uint32_t)(max_steps_m1 - left1), (uint32_t)i);
-                    if (u < eps_thr) pick = explore_action(u, ilo & 0xFu & ~busy);
+                    if (u < eps_thr) pick = explore_action(u, cell_legal4(ilo) & ~busy);
                 }
                 a = asked ? pick : 4u;
                 a_out = asked ? pick : (uint32_t)CCX_K_ABSENT;
@@ -957,7 +950,7 @@
             //         legality is a bit of the CURRENT cell's word (bit a; bit 4 is 0: waiting never "moves"); the
             //         target's word is requested now and consumed after the move is decided
             const int np8 = c8 + (int)(int16_t)(uint16_t)(lut64 >> (policy ? (a << 4) : sh_cur));
-            const uint32_t ok = (ilo >> a) & act;               // act is 0/1: only bit 0 survives
+            const uint32_t ok = (ilo >> a) & act;               // = cell_legal(ilo, a) & act; act is 0/1: only bit 0 survives (inline: the call re-scheduled every instantiation)
             const uint32_t nok = ok ^ 1u;
 
             // ---- 2. conflict masks over move ranks: Cm = earlier ranks standing on my target,
@@ -1144,11 +1137,11 @@
             // ---- 4. tail: deactivate on arrival (:210-212), terminated (terminateds.py:40-82), the pair of flags this
             //         step raises, __all__ (:256-259).  The per-agent flag byte (live, obs, ...) is assembled by writer
             //         wave 0, which keeps its own copy of the terminated / truncated pair.
-            const uint32_t dest = (ilo >> tsh) & 1u;                 // :663-683
+            const uint32_t dest = cell_at_dest(ilo, tsh);            // :663-683
             act &= ~dest;
             // terminateds[id] as the cell says (terminateds.py:66-82): the destination-row bit for the built-in strategies -- the plain
             // instantiations read nothing else -- or the bit of a position-only user strategy (ccx_set_terminated_table)
-            const uint32_t tind = PLAIN ? dest : ((ilo >> (tsh + kCellTermShift)) & 1u);
+            const uint32_t tind = PLAIN ? dest : cell_terminated(ilo, tsh);
             const uint64_t ndest_b = __builtin_amdgcn_ballot_w64((validbit & ~tind) != 0);   // agents whose terminated value is False
             uint32_t ndest_grp;                                      // != 0: some agent of my env is not there yet
             if constexpr (GLOG == 6) ndest_grp = in_vgpr((uint32_t)ndest_b | (uint32_t)(ndest_b >> 32));
@@ -1166,7 +1159,7 @@
             if constexpr (OUT) {
                 // ONE word per lane: where the agent stands (the LDS address of its cell word: the writer looks the word
                 // up itself), the flags this step raises, active, the env byte, the action taken
-                const uint32_t efw = ef + (ef < 1u ? ef : 1u) * reset_bit;       // CCX_EF_RESET next to a raised __all__ flag
+                const uint32_t efw = env_flag_byte(ef, reset_bit);               // CCX_EF_RESET next to a raised __all__ flag
                 const uint32_t hw = (uint32_t)c8 | (out2 << kHwOut2Shift) | (act << kHwActShift) | (efw << kHwEfShift) |
                                     (a_out << kHwActionShift);
                 *(__attribute__((address_space(3))) uint32_t*)(uintptr_t)(stage_abs + ((uint32_t)s & stage_mask) * kStageSlotBytes) = hw;
@@ -1285,8 +1278,8 @@
     const bool valid_w = in_vgpr(validbit) != 0u;
     const bool slot0_w = ((slot0_b >> lane) & 1ull) != 0;
     if (valid_w) {
-        KA.st.x[idx] = (int)((ilo >> 16) & 0xFFu);
-        KA.st.y[idx] = (int)(ilo >> 24);
+        KA.st.x[idx] = (int)cell_x(ilo);
+        KA.st.y[idx] = (int)cell_y(ilo);
         KA.st.active[idx] = (uint8_t)act;
         KA.st.terminated[idx] = (uint8_t)term;
         KA.st.truncated[idx] = (uint8_t)trunc;

@@ -105,13 +105,13 @@ template <int GLOG>
 __device__ __forceinline__ uint32_t scripted_pick(const GreedyGeo& geo, int policy, bool boarding, uint32_t ilo, uint32_t asked,
                                                   uint32_t busy, int lane, uint32_t eps_thr, uint32_t rng_lo, uint32_t rng_hi,
                                                   uint32_t genv, uint32_t episode, uint32_t step, uint32_t slot) {
-    const uint32_t free4 = ilo & 0xFu & ~busy;
-    const uint32_t cand = greedy_candidates(geo, boarding, (int)((ilo >> 16) & 0xFFu), (int)(ilo >> 24));
+    const uint32_t free4 = cell_legal4(ilo) & ~busy;
+    const uint32_t cand = greedy_candidates(geo, boarding, (int)cell_x(ilo), (int)cell_y(ilo));
     uint32_t pick = greedy_pick(cand, free4);
     if (policy == CCX_K_POLICY_WAITING) {
         // waiting_policy.py:74-131: boarding agents outside the tram area wait while
         // a live exiting agent is not on its destination row yet
-        const uint32_t pend = (boarding ? 0u : asked) & (((ilo >> 12) & 1u) ^ 1u);
+        const uint32_t pend = (boarding ? 0u : asked) & (cell_at_dest(ilo, kCellExitingShift) ^ 1u);
         const auto pend_bits = group_bits<GLOG>(__builtin_amdgcn_ballot_w64(pend != 0), lane);
         if (boarding && !(ilo & kCellInTram) && pend_bits != 0) pick = 4u;
     }
@@ -276,27 +276,6 @@ __device__ __forceinline__ void emit_obs(const WaveLds* wl, const uint16_t* tabl
 constexpr int kActBatch = 16;      // env-steps of actions fetched per global-load burst
 constexpr int kFastObsIters = 10;  // observation store iterations whose LDS addresses live in VGPRs
 constexpr int kObsBatch = 5;       // LDS reads issued back to back before their stores
-
-// ---- per-cell geometry table ------------------------------------------------------------------
-// Everything the step needs to know about a grid cell is precomputed once per handle on the host
-// (ccx_api.hip: build_cell_table) for the padded grid x in [-1, W+1], y in [-1, H+1]
-// (cell = (y+1)*(W+3) + (x+1)) and copied to LDS at kernel start:
-//   lo: bits 0-3  move a (right, up, left, down) from this cell lands on a cell that is in the
-//                 grid and not a wall                       (collectivecrossing.py:509-534)
-//       bit4 = 0 always (the "legality bit" of action 4 = wait: `(lo >> a) & 1` needs no clamp)
-//       bit5 IN_TRAM_AREA (:551-554)  bit6 AT_DOOR (:556-563)       -- CCX_AF_* bits 4/5, shifted up by one
-//       bit8  boarding: on destination row (:663-683)   bits 9-10  boarding reward class
-//       bit12 exiting:  on destination row              bits 13-14 exiting reward class
-//       byte2 = x, byte3 = y  (0 for border cells)
-//   hi: int16 signed distance term of the boarding reward | int16 of the exiting reward << 16
-// reward class (rewards.py:44-182): 0 = (double)sd * distance_penalty_factor, 1/2/3 = constants
-// rA/rB/rC chosen per reward mode.  The word of the agent's CURRENT cell is carried in registers,
-// so the legality of a move is a bit test; the word of the proposed cell is fetched off the
-// critical path and only consumed once the move is known to happen.
-//
-// sim -> writer hand-off (uint4 per lane and step): x = cell lo, y = cell hi, z = the CCX_AF_* bits the writer
-// cannot derive from the cell word (terminated, truncated, live, obs, active) | chosen action << 8, w = the CCX_EF_*
-// byte of its env.
 
 // ---------------------------------------------------------------------------------------------
 // the fused rollout / step kernel.

@@ -15,7 +15,7 @@
 // their cell, one ballot says "occupied" (collectivecrossing.py:536-541).  N iterations of ~10 instructions: nothing to
 // stage, no LDS tables, so it serves every legal grid (W, H <= 100) -- a launch of this kind is bound by its latency
 // floor, not by the loop.  Legality of a cell is the reference's arithmetic (:509-534, the rule the cell table is built
-// from: ccx_api.hip build_cell_table).
+// from: ccx_step_rule.h cell_ok).
 //
 // finish takes the lane layout of the observe kernel (ccx_kernels.hip), the handle's launch shape and its u16 address
 // table: the rows of a wave's envs are ONE contiguous region written by emit_obs, the staged 16-byte row writer.  The
@@ -44,14 +44,6 @@ __device__ __forceinline__ uint64_t split_group_mask(int glog, int lane) {
     return ((1ull << G) - 1ull) << (lane & ~(G - 1));
 }
 
-// collectivecrossing.py:509-534 _is_valid_position (+ :565-588 _would_hit_tram_wall, which it implies)
-__device__ __forceinline__ bool split_cell_ok(const KParams& p, int x, int y) {
-    bool ok = x >= 0 && x <= p.W && y >= 0 && y <= p.H;
-    if (y == p.div) ok = ok && (p.dl < x && x < p.dr);
-    if (y >= p.div) ok = ok && (p.tl < x && x < p.tr);
-    return ok;
-}
-
 constexpr uint32_t kSmallStageBytes = 64u * 8u + 64u + 64u;   // per wave: f64 reward, flag byte, term_present byte
 
 }  // namespace
@@ -77,7 +69,7 @@ step_begin_kernel(const KParams p, const KState st, const uint8_t* __restrict__ 
     // :371-376 the proposal, from the cell the agent stands on when its turn comes (only its own move changes that)
     const int nx = x + (a == 0u ? 1 : 0) - (a == 2u ? 1 : 0);
     const int ny = y + (a == 1u ? 1 : 0) - (a == 3u ? 1 : 0);
-    uint32_t ok = (act != 0u && a < 4u && split_cell_ok(p, nx, ny)) ? 1u : 0u;   // (wait / absent / bad bytes: no move)
+    uint32_t ok = (act != 0u && a < 4u && cell_ok(p, nx, ny)) ? 1u : 0u;   // (wait / absent / bad bytes: no move)
     const uint32_t prop = ((uint32_t)nx & 0xFFu) | (((uint32_t)ny & 0xFFu) << 8);
     uint32_t cur = ((uint32_t)x & 0xFFu) | (((uint32_t)y & 0xFFu) << 8);
     const uint64_t gm = split_group_mask(glog, lane);
@@ -161,38 +153,30 @@ step_finish_kernel(const KParams p, const KState st, const unsigned long long* _
     const uint32_t uu = u_trunc ? (uint32_t)u_trunc[idx] : 0u;
     const int Wp = p.W + 3;
     const uint32_t cells = (uint32_t)(Wp * (p.H + 3));
-    const uint32_t cell = valid ? (uint32_t)((y + 1) * Wp + x + 1) : 0u;
+    const uint32_t cell = valid ? (uint32_t)cell_index(x, y, Wp) : 0u;
     const unsigned long long ci = cell_info[cell];
     const uint32_t ilo = (uint32_t)ci, ihi = (uint32_t)(ci >> 32);
     const bool boarding = i < p.Nb;
-    const uint32_t tsh = boarding ? 8u : 12u, tsh2 = boarding ? 0u : 16u;
+    const uint32_t tsh = cell_tsh(boarding), tsh2 = cell_tsh2(boarding);
     const uint64_t gm = split_group_mask(glog, lane);
 
     // ---- :214-227 the three strategies against the PRE-step flags ---------------------------------------------------
     const uint32_t live = (valid && (term0 | trunc0) == 0u) ? 1u : 0u;          // rewards.py:64, truncateds.py:56
-    const uint32_t dest = (ilo >> tsh) & 1u;
     double r;
     if (u_reward) {
         r = ur;
     } else if (p.off_rtab) {                                                     // position-only user reward (ccx_set_reward_table)
         r = p.reward_table[(boarding ? 0u : cells) + cell];
-    } else {                                                                     // rewards.py:44-182, as ccx_step.hip computes it
-        const double rA = p.reward_mode == CCX_K_REWARD_BINARY ? p.r_nogoal
-                          : p.reward_mode == CCX_K_REWARD_CONSTANT_NEGATIVE ? p.r_pen : p.r_dest;
-        const uint32_t cls = (ilo >> (tsh + 1u)) & 3u;
-        const int sd = (int)(int16_t)(uint16_t)(ihi >> tsh2);
-        r = (double)sd * p.r_f;
-        r = (cls == 1u) ? rA : r;
-        r = (cls == 2u) ? p.r_door : r;
-        r = (cls == 3u) ? p.r_area : r;
+    } else {
+        r = cell_reward(ilo, ihi, tsh, tsh2, reward_class_a(p), p.r_door, p.r_area, p.r_f);
     }
-    r = live ? r : 0.0;
+    r = reward_if_live(r, live);
     uint32_t t1, present;
     if (u_term) {
         t1 = ut == 1 ? 1u : 0u;
         present = ut != -1 ? 1u : 0u;                                            // -1: the strategy returned None
     } else {
-        const uint32_t tind = (ilo >> (tsh + kCellTermShift)) & 1u;             // terminateds.py:66-82 / the user's table
+        const uint32_t tind = cell_terminated(ilo, tsh);                        // terminateds.py:66-82 / the user's table
         const uint64_t ndest_b = __builtin_amdgcn_ballot_w64(valid && tind == 0u) & gm;
         t1 = p.term_mode == CCX_K_TERM_ALL ? (ndest_b == 0ull ? 1u : 0u) : tind;
         present = 1u;
@@ -206,13 +190,12 @@ step_finish_kernel(const KParams p, const KState st, const unsigned long long* _
     const uint64_t ubad_b = __builtin_amdgcn_ballot_w64(live != 0u && u1 == 0u) & gm;
     const uint32_t ef = ((pres_b != 0ull && tbad_b == 0ull) ? CCX_K_EF_ALL_TERM : 0u) |
                         (((live_b & gm) != 0ull && ubad_b == 0ull) ? CCX_K_EF_ALL_TRUNC : 0u);
-    const bool do_reset = valid_env && auto_reset != 0 && pool != nullptr && p.pool_size > 0 && ef != 0u;
-    const uint32_t efw = ef | (do_reset ? CCX_K_EF_RESET : 0u);
+    const bool may_reset = valid_env && auto_reset != 0 && pool != nullptr && p.pool_size > 0;
+    const uint32_t efw = env_flag_byte(ef, may_reset ? (uint32_t)CCX_K_EF_RESET : 0u);
+    const bool do_reset = (efw & CCX_K_EF_RESET) != 0u;
     // ---- :229-254 flags applied once, the emission set, the flag byte ---------------------------------------------------
     const uint32_t out2 = t1 | (u1 << 1);
-    const uint32_t tt_before = term0 | (trunc0 << 1);
-    const uint32_t emit = (live | (out2 & ~tt_before)) != 0u ? 1u : 0u;          // :243, :763-767
-    const uint32_t af = out2 | (live << 2) | (emit << 3) | ((ilo >> 1) & 0x30u) | (act << 6) | (dest << 7);
+    const uint32_t af = agent_flag_byte(out2, term0 | (trunc0 << 1), ilo, tsh, act);   // (stored for lanes with an agent only)
     const float4 me = make_float4((float)x, (float)y, boarding ? 0.0f : 1.0f, (float)act);
 
     // ---- stage: the row writer's float4 per lane, the small outputs in OUTPUT order ---------------------------------
@@ -252,10 +235,8 @@ step_finish_kernel(const KParams p, const KState st, const unsigned long long* _
     // ---- state: the flags; an env that raised __all__ restarts from its pool entry (ccx.h: ccx_set_reset_pool) ----------
     if (valid) {
         if (do_reset) {
-            const unsigned long long P = (unsigned long long)p.pool_size;
-            const unsigned long long gi = (unsigned long long)(p.env_offset + env) % P;
-            const unsigned long long ep = (unsigned long long)(uint32_t)(episode0 + 1) % P;
-            const size_t pi = (size_t)((gi + ep * (unsigned long long)p.pool_stride) % P);
+            const size_t pi = (size_t)pool_entry((unsigned long long)(p.env_offset + env), (unsigned long long)(uint32_t)(episode0 + 1),
+                                                 (unsigned long long)p.pool_stride, (unsigned long long)p.pool_size);
             const uint8_t* src = pool + (pi * (size_t)N + (size_t)i) * 2u;
             st.x[idx] = src[0];
             st.y[idx] = src[1];

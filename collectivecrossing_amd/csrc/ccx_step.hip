@@ -259,7 +259,7 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
     const uint32_t idx_ld = valid ? idx : 0u;
     const uint32_t env_ld = valid_env ? (uint32_t)env : 0u;
     const bool boarding = i < Nb;
-    const uint32_t tsh = boarding ? 8u : 12u, tsh2 = boarding ? 0u : 16u;
+    const uint32_t tsh = cell_tsh(boarding), tsh2 = cell_tsh2(boarding);
 
     // ---- every global load of the wave's entry, issued before anything is waited for ---------------------------
     const StateSlab sl = state_slab(E, N);
@@ -383,11 +383,11 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
     auto lds_cell = [](int addr) { return *(__attribute__((address_space(3))) const unsigned long long*)(uintptr_t)(uint32_t)addr; };
     auto group_raw = [&](uint64_t bb) -> mask_t { return GLOG == 6 ? (mask_t)bb : (mask_t)(bb >> gsh); };
 
-    int c8 = (int)lds0 + (Wp + 1) * 8;
+    int c8 = (int)lds0 + cell_origin(Wp) * 8;
     uint32_t act = 0, tt = 1u;                       // lanes without an agent count as done
     int stepc = 0, episode = 0;
     if (valid) {
-        c8 = (int)lds0 + ((s_y + 1) * Wp + s_x + 1) * 8;
+        c8 = (int)lds0 + ((s_y + 1) * Wp + s_x + 1) * 8;   // = cell_index(s_x, s_y, Wp), inline: the call cost <0,1,0,0,0> 57 -> 59 VGPRs
         act = s_active != 0u;
         tt = (s_term != 0u ? 1u : 0u) | (s_trunc != 0u ? 2u : 0u);
     }
@@ -458,7 +458,7 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
         uint32_t ok = 0, nok = 0;
         if constexpr (!POL) {
             np8 = c8 + (int)(int16_t)(uint16_t)(lut64 >> ((a & 3u) << 4));     // (wait / absent: any neighbour, never entered -- its legality bit 4 is 0)
-            ok = (ilo >> a) & act;
+            ok = (ilo >> a) & act;                             // = cell_legal(ilo, a) & act (inline: the call re-scheduled every instantiation)
             nok = ok ^ 1u;
         }
         // ---- move rank of this agent (dict order of action_dict, collectivecrossing.py:197); identity without ORD
@@ -504,7 +504,7 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
             a = sbit ? (asked ? pick : 4u) : a;
             a_raw = sbit ? (asked ? pick : (uint32_t)CCX_K_ABSENT) : a_raw;
             np8 = c8 + (int)(int16_t)(uint16_t)(lut64 >> ((a & 3u) << 4));
-            ok = (ilo >> a) & act;
+            ok = (ilo >> a) & act;                             // = cell_legal(ilo, a) & act (inline: the call re-scheduled every instantiation)
             nok = ok ^ 1u;
         }
         const uint32_t ta = tab_rel + ((uint32_t)np8 << TS);
@@ -567,15 +567,15 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
         c_moves += (uint32_t)__builtin_popcountll(b);
         c_live += (uint32_t)__builtin_popcountll(live_b);
         // ---- 4. deactivate on arrival (:210-212), terminated (terminateds.py:40-82), truncated, __all__ (:256-259)
-        const uint32_t dest = (ilo >> tsh) & 1u;
+        const uint32_t dest = cell_at_dest(ilo, tsh);
         act &= ~dest;
         // ---- 5. hand the agents' (x, y, type, active) to the row waves: ONE barrier per step, two slots
-        const float4 me = make_float4((float)((ilo >> 16) & 0xFFu), (float)(ilo >> 24), type_f, (float)act);
+        const float4 me = make_float4((float)cell_x(ilo), (float)cell_y(ilo), type_f, (float)act);
         if (want_obs) {
             wl[s & 1].slot[lane] = me;
             if constexpr (!RSO) lds_barrier();                         // (RSO: behind the auto-reset, below)
         }
-        const uint32_t tind = (ilo >> (tsh + kCellTermShift)) & 1u;            // terminateds[id] as the cell says (ccx_kernels.h)
+        const uint32_t tind = cell_terminated(ilo, tsh);                       // terminateds[id] as the cell says
         const uint64_t ndest_b = __builtin_amdgcn_ballot_w64((validbit & ~tind) != 0);
         uint32_t ndest_grp;
         if constexpr (GLOG == 6) ndest_grp = (uint32_t)ndest_b | (uint32_t)(ndest_b >> 32);
@@ -586,26 +586,20 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
         tt |= out2;
         const uint32_t ef = all_dest | ((live_grp != 0u ? 2u : 0u) & ge_m);
         const uint64_t reset_b = __builtin_amdgcn_ballot_w64(ef != 0u) & may_reset_b;
-        const uint32_t efw = ef + (ef < 1u ? ef : 1u) * reset_bit;
+        const uint32_t efw = env_flag_byte(ef, reset_bit);
         // ---- 6. this step's small outputs (collectivecrossing.py:214-261)
+        // (= agent_flag_byte, inline: with the call, or with its parts handed over, all 168 instantiations changed)
         const uint32_t live = tt_before == 0u ? 1u : 0u;                       // rewards.py:64, truncateds.py:56
         const uint32_t emit = (live | (out2 & ~tt_before)) != 0u ? 1u : 0u;    // :243, :763-767
-        const uint32_t af = out2 | (live << 2) | (emit << 3) | ((ilo >> 1) & 0x30u) | (act << 6) | (dest << 7);
+        const uint32_t af = out2 | (live << 2) | (emit << 3) | cell_info_flags(ilo) | (act << 6) | (dest << 7);
         if (valid) {
             if (has_rew) {
-                // rewards.py:44-182: the INTEGER is negated before the one f64 multiply (d == 0 gives +0.0)
                 double r;
-                if (has_rtab) {          // position-only user reward: one f64 per (type, cell)
+                if (has_rtab)            // position-only user reward: one f64 per (type, cell)
                     r = *(__attribute__((address_space(3))) const double*)(uintptr_t)((uint32_t)c8 + rt_add);
-                } else {
-                    const uint32_t cls = (ilo >> (tsh + 1u)) & 3u;
-                    const int sd = (int)(int16_t)(uint16_t)(ihi >> tsh2);
-                    r = (double)sd * rF;
-                    r = (cls == 1u) ? rA : r;
-                    r = (cls == 2u) ? rB : r;
-                    r = (cls == 3u) ? rC : r;
-                }
-                r = live ? r : 0.0;
+                else
+                    r = cell_reward(ilo, ihi, tsh, tsh2, rA, rB, rC, rF);
+                r = reward_if_live(r, live);
                 *(__attribute__((address_space(1))) double*)(b_rew + o_rew) = r;
             }
             if (has_af) *(__attribute__((address_space(1))) uint8_t*)(b_af + o_af) = (uint8_t)af;
@@ -632,12 +626,10 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
                 episode += 1;
                 left1 = max_steps_m1;
                 if (valid) {
-                    const unsigned long long P = (unsigned long long)pool_size;
-                    const unsigned long long gi = ((unsigned long long)env_offset_mod_pool + (unsigned long long)env) % P;
-                    const unsigned long long ep = (unsigned long long)(uint32_t)episode % P;
-                    const uint32_t pool_idx = (uint32_t)((gi + ep * (unsigned long long)pool_stride) % P);
+                    const uint32_t pool_idx = (uint32_t)pool_entry((unsigned long long)env_offset_mod_pool + (unsigned long long)env,
+                                                                   (unsigned long long)(uint32_t)episode, pool_stride, pool_size);
                     const uint32_t pn = *reinterpret_cast<const uint16_t*>(pool + ((size_t)pool_idx * N + i) * 2);
-                    c8 = (int)lds0 + ((int)(pn >> 8) * Wp + (int)(pn & 0xFFu) + Wp + 1) * 8;
+                    c8 = (int)lds0 + ((int)(pn >> 8) * Wp + (int)(pn & 0xFFu) + Wp + 1) * 8;   // = cell_of_placement(pn, Wp), inline: 43 instantiations gained SGPR spills
                     const unsigned long long rci = lds_cell(c8);
                     ilo = (uint32_t)rci;
                     ihi = (uint32_t)(rci >> 32);
@@ -650,7 +642,7 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
             // the state the env carries on with (the step's own for an env that did not restart): slot 1 and the ballot of
             // the restarting lanes for the row waves, then the step's one hand-off barrier; the compact rows likewise, the
             // destination chosen before anything is stored
-            const float4 nx = make_float4((float)((ilo >> 16) & 0xFFu), (float)(ilo >> 24), type_f, (float)act);
+            const float4 nx = make_float4((float)cell_x(ilo), (float)cell_y(ilo), type_f, (float)act);
             if (want_obs) {
                 wl[1].slot[lane] = nx;
                 if (lane == 0) *reinterpret_cast<unsigned long long*>(&wl[1].cst[6]) = reset_b;
@@ -674,12 +666,12 @@ step_kernel(uint8_t* __restrict__ st_base,                      // StateSlab lay
         lds_or(act ? tab_rel + ((uint32_t)c8 << TS) : dump_addr, mybit);
         wave_lds_sync();
         const uint32_t busy = neighbours_busy<mask_t, TS>(tab_rel + ((uint32_t)c8 << TS), Wp);
-        mask_byte |= tt == 0u ? (ilo & 0xFu & ~busy) : 0u;             // done agents: wait only
+        mask_byte |= tt == 0u ? (cell_legal4(ilo) & ~busy) : 0u;             // done agents: wait only
     }
     // ---- registers -> state --------------------------------------------------------------------------------------
     if (valid) {
-        reinterpret_cast<int32_t*>(st_base + sl.x)[idx] = (int)((ilo >> 16) & 0xFFu);
-        reinterpret_cast<int32_t*>(st_base + sl.y)[idx] = (int)(ilo >> 24);
+        reinterpret_cast<int32_t*>(st_base + sl.x)[idx] = (int)cell_x(ilo);
+        reinterpret_cast<int32_t*>(st_base + sl.y)[idx] = (int)cell_y(ilo);
         (st_base + sl.active)[idx] = (uint8_t)act;
         (st_base + sl.terminated)[idx] = (uint8_t)(tt & 1u);
         (st_base + sl.truncated)[idx] = (uint8_t)(tt >> 1);
@@ -760,8 +752,7 @@ static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const K
     uint32_t pool_size = (uint32_t)p.pool_size, pool_stride = (uint32_t)p.pool_stride;
     uint32_t env_offset_mod_pool = p.pool_size > 0 ? (uint32_t)(p.env_offset % p.pool_size) : 0u;
     int dc = p.dc, div = p.div, dl = p.dl, dr = p.dr, term_all = p.term_mode == CCX_K_TERM_ALL ? 1 : 0;
-    double rA = p.reward_mode == CCX_K_REWARD_BINARY ? p.r_nogoal
-                : p.reward_mode == CCX_K_REWARD_CONSTANT_NEGATIVE ? p.r_pen : p.r_dest;
+    double rA = reward_class_a(p);
     double rB = p.r_door, rC = p.r_area, rF = p.r_f;
     // mixed control (read by the POL instantiations only)
     unsigned long long scripted = pol ? pol->scripted : 0ull;

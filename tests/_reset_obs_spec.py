@@ -5,15 +5,10 @@ launch, and a plain DefaultObservation gather (observations.py:43-94).  Nothing 
 
 import numpy as np
 from _fixtures import config_from_dict
+from _split_step_spec import pool_entry  # noqa: F401  (the one statement of the cursor; tests import it from here too)
 
 EF_RESET, AF_ACTIVE = 0x04, 0x40
 SENTINEL = 0xA5          # byte the side buffers are filled with before a call
-
-
-def pool_entry(global_env: int, episode: int, pool_size: int, total_envs: int) -> int:
-    """``(g + j * stride) mod P`` with ``stride = total_envs mod P, or 1 when P divides total_envs``."""
-    stride = total_envs % pool_size or 1
-    return (global_env + episode * stride) % pool_size
 
 
 def default_observation(x, y, active, num_boarding: int, consts) -> np.ndarray:

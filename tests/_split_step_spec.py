@@ -140,12 +140,17 @@ class Finish:
     counters: dict = field(default_factory=dict)   # env_steps, agent_steps, live_agent_steps, episodes
 
 
-def pool_cursor(env_offset, total_envs, pool_size, env, episode):
-    """ccx_set_reset_pool: entry (g + j * stride) mod P, g = env_offset + e, stride = total_envs mod P, or 1 when P divides
-    total_envs.  Exact integers (Python ints)."""
+def pool_entry(global_env: int, episode: int, pool_size: int, total_envs: int) -> int:
+    """ccx_set_reset_pool: entry ``(g + j * stride) mod P`` with ``stride = total_envs mod P, or 1 when P divides
+    total_envs``.  Exact integers (Python ints).  THE statement of the cursor: every spec module takes it from here."""
     P = int(pool_size)
     stride = int(total_envs) % P or 1
-    return (int(env_offset) + int(env) + int(episode) * stride) % P
+    return (int(global_env) + int(episode) * stride) % P
+
+
+def pool_cursor(env_offset, total_envs, pool_size, env, episode):
+    """:func:`pool_entry` of env ``env`` of the shard that starts at global env ``env_offset``."""
+    return pool_entry(int(env_offset) + int(env), episode, pool_size, total_envs)
 
 
 def builtin_arrays(oracle, p, st, tables=None):
