@@ -106,7 +106,7 @@ void fill_config(const ccx_handle* h, ccx::KParams& k) {
     k.pool_stride = h->pool_size > 0 ? (long long)ccx::pool_stride_of((unsigned long long)h->total_envs, (unsigned long long)h->pool_size) : 0;
 }
 
-// THE place that writes a plan into the handle: h->shape* / h->kp*, h->step_shape and the pace_* fields; it also uploads the
+// THE place that writes a plan into the handle: h->shape* / h->kp*, h->step_shape and the controller's start (h->pace); it also uploads the
 // observation address table of the rows shape (ccx_kernels.h: obs_unit_addr).  Shape changes are rare and never happen
 // inside a graph capture: wait for launches that still read the old table, then copy.
 int apply(ccx_handle* h, bool rows, const ccxp::ShapePlan& sp, const ccxp::PacePlan& pp) {
@@ -114,7 +114,7 @@ int apply(ccx_handle* h, bool rows, const ccxp::ShapePlan& sp, const ccxp::PaceP
     ccx::KParams& k = rows ? h->kp : h->kp_small;
     ccxp::materialize(sp, pp, s, k);
     fill_config(h, k);
-    k.pace_state = pp.paced ? h->pace_state : nullptr;
+    k.pace_state = pp.paced ? h->pace.state : nullptr;
     if (rows) {
         h->ring_when_paced = pp.ring_when_paced;
         h->obs_table_host.assign((size_t)k.units_per_wave + 2u, 0);
@@ -122,10 +122,10 @@ int apply(ccx_handle* h, bool rows, const ccxp::ShapePlan& sp, const ccxp::PaceP
         CCX_HIP(hipStreamSynchronize(h->stream));
         CCX_HIP(hipMemcpy(h->obs_table, h->obs_table_host.data(), h->obs_table_host.size() * sizeof(uint16_t),
                           hipMemcpyHostToDevice));
-        h->pace_init_fp = pp.pace_init_fp;
-        h->pace_start_source = pp.pace_start_source;
-        h->pace_dirty = true;
-        h->pace_needs_calibration = false;
+        h->pace.init_fp = pp.pace_init_fp;
+        h->pace.start_source = pp.pace_start_source;
+        h->pace.dirty = true;
+        h->pace.needs_calibration = false;
         h->step_shape = sp.step;
     }
     k.obs_table = h->obs_table;
@@ -196,17 +196,17 @@ int* g_lag_buf = nullptr;
 // rate (round 3: C2 7.3-7.6 TB/s vs fills of 6.4-7.1 in the same process), so the controller starts 5 % above the
 // measured rate and keeps descending at its fast rate until a launch comes in late.  Synchronises the stream once; skipped inside a stream capture, with a caller's start value
 // (ccx_set_step_pace_start), with a fixed pace, or with ccx_set_pace_calibration(h, 0) / CCX_PACE_CALIBRATION=0.
-int calibrate_pace(ccx_handle* h, float* obs, size_t obs_bytes) {
-    const size_t bytes = std::min<size_t>(obs_bytes & ~(size_t)15, (size_t)3 << 30);
-    if (bytes < ((size_t)16 << 20)) return CCX_OK;            // too small a buffer to say anything about a stream
+// The probe itself: the best rate of `bytes` written to `obs`, in GB/s (0: nothing measured).
+int probe_write_rate(const ccx_handle* h, float* obs, size_t bytes, double& best_gbs) {
     hipEvent_t e0 = nullptr, e1 = nullptr;
     CCX_HIP(hipEventCreate(&e0));
     if (hipError_t ee = hipEventCreate(&e1); ee != hipSuccess) {
         (void)hipEventDestroy(e0);
         return fail(CCX_EHIP, "hipEventCreate failed: %s", hipGetErrorString(ee));
     }
-    double best_gbs = 0.0, spent_ms = 0.0;
+    double spent_ms = 0.0;
     int rc = CCX_OK;
+    best_gbs = 0.0;
     for (int pass = 0; pass < 24 && spent_ms < 2.5 && rc == CCX_OK; ++pass) {
         float ms = 0.0f;
         hipError_t e = hipEventRecord(e0, h->stream);
@@ -222,14 +222,60 @@ int calibrate_pace(ccx_handle* h, float* obs, size_t obs_bytes) {
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (rc) return rc;
-    if (best_gbs > 1000.0 && best_gbs < 12000.0) {            // (a sane measurement; else keep the assumption)
-        h->pace_probe_gbs = (float)best_gbs;
-        h->pace_init_fp = std::min(std::max(ccxp::to_fp(h->shape.step_bytes / (best_gbs * 1.05)), h->kp.pace_min_fp), h->kp.pace_max_fp);
-        h->pace_start_source = CCX_PACE_START_CALIBRATED;
+    return rc;
+}
+
+}  // namespace
+
+int ccxi::PaceController::prepare(const ccx_handle* h, bool paced, bool adaptive, bool capturing, float* obs, size_t obs_bytes) {
+    // (re)start the pace controller: new handle, new launch shape or new setting
+    // Never inside a stream capture: the memsets would become graph nodes and every replay would re-zero the
+    // controller's state, and the calibration must synchronise (ADVICE r2).  Only a launch that would actually run them
+    // is refused while capturing; a controller that has been started (by ANY eager paced launch of the shape) and merely
+    // waits for its calibration captures fine and runs at the pace in effect (ADVICE r3: K = 16..63 on the C2 shape).
+    if (dirty && !h->kp.pace_state) {
+        dirty = false;                      // rollouts of this shape are not paced at all
+        needs_calibration = false;
     }
+    if (dirty && paced) {                   // (launches that are not paced never look at the controller: nothing to do yet)
+        if (capturing)
+            return fail(CCX_EINVAL, "the pace controller of this handle must be (re)started (new handle, launch shape or "
+                        "setting): run one eager rollout of this shape (any paced length: >= %u steps) before capturing it "
+                        "into a graph, or switch pacing off (ccx_set_step_pace(h, -1))", h->kp.pace_min_k);
+        needs_calibration = h->kp.pace_adapt != 0u && h->pace_calibrate && h->pace_start_ns <= 0.0f;
+    }
+    const bool calibrate_now = needs_calibration && adaptive && !capturing;
+    if (!(dirty && paced) && !calibrate_now) return CCX_OK;
+    if (calibrate_now) {
+        const size_t bytes = std::min<size_t>(obs_bytes & ~(size_t)15, (size_t)3 << 30);
+        if (bytes >= ((size_t)16 << 20)) {                    // (else: too small a buffer to say anything about a stream)
+            double gbs = 0.0;
+            const int rc = probe_write_rate(h, obs, bytes, gbs);
+            if (rc) return rc;
+            if (gbs > 1000.0 && gbs < 12000.0) {              // (a sane measurement; else keep the assumption)
+                probe_gbs = (float)gbs;
+                init_fp = std::min(std::max(ccxp::to_fp(h->shape.step_bytes / (gbs * 1.05)), h->kp.pace_min_fp), h->kp.pace_max_fp);
+                start_source = CCX_PACE_START_CALIBRATED;
+            }
+        }
+        needs_calibration = false;
+    }
+    CCX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(state), 0, 8, h->stream));   // floor, cliff memory = 0
+    CCX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(state + slot), (int)init_fp, 1, h->stream));
+    // A start value from the caller (ccx_set_step_pace_start: the pace a previous handle of this shape settled at)
+    // is also the controller's first FLOOR: a process that already knows its pace skips the descent into a first
+    // collapse; the floor decays as always.  A CALIBRATED start gets no floor: the probe is a lower bound of what
+    // the paced stream reaches (measured: the paced rollouts settle 5-15 % above a plain fill of the same buffer),
+    // so the controller descends from it at its fast rate (1.6 % per launch) until the memory side says stop.
+    if (h->step_pace_ns == 0 && h->pace_start_ns > 0.0f)
+        CCX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(state + 2), (int)init_fp, 1, h->stream));
+    // (a paced launch too short to calibrate on runs from the assumption; the first adaptive eager one calibrates
+    // and restarts: needs_calibration)
+    dirty = false;
     return CCX_OK;
 }
+
+namespace {
 
 // ---- one stepping call: what ccx_step, ccx_rollout, ccx_rollout_policy and ccx_rollout_mixed hand to the launch code ----
 struct StepCall {     // (the first five fields in the order of ccx_rollout's arguments: the entry points fill them by position)
@@ -241,6 +287,8 @@ struct StepCall {     // (the first five fields in the order of ccx_rollout's ar
     int policy = 0;                        // in-kernel policy of the rollout kernel (0 = the action tensor)
     uint8_t* actions_out = nullptr;        // ... and where its actions go
     bool inputs_checked = false;           // the entry point has enqueued the input check of the whole call itself
+    bool mixed = false;                    // ccx_rollout_mixed: `pol` names the scripted slots and their policy (its actions_out: ours)
+    ccx::StepPolicy pol{};
     // what the step kernel may do in its own launch instead of leaving it to finish_call (never given to a sub-launch of a cut)
     uint8_t* masks = nullptr;
     const ccx::StepResetObs* rso = nullptr;
@@ -302,99 +350,54 @@ bool stream_is_capturing(const ccx_handle* h) {
     return false;
 }
 
+// ---- what the planner is asked (ccx_plan.hip: plan_call, plan_launch): the handle's two shapes, the call and the tunables ----
+ccxp::CallFacts call_facts(const ccx_handle* h) {
+    return ccxp::CallFacts{h->E, h->N, {ccxp::call_shape(h->shape, h->kp, h->ring_when_paced, h->step_shape.ok != 0),
+                                        ccxp::call_shape(h->shape_small, h->kp_small, false, false)}};
+}
+
+ccxp::CallIn call_in(const ccx_handle* h, const StepCall& c) {
+    ccxp::CallIn in{};
+    in.K = c.K; in.actions = c.actions != nullptr; in.order = c.order != nullptr; in.actions_out = c.actions_out != nullptr;
+    in.policy = c.policy; in.mixed = c.mixed; in.writes_obs = c.out.obs != nullptr;
+    in.masks_bound = c.masks != nullptr; in.reset_obs_on = c.rso != nullptr;
+    in.hand2 = h->tun_hand2; in.round_launches = h->tun_round_launches; in.small_shape = h->tun_small_shape;
+    in.step_kernel = h->tun_step_kernel; in.max_launch_steps = h->tun_max_launch_steps; in.reset_obs_fused = h->tun_reset_obs_fused;
+    return in;
+}
+
 // ---- the short launch: the step kernel (ccx_step.hip), CollectiveCrossingEnv.step itself -- no pacing, no controller state,
-// no capture query.  `pol`: the kernel's mixed-control instantiations (ccx_rollout_mixed)
-Launched launch_short(ccx_handle* h, const StepCall& c, const ccx::StepPolicy* pol = nullptr) {
+// no capture query; with the scripted slots of a mixed-control call
+Launched launch_short(ccx_handle* h, const StepCall& c, const ccxp::LaunchPlan& lp) {
     int rc = c.inputs_checked ? CCX_OK : enqueue_input_check(h, c.K, c.actions, c.order);
     if (!rc) rc = begin_timed(h);
     if (rc) return rc;
-    // (bound action masks: this launch writes them itself where an MSK instantiation exists -- ccx_kernels.h)
-    uint8_t* const m = ccx::step_masks_fused(c.K, c.order != nullptr) ? c.masks : nullptr;
-    // (CCX_RESET_OBS_NEXT: likewise where an RSO instantiation exists; finish_call serves the rest)
-    const ccx::StepResetObs* const r =
-        (h->tun_reset_obs_fused != 0 && ccx::step_reset_obs_fused(c.K, c.order != nullptr, pol != nullptr)) ? c.rso : nullptr;
+    const ccx::StepPolicy pol{c.pol.scripted, c.pol.policy, c.actions_out};
+    // (bound action masks, CCX_RESET_OBS_NEXT: this launch serves them itself where the plan says so; finish_call the rest)
+    uint8_t* const m = lp.masks_fused ? c.masks : nullptr;
+    const ccx::StepResetObs* const r = lp.reset_obs_fused ? c.rso : nullptr;
     hipError_t e = ccx::launch_step(h->step_shape, h->stream, launch_params(h), h->st_slab, h->cell_info, c.actions, c.order, c.K,
-                                    c.auto_reset, h->pool, c.out, h->counters, pol, m, r);
+                                    c.auto_reset, h->pool, c.out, h->counters, c.mixed ? &pol : nullptr, m, r);
     if (e != hipSuccess) return fail(CCX_EHIP, "step kernel launch failed: %s", hipGetErrorString(e));
     Launched l(end_timed(h));
     l.masks_written = m != nullptr, l.reset_obs_written = r != nullptr;
     return l;
 }
 
-// ---- the paced launch: the rollout kernel.  First its controller: (re)start and calibration, ahead of the launch ---------
-int restart_pace(ccx_handle* h, const StepCall& c, bool capturing) {
-    const int K = c.K;
-    const bool writes_obs = c.out.obs != nullptr;
-    // (re)start the pace controller: new handle, new launch shape or new setting
-    // Never inside a stream capture: the memsets would become graph nodes and every replay would re-zero the
-    // controller's state, and the calibration must synchronise (ADVICE r2).  Only a launch that would actually run them
-    // is refused while capturing; a controller that has been started (by ANY eager paced launch of the shape) and merely
-    // waits for its calibration captures fine and runs at the pace in effect (ADVICE r3: K = 16..63 on the C2 shape).
-    const bool paced_launch = ccx::launch_is_paced(h->kp.pace_state != nullptr, writes_obs, K, h->kp.pace_min_k);
-    const bool adaptive_launch =
-        ccx::launch_is_adaptive(h->kp.pace_state != nullptr, h->kp.pace_adapt != 0u, writes_obs, K, h->kp.pace_min_k, h->kp.adapt_min_k);
-    if (h->pace_dirty && !h->kp.pace_state) {
-        h->pace_dirty = false;              // rollouts of this shape are not paced at all
-        h->pace_needs_calibration = false;
-    }
-    if (h->pace_dirty && paced_launch) {    // (launches that are not paced never look at the controller: nothing to do yet)
-        if (capturing)
-            return fail(CCX_EINVAL, "the pace controller of this handle must be (re)started (new handle, launch shape or "
-                        "setting): run one eager rollout of this shape (any paced length: >= %u steps) before capturing it "
-                        "into a graph, or switch pacing off (ccx_set_step_pace(h, -1))", h->kp.pace_min_k);
-        h->pace_needs_calibration = h->kp.pace_adapt != 0u && h->pace_calibrate && h->pace_start_ns <= 0.0f;
-    }
-    const bool calibrate_now = h->pace_needs_calibration && adaptive_launch && !capturing;
-    if ((h->pace_dirty && paced_launch) || calibrate_now) {
-        if (calibrate_now) {
-            const size_t obs_bytes = (size_t)K * (size_t)h->E * h->N * (size_t)(6 + 4 * h->N) * sizeof(float);
-            const int rc = calibrate_pace(h, c.out.obs, obs_bytes);
-            if (rc) return rc;
-            h->pace_needs_calibration = false;
-        }
-        CCX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->pace_state), 0, 8, h->stream));   // floor, cliff memory = 0
-        CCX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->pace_state + h->pace_slot),
-                                  (int)h->pace_init_fp, 1, h->stream));
-        // A start value from the caller (ccx_set_step_pace_start: the pace a previous handle of this shape settled at)
-        // is also the controller's first FLOOR: a process that already knows its pace skips the descent into a first
-        // collapse; the floor decays as always.  A CALIBRATED start gets no floor: the probe is a lower bound of what
-        // the paced stream reaches (measured: the paced rollouts settle 5-15 % above a plain fill of the same buffer),
-        // so the controller descends from it at its fast rate (1.6 % per launch) until the memory side says stop.
-        if (h->step_pace_ns == 0 && h->pace_start_ns > 0.0f)
-            CCX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(h->pace_state + 2), (int)h->pace_init_fp, 1, h->stream));
-        // (a paced launch too short to calibrate on runs from the assumption; the first adaptive eager one calibrates
-        // and restarts: pace_needs_calibration)
-        h->pace_dirty = false;
-    }
-    return CCX_OK;
-}
-
-// ... then the launch itself, round by round where the grid exceeds the device
-int launch_paced(ccx_handle* h, const StepCall& c) {
-    const int K = c.K;
-    const bool writes_obs = c.out.obs != nullptr;
-    const bool capturing = stream_is_capturing(h);
-    int rc = restart_pace(h, c, capturing);
+// ---- the paced launch: the rollout kernel.  First its controller, then the launch itself, round by round where the plan
+// says so
+int launch_paced(ccx_handle* h, const StepCall& c, const ccxp::LaunchPlan& lp, bool capturing) {
+    int rc = h->pace.prepare(h, lp.paced, lp.adaptive, capturing, c.out.obs, ccxp::obs_bytes(h->E, h->N, (size_t)c.K));
     if (rc) return rc;
-    h->kp.pace_slot = h->pace_slot;
-    if (!c.inputs_checked) rc = enqueue_input_check(h, K, c.actions, c.order);
+    h->kp.pace_slot = h->pace.slot;
+    if (!c.inputs_checked) rc = enqueue_input_check(h, c.K, c.actions, c.order);
     if (rc) return rc;
-    // A launch that is being captured into a HIP graph is replayed with these very arguments: the controller
-    // cannot adapt across replays (the slot flip below happens once, at capture time), so such a launch runs
-    // at the pace in effect and neither votes nor touches the controller's state.
-    const bool small_launch = !writes_obs && h->tun_small_shape != 0;      // rewards / flag bytes / compact rows only
-    const ccx::LaunchShape& shape = small_launch ? h->shape_small : h->shape;
-    ccx::KParams kp = launch_params(h, small_launch);
-    kp.pace_slot = h->pace_slot;
-    kp.launch_flags = 0u;
-    // launches the kernel will not pace hand steps to the writer waves through sequence words (ccx_kernels.h: one
-    // definition of the launch modes for the host and the kernel)
-    kp.hand_flags = ccx::launch_uses_flags(kp.pace_state != nullptr, writes_obs, K, kp.pace_min_k, h->tun_hand2) ? 1u : 0u;
-    // Paced batches whose step period is close to the sim wave's own chain (C2: 2200 .. 3000 envs, 0.41-0.52 us per env-step)
-    // keep the ring too: a barrier per step couples the chain to the writers and such tiles step in 0.46 us instead of 0.40
-    // (2304 envs 0.77 -> 0.83 of the peak, 2816 envs 0.88 -> 0.91; from 3072 envs on there is nothing in it, and saturating
-    // batches want the barrier: DESIGN 3.7; profiles/r04_small_batch.txt)
-    if (h->tun_hand2 == 1 && writes_obs && !small_launch && h->ring_when_paced) kp.hand_flags = 1u;
+    ccx::LaunchShape shape = lp.shape ? h->shape_small : h->shape;
+    ccx::KParams kp = launch_params(h, lp.shape != 0);
+    kp.pace_slot = h->pace.slot;
+    kp.launch_flags = lp.by_rounds ? (uint32_t)ccx::CCX_K_LAUNCH_ROUND : 0u;
+    kp.hand_flags = lp.hand_flags;
+    kp.pace_adapt = lp.pace_adapt;
 #ifdef CCX_LAG_TRACE
     {
         static int* lag_buf = nullptr;
@@ -406,102 +409,61 @@ int launch_paced(ccx_handle* h, const StepCall& c) {
         g_lag_buf = lag_buf;
     }
 #endif
-    const bool adaptive = ccx::launch_is_adaptive(kp.pace_state != nullptr, kp.pace_adapt != 0u, writes_obs, K, kp.pace_min_k, kp.adapt_min_k);
-    if (adaptive && capturing) kp.pace_adapt = 0u;
     rc = begin_timed(h);
     if (rc) return rc;
-    // A grid of more workgroups than the device holds is launched ROUND BY ROUND: one launch per `resident_blocks`
-    // workgroups, back to back on the stream.  In ONE launch the workgroups of the second round start as slots come free, each on
-    // a schedule of its own, and the chip's write front -- one narrow window per env-step while the tiles march in step --
-    // frays over several slabs.  A launch boundary between the rounds (~2 us against rounds of 100+ us) restarts every round in step.  The kernel sees
-    // its place in the grid through block_base (env indices, tile phases) and knows that it is one round (launch_flags: the pace of a partial last round); the
-    // controller's owner is tile 0 of the first launch and all rounds vote into the same slot, as in one launch.
-    // Only where the rows of the launch exceed the ~4 GB footprint knee (a stream through more memory than that
-    // sustains 5-8 % less, whatever the kernel does; profiles/r04_output_size.txt):
-    // below it the boundary costs 1-2 % (32 768 envs x 64 steps: 0.887 -> 0.873), beyond it the rounds in step win 3-5 %
-    // (65 536 x 64: 0.750 -> 0.785).
-    // The rounds are made EQUAL (R = ceil(blocks / resident) launches of ceil(blocks / R) workgroups, each on a schedule
-    // scaled to its fill): a grid just above a whole number of rounds -- 17 768 envs of C2: 1111 workgroups on 1024 slots --
-    // otherwise spends a full round's time on its last few tiles (0.74-0.77 of the peak where 15 800 envs reach 0.91; balanced:
-    // 0.86-0.87).  That alone is worth the boundary for a paced grid of TWO rounds whose second would be less than 30 % full
-    // (17 000 .. 20 500 envs of C2: +4 .. +12 %; fuller second rounds and grids of three or more rounds: nothing or a loss --
-    // profiles/r04_balanced_rounds.txt).
-    const int resident = shape.resident_blocks;
-    const double rows_bytes = writes_obs ? (double)K * (double)h->E * h->N * (double)(6 + 4 * h->N) * 4.0 : 0.0;
-    const int n_rounds = resident > 0 ? (shape.num_blocks + resident - 1) / resident : 1;
-    // ... and whose tiles can FOLLOW the scaled schedule: a tile with one throttled writer steps in ~1 us at best; where the
-    // common pace is already short (5 agents: 1.3 us for a full device) half-full rounds would be asked for 0.7 us, be late,
-    // vote, and drag the common pace up (N = 5, 17 776 envs: 0.52 of the peak that way; profiles/r04_cliff_scan2.txt)
-    const bool thin_second_round = n_rounds == 2 && (double)(shape.num_blocks - resident) < 0.3 * resident &&
-                                   shape.step_bytes / 7000.0 * (0.5 * shape.num_blocks / resident) >= 1200.0;
-    const bool paced_rows = ccx::launch_is_paced(kp.pace_state != nullptr, writes_obs, K, kp.pace_min_k);
-    const bool by_rounds = resident > 0 && shape.num_blocks > resident &&
-                           (h->tun_round_launches >= 2 ||
-                            (h->tun_round_launches == 1 && (rows_bytes > 3.5e9 || (paced_rows && thin_second_round))));
+    // (one launch of the whole grid is the one "round" of a plan that is not by rounds: per_round = the grid)
+    const int num_blocks = shape.num_blocks;
     hipError_t e = hipSuccess;
-    if (by_rounds) {
-        ccx::LaunchShape round = shape;
-        kp.launch_flags |= ccx::CCX_K_LAUNCH_ROUND;
-        const int per_round = (shape.num_blocks + n_rounds - 1) / n_rounds;
-        for (int b0 = 0; b0 < shape.num_blocks && e == hipSuccess; b0 += per_round) {
-            round.num_blocks = std::min(per_round, shape.num_blocks - b0);
-            kp.block_base = (uint32_t)b0;
-            e = ccx::launch_rollout(round, h->stream, kp, h->st, h->cell_info, c.actions,
-                                    c.order, K, c.auto_reset, h->pool, c.out, h->counters, c.policy, c.actions_out);
-        }
-    } else {
+    for (int b0 = 0; b0 < num_blocks && e == hipSuccess; b0 += lp.per_round) {
+        shape.num_blocks = std::min(lp.per_round, num_blocks - b0);
+        kp.block_base = (uint32_t)b0;
         e = ccx::launch_rollout(shape, h->stream, kp, h->st, h->cell_info, c.actions,
-                                c.order, K, c.auto_reset, h->pool, c.out, h->counters, c.policy, c.actions_out);
+                                c.order, c.K, c.auto_reset, h->pool, c.out, h->counters, c.policy, c.actions_out);
     }
     if (e != hipSuccess) return fail(CCX_EHIP, "rollout kernel launch failed: %s", hipGetErrorString(e));
-    // the kernel collected the votes for the next pace in the other slot (same condition as in the kernel)
-    if (adaptive && !capturing) h->pace_slot ^= 1u;
+    if (lp.flip_slot) h->pace.slot ^= 1u;
     return end_timed(h);
 }
 
-// one launch of a call: the step kernel where it applies, else the rollout kernel
-Launched launch_one(ccx_handle* h, const StepCall& c) {
+// one launch of a call: the step kernel where the plan says so, else the rollout kernel.  Only the latter asks whether the
+// stream is being captured, and a capturing stream has the launch planned again with that answer.
+Launched launch_one(ccx_handle* h, const StepCall& c, const ccxp::CallFacts& f, const ccxp::CallIn& in) {
     const int rc = check_out_align(c.out);
     if (rc) return rc;
     CCX_HIP(hipSetDevice(h->device));
-    if (c.K <= ccx::kStepMaxK && c.actions && c.policy == 0 && !c.actions_out && h->step_shape.ok && h->tun_step_kernel != 0)
-        return launch_short(h, c);
-    return launch_paced(h, c);
+    ccxp::LaunchPlan lp = ccxp::plan_launch(f, in, c.K);
+    if (lp.kernel == ccxp::KERNEL_STEP) return launch_short(h, c, lp);
+    const bool capturing = stream_is_capturing(h);
+    if (capturing) {
+        ccxp::CallIn captured = in;
+        captured.capturing = 1;
+        lp = ccxp::plan_launch(f, captured, c.K);
+    }
+    return launch_paced(h, c, lp, capturing);
 }
 
-// ---- the cutter: a call as one launch, or as several below 4 GiB per stream --------------------------------------------
+// ---- the cutter: a call as one launch, or as several of the plan's length --------------------------------------------------
 Launched run_rollout(ccx_handle* h, const StepCall& c) {
-    // The writer waves address the small output streams (rewards, flag bytes, compact rows, chosen actions) with 32-bit
-    // byte offsets from the stream's base: one launch must stay below 4 GiB per stream.  Longer rollouts are cut into
-    // launches on the same stream (bit-identical: an env's trajectory does not depend on how a rollout is split).
-    const unsigned long long per_step = (unsigned long long)h->E * (unsigned long long)h->N * 16ull;   // the widest stream
-    const unsigned long long fit = 0xFFFFFFFFull / per_step;
-    int max_k = (int)std::min<unsigned long long>(fit > 1 ? fit - 1 : 1, 0x7FFFFFFFull);
-    if (h->tun_max_launch_steps > 0) max_k = std::min(max_k, h->tun_max_launch_steps);   // (tests: force the cut)
-    // L = 6 + 4N is 2 mod 4: one step's observation slab (E x N x L floats) is a multiple of 16 bytes only when E x N is
-    // even; with E x N odd every sub-launch must start on an EVEN step so that its slice of the tensor stays 16-byte
-    // aligned (an odd cut failed on "obs buffer must be 16-byte aligned" after the first sub-launch had
-    // already advanced the state)
-    const bool odd_slab = c.out.obs && ((((size_t)h->E * h->N * (size_t)(6 + 4 * h->N) * sizeof(float)) & 15u) != 0);
-    if (odd_slab && max_k > 1) max_k &= ~1;
-    if (c.K <= max_k) return launch_one(h, c);
-    if (odd_slab && max_k == 1)
+    const ccxp::CallFacts f = call_facts(h);
+    const ccxp::CallIn in = call_in(h, c);
+    const ccxp::CallPlan cp = ccxp::plan_call(f, in);
+    if (cp.refused)
         return fail(CCX_EINVAL, "a rollout of an odd number of agent slots (E x N = %lld) cannot be cut into launches of "
                     "one step: its per-step observation slabs are not 16-byte aligned (raise max_launch_steps to >= 2)",
                     (long long)h->E * h->N);
+    if (cp.launches == 1) return launch_one(h, c, f, in);
     const size_t EN = (size_t)h->E * h->N;
-    for (int k0 = 0; k0 < c.K; k0 += max_k) {
+    for (int k0 = 0; k0 < c.K; k0 += cp.steps_per_launch) {
         StepCall sub = c;
-        sub.K = std::min(max_k, c.K - k0);
+        sub.K = std::min(cp.steps_per_launch, c.K - k0);
         if (c.actions) sub.actions = c.actions + (size_t)k0 * EN;
         if (c.order) sub.order = c.order + (size_t)k0 * EN;
         if (c.actions_out) sub.actions_out = c.actions_out + (size_t)k0 * EN;
         sub.out = kout_at(h, c.out, k0);
-        // (the sub-launches get neither `masks` nor `rso`: a call that is cut leaves both to the stand-alone kernels
-        //  behind its LAST launch -- finish_call -- also where it is cut into single steps; same bytes)
+        // (the sub-launches get neither `masks` nor `rso`: the plan fuses them into a call of one step only)
         sub.masks = nullptr;
         sub.rso = nullptr;
-        const Launched l = launch_one(h, sub);
+        const Launched l = launch_one(h, sub, f, in);
         if (l.rc) return l;
     }
     return CCX_OK;
@@ -548,15 +510,15 @@ int finish_call(ccx_handle* h, int K, const ccx::KOut& ko, int auto_reset, const
 // actions_out takes them) and, where a step's slice of the observation tensor is not 16-byte aligned (E x N x L x 4 not a
 // multiple of 16), an aligned staging slab.
 int stepwise_scratch(ccx_handle* h, const StepCall& c, const char* what) {
-    const size_t EN = (size_t)h->E * h->N, L = (size_t)(6 + 4 * h->N);
+    const size_t EN = (size_t)h->E * h->N, slab = ccxp::obs_bytes(h->E, h->N);
     const bool own_actions = !c.actions_out && !h->stream_actions;
-    const bool staging = c.out.obs && ((EN * L * sizeof(float)) & 15u) && c.K > 1 && !h->stream_obs;
+    const bool staging = c.out.obs && (slab & 15u) && c.K > 1 && !h->stream_obs;
     if (!own_actions && !staging) return CCX_OK;
     if (stream_is_capturing(h))
         return fail(CCX_EINVAL, "%s allocates scratch buffers on first use: run one eager call of this shape before "
                     "capturing it into a graph", what);
     if (own_actions) CCX_HIP(hipMalloc(&h->stream_actions, EN));
-    if (staging) CCX_HIP(hipMalloc(&h->stream_obs, EN * L * sizeof(float)));
+    if (staging) CCX_HIP(hipMalloc(&h->stream_obs, slab));
     return CCX_OK;
 }
 
@@ -564,7 +526,7 @@ int stepwise_scratch(ccx_handle* h, const StepCall& c, const char* what) {
 // path, its observation rows staged where their slice is misaligned
 template <class Produce>
 Launched run_stepwise(ccx_handle* h, const StepCall& c, const char* what, Produce produce_actions) {
-    const size_t EN = (size_t)h->E * h->N, L = (size_t)(6 + 4 * h->N);
+    const size_t EN = (size_t)h->E * h->N, slab = ccxp::obs_bytes(h->E, h->N);
     int rc = stepwise_scratch(h, c, what);
     for (int s = 0; s < c.K && !rc; ++s) {
         uint8_t* const acts = c.actions_out ? c.actions_out + (size_t)s * EN : h->stream_actions;
@@ -578,7 +540,7 @@ Launched run_stepwise(ccx_handle* h, const StepCall& c, const char* what, Produc
         }
         rc = produce_actions(s, acts);
         if (!rc) rc = run_rollout(h, step).rc;
-        if (!rc && staged) CCX_HIP(hipMemcpyAsync(obs_dst, h->stream_obs, EN * L * sizeof(float), hipMemcpyDeviceToDevice, h->stream));
+        if (!rc && staged) CCX_HIP(hipMemcpyAsync(obs_dst, h->stream_obs, slab, hipMemcpyDeviceToDevice, h->stream));
     }
     return rc;
 }
@@ -655,7 +617,7 @@ int ccx_create(const ccx_params* params, int32_t num_envs, int64_t env_offset, i
     }
     alloc((void**)&h->counters, ccx::counter_words(h->E) * sizeof(unsigned long long));
     alloc((void**)&h->placement_scratch, en * 2);
-    alloc((void**)&h->pace_state, 8 * sizeof(uint32_t));
+    alloc((void**)&h->pace.state, 8 * sizeof(uint32_t));
     alloc((void**)&h->input_errors, 2 * sizeof(unsigned long long));
     alloc((void**)&h->obs_table, kMaxObsUnits * sizeof(uint16_t));
     if (hipDeviceGetAttribute(&h->num_cus, hipDeviceAttributeMultiprocessorCount, h->device) != hipSuccess ||
@@ -700,7 +662,7 @@ void ccx_destroy(ccx_handle* h) {
     (void)hipStreamSynchronize(h->stream);
     (void)hipFree(h->st_slab);
     (void)hipFree(h->counters);
-    (void)hipFree(h->pace_state);
+    (void)hipFree(h->pace.state);
     (void)hipFree(h->input_errors);
     (void)hipFree(h->obs_table);
     (void)hipFree(h->cell_info);
@@ -982,7 +944,10 @@ int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t
         return fail(CCX_EINVAL, "a mixed-control step cannot draw from the MT19937 exploration stream: that stream is "
                     "sequential per env and walked by a kernel of its own (ccx_policy_actions); select "
                     "CCX_EPS_STREAM_COUNTER or set epsilon to 0");
-    const StepCall c{num_steps, actions, order, auto_reset ? 1 : 0, kout_of(out), 0, actions_out, /*inputs_checked=*/true};
+    StepCall c{num_steps, actions, order, auto_reset ? 1 : 0, kout_of(out), 0, actions_out, /*inputs_checked=*/true};
+    c.mixed = true;
+    c.pol = ccx::StepPolicy{scripted_slots, policy, nullptr};
+    c.masks = h->bound_masks;
     rc = check_out_align(c.out);
     if (!rc) rc = check_reset_obs(h, c.out, auto_reset);
     if (rc) return rc;
@@ -991,24 +956,11 @@ int ccx_rollout_mixed(ccx_handle* h, int32_t num_steps, int32_t policy, uint64_t
     // ccx_set_check_inputs: the caller's bytes outside the mask and the order rows, once, on either path
     rc = enqueue_input_check(h, num_steps, actions, order, scripted_slots);
     if (rc) return rc;
-    if (h->step_shape.ok && h->tun_step_kernel != 0) {
-        // the short-launch kernel's policy instantiations (ccx_step.hip, POL): policy + merge + step in ONE launch per
-        // <= 16 steps (16 is even: every sub-launch's slice of the observation tensor stays 16-byte aligned)
-        Launched l;
-        for (int k0 = 0; k0 < num_steps && !l.rc; k0 += ccx::kStepMaxK) {
-            const ccx::StepPolicy pol{scripted_slots, policy, actions_out ? actions_out + (size_t)k0 * EN : nullptr};
-            StepCall sub = c;
-            sub.K = std::min(ccx::kStepMaxK, num_steps - k0);
-            if (actions) sub.actions = actions + (size_t)k0 * EN;
-            if (order) sub.order = order + (size_t)k0 * EN;
-            sub.out = kout_at(h, c.out, k0);
-            sub.masks = ccx::step_masks_fused(num_steps, order != nullptr) ? h->bound_masks : nullptr;   // (only a call of ONE step)
-            l = launch_short(h, sub, &pol);
-        }
-        return finish_call(h, num_steps, c.out, auto_reset, l);
-    }
-    // Handles whose short launches cannot use the step kernel (tables beyond the LDS, or the tunable): the composition
-    // itself, step by step on the handle's stream -- policy kernel, merge kernel, the existing step path.
+    // policy + merge + step in the launches of the step kernel (the cutter, like every other call) ...
+    if (!ccxp::plan_call(call_facts(h), call_in(h, c)).stepwise)
+        return finish_call(h, num_steps, c.out, auto_reset, run_rollout(h, c));
+    // ... or, on handles whose short launches cannot use the step kernel, the composition itself, step by step on the handle's
+    // stream -- policy kernel, merge kernel, the existing step path.
     auto policy_then_merge = [&](int s, uint8_t* acts) {
         hipError_t e = ccx::launch_greedy_actions(h->stream, launch_params(h), h->st, h->cell_info, acts, policy);
         if (e != hipSuccess) return fail(CCX_EHIP, "policy kernel launch failed: %s", hipGetErrorString(e));
@@ -1029,6 +981,20 @@ int ccx_action_masks(ccx_handle* h, uint8_t* masks) {
     return CCX_OK;
 }
 
+namespace {
+// ccx_get_masks_fused, ccx_get_reset_obs_fused: the plan of the first launch of such a call from an action tensor, with masks
+// bound and restarted rows to write
+ccxp::LaunchPlan query_plan(const ccx_handle* h, int num_steps, int has_order, int mixed) {
+    StepCall c;
+    c.K = num_steps;
+    c.mixed = mixed != 0;
+    ccxp::CallIn in = call_in(h, c);
+    in.actions = 1; in.order = has_order != 0; in.masks_bound = 1; in.reset_obs_on = 1;
+    const ccxp::CallFacts f = call_facts(h);
+    return ccxp::plan_launch(f, in, std::min(num_steps, ccxp::plan_call(f, in).steps_per_launch));
+}
+}  // namespace
+
 int ccx_bind_action_masks(ccx_handle* h, uint8_t* masks_or_null) {
     if (!h) return fail(CCX_EINVAL, "NULL handle");
     h->bound_masks = masks_or_null;
@@ -1038,8 +1004,7 @@ int ccx_bind_action_masks(ccx_handle* h, uint8_t* masks_or_null) {
 int ccx_get_masks_fused(ccx_handle* h, int32_t num_steps, int32_t has_order, int32_t mixed, int32_t* fused) {
     if (!h || !fused) return fail(CCX_EINVAL, "NULL argument");
     if (num_steps < 1) return fail(CCX_EINVAL, "num_steps must be >= 1");
-    (void)mixed;      // (both kinds of launch have their MSK instantiations: ccx_step.hip)
-    *fused = (h->step_shape.ok && h->tun_step_kernel != 0 && ccx::step_masks_fused(num_steps, has_order != 0)) ? 1 : 0;
+    *fused = query_plan(h, num_steps, has_order, mixed).masks_fused ? 1 : 0;
     return CCX_OK;
 }
 
@@ -1061,8 +1026,7 @@ int ccx_bind_final_obs(ccx_handle* h, float* final_obs_or_null, float* final_com
 int ccx_get_reset_obs_fused(ccx_handle* h, int32_t num_steps, int32_t has_order, int32_t mixed, int32_t* fused) {
     if (!h || !fused) return fail(CCX_EINVAL, "NULL argument");
     if (num_steps < 1) return fail(CCX_EINVAL, "num_steps must be >= 1");
-    *fused = (h->step_shape.ok && h->tun_step_kernel != 0 && h->tun_reset_obs_fused != 0 &&
-              ccx::step_reset_obs_fused(num_steps, has_order != 0, mixed != 0)) ? 1 : 0;
+    *fused = query_plan(h, num_steps, has_order, mixed).reset_obs_fused ? 1 : 0;
     return CCX_OK;
 }
 
@@ -1295,9 +1259,9 @@ int ccx_set_pace_calibration(ccx_handle* h, int32_t enabled) {
 
 int ccx_get_pace_start(ccx_handle* h, float* ns_per_env_step, int32_t* source, float* probe_gbs) {
     if (!h) return fail(CCX_EINVAL, "NULL handle");
-    if (ns_per_env_step) *ns_per_env_step = h->kp.pace_state ? ccxp::fp_to_ns(h->pace_init_fp) : 0.0f;
-    if (source) *source = h->kp.pace_state ? h->pace_start_source : CCX_PACE_START_UNPACED;
-    if (probe_gbs) *probe_gbs = h->pace_probe_gbs;
+    if (ns_per_env_step) *ns_per_env_step = h->kp.pace_state ? ccxp::fp_to_ns(h->pace.init_fp) : 0.0f;
+    if (source) *source = h->kp.pace_state ? h->pace.start_source : CCX_PACE_START_UNPACED;
+    if (probe_gbs) *probe_gbs = h->pace.probe_gbs;
     return CCX_OK;
 }
 
@@ -1334,14 +1298,14 @@ int ccx_set_tunable(ccx_handle* h, const char* name, int32_t value) {
 int ccx_get_step_pace(ccx_handle* h, float* ns_per_env_step) {
     if (!h || !ns_per_env_step) return fail(CCX_EINVAL, "NULL argument");
     CCX_HIP(hipSetDevice(h->device));
-    uint32_t fp = h->pace_init_fp;
+    uint32_t fp = h->pace.init_fp;
     if (!h->kp.pace_state) {   // off, or adaptive on a batch too small to be memory-bound
         fp = 0;
-    } else if (!h->pace_dirty) {
+    } else if (!h->pace.dirty) {
         CCX_HIP(hipStreamSynchronize(h->stream));
         uint32_t st[4];
-        CCX_HIP(hipMemcpy(st, h->pace_state, sizeof(st), hipMemcpyDeviceToHost));
-        fp = st[h->pace_slot] > st[2] ? st[h->pace_slot] : st[2];
+        CCX_HIP(hipMemcpy(st, h->pace.state, sizeof(st), hipMemcpyDeviceToHost));
+        fp = st[h->pace.slot] > st[2] ? st[h->pace.slot] : st[2];
     }
     *ns_per_env_step = ccxp::fp_to_ns(fp);
     return CCX_OK;
@@ -1352,14 +1316,15 @@ int ccx_get_pace_state(ccx_handle* h, float* out6) {
     CCX_HIP(hipSetDevice(h->device));
     CCX_HIP(hipStreamSynchronize(h->stream));
     uint32_t st[8];
-    CCX_HIP(hipMemcpy(st, h->pace_state, sizeof(st), hipMemcpyDeviceToHost));
+    CCX_HIP(hipMemcpy(st, h->pace.state, sizeof(st), hipMemcpyDeviceToHost));
     const auto ns = ccxp::fp_to_ns;
-    out6[0] = h->pace_dirty ? ns(h->pace_init_fp) : ns(st[h->pace_slot]);   // the vote the next launch reads
-    out6[1] = h->pace_dirty ? 0.0f : ns(st[2]);                             // floor
-    out6[2] = h->pace_dirty ? 0.0f : (float)st[3];                          // launches since the last collapse
+    const bool dirty = h->pace.dirty;
+    out6[0] = dirty ? ns(h->pace.init_fp) : ns(st[h->pace.slot]);   // the vote the next launch reads
+    out6[1] = dirty ? 0.0f : ns(st[2]);                             // floor
+    out6[2] = dirty ? 0.0f : (float)st[3];                          // launches since the last collapse
     out6[3] = h->kp.pace_state ? 1.0f : 0.0f;
-    out6[4] = h->pace_dirty ? 0.0f : ns(st[4]);                             // pace of the last collapse (the cliff)
-    out6[5] = h->pace_dirty ? 0.0f : (float)st[5];                          // confirmations of that cliff
+    out6[4] = dirty ? 0.0f : ns(st[4]);                             // pace of the last collapse (the cliff)
+    out6[5] = dirty ? 0.0f : (float)st[5];                          // confirmations of that cliff
     return CCX_OK;
 }
 
@@ -1438,11 +1403,21 @@ int ccxi_handle_plan(const ccx_handle* h, int rows, ccxi_plan_out* out, int* blo
     pp.paced = k.pace_state != nullptr;
     if (rows) {
         pp.ring_when_paced = h->ring_when_paced;
-        pp.pace_init_fp = h->pace_init_fp;
-        pp.pace_start_source = h->pace_start_source;
+        pp.pace_init_fp = h->pace.init_fp;
+        pp.pace_start_source = h->pace.start_source;
     }
     ccxp::plan_out(s, k, rows ? h->step_shape : ccx::StepShape{}, pp, out);
     if (blocks_per_cu) *blocks_per_cu = ccx::rollout_blocks_per_cu(s, h->N);   // (the query choose_shape made for this shape)
+    return CCX_OK;
+}
+
+int ccxi_handle_call_plan(const ccx_handle* h, const ccxi_call_in* call, int launch, ccxi_call_out* out) {
+    if (!h || !call || !out) return fail(CCX_EINVAL, "NULL argument");
+    ccxp::CallIn in = *call;
+    in.hand2 = h->tun_hand2; in.round_launches = h->tun_round_launches; in.small_shape = h->tun_small_shape;
+    in.step_kernel = h->tun_step_kernel; in.max_launch_steps = h->tun_max_launch_steps; in.reset_obs_fused = h->tun_reset_obs_fused;
+    if (ccxp::plan_call_out(call_facts(h), in, launch, out) != CCX_OK)
+        return fail(CCX_EINVAL, "K = %d has no launch number %d", in.K, launch);
     return CCX_OK;
 }
 

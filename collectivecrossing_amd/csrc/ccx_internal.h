@@ -22,6 +22,24 @@ int row_blocks(const char* who, int64_t rows, int64_t rows_per_block, unsigned& 
 int episode_stats_reset(struct ::ccx_handle* h, const uint8_t* env_mask);
 void episode_stats_destroy(struct ::ccx_handle* h);
 
+// The pace controller of the rollout kernel (ccx_kernels.h: KParams::pace_state), host side.  apply() (ccx_api.hip) resets it
+// with every new plan; prepare() is the ONE function that restarts it on the device.
+struct PaceController {
+    uint32_t* state = nullptr;        // device u32 [8]: current pace (ticks x 256) in [slot], votes in [slot ^ 1], floor, cliff memory
+    uint32_t slot = 0;                // slot of `state` the next launch reads
+    uint32_t init_fp = 0;             // value to (re)start the controller from
+    bool dirty = true;                // `state` must be rewritten before a paced launch
+    bool needs_calibration = false;   // the controller runs from the assumed start value: the first ADAPTIVE eager launch calibrates and restarts it
+    int start_source = 0;             // CCX_PACE_START_*: where the start value came from
+    float probe_gbs = 0.0f;           // write rate the calibration probe measured (GB/s), 0 = not run
+
+    // Ahead of a launch of the rollout kernel that the plan calls `paced` / `adaptive` (ccx_plan.h: LaunchPlan), on a stream
+    // that is `capturing` or not: (re)start the controller where it is due -- new handle, launch shape or setting --, with the
+    // start value calibrated on the `obs_bytes` at `obs` that the launch is about to overwrite.  Enqueues memsets on the
+    // handle's stream and, when it calibrates, synchronises it once; refuses to do either inside a capture.
+    int prepare(const ::ccx_handle* h, bool paced, bool adaptive, bool capturing, float* obs, size_t obs_bytes);
+};
+
 }  // namespace ccxi
 
 #define CCX_HIP(call)                                                                         \
@@ -53,18 +71,12 @@ struct ccx_handle {
     int lanes_per_wave = 0, waves_per_block = 0, writers = 0;  // user overrides (0 = default)
     int store_throttle = 0;                                    // 0 = default, -1 = off, >0 = stores in flight
     int step_pace_ns = 0;                                      // 0 = adaptive, -1 = off, >0 = fixed ns per env-step
-    uint32_t* pace_state = nullptr;                            // device: current pace (ticks x 256)
-    uint32_t pace_init_fp = 0;                                 // value to (re)start the controller from
-    bool pace_dirty = true;                                    // pace_state must be rewritten before a launch
-    bool pace_needs_calibration = false;                       // the controller runs from the assumed start value: the first ADAPTIVE eager launch calibrates and restarts it
+    ccxi::PaceController pace;                                 // the pace controller's host side (the caller's settings: step_pace_ns above, pace_start_ns, pace_calibrate)
     uint16_t* obs_table = nullptr;                             // device: obs address table of the current shape
     std::vector<uint16_t> obs_table_host;
-    uint32_t pace_slot = 0;                                    // slot of pace_state the next launch reads
     int num_cus = 256;
     float pace_start_ns = 0.0f;                                // > 0: the adaptive controller starts here (ccx_set_step_pace_start)
     bool pace_calibrate = true;                                // measure the start value in-process (ccx_set_pace_calibration)
-    int pace_start_source = 0;                                 // CCX_PACE_START_*: where the controller's start value came from
-    float pace_probe_gbs = 0.0f;                               // write rate the calibration probe measured (GB/s), 0 = not run
     int tun_pace_phase = -1, tun_tile_map = -1;                 // -1 = the library's choice for the launch shape
     int tun_writer_roles = -1;                                  // -1 = by batch size, 0 = writers share everything, 1 = writer 0 small outputs only
     int tun_hand2 = 1;                                          // sim -> writer hand-off: 0 barrier per step, 1 sequence words in unpaced launches, 2 always

@@ -66,7 +66,7 @@ constexpr uint32_t kSyncOff = 256u, kSyncBytes = 64u, kStageOff = kSyncOff + kSy
 constexpr uint32_t tile_head_bytes(uint32_t stage_slots) { return kStageOff + stage_slots * kStageSlotBytes; }
 constexpr uint32_t kSyncSeq = 0u, kSyncProg = 4u;          // (kSyncProg + writer index, at most 7 writers)
 
-// ONE definition of how a launch is driven, shared by the host (run_rollout) and the kernel: a launch is PACED when the
+// ONE definition of how a launch is driven, shared by the host (plan_launch) and the kernel: a launch is PACED when the
 // handle paces its shape, it writes observation rows and is long enough to be worth the clock reads; the pace controller
 // ADAPTS (votes, slot flip on the host) only in paced launches of at least 64 steps; launches that are not paced hand
 // steps from the sim wave to the writer waves through sequence words instead of a barrier per step (tunable "hand2").
@@ -130,7 +130,7 @@ struct KParams {
     const double* reward_table;
     uint32_t off_rtab;
     uint32_t user_tables;                // 1: a user reward / terminated table is set: launch the instantiations that are not PLAIN
-    // A grid of more workgroups than the device holds is launched ROUND BY ROUND (ccx_api.hip: run_rollout): this launch
+    // A grid of more workgroups than the device holds is launched ROUND BY ROUND (ccx_plan.hip: plan_launch): this launch
     // carries workgroups block_base .. block_base + gridDim.x - 1 of the grid (launch_flags bit 0: it is one round of a larger grid).
     uint32_t block_base, launch_flags;
 #ifdef CCX_LAG_TRACE

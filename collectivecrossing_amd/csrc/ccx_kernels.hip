@@ -257,7 +257,7 @@ hipError_t launch_expand(const LaunchShape& ls, hipStream_t stream, const KParam
     return launch_observe_any(ls, stream, q, KState{}, obs, reinterpret_cast<const float4*>(compact), (unsigned)blocks);
 }
 
-// Pace calibration probe (ccx_api.hip: calibrate_pace): a plain fill of the caller's own trajectory buffer -- one
+// Pace calibration probe (ccx_api.hip: probe_write_rate): a plain fill of the caller's own trajectory buffer -- one
 // workgroup per 16 KiB, four 16-byte stores per lane, cached stores like a library fill (measured: streaming `nt` stores
 // issued flat out, without the rollout's pacing, drain 25 % slower than the paced rollout does and are no yardstick for
 // it; a plain fill lands within a few per cent of it on every box seen).  What it writes is overwritten by the rollout

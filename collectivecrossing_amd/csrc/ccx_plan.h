@@ -45,6 +45,39 @@ int ccxi_plan(const ccxi_plan_in* in, int blocks_per_cu, ccxi_plan_out* out);
 // the plan of a live handle's rows (rows = 1) or no-rows shape, and the occupancy figure the runtime gives for it
 int ccxi_handle_plan(const struct ccx_handle* h, int rows, ccxi_plan_out* out, int* blocks_per_cu);
 
+// one stepping call, as the per-call planner reads it (every field an int32): the call itself, then the handle's tunables
+typedef struct ccxi_call_in {
+    int32_t K;                                            // env-steps of the call
+    int32_t actions, order, actions_out;                  // 1: the call has an action tensor / a move order / an actions_out tensor
+    int32_t policy;                                       // in-kernel policy of the rollout kernel (CCX_POLICY_*, 0 = the tensor)
+    int32_t mixed;                                        // 1: the mixed-control entry point (ccx_rollout_mixed)
+    int32_t writes_obs;                                   // 1: the call writes observation rows
+    int32_t capturing;                                    // 1: the handle's stream is being captured into a graph
+    int32_t masks_bound, reset_obs_on;                    // 1: the call may write the bound masks / the restarted rows in its launch
+    int32_t hand2, round_launches, small_shape, step_kernel, max_launch_steps, reset_obs_fused;   // tunables
+} ccxi_call_in;
+
+// one int64 per field, in this order (ccxi_call_field_names()).  The first four describe the call, the rest ONE of its launches
+// (`k` steps); a refused call has no launches and zeros there.
+#define CCXI_CALL_FIELDS(X)                                                                                              \
+    X(steps_per_launch) X(launches) X(refused) X(stepwise)                                                               \
+    X(k) X(kernel) X(shape) X(paced) X(adaptive) X(pace_adapt) X(flip_slot) X(hand_flags) X(by_rounds) X(per_round)      \
+    X(rounds) X(masks_fused) X(reset_obs_fused)
+enum {
+#define CCXI_X(name) CCXI_C_##name,
+    CCXI_CALL_FIELDS(CCXI_X)
+#undef CCXI_X
+    CCXI_CALL_NFIELDS
+};
+typedef struct ccxi_call_out { int64_t v[CCXI_CALL_NFIELDS]; } ccxi_call_out;
+
+const char* ccxi_call_field_names(void);
+// the pure per-call planner: both shapes of `in` planned with their occupancy figures (blocks_per_cu[0]: rows, [1]: no rows;
+// in->rows is ignored), then plan_call and plan_launch of launch number `launch` (0 .. launches - 1).  Works without a GPU.
+int ccxi_plan_call(const ccxi_plan_in* in, const int* blocks_per_cu, const ccxi_call_in* call, int launch, ccxi_call_out* out);
+// the same for a live handle: its two shapes and ITS tunables (the six tunable fields of `call` are ignored)
+int ccxi_handle_call_plan(const struct ccx_handle* h, const ccxi_call_in* call, int launch, ccxi_call_out* out);
+
 }  // extern "C"
 
 namespace ccxp {
@@ -96,5 +129,50 @@ bool reward_table_fits(PlanIn in);   // both shapes of `in` with a reward table 
 void materialize(const ShapePlan& sp, const PacePlan& pp, ccx::LaunchShape& s, ccx::KParams& k);
 // reads `paced`, `ring_when_paced`, `pace_init_fp` and `pace_start_source` from pp, everything else from s / k / step
 void plan_out(const ccx::LaunchShape& s, const ccx::KParams& k, const ccx::StepShape& step, const PacePlan& pp, ccxi_plan_out* out);
+
+// ---- Stage 3, per call: how a stepping call is cut into launches and how each launch is driven.  Pure like the
+// rest: the caller says what the handle's two shapes are and what the call is.
+using CallIn = ccxi_call_in;
+
+// what a call's launches depend on of one planned shape
+struct CallShape {
+    int num_blocks, resident_blocks;
+    double step_bytes;
+    bool paced;                       // PacePlan::paced: KParams::pace_state is set
+    uint32_t pace_adapt, pace_min_k, adapt_min_k;
+    bool ring_when_paced, step_ok;    // rows shape only (PacePlan::ring_when_paced, StepShape::ok)
+};
+CallShape call_shape(const ccx::LaunchShape& s, const ccx::KParams& k, bool ring_when_paced, bool step_ok);
+struct CallFacts {
+    int E, N;
+    CallShape shape[2];               // [0] launches that write observation rows, [1] launches without
+};
+
+struct CallPlan {
+    int steps_per_launch, launches;   // every launch takes steps_per_launch steps but the last, which takes the rest
+    bool refused;                     // an odd E x N slab that would have to be cut into launches of one step
+    bool stepwise;                    // the unfused mixed-control step: one env-step per launch, actions produced in between
+};
+enum : int { KERNEL_STEP = 0, KERNEL_ROLLOUT = 1 };
+struct LaunchPlan {
+    int kernel;                       // KERNEL_STEP: the short-launch kernel (ccx_step.hip), KERNEL_ROLLOUT: the rollout kernel
+    int shape;                        // index into CallFacts::shape; this and the next nine: rollout kernel only, 0 for the step kernel
+    bool paced, adaptive;           // ccx_kernels.h: launch_is_paced / launch_is_adaptive of this launch
+    uint32_t pace_adapt;              // KParams::pace_adapt as sent: cleared for an adaptive launch that is being captured
+    bool flip_slot;                   // the host flips the controller's slot behind the launch (the kernel voted)
+    uint32_t hand_flags;              // KParams::hand_flags
+    bool by_rounds;                   // `rounds` launches of per_round workgroups (the last: the rest), block_base 0, per_round, ...
+    int per_round, rounds;
+    bool masks_fused, reset_obs_fused;   // the step launch writes the bound masks / the restarted rows itself
+};
+
+// bytes of the observation rows of `steps` env-steps: [steps][E][N][6 + 4N] floats
+inline size_t obs_bytes(int E, int N, size_t steps = 1) { return steps * (size_t)E * (size_t)N * (size_t)(6 + 4 * N) * sizeof(float); }
+
+CallPlan plan_call(const CallFacts& f, const CallIn& c);
+LaunchPlan plan_launch(const CallFacts& f, const CallIn& c, int k);   // a launch of k steps of the call c
+void call_out(const CallPlan& cp, int k, const LaunchPlan& lp, ccxi_call_out* out);
+// the C entry points' tail: plan_call, then plan_launch of launch number `launch`
+int plan_call_out(const CallFacts& f, const CallIn& c, int launch, ccxi_call_out* out);
 
 }  // namespace ccxp

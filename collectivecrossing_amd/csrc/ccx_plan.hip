@@ -2,6 +2,10 @@
 // count.  Host arithmetic only: no runtime call, no handle, no allocation, no environment.  ccx_api.hip (choose_shape) feeds
 // it from a handle and applies the result; tests/test_shape_plan.py replays a recorded table of decisions through it on
 // a machine without a GPU.
+// The second function, plan_call / plan_launch at the end of the file, decides what is decided per CALL on top of a handle's
+// two planned shapes: how the call is cut into launches, which kernel takes each launch and how that launch is driven (pacing,
+// hand-off, rounds, what the step launch fuses).  ccx_api.hip asks it before every launch; tests/test_call_plan.py holds it
+// against an independent restatement of the rules over a sweep, sizes no test could allocate included.
 //
 // A tile (EW envs) is served by a sim wave and, when outputs are written, writer waves on other SIMDs; one step of a tile
 // is a latency chain of ~1.5k cycles whatever EW is, so the batch should be cut into at least ~512 tiles (1024 waves = one
@@ -585,6 +589,139 @@ bool reward_table_fits(PlanIn in) {
     return true;
 }
 
+// ---- per call ----------------------------------------------------------------------------------------------------------
+CallShape call_shape(const ccx::LaunchShape& s, const ccx::KParams& k, bool ring_when_paced, bool step_ok) {
+    return CallShape{s.num_blocks, s.resident_blocks, s.step_bytes, k.pace_state != nullptr, k.pace_adapt, k.pace_min_k, k.adapt_min_k,
+                     ring_when_paced, step_ok};
+}
+
+namespace {
+
+// the handle's short launches take the step kernel at all (StepShape::ok and the tunable)
+bool step_kernel_on(const CallFacts& f, const CallIn& c) { return f.shape[0].step_ok && c.step_kernel != 0; }
+
+// L = 6 + 4N is 2 mod 4: one step's observation slab (E x N x L floats) is a multiple of 16 bytes only when E x N is even
+bool odd_slab(const CallFacts& f, const CallIn& c) { return c.writes_obs && (obs_bytes(f.E, f.N) & 15u) != 0; }
+
+}  // namespace
+
+// The cutter: a call as one launch, or as several.
+CallPlan plan_call(const CallFacts& f, const CallIn& c) {
+    CallPlan p{};
+    int max_k;
+    if (c.mixed) {
+        // the short-launch kernel's policy instantiations (ccx_step.hip, POL): policy + merge + step in ONE launch per
+        // <= 16 steps, whatever max_launch_steps says (16 is even: every sub-launch's slice of the observation tensor stays
+        // 16-byte aligned).  Handles whose short launches cannot use the step kernel (tables beyond the LDS, or the tunable)
+        // run the composition itself, step by step: policy kernel, merge kernel, the one-step call of the action tensor.
+        p.stepwise = !step_kernel_on(f, c);
+        max_k = p.stepwise ? 1 : ccx::kStepMaxK;
+    } else {
+        // The writer waves address the small output streams (rewards, flag bytes, compact rows, chosen actions) with 32-bit
+        // byte offsets from the stream's base: one launch must stay below 4 GiB per stream.  Longer rollouts are cut into
+        // launches on the same stream (bit-identical: an env's trajectory does not depend on how a rollout is split).
+        const unsigned long long per_step = (unsigned long long)f.E * (unsigned long long)f.N * 16ull;   // the widest stream
+        const unsigned long long fit = 0xFFFFFFFFull / per_step;
+        max_k = (int)std::min<unsigned long long>(fit > 1 ? fit - 1 : 1, 0x7FFFFFFFull);
+        if (c.max_launch_steps > 0) max_k = std::min(max_k, c.max_launch_steps);   // (tests: force the cut)
+        // with E x N odd every sub-launch must start on an EVEN step so that its slice of the tensor stays 16-byte
+        // aligned (an odd cut failed on "obs buffer must be 16-byte aligned" after the first sub-launch had
+        // already advanced the state); launches of ONE step cannot, and such a cut is refused before anything is launched
+        if (odd_slab(f, c) && max_k > 1) max_k &= ~1;
+        p.refused = c.K > max_k && odd_slab(f, c) && max_k == 1;
+    }
+    p.steps_per_launch = max_k;
+    p.launches = p.refused ? 0 : (int)(((long long)c.K + max_k - 1) / max_k);
+    return p;
+}
+
+LaunchPlan plan_launch(const CallFacts& f, const CallIn& c, int k) {
+    LaunchPlan l{};
+    // the step kernel takes what it has instantiations for: up to 16 steps from an action tensor (the mixed entry point:
+    // with its scripted slots, with or without a tensor or actions_out), on handles whose tables fit its LDS
+    const bool tensor_only = c.actions && c.policy == 0 && !c.actions_out;
+    l.kernel = step_kernel_on(f, c) && (c.mixed || (k <= ccx::kStepMaxK && tensor_only)) ? KERNEL_STEP : KERNEL_ROLLOUT;
+    if (l.kernel == KERNEL_STEP) {
+        // Only a call of ONE step fuses (a call that is cut leaves both to the stand-alone kernels behind its LAST launch,
+        // also where it is cut into single steps; same bytes), where an MSK / RSO instantiation exists (ccx_kernels.h); the
+        // mixed launches have none for the restarted rows
+        l.masks_fused = c.masks_bound && ccx::step_masks_fused(c.K, c.order != 0);
+        l.reset_obs_fused = c.reset_obs_on && c.reset_obs_fused != 0 && ccx::step_reset_obs_fused(c.K, c.order != 0, c.mixed != 0);
+        return l;   // (no pacing, no controller state, no capture query)
+    }
+    const bool writes_obs = c.writes_obs != 0;
+    l.shape = !writes_obs && c.small_shape != 0 ? 1 : 0;      // rewards / flag bytes / compact rows only: the no-rows shape
+    const CallShape& s = f.shape[l.shape];
+    l.paced = ccx::launch_is_paced(s.paced, writes_obs, k, s.pace_min_k);
+    l.adaptive = ccx::launch_is_adaptive(s.paced, s.pace_adapt != 0u, writes_obs, k, s.pace_min_k, s.adapt_min_k);
+    // A launch that is being captured into a HIP graph is replayed with these very arguments: the controller
+    // cannot adapt across replays (the slot flip happens once, at capture time), so such a launch runs
+    // at the pace in effect and neither votes nor touches the controller's state.
+    l.pace_adapt = l.adaptive && c.capturing ? 0u : s.pace_adapt;
+    l.flip_slot = l.adaptive && !c.capturing;     // the kernel collected the votes for the next pace in the other slot
+    // launches the kernel will not pace hand steps to the writer waves through sequence words (ccx_kernels.h: one
+    // definition of the launch modes for the host and the kernel)
+    l.hand_flags = ccx::launch_uses_flags(s.paced, writes_obs, k, s.pace_min_k, c.hand2) ? 1u : 0u;
+    // Paced batches whose step period is close to the sim wave's own chain (C2: 2200 .. 3000 envs, 0.41-0.52 us per env-step)
+    // keep the ring too: a barrier per step couples the chain to the writers and such tiles step in 0.46 us instead of 0.40
+    // (2304 envs 0.77 -> 0.83 of the peak, 2816 envs 0.88 -> 0.91; from 3072 envs on there is nothing in it, and saturating
+    // batches want the barrier: DESIGN 3.7; profiles/r04_small_batch.txt)
+    if (c.hand2 == 1 && writes_obs && f.shape[0].ring_when_paced) l.hand_flags = 1u;
+    // A grid of more workgroups than the device holds is launched ROUND BY ROUND: one launch per `resident_blocks`
+    // workgroups, back to back on the stream.  In ONE launch the workgroups of the second round start as slots come free, each on
+    // a schedule of its own, and the chip's write front -- one narrow window per env-step while the tiles march in step --
+    // frays over several slabs.  A launch boundary between the rounds (~2 us against rounds of 100+ us) restarts every round in step.  The kernel sees
+    // its place in the grid through block_base (env indices, tile phases) and knows that it is one round (launch_flags: the pace of a partial last round); the
+    // controller's owner is tile 0 of the first launch and all rounds vote into the same slot, as in one launch.
+    // Only where the rows of the launch exceed the ~4 GB footprint knee (a stream through more memory than that
+    // sustains 5-8 % less, whatever the kernel does; profiles/r04_output_size.txt):
+    // below it the boundary costs 1-2 % (32 768 envs x 64 steps: 0.887 -> 0.873), beyond it the rounds in step win 3-5 %
+    // (65 536 x 64: 0.750 -> 0.785).
+    // The rounds are made EQUAL (R = ceil(blocks / resident) launches of ceil(blocks / R) workgroups, each on a schedule
+    // scaled to its fill): a grid just above a whole number of rounds -- 17 768 envs of C2: 1111 workgroups on 1024 slots --
+    // otherwise spends a full round's time on its last few tiles (0.74-0.77 of the peak where 15 800 envs reach 0.91; balanced:
+    // 0.86-0.87).  That alone is worth the boundary for a paced grid of TWO rounds whose second would be less than 30 % full
+    // (17 000 .. 20 500 envs of C2: +4 .. +12 %; fuller second rounds and grids of three or more rounds: nothing or a loss --
+    // profiles/r04_balanced_rounds.txt).
+    const int resident = s.resident_blocks;
+    const double rows_bytes = writes_obs ? (double)k * (double)obs_bytes(f.E, f.N) : 0.0;
+    const int n_rounds = resident > 0 ? (s.num_blocks + resident - 1) / resident : 1;
+    // ... and whose tiles can FOLLOW the scaled schedule: a tile with one throttled writer steps in ~1 us at best; where the
+    // common pace is already short (5 agents: 1.3 us for a full device) half-full rounds would be asked for 0.7 us, be late,
+    // vote, and drag the common pace up (N = 5, 17 776 envs: 0.52 of the peak that way; profiles/r04_cliff_scan2.txt)
+    const bool thin_second_round = n_rounds == 2 && (double)(s.num_blocks - resident) < 0.3 * resident &&
+                                   s.step_bytes / 7000.0 * (0.5 * s.num_blocks / resident) >= 1200.0;
+    l.by_rounds = resident > 0 && s.num_blocks > resident &&
+                  (c.round_launches >= 2 || (c.round_launches == 1 && (rows_bytes > 3.5e9 || (l.paced && thin_second_round))));
+    l.per_round = l.by_rounds ? (s.num_blocks + n_rounds - 1) / n_rounds : s.num_blocks;
+    l.rounds = (s.num_blocks + l.per_round - 1) / l.per_round;
+    return l;
+}
+
+void call_out(const CallPlan& cp, int k, const LaunchPlan& lp, ccxi_call_out* out) {
+    int64_t* v = out->v;
+    v[CCXI_C_steps_per_launch] = cp.steps_per_launch; v[CCXI_C_launches] = cp.launches; v[CCXI_C_refused] = cp.refused ? 1 : 0;
+    v[CCXI_C_stepwise] = cp.stepwise ? 1 : 0;
+    v[CCXI_C_k] = k; v[CCXI_C_kernel] = lp.kernel; v[CCXI_C_shape] = lp.shape; v[CCXI_C_paced] = lp.paced ? 1 : 0;
+    v[CCXI_C_adaptive] = lp.adaptive ? 1 : 0; v[CCXI_C_pace_adapt] = lp.pace_adapt; v[CCXI_C_flip_slot] = lp.flip_slot ? 1 : 0;
+    v[CCXI_C_hand_flags] = lp.hand_flags; v[CCXI_C_by_rounds] = lp.by_rounds ? 1 : 0; v[CCXI_C_per_round] = lp.per_round;
+    v[CCXI_C_rounds] = lp.rounds; v[CCXI_C_masks_fused] = lp.masks_fused ? 1 : 0;
+    v[CCXI_C_reset_obs_fused] = lp.reset_obs_fused ? 1 : 0;
+}
+
+int plan_call_out(const CallFacts& f, const CallIn& c, int launch, ccxi_call_out* out) {
+    if (c.K < 1 || f.E < 1 || f.N < 1 || launch < 0) return CCX_EINVAL;
+    const CallPlan cp = plan_call(f, c);
+    if (cp.refused) {
+        call_out(cp, 0, LaunchPlan{}, out);
+        return CCX_OK;
+    }
+    if (launch >= cp.launches) return CCX_EINVAL;
+    const int k = (int)std::min<long long>(cp.steps_per_launch, (long long)c.K - (long long)launch * cp.steps_per_launch);
+    call_out(cp, k, plan_launch(f, c, k), out);
+    return CCX_OK;
+}
+
 }  // namespace ccxp
 
 namespace ccx {
@@ -614,6 +751,26 @@ int ccxi_plan(const ccxi_plan_in* in, int blocks_per_cu, ccxi_plan_out* out) {
     ccxp::materialize(sp, pp, s, k);
     ccxp::plan_out(s, k, sp.step, pp, out);
     return CCX_OK;
+}
+
+const char* ccxi_call_field_names(void) {
+#define CCXI_X(name) #name ","
+    return CCXI_CALL_FIELDS(CCXI_X);
+#undef CCXI_X
+}
+
+int ccxi_plan_call(const ccxi_plan_in* in, const int* blocks_per_cu, const ccxi_call_in* call, int launch, ccxi_call_out* out) {
+    if (!in || !blocks_per_cu || !call || !out) return CCX_EINVAL;
+    ccxp::CallFacts f{in->E, in->N, {}};
+    for (int i = 0; i < 2; ++i) {
+        ccxp::PlanIn pin = *in;
+        pin.rows = i == 0 ? 1 : 0;
+        const ccxp::ShapePlan sp = ccxp::plan_shape(pin);
+        const ccxp::PacePlan pp = ccxp::plan_pacing(pin, sp, blocks_per_cu[i]);
+        f.shape[i] = ccxp::CallShape{sp.shape.num_blocks, pp.resident_blocks, pp.step_bytes, pp.paced, pp.pace_adapt, pp.pace_min_k,
+                                     pp.adapt_min_k, pp.ring_when_paced, sp.step.ok != 0};
+    }
+    return ccxp::plan_call_out(f, *call, launch, out);
 }
 
 #ifdef CCX_PLAN_COVERAGE

@@ -136,8 +136,9 @@ def apply_setting(lib, handle, w, h, name, value):
     raise ValueError(name)
 
 
-def handle_rows(lib, nfields, point, num_cus):
-    """The two rows (rows = 1, 0) of one sweep point from a live handle: (inputs dict, refused, blocks_per_cu, outputs)."""
+def handle_rows(lib, nfields, point, num_cus, probe=None):
+    """The two rows (rows = 1, 0) of one sweep point from a live handle: (inputs dict, refused, blocks_per_cu, outputs).
+    ``probe(handle)`` is called on the live handle, after the setting."""
     w, h, n, e, name, value = point
     handle = create(lib, w, h, n, e)
     if handle is None:
@@ -153,6 +154,8 @@ def handle_rows(lib, nfields, point, num_cus):
             rc = lib.ccxi_handle_plan(handle, rows, buf, C.byref(per_cu))
             assert rc == 0, lib.ccx_last_error()
             out.append((plan_inputs(w, h, n, e, name, value, num_cus, rows), refused, per_cu.value, list(buf)))
+        if probe:
+            probe(handle)
         return out
     finally:
         lib.ccx_destroy(handle)

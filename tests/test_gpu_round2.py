@@ -465,7 +465,7 @@ def _shape_config(name):
 @pytest.mark.parametrize("workload,E,K", [("c2", 6001, 128), ("c3", 3000, 64), ("c5_50", 1000, 64)])
 def test_a_new_shape_starts_within_five_percent_of_its_steady_state(ccx, workload, E, K):
     """the first paced launch of a shape nobody has seen measures its start value in-process (a
-    ~2.5 ms write probe of the rollout's own observation buffer, ccx_api.hip: calibrate_pace).  Three shapes that never
+    ~2.5 ms write probe of the rollout's own observation buffer, ccx_api.hip: PaceController::prepare).  Three shapes that never
     had a shipped or cached pace: launches 5-25 of a fresh handle run within 5 % of launches 80-120."""
     import torch
     cfg = _shape_config(workload)
@@ -567,7 +567,7 @@ def test_capturing_a_paced_rollout_before_its_controller_started_is_refused(ccx)
 def test_launch_mode_boundaries_against_the_oracle(oracle, ccx, K, pace, obs):
     """VERDICT r2 item 7.  Whether a launch is paced (pace handle, observations, K >= 16), whether the controller adapts
     (K >= 64) and whether the sim wave hands steps over through sequence words or a barrier are decided by ONE set of
-    helpers (ccx_kernels.h: launch_is_paced / launch_is_adaptive / launch_uses_flags) shared by launch_paced and the
+    helpers (ccx_kernels.h: launch_is_paced / launch_is_adaptive / launch_uses_flags) shared by plan_launch and the
     kernel.  Swept here across the boundaries, at a batch size that is paced at all: two launches each (the second one
     starts from the controller state the first one left), every output equal to the oracle."""
     from collectivecrossing_amd.reset import build_reset_pool
@@ -785,7 +785,7 @@ def test_a_partial_last_round_does_not_drive_the_common_pace_up(ccx):
 @pytest.mark.parametrize("mode", [0, 2])
 def test_round_by_round_launches_equal_the_oracle(oracle, ccx, mode):
     """A grid of more workgroups than the device holds is launched one round per launch when its rows exceed the reach of
-    the ~4 GB footprint knee (ccx_api.hip: launch_paced, KParams::block_base / launch_flags; tunable round_launches: 0 = one
+    the ~4 GB footprint knee (ccx_plan.hip: plan_launch, KParams::block_base / launch_flags; tunable round_launches: 0 = one
     launch, 2 = always by rounds): 6001 envs of the C3 geometry in 3001 tiles -- ragged last tile, partial last round -- are
     bit-equal to the oracle either way, and the counters add up over the rounds."""
     g = Golden("g3_c3_dense_simple_distance")

@@ -8,6 +8,7 @@ and that occupancy figure must return exactly those integers.  The table is rege
 alter decisions, on that change's parent."""
 
 import ctypes as C
+from pathlib import Path
 
 import numpy as np
 import pytest
@@ -33,6 +34,9 @@ def test_internal_entry_points_stay_out_of_the_public_abi(lib):
     from collectivecrossing_amd import _abi
 
     assert hasattr(lib, "ccxi_plan") and hasattr(lib, "ccxi_handle_plan")
+    assert hasattr(lib, "ccxi_plan_call") and hasattr(lib, "ccxi_handle_call_plan") and hasattr(lib, "ccxi_call_field_names")
+    header = (Path(__file__).resolve().parents[1] / "include" / "ccx.h").read_text()
+    assert "ccxi_" not in header
     assert not [n for n in _abi.PROTOTYPES if n.startswith("ccxi_")]
 
 
