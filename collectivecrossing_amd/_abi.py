@@ -85,7 +85,16 @@ class CcxEpisodeStats(C.Structure):
         ("log_capacity", C.c_int64)]
 
 
-COUNTER_FIELDS = tuple(name for name, _ in CcxCounters._fields_)
+ADAM_MAX_TENSORS = 32
+
+
+class CcxAdamTensor(C.Structure):
+    """``ccx_adam_tensor``: one row of ``ccx_adam_step``'s table (CCX_ADAM), device pointers and the element count."""
+
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("numel", C.c_int64)]
+
+
+COUNTER_FIELDS =tuple(name for name, _ in CcxCounters._fields_)
 
 _H = C.c_void_p  # ccx_handle*
 
@@ -149,6 +158,9 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_mlp_sample_actions": (C.c_int, [_H, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 4),
     "ccx_mlp_backward_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "ccx_mlp_backward": (C.c_int, [_H, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p] * 10),
+    "ccx_adam_workspace_bytes": (C.c_int64, [C.c_int32, C.POINTER(C.c_int64)]),
+    "ccx_adam_step": (C.c_int, [_H, C.c_int32, C.POINTER(CcxAdamTensor), C.c_float, C.c_void_p] + [C.c_float] * 5
+                      + [C.c_void_p] * 3),
     "ccx_set_check_inputs": (C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),

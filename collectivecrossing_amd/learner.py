@@ -1,9 +1,9 @@
 """The learner's half of the loop on the device: advantages (CCX_GAE), masked sampling (CCX_SAMPLE), stored actions under
-new logits (CCX_EVALUATE), the PPO loss (CCX_PPO_LOSS) and the two-layer policy head with its backward pass (CCX_MLP) of
-``include/ccx.h``.
+new logits (CCX_EVALUATE), the PPO loss (CCX_PPO_LOSS), the two-layer policy head with its backward pass (CCX_MLP) and the
+optimiser step (CCX_ADAM) of ``include/ccx.h``.
 
 :class:`LearnerOps` carries the methods and is mixed into :class:`~collectivecrossing_amd.batched.BatchedCollectiveCrossing`;
-the result dataclasses, :class:`MlpHead` and the three ``torch.autograd.Function`` classes live here with it.  What a tensor
+the result dataclasses, :class:`MlpHead`, :class:`DeviceAdam` and the three ``torch.autograd.Function`` classes live here with it.  What a tensor
 argument must be is stated once, in :func:`_require`: a pure function of the tensor and the device, so it runs without a
 batch."""
 
@@ -15,6 +15,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from ._abi import ADAM_MAX_TENSORS, CcxAdamTensor
 from ._lib import check
 
 
@@ -601,8 +602,183 @@ class LearnerOps:
             self._current_stream_waits()
         return gl, gv
 
+    # ------------------------------------------------------------------ the optimiser step
+    def adam(self, params, lr: float = 3e-4, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+             max_grad_norm: float = 0.0) -> "DeviceAdam":
+        """An optimiser over ``params`` (up to 32 f32 tensors of this batch's device, e.g. ``[*actor.parameters(),
+        *critic.parameters()]``) whose step is ``ccx_adam_step`` (include/ccx.h CCX_ADAM): the global gradient norm by a
+        fixed f64 tree, the clip at ``max_grad_norm`` (0: none) and Adam with decoupled weight decay, bit-defined, the step
+        count on the device -- three launches on the handle's stream that capture into a graph.  See :class:`DeviceAdam`."""
+        return DeviceAdam(self, params, lr, betas, eps, weight_decay, max_grad_norm)
+
+    def _adam_step(self, params, grads, ms, vs, lr: float, lr_dev, hyper, state, workspace, stats) -> None:
+        """``ccx_adam_step`` on checked tensors: ``hyper`` = (beta1, beta2, eps, weight_decay, max_grad_norm); ``lr_dev`` f32
+        [1] on the device or ``None`` (then ``lr`` by value is the rate)."""
+        table =(CcxAdamTensor * len(params))()
+        for row, p, g, m, v in zip(table, params, grads, ms, vs):
+            row.param, row.grad, row.m, row.v, row.numel = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
+        self._order_after_current_stream(*params, *grads, *ms, *vs, lr_dev, state, workspace, stats)
+        check(self._lib.ccx_adam_step(self._h, len(params), table, lr, _ptr(lr_dev), *hyper, _ptr(state), _ptr(workspace),
+                                      _ptr(stats)))
+        self._current_stream_waits()
+
+
+def _check_adam_hyper(lr, betas, eps, weight_decay, max_grad_norm):
+    """The hyper-parameters as the f32 values the library will see, or ``ValueError``: ``(lr, (beta1, beta2, eps,
+    weight_decay, max_grad_norm))``."""
+    try:
+        beta1, beta2 = betas
+        vals = [float(np.float32(x)) for x in (lr, beta1, beta2, eps, weight_decay, max_grad_norm)]
+    except (TypeError, ValueError):
+        raise ValueError("lr, eps, weight_decay and max_grad_norm must be numbers and betas a pair of numbers") from None
+    lr, beta1, beta2, eps, weight_decay, max_grad_norm = vals
+    inf = float("inf")
+    for name, x in (("beta1", beta1), ("beta2", beta2)):
+        if not 0.0 <= x < 1.0:                                       # (false for NaN)
+            raise ValueError(f"{name} must lie in [0, 1) as a float32, got {x!r}")
+    if not 0.0 < eps < inf:
+        raise ValueError(f"eps must be finite and positive as a float32, got {eps!r}")
+    for name, x in (("lr", lr), ("weight_decay", weight_decay), ("max_grad_norm", max_grad_norm)):
+        if not 0.0 <= x < inf:
+            raise ValueError(f"{name} must be finite and not negative, got {x!r}")
+    return lr, (beta1, beta2, eps, weight_decay, max_grad_norm)
+
+
+class DeviceAdam:
+    """Adam with decoupled weight decay and global-norm gradient clipping over up to 32 f32 tensors, one step =
+    ``ccx_adam_step`` (include/ccx.h CCX_ADAM): three launches on the handle's stream, every bit of the new parameters,
+    ``m``, ``v`` and of the norm defined by the written rule, so the same gradients give the same update on any machine, eager
+    or captured.  Made by :meth:`BatchedCollectiveCrossing.adam`.
+
+    The optimiser owns ``m`` and ``v`` (lists of zeros shaped like the parameters), ``state`` (u8 [64] on the device: the
+    running products ``beta^step`` as f64, the step count and the count of skipped steps as i64), the workspace and ``stats``
+    (f32 [4] = gradient norm, clip scale, skipped 0 / 1, the rate used; :attr:`grad_norm`, :attr:`scale` and :attr:`skipped`
+    are 0-dim views).  A step whose norm is NaN or infinite changes nothing but ``skipped``.  The rate lives in a device
+    scalar: ``opt.lr = x`` writes it on the handle's stream, so a schedule works between the replays of a captured graph.
+
+    ``step(grads=None)`` reads every parameter's ``.grad``; ``grads=`` names the gradient tensors instead, in the order of
+    the parameters (e.g. the ``w1t, b1, w2, b2`` of an :class:`MlpGradResult` per head: static buffers for a graph).  The
+    gradients are read only; the clipped gradient is never stored.  A wrong dtype, shape or device, a non-contiguous or
+    misaligned tensor, a missing ``.grad``, more than 32 tensors or a hyper-parameter out of range raises ``ValueError``
+    before the library is called.  Only enqueues."""
+
+    def __init__(self, batch, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0):
+        self._lr, self._hyper = _check_adam_hyper(lr, betas, eps, weight_decay, max_grad_norm)
+        try:
+            params = list(params)
+        except TypeError:
+            raise ValueError("params must be an iterable of tensors") from None
+        if not 1 <= len(params) <= ADAM_MAX_TENSORS:
+            raise ValueError(f"params must hold 1..{ADAM_MAX_TENSORS} tensors, got {len(params)}")
+        self.batch, self.params = batch, params
+        self._check_params()
+        dev = batch.device
+        self.m = [torch.zeros_like(p, requires_grad=False) for p in params]
+        self.v = [torch.zeros_like(p, requires_grad=False) for p in params]
+        self.state = torch.zeros((64,), dtype=torch.uint8, device=dev)
+        self.state.view(torch.float64)[:2] = 1.0
+        self.stats = torch.zeros((4,), dtype=torch.float32, device=dev)
+        self._lr_dev = torch.full((1,), self._lr, dtype=torch.float32, device=dev)
+        numel = (C.c_int64 * len(params))(*(p.numel() for p in params))
+        self.workspace = torch.empty((int(batch._lib.ccx_adam_workspace_bytes(len(params), numel)),), dtype=torch.uint8, device=dev)
+
+    grad_norm = property(lambda self: self.stats[0])
+    scale = property(lambda self: self.stats[1])
+    skipped = property(lambda self: self.stats[2])
+
+    def _check_params(self) -> None:
+        for i, p in enumerate(self.params):
+            _require(f"params[{i}]", p, torch.float32, None, self.batch.device, align=16, verb="be and stay")
+            if p.numel() < 1:
+                raise ValueError(f"params[{i}] must have at least one element")
+
+    @property
+    def lr(self) -> float:
+        return self._lr
+
+    @lr.setter
+    def lr(self, value) -> None:
+        self._lr, _ = _check_adam_hyper(value, *self._hyper_args())
+        b = self.batch
+        b._order_after_current_stream(self._lr_dev)
+        with torch.cuda.stream(b._stream):
+            self._lr_dev.fill_(self._lr)
+
+    def _hyper_args(self):
+        beta1, beta2, eps, weight_decay, max_grad_norm = self._hyper
+        return (beta1, beta2), eps, weight_decay, max_grad_norm
+
+    def zero_grad(self, set_to_none: bool = False) -> None:
+        """Zero every parameter's ``.grad`` in place (the default: the buffers stay where a graph found them) or drop it."""
+        for p in self.params:
+            if p.grad is not None:
+                if set_to_none:
+                    p.grad = None
+                else:
+                    p.grad.detach_()
+                    p.grad.zero_()
+
+    def step(self, grads=None) -> None:
+        self._check_params()
+        if grads is None:
+            grads = [p.grad for p in self.params]
+            names = [f"params[{i}].grad" for i in range(len(grads))]
+            hint = " (a parameter without .grad: run backward first, or pass grads=)"
+        else:
+            try:
+                grads = list(grads)
+            except TypeError:
+                raise ValueError("grads must be an iterable of tensors") from None
+            if len(grads) != len(self.params):
+                raise ValueError(f"grads must hold one tensor per parameter ({len(self.params)}), got {len(grads)}")
+            names = [f"grads[{i}]" for i in range(len(grads))]
+            hint = ""
+        b = self.batch
+        _require_all(b.device, *((n, g, torch.float32, tuple(p.shape), {"align": 16, "hint": hint})
+                                 for n, g, p in zip(names, grads, self.params)))
+        b._adam_step([p.detach() for p in self.params], [g.detach() for g in grads], self.m, self.v, self._lr, self._lr_dev,
+                     self._hyper, self.state, self.workspace, self.stats)
+
+    def counts(self) -> tuple[int, int]:
+        """``(steps taken, steps skipped)`` from the device state.  Synchronises."""
+        self.batch._current_stream_waits()
+        step, skipped = self.state.view(torch.int64)[2:4].tolist()
+        return int(step), int(skipped)
+
+    def state_dict(self) -> dict:
+        """Copies of ``m``, ``v`` and the 64 state bytes, and the hyper-parameters."""
+        self.batch._current_stream_waits()
+        (beta1, beta2), eps, weight_decay, max_grad_norm = self._hyper_args()
+        return {"m": [t.clone() for t in self.m], "v": [t.clone() for t in self.v], "state": self.state.clone(),
+                "hyper": {"lr": self._lr, "betas": (beta1, beta2), "eps": eps, "weight_decay": weight_decay,
+                          "max_grad_norm": max_grad_norm}}
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Continue from a :meth:`state_dict` (of an optimiser over parameters of the same shapes): exact copies."""
+        try:
+            ms, vs, state, hy = list(sd["m"]), list(sd["v"]), sd["state"], dict(sd["hyper"])
+            lr, hyper = _check_adam_hyper(hy["lr"], hy["betas"], hy["eps"], hy["weight_decay"], hy["max_grad_norm"])
+        except (KeyError, TypeError):
+            raise ValueError("not a DeviceAdam state_dict (keys m, v, state, hyper)") from None
+        if len(ms) != len(self.m) or len(vs) != len(self.v):
+            raise ValueError(f"the state_dict holds {len(ms)} tensors, the optimiser {len(self.m)}")
+        for name, src, dst in (("m", ms, self.m), ("v", vs, self.v)):
+            for i, (s, d) in enumerate(zip(src, dst)):
+                if not isinstance(s, torch.Tensor) or s.dtype is not torch.float32 or s.shape != d.shape:
+                    raise ValueError(f"state_dict {name}[{i}] must be a torch.float32 tensor of shape {tuple(d.shape)}")
+        if not isinstance(state, torch.Tensor) or state.dtype is not torch.uint8 or tuple(state.shape) != (64,):
+            raise ValueError("state_dict state must be a torch.uint8 tensor of 64 bytes")
+        with torch.no_grad():
+            for src, dst in ((ms, self.m), (vs, self.v)):
+                for s, d in zip(src, dst):
+                    d.copy_(s)
+            self.state.copy_(state)
+        self._hyper = hyper
+        self.lr = lr
+
 
 class _EvaluateActions(torch.autograd.Function):
+
     """:meth:`BatchedCollectiveCrossing.evaluate_actions` for logits that require a gradient: forward and backward are
     the two kernels of CCX_EVALUATE; nothing is saved but the inputs."""
 

@@ -909,6 +909,77 @@ int ccx_mlp_backward(ccx_handle* h, int64_t rows, int32_t L, int32_t H, int32_t 
                      void* workspace, float* grad_w1t /* [L][H] */, float* grad_b1 /* [H] */, float* grad_w2 /* [O][H] */,
                      float* grad_b2 /* [O] */, float* grad_a_or_null /* [rows][H] */);
 /*
+ * CCX_ADAM: one optimiser step over a set of f32 parameter tensors -- the global gradient norm, the clip scale, and Adam
+ * with decoupled weight decay (AdamW; the only kind) -- the link between ccx_mlp_backward's gradients and the next forward.
+ * The step counter and the bias corrections live on the device, so a captured graph advances them on replay.  Every output
+ * is bit-defined, the norm's reduction included.  A pure function of its arrays: the handle supplies device and stream only.
+ *
+ * The discipline is CCX_SAMPLE's and CCX_PPO_LOSS's: every f32 operation named below is ONE correctly rounded f32 operation
+ * (+ - * / sqrt), every f64 operation ONE correctly rounded f64 operation, nothing is fused (no fma), nothing is
+ * reassociated, subnormals are kept, and a choice is a select.
+ *
+ * Inputs: T tensors, 1 <= T <= CCX_ADAM_MAX_TENSORS, as a HOST array of ccx_adam_tensor (it is copied into the kernel
+ * arguments: no host-to-device copy is enqueued).  Each row: param, grad, m, v (device pointers, contiguous f32, 16-byte
+ * aligned, numel >= 1 elements each, no two overlapping).  param, m and v are updated in place; grad is read only -- the
+ * clipped gradient is never stored.  By value: lr >= 0, 0 <= beta1 < 1, 0 <= beta2 < 1, eps > 0, weight_decay >= 0,
+ * max_grad_norm >= 0 (0 = no clipping), all finite.  lr_dev_or_null: when given, the rate is lr_dev[0] (a device scalar: a
+ * schedule works under a captured graph) and the by-value lr is not used.
+ *
+ * 1. Sum of squares, by the tree of CCX_PPO_LOSS.  The elements form a virtual sequence: the tensors in table order, each
+ *    padded to a multiple of 256 places, so a block of 256 places never straddles two tensors and B = sum ceil(numel_t / 256).
+ *    A place that exists contributes the exact f64 product (double)g * (double)g, a padding place +0.0.  Groups of 64 places
+ *    are reduced by halving, four groups to a block as ((G0 + G1) + G2) + G3, and the B block partials by the final step
+ *    (place j of 64 adds P[j], P[j + 64], ... in ascending order onto +0.0; the 64 places are halved).  The result is S.
+ *    The tree depends on the list of numel alone.
+ * 2. Norm and skip.  nd = sqrt(S) in f64;  gn = (float)nd;  skip = gn is NaN or +inf (any NaN or +-inf among the gradients,
+ *    or a norm beyond f32).  When skip holds, every param, m, v, pow1, pow2 and step keep their bits, state.skipped increases
+ *    by one and stats[2] = 1.0f.
+ * 3. Scale.  max_grad_norm > 0:  den = gn + 1e-6f;  c = max_grad_norm / den;  scale = c < 1.0f ? c : 1.0f  (computed from gn
+ *    whether or not skip holds).  max_grad_norm == 0: the gradient is used as it is and scale = 1.0f.
+ * 4. Bias corrections, without pow (whose bits no libm promises).  state keeps the f64 running products pow1 and pow2, both
+ *    1.0 at the start.  A step that is not skipped:  pow1 = pow1 * (double)beta1;  pow2 = pow2 * (double)beta2;  step += 1.
+ *    Then  bc1 = (float)(1.0 - pow1);  bc2 = (float)(1.0 - pow2);  once per call in f64, rounded to f32 once each,
+ *    omb1 = (float)(1.0 - (double)beta1);  omb2 = (float)(1.0 - (double)beta2);  once per call in f32,  lrwd = lr * weight_decay.
+ * 5. Per element of a step that is not skipped (f32, one rounding each):
+ *      gs = max_grad_norm > 0 ? g * scale : g
+ *      pd = weight_decay != 0 ? p - p * lrwd : p                         (two operations)
+ *      m' = beta1 * m + omb1 * gs                                        (three operations)
+ *      gg = gs * gs;   v' = beta2 * v + omb2 * gg                        (three operations)
+ *      mh = m' / bc1;  vh = v' / bc2;  dn = sqrt(vh) + eps;  u = mh / dn
+ *      p' = pd - lr * u                                                  (two operations)
+ * Outputs: stats f32 [4] = {gn, scale, skip ? 1.0f : 0.0f, the lr used}.  state: 64 bytes on the device, 8-byte aligned --
+ * f64 pow1, f64 pow2, i64 step, i64 skipped, 32 reserved bytes (zero; never written).  A fresh state is {1.0, 1.0, 0, 0, 0...}.
+ *
+ * Against IEEE f64 (measured on the CPU, tests/test_adam_spec.py, maxima doubled), as max |err| / max(1, |f64 value|) against
+ * torch.optim.AdamW / Adam with clip_grad_norm_ in f64 on the same f32 gradients, 50 steps of the two-head set (5 382
+ * parameters, lr = 3e-4, max_grad_norm = 0.5, 17 steps clipped): parameters within 7.8e-7 without weight decay and within
+ * 4.8e-6 with weight_decay = 0.01 (where a parameter hardly moves, p - p * lrwd rounds the same way step after step), m
+ * within 2.8e-9, v within 6.7e-11 (absolute: |m| and |v| are far below 1 there); gn within one f32 ulp of the f64 norm.
+ *
+ * ccx_adam_step only enqueues THREE plain launches on the handle's stream: block partials; one final wave (norm, skip, scale,
+ * bias corrections, the state advance, stats); the element update, which on a skip returns without a store.  No workgroup
+ * reads a word that another workgroup of the same launch writes; there is no floating-point atomic, no last-block-done
+ * counter, no grid synchronisation, no host synchronisation and no allocation, and everything captures into a HIP graph.
+ * The caller owns the workspace: ccx_adam_workspace_bytes(T, numel) = 64 + 8 * B bytes (0 for a T or a numel outside the
+ * limits), 8-byte aligned; its contents mean nothing between calls.  Offsets are 64-bit.  A NULL handle or a NULL required
+ * pointer, T outside 1..32, a numel < 1 (or beyond 2^40, or B beyond 2^31 - 1), a tensor pointer that is not 16-byte aligned,
+ * a state or workspace that is not 8-byte aligned, or a hyper-parameter outside its range: CCX_EINVAL with a ccx_last_error
+ * message, before any launch.  Not here: other optimisers, L2-coupled weight decay, amsgrad, per-tensor norms, per-group
+ * hyper-parameters, bf16 / f16 state, writing the clipped gradients back.
+ */
+#define CCX_ADAM_MAX_TENSORS 32
+typedef struct ccx_adam_tensor {
+    float*       param;
+    const float* grad;
+    float*       m;
+    float*       v;
+    int64_t      numel;
+} ccx_adam_tensor;
+int64_t ccx_adam_workspace_bytes(int32_t num_tensors, const int64_t* numel /* host [T] */);
+int ccx_adam_step(ccx_handle* h, int32_t num_tensors, const ccx_adam_tensor* tensors /* host [T] */, float lr,
+                  const float* lr_dev_or_null /* [1] */, float beta1, float beta2, float eps, float weight_decay,
+                  float max_grad_norm, void* state /* 64 bytes */, void* workspace, float* stats /* [4] */);
+/*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
  * `rng_seed` of ccx_rollout).  The action of agent slot a of global env g at step t (0-based) of its episode j is
