@@ -172,8 +172,20 @@ def scripted_slot_mask(config: CollectiveCrossingConfig, scripted) -> int:
     return mask
 
 
+def _result_tensors(res) -> list:
+    """The tensors of a StepResult / RolloutResult (``None``: none)."""
+    return [] if res is None else [v for v in vars(res).values() if isinstance(v, torch.Tensor)]
+
+
 class BatchedCollectiveCrossing(LearnerOps):
-    """E envs sharing one config, resident on one GPU for their whole life."""
+    """E envs sharing one config, resident on one GPU for their whole life.
+
+    Every method that enqueues device work keeps the stream-order contract stated in :class:`LearnerOps` (DESIGN.md
+    3.18): launches go to the handle's stream, ordered behind what torch's current stream held before the call and in
+    front of what it gets afterwards, at no cost when the two are the same stream.  Outside it, because they synchronise
+    with the host: ``reset``, ``reset_host``, ``make_reset_pool``, ``set_state`` / ``get_state``, ``counters``,
+    ``finished_episodes``, ``track_episodes``, ``check_inputs``, ``policy_stream_state``, ``set_policy_stream``, the
+    table setters, the pace queries, ``use_stream``, ``synchronize`` and ``close``."""
 
     def __init__(self, config: CollectiveCrossingConfig, num_envs: int, device: int | str | None = None,
                  env_offset: int = 0, total_envs: int | None = None, check_inputs: bool | None = None):
@@ -251,7 +263,9 @@ class BatchedCollectiveCrossing(LearnerOps):
     def _new(self, shape, dtype) -> torch.Tensor:
         return torch.empty(shape, dtype=dtype, device=self.device)
 
-    def _as_dev_u8(self, a, shape) -> torch.Tensor:
+    def _as_dev_u8(self, a, shape, cur=False) -> torch.Tensor:
+        """``a`` as a contiguous u8 device tensor of ``shape``, ordered in front of the launch.  ``cur``: what
+        :meth:`_other_stream` answered earlier in the same call (``None``: the streams are the same, nothing to order)."""
         if isinstance(a, torch.Tensor):
             # (fast path first: a step-wise loop hands over a ready device tensor every few microseconds)
             t = a if (a.dtype is torch.uint8 and a.device == self.device) else a.to(device=self.device, dtype=torch.uint8)
@@ -261,21 +275,26 @@ class BatchedCollectiveCrossing(LearnerOps):
             raise ValueError(f"expected shape {tuple(shape)}, got {tuple(t.shape)}")
         if not t.is_contiguous():
             t = t.contiguous()
-        self._order_after_current_stream(t)
+        if cur is not None:
+            self._order_after_current_stream(t, cur=cur)
         return t
 
-    def _order_after_current_stream(self, *tensors) -> None:
-        """The library launches on the stream captured at construction (or `use_stream`).  Inputs are
-        produced / copied on torch's CURRENT stream: when that is another stream, make the launch stream
-        wait for it and tell the caching allocator that the launch stream uses the buffers (otherwise
-        nothing orders the H2D copy before the kernel, and a temporary could be recycled while the
-        kernel still reads it)."""
-        raw = torch._C._cuda_getCurrentRawStream(self.device.index)      # (an int; ~0.2 us, this is the per-step path)
-        if raw != self._stream_raw:
-            self._stream.wait_stream(torch.cuda.current_stream(self.device))
+    def _order_after_current_stream(self, *tensors, cur=False):
+        """The entry of every enqueueing method (rules (a) and (c) of the stream-order contract, :class:`LearnerOps`).  The
+        library launches on the stream captured at construction (or `use_stream`).  Inputs are produced / copied on
+        torch's CURRENT stream, and earlier work there may still read or write the outputs: when that is another stream,
+        make the launch stream wait for it and tell the caching allocator that the launch stream uses the buffers
+        (otherwise nothing orders the H2D copy before the kernel, and a temporary could be recycled while the kernel still
+        reads it).  ``tensors``: everything the launch touches, outputs included.  ``cur``: what :meth:`_other_stream`
+        answered earlier in the same call (default: ask now); returns it for the exit, :meth:`_current_stream_waits`."""
+        if cur is False:
+            cur = self._other_stream()                                   # (one raw read: this is the per-step path)
+        if cur is not None:
+            self._stream.wait_stream(cur)
             for t in tensors:
                 if t is not None and t.is_cuda:
                     t.record_stream(self._stream)
+        return cur
 
     # ------------------------------------------------------------------ state
     def set_state(self, x=None, y=None, active=None, terminated=None, truncated=None,
@@ -321,7 +340,9 @@ class BatchedCollectiveCrossing(LearnerOps):
         if s.numel() != self.num_envs:
             raise ValueError(f"need {self.num_envs} seeds, got {s.numel()}")
         m = None if env_mask is None else self._as_dev_u8(env_mask, (self.num_envs,))
-        check(self._lib.ccx_reset_seeded(self._h, _ptr(s.contiguous()), _ptr(m)))
+        s = s.contiguous()
+        self._order_after_current_stream(s)
+        check(self._lib.ccx_reset_seeded(self._h, _ptr(s), _ptr(m)))
         return self.observe()
 
     def reset_host(self, seeds) -> torch.Tensor:
@@ -345,6 +366,7 @@ class BatchedCollectiveCrossing(LearnerOps):
         if t.ndim != 3 or tuple(t.shape[1:]) != (self.num_agents, 2):
             raise ValueError(f"pool must be [P, {self.num_agents}, 2], got {tuple(t.shape)}")
         self._pool = t
+        self._order_after_current_stream(t)                  # (copied on the current stream, read by later launches)
         check(self._lib.ccx_set_reset_pool(self._h, _ptr(t), t.shape[0]))
 
     def make_reset_pool(self, seed0: int, size: int, on_device: bool = True) -> None:
@@ -354,6 +376,7 @@ class BatchedCollectiveCrossing(LearnerOps):
             self.set_reset_pool(build_reset_pool(self.config, seed0, size))
             return
         t = self._new((size, self.num_agents, 2), torch.uint8)
+        self._order_after_current_stream(t)
         check(self._lib.ccx_fill_reset_pool_seeded(self._h, _ptr(t), size, seed0))
         self._pool = t
         check(self._lib.ccx_set_reset_pool(self._h, _ptr(t), size))
@@ -362,8 +385,11 @@ class BatchedCollectiveCrossing(LearnerOps):
         return self._pool
 
     def reset_from_pool(self, env_mask=None) -> None:
-        m = None if env_mask is None else self._as_dev_u8(env_mask, (self.num_envs,))
+        cur = self._other_stream()
+        m = None if env_mask is None else self._as_dev_u8(env_mask, (self.num_envs,), cur)
+        self._order_after_current_stream(cur=cur)            # (the state: strategy_view / episode_stats readers)
         check(self._lib.ccx_reset_from_pool(self._h, _ptr(m)))
+        self._current_stream_waits(cur=cur)
 
     # ------------------------------------------------------------------ scripted policy
     def policy_actions(self, policy: str = "greedy", out: torch.Tensor | None = None) -> torch.Tensor:
@@ -372,14 +398,18 @@ class BatchedCollectiveCrossing(LearnerOps):
         :meth:`set_policy_epsilon` is in effect (then the same draws as inside ``rollout_policy``)."""
         if out is None:
             out = self._new((self.num_envs, self.num_agents), torch.uint8)
+        cur = self._order_after_current_stream(out)
         check(self._lib.ccx_policy_actions(self._h, _abi.POLICIES[policy], _ptr(out)))
+        self._current_stream_waits(cur=cur)
         return out
 
     def greedy_actions(self, out: torch.Tensor | None = None) -> torch.Tensor:
         """``GreedyPolicy(epsilon=0)`` for every live agent (``ccx_greedy_actions``; never explores)."""
         if out is None:
             out = self._new((self.num_envs, self.num_agents), torch.uint8)
+        cur = self._order_after_current_stream(out)
         check(self._lib.ccx_greedy_actions(self._h, _ptr(out)))
+        self._current_stream_waits(cur=cur)
         return out
 
     # ------------------------------------------------------------------ legal-action masks
@@ -408,10 +438,11 @@ class BatchedCollectiveCrossing(LearnerOps):
         """Legal actions of every agent slot in the CURRENT state, u8 [E, N] (``ccx_action_masks``): bit a = action a
         would move the agent (the reference's ``_is_valid_action``: bounds, walls, door row, no other active agent on the
         target), bit 4 = wait, always set; 0x10 for agents that are terminated or truncated.
-        :func:`unpack_action_masks` turns the bytes into ``bool [E, N, 5]``.  Only enqueues on the handle's stream."""
+        :func:`unpack_action_masks` turns the bytes into ``bool [E, N, 5]``.  Only enqueues (no host synchronisation)."""
         out = self._new((self.num_envs, self.num_agents), torch.uint8) if out is None else self._check_masks(out)
-        self._order_after_current_stream(out)
+        cur = self._order_after_current_stream(out)
         check(self._lib.ccx_action_masks(self._h, _ptr(out)))
+        self._current_stream_waits(cur=cur)
         return out
 
     def masks_fused(self, num_steps: int = 1, order: bool = False, mixed: bool = False) -> bool:
@@ -457,23 +488,29 @@ class BatchedCollectiveCrossing(LearnerOps):
             self._reset_obs(mode, out.final_obs, out.final_compact, (out.obs, out.obs_compact))
 
     @contextlib.contextmanager
-    def _rollout_call(self, K, auto_reset, out, want_traj, want_obs, want_compact, reset_obs, check_pool=False):
+    def _rollout_call(self, K, auto_reset, out, want_traj, want_obs, want_compact, reset_obs, check_pool=False, cur=False,
+                      extra=()):
         """Head and tail of every rollout wrapper.  Before the call: the pool an auto-reset needs (``check_pool``; the other
         wrappers leave that refusal to the library), the refusal of a tracked call without a trajectory, the result
-        (allocated unless the caller's, ``None`` without a trajectory) and the reset-observation mode with that result's
-        side buffers.  Yields ``(result, byref of its CcxRolloutOut or None)``; behind the body the tracked update."""
+        (allocated unless the caller's, ``None`` without a trajectory), the reset-observation mode with that result's
+        side buffers, and the entry of the stream-order contract over the result and ``extra`` (the other outputs).
+        Yields ``(result, byref of its CcxRolloutOut or None)``; behind the body the tracked update and the exit."""
         if check_pool and auto_reset and self._pool is None:
             raise ValueError("auto_reset needs a reset pool (set_reset_pool / make_reset_pool)")
         self._track_check(out, want_traj)
         if out is None and want_traj:
             out = self.alloc_rollout(K, want_obs, want_compact)
         self._reset_obs_out(reset_obs, out)
+        if cur is not None:
+            cur = self._order_after_current_stream(*_result_tensors(out), *extra, cur=cur)
         ro = None if out is None else C.byref(_abi.CcxRolloutOut(
             _ptr(out.obs).value, _ptr(out.reward).value, _ptr(out.agent_flags).value, _ptr(out.env_flags).value,
             _ptr(out.obs_compact).value))
         yield out, ro
         if self._tracking:
             self._track(K, out)
+        if cur is not None:
+            self._current_stream_waits(cur=cur)
 
     def step_final_buffers(self, want_obs: bool = True, want_compact: bool = False):
         """The batch's own one-step side buffers ``(final_obs f32 [E, N, L], final_compact f32 [E, N, 4])`` that
@@ -556,7 +593,7 @@ class BatchedCollectiveCrossing(LearnerOps):
     def update_episode_stats(self, reward: torch.Tensor, agent_flags: torch.Tensor, env_flags: torch.Tensor) -> None:
         """Feed a trajectory the caller holds (``ccx_episode_stats_update``): ``reward`` f64 [K, E, N], ``agent_flags`` u8
         [K, E, N], ``env_flags`` u8 [K, E] (or one step without the leading axis), contiguous device tensors.  Only
-        enqueues on the handle's stream."""
+        enqueues (no host synchronisation)."""
         self._need_tracking()
         E, N = self.num_envs, self.num_agents
         for name, t, dt in (("reward", reward, torch.float64), ("agent_flags", agent_flags, torch.uint8),
@@ -568,8 +605,9 @@ class BatchedCollectiveCrossing(LearnerOps):
         if K < 1 or tuple(reward.shape) != (K, E, N) or tuple(agent_flags.shape) != (K, E, N) or tuple(env_flags.shape) != (K, E):
             raise ValueError(f"expected reward / agent_flags [K, {E}, {N}] and env_flags [K, {E}], got {tuple(reward.shape)}, "
                              f"{tuple(agent_flags.shape)}, {tuple(env_flags.shape)}")
-        self._order_after_current_stream(reward, agent_flags, env_flags)
+        cur = self._order_after_current_stream(reward, agent_flags, env_flags)
         check(self._lib.ccx_episode_stats_update(self._h, K, reward.data_ptr(), agent_flags.data_ptr(), env_flags.data_ptr()))
+        self._current_stream_waits(cur=cur)
 
     def _track(self, K: int, res) -> None:
         """The update behind a tracked call, on the buffers that call hands out."""
@@ -591,8 +629,11 @@ class BatchedCollectiveCrossing(LearnerOps):
         to zero; no record is written, ``finished`` and ``last_*`` stay (``ccx_episode_stats_reset``).  ``reset`` and
         ``reset_from_pool`` do this for the envs they restart.  Only enqueues."""
         self._need_tracking()
-        m = None if env_mask is None else self._as_dev_u8(env_mask, (self.num_envs,))
+        cur = self._other_stream()
+        m = None if env_mask is None else self._as_dev_u8(env_mask, (self.num_envs,), cur)
+        self._order_after_current_stream(cur=cur)            # (readers of the episode_stats views)
         check(self._lib.ccx_episode_stats_reset(self._h, _ptr(m)))
+        self._current_stream_waits(cur=cur)
 
     def finished_episodes(self, clear: bool = True) -> FinishedEpisodes:
         """Synchronise and return the stored records of the log (:class:`FinishedEpisodes`; needs
@@ -620,33 +661,47 @@ class BatchedCollectiveCrossing(LearnerOps):
     def clear_episode_log(self) -> None:
         """Empty the finished-episode log: stored = dropped = 0 (``ccx_episode_log_clear``).  Only enqueues."""
         self._need_tracking()
+        cur = self._order_after_current_stream()
         check(self._lib.ccx_episode_log_clear(self._h))
+        self._current_stream_waits(cur=cur)
 
     # ------------------------------------------------------------------ compute
     def observe(self, out: torch.Tensor | None = None) -> torch.Tensor:
         if out is None:
             out = self._new((self.num_envs, self.num_agents, self.obs_len), torch.float32)
+        cur = self._order_after_current_stream(out)
         check(self._lib.ccx_observe(self._h, _ptr(out)))
+        self._current_stream_waits(cur=cur)
         return out
 
     def step(self, actions, order=None, want_obs: bool = True, want_compact: bool = False,
              want_masks: bool = False) -> StepResult:
         """One env-step (``ccx_step``).  ``want_masks``: ``StepResult.action_masks`` (u8 [E, N]) holds the legal actions
         of the state BEHIND the step, written by the same launch where :meth:`masks_fused` says so."""
+        # (_other_stream, inline: the raw stream is read once per call and the answer shared, so the same-stream path --
+        # a few microseconds of Python per step -- makes no other call into torch and pays no call for asking)
+        cur = (None if torch._C._cuda_getCurrentRawStream(self.device.index) == self._stream_raw
+               else torch.cuda.current_stream(self.device))
         self._step_masks(want_masks)
         if self._array_strategies:
-            res = self._step_array(actions, order, want_obs, want_compact)
+            res = self._step_array(actions, order, want_obs, want_compact, cur=cur)
             if self._tracking:
                 self._track(1, res)
+            if cur is not None:
+                self._current_stream_waits(self._masks_buf if want_masks else None, cur=cur)
             return res if not want_masks else StepResult(res.obs, res.reward, res.agent_flags, res.env_flags, res.obs_compact,
                                                          res.term_present, self._masks_buf)
         E, N = self.num_envs, self.num_agents
-        a = self._as_dev_u8(actions, (E, N))
-        o = None if order is None else self._as_dev_u8(order, (E, N))
+        a = self._as_dev_u8(actions, (E, N), cur)
+        o = None if order is None else self._as_dev_u8(order, (E, N), cur)
         cached = self._step_out(_abi.CcxStepOut, want_obs, want_compact, want_masks)
+        if cur is not None:                  # (buffers allocated just now, and earlier readers of the static ones)
+            self._order_after_current_stream(*_result_tensors(cached[2]), cur=cur)
         check(self._lib.ccx_step(self._h, a.data_ptr(), None if o is None else o.data_ptr(), cached[1]))
         if self._tracking:
             self._track(1, cached[2])
+        if cur is not None:
+            self._current_stream_waits(cur=cur)
         return cached[2]
 
     def _step_out(self, struct, want_obs, want_compact, want_masks=False):
@@ -697,16 +752,21 @@ class BatchedCollectiveCrossing(LearnerOps):
         E, N = self.num_envs, self.num_agents
         if actions is None and mask != (1 << N) - 1:
             raise ValueError("actions may be None only when every slot is scripted")
-        a = None if actions is None else self._as_dev_u8(actions, (E, N))
-        o = None if order is None else self._as_dev_u8(order, (E, N))
+        cur = self._other_stream()
+        a = None if actions is None else self._as_dev_u8(actions, (E, N), cur)
+        o = None if order is None else self._as_dev_u8(order, (E, N), cur)
         if actions_out is not None:
             self._check_actions_out(actions_out, (E, N))
         cached = self._step_out(_abi.CcxRolloutOut, want_obs, want_compact, want_masks)
+        if cur is not None:
+            self._order_after_current_stream(*_result_tensors(cached[2]), actions_out, cur=cur)
         check(self._lib.ccx_rollout_mixed(self._h, 1, pol, mask, None if a is None else a.data_ptr(),
                                           None if o is None else o.data_ptr(), 0, cached[1],
                                           None if actions_out is None else actions_out.data_ptr()))
         if self._tracking:
             self._track(1, cached[2])
+        if cur is not None:
+            self._current_stream_waits(cur=cur)
         return cached[2]
 
     def _check_actions_out(self, t, shape) -> None:
@@ -726,6 +786,7 @@ class BatchedCollectiveCrossing(LearnerOps):
         mask, pol = self._mixed_args(scripted, policy)
         self._bind_masks(None if masks_out is None else self._check_masks(masks_out))
         E, N = self.num_envs, self.num_agents
+        cur = self._other_stream()
         if actions is None:
             if mask != (1 << N) - 1:
                 raise ValueError("actions may be None only when every slot is scripted")
@@ -736,11 +797,12 @@ class BatchedCollectiveCrossing(LearnerOps):
             K = int(actions.shape[0])
             if num_steps is not None and int(num_steps) != K:
                 raise ValueError(f"num_steps = {num_steps} but actions holds {K} steps")
-            a = self._as_dev_u8(actions, (K, E, N))
-        o = None if order is None else self._as_dev_u8(order, (K, E, N))
+            a = self._as_dev_u8(actions, (K, E, N), cur)
+        o = None if order is None else self._as_dev_u8(order, (K, E, N), cur)
         if actions_out is not None:
             self._check_actions_out(actions_out, (K, E, N))
-        with self._rollout_call(K, auto_reset, out, want_traj, want_obs, want_compact, reset_obs, check_pool=True) as (out, ro):
+        with self._rollout_call(K, auto_reset, out, want_traj, want_obs, want_compact, reset_obs, check_pool=True, cur=cur,
+                                extra=(actions_out, masks_out)) as (out, ro):
             check(self._lib.ccx_rollout_mixed(self._h, K, pol, mask, _ptr(a), _ptr(o), int(bool(auto_reset)), ro,
                                               _ptr(actions_out)))
         return out
@@ -775,12 +837,20 @@ class BatchedCollectiveCrossing(LearnerOps):
     def step_begin(self, actions, order=None) -> None:
         """First half of ``step`` (``ccx_step_begin``, collectivecrossing.py:188-212): the step counter, the ordered moves,
         deactivation on arrival.  No flag changes and nothing is written out; :meth:`strategy_view` shows the result."""
+        cur = self._other_stream()
+        self._begin(actions, order, cur)
+        if cur is not None:
+            self._current_stream_waits(cur=cur)              # (readers of the strategy_view)
+
+    def _begin(self, actions, order, cur) -> None:
         E, N = self.num_envs, self.num_agents
-        a = self._as_dev_u8(actions, (E, N))
-        o = None if order is None else self._as_dev_u8(order, (E, N))
+        a = self._as_dev_u8(actions, (E, N), cur)
+        o = None if order is None else self._as_dev_u8(order, (E, N), cur)
+        if cur is not None:
+            self._order_after_current_stream(cur=cur)        # (the state: earlier readers of the strategy_view)
         check(self._lib.ccx_step_begin(self._h, a.data_ptr(), None if o is None else o.data_ptr()))
 
-    def _user_array(self, name: str, t, dtypes, to_dtype):
+    def _user_array(self, name: str, t, dtypes, to_dtype, cur=False):
         """A caller's reward / terminated / truncated array for ``step_finish``: a device tensor [E, N] of the C type."""
         if t is None:
             return None
@@ -794,7 +864,8 @@ class BatchedCollectiveCrossing(LearnerOps):
         t = t.to(self.device).contiguous()
         if t.dtype is torch.bool:
             t = t.to(to_dtype) if to_dtype is torch.int8 else t.view(torch.uint8)
-        self._order_after_current_stream(t)
+        if cur is not None:
+            self._order_after_current_stream(t, cur=cur)
         return t
 
     def step_finish(self, reward=None, terminated=None, truncated=None, want_obs: bool = True, want_compact: bool = False,
@@ -811,19 +882,23 @@ class BatchedCollectiveCrossing(LearnerOps):
         that kind (:meth:`run_array_strategies`), never by the stand-in mode the handle was built with: ``step_begin`` +
         ``step_finish()`` is ``step`` there too."""
         self._bind_masks(None)
-        r = self._user_array("reward", reward, (torch.float64,), None)
-        t = self._user_array("terminated", terminated, (torch.bool, torch.int8), torch.int8)
-        u = self._user_array("truncated", truncated, (torch.bool, torch.uint8), torch.uint8)
+        cur = self._other_stream()
+        r = self._user_array("reward", reward, (torch.float64,), None, cur)
+        t = self._user_array("terminated", terminated, (torch.bool, torch.int8), torch.int8, cur)
+        u = self._user_array("truncated", truncated, (torch.bool, torch.uint8), torch.uint8, cur)
         if self._array_strategies:
             kinds = [k for k, v in (("reward", r), ("termination", t), ("truncation", u)) if v is None]
-            own = self.run_array_strategies(kinds)
+            own = self._run_array(kinds, cur)
             r, t, u = (v if v is not None else o for v, o in zip((r, t, u), own))
-        res = self._finish(r, t, u, want_obs, want_compact, auto_reset, reset_obs, want_final)
+        res = self._finish(r, t, u, want_obs, want_compact, auto_reset, reset_obs, want_final, cur)
         if self._tracking:
             self._track(1, res)
+        if cur is not None:
+            self._current_stream_waits(cur=cur)
         return res
 
-    def _finish(self, r, t, u, want_obs, want_compact, auto_reset, reset_obs: str = "terminal", want_final: bool = False) -> StepResult:
+    def _finish(self, r, t, u, want_obs, want_compact, auto_reset, reset_obs: str = "terminal", want_final: bool = False,
+                cur=False) -> StepResult:
         E, N = self.num_envs, self.num_agents
         want_final = bool(want_final) and reset_obs == "next"
         key = (bool(want_obs), bool(want_compact), want_final)
@@ -843,6 +918,8 @@ class BatchedCollectiveCrossing(LearnerOps):
             self._finish_cache[key] = cached
         res = cached[2]
         self._reset_obs(reset_obs, res.final_obs, res.final_compact, (res.obs, res.obs_compact))
+        if cur is not None:                  # (buffers allocated or zeroed just now, and earlier readers of the static ones)
+            self._order_after_current_stream(*_result_tensors(res), cur=cur)
         check(self._lib.ccx_step_finish(self._h, _ptr(r), _ptr(t), _ptr(u), cached[1], _ptr(self._term_present),
                                         int(bool(auto_reset))))
         return cached[2]
@@ -850,22 +927,34 @@ class BatchedCollectiveCrossing(LearnerOps):
     def run_array_strategies(self, kinds=("reward", "termination", "truncation")):
         """The config's array-form classes on the state ``begin`` left: ``(reward, terminated, truncated)`` device tensors
         in the C types of ``ccx_step_finish``, ``None`` where the strategy is built-in (or its kind is not in ``kinds``).
-        Runs on the handle's stream."""
+        Runs on the handle's stream, inside the stream-order contract: the results come from that stream's pool and are
+        recorded for torch's current stream when it is another one."""
+        return self._run_array(kinds, self._other_stream())
+
+    def _run_array(self, kinds, cur):
         from .strategies import ARRAY_METHODS, check_batch_result
         view = self.strategy_view()
         out = []
-        other = torch._C._cuda_getCurrentRawStream(self.device.index) != self._stream_raw
-        ctx = torch.cuda.stream(self._stream) if other else contextlib.nullcontext()
+        if cur is not None:
+            self._order_after_current_stream(cur=cur)
+        ctx = torch.cuda.stream(self._stream) if cur is not None else contextlib.nullcontext()
         with ctx:
             for kind in ("reward", "termination", "truncation"):
                 fn = self._array_strategies.get(kind) if kind in kinds else None
                 out.append(None if fn is None else check_batch_result(kind, fn, getattr(fn, ARRAY_METHODS[kind])(view), view))
+        if cur is not None:
+            self._current_stream_waits(cur=cur)
+            for t in out:
+                if t is not None:
+                    t.record_stream(cur)
         return out
 
-    def _step_array(self, actions, order, want_obs, want_compact, auto_reset: bool = False) -> StepResult:
-        self.step_begin(actions, order)
-        r, t, u = self.run_array_strategies()
-        return self._finish(r, t, u, want_obs, want_compact, auto_reset)
+    def _step_array(self, actions, order, want_obs, want_compact, auto_reset: bool = False, cur=False) -> StepResult:
+        if cur is False:
+            cur = self._other_stream()
+        self._begin(actions, order, cur)
+        r, t, u = self._run_array(("reward", "termination", "truncation"), cur)
+        return self._finish(r, t, u, want_obs, want_compact, auto_reset, cur=cur)
 
     def _finish_into(self, r, t, u, out: "RolloutResult | None", s: int, auto_reset: bool, reset_obs: str = "terminal") -> None:
         fields = ("obs", "reward", "agent_flags", "env_flags", "obs_compact", "term_present")
@@ -879,26 +968,31 @@ class BatchedCollectiveCrossing(LearnerOps):
         check(self._lib.ccx_step_finish(self._h, _ptr(r), _ptr(t), _ptr(u), C.byref(so), ptrs[5], int(bool(auto_reset))))
 
     def _rollout_array(self, K, actions, order, policy, auto_reset, out, want_traj, want_obs, want_compact, actions_out,
-                       reset_obs: str = "terminal"):
+                       reset_obs: str = "terminal", cur=False):
         """``rollout`` / ``rollout_policy`` of a batch with array-form strategies: the split step once per tick (three
         launches plus the user's tensor code per step: launch-bound, not the fused kernel's speed).  A result allocated
         here carries ``term_present``; a caller's own ``out`` gets it only if its ``term_present`` is set; without a
         trajectory (``want_traj=False``) nothing is written out."""
         E, N = self.num_envs, self.num_agents
         own = out is None and want_traj
-        with self._rollout_call(K, auto_reset, out, want_traj, want_obs, want_compact, reset_obs, check_pool=True) as (out, _):
+        if cur is False:
+            cur = self._other_stream()
+        with self._rollout_call(K, auto_reset, out, want_traj, want_obs, want_compact, reset_obs, check_pool=True, cur=cur,
+                                extra=(actions_out,)) as (out, _):
             if own:
                 out.term_present = self._new((K, E, N), torch.uint8)
+                if cur is not None:
+                    out.term_present.record_stream(self._stream)
             row_align = 16 if N % 2 == 0 else 8       # (odd agent counts write the rows in 8-byte units)
             if out is not None and out.obs is not None and K > 1 and (E * N * self.obs_len * 4) % row_align:
                 raise ValueError(f"{E} envs x {N} agents: a step's observation rows are not a multiple of {row_align} bytes")
             for s in range(K):
                 if policy is None:
-                    self.step_begin(actions[s], None if order is None else order[s])
+                    self._begin(actions[s], None if order is None else order[s], cur)
                 else:
                     a = self.policy_actions(policy, out=None if actions_out is None else actions_out[s])
-                    self.step_begin(a)
-                r, t, u = self.run_array_strategies()
+                    self._begin(a, None, cur)
+                r, t, u = self._run_array(("reward", "termination", "truncation"), cur)
                 self._finish_into(r, t, u, out, s, auto_reset, reset_obs)
         return out
 
@@ -939,8 +1033,9 @@ class BatchedCollectiveCrossing(LearnerOps):
         rows = int(c.numel() // (self.num_agents * 4))
         if out is None:
             out = self._new((*c.shape[:-1], self.obs_len), torch.float32)
-        self._order_after_current_stream(c, out)
+        cur = self._order_after_current_stream(c, out)
         check(self._lib.ccx_expand_observations(self._h, _ptr(c), rows, _ptr(out)))
+        self._current_stream_waits(cur=cur)
         return out
 
     # ------------------------------------------------------------------ rendering
@@ -967,7 +1062,7 @@ class BatchedCollectiveCrossing(LearnerOps):
         """rgb_array frames of the current state (``ccx_render``): ``torch.uint8 [R, H*cell_px, W*cell_px, 3]`` on the
         device, R = E (``env_ids=None``) or ``len(env_ids)``.  The picture of the reference's rendering.py without text,
         ticks, title and legend (the frame spec is in include/ccx.h, CCX_RENDER); an id outside [0, E) gives a frame of
-        the static layers only.  Only enqueues work on the handle's stream, so it captures into a graph after ``step``."""
+        the static layers only.  Only enqueues (no host synchronisation), so it captures into a graph after ``step``."""
         cp = _check_cell_px(cell_px)
         ids = None
         if env_ids is not None:
@@ -990,8 +1085,9 @@ class BatchedCollectiveCrossing(LearnerOps):
         rows = self.num_envs if ids is None else int(ids.shape[0])
         frames = self._frames_out((rows,), cp, out)
         if rows:
-            self._order_after_current_stream(ids, frames)
+            cur = self._order_after_current_stream(ids, frames)
             check(self._lib.ccx_render(self._h, _ptr(ids), rows, cp, _ptr(frames)))
+            self._current_stream_waits(cur=cur)
         return frames
 
     def render_compact(self, obs_compact: torch.Tensor, cell_px: int = 8, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -1007,8 +1103,9 @@ class BatchedCollectiveCrossing(LearnerOps):
         rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
         frames = self._frames_out(lead, cp, out)
         if rows:
-            self._order_after_current_stream(c, frames)
+            cur = self._order_after_current_stream(c, frames)
             check(self._lib.ccx_render_compact(self._h, _ptr(c), rows, cp, _ptr(frames)))
+            self._current_stream_waits(cur=cur)
         return frames
 
     def rollout(self, actions, order=None, auto_reset: bool = False,
@@ -1026,12 +1123,14 @@ class BatchedCollectiveCrossing(LearnerOps):
         step) into the same preallocated result, with ``term_present`` filled."""
         K = int(actions.shape[0])
         E, N = self.num_envs, self.num_agents
-        a = self._as_dev_u8(actions, (K, E, N))
-        o = None if order is None else self._as_dev_u8(order, (K, E, N))
+        cur = self._other_stream()
+        a = self._as_dev_u8(actions, (K, E, N), cur)
+        o = None if order is None else self._as_dev_u8(order, (K, E, N), cur)
         self._bind_masks(None if masks_out is None else self._check_masks(masks_out))
         if self._array_strategies:
-            return self._rollout_array(K, a, o, None, auto_reset, out, want_traj, want_obs, want_compact, None, reset_obs)
-        with self._rollout_call(K, auto_reset, out, want_traj, want_obs, want_compact, reset_obs) as (out, ro):
+            return self._rollout_array(K, a, o, None, auto_reset, out, want_traj, want_obs, want_compact, None, reset_obs, cur)
+        with self._rollout_call(K, auto_reset, out, want_traj, want_obs, want_compact, reset_obs, cur=cur,
+                                extra=(masks_out,)) as (out, ro):
             check(self._lib.ccx_rollout(self._h, K, _ptr(a), _ptr(o), int(bool(auto_reset)), ro))    # (no trajectory: NULL)
             self._rollouts_with_obs += int(out is not None and out.obs is not None and K >= 64)
         return out
@@ -1047,10 +1146,12 @@ class BatchedCollectiveCrossing(LearnerOps):
         self._bind_masks(None if masks_out is None else self._check_masks(masks_out))
         if actions_out is None and want_actions:
             actions_out = self._new((K, E, N), torch.uint8)
+        cur = self._other_stream()
         if self._array_strategies:
             return self._rollout_array(K, None, None, policy, auto_reset, out, True, want_obs, False, actions_out,
-                                       reset_obs), actions_out
-        with self._rollout_call(K, auto_reset, out, True, want_obs, False, reset_obs) as (out, ro):
+                                       reset_obs, cur), actions_out
+        with self._rollout_call(K, auto_reset, out, True, want_obs, False, reset_obs, cur=cur,
+                                extra=(actions_out, masks_out)) as (out, ro):
             check(self._lib.ccx_rollout_policy(self._h, K, _abi.POLICIES[policy], int(bool(auto_reset)), ro, _ptr(actions_out)))
             self._rollouts_with_obs += int(out.obs is not None and K >= 64)
         return out, actions_out
@@ -1094,7 +1195,9 @@ class BatchedCollectiveCrossing(LearnerOps):
 
     # ------------------------------------------------------------------ counters / timing / shape
     def zero_counters(self) -> None:
+        cur = self._order_after_current_stream()             # (readers of counters_tensor)
         check(self._lib.ccx_zero_counters(self._h))
+        self._current_stream_waits(cur=cur)
 
     def counters(self) -> dict[str, int]:
         c = _abi.CcxCounters()

@@ -139,7 +139,24 @@ class LearnerOps:
     """The learner-side methods of a batch.  The host class provides ``_lib`` (the loaded library), ``_h`` (the handle),
     ``device``, ``num_envs``, ``num_agents``, ``obs_len``, ``_new(shape, dtype)`` (an uninitialised device tensor),
     ``_order_after_current_stream(*tensors)`` (the handle's stream waits for torch's current one), and ``_stream`` /
-    ``_stream_raw`` (the handle's stream as torch's object and as the raw pointer)."""
+    ``_stream_raw`` (the handle's stream as torch's object and as the raw pointer).
+
+    **Stream order** (the contract of every method here, of :class:`BatchedCollectiveCrossing`,
+    :class:`MlpHead` and :class:`DeviceAdam` that enqueues device work).  The launches go to the handle's stream: the one
+    current at construction, or ``use_stream``'s.  The caller's tensors live on torch's CURRENT stream.  (a) Everything
+    enqueued on the current stream before the call -- the producers of the inputs, and earlier readers or writers of the
+    outputs -- happens before the method's launches.  (b) The launches happen before anything enqueued on the current
+    stream after the method returns.  (c) When the two streams differ, every tensor handed in or out is recorded
+    (``record_stream``) for the handle's stream.  When the current stream IS the handle's stream none of this costs a wait
+    or an event, and nothing enters a captured graph.  Methods that synchronise with the host are outside the contract."""
+
+    def _other_stream(self):
+        """torch's current stream of the device when it is NOT the handle's stream, else ``None``: one read of the raw
+        stream (an int; ~0.2 us), so the same-stream path makes no other call into torch.  A method reads it once and
+        hands it to both helpers as ``cur=``."""
+        if torch._C._cuda_getCurrentRawStream(self.device.index) == self._stream_raw:
+            return None
+        return torch.cuda.current_stream(self.device)
 
     # ------------------------------------------------------------------ advantages
     def alloc_gae(self, num_steps: int, want_valid: bool = True) -> GaeResult:
@@ -159,7 +176,8 @@ class LearnerOps:
         step ENDED ON -- read only where an episode is cut without termination (truncation, ``EF_RESET``); evaluate the
         critic on ``final_obs`` there (``reset_obs="next"``).  Without it a cut bootstraps from 0.  Termination never
         bootstraps.  ``out`` reuses a :class:`GaeResult` (``out.valid`` may be ``None``).  All tensors: contiguous, on the
-        batch's device; anything else raises ``ValueError`` before the library is called.  Only enqueues."""
+        batch's device; anything else raises ``ValueError`` before the library is called.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         from .batched import RolloutResult                           # (batched imports this module)
         if isinstance(traj, RolloutResult):
             reward, agent_flags, env_flags = traj.reward, traj.agent_flags, traj.env_flags
@@ -187,10 +205,11 @@ class LearnerOps:
                      ("final_values", final_values, torch.float32, KEN, _OPT),
                      ("out.advantages", out.advantages, torch.float32, KEN),
                      ("out.returns", out.returns, torch.float32, KEN), ("out.valid", out.valid, torch.uint8, KEN, _OPT))
-        self._order_after_current_stream(reward, agent_flags, env_flags, values, last_values, final_values,
-                                         out.advantages, out.returns, out.valid)
+        cur = self._order_after_current_stream(reward, agent_flags, env_flags, values, last_values, final_values,
+                                               out.advantages, out.returns, out.valid)
         check(self._lib.ccx_gae(self._h, K, _ptr(reward), _ptr(agent_flags), _ptr(env_flags), _ptr(values), _ptr(last_values),
                                 _ptr(final_values), gamma, lam, _ptr(out.advantages), _ptr(out.returns), _ptr(out.valid)))
+        self._current_stream_waits(cur=cur)
         return out
 
     # ------------------------------------------------------------------ sampling from a learned policy
@@ -214,7 +233,8 @@ class LearnerOps:
         ``logp`` / ``entropy`` may be ``None``; ``want_*`` is then ignored): ``out.actions`` may be a ``[E, N]`` view of the
         ``[1, E, N]`` tensor :meth:`rollout` reads.  All tensors: contiguous, on the batch's device; anything else raises
         ``ValueError`` before the library is called.  Not here: bf16 / f16 logits (cast first), a temperature (scale the
-        logits first).  Only enqueues."""
+        logits first).
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         E, N = self.num_envs, self.num_agents
         _require_out(out, SampleResult, "alloc_sample")
         if out is None:
@@ -223,9 +243,10 @@ class LearnerOps:
                      ("logits", logits, torch.float32, (E, N, 5), {"align": 16}), ("masks", masks, torch.uint8, (E, N), _OPT),
                      ("out.actions", out.actions, torch.uint8, (E, N)), ("out.logp", out.logp, torch.float32, (E, N), _OPT),
                      ("out.entropy", out.entropy, torch.float32, (E, N), _OPT))
-        self._order_after_current_stream(logits, masks, out.actions, out.logp, out.entropy)
+        cur = self._order_after_current_stream(logits, masks, out.actions, out.logp, out.entropy)
         check(self._lib.ccx_sample_actions(self._h, _ptr(logits), _ptr(masks), int(bool(deterministic)), _ptr(out.actions),
                                            _ptr(out.logp), _ptr(out.entropy)))
+        self._current_stream_waits(cur=cur)
         return out
 
     # ------------------------------------------------------------------ the policy head: observation rows to logits
@@ -237,9 +258,10 @@ class LearnerOps:
         return MlpHead(self, H, O, activation, L, backward)
 
     def _mlp_forward(self, head: "MlpHead", x: torch.Tensor, y: torch.Tensor, hidden: torch.Tensor | None) -> None:
-        self._order_after_current_stream(x, head.w1t, head.b1, head.w2, head.b2, y, hidden)
+        cur = self._order_after_current_stream(x, head.w1t, head.b1, head.w2, head.b2, y, hidden)
         check(self._lib.ccx_mlp_forward(self._h, x.numel() // head.L, head.L, head.H, head.O, head.activation_id, _ptr(x),
                                         _ptr(head.w1t), _ptr(head.b1), _ptr(head.w2), _ptr(head.b2), _ptr(y), _ptr(hidden)))
+        self._current_stream_waits(cur=cur)
 
     def _mlp_backward_workspace(self, dims, rows: int, workspace: torch.Tensor | None) -> torch.Tensor:
         """The workspace of a backward over ``rows`` rows: the caller's, checked, or one from torch's allocator (so a call
@@ -288,11 +310,11 @@ class LearnerOps:
             return out
         workspace = self._mlp_backward_workspace(dims, rows, out.workspace)
         x, hidden, grad_y, w2 = x.detach(), hidden.detach(), grad_y.detach(), w2.detach()
-        self._order_after_current_stream(x, hidden, grad_y, w2, workspace, out.w1t, out.b1, out.w2, out.b2, out.grad_a)
+        cur = self._order_after_current_stream(x, hidden, grad_y, w2, workspace, out.w1t, out.b1, out.w2, out.b2, out.grad_a)
         check(self._lib.ccx_mlp_backward(self._h, rows, L, H, O, act, _ptr(x), _ptr(hidden), _ptr(grad_y), _ptr(w2),
                                          _ptr(workspace), _ptr(out.w1t), _ptr(out.b1), _ptr(out.w2), _ptr(out.b2),
                                          _ptr(out.grad_a)))
-        self._current_stream_waits()
+        self._current_stream_waits(cur=cur)
         return out
 
     def mlp_backward(self, head: "MlpHead", x: torch.Tensor, hidden: torch.Tensor, grad_y: torch.Tensor,
@@ -308,7 +330,8 @@ class LearnerOps:
         form).  ``out`` reuses a result of :meth:`alloc_mlp_backward` (its ``grad_a`` decides, ``want_grad_a`` is then
         ignored); otherwise the workspace comes from torch's allocator, so the call captures.  A wrong dtype, shape or
         device, a non-contiguous tensor, a misaligned pointer or a workspace that is too small raises ``ValueError`` before
-        the library is called; zero rows return zeros without calling it.  Only enqueues."""
+        the library is called; zero rows return zeros without calling it.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         self._check_head(head)
         _require_out(out, MlpGradResult, "alloc_mlp_backward")
         if out is None:
@@ -328,7 +351,8 @@ class LearnerOps:
         16-byte aligned: the ``obs`` of :meth:`step` / :meth:`rollout`); ``logits_out`` f32 [E, N, 5] receives the logits of
         every slot, dead ones included.  ``masks``, ``deterministic``, ``want_*`` and ``out`` are :meth:`sample_actions`'.
         No gradient flows through this call (the update re-evaluates stored rows with ``head(rows)``).  Anything else than
-        the tensors described raises ``ValueError`` before the library is called.  Only enqueues."""
+        the tensors described raises ``ValueError`` before the library is called.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         E, N = self.num_envs, self.num_agents
         if not isinstance(head, MlpHead) or head.batch is not self:
             raise ValueError("head must be an MlpHead of this batch (mlp_head)")
@@ -343,11 +367,12 @@ class LearnerOps:
                      ("logits_out", logits_out, torch.float32, (E, N, 5), _OPT),
                      ("out.actions", out.actions, torch.uint8, (E, N)), ("out.logp", out.logp, torch.float32, (E, N), _OPT),
                      ("out.entropy", out.entropy, torch.float32, (E, N), _OPT))
-        self._order_after_current_stream(obs, head.w1t, head.b1, head.w2, head.b2, masks, logits_out, out.actions, out.logp,
-                                         out.entropy)
+        cur = self._order_after_current_stream(obs, head.w1t, head.b1, head.w2, head.b2, masks, logits_out, out.actions,
+                                               out.logp, out.entropy)
         check(self._lib.ccx_mlp_sample_actions(self._h, head.H, head.activation_id, _ptr(obs), _ptr(head.w1t), _ptr(head.b1),
                                                _ptr(head.w2), _ptr(head.b2), _ptr(masks), int(bool(deterministic)),
                                                _ptr(out.actions), _ptr(out.logp), _ptr(out.entropy), _ptr(logits_out)))
+        self._current_stream_waits(cur=cur)
         return out
 
     # ------------------------------------------------------------------ stored actions under new logits
@@ -367,15 +392,23 @@ class LearnerOps:
         return lead
 
     def _evaluate_forward(self, logits, actions, masks, out: EvalResult) -> None:
-        self._order_after_current_stream(logits, actions, masks, out.logp, out.entropy)
+        cur = self._order_after_current_stream(logits, actions, masks, out.logp, out.entropy)
         check(self._lib.ccx_evaluate_actions(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks), _ptr(out.logp),
                                              _ptr(out.entropy)))
+        self._current_stream_waits(cur=cur)
 
-    def _current_stream_waits(self) -> None:
-        """Results of a launch on the handle's stream that torch ops consume at once on torch's CURRENT stream: when that
-        is another stream, it waits for the handle's stream."""
-        if torch._C._cuda_getCurrentRawStream(self.device.index) != self._stream_raw:
-            torch.cuda.current_stream(self.device).wait_stream(self._stream)
+    def _current_stream_waits(self, *tensors, cur=False) -> None:
+        """The exit of every enqueueing method (rules (b) and (c) of the class docstring): when torch's CURRENT stream is
+        not the handle's, it waits for the handle's stream, so whatever consumes the results there runs behind the
+        launches, and ``tensors`` (outputs not yet handed to :meth:`_order_after_current_stream`) are recorded for the
+        handle's stream.  ``cur``: what :meth:`_other_stream` answered earlier in the same call (default: ask now)."""
+        if cur is False:
+            cur = self._other_stream()
+        if cur is not None:
+            cur.wait_stream(self._stream)
+            for t in tensors:
+                if t is not None and t.is_cuda:
+                    t.record_stream(self._stream)
 
     def evaluate_actions(self, logits: torch.Tensor, actions: torch.Tensor, masks: torch.Tensor | None = None,
                          want_entropy: bool = True, out: EvalResult | None = None) -> EvalResult:
@@ -420,7 +453,8 @@ class LearnerOps:
         (``ccx_evaluate_actions_backward``): one kernel that recomputes the forward quantities from the logits.  Either of
         ``grad_logp`` / ``grad_entropy`` (f32, the leading shape of ``logits``) may be ``None``, not both.  ``out`` reuses a
         f32 tensor of the shape of ``logits`` (16-byte aligned): with :meth:`evaluate_actions` ``(out=)`` the static-buffer
-        pair for a captured graph.  Only enqueues."""
+        pair for a captured graph.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         if grad_logp is None and grad_entropy is None:
             raise ValueError("at least one of grad_logp and grad_entropy is required")
         if out is None and isinstance(logits, torch.Tensor):
@@ -430,9 +464,10 @@ class LearnerOps:
             ("grad_logp", grad_logp, torch.float32, lead, _OPT), ("grad_entropy", grad_entropy, torch.float32, lead, _OPT),
             ("out", out, torch.float32, lead + (5,), {"align": 16})))
         if logits.numel():
-            self._order_after_current_stream(logits, actions, masks, grad_logp, grad_entropy, out)
+            cur = self._order_after_current_stream(logits, actions, masks, grad_logp, grad_entropy, out)
             check(self._lib.ccx_evaluate_actions_backward(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks),
                                                           _ptr(grad_logp), _ptr(grad_entropy), _ptr(out)))
+            self._current_stream_waits(cur=cur)
         return out
 
     # ------------------------------------------------------------------ the PPO loss over the rows that count
@@ -481,7 +516,8 @@ class LearnerOps:
         zero (``None``: all), by ``ccx_masked_moments`` (include/ccx.h CCX_PPO_LOSS): two kernels on the handle's stream, a
         fixed f64 tree, bit-defined, no host synchronisation.  ``std`` is the unbiased one; ``n < 2`` gives mean 0, std 1.
         Hand the result to :meth:`ppo_loss` as ``norm=``.  ``out`` / ``workspace`` reuse buffers (a captured graph).  Zero
-        elements return ``[0, 0, 1, 0]`` without calling the library.  Only enqueues."""
+        elements return ``[0, 0, 1, 0]`` without calling the library.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         _require("x", x, torch.float32, None, self.device)
         _require("valid", valid, torch.uint8, x.shape, self.device, optional=True)
         if out is None:
@@ -492,9 +528,9 @@ class LearnerOps:
             out.copy_(torch.tensor([0.0, 0.0, 1.0, 0.0], dtype=torch.float32))
             return out
         workspace = self._ppo_workspace_arg(workspace, rows)
-        self._order_after_current_stream(x, valid, out, workspace)
+        cur = self._order_after_current_stream(x, valid, out, workspace)
         check(self._lib.ccx_masked_moments(self._h, rows, _ptr(x), _ptr(valid), _ptr(workspace), _ptr(out)))
-        self._current_stream_waits()
+        self._current_stream_waits(cur=cur)
         return out
 
     def _ppo_workspace_arg(self, workspace, rows: int) -> torch.Tensor:
@@ -509,11 +545,12 @@ class LearnerOps:
         return workspace
 
     def _ppo_forward(self, logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper, workspace, stats):
-        self._order_after_current_stream(logits, values, actions, logp_old, advantages, returns, masks, valid, norm, workspace, stats)
+        cur = self._order_after_current_stream(logits, values, actions, logp_old, advantages, returns, masks, valid, norm,
+                                               workspace, stats)
         check(self._lib.ccx_ppo_loss(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks), _ptr(logp_old),
                                      _ptr(advantages), _ptr(returns), _ptr(values), _ptr(valid), _ptr(norm), *hyper,
                                      _ptr(workspace), _ptr(stats)))
-        self._current_stream_waits()
+        self._current_stream_waits(cur=cur)
 
     def ppo_loss(self, logits: torch.Tensor, values: torch.Tensor, actions: torch.Tensor, logp_old: torch.Tensor,
                  advantages: torch.Tensor, returns: torch.Tensor, masks: torch.Tensor | None = None,
@@ -536,7 +573,8 @@ class LearnerOps:
         +0.0), ``None`` goes to the one that does not require grad, ``out=`` is refused, and the workspace comes from
         torch's allocator, so the call captures.  Otherwise ``out=`` reuses a result of :meth:`alloc_ppo_loss`.  A wrong
         dtype, shape or device, a non-contiguous tensor, a misaligned pointer or a bad hyperparameter raises ``ValueError``
-        before the library is called; zero rows return zeros without calling it.  Only enqueues."""
+        before the library is called; zero rows return zeros without calling it.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         hyper = self._check_ppo_hyper(clip, vf_coef, ent_coef, adv_eps)
         lead, norm = self._check_ppo(logits, values, actions, logp_old, advantages, returns, masks, valid, norm)
         needs = [t.requires_grad for t in (logits, values)]
@@ -594,12 +632,12 @@ class LearnerOps:
                      ("grad_values", gv, torch.float32, lead, _OPT))
         if logits.numel():
             logits, values = logits.detach(), values.detach()
-            self._order_after_current_stream(logits, values, actions, logp_old, advantages, returns, masks, valid, norm, stats,
-                                             grad_loss, gl, gv)
+            cur = self._order_after_current_stream(logits, values, actions, logp_old, advantages, returns, masks, valid, norm,
+                                                   stats, grad_loss, gl, gv)
             check(self._lib.ccx_ppo_loss_backward(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks),
                                                   _ptr(logp_old), _ptr(advantages), _ptr(returns), _ptr(values), _ptr(valid),
                                                   _ptr(norm), *hyper, _ptr(stats), _ptr(grad_loss), _ptr(gl), _ptr(gv)))
-            self._current_stream_waits()
+            self._current_stream_waits(cur=cur)
         return gl, gv
 
     # ------------------------------------------------------------------ the optimiser step
@@ -617,10 +655,10 @@ class LearnerOps:
         table =(CcxAdamTensor * len(params))()
         for row, p, g, m, v in zip(table, params, grads, ms, vs):
             row.param, row.grad, row.m, row.v, row.numel = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-        self._order_after_current_stream(*params, *grads, *ms, *vs, lr_dev, state, workspace, stats)
+        cur = self._order_after_current_stream(*params, *grads, *ms, *vs, lr_dev, state, workspace, stats)
         check(self._lib.ccx_adam_step(self._h, len(params), table, lr, _ptr(lr_dev), *hyper, _ptr(state), _ptr(workspace),
                                       _ptr(stats)))
-        self._current_stream_waits()
+        self._current_stream_waits(cur=cur)
 
 
 def _check_adam_hyper(lr, betas, eps, weight_decay, max_grad_norm):
@@ -660,7 +698,8 @@ class DeviceAdam:
     the parameters (e.g. the ``w1t, b1, w2, b2`` of an :class:`MlpGradResult` per head: static buffers for a graph).  The
     gradients are read only; the clipped gradient is never stored.  A wrong dtype, shape or device, a non-contiguous or
     misaligned tensor, a missing ``.grad``, more than 32 tensors or a hyper-parameter out of range raises ``ValueError``
-    before the library is called.  Only enqueues."""
+    before the library is called.
+    Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
 
     def __init__(self, batch, params, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0):
         self._lr, self._hyper = _check_adam_hyper(lr, betas, eps, weight_decay, max_grad_norm)
@@ -700,9 +739,10 @@ class DeviceAdam:
     def lr(self, value) -> None:
         self._lr, _ = _check_adam_hyper(value, *self._hyper_args())
         b = self.batch
-        b._order_after_current_stream(self._lr_dev)
+        cur = b._order_after_current_stream(self._lr_dev)
         with torch.cuda.stream(b._stream):
             self._lr_dev.fill_(self._lr)
+        b._current_stream_waits(cur=cur)
 
     def _hyper_args(self):
         beta1, beta2, eps, weight_decay, max_grad_norm = self._hyper
@@ -768,6 +808,7 @@ class DeviceAdam:
                     raise ValueError(f"state_dict {name}[{i}] must be a torch.float32 tensor of shape {tuple(d.shape)}")
         if not isinstance(state, torch.Tensor) or state.dtype is not torch.uint8 or tuple(state.shape) != (64,):
             raise ValueError("state_dict state must be a torch.uint8 tensor of 64 bytes")
+        self.batch._current_stream_waits()                           # (a step in flight still reads m, v and the state)
         with torch.no_grad():
             for src, dst in ((ms, self.m), (vs, self.v)):
                 for s, d in zip(src, dst):
@@ -787,7 +828,6 @@ class _EvaluateActions(torch.autograd.Function):
         logits = logits.detach()
         out = batch.alloc_evaluate(logits.shape[:-1], want_entropy)
         batch._evaluate_forward(logits, actions, masks, out)
-        batch._current_stream_waits()
         ctx.batch, ctx.actions, ctx.masks = batch, actions, masks
         ctx.save_for_backward(logits)
         ctx.set_materialize_grads(False)                # an output the loss did not use arrives as None and is passed as NULL
@@ -802,7 +842,6 @@ class _EvaluateActions(torch.autograd.Function):
         if grad_logp is None and grad_entropy is None:
             return None, None, None, None, None
         grad = ctx.batch.evaluate_actions_backward(logits, ctx.actions, ctx.masks, grad_logp, grad_entropy)
-        ctx.batch._current_stream_waits()
         return None, grad, None, None, None
 
 
@@ -953,7 +992,6 @@ class _MlpForward(torch.autograd.Function):
         y = b._new(tuple(x.shape[:-1]) + (head.O,), torch.float32)
         hidden = b._new(tuple(x.shape[:-1]) + (head.H,), torch.float32)
         b._mlp_forward(head, x, y, hidden)
-        b._current_stream_waits()
         ctx.relu = head.activation == "relu"
         ctx.batch, ctx.dims, ctx.device_backward = b, head.dims, head.backward == "device"
         ctx.save_for_backward(x, w1t.detach(), w2.detach(), hidden)

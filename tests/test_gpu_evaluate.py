@@ -253,25 +253,37 @@ def test_autograd_matches_the_backward_spec_and_torchs_composition(batch, refere
 
 # ------------------------------------------------------------------------------------------------- 4. streams and capture
 def test_another_current_stream(batch, reference):
+    """torch's current stream is not the handle's stream, and a blocker (tests/_stream_order.py) keeps one of the two
+    busy: first the current one, so the launches must wait for inputs produced behind it; then the handle's, so the torch
+    ops that consume the results at once must wait for the launches."""
     import torch
+    from _stream_order import Blocker
 
     case, want = reference
     M = 129
     logits, actions, masks, glp, gent = _device_inputs(case, True, M)
-    torch.cuda.synchronize()
-    other = torch.cuda.Stream()
-    with torch.cuda.stream(other):                                       # torch's current stream is not the handle's stream
-        x = (logits * 1.0).requires_grad_(True)                          # produced on `other`
-        r = batch.evaluate_actions(x, actions, masks)
-        ok = torch.isfinite(glp) & torch.isfinite(gent)
-        c1, c2 = torch.where(ok, glp, 0.5), torch.where(ok, gent, -0.25)
-        g, = torch.autograd.grad((c1 * r.logp + c2 * r.entropy).sum(), x)
-        got = [t.detach().cpu().numpy() for t in (r.logp, r.entropy, g)]
-        c1_np, c2_np = c1.cpu().numpy(), c2.cpu().numpy()
-    np.testing.assert_array_equal(bits32(got[0]), bits32(want[True][0][:M]))
-    np.testing.assert_array_equal(bits32(got[1]), bits32(want[True][1][:M]))
     lg, ac, mk, _, _ = (a[:M] for a in case_args(case, True))
-    np.testing.assert_array_equal(bits32(got[2]), bits32(evaluate_backward_spec(lg, ac, mk, c1_np, c2_np)))
+    blocker = Blocker()
+    handle = batch._stream                                               # (where the batch launches)
+    other = torch.cuda.Stream()
+    blocker.warm(other, handle)
+    for busy in (None, other, handle):                                   # (None: once without a blocker, the one-off host work)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(other):                                   # torch's current stream is not the handle's stream
+            ev = None if busy is None else blocker.run(busy)
+            x = (logits * 1.0).requires_grad_(True)                      # produced on `other`
+            r = batch.evaluate_actions(x, actions, masks)
+            ok = torch.isfinite(glp) & torch.isfinite(gent)
+            c1, c2 = torch.where(ok, glp, 0.5), torch.where(ok, gent, -0.25)
+            g, = torch.autograd.grad((c1 * r.logp + c2 * r.entropy).sum(), x)
+            early = [t.detach().clone() for t in (r.logp, r.entropy, g)]  # consumers enqueued at once, on `other`
+            still_running = ev is None or not ev.query()
+            got = [t.cpu().numpy() for t in early]
+            c1_np, c2_np = c1.cpu().numpy(), c2.cpu().numpy()
+        assert still_running, "blocker too short: it had ended before the consumers were enqueued"
+        np.testing.assert_array_equal(bits32(got[0]), bits32(want[True][0][:M]))
+        np.testing.assert_array_equal(bits32(got[1]), bits32(want[True][1][:M]))
+        np.testing.assert_array_equal(bits32(got[2]), bits32(evaluate_backward_spec(lg, ac, mk, c1_np, c2_np)))
 
 
 def test_captured_autograd_and_static_buffers(batch, reference):

@@ -286,26 +286,39 @@ def test_autograd_equals_the_backward_entry_point_and_torchs_composition(batch, 
 
 # ------------------------------------------------------------------------------------------------- 4. streams and capture
 def test_another_current_stream(batch, case):
+    """torch's current stream is not the handle's stream, and a blocker (tests/_stream_order.py) keeps one of the two
+    busy: first the current one, so the launches must wait for inputs produced behind it; then the handle's, so the torch
+    ops that consume the results at once must wait for the launches."""
     import torch
+    from _stream_order import Blocker
 
     M = 257
     kw = case_args(case, True, True, M)
     d = _dev_kw(kw)
-    torch.cuda.synchronize()
-    other = torch.cuda.Stream()
-    with torch.cuda.stream(other):                                       # torch's current stream is not the handle's stream
-        logits = (d["logits"] * 1.0).requires_grad_(True)                # produced on `other`
-        values = (d["values"] * 1.0).requires_grad_(True)
-        norm = batch.masked_moments(d["advantages"] * 1.0, _dev(_live(kw)))
-        r = batch.ppo_loss(**{**d, "logits": logits, "values": values}, norm=norm, **HYPER)
-        r.loss.backward()
-        got = [t.detach().cpu().numpy() for t in (norm, r.stats, logits.grad, values.grad)]
+    live = _dev(_live(kw))
     nn = masked_moments_spec(kw["advantages"], _live(kw))
     want = ppo_loss_spec(**kw, norm=nn[1:3], **HYPER)
     assert np.isfinite(want).all()
     wl, wv = ppo_loss_backward_spec(**kw, norm=nn[1:3], **HYPER, stats=want)
-    for g, w in zip(got, (nn, want, wl, wv)):
-        np.testing.assert_array_equal(bits32(g), bits32(w))
+    blocker = Blocker()
+    handle = batch._stream                                               # (where the batch launches)
+    other = torch.cuda.Stream()
+    blocker.warm(other, handle)
+    for busy in (None, other, handle):                                   # (None: once without a blocker, the one-off host work)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(other):                                   # torch's current stream is not the handle's stream
+            ev = None if busy is None else blocker.run(busy)
+            logits = (d["logits"] * 1.0).requires_grad_(True)            # produced on `other`
+            values = (d["values"] * 1.0).requires_grad_(True)
+            norm = batch.masked_moments(d["advantages"] * 1.0, live)
+            r = batch.ppo_loss(**{**d, "logits": logits, "values": values}, norm=norm, **HYPER)
+            r.loss.backward()
+            early = [t.detach().clone() for t in (norm, r.stats, logits.grad, values.grad)]   # consumers, at once, on `other`
+            still_running = ev is None or not ev.query()
+            got = [t.cpu().numpy() for t in early]
+        assert still_running, "blocker too short: it had ended before the consumers were enqueued"
+        for g, w in zip(got, (nn, want, wl, wv)):
+            np.testing.assert_array_equal(bits32(g), bits32(w))
 
 
 def test_captured_forward_and_backward_and_static_buffers(batch, case):
