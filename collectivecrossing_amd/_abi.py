@@ -94,6 +94,15 @@ class CcxAdamTensor(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p), ("numel", C.c_int64)]
 
 
+SIDES_MAX_GROUPS = 8
+
+
+class CcxSlotGroup(C.Structure):
+    """``ccx_slot_group``: one row of the group table of CCX_SIDES, the slot mask and the head's four device pointers."""
+
+    _fields_ = [("slots", C.c_uint64), ("w1t", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p)]
+
+
 COUNTER_FIELDS =tuple(name for name, _ in CcxCounters._fields_)
 
 _H = C.c_void_p  # ccx_handle*
@@ -161,6 +170,11 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_adam_workspace_bytes": (C.c_int64, [C.c_int32, C.POINTER(C.c_int64)]),
     "ccx_adam_step": (C.c_int, [_H, C.c_int32, C.POINTER(CcxAdamTensor), C.c_float, C.c_void_p] + [C.c_float] * 5
                       + [C.c_void_p] * 3),
+    "ccx_sides_forward": (C.c_int, [_H, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.POINTER(CcxSlotGroup), C.c_void_p,
+                                    C.c_void_p]),
+    "ccx_sides_sample_actions": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(CcxSlotGroup), C.c_void_p,
+                                           C.c_int32] + [C.c_void_p] * 4),
+    "ccx_sides_backward": (C.c_int, [_H, C.c_int64, C.c_int32, C.c_uint64] + [C.c_int32] * 4 + [C.c_void_p] * 10),
     "ccx_set_check_inputs": (C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),

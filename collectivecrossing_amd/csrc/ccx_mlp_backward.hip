@@ -17,8 +17,17 @@
 // head_grad_final_kernel: one wave per element; lane j is place j of ccx_ppo.h's final step (contiguous, coalesced reads of
 // the element's B partials), the 64 places are halved by the butterfly of ccx_ppo_loss.hip, lane 0 rounds to f32 once and
 // stores.  No atomic, no last-block-done counter: a kernel boundary orders the partials.
+//
+// CCX_SIDES (ccx_sides_backward): the same two launches over the SELECTED rows of one slot group of [M][N][..] arrays
+// (ccx_sides.h).  The body of the blocks kernel is one function, grad_blocks, over a `Rows` argument that says where the
+// rows of a sub-tile lie: AdjacentRows (rows rs .. rs + nr - 1 of the arrays, the loads above) or PickedRows (block b holds
+// selection indices 256 b .. 256 b + 255; per sub-tile the first nr threads leave the flat rows m N + a in LDS, and x -- 8-byte
+// pieces when L is even, as in ccx_sides.hip --, hidden, grad_y and grad_a are addressed through them).  The row image, ga,
+// the chains and the partials' layout are the same code, so sides_grad_blocks_kernel's partials are those of the gathered
+// call and head_grad_final_kernel finishes them as it is.
 #include "ccx_internal.h"
 #include "ccx_mlp_grad.h"
+#include "ccx_sides.h"
 
 using ccxi::fail;
 namespace mg = ccx_mlp_grad;
@@ -68,40 +77,11 @@ __device__ __forceinline__ double halve_wave(double s) {
     return s;
 }
 
-__global__ __launch_bounds__(kThreads) void head_grad_blocks_kernel(const HeadGradArgs A) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    const int tid = (int)threadIdx.x;
-    const int L = A.L, H = A.H, O = A.O, R = A.sub, H4 = H / 4;
-    const RowImage m = row_image(L, H, O);
-    const int RS = m.stride;
-    float* w2s = lds + R * RS;
-    const long long r0 = (long long)blockIdx.x * mg::kBlockRows, left = A.rows - r0;
-    const int nb = left < mg::kBlockRows ? (int)left : mg::kBlockRows;   // (>= 1: the grid has ceil(rows / 256) blocks)
-    // this thread's tile: li / rj = its first left / right index, loff / roff = where those sit in a row's image
-    const int KT1 = m.ga / 4, JT2 = H4 + 1, T1 = KT1 * H4, T = T1 + ((O + 3) / 4) * JT2;
-    const int t = (int)blockIdx.y * kThreads + tid;
-    const bool live = t < T, second = live && t >= T1;
-    int li = 0, rj = 0, loff = 0, roff = m.ga;
-    if (live && !second) {
-        li = 4 * (t / H4);
-        rj = 4 * (t % H4);
-        loff = li;
-        roff = m.ga + rj;
-    } else if (second) {
-        li = 4 * ((t - T1) / JT2);
-        rj = 4 * ((t - T1) % JT2);
-        loff = m.gy + li;
-        roff = m.hid + rj;
-    }
-    for (int i = tid; i < O * H; i += kThreads) w2s[i] = A.w2[i];
-    for (int r = tid; r < R; r += kThreads) {
-        lds[r * RS + L] = 1.0f;
-        lds[r * RS + m.hid + H] = 1.0f;
-    }
-    double acc[mg::kTile][mg::kTile] = {};
-    for (int s0 = 0; s0 < nb; s0 += R) {
-        const int nr = nb - s0 < R ? nb - s0 : R;
-        const long long rs = r0 + s0;                                    // the sub-tile's first row: a multiple of 8
+// Where the rows of a sub-tile lie.  AdjacentRows: rows rs .. rs + nr - 1 of [rows][..] arrays.
+struct AdjacentRows {
+    __device__ __forceinline__ void begin(const HeadGradArgs&, long long, int) const {}
+    __device__ __forceinline__ void load(const HeadGradArgs& A, float* lds, const RowImage& m, long long rs, int nr, int tid, int L,
+                                         int H4, int O, int RS) const {
         // 1. x: 16-byte pieces from rs * L on (16-byte aligned: rs * L is a multiple of 8 floats); the piece that holds the
         //    array's end is read element by element
         const int pieces = (nr * L + 3) / 4;
@@ -138,6 +118,87 @@ __global__ __launch_bounds__(kThreads) void head_grad_blocks_kernel(const HeadGr
             const int r = i / O, o = i - r * O;
             lds[r * RS + m.gy + o] = A.grad_y[rs * O + i];
         }
+    }
+    __device__ __forceinline__ long long row(long long rs, int r) const { return rs + r; }
+};
+
+// PickedRows: the sub-tile's rows are selection indices rs .. rs + nr - 1 of one slot group (ccx_sides.h); their flat rows
+// m N + a are left in LDS by the first nr threads.  A.rows = M S, the number of selected rows.
+struct PickedRows {
+    uint64_t slots;
+    int32_t S, N;
+    long long* flat;                   // LDS [sub]
+    __device__ __forceinline__ void begin(const HeadGradArgs&, long long rs, int nr) const {
+        const int tid = (int)threadIdx.x;
+        if (tid < nr) flat[tid] = ccx_sides::row_of(slots, S, N, ccx_sides::start_of(rs, S), (uint32_t)tid).row;
+        __syncthreads();
+    }
+    __device__ __forceinline__ void load(const HeadGradArgs& A, float* lds, const RowImage& m, long long, int nr, int tid, int L,
+                                         int H4, int O, int RS) const {
+        // x: a row starts at a multiple of 8 bytes when L is even (x is 16-byte aligned), else dwords
+        if ((L & 1) == 0) {
+            const int L2 = L >> 1;
+            for (int p = tid; p < nr * L2; p += kThreads) {
+                const int r = p / L2, q = p - r * L2;
+                const float2 v = reinterpret_cast<const float2*>(A.x + flat[r] * L)[q];
+                lds[r * RS + 2 * q] = v.x;
+                lds[r * RS + 2 * q + 1] = v.y;
+            }
+        } else {
+            for (int p = tid; p < nr * L; p += kThreads) {
+                const int r = p / L, k = p - r * L;
+                lds[r * RS + k] = A.x[flat[r] * L + k];
+            }
+        }
+        for (int p = tid; p < nr * H4; p += kThreads) {
+            const int r = p / H4, q = p - r * H4;
+            *quad(lds + r * RS + m.hid + 4 * q) = reinterpret_cast<const float4*>(A.hidden + flat[r] * A.H)[q];
+        }
+        for (int i = tid; i < nr * O; i += kThreads) {
+            const int r = i / O, o = i - r * O;
+            lds[r * RS + m.gy + o] = A.grad_y[flat[r] * O + o];
+        }
+    }
+    __device__ __forceinline__ long long row(long long, int r) const { return flat[r]; }
+};
+
+template <class Rows>
+__device__ __forceinline__ void grad_blocks(const HeadGradArgs& A, const Rows& rows) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int tid = (int)threadIdx.x;
+    const int L = A.L, H = A.H, O = A.O, R = A.sub, H4 = H / 4;
+    const RowImage m = row_image(L, H, O);
+    const int RS = m.stride;
+    float* w2s = lds + R * RS;
+    const long long r0 = (long long)blockIdx.x * mg::kBlockRows, left = A.rows - r0;
+    const int nb = left < mg::kBlockRows ? (int)left : mg::kBlockRows;   // (>= 1: the grid has ceil(rows / 256) blocks)
+    // this thread's tile: li / rj = its first left / right index, loff / roff = where those sit in a row's image
+    const int KT1 = m.ga / 4, JT2 = H4 + 1, T1 = KT1 * H4, T = T1 + ((O + 3) / 4) * JT2;
+    const int t = (int)blockIdx.y * kThreads + tid;
+    const bool live = t < T, second = live && t >= T1;
+    int li = 0, rj = 0, loff = 0, roff = m.ga;
+    if (live && !second) {
+        li = 4 * (t / H4);
+        rj = 4 * (t % H4);
+        loff = li;
+        roff = m.ga + rj;
+    } else if (second) {
+        li = 4 * ((t - T1) / JT2);
+        rj = 4 * ((t - T1) % JT2);
+        loff = m.gy + li;
+        roff = m.hid + rj;
+    }
+    for (int i = tid; i < O * H; i += kThreads) w2s[i] = A.w2[i];
+    for (int r = tid; r < R; r += kThreads) {
+        lds[r * RS + L] = 1.0f;
+        lds[r * RS + m.hid + H] = 1.0f;
+    }
+    double acc[mg::kTile][mg::kTile] = {};
+    for (int s0 = 0; s0 < nb; s0 += R) {
+        const int nr = nb - s0 < R ? nb - s0 : R;
+        const long long rs = r0 + s0;                                    // the sub-tile's first row: a multiple of 8
+        rows.begin(A, rs, nr);
+        rows.load(A, lds, m, rs, nr, tid, L, H4, O, RS);
         __syncthreads();
         // 2. ga, four units at a time
         for (int p = tid; p < nr * H4; p += kThreads) {
@@ -149,7 +210,7 @@ __global__ __launch_bounds__(kThreads) void head_grad_blocks_kernel(const HeadGr
                 g[c] = mg::ga_unit(A.activation, mg::gh_unit(O, row + m.gy, w2s + j + c, H), row[m.hid + j + c]);
             const float4 q = make_float4(g[0], g[1], g[2], g[3]);
             *quad(lds + r * RS + m.ga + j) = q;
-            if (A.grad_a && blockIdx.y == 0) reinterpret_cast<float4*>(A.grad_a)[(rs + r) * H4 + (j >> 2)] = q;
+            if (A.grad_a && blockIdx.y == 0) reinterpret_cast<float4*>(A.grad_a)[rows.row(rs, r) * H4 + (j >> 2)] = q;
         }
         __syncthreads();
         // 3. the chains: this thread's 16 elements, the sub-tile's rows in ascending order
@@ -174,6 +235,23 @@ __global__ __launch_bounds__(kThreads) void head_grad_blocks_kernel(const HeadGr
     }
 }
 
+
+__global__ __launch_bounds__(kThreads) void head_grad_blocks_kernel(const HeadGradArgs A) {
+    grad_blocks(A, AdjacentRows{});
+}
+
+// the slot group of a ccx_sides_backward call
+struct SideSel {
+    uint64_t slots;
+    int32_t S, N;
+    int32_t flat_at;                   // where the flat rows sit in LDS, in floats (behind w2)
+};
+
+__global__ __launch_bounds__(kThreads) void sides_grad_blocks_kernel(const HeadGradArgs A, const SideSel G) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    grad_blocks(A, PickedRows{G.slots, G.S, G.N, reinterpret_cast<long long*>(lds + G.flat_at)});
+}
+
 __global__ __launch_bounds__(kThreads) void head_grad_final_kernel(const HeadGradArgs A) {
     const int lane = (int)(threadIdx.x & 63u);
     const long long e = (long long)blockIdx.x * (kThreads / 64) + (long long)(threadIdx.x >> 6);
@@ -188,12 +266,53 @@ __global__ __launch_bounds__(kThreads) void head_grad_final_kernel(const HeadGra
 }
 
 // rows of a sub-tile: the most of 64, 32, 16, 8 whose images fit the budget beside w2 (8 always do: 33 KB + 8 KB at the limits)
-int sub_rows(int L, int H, int O, size_t& bytes) {
-    const size_t row = (size_t)row_image(L, H, O).stride * sizeof(float), fixed = (size_t)O * H * sizeof(float);
+// (`per_row`: further bytes per row behind w2 -- the flat rows of the sides kernel)
+int sub_rows(int L, int H, int O, size_t& bytes, size_t per_row = 0) {
+    const size_t row = (size_t)row_image(L, H, O).stride * sizeof(float) + per_row, fixed = (size_t)O * H * sizeof(float);
     int R = 64;
     while (R > 8 && R * row + fixed > kLdsBudget) R >>= 1;
     bytes = R * row + fixed;
     return R;
+}
+
+// the checks and the two launches of both entry points; `sel`: the slot group of ccx_sides_backward (rows = M S), or null
+int backward_launches(const char* who, ccx_handle* h, int64_t rows, const SideSel* sel, int32_t L, int32_t H, int32_t O, int32_t activation,
+                      const float* x, const float* hidden, const float* grad_y, const float* w2, void* workspace, float* grad_w1t,
+                      float* grad_b1, float* grad_w2, float* grad_b2, float* grad_a_or_null) {
+    if (!x || !hidden || !grad_y || !w2 || !workspace || !grad_w1t || !grad_b1 || !grad_w2 || !grad_b2)
+        return fail(CCX_EINVAL, "%s: NULL argument (only grad_a may be NULL)", who);
+    unsigned blocks = 0;
+    if (int rc = ccxi::row_blocks(who, rows, mg::kBlockRows, blocks)) return rc;
+    if (!ccx_mlp::shape_ok(L, H, O, activation))
+        return fail(CCX_EINVAL, "%s: L = %d, H = %d, O = %d, activation = %d: 1 <= L <= %d, H a multiple of 16 in 16..%d, "
+                    "1 <= O <= %d and activation 0 (tanh) or 1 (relu) are required", who, L, H, O, activation, ccx_mlp::kMaxL, ccx_mlp::kMaxH,
+                    ccx_mlp::kMaxO);
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hidden) | reinterpret_cast<uintptr_t>(grad_a_or_null)) & 15u)
+        return fail(CCX_EINVAL, "%s: x, hidden and grad_a must be 16-byte aligned", who);
+    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "%s: workspace must be 8-byte aligned", who);
+    if ((reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(w2) | reinterpret_cast<uintptr_t>(grad_w1t) |
+         reinterpret_cast<uintptr_t>(grad_b1) | reinterpret_cast<uintptr_t>(grad_w2) | reinterpret_cast<uintptr_t>(grad_b2)) & 3u)
+        return fail(CCX_EINVAL, "%s: grad_y, w2, grad_w1t, grad_b1, grad_w2 and grad_b2 must be 4-byte aligned", who);
+    CCX_HIP(hipSetDevice(h->device));
+    size_t bytes = 0;
+    const int R = sub_rows(L, H, O, bytes, sel ? sizeof(long long) : 0);
+    const HeadGradArgs A{x, hidden, grad_y, w2, static_cast<double*>(workspace), grad_w1t, grad_b1, grad_w2, grad_b2, grad_a_or_null,
+                         (long long)rows, (long long)blocks, L, H, O, activation, R};
+    const RowImage m = row_image(L, H, O);
+    const int tiles = (m.ga / 4) * (H / 4) + ((O + 3) / 4) * (H / 4 + 1);
+    const long long elements = mg::elements_of(L, H, O);
+    const dim3 grid(blocks, (unsigned)((tiles + kThreads - 1) / kThreads));
+    if (sel) {
+        SideSel G = *sel;
+        G.flat_at = R * m.stride + O * H;                                // (floats; an even number: the stride and H are multiples of 4)
+        hipLaunchKernelGGL(sides_grad_blocks_kernel, grid, dim3(kThreads), bytes, h->stream, A, G);
+    } else {
+        hipLaunchKernelGGL(head_grad_blocks_kernel, grid, dim3(kThreads), bytes, h->stream, A);
+    }
+    hipLaunchKernelGGL(head_grad_final_kernel, dim3((unsigned)((elements + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0,
+                       h->stream, A);
+    CCX_HIP(hipGetLastError());
+    return CCX_OK;
 }
 
 }  // namespace
@@ -206,34 +325,25 @@ int ccx_mlp_backward(ccx_handle* h, int64_t rows, int32_t L, int32_t H, int32_t 
                      const float* hidden, const float* grad_y, const float* w2, void* workspace, float* grad_w1t, float* grad_b1,
                      float* grad_w2, float* grad_b2, float* grad_a_or_null) {
     if (!h) return fail(CCX_EINVAL, "NULL handle");
-    if (!x || !hidden || !grad_y || !w2 || !workspace || !grad_w1t || !grad_b1 || !grad_w2 || !grad_b2)
-        return fail(CCX_EINVAL, "ccx_mlp_backward: NULL argument (only grad_a may be NULL)");
-    unsigned blocks = 0;
-    if (int rc = ccxi::row_blocks("ccx_mlp_backward", rows, mg::kBlockRows, blocks)) return rc;
-    if (!ccx_mlp::shape_ok(L, H, O, activation))
-        return fail(CCX_EINVAL, "ccx_mlp_backward: L = %d, H = %d, O = %d, activation = %d: 1 <= L <= %d, H a multiple of 16 in 16..%d, "
-                    "1 <= O <= %d and activation 0 (tanh) or 1 (relu) are required", L, H, O, activation, ccx_mlp::kMaxL, ccx_mlp::kMaxH,
-                    ccx_mlp::kMaxO);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hidden) | reinterpret_cast<uintptr_t>(grad_a_or_null)) & 15u)
-        return fail(CCX_EINVAL, "ccx_mlp_backward: x, hidden and grad_a must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "ccx_mlp_backward: workspace must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(w2) | reinterpret_cast<uintptr_t>(grad_w1t) |
-         reinterpret_cast<uintptr_t>(grad_b1) | reinterpret_cast<uintptr_t>(grad_w2) | reinterpret_cast<uintptr_t>(grad_b2)) & 3u)
-        return fail(CCX_EINVAL, "ccx_mlp_backward: grad_y, w2, grad_w1t, grad_b1, grad_w2 and grad_b2 must be 4-byte aligned");
-    CCX_HIP(hipSetDevice(h->device));
-    size_t bytes = 0;
-    const int R = sub_rows(L, H, O, bytes);
-    const HeadGradArgs A{x, hidden, grad_y, w2, static_cast<double*>(workspace), grad_w1t, grad_b1, grad_w2, grad_b2, grad_a_or_null,
-                         (long long)rows, (long long)blocks, L, H, O, activation, R};
-    const RowImage m = row_image(L, H, O);
-    const int tiles = (m.ga / 4) * (H / 4) + ((O + 3) / 4) * (H / 4 + 1);
-    const long long elements = mg::elements_of(L, H, O);
-    hipLaunchKernelGGL(head_grad_blocks_kernel, dim3(blocks, (unsigned)((tiles + kThreads - 1) / kThreads)), dim3(kThreads), bytes,
-                       h->stream, A);
-    hipLaunchKernelGGL(head_grad_final_kernel, dim3((unsigned)((elements + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0,
-                       h->stream, A);
-    CCX_HIP(hipGetLastError());
-    return CCX_OK;
+    return backward_launches("ccx_mlp_backward", h, rows, nullptr, L, H, O, activation, x, hidden, grad_y, w2, workspace, grad_w1t, grad_b1,
+                             grad_w2, grad_b2, grad_a_or_null);
+}
+
+int ccx_sides_backward(ccx_handle* h, int64_t M, int32_t N, uint64_t slots, int32_t L, int32_t H, int32_t O, int32_t activation,
+                       const float* x, const float* hidden, const float* grad_y, const float* w2, void* workspace, float* grad_w1t,
+                       float* grad_b1, float* grad_w2, float* grad_b2, float* grad_a_or_null) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (N < 1 || N > 64) return fail(CCX_EINVAL, "ccx_sides_backward: N = %d, 1..64 agent slots are required", N);
+    if (M < 1 || M > ((int64_t)1 << 40)) return fail(CCX_EINVAL, "ccx_sides_backward: M = %lld, 1..2^40 env-rows are required", (long long)M);
+    int which = 0;
+    switch (ccx_sides::check_masks(&slots, 1, N, which)) {
+        case 0: break;
+        case 2: return fail(CCX_EINVAL, "ccx_sides_backward: the group owns no slot (an empty mask)");
+        default: return fail(CCX_EINVAL, "ccx_sides_backward: the mask %#llx has a bit at or above N = %d", (unsigned long long)slots, N);
+    }
+    const SideSel sel{slots, ccx_sides::popcount(slots), N, 0};
+    return backward_launches("ccx_sides_backward", h, M * sel.S, &sel, L, H, O, activation, x, hidden, grad_y, w2, workspace, grad_w1t,
+                             grad_b1, grad_w2, grad_b2, grad_a_or_null);
 }
 
 }  // extern "C"

@@ -980,6 +980,71 @@ int ccx_adam_step(ccx_handle* h, int32_t num_tensors, const ccx_adam_tensor* ten
                   const float* lr_dev_or_null /* [1] */, float beta1, float beta2, float eps, float weight_decay,
                   float max_grad_norm, void* state /* 64 bytes */, void* workspace, float* stats /* [4] */);
 /*
+ * CCX_SIDES: several heads of CCX_MLP, each owning a set of agent slots, run directly on the [..][N][L] arrays a rollout
+ * wrote -- the two policies ("boarding", "exiting") the reference trains, a learner beside scripted agents, or a head per
+ * agent -- without a gathered copy.  Nothing about the arithmetic is new: every output is, bit for bit, what an existing
+ * call gives on the gathered rows, and no tolerance enters anywhere.
+ *
+ * A group is a 64-bit slot mask and one head (w1t, b1, w2, b2: device pointers, CCX_MLP's layouts).  Bit a of the mask
+ * stands for agent slot a, boarding slots first (ccx_rollout_mixed's convention).  A call takes 1 to
+ * CCX_SIDES_MAX_GROUPS groups as a HOST array of ccx_slot_group (it is copied into the kernel arguments: no host-to-device
+ * copy is enqueued); the masks are non-empty, pairwise disjoint and have no bit at or above N (1 <= N <= 64); all groups of
+ * a call share (L, H, O, activation), within CCX_MLP's limits.
+ *
+ * An array x is [M][N][L], M >= 1 the product of the leading dimensions.  The SELECTED rows of a group are the flat rows
+ * m * N + a with bit a set, in ascending flat index: m-major, then a ascending.  S = popcount(mask); a group has M * S
+ * selected rows, and selection index j = m * S + i names the i-th set bit of m.
+ *
+ * Forward (ccx_sides_forward).  For every selected row of every group, y[row][0 .. O-1] (and hidden[row][0 .. H-1] when
+ * given) are exactly CCX_MLP's outputs for x[row] under the group's parameters: the per-row sequence of CCX_MLP, which does
+ * not depend on the row's place or on how many rows there are.  Rows of slots that no group owns are not read, and their y
+ * and hidden bytes are not written.
+ *
+ * Fused sampling (ccx_sides_sample_actions): by definition ccx_sample_actions on the logits the forward with M = E,
+ * L = ccx_obs_len(N), O = 5 assembles from obs [E][N][L] -- the same key (global env, episode, step, slot), the same rule
+ * for terminated or truncated slots, the same bits in actions, logp and entropy -- in ONE kernel.  A slot that no group
+ * owns gets action 255 (CCX_ACTION_ABSENT), logp = +0.0f and entropy = +0.0f, and its logits_or_null bytes are untouched;
+ * every element of actions, logp and entropy is written.
+ *
+ * Backward (ccx_sides_backward; one group per call): grad_w1t, grad_b1, grad_w2, grad_b2 and grad_a are exactly what
+ * ccx_mlp_backward gives on the gathered arrays -- the group's selected rows of x, hidden and grad_y, contiguous, in
+ * selection order.  In detail: blocks of 256 SELECTED rows, chains in ascending selection order, B = ceil(M * S / 256)
+ * block partials per element, then CCX_PPO_LOSS's final step.  The workspace is
+ * ccx_mlp_backward_workspace_bytes(M * S, L, H, O) bytes.  grad_a_or_null is [M][N][H] and is written at the selected
+ * rows only.
+ *
+ * ccx_sides_forward and ccx_sides_sample_actions enqueue ONE kernel on the handle's stream, ccx_sides_backward TWO plain
+ * launches: no host synchronisation, no atomic, no allocation, and everything captures into a HIP graph.  Offsets are
+ * 64-bit.  A NULL handle or a NULL required pointer (everything but hidden, masks, logp, entropy, logits and grad_a), M < 1
+ * or beyond 2^40, N outside 1..64, more than CCX_SIDES_MAX_GROUPS groups or none, an empty mask, a mask with a bit at or
+ * above N, overlapping masks, a grid beyond 2^31 - 1 workgroups (of 64 selected rows; of 256 in the backward), a shape
+ * outside CCX_MLP's limits, x / obs, hidden or grad_a not 16-byte aligned, a workspace not 8-byte aligned, or any other
+ * f32 array not 4-byte aligned: CCX_EINVAL with a ccx_last_error message, before any launch.
+ *
+ * Not here: groups of different (H, O, activation) in one launch, per-env slot assignments (the mask holds for every env,
+ * as in ccx_rollout_mixed), the gradient with respect to x, critics inside the actor launch, bf16 / f16.
+ */
+#define CCX_SIDES_MAX_GROUPS 8
+typedef struct ccx_slot_group {
+    uint64_t     slots;
+    const float* w1t;
+    const float* b1;
+    const float* w2;
+    const float* b2;
+} ccx_slot_group;
+int ccx_sides_forward(ccx_handle* h, int64_t M, int32_t N, int32_t L, int32_t H, int32_t O, int32_t activation,
+                      const float* x /* [M][N][L] */, int32_t num_groups, const ccx_slot_group* groups /* host [num_groups] */,
+                      float* y /* [M][N][O] */, float* hidden_or_null /* [M][N][H] */);
+int ccx_sides_sample_actions(ccx_handle* h, int32_t H, int32_t activation, const float* obs /* [E][N][ccx_obs_len(N)] */,
+                             int32_t num_groups, const ccx_slot_group* groups /* host [num_groups] */,
+                             const uint8_t* masks_or_null /* [E][N] */, int32_t deterministic, uint8_t* actions /* [E][N] */,
+                             float* logp_or_null /* [E][N] */, float* entropy_or_null /* [E][N] */,
+                             float* logits_or_null /* [E][N][5] */);
+int ccx_sides_backward(ccx_handle* h, int64_t M, int32_t N, uint64_t slots, int32_t L, int32_t H, int32_t O, int32_t activation,
+                       const float* x /* [M][N][L] */, const float* hidden /* [M][N][H] */, const float* grad_y /* [M][N][O] */,
+                       const float* w2 /* [O][H] */, void* workspace, float* grad_w1t /* [L][H] */, float* grad_b1 /* [H] */,
+                       float* grad_w2 /* [O][H] */, float* grad_b2 /* [O] */, float* grad_a_or_null /* [M][N][H] */);
+/*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
  * `rng_seed` of ccx_rollout).  The action of agent slot a of global env g at step t (0-based) of its episode j is
