@@ -175,7 +175,11 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_sides_sample_actions": (C.c_int, [_H, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(CcxSlotGroup), C.c_void_p,
                                            C.c_int32] + [C.c_void_p] * 4),
     "ccx_sides_backward": (C.c_int, [_H, C.c_int64, C.c_int32, C.c_uint64] + [C.c_int32] * 4 + [C.c_void_p] * 10),
-    "ccx_set_check_inputs": (C.c_int, [_H, C.c_int32]),
+    "ccx_q_actions": (C.c_int, [_H] + [C.c_void_p] * 5),
+    "ccx_td_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "ccx_td_loss": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 9 + [C.c_float] * 2 + [C.c_void_p] * 3),
+    "ccx_td_loss_backward": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 9 + [C.c_float] * 2 + [C.c_void_p] * 3),
+    "ccx_set_check_inputs":(C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),
     "ccx_set_policy_epsilon": (C.c_int, [_H, C.c_double]),

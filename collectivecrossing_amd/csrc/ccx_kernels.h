@@ -36,6 +36,12 @@ enum : uint32_t { kEpsStream = 0x5BD1E995u };
 // CCX_SAMPLE (include/ccx.h, ccx_sample.hip): the draw of a learned policy's action comes from the same word with
 // seed_hi ^ kSampleStream -- a third stream beside CCX_POLICY_RANDOM's (0) and the epsilon draws'.
 enum : uint32_t { kSampleStream = 0x2545F491u };
+// CCX_QLEARN (include/ccx.h, ccx_qlearn.hip): the two draws of an epsilon-greedy action over Q-values -- whether the slot
+// explores, and which legal action it then takes -- are two more streams of the same word (seed_hi ^ the constant).
+enum : uint32_t { kQExploreStream = 0x68E31DA4u, kQChoiceStream = 0xB5297A4Du };
+static_assert(kQExploreStream != kQChoiceStream && kQExploreStream != kEpsStream && kQExploreStream != kSampleStream &&
+              kQChoiceStream != kEpsStream && kQChoiceStream != kSampleStream && kQExploreStream != 0u && kQChoiceStream != 0u,
+              "every stream of the counter-based word has its own constant");
 __host__ __device__ inline uint32_t explore_action(uint32_t u, uint32_t free_dirs) {
     uint32_t vm = (free_dirs & 0xFu) | 0x10u;          // wait is always valid (greedy_policy.py:251)
 #if defined(__HIP_DEVICE_COMPILE__)

@@ -1,0 +1,280 @@
+// ccx_qlearn.hip -- CCX_QLEARN (include/ccx.h): epsilon-greedy actions over the legal set from a network's Q-values, and the
+// double-DQN TD error with its Huber loss, its means over the rows that count and its gradient with respect to the Q-values.
+// The per-slot and per-row rules and the final values are ccx_qlearn.h; the tree is ccx_ppo.h's; the slot rule (which (e, a) a
+// lane owns, its small loads, its key) is ccx_draw.h's; the rows of five f32 travel through LDS by ccx_rows.h.
+//
+// q_act_kernel: ccx_sample.hip's shape.  One lane owns one slot, a workgroup is one wave; every load -- the small ones, the
+// exploration rate, the wave's pieces -- is issued before the first wait.  The greedy instantiation reads neither counter.
+// td_partial_kernel / td_final_kernel: ccx_ppo_loss.hip's forward.  A workgroup of four waves takes 256 consecutive rows, one
+// lane one row; each wave reduces its rows' six f64 terms by a butterfly, the first six threads add the four groups and write
+// the block's partials ([6][B] f64); ONE wave then adds the partials lane-strided, runs the same butterfly and writes `stats`.
+// Two plain launches: no atomic, no last-block-done counter.
+// td_bwd_kernel: one lane one row, a workgroup is one wave; it recomputes the forward terms from the inputs and reads nothing
+// else but `stats`; every element of grad_q is written, whole 16-byte pieces through LDS.
+#include "ccx_draw.h"
+#include "ccx_qlearn.h"
+#include "ccx_rows.h"
+
+using ccx_draw::DrawArgs;
+using ccxi::fail;
+
+namespace {
+
+template <bool MASK, bool EPS>
+__global__ __launch_bounds__(64) void q_act_kernel(const float* q, const DrawArgs D, const float* epsilon, uint8_t* explored) {
+    __shared__ float4 pieces[80];
+    const uint32_t lane = threadIdx.x;
+    const ccx_draw::Slot s = ccx_draw::slot_of(D, lane);
+    // every load is issued before the first wait: the small ones, the rate, then the wave's pieces
+    const ccx_draw::Small v = ccx_draw::small_loads<!EPS>(D, s, MASK);
+    float eps = 0.0f;
+    if (EPS) eps = epsilon[0];
+    const long long floats = D.EN * 5, last_piece = floats / 4 - 1;
+    float l[5];
+    ccx_rows::load_rows(q, D.EN, pieces, lane, blockIdx.x, s.slot, floats, last_piece, l);
+    if (s.slot >= D.EN) return;
+    const bool dead = (v.term | v.trunc) != 0;
+    const uint32_t m = ccx_qlearn::legal_set(v.mbyte);
+    uint32_t action = ccx_qlearn::greedy(l, m);
+    bool explore = false;
+    if (EPS) {
+        const uint32_t g = D.genv0 + (uint32_t)s.e;
+        const uint32_t u1 = ccx::random_word(D.seed_lo, D.seed_hi ^ ccx::kQExploreStream, g, v.episode, v.step, s.a);
+        const uint32_t u2 = ccx::random_word(D.seed_lo, D.seed_hi ^ ccx::kQChoiceStream, g, v.episode, v.step, s.a);
+        explore = ccx_qlearn::explores(u1, eps);
+        const uint32_t ch = ccx_qlearn::choice(u2, m);
+        action = explore ? ch : action;
+    }
+    D.actions[s.slot] = dead ? (uint8_t)CCX_ACTION_ABSENT : (uint8_t)action;
+    if (explored) explored[s.slot] = (!dead && explore) ? (uint8_t)1 : (uint8_t)0;
+}
+
+struct TdArgs {
+    const float* q;
+    const float* q_next_target;
+    const float* q_next_online;        // read only where DOUBLE
+    const uint8_t* actions;
+    const double* reward;
+    const uint8_t* done;
+    const uint8_t* masks_next;         // or null (everything legal)
+    const uint8_t* valid;              // or null
+    const float* weights;              // or null
+    const float* stats_in;             // backward: the forward's stats
+    const float* grad_loss;            // backward, or null (= 1.0f)
+    float* grad_q;                     // backward
+    double* partials;                  // forward: [6][B]
+    float* stats;                      // forward
+    float* td_error;                   // forward, or null
+    float gamma, delta, c;
+    long long M, B;
+};
+
+struct TdSmall {
+    uint32_t a, mbyte, vbyte;
+    bool done, has_valid, has_w;
+    float r, w;
+};
+
+// what a row reads besides its rows of five: unconditional loads at a clamped index (surplus lanes load what the last row loads)
+__device__ __forceinline__ TdSmall td_small(const TdArgs& A, long long rl) {
+    TdSmall v;
+    v.a = A.actions[rl];
+    v.done = A.done[rl] != 0;
+    v.r = (float)A.reward[rl];                                          // one rounding, as CCX_GAE does it
+    v.mbyte = A.masks_next ? (uint32_t)A.masks_next[rl] : ccx_qlearn::kLegalAll;
+    v.has_valid = A.valid != nullptr;
+    v.vbyte = v.has_valid ? (uint32_t)A.valid[rl] : 1u;
+    v.has_w = A.weights != nullptr;
+    v.w = v.has_w ? A.weights[rl] : 1.0f;
+    return v;
+}
+
+// a group of the tree: for o = 32 .. 1 every lane takes s + (lane ^ o)'s s; f64 addition commutes, so all lanes agree
+__device__ __forceinline__ double halve_wave(double s) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s = s + __shfl_xor(s, o, 64);
+    return s;
+}
+
+template <bool DOUBLE>
+__global__ __launch_bounds__(256) void td_partial_kernel(const TdArgs A) {
+    __shared__ float4 pieces[DOUBLE ? 3 : 2][ccx_ppo::kBlockGroups][80];
+    __shared__ double groups[ccx_qlearn::kSums][ccx_ppo::kBlockGroups];
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const long long wave = (long long)blockIdx.x * ccx_ppo::kBlockGroups + w;
+    const long long row = wave * 64 + lane;
+    const long long rl = row < A.M ? row : A.M - 1;
+    const TdSmall v = td_small(A, rl);
+    const long long floats = A.M * 5, last_piece = floats / 4 - 1;      // M >= 1: at least one whole piece
+    float q[5], qt[5], qo[5];
+    ccx_rows::load_rows(A.q, A.M, pieces[0][w], lane, wave, row, floats, last_piece, q);
+    ccx_rows::load_rows(A.q_next_target, A.M, pieces[1][w], lane, wave, row, floats, last_piece, qt);
+    if constexpr (DOUBLE) ccx_rows::load_rows(A.q_next_online, A.M, pieces[2][w], lane, wave, row, floats, last_piece, qo);
+    const bool counts = row < A.M && ccx_qlearn::row_counts(v.has_valid, v.vbyte, v.a);
+    const bool bad = row < A.M && ccx_qlearn::row_bad(v.has_valid, v.vbyte, v.a);
+    ccx_qlearn::Row t;
+    if constexpr (DOUBLE) ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qo, v.mbyte, A.gamma, A.delta, A.c, v.has_w, v.w, t);
+    else ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qt, v.mbyte, A.gamma, A.delta, A.c, v.has_w, v.w, t);
+    if (A.td_error && row < A.M) A.td_error[row] = counts ? t.d : 0.0f;
+    // rows that do not count and rows >= M enter as +0.0, selected
+    double s[ccx_qlearn::kSums] = {counts ? 1.0 : 0.0,           counts ? (double)t.term : 0.0, counts ? (double)t.ad : 0.0,
+                                   counts ? (double)t.qa : 0.0,  counts ? (double)t.y : 0.0,    bad ? 1.0 : 0.0};
+#pragma unroll
+    for (int k = 0; k < ccx_qlearn::kSums; ++k) {
+        s[k] = halve_wave(s[k]);
+        if (lane == 0u) groups[k][w] = s[k];
+    }
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)ccx_qlearn::kSums) {
+        const uint32_t k = threadIdx.x;
+        A.partials[(long long)k * A.B + blockIdx.x] = ccx_ppo::block_partial(groups[k][0], groups[k][1], groups[k][2], groups[k][3]);
+    }
+}
+
+__global__ __launch_bounds__(64) void td_final_kernel(const TdArgs A) {
+    const int lane = (int)threadIdx.x;
+    double s[ccx_qlearn::kSums];
+    ccx_ppo::strided_partials(A.partials, A.B, lane, s);
+#pragma unroll
+    for (int k = 0; k < ccx_qlearn::kSums; ++k) s[k] = halve_wave(s[k]);
+    if (lane == 0) {
+        float st[8];
+        ccx_qlearn::td_finals(s, st);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) A.stats[k] = st[k];
+    }
+}
+
+template <bool DOUBLE>
+__global__ __launch_bounds__(64) void td_bwd_kernel(const TdArgs A) {
+    __shared__ float4 pieces[DOUBLE ? 3 : 2][80];
+    const uint32_t lane = threadIdx.x;
+    const long long row = (long long)blockIdx.x * 64 + lane;
+    const long long rl = row < A.M ? row : A.M - 1;
+    const TdSmall v = td_small(A, rl);
+    const float n = A.stats_in[6];
+    const float g = A.grad_loss ? A.grad_loss[0] : 1.0f;
+    const long long floats = A.M * 5, last_piece = floats / 4 - 1;
+    float q[5], qt[5], qo[5];
+    ccx_rows::load_rows(A.q, A.M, pieces[0], lane, blockIdx.x, row, floats, last_piece, q);
+    ccx_rows::load_rows(A.q_next_target, A.M, pieces[1], lane, blockIdx.x, row, floats, last_piece, qt);
+    if constexpr (DOUBLE) ccx_rows::load_rows(A.q_next_online, A.M, pieces[2], lane, blockIdx.x, row, floats, last_piece, qo);
+    const float sc = g / n;
+    const float gw = ccx_qlearn::row_scale(v.has_w, sc, v.w);
+    const bool counts = n != 0.0f && ccx_qlearn::row_counts(v.has_valid, v.vbyte, v.a);      // n == 0: every gradient +0.0f, selected
+    ccx_qlearn::Row t;
+    if constexpr (DOUBLE) ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qo, v.mbyte, A.gamma, A.delta, A.c, v.has_w, v.w, t);
+    else ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qt, v.mbyte, A.gamma, A.delta, A.c, v.has_w, v.w, t);
+    const float ga = ccx_qlearn::backward_row(t.d, t.ad, A.delta, gw);
+    float gr[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) gr[k] = (counts && v.a == (uint32_t)k) ? ga : 0.0f;
+    ccx_rows::store_rows(A.grad_q, A.M, pieces[0], lane, blockIdx.x, row, floats, last_piece, gr);
+}
+
+int check_td(const char* who, const void* q, const void* qt, const void* qo, float gamma, float huber_delta) {
+    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(qt) | reinterpret_cast<uintptr_t>(qo)) & 15u)
+        return fail(CCX_EINVAL, "%s: q, q_next_target and q_next_online must be 16-byte aligned", who);
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(CCX_EINVAL, "%s: gamma must be finite and lie in [0, 1], got %g", who, (double)gamma);
+    if (!(huber_delta > 0.0f)) return fail(CCX_EINVAL, "%s: huber_delta must be > 0 (+inf: the squared error), got %g", who, (double)huber_delta);
+    return CCX_OK;
+}
+
+TdArgs td_args(int64_t rows, const float* q, const uint8_t* actions, const double* reward, const uint8_t* done,
+               const float* q_next_target, const float* q_next_online_or_null, const uint8_t* masks_next_or_null,
+               const uint8_t* valid_or_null, const float* weights_or_null, float gamma, float huber_delta) {
+    TdArgs A{};
+    A.q = q;
+    A.q_next_target = q_next_target;
+    A.q_next_online = q_next_online_or_null;
+    A.actions = actions;
+    A.reward = reward;
+    A.done = done;
+    A.masks_next = masks_next_or_null;
+    A.valid = valid_or_null;
+    A.weights = weights_or_null;
+    A.gamma = gamma;
+    A.delta = huber_delta;
+    A.c = 0.5f * huber_delta;                                           // computed once, one f32 operation
+    A.M = rows;
+    return A;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ccx_q_actions(ccx_handle* h, const float* q, const uint8_t* masks_or_null, const float* epsilon_or_null, uint8_t* actions,
+                  uint8_t* explored_or_null) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (!q || !actions) return fail(CCX_EINVAL, "ccx_q_actions: NULL argument (q and actions are required)");
+    if (reinterpret_cast<uintptr_t>(q) & 15u) return fail(CCX_EINVAL, "ccx_q_actions: q must be 16-byte aligned");
+    CCX_HIP(hipSetDevice(h->device));
+    DrawArgs D = ccx_draw::draw_args(h, masks_or_null, actions, nullptr, nullptr);
+    D.seed_hi = h->rng_hi;                                              // the kernel adds its two streams itself
+    const dim3 grid((unsigned)((D.EN + 63) / 64)), block(64);           // E < 2^31, N <= 64: below 2^31
+    if (masks_or_null) {
+        if (epsilon_or_null) hipLaunchKernelGGL((q_act_kernel<true, true>), grid, block, 0, h->stream, q, D, epsilon_or_null, explored_or_null);
+        else hipLaunchKernelGGL((q_act_kernel<true, false>), grid, block, 0, h->stream, q, D, epsilon_or_null, explored_or_null);
+    } else {
+        if (epsilon_or_null) hipLaunchKernelGGL((q_act_kernel<false, true>), grid, block, 0, h->stream, q, D, epsilon_or_null, explored_or_null);
+        else hipLaunchKernelGGL((q_act_kernel<false, false>), grid, block, 0, h->stream, q, D, epsilon_or_null, explored_or_null);
+    }
+    CCX_HIP(hipGetLastError());
+    return CCX_OK;
+}
+
+int64_t ccx_td_workspace_bytes(int64_t rows) {
+    if (rows < 1) return 0;
+    return (int64_t)ccx_ppo::blocks_of(rows) * ccx_qlearn::kSums * (int64_t)sizeof(double);
+}
+
+int ccx_td_loss(ccx_handle* h, int64_t rows, const float* q, const uint8_t* actions, const double* reward, const uint8_t* done,
+                const float* q_next_target, const float* q_next_online_or_null, const uint8_t* masks_next_or_null,
+                const uint8_t* valid_or_null, const float* weights_or_null, float gamma, float huber_delta, void* workspace,
+                float* stats, float* td_error_or_null) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (!q || !actions || !reward || !done || !q_next_target || !workspace || !stats)
+        return fail(CCX_EINVAL, "ccx_td_loss: NULL argument (only q_next_online, masks_next, valid, weights and td_error may be NULL)");
+    unsigned blocks = 0;
+    if (int rc = ccxi::row_blocks("ccx_td_loss", rows, ccx_ppo::kBlockRows, blocks)) return rc;
+    if (int rc = check_td("ccx_td_loss", q, q_next_target, q_next_online_or_null, gamma, huber_delta)) return rc;
+    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "ccx_td_loss: workspace must be 8-byte aligned");
+    CCX_HIP(hipSetDevice(h->device));
+    TdArgs A = td_args(rows, q, actions, reward, done, q_next_target, q_next_online_or_null, masks_next_or_null, valid_or_null,
+                       weights_or_null, gamma, huber_delta);
+    A.partials = static_cast<double*>(workspace);
+    A.stats = stats;
+    A.td_error = td_error_or_null;
+    A.B = blocks;
+    if (q_next_online_or_null) hipLaunchKernelGGL((td_partial_kernel<true>), dim3(blocks), dim3(256), 0, h->stream, A);
+    else hipLaunchKernelGGL((td_partial_kernel<false>), dim3(blocks), dim3(256), 0, h->stream, A);
+    hipLaunchKernelGGL(td_final_kernel, dim3(1), dim3(64), 0, h->stream, A);
+    CCX_HIP(hipGetLastError());
+    return CCX_OK;
+}
+
+int ccx_td_loss_backward(ccx_handle* h, int64_t rows, const float* q, const uint8_t* actions, const double* reward,
+                         const uint8_t* done, const float* q_next_target, const float* q_next_online_or_null,
+                         const uint8_t* masks_next_or_null, const uint8_t* valid_or_null, const float* weights_or_null, float gamma,
+                         float huber_delta, const float* stats, const float* grad_loss_or_null, float* grad_q) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (!q || !actions || !reward || !done || !q_next_target || !stats || !grad_q)
+        return fail(CCX_EINVAL, "ccx_td_loss_backward: NULL argument (only q_next_online, masks_next, valid, weights and grad_loss may be NULL)");
+    unsigned blocks = 0;
+    if (int rc = ccxi::row_blocks("ccx_td_loss_backward", rows, 64, blocks)) return rc;
+    if (int rc = check_td("ccx_td_loss_backward", q, q_next_target, q_next_online_or_null, gamma, huber_delta)) return rc;
+    if (reinterpret_cast<uintptr_t>(grad_q) & 15u) return fail(CCX_EINVAL, "ccx_td_loss_backward: grad_q must be 16-byte aligned");
+    CCX_HIP(hipSetDevice(h->device));
+    TdArgs A = td_args(rows, q, actions, reward, done, q_next_target, q_next_online_or_null, masks_next_or_null, valid_or_null,
+                       weights_or_null, gamma, huber_delta);
+    A.stats_in = stats;
+    A.grad_loss = grad_loss_or_null;
+    A.grad_q = grad_q;
+    if (q_next_online_or_null) hipLaunchKernelGGL((td_bwd_kernel<true>), dim3(blocks), dim3(64), 0, h->stream, A);
+    else hipLaunchKernelGGL((td_bwd_kernel<false>), dim3(blocks), dim3(64), 0, h->stream, A);
+    CCX_HIP(hipGetLastError());
+    return CCX_OK;
+}
+
+}  // extern "C"

@@ -1045,6 +1045,101 @@ int ccx_sides_backward(ccx_handle* h, int64_t M, int32_t N, uint64_t slots, int3
                        const float* w2 /* [O][H] */, void* workspace, float* grad_w1t /* [L][H] */, float* grad_b1 /* [H] */,
                        float* grad_w2 /* [O][H] */, float* grad_b2 /* [O] */, float* grad_a_or_null /* [M][N][H] */);
 /*
+ * CCX_QLEARN: the two links a Q-learning iteration needs beside the heads, the optimiser and the rollout -- epsilon-greedy
+ * actions over the legal set from a network's Q-values (the actor loop), and the double-DQN TD error with its Huber loss, its
+ * means over the rows that count and its gradient with respect to the Q-values (the update).  Q-values are the [..][5]
+ * outputs of CCX_MLP / CCX_SIDES (index = action id), the online and the target network being two sets of parameters.  Every
+ * output is bit-defined, the reduction included.  The discipline is CCX_SAMPLE's and CCX_PPO_LOSS's: every f32 operation
+ * named below is ONE correctly rounded f32 operation (+ - * /), nothing is fused (no fma), nothing is reassociated,
+ * subnormals are kept; every f64 operation likewise.  What a rule does not read is SELECTED away, never multiplied by zero.
+ *
+ * greedy(v, m), the ONE argmax of this section, over five values v_k and a legal set m (bit k set = legal, bit 4 always):
+ *     kg = the lowest legal k;  mx = -inf;  for legal k ascending: if (v_k > mx) { mx = v_k; kg = k; }
+ * A NaN never wins (the comparison is false); a row of NaNs (or of -inf) gives the lowest legal k; ties go to the lowest
+ * index; a value at an illegal k reaches no result.
+ *
+ * ccx_q_actions.  Inputs (device pointers): q f32 [E][N][5] (16-byte aligned), masks u8 [E][N] or NULL (the bytes of
+ * CCX_ACTION_MASKS; NULL = everything legal), epsilon f32 [1] ON THE DEVICE or NULL (NULL = greedy: nothing is drawn and
+ * neither step_count nor episode is read).  Outputs: actions u8 [E][N], explored u8 [E][N] or NULL; every element of every
+ * output given is written.  The rate is a device scalar so that an annealed rate changes between the replays of a captured
+ * actor loop without a re-capture.  For every slot (e, a) on its own, with the key (g, j, t, a) of CCX_SAMPLE step 7
+ * (g = env_offset + e, j = episode[e], t = step_count[e]) and eps = epsilon[0]:
+ *   1. dead slot (terminated[e][a] or truncated[e][a]): actions = CCX_ACTION_ABSENT, explored = 0; its Q-values and its mask
+ *      byte reach no result.
+ *   2. m = the legal set of CCX_SAMPLE step 2: ((masks ? masks[e][a] : 0x1F) & 0x1F) | 0x10.  Wait is always legal.
+ *   3. kg = greedy(q[e][a], m).
+ *   4. only with epsilon given: u1 = word(seed_lo, seed_hi ^ 0x68E31DA4; g, j, t, a);  r = (float)(u1 >> 8) * 0x1p-24f
+ *      (exact, in [0, 1));  the slot explores iff r < eps.  By the comparison alone: a NaN eps never explores, eps <= 0 never
+ *      does, eps >= 1 always does.
+ *   5. u2 = word(seed_lo, seed_hi ^ 0xB5297A4D; g, j, t, a);  n = popcount(m);  idx = (u32)(((u64)u2 * n) >> 32);  choice =
+ *      the idx-th legal k, ascending from idx = 0: uniform over the legal set, with a bias of at most n / 2^32.
+ *   6. actions = explores ? choice : kg;  explored = explores ? 1 : 0 (0 in every slot when epsilon is NULL).
+ * The two stream constants differ from each other, from 0 (CCX_POLICY_RANDOM), from 0x5BD1E995 (the scripted policies'
+ * epsilon) and from 0x2545F491 (CCX_SAMPLE): the four draws of a slot are four words.  As in CCX_SAMPLE the actions are the
+ * same for any split of a run into calls, any world size, eager or captured.
+ *
+ * ccx_td_loss / ccx_td_loss_backward.  Pure functions of their arrays: the handle supplies device and stream only.  Rows are
+ * flat: M >= 1.  Inputs (device pointers): q f32 [M][5] (the online network at the state), actions u8 [M], reward f64 [M] (the
+ * rollout's own), done u8 [M] (not zero: the step ended the agent's episode by termination, nothing is bootstrapped),
+ * q_next_target f32 [M][5] (the target network at the next state), q_next_online f32 [M][5] or NULL (the online network at
+ * the next state: double-Q; NULL: the target network chooses its own action), masks_next u8 [M] or NULL (the legal set of
+ * the next state), valid u8 [M] or NULL, weights f32 [M] or NULL (importance weights of a prioritised replay), and by value
+ * gamma in [0, 1] and huber_delta > 0 (+inf allowed: the squared error).  The three Q arrays are 16-byte aligned.
+ * Per row i, with a = actions[i] and c = 0.5f * huber_delta computed once:
+ *   1. the row counts iff (valid == NULL || valid[i] != 0) && a <= 4.  A row with (valid == NULL || valid[i] != 0) and a in
+ *      5..254 does not count and is tallied in stats[7] (bad): a corrupt action is visible and poisons no mean.  a == 255
+ *      (an absent agent) and valid[i] == 0 are the ordinary ways not to count.  A row that does not count contributes to no
+ *      sum and gets +0.0f in td_error and in every gradient, whatever its inputs hold (NaN included).
+ *   2. qa = q[i][a], selected.
+ *   3. m' = CCX_SAMPLE step 2 on masks_next;  k* = greedy(q_next_online ? q_next_online[i] : q_next_target[i], m');
+ *      boot = q_next_target[i][k*], selected.
+ *   4. r = (float)reward[i] (one rounding, as CCX_GAE does it);  nb = (done[i] || gamma == 0.0f) ? +0.0f : gamma * boot
+ *      (selected: a NaN in a terminal row's next-Q stays there, and gamma = 0 reads no next-state array into a result);
+ *      y = r + nb.
+ *   5. d = qa - y;  ad = |d|;  h = (ad <= huber_delta) ? 0.5f * (d * d) : huber_delta * (ad - c)  (two operations in either
+ *      branch);  term = weights ? weights[i] * h : h.
+ * Reduction: six sums over the rows -- 1 (the count n), term, ad, qa, y over the rows that count, and 1 over the bad rows --
+ * in f64, each f32 term converted exactly, by the tree of CCX_PPO_LOSS, unchanged (blocks of 256 rows, groups of 64 by
+ * halving, ((G0 + G1) + G2) + G3, the final wave).  Final values, in f64, each output rounded to f32 once:
+ *     stats = {S_term / n, S_ad / n, S_qa / n, S_y / n, +0.0f, +0.0f, (float)n, (float)bad};  n == 0: the first six are +0.0f
+ *     td_error[i] = counts ? d : +0.0f                           (written where td_error is given)
+ * Backward: one elementwise pass that recomputes steps 1-5 from the same inputs; nothing is saved but the inputs and stats.
+ * g = grad_loss ? grad_loss[0] : 1.0f;  sc = g / stats[6], computed once;  gw = weights ? sc * weights[i] : sc;
+ *     dd = (ad <= huber_delta || d is NaN) ? d : (d < 0 ? -huber_delta : huber_delta)        (a NaN goes through loudly)
+ *     grad_q[i][k] = (counts && k == a) ? gw * dd : +0.0f
+ * Every element of grad_q (16-byte aligned) is written; rows that do not count, and stats[6] == 0, give exactly +0.0f
+ * whatever the inputs hold.  No gradient reaches the next-state arrays: the target is a constant.
+ *
+ * Against IEEE f64 (measured on the CPU, tests/test_qlearn_spec.py, maxima doubled), as max |err| / max(1, |f64 value|)
+ * against the textbook composition in torch f64 on the same f32 inputs (masked argmax, gather, where(done), Huber, mean
+ * over the rows that count, autograd): loss within 1.1e-7, mean |td| within 9.9e-8, grad_q (times n) within 1.1e-6 (rows whose |d| lies within 1e-6 of
+ * huber_delta, where the two sides may sit on different branches of the derivative, are left out: under 10 %, asserted).
+ *
+ * Launches: ccx_q_actions enqueues ONE kernel on the handle's stream, ccx_td_loss TWO (block partials, then one final
+ * wave; no atomic, no last-block-done counter), ccx_td_loss_backward ONE.  No host synchronisation, no allocation: the
+ * caller owns the workspace (ccx_td_workspace_bytes(rows) bytes, 8-byte aligned; 0 for rows < 1).  Everything captures into
+ * a HIP graph.  Offsets are 64-bit.  A NULL handle or a NULL required pointer, rows < 1 (or so many that a grid would pass
+ * 2^31 - 1 workgroups), a Q array or grad_q that is not 16-byte aligned, a workspace that is not 8-byte aligned, a gamma that
+ * is not finite or lies outside [0, 1], a huber_delta that is not > 0: CCX_EINVAL with a ccx_last_error message, before any
+ * launch.  Not here: a dueling combine, n-step targets, distributional heads, a replay buffer or prioritised sampling
+ * (weights and td_error are its two hooks), the fusion of the head's forward with the action choice, bf16 / f16.
+ */
+int ccx_q_actions(ccx_handle* h, const float* q /* [E][N][5] */, const uint8_t* masks_or_null /* [E][N] */,
+                  const float* epsilon_or_null /* device f32 [1]; NULL = greedy */, uint8_t* actions /* [E][N] */,
+                  uint8_t* explored_or_null /* [E][N] */);
+int64_t ccx_td_workspace_bytes(int64_t rows);
+int ccx_td_loss(ccx_handle* h, int64_t rows, const float* q /* [M][5] */, const uint8_t* actions /* [M] */,
+                const double* reward /* [M] */, const uint8_t* done /* [M] */, const float* q_next_target /* [M][5] */,
+                const float* q_next_online_or_null /* [M][5] */, const uint8_t* masks_next_or_null /* [M] */,
+                const uint8_t* valid_or_null /* [M] */, const float* weights_or_null /* [M] */, float gamma, float huber_delta,
+                void* workspace, float* stats /* [8] */, float* td_error_or_null /* [M] */);
+int ccx_td_loss_backward(ccx_handle* h, int64_t rows, const float* q /* [M][5] */, const uint8_t* actions /* [M] */,
+                         const double* reward /* [M] */, const uint8_t* done /* [M] */, const float* q_next_target /* [M][5] */,
+                         const float* q_next_online_or_null /* [M][5] */, const uint8_t* masks_next_or_null /* [M] */,
+                         const uint8_t* valid_or_null /* [M] */, const float* weights_or_null /* [M] */, float gamma,
+                         float huber_delta, const float* stats /* [8] */, const float* grad_loss_or_null /* [1] */,
+                         float* grad_q /* [M][5] */);
+/*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
  * `rng_seed` of ccx_rollout).  The action of agent slot a of global env g at step t (0-based) of its episode j is
