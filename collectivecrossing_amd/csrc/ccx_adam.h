@@ -1,16 +1,16 @@
 // ccx_adam.h -- CCX_ADAM (include/ccx.h) as inline functions: where a block of the padded sequence lies, the per-call
 // scalars with the state advance (norm, skip, clip scale, bias corrections), and the per-element update.  The pieces of the
-// f64 tree are ccx_ppo.h's halve64 / block_partial / strided_partials, called, not restated.  Included by ccx_adam.hip; it
+// f64 tree are ccx_tree.h's, called, not restated.  Included by ccx_adam.hip; it
 // also compiles with a plain host C++ compiler (tests/test_adam_host_rule.py runs it against the NumPy spec bit for bit).
 // The discipline is ccx_softmax.h's: every line is ONE operation of the stated type, the including units are compiled with
 // -ffp-contract=off, `/` and sqrt are the correctly rounded ones, and a choice is a select, never a multiplication by zero.
 #pragma once
-#include "ccx_ppo.h"
+#include "ccx_tree.h"
 
 namespace ccx_adam {
 
 constexpr int kMaxTensors = 32;                                           // CCX_ADAM_MAX_TENSORS
-constexpr int kBlockPlaces = ccx_ppo::kBlockRows;                         // a block of the sequence: 256 places of ONE tensor
+constexpr int kBlockPlaces = ccx_tree::kBlockRows;                         // a block of the sequence: 256 places of ONE tensor
 constexpr float kNormEps = 1e-6f;                                         // den = gn + 1e-6f
 
 // one row of the table: ccx_adam_tensor's layout (40 bytes)
@@ -39,7 +39,7 @@ struct Scalars {
 constexpr long long kScalarBytes = (long long)sizeof(Scalars);
 
 // blocks of one tensor: each tensor is padded to a multiple of 256 places
-CCX_HD long long blocks_of(long long numel) { return ccx_ppo::blocks_of(numel); }
+CCX_HD long long blocks_of(long long numel) { return ccx_tree::blocks_of(numel); }
 
 // B of the whole table
 CCX_HD long long total_blocks(const Tensor* tab, int T) {

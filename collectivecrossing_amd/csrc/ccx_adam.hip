@@ -1,6 +1,6 @@
 // ccx_adam.hip -- CCX_ADAM (include/ccx.h): one optimiser step over up to 32 f32 tensors -- the global gradient norm by
 // CCX_PPO_LOSS's fixed f64 tree, the clip scale, and Adam with decoupled weight decay, the step counter and the running
-// bias-correction products in 64 bytes of device memory.  The rule is ccx_adam.h (which calls ccx_ppo.h's tree pieces).
+// bias-correction products in 64 bytes of device memory.  The rule is ccx_adam.h; the tree is ccx_tree.h's.
 //
 // Three plain launches on the handle's stream:
 //   adam_partial_kernel   one workgroup of four waves per block of the padded sequence (256 places of ONE tensor).  The block
@@ -43,16 +43,8 @@ struct AdamArgs {
     long long B;
 };
 
-// a group of the tree: for o = 32 .. 1 every lane takes s + (lane ^ o)'s s; f64 addition commutes, so all lanes agree
-__device__ __forceinline__ double halve_wave(double s) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s = s + __shfl_xor(s, o, 64);
-    return s;
-}
-
 __global__ __launch_bounds__(256) void adam_partial_kernel(const AdamArgs A) {
-    __shared__ double groups[ccx_ppo::kBlockGroups];
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    __shared__ double groups[ccx_tree::kBlockGroups];
     int t;
     long long bt;
     ccx_adam::locate(A.tab, A.T, (long long)blockIdx.x, t, bt);
@@ -61,18 +53,12 @@ __global__ __launch_bounds__(256) void adam_partial_kernel(const AdamArgs A) {
     const long long place = bt * ccx_adam::kBlockPlaces + threadIdx.x;
     const bool exists = place < numel;
     const float g = grad[exists ? place : numel - 1];                   // surplus threads load what the last place loads
-    const double s = halve_wave(ccx_adam::square_term(exists, g));
-    if (lane == 0u) groups[w] = s;
-    __syncthreads();
-    if (threadIdx.x == 0u) A.partials[blockIdx.x] = ccx_ppo::block_partial(groups[0], groups[1], groups[2], groups[3]);
+    ccx_tree::block_sums(ccx_adam::square_term(exists, g), groups, A.partials);
 }
 
 __global__ __launch_bounds__(64) void adam_final_kernel(const AdamArgs A) {
-    const int lane = (int)threadIdx.x;
-    double s[1];
-    ccx_ppo::strided_partials<1>(A.partials, A.B, lane, s);
-    const double S = halve_wave(s[0]);
-    if (lane == 0) {
+    const double S = ccx_tree::final_sums(A.partials, A.B);
+    if (threadIdx.x == 0u) {
         const float lr = A.lr_dev ? A.lr_dev[0] : A.lr;
         ccx_adam::State st = *A.state;
         ccx_adam::Scalars sc{};

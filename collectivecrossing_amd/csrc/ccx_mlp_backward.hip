@@ -1,6 +1,6 @@
 // ccx_mlp_backward.hip -- the backward pass of CCX_MLP (include/ccx.h): the gradients of the four parameter arrays from the
 // rows, the saved activations and the gradient of the outputs, by a written rule.  The per-row f32 part, the terms of the
-// f64 chains and the final step are ccx_mlp_grad.h (which calls ccx_ppo.h's final step).
+// f64 chains are ccx_mlp_grad.h; the final step over the block partials is ccx_tree.h's.
 //
 // Two launches.  head_grad_blocks_kernel: workgroup (b, s) takes block b of 256 consecutive rows and slice s of the output
 // elements.  The elements are cut into 4 x 4 tiles, one tile per thread, 256 tiles per slice: the tiles of
@@ -14,8 +14,8 @@
 // conversions, sixteen f64 multiply-adds per row.  A thread owns its elements and walks the rows, so the chain of the rule
 // is the loop itself and nothing crosses lanes.  Rows >= M are never walked.  The partial of element e lands at
 // partials[e][b].
-// head_grad_final_kernel: one wave per element; lane j is place j of ccx_ppo.h's final step (contiguous, coalesced reads of
-// the element's B partials), the 64 places are halved by the butterfly of ccx_ppo_loss.hip, lane 0 rounds to f32 once and
+// head_grad_final_kernel: one wave per element; lane j is place j of ccx_tree.h's final step (contiguous, coalesced reads of
+// the element's B partials), the 64 places are halved by ccx_tree.h's butterfly, lane 0 rounds to f32 once and
 // stores.  No atomic, no last-block-done counter: a kernel boundary orders the partials.
 //
 // CCX_SIDES (ccx_sides_backward): the same two launches over the SELECTED rows of one slot group of [M][N][..] arrays
@@ -69,13 +69,6 @@ __host__ __device__ inline RowImage row_image(int L, int H, int O) {
 // a quad of the LDS image: every part of a row starts at a multiple of four floats and so does the row stride, which the
 // compiler cannot see from the run-time sizes
 __device__ __forceinline__ float4* quad(float* p) { return static_cast<float4*>(__builtin_assume_aligned(p, 16)); }
-
-// the same butterfly as ccx_ppo_loss.hip's: for o = 32 .. 1 every lane takes s + (lane ^ o)'s s
-__device__ __forceinline__ double halve_wave(double s) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s = s + __shfl_xor(s, o, 64);
-    return s;
-}
 
 // Where the rows of a sub-tile lie.  AdjacentRows: rows rs .. rs + nr - 1 of [rows][..] arrays.
 struct AdjacentRows {
@@ -257,7 +250,9 @@ __global__ __launch_bounds__(kThreads) void head_grad_final_kernel(const HeadGra
     const long long e = (long long)blockIdx.x * (kThreads / 64) + (long long)(threadIdx.x >> 6);
     const int L = A.L, H = A.H, O = A.O;
     if (e >= mg::elements_of(L, H, O)) return;                           // (whole waves: e is the same for a wave's lanes)
-    const double s = halve_wave(mg::final_place(A.partials + e * A.B, A.B, lane));
+    double place[1];
+    ccx_tree::strided_partials<1>(A.partials + e * A.B, A.B, lane, place);
+    const double s = ccx_tree::halve_wave(place[0]);
     if (lane != 0) return;
     const float v = (float)s;
     long long i;

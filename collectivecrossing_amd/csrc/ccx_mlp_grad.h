@@ -1,17 +1,17 @@
 // ccx_mlp_grad.h -- the backward rule of CCX_MLP (include/ccx.h) as inline functions: the per-row f32 part (gh, ga), one
 // term of a block's f64 chain, the place of every output element in the workspace, and the final step over the block
-// partials, which is ccx_ppo.h's (strided_partials, then the halving): the project keeps one tree.  Included by
+// partials, which is ccx_tree.h's (strided_partials, then the halving): the project keeps one tree.  Included by
 // ccx_mlp_backward.hip, whose kernels inline exactly these functions; it also compiles with a plain host C++ compiler
 // (tests/test_mlp_backward_host_rule.py runs backward_host against the NumPy spec bit for bit).
-// The discipline is ccx_mlp.h's and ccx_ppo.h's: every line is ONE operation of the stated type, and the including units are
+// The discipline is ccx_mlp.h's and ccx_tree.h's: every line is ONE operation of the stated type, and the including units are
 // compiled with -ffp-contract=off.
 #pragma once
 #include "ccx_mlp.h"
-#include "ccx_ppo.h"
+#include "ccx_tree.h"
 
 namespace ccx_mlp_grad {
 
-constexpr int kBlockRows = ccx_ppo::kBlockRows;                          // 256 consecutive rows to a block partial
+constexpr int kBlockRows = ccx_tree::kBlockRows;                          // 256 consecutive rows to a block partial
 constexpr int kTile = 4;                                                 // a thread's register tile: 4 x 4 output elements
 
 // The output elements of one call in the order of the workspace: the (L + 1) x H elements of [x | 1]^T ga -- grad_w1t [L][H],
@@ -32,7 +32,7 @@ CCX_HD int place_of(long long e, int L, int H, long long& index) {
 // B x elements doubles ([element][B]); 0 for rows < 1 or a shape outside CCX_MLP's limits (the activation is not a size)
 CCX_HD long long workspace_bytes(long long rows, int L, int H, int O) {
     if (rows < 1 || !ccx_mlp::shape_ok(L, H, O, ccx_mlp::kTanh)) return 0;
-    return ccx_ppo::blocks_of(rows) * elements_of(L, H, O) * (long long)sizeof(double);
+    return ccx_tree::blocks_of(rows) * elements_of(L, H, O) * (long long)sizeof(double);
 }
 
 // step 1 for one hidden unit: gy the row's O gradients, w = &w2[0][j], stride = H
@@ -71,18 +71,11 @@ CCX_HD void tile_row(double (&acc)[kTile][kTile], const float (&a)[kTile], const
     }
 }
 
-// place j of the final step for one element: P points at the element's B partials
-CCX_HD double final_place(const double* P, long long B, int j) {
-    double acc[1];
-    ccx_ppo::strided_partials<1>(P, B, j, acc);
-    return acc[0];
-}
-
 // ---- the whole rule on the host, one addition at a time.  ws: workspace_bytes(...) bytes; ga: [rows][H] scratch or output.
 inline void backward_host(long long rows, int L, int H, int O, int activation, const float* x, const float* hidden,
                           const float* grad_y, const float* w2, double* ws, float* grad_w1t, float* grad_b1, float* grad_w2,
                           float* grad_b2, float* ga) {
-    const long long B = ccx_ppo::blocks_of(rows), NE = elements_of(L, H, O);
+    const long long B = ccx_tree::blocks_of(rows), NE = elements_of(L, H, O);
     for (long long r = 0; r < rows; ++r)
         for (int j = 0; j < H; ++j)
             ga[r * H + j] = ga_unit(activation, gh_unit(O, grad_y + r * O, w2 + j, H), hidden[r * H + j]);
@@ -102,9 +95,7 @@ inline void backward_host(long long rows, int L, int H, int O, int activation, c
         }
     }
     for (long long e = 0; e < NE; ++e) {
-        double places[64];
-        for (int j = 0; j < 64; ++j) places[j] = final_place(ws + e * B, B, j);
-        const float v = (float)ccx_ppo::halve64(places);
+        const float v = (float)ccx_tree::final_host(ws + e * B, B);
         long long i;
         const int which = place_of(e, L, H, i);
         (which == 0 ? grad_w1t : which == 1 ? grad_b1 : which == 2 ? grad_w2 : grad_b2)[i] = v;

@@ -1,22 +1,20 @@
 // ccx_ppo.h -- CCX_PPO_LOSS (include/ccx.h) as inline functions: which rows count, the per-row forward terms and gradients
-// (built on ccx_softmax.h's evaluate_row / evaluate_row_backward, which are called, not restated), the pieces of the fixed
-// f64 reduction tree, and the final values of the loss and of the masked moments.  Included by ccx_ppo_loss.hip; it also
-// compiles with a plain host C++ compiler (tests/test_ppo_loss_host_rule.py runs it against the NumPy spec bit for bit).
+// (built on ccx_softmax.h's evaluate_row / evaluate_row_backward, which are called, not restated), and the final values of
+// the loss and of the masked moments.  The sums between the two go through ccx_tree.h's fixed f64 reduction tree.  Included
+// by ccx_ppo_loss.hip; it also compiles with a plain host C++ compiler (tests/test_ppo_loss_host_rule.py runs it against the
+// NumPy spec bit for bit).
 // The discipline is ccx_softmax.h's: every line is ONE operation of the stated type, the including units are compiled with
 // -ffp-contract=off, `/` and sqrt are the correctly rounded ones, and what a rule does not read is SELECTED away before any
 // arithmetic, never multiplied by zero.
 #pragma once
 #include "ccx_softmax.h"
+#include "ccx_tree.h"
 
 namespace ccx_ppo {
 
 constexpr float kXMax = 80.0f;                                            // |logp - logp_old| is clamped here: exp_spec's domain
-constexpr int kGroupRows = 64, kBlockGroups = 4, kBlockRows = kGroupRows * kBlockGroups;
 constexpr int kSums = 6;                                                  // count, surr, vl, H, kl, cf
 constexpr int kMomentSums = 3;                                            // count, x, x * x
-
-// number of block partials per quantity, B = ceil(M / 256)
-CCX_HD long long blocks_of(long long M) { return (M + (kBlockRows - 1)) / kBlockRows; }
 
 CCX_HD bool row_counts(bool has_valid, uint32_t vbyte, uint32_t a) {
     return (!has_valid || vbyte != 0u) && a != ccx_softmax::kActionAbsent;
@@ -74,35 +72,6 @@ CCX_HD float backward_row_value(float ret, float val, float scv) {
     const float ve = val - ret;
     const float two = ve + ve;
     return scv * two;
-}
-
-// ---- the tree.  A group of 64 consecutive rows is reduced by halving: for o = 32, 16, 8, 4, 2, 1 every place j takes
-// s[j] + s[j ^ o] (on the device a wave butterfly; here the array form for the host).  Every place ends with the same bits.
-inline double halve64(const double* v) {
-    double s[64], t[64];
-    for (int j = 0; j < 64; ++j) s[j] = v[j];
-    for (int o = 32; o >= 1; o >>= 1) {
-        for (int j = 0; j < 64; ++j) t[j] = s[j] + s[j ^ o];
-        for (int j = 0; j < 64; ++j) s[j] = t[j];
-    }
-    return s[0];
-}
-
-// a block of 256 consecutive rows from its four groups
-CCX_HD double block_partial(double g0, double g1, double g2, double g3) { return ((g0 + g1) + g2) + g3; }
-
-// place j of the final wave, NQ quantities at once (P = [NQ][B]): per quantity P[j], P[j + 64], ... in ascending order onto
-// +0.0.  (One loop for all quantities, unrolled: the loads of several rounds are in flight together; the additions of a
-// quantity keep their order.)
-template <int NQ>
-CCX_HD void strided_partials(const double* P, long long B, int j, double (&acc)[NQ]) {
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) acc[q] = 0.0;
-#pragma unroll 4
-    for (long long i = j; i < B; i += 64) {
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) acc[q] = acc[q] + P[(long long)q * B + i];
-    }
 }
 
 // ---- final values.  S = the six sums (count, surr, vl, H, kl, cf); all arithmetic f64, each output rounded to f32 once.

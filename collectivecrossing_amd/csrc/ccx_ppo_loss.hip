@@ -1,6 +1,6 @@
 // ccx_ppo_loss.hip -- CCX_PPO_LOSS (include/ccx.h): the clipped-surrogate PPO loss over the rows that count, its statistics
 // and its gradient with respect to logits and values, plus the masked moments that normalise the advantages.  The per-row
-// rule, the pieces of the reduction tree and the final values are ccx_ppo.h (which calls ccx_softmax.h's evaluate_row*); the
+// rule and the final values are ccx_ppo.h (which calls ccx_softmax.h's evaluate_row*), the reduction tree is ccx_tree.h; the
 // logits travel through LDS by ccx_rows.h.  `valid` is a selection inside the kernels: shapes stay static, nothing is
 // compacted, nothing synchronises with the host.
 //
@@ -48,19 +48,12 @@ struct MomentArgs {
     long long M, B;
 };
 
-// a group of the tree: for o = 32 .. 1 every lane takes s + (lane ^ o)'s s; f64 addition commutes, so all lanes agree
-__device__ __forceinline__ double halve_wave(double s) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s = s + __shfl_xor(s, o, 64);
-    return s;
-}
-
 template <bool MASK>
 __global__ __launch_bounds__(256) void ppo_partial_kernel(const PpoArgs A) {
-    __shared__ float4 pieces[ccx_ppo::kBlockGroups][80];
-    __shared__ double groups[ccx_ppo::kSums][ccx_ppo::kBlockGroups];
+    __shared__ float4 pieces[ccx_tree::kBlockGroups][80];
+    __shared__ double groups[ccx_ppo::kSums][ccx_tree::kBlockGroups];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const long long wave = (long long)blockIdx.x * ccx_ppo::kBlockGroups + w;
+    const long long wave = (long long)blockIdx.x * ccx_tree::kBlockGroups + w;
     const long long row = wave * 64 + lane;
     const long long rl = row < A.M ? row : A.M - 1;                     // surplus lanes load what the last row loads
     const uint32_t a = A.actions[rl];
@@ -83,25 +76,13 @@ __global__ __launch_bounds__(256) void ppo_partial_kernel(const PpoArgs A) {
     // rows that do not count and rows >= M enter as +0.0, selected
     double s[ccx_ppo::kSums] = {counts ? 1.0 : 0.0,           counts ? (double)t.surr : 0.0, counts ? (double)t.vl : 0.0,
                                 counts ? (double)t.H : 0.0,   counts ? (double)t.kl : 0.0,   counts ? (double)t.cf : 0.0};
-#pragma unroll
-    for (int q = 0; q < ccx_ppo::kSums; ++q) {
-        s[q] = halve_wave(s[q]);
-        if (lane == 0u) groups[q][w] = s[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)ccx_ppo::kSums) {
-        const uint32_t q = threadIdx.x;
-        A.partials[(long long)q * A.B + blockIdx.x] = ccx_ppo::block_partial(groups[q][0], groups[q][1], groups[q][2], groups[q][3]);
-    }
+    ccx_tree::block_sums(s, groups, A.partials, A.B);
 }
 
 __global__ __launch_bounds__(64) void ppo_final_kernel(const PpoArgs A) {
-    const int lane = (int)threadIdx.x;
     double s[ccx_ppo::kSums];
-    ccx_ppo::strided_partials(A.partials, A.B, lane, s);
-#pragma unroll
-    for (int q = 0; q < ccx_ppo::kSums; ++q) s[q] = halve_wave(s[q]);
-    if (lane == 0) {
+    ccx_tree::final_sums(A.partials, A.B, s);
+    if (threadIdx.x == 0u) {
         float st[8];
         ccx_ppo::loss_finals(s, A.vf_coef, A.ent_coef, st);
 #pragma unroll
@@ -151,33 +132,20 @@ __global__ __launch_bounds__(64) void ppo_bwd_kernel(const PpoArgs A) {
 }
 
 __global__ __launch_bounds__(256) void moments_partial_kernel(const MomentArgs A) {
-    __shared__ double groups[ccx_ppo::kMomentSums][ccx_ppo::kBlockGroups];
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const long long row = (long long)blockIdx.x * ccx_ppo::kBlockRows + threadIdx.x;
+    __shared__ double groups[ccx_ppo::kMomentSums][ccx_tree::kBlockGroups];
+    const long long row = (long long)blockIdx.x * ccx_tree::kBlockRows + threadIdx.x;
     const long long rl = row < A.M ? row : A.M - 1;
     const bool counts = row < A.M && (A.valid == nullptr || A.valid[rl] != 0);
     const double x = (double)A.x[rl];                                   // exact
     const double xx = x * x;                                            // exact: 48 significant bits at most
     double s[ccx_ppo::kMomentSums] = {counts ? 1.0 : 0.0, counts ? x : 0.0, counts ? xx : 0.0};
-#pragma unroll
-    for (int q = 0; q < ccx_ppo::kMomentSums; ++q) {
-        s[q] = halve_wave(s[q]);
-        if (lane == 0u) groups[q][w] = s[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)ccx_ppo::kMomentSums) {
-        const uint32_t q = threadIdx.x;
-        A.partials[(long long)q * A.B + blockIdx.x] = ccx_ppo::block_partial(groups[q][0], groups[q][1], groups[q][2], groups[q][3]);
-    }
+    ccx_tree::block_sums(s, groups, A.partials, A.B);
 }
 
 __global__ __launch_bounds__(64) void moments_final_kernel(const MomentArgs A) {
-    const int lane = (int)threadIdx.x;
     double s[ccx_ppo::kMomentSums];
-    ccx_ppo::strided_partials(A.partials, A.B, lane, s);
-#pragma unroll
-    for (int q = 0; q < ccx_ppo::kMomentSums; ++q) s[q] = halve_wave(s[q]);
-    if (lane == 0) {
+    ccx_tree::final_sums(A.partials, A.B, s);
+    if (threadIdx.x == 0u) {
         float o[4];
         ccx_ppo::moments_finals(s, o);
 #pragma unroll
@@ -209,14 +177,14 @@ extern "C" {
 
 int64_t ccx_ppo_workspace_bytes(int64_t rows) {
     if (rows < 1) return 0;
-    return (int64_t)ccx_ppo::blocks_of(rows) * ccx_ppo::kSums * (int64_t)sizeof(double);
+    return (int64_t)ccx_tree::blocks_of(rows) * ccx_ppo::kSums * (int64_t)sizeof(double);
 }
 
 int ccx_masked_moments(ccx_handle* h, int64_t rows, const float* x, const uint8_t* valid_or_null, void* workspace, float* out) {
     if (!h) return fail(CCX_EINVAL, "NULL handle");
     if (!x || !workspace || !out) return fail(CCX_EINVAL, "ccx_masked_moments: NULL argument (x, workspace and out are required)");
     unsigned blocks = 0;
-    if (int rc = ccxi::row_blocks("ccx_masked_moments", rows, ccx_ppo::kBlockRows, blocks)) return rc;
+    if (int rc = ccxi::row_blocks("ccx_masked_moments", rows, ccx_tree::kBlockRows, blocks)) return rc;
     if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "ccx_masked_moments: workspace must be 8-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     MomentArgs A{};
@@ -240,7 +208,7 @@ int ccx_ppo_loss(ccx_handle* h, int64_t rows, const float* logits, const uint8_t
     if (!logits || !actions || !logp_old || !advantages || !returns || !values || !workspace || !stats)
         return fail(CCX_EINVAL, "ccx_ppo_loss: NULL argument (only masks, valid and norm may be NULL)");
     unsigned blocks = 0;
-    if (int rc = ccxi::row_blocks("ccx_ppo_loss", rows, ccx_ppo::kBlockRows, blocks)) return rc;
+    if (int rc = ccxi::row_blocks("ccx_ppo_loss", rows, ccx_tree::kBlockRows, blocks)) return rc;
     if (reinterpret_cast<uintptr_t>(logits) & 15u) return fail(CCX_EINVAL, "ccx_ppo_loss: logits must be 16-byte aligned");
     if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "ccx_ppo_loss: workspace must be 8-byte aligned");
     if (int rc = check_hyper("ccx_ppo_loss", clip, vf_coef, ent_coef, adv_eps)) return rc;

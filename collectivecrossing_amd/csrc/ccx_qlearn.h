@@ -1,13 +1,14 @@
 // ccx_qlearn.h -- CCX_QLEARN (include/ccx.h) as inline functions: the greedy action over a legal set (ONE function, shared by
 // the actor's epsilon-greedy choice and the bootstrap action of the TD target), the exploration draw and the uniform choice
 // over the legal set, the per-row TD terms (taken Q-value, target, Huber), the per-row gradient, and the final values.  The
-// reduction tree is ccx_ppo.h's, called, not restated.  Included by ccx_qlearn.hip; it also compiles with a plain host C++
+// reduction tree is ccx_tree.h's, called, not restated.  Included by ccx_qlearn.hip; it also compiles with a plain host C++
 // compiler (tests/test_qlearn_host_rule.py runs it against the NumPy spec bit for bit).
 // The discipline is ccx_softmax.h's: every line is ONE operation of the stated type, the including units are compiled with
 // -ffp-contract=off, `/` is the correctly rounded division, and what a rule does not read is SELECTED away before any
 // arithmetic, never multiplied by zero.
 #pragma once
-#include "ccx_ppo.h"
+#include "ccx_softmax.h"
+#include "ccx_tree.h"
 
 namespace ccx_qlearn {
 

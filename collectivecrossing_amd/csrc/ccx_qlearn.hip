@@ -1,6 +1,6 @@
 // ccx_qlearn.hip -- CCX_QLEARN (include/ccx.h): epsilon-greedy actions over the legal set from a network's Q-values, and the
 // double-DQN TD error with its Huber loss, its means over the rows that count and its gradient with respect to the Q-values.
-// The per-slot and per-row rules and the final values are ccx_qlearn.h; the tree is ccx_ppo.h's; the slot rule (which (e, a) a
+// The per-slot and per-row rules and the final values are ccx_qlearn.h; the tree is ccx_tree.h's; the slot rule (which (e, a) a
 // lane owns, its small loads, its key) is ccx_draw.h's; the rows of five f32 travel through LDS by ccx_rows.h.
 //
 // q_act_kernel: ccx_sample.hip's shape.  One lane owns one slot, a workgroup is one wave; every load -- the small ones, the
@@ -89,19 +89,12 @@ __device__ __forceinline__ TdSmall td_small(const TdArgs& A, long long rl) {
     return v;
 }
 
-// a group of the tree: for o = 32 .. 1 every lane takes s + (lane ^ o)'s s; f64 addition commutes, so all lanes agree
-__device__ __forceinline__ double halve_wave(double s) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s = s + __shfl_xor(s, o, 64);
-    return s;
-}
-
 template <bool DOUBLE>
 __global__ __launch_bounds__(256) void td_partial_kernel(const TdArgs A) {
-    __shared__ float4 pieces[DOUBLE ? 3 : 2][ccx_ppo::kBlockGroups][80];
-    __shared__ double groups[ccx_qlearn::kSums][ccx_ppo::kBlockGroups];
+    __shared__ float4 pieces[DOUBLE ? 3 : 2][ccx_tree::kBlockGroups][80];
+    __shared__ double groups[ccx_qlearn::kSums][ccx_tree::kBlockGroups];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const long long wave = (long long)blockIdx.x * ccx_ppo::kBlockGroups + w;
+    const long long wave = (long long)blockIdx.x * ccx_tree::kBlockGroups + w;
     const long long row = wave * 64 + lane;
     const long long rl = row < A.M ? row : A.M - 1;
     const TdSmall v = td_small(A, rl);
@@ -119,25 +112,13 @@ __global__ __launch_bounds__(256) void td_partial_kernel(const TdArgs A) {
     // rows that do not count and rows >= M enter as +0.0, selected
     double s[ccx_qlearn::kSums] = {counts ? 1.0 : 0.0,           counts ? (double)t.term : 0.0, counts ? (double)t.ad : 0.0,
                                    counts ? (double)t.qa : 0.0,  counts ? (double)t.y : 0.0,    bad ? 1.0 : 0.0};
-#pragma unroll
-    for (int k = 0; k < ccx_qlearn::kSums; ++k) {
-        s[k] = halve_wave(s[k]);
-        if (lane == 0u) groups[k][w] = s[k];
-    }
-    __syncthreads();
-    if (threadIdx.x < (uint32_t)ccx_qlearn::kSums) {
-        const uint32_t k = threadIdx.x;
-        A.partials[(long long)k * A.B + blockIdx.x] = ccx_ppo::block_partial(groups[k][0], groups[k][1], groups[k][2], groups[k][3]);
-    }
+    ccx_tree::block_sums(s, groups, A.partials, A.B);
 }
 
 __global__ __launch_bounds__(64) void td_final_kernel(const TdArgs A) {
-    const int lane = (int)threadIdx.x;
     double s[ccx_qlearn::kSums];
-    ccx_ppo::strided_partials(A.partials, A.B, lane, s);
-#pragma unroll
-    for (int k = 0; k < ccx_qlearn::kSums; ++k) s[k] = halve_wave(s[k]);
-    if (lane == 0) {
+    ccx_tree::final_sums(A.partials, A.B, s);
+    if (threadIdx.x == 0u) {
         float st[8];
         ccx_qlearn::td_finals(s, st);
 #pragma unroll
@@ -226,7 +207,7 @@ int ccx_q_actions(ccx_handle* h, const float* q, const uint8_t* masks_or_null, c
 
 int64_t ccx_td_workspace_bytes(int64_t rows) {
     if (rows < 1) return 0;
-    return (int64_t)ccx_ppo::blocks_of(rows) * ccx_qlearn::kSums * (int64_t)sizeof(double);
+    return (int64_t)ccx_tree::blocks_of(rows) * ccx_qlearn::kSums * (int64_t)sizeof(double);
 }
 
 int ccx_td_loss(ccx_handle* h, int64_t rows, const float* q, const uint8_t* actions, const double* reward, const uint8_t* done,
@@ -237,7 +218,7 @@ int ccx_td_loss(ccx_handle* h, int64_t rows, const float* q, const uint8_t* acti
     if (!q || !actions || !reward || !done || !q_next_target || !workspace || !stats)
         return fail(CCX_EINVAL, "ccx_td_loss: NULL argument (only q_next_online, masks_next, valid, weights and td_error may be NULL)");
     unsigned blocks = 0;
-    if (int rc = ccxi::row_blocks("ccx_td_loss", rows, ccx_ppo::kBlockRows, blocks)) return rc;
+    if (int rc = ccxi::row_blocks("ccx_td_loss", rows, ccx_tree::kBlockRows, blocks)) return rc;
     if (int rc = check_td("ccx_td_loss", q, q_next_target, q_next_online_or_null, gamma, huber_delta)) return rc;
     if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "ccx_td_loss: workspace must be 8-byte aligned");
     CCX_HIP(hipSetDevice(h->device));

@@ -263,18 +263,21 @@ class LearnerOps:
                                         _ptr(head.w1t), _ptr(head.b1), _ptr(head.w2), _ptr(head.b2), _ptr(y), _ptr(hidden)))
         self._current_stream_waits(cur=cur)
 
-    def _mlp_backward_workspace(self, dims, rows: int, workspace: torch.Tensor | None) -> torch.Tensor:
-        """The workspace of a backward over ``rows`` rows: the caller's, checked, or one from torch's allocator (so a call
+    def _workspace_arg(self, need: int, workspace: torch.Tensor | None, alloc_name: str) -> torch.Tensor:
+        """The workspace of a call that needs ``need`` bytes: the caller's, checked, or one from torch's allocator (so a call
         inside a graph capture stays capturable)."""
-        need = int(self._lib.ccx_mlp_backward_workspace_bytes(int(rows), *dims[:3]))
         if workspace is None:
             return self._new((max(8, need),), torch.uint8)
         # (inline: a minimum length, not a shape, and the alignment is part of the one message)
         if (not isinstance(workspace, torch.Tensor) or workspace.dtype is not torch.uint8 or workspace.device != self.device
                 or workspace.dim() != 1 or workspace.numel() < need or not workspace.is_contiguous() or workspace.data_ptr() % 8):
             raise ValueError(f"workspace must be a contiguous, 8-byte aligned torch.uint8 tensor of at least {need} bytes on "
-                             f"{self.device} (alloc_mlp_backward)")
+                             f"{self.device} ({alloc_name})")
         return workspace
+
+    def _mlp_backward_workspace(self, dims, rows: int, workspace: torch.Tensor | None) -> torch.Tensor:
+        return self._workspace_arg(int(self._lib.ccx_mlp_backward_workspace_bytes(int(rows), *dims[:3])), workspace,
+                                   "alloc_mlp_backward")
 
     def _check_head(self, head) -> None:
         if not isinstance(head, MlpHead) or head.batch is not self:
@@ -471,9 +474,11 @@ class LearnerOps:
         return out
 
     # ------------------------------------------------------------------ the PPO loss over the rows that count
+    def _ppo_workspace_arg(self, workspace, rows: int) -> torch.Tensor:
+        return self._workspace_arg(int(self._lib.ccx_ppo_workspace_bytes(int(rows))), workspace, "alloc_ppo_loss")
+
     def _ppo_workspace(self, rows: int) -> torch.Tensor:
-        """A workspace from torch's allocator (so a call inside a graph capture stays capturable)."""
-        return self._new((max(8, int(self._lib.ccx_ppo_workspace_bytes(int(rows)))),), torch.uint8)
+        return self._ppo_workspace_arg(None, rows)
 
     def alloc_ppo_loss(self, shape, want_logits_grad: bool = True, want_values_grad: bool = True) -> PpoLossResult:
         """Static buffers of :meth:`ppo_loss` / :meth:`ppo_loss_backward` for rows of the leading shape ``shape``: stats,
@@ -532,17 +537,6 @@ class LearnerOps:
         check(self._lib.ccx_masked_moments(self._h, rows, _ptr(x), _ptr(valid), _ptr(workspace), _ptr(out)))
         self._current_stream_waits(cur=cur)
         return out
-
-    def _ppo_workspace_arg(self, workspace, rows: int) -> torch.Tensor:
-        if workspace is None:
-            return self._ppo_workspace(rows)
-        need = int(self._lib.ccx_ppo_workspace_bytes(int(rows)))
-        # (inline: a minimum length, not a shape, and the alignment is part of the one message)
-        if (not isinstance(workspace, torch.Tensor) or workspace.dtype is not torch.uint8 or workspace.device != self.device
-                or workspace.dim() != 1 or workspace.numel() < need or not workspace.is_contiguous() or workspace.data_ptr() % 8):
-            raise ValueError(f"workspace must be a contiguous, 8-byte aligned torch.uint8 tensor of at least {need} bytes on "
-                             f"{self.device} (alloc_ppo_loss)")
-        return workspace
 
     def _ppo_forward(self, logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper, workspace, stats):
         cur = self._order_after_current_stream(logits, values, actions, logp_old, advantages, returns, masks, valid, norm,

@@ -139,22 +139,12 @@ class QLearning:
         return out
 
     # ------------------------------------------------------------------ the TD loss over the rows that count
-    def _workspace(self, rows: int) -> torch.Tensor:
-        """A workspace from torch's allocator (so a call inside a graph capture stays capturable)."""
-        b = self.batch
-        return b._new((max(8, int(b._lib.ccx_td_workspace_bytes(int(rows)))),), torch.uint8)
-
     def _workspace_arg(self, workspace, rows: int) -> torch.Tensor:
-        if workspace is None:
-            return self._workspace(rows)
         b = self.batch
-        need = int(b._lib.ccx_td_workspace_bytes(int(rows)))
-        # (inline: a minimum length, not a shape, and the alignment is part of the one message)
-        if (not isinstance(workspace, torch.Tensor) or workspace.dtype is not torch.uint8 or workspace.device != b.device
-                or workspace.dim() != 1 or workspace.numel() < need or not workspace.is_contiguous() or workspace.data_ptr() % 8):
-            raise ValueError(f"workspace must be a contiguous, 8-byte aligned torch.uint8 tensor of at least {need} bytes on "
-                             f"{b.device} (alloc_td_loss)")
-        return workspace
+        return b._workspace_arg(int(b._lib.ccx_td_workspace_bytes(int(rows))), workspace, "alloc_td_loss")
+
+    def _workspace(self, rows: int) -> torch.Tensor:
+        return self._workspace_arg(None, rows)
 
     def alloc_td_loss(self, shape, want_td_error: bool = True) -> TdLossResult:
         """Static buffers of :meth:`td_loss` / :meth:`td_loss_backward` for rows of the leading shape ``shape``: stats, the

@@ -1,6 +1,6 @@
 // The rule of csrc/ccx_adam.h compiled for the host (tests/test_adam_host_rule.py: -O2 -ffp-contract=off), behind a C interface
-// for ctypes.  The loops here only walk blocks, groups and places in the order the header states; every arithmetic operation
-// is one of ccx_adam.h's or of ccx_ppo.h's tree pieces.
+// for ctypes.  The loops here only walk blocks and places in the order the header states; every arithmetic operation
+// is one of ccx_adam.h's or of ccx_tree.h's.
 #include <vector>
 
 #include "ccx_adam.h"
@@ -17,25 +17,15 @@ void host_adam_step(int T, const ccx_adam::Tensor* tab, float lr, const float* l
         int t;
         long long bt;
         ccx_adam::locate(tab, T, b, t, bt);
-        double G[4];
-        for (int g = 0; g < 4; ++g) {
-            double v[64];
-            for (int j = 0; j < 64; ++j) {
-                const long long place = bt * ccx_adam::kBlockPlaces + g * 64 + j;
-                const bool exists = place < tab[t].numel;
-                v[j] = ccx_adam::square_term(exists, tab[t].grad[exists ? place : tab[t].numel - 1]);
-            }
-            G[g] = ccx_ppo::halve64(v);
+        double v[ccx_adam::kBlockPlaces];
+        for (int j = 0; j < ccx_adam::kBlockPlaces; ++j) {
+            const long long place = bt * ccx_adam::kBlockPlaces + j;
+            const bool exists = place < tab[t].numel;
+            v[j] = ccx_adam::square_term(exists, tab[t].grad[exists ? place : tab[t].numel - 1]);
         }
-        P[b] = ccx_ppo::block_partial(G[0], G[1], G[2], G[3]);
+        P[b] = ccx_tree::block_host(v, ccx_adam::kBlockPlaces);
     }
-    double acc[64];
-    for (int j = 0; j < 64; ++j) {
-        double one[1];
-        ccx_ppo::strided_partials<1>(P.data(), B, j, one);
-        acc[j] = one[0];
-    }
-    const double S = ccx_ppo::halve64(acc);
+    const double S = ccx_tree::final_host(P.data(), B);
     // 2-4. the call's scalars and the state advance
     ccx_adam::Scalars sc{};
     float st[4];

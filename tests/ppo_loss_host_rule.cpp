@@ -1,36 +1,11 @@
-// The per-row rule, the tree and the final values of csrc/ccx_ppo.h compiled for the host (tests/test_ppo_loss_host_rule.py:
-// -O2 -ffp-contract=off), behind a C interface for ctypes.  The loops here only walk rows, groups and blocks in the order the
-// header states; every arithmetic operation is one of ccx_ppo.h's.
+// The per-row rule and the final values of csrc/ccx_ppo.h and the tree of csrc/ccx_tree.h compiled for the host
+// (tests/test_ppo_loss_host_rule.py: -O2 -ffp-contract=off), behind a C interface for ctypes.  The loops here only walk rows;
+// every arithmetic operation is one of the two headers'.
 #include <vector>
 
 #include "ccx_ppo.h"
 
 namespace {
-
-// the tree over M f64 terms: blocks of 256 rows, four groups of 64, rows >= M as +0.0, then the final wave
-double tree(const std::vector<double>& terms) {
-    const long long M = (long long)terms.size(), B = ccx_ppo::blocks_of(M);
-    std::vector<double> P(B);
-    for (long long b = 0; b < B; ++b) {
-        double G[4];
-        for (int g = 0; g < 4; ++g) {
-            double v[64];
-            for (int j = 0; j < 64; ++j) {
-                const long long i = b * 256 + g * 64 + j;
-                v[j] = i < M ? terms[i] : 0.0;
-            }
-            G[g] = ccx_ppo::halve64(v);
-        }
-        P[b] = ccx_ppo::block_partial(G[0], G[1], G[2], G[3]);
-    }
-    double acc[64];
-    for (int j = 0; j < 64; ++j) {
-        double one[1];
-        ccx_ppo::strided_partials(P.data(), B, j, one);
-        acc[j] = one[0];
-    }
-    return ccx_ppo::halve64(acc);
-}
 
 struct Norm {
     bool has;
@@ -69,7 +44,7 @@ void host_ppo_loss(long long M, const float* logits, const unsigned char* action
         for (int q = 0; q < ccx_ppo::kSums; ++q) terms[q][i] = v[q];
     }
     double S[ccx_ppo::kSums];
-    for (int q = 0; q < ccx_ppo::kSums; ++q) S[q] = tree(terms[q]);
+    for (int q = 0; q < ccx_ppo::kSums; ++q) S[q] = ccx_tree::sum_host(terms[q].data(), M);
     float st[8];
     ccx_ppo::loss_finals(S, vf_coef, ent_coef, st);
     for (int k = 0; k < 8; ++k) stats[k] = st[k];
@@ -116,13 +91,13 @@ void host_masked_moments(long long M, const float* x, const unsigned char* valid
         terms[2][i] = xd * xd;
     }
     double S[ccx_ppo::kMomentSums];
-    for (int q = 0; q < ccx_ppo::kMomentSums; ++q) S[q] = tree(terms[q]);
+    for (int q = 0; q < ccx_ppo::kMomentSums; ++q) S[q] = ccx_tree::sum_host(terms[q].data(), M);
     float o[4];
     ccx_ppo::moments_finals(S, o);
     for (int k = 0; k < 4; ++k) out[k] = o[k];
 }
 
-double host_tree(long long M, const double* terms) { return tree(std::vector<double>(terms, terms + M)); }
+double host_tree(long long M, const double* terms) { return ccx_tree::sum_host(terms, M); }
 
 float host_exp_spec(float x) { return ccx_softmax::exp_spec(x); }
 

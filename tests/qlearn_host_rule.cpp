@@ -1,6 +1,6 @@
 // The rules of csrc/ccx_qlearn.h compiled for the host (tests/test_qlearn_host_rule.py: -O2 -ffp-contract=off), behind a C
-// interface for ctypes.  The loops here only walk slots, rows, groups and blocks in the order the header states; every
-// arithmetic operation is one of ccx_qlearn.h's or ccx_ppo.h's, and the word is ccx_kernels.h's formula restated in four lines
+// interface for ctypes.  The loops here only walk slots and rows in the order the header states; every
+// arithmetic operation is one of ccx_qlearn.h's or ccx_tree.h's, and the word is ccx_kernels.h's formula restated in four lines
 // (that header needs the HIP runtime).
 #include <vector>
 
@@ -17,31 +17,6 @@ uint32_t mix32(uint32_t k) {
 uint32_t random_word(uint32_t seed_lo, uint32_t seed_hi, uint32_t genv, uint32_t episode, uint32_t step, uint32_t agent) {
     const uint32_t k = genv * 0x9E3779B1u + episode * 0x85EBCA77u + step * 0xC2B2AE3Du + agent * 0x27D4EB2Fu + seed_lo;
     return mix32(mix32(k) ^ seed_hi);
-}
-
-// the tree over M f64 terms: blocks of 256 rows, four groups of 64, rows >= M as +0.0, then the final wave
-double tree(const std::vector<double>& terms) {
-    const long long M = (long long)terms.size(), B = ccx_ppo::blocks_of(M);
-    std::vector<double> P(B);
-    for (long long b = 0; b < B; ++b) {
-        double G[4];
-        for (int g = 0; g < 4; ++g) {
-            double v[64];
-            for (int j = 0; j < 64; ++j) {
-                const long long i = b * 256 + g * 64 + j;
-                v[j] = i < M ? terms[i] : 0.0;
-            }
-            G[g] = ccx_ppo::halve64(v);
-        }
-        P[b] = ccx_ppo::block_partial(G[0], G[1], G[2], G[3]);
-    }
-    double acc[64];
-    for (int j = 0; j < 64; ++j) {
-        double one[1];
-        ccx_ppo::strided_partials(P.data(), B, j, one);
-        acc[j] = one[0];
-    }
-    return ccx_ppo::halve64(acc);
 }
 
 struct RowIn {
@@ -113,7 +88,7 @@ void host_td_loss(long long M, const float* q, const unsigned char* actions, con
         for (int k = 0; k < 5; ++k) terms[k][i] = v[k];
     }
     double S[ccx_qlearn::kSums];
-    for (int k = 0; k < ccx_qlearn::kSums; ++k) S[k] = tree(terms[k]);
+    for (int k = 0; k < ccx_qlearn::kSums; ++k) S[k] = ccx_tree::sum_host(terms[k].data(), M);
     float st[8];
     ccx_qlearn::td_finals(S, st);
     for (int k = 0; k < 8; ++k) stats[k] = st[k];
