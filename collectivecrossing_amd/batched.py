@@ -26,7 +26,7 @@ from . import _abi
 from ._lib import check, load
 from .configs import CollectiveCrossingConfig
 from .learner import (MLP_ACTIVATIONS, EvalResult, GaeResult, LearnerOps, MlpGradResult, MlpHead,  # noqa: F401 (re-exported)
-                      PpoLossResult, SampleResult, _EvaluateActions, _MlpForward, _PpoLoss, _ptr, _require)
+                      PpoLossResult, SampleResult, _EvaluateActions, _MlpForward, _PpoLoss, _require)
 from .params import agent_ids, array_form_strategies, lower_config, position_only_tables
 from .reset import build_reset_pool, seeded_positions
 
@@ -170,6 +170,10 @@ def scripted_slot_mask(config: CollectiveCrossingConfig, scripted) -> int:
             raise ValueError(f"scripted entries are slot indices or agent ids, got {it!r}")
         mask |= 1 << slot
     return mask
+
+
+def _ptr(t: torch.Tensor | None) -> C.c_void_p:
+    return C.c_void_p(None if t is None else t.data_ptr())
 
 
 def _result_tensors(res) -> list:
@@ -339,10 +343,9 @@ class BatchedCollectiveCrossing(LearnerOps):
             s = torch.from_numpy(np.asarray(seeds, dtype=np.uint64).reshape(-1).view(np.int64)).to(self.device)
         if s.numel() != self.num_envs:
             raise ValueError(f"need {self.num_envs} seeds, got {s.numel()}")
-        m = None if env_mask is None else self._as_dev_u8(env_mask, (self.num_envs,))
+        m = None if env_mask is None else self._as_dev_u8(env_mask, (self.num_envs,), cur=None)
         s = s.contiguous()
-        self._order_after_current_stream(s)
-        check(self._lib.ccx_reset_seeded(self._h, _ptr(s), _ptr(m)))
+        self._enqueue(self._lib.ccx_reset_seeded, s, m)
         return self.observe()
 
     def reset_host(self, seeds) -> torch.Tensor:
@@ -376,8 +379,7 @@ class BatchedCollectiveCrossing(LearnerOps):
             self.set_reset_pool(build_reset_pool(self.config, seed0, size))
             return
         t = self._new((size, self.num_agents, 2), torch.uint8)
-        self._order_after_current_stream(t)
-        check(self._lib.ccx_fill_reset_pool_seeded(self._h, _ptr(t), size, seed0))
+        self._enqueue(self._lib.ccx_fill_reset_pool_seeded, t, size, seed0)
         self._pool = t
         check(self._lib.ccx_set_reset_pool(self._h, _ptr(t), size))
 
@@ -385,11 +387,8 @@ class BatchedCollectiveCrossing(LearnerOps):
         return self._pool
 
     def reset_from_pool(self, env_mask=None) -> None:
-        cur = self._other_stream()
-        m = None if env_mask is None else self._as_dev_u8(env_mask, (self.num_envs,), cur)
-        self._order_after_current_stream(cur=cur)            # (the state: strategy_view / episode_stats readers)
-        check(self._lib.ccx_reset_from_pool(self._h, _ptr(m)))
-        self._current_stream_waits(cur=cur)
+        m = None if env_mask is None else self._as_dev_u8(env_mask, (self.num_envs,), cur=None)
+        self._enqueue(self._lib.ccx_reset_from_pool, m)      # (the state: strategy_view / episode_stats readers)
 
     # ------------------------------------------------------------------ scripted policy
     def policy_actions(self, policy: str = "greedy", out: torch.Tensor | None = None) -> torch.Tensor:
@@ -398,18 +397,14 @@ class BatchedCollectiveCrossing(LearnerOps):
         :meth:`set_policy_epsilon` is in effect (then the same draws as inside ``rollout_policy``)."""
         if out is None:
             out = self._new((self.num_envs, self.num_agents), torch.uint8)
-        cur = self._order_after_current_stream(out)
-        check(self._lib.ccx_policy_actions(self._h, _abi.POLICIES[policy], _ptr(out)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_policy_actions, _abi.POLICIES[policy], out)
         return out
 
     def greedy_actions(self, out: torch.Tensor | None = None) -> torch.Tensor:
         """``GreedyPolicy(epsilon=0)`` for every live agent (``ccx_greedy_actions``; never explores)."""
         if out is None:
             out = self._new((self.num_envs, self.num_agents), torch.uint8)
-        cur = self._order_after_current_stream(out)
-        check(self._lib.ccx_greedy_actions(self._h, _ptr(out)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_greedy_actions, out)
         return out
 
     # ------------------------------------------------------------------ legal-action masks
@@ -440,9 +435,7 @@ class BatchedCollectiveCrossing(LearnerOps):
         target), bit 4 = wait, always set; 0x10 for agents that are terminated or truncated.
         :func:`unpack_action_masks` turns the bytes into ``bool [E, N, 5]``.  Only enqueues (no host synchronisation)."""
         out = self._new((self.num_envs, self.num_agents), torch.uint8) if out is None else self._check_masks(out)
-        cur = self._order_after_current_stream(out)
-        check(self._lib.ccx_action_masks(self._h, _ptr(out)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_action_masks, out)
         return out
 
     def masks_fused(self, num_steps: int = 1, order: bool = False, mixed: bool = False) -> bool:
@@ -605,9 +598,7 @@ class BatchedCollectiveCrossing(LearnerOps):
         if K < 1 or tuple(reward.shape) != (K, E, N) or tuple(agent_flags.shape) != (K, E, N) or tuple(env_flags.shape) != (K, E):
             raise ValueError(f"expected reward / agent_flags [K, {E}, {N}] and env_flags [K, {E}], got {tuple(reward.shape)}, "
                              f"{tuple(agent_flags.shape)}, {tuple(env_flags.shape)}")
-        cur = self._order_after_current_stream(reward, agent_flags, env_flags)
-        check(self._lib.ccx_episode_stats_update(self._h, K, reward.data_ptr(), agent_flags.data_ptr(), env_flags.data_ptr()))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_episode_stats_update, K, reward, agent_flags, env_flags)
 
     def _track(self, K: int, res) -> None:
         """The update behind a tracked call, on the buffers that call hands out."""
@@ -629,11 +620,8 @@ class BatchedCollectiveCrossing(LearnerOps):
         to zero; no record is written, ``finished`` and ``last_*`` stay (``ccx_episode_stats_reset``).  ``reset`` and
         ``reset_from_pool`` do this for the envs they restart.  Only enqueues."""
         self._need_tracking()
-        cur = self._other_stream()
-        m = None if env_mask is None else self._as_dev_u8(env_mask, (self.num_envs,), cur)
-        self._order_after_current_stream(cur=cur)            # (readers of the episode_stats views)
-        check(self._lib.ccx_episode_stats_reset(self._h, _ptr(m)))
-        self._current_stream_waits(cur=cur)
+        m = None if env_mask is None else self._as_dev_u8(env_mask, (self.num_envs,), cur=None)
+        self._enqueue(self._lib.ccx_episode_stats_reset, m)  # (readers of the episode_stats views)
 
     def finished_episodes(self, clear: bool = True) -> FinishedEpisodes:
         """Synchronise and return the stored records of the log (:class:`FinishedEpisodes`; needs
@@ -661,17 +649,13 @@ class BatchedCollectiveCrossing(LearnerOps):
     def clear_episode_log(self) -> None:
         """Empty the finished-episode log: stored = dropped = 0 (``ccx_episode_log_clear``).  Only enqueues."""
         self._need_tracking()
-        cur = self._order_after_current_stream()
-        check(self._lib.ccx_episode_log_clear(self._h))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_episode_log_clear)
 
     # ------------------------------------------------------------------ compute
     def observe(self, out: torch.Tensor | None = None) -> torch.Tensor:
         if out is None:
             out = self._new((self.num_envs, self.num_agents, self.obs_len), torch.float32)
-        cur = self._order_after_current_stream(out)
-        check(self._lib.ccx_observe(self._h, _ptr(out)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_observe, out)
         return out
 
     def step(self, actions, order=None, want_obs: bool = True, want_compact: bool = False,
@@ -1033,9 +1017,7 @@ class BatchedCollectiveCrossing(LearnerOps):
         rows = int(c.numel() // (self.num_agents * 4))
         if out is None:
             out = self._new((*c.shape[:-1], self.obs_len), torch.float32)
-        cur = self._order_after_current_stream(c, out)
-        check(self._lib.ccx_expand_observations(self._h, _ptr(c), rows, _ptr(out)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_expand_observations, c, rows, out)
         return out
 
     # ------------------------------------------------------------------ rendering
@@ -1085,9 +1067,7 @@ class BatchedCollectiveCrossing(LearnerOps):
         rows = self.num_envs if ids is None else int(ids.shape[0])
         frames = self._frames_out((rows,), cp, out)
         if rows:
-            cur = self._order_after_current_stream(ids, frames)
-            check(self._lib.ccx_render(self._h, _ptr(ids), rows, cp, _ptr(frames)))
-            self._current_stream_waits(cur=cur)
+            self._enqueue(self._lib.ccx_render, ids, rows, cp, frames)
         return frames
 
     def render_compact(self, obs_compact: torch.Tensor, cell_px: int = 8, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -1103,9 +1083,7 @@ class BatchedCollectiveCrossing(LearnerOps):
         rows = int(np.prod(lead, dtype=np.int64)) if lead else 1
         frames = self._frames_out(lead, cp, out)
         if rows:
-            cur = self._order_after_current_stream(c, frames)
-            check(self._lib.ccx_render_compact(self._h, _ptr(c), rows, cp, _ptr(frames)))
-            self._current_stream_waits(cur=cur)
+            self._enqueue(self._lib.ccx_render_compact, c, rows, cp, frames)
         return frames
 
     def rollout(self, actions, order=None, auto_reset: bool = False,
@@ -1195,9 +1173,7 @@ class BatchedCollectiveCrossing(LearnerOps):
 
     # ------------------------------------------------------------------ counters / timing / shape
     def zero_counters(self) -> None:
-        cur = self._order_after_current_stream()             # (readers of counters_tensor)
-        check(self._lib.ccx_zero_counters(self._h))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_zero_counters)           # (readers of counters_tensor)
 
     def counters(self) -> dict[str, int]:
         c = _abi.CcxCounters()

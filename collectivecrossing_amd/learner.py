@@ -83,10 +83,6 @@ class MlpGradResult:
     workspace: torch.Tensor | None = None     # u8 [ccx_mlp_backward_workspace_bytes(rows, L, H, O)]
 
 
-def _ptr(t: torch.Tensor | None) -> C.c_void_p:
-    return C.c_void_p(None if t is None else t.data_ptr())
-
-
 def _require_aligned(name: str, t: torch.Tensor | None, align: int) -> None:
     if t is not None and t.data_ptr() % align:
         raise ValueError(f"{name} must be {align}-byte aligned (a view at an odd offset of its storage is not)")
@@ -133,13 +129,15 @@ def _require_out(out, cls, alloc: str) -> None:
 
 
 _OPT = {"optional": True}
+_Tensor = torch.Tensor                                               # (a global: _enqueue looks at every argument)
 
 
 class LearnerOps:
     """The learner-side methods of a batch.  The host class provides ``_lib`` (the loaded library), ``_h`` (the handle),
     ``device``, ``num_envs``, ``num_agents``, ``obs_len``, ``_new(shape, dtype)`` (an uninitialised device tensor),
     ``_order_after_current_stream(*tensors)`` (the handle's stream waits for torch's current one), and ``_stream`` /
-    ``_stream_raw`` (the handle's stream as torch's object and as the raw pointer).
+    ``_stream_raw`` (the handle's stream as torch's object and as the raw pointer).  Every enqueueing library call here goes
+    through :meth:`_enqueue`, which orders what it passes.
 
     **Stream order** (the contract of every method here, of :class:`BatchedCollectiveCrossing`,
     :class:`MlpHead` and :class:`DeviceAdam` that enqueues device work).  The launches go to the handle's stream: the one
@@ -157,6 +155,26 @@ class LearnerOps:
         if torch._C._cuda_getCurrentRawStream(self.device.index) == self._stream_raw:
             return None
         return torch.cuda.current_stream(self.device)
+
+    def _enqueue(self, fn, *args, also=()) -> None:
+        """THE way a library call keeps the stream-order contract: ``check(fn(self._h, *args))`` between the entry
+        (:meth:`_order_after_current_stream`) and the exit (:meth:`_current_stream_waits`), with every tensor among ``args``
+        ordered at the entry and handed to ``fn`` as its ``data_ptr()``.  What is passed is what is ordered; ``None``,
+        numbers and ctypes tables pass through as they are.  ``also``: tensors the launch touches whose pointers travel
+        inside a by-value table (the rows of a ``CcxAdamTensor`` or ``CcxSlotGroup`` array).  With the handle's stream
+        current there is nothing to order and neither helper is entered: the call costs the one raw read of
+        :meth:`_other_stream` and the ``data_ptr()`` calls (profiles/enqueue_host_time.txt).
+
+        Deliberately NOT through here: the stepping calls whose pointers sit in a cached ``CcxStepOut`` /
+        ``CcxRolloutOut`` (``step`` is the per-step path) use the two helpers directly; the scalar setters
+        (``DeviceAdam.lr``, ``QLearning.epsilon``) make no library call; host-synchronous, query and setting calls are
+        outside the contract."""
+        cur = self._other_stream()
+        if cur is not None:
+            self._order_after_current_stream(*[a for a in args if isinstance(a, _Tensor)], *also, cur=cur)
+        check(fn(self._h, *[a.data_ptr() if isinstance(a, _Tensor) else a for a in args]))
+        if cur is not None:
+            self._current_stream_waits(cur=cur)
 
     # ------------------------------------------------------------------ advantages
     def alloc_gae(self, num_steps: int, want_valid: bool = True) -> GaeResult:
@@ -205,11 +223,8 @@ class LearnerOps:
                      ("final_values", final_values, torch.float32, KEN, _OPT),
                      ("out.advantages", out.advantages, torch.float32, KEN),
                      ("out.returns", out.returns, torch.float32, KEN), ("out.valid", out.valid, torch.uint8, KEN, _OPT))
-        cur = self._order_after_current_stream(reward, agent_flags, env_flags, values, last_values, final_values,
-                                               out.advantages, out.returns, out.valid)
-        check(self._lib.ccx_gae(self._h, K, _ptr(reward), _ptr(agent_flags), _ptr(env_flags), _ptr(values), _ptr(last_values),
-                                _ptr(final_values), gamma, lam, _ptr(out.advantages), _ptr(out.returns), _ptr(out.valid)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_gae, K, reward, agent_flags, env_flags, values, last_values, final_values, gamma, lam,
+                      out.advantages, out.returns, out.valid)
         return out
 
     # ------------------------------------------------------------------ sampling from a learned policy
@@ -243,10 +258,7 @@ class LearnerOps:
                      ("logits", logits, torch.float32, (E, N, 5), {"align": 16}), ("masks", masks, torch.uint8, (E, N), _OPT),
                      ("out.actions", out.actions, torch.uint8, (E, N)), ("out.logp", out.logp, torch.float32, (E, N), _OPT),
                      ("out.entropy", out.entropy, torch.float32, (E, N), _OPT))
-        cur = self._order_after_current_stream(logits, masks, out.actions, out.logp, out.entropy)
-        check(self._lib.ccx_sample_actions(self._h, _ptr(logits), _ptr(masks), int(bool(deterministic)), _ptr(out.actions),
-                                           _ptr(out.logp), _ptr(out.entropy)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_sample_actions, logits, masks, int(bool(deterministic)), out.actions, out.logp, out.entropy)
         return out
 
     # ------------------------------------------------------------------ the policy head: observation rows to logits
@@ -258,10 +270,8 @@ class LearnerOps:
         return MlpHead(self, H, O, activation, L, backward)
 
     def _mlp_forward(self, head: "MlpHead", x: torch.Tensor, y: torch.Tensor, hidden: torch.Tensor | None) -> None:
-        cur = self._order_after_current_stream(x, head.w1t, head.b1, head.w2, head.b2, y, hidden)
-        check(self._lib.ccx_mlp_forward(self._h, x.numel() // head.L, head.L, head.H, head.O, head.activation_id, _ptr(x),
-                                        _ptr(head.w1t), _ptr(head.b1), _ptr(head.w2), _ptr(head.b2), _ptr(y), _ptr(hidden)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_mlp_forward, x.numel() // head.L, head.L, head.H, head.O, head.activation_id, x,
+                      head.w1t, head.b1, head.w2, head.b2, y, hidden)
 
     def _workspace_arg(self, need: int, workspace: torch.Tensor | None, alloc_name: str) -> torch.Tensor:
         """The workspace of a call that needs ``need`` bytes: the caller's, checked, or one from torch's allocator (so a call
@@ -313,11 +323,8 @@ class LearnerOps:
             return out
         workspace = self._mlp_backward_workspace(dims, rows, out.workspace)
         x, hidden, grad_y, w2 = x.detach(), hidden.detach(), grad_y.detach(), w2.detach()
-        cur = self._order_after_current_stream(x, hidden, grad_y, w2, workspace, out.w1t, out.b1, out.w2, out.b2, out.grad_a)
-        check(self._lib.ccx_mlp_backward(self._h, rows, L, H, O, act, _ptr(x), _ptr(hidden), _ptr(grad_y), _ptr(w2),
-                                         _ptr(workspace), _ptr(out.w1t), _ptr(out.b1), _ptr(out.w2), _ptr(out.b2),
-                                         _ptr(out.grad_a)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_mlp_backward, rows, L, H, O, act, x, hidden, grad_y, w2, workspace, out.w1t, out.b1,
+                      out.w2, out.b2, out.grad_a)
         return out
 
     def mlp_backward(self, head: "MlpHead", x: torch.Tensor, hidden: torch.Tensor, grad_y: torch.Tensor,
@@ -370,12 +377,8 @@ class LearnerOps:
                      ("logits_out", logits_out, torch.float32, (E, N, 5), _OPT),
                      ("out.actions", out.actions, torch.uint8, (E, N)), ("out.logp", out.logp, torch.float32, (E, N), _OPT),
                      ("out.entropy", out.entropy, torch.float32, (E, N), _OPT))
-        cur = self._order_after_current_stream(obs, head.w1t, head.b1, head.w2, head.b2, masks, logits_out, out.actions,
-                                               out.logp, out.entropy)
-        check(self._lib.ccx_mlp_sample_actions(self._h, head.H, head.activation_id, _ptr(obs), _ptr(head.w1t), _ptr(head.b1),
-                                               _ptr(head.w2), _ptr(head.b2), _ptr(masks), int(bool(deterministic)),
-                                               _ptr(out.actions), _ptr(out.logp), _ptr(out.entropy), _ptr(logits_out)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_mlp_sample_actions, head.H, head.activation_id, obs, head.w1t, head.b1, head.w2, head.b2,
+                      masks, int(bool(deterministic)), out.actions, out.logp, out.entropy, logits_out)
         return out
 
     # ------------------------------------------------------------------ stored actions under new logits
@@ -395,10 +398,7 @@ class LearnerOps:
         return lead
 
     def _evaluate_forward(self, logits, actions, masks, out: EvalResult) -> None:
-        cur = self._order_after_current_stream(logits, actions, masks, out.logp, out.entropy)
-        check(self._lib.ccx_evaluate_actions(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks), _ptr(out.logp),
-                                             _ptr(out.entropy)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_evaluate_actions, actions.numel(), logits, actions, masks, out.logp, out.entropy)
 
     def _current_stream_waits(self, *tensors, cur=False) -> None:
         """The exit of every enqueueing method (rules (b) and (c) of the class docstring): when torch's CURRENT stream is
@@ -467,10 +467,8 @@ class LearnerOps:
             ("grad_logp", grad_logp, torch.float32, lead, _OPT), ("grad_entropy", grad_entropy, torch.float32, lead, _OPT),
             ("out", out, torch.float32, lead + (5,), {"align": 16})))
         if logits.numel():
-            cur = self._order_after_current_stream(logits, actions, masks, grad_logp, grad_entropy, out)
-            check(self._lib.ccx_evaluate_actions_backward(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks),
-                                                          _ptr(grad_logp), _ptr(grad_entropy), _ptr(out)))
-            self._current_stream_waits(cur=cur)
+            self._enqueue(self._lib.ccx_evaluate_actions_backward, actions.numel(), logits, actions, masks, grad_logp,
+                          grad_entropy, out)
         return out
 
     # ------------------------------------------------------------------ the PPO loss over the rows that count
@@ -533,18 +531,12 @@ class LearnerOps:
             out.copy_(torch.tensor([0.0, 0.0, 1.0, 0.0], dtype=torch.float32))
             return out
         workspace = self._ppo_workspace_arg(workspace, rows)
-        cur = self._order_after_current_stream(x, valid, out, workspace)
-        check(self._lib.ccx_masked_moments(self._h, rows, _ptr(x), _ptr(valid), _ptr(workspace), _ptr(out)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_masked_moments, rows, x, valid, workspace, out)
         return out
 
     def _ppo_forward(self, logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper, workspace, stats):
-        cur = self._order_after_current_stream(logits, values, actions, logp_old, advantages, returns, masks, valid, norm,
-                                               workspace, stats)
-        check(self._lib.ccx_ppo_loss(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks), _ptr(logp_old),
-                                     _ptr(advantages), _ptr(returns), _ptr(values), _ptr(valid), _ptr(norm), *hyper,
-                                     _ptr(workspace), _ptr(stats)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_ppo_loss, actions.numel(), logits, actions, masks, logp_old, advantages, returns, values,
+                      valid, norm, *hyper, workspace, stats)
 
     def ppo_loss(self, logits: torch.Tensor, values: torch.Tensor, actions: torch.Tensor, logp_old: torch.Tensor,
                  advantages: torch.Tensor, returns: torch.Tensor, masks: torch.Tensor | None = None,
@@ -626,12 +618,8 @@ class LearnerOps:
                      ("grad_values", gv, torch.float32, lead, _OPT))
         if logits.numel():
             logits, values = logits.detach(), values.detach()
-            cur = self._order_after_current_stream(logits, values, actions, logp_old, advantages, returns, masks, valid, norm,
-                                                   stats, grad_loss, gl, gv)
-            check(self._lib.ccx_ppo_loss_backward(self._h, actions.numel(), _ptr(logits), _ptr(actions), _ptr(masks),
-                                                  _ptr(logp_old), _ptr(advantages), _ptr(returns), _ptr(values), _ptr(valid),
-                                                  _ptr(norm), *hyper, _ptr(stats), _ptr(grad_loss), _ptr(gl), _ptr(gv)))
-            self._current_stream_waits(cur=cur)
+            self._enqueue(self._lib.ccx_ppo_loss_backward, actions.numel(), logits, actions, masks, logp_old, advantages,
+                          returns, values, valid, norm, *hyper, stats, grad_loss, gl, gv)
         return gl, gv
 
     # ------------------------------------------------------------------ the optimiser step
@@ -649,10 +637,8 @@ class LearnerOps:
         table =(CcxAdamTensor * len(params))()
         for row, p, g, m, v in zip(table, params, grads, ms, vs):
             row.param, row.grad, row.m, row.v, row.numel = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel()
-        cur = self._order_after_current_stream(*params, *grads, *ms, *vs, lr_dev, state, workspace, stats)
-        check(self._lib.ccx_adam_step(self._h, len(params), table, lr, _ptr(lr_dev), *hyper, _ptr(state), _ptr(workspace),
-                                      _ptr(stats)))
-        self._current_stream_waits(cur=cur)
+        self._enqueue(self._lib.ccx_adam_step, len(params), table, lr, lr_dev, *hyper, state, workspace, stats,
+                      also=(*params, *grads, *ms, *vs))
 
 
 def _check_adam_hyper(lr, betas, eps, weight_decay, max_grad_norm):

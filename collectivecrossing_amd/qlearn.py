@@ -15,8 +15,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
-from ._lib import check
-from .learner import _OPT, _ptr, _require, _require_all, _require_out
+from .learner import _OPT, _require, _require_all, _require_out
 
 
 @dataclass
@@ -65,7 +64,7 @@ class QLearning:
 
     ``epsilon`` is a float property backed by a device f32 [1] (:attr:`epsilon_dev`), written on the handle's stream: an
     annealed rate changes between the replays of a captured actor loop without a re-capture.  Every method that enqueues
-    keeps the stream-order contract of :class:`~collectivecrossing_amd.learner.LearnerOps` through the batch's own helpers.
+    keeps the stream-order contract of :class:`~collectivecrossing_amd.learner.LearnerOps` through the batch's ``_enqueue``.
     Anything else than the tensors described raises ``ValueError`` before the library is called; zero rows return without
     calling it.  Not here: a dueling combine, n-step targets, distributional heads, a replay buffer or prioritised sampling
     (``weights`` and ``td_error`` are its hooks), the head's forward fused with the action choice, bf16 / f16."""
@@ -133,9 +132,7 @@ class QLearning:
                      ("out.actions", out.actions, torch.uint8, (E, N)), ("out.explored", out.explored, torch.uint8, (E, N), _OPT))
         eps = None if greedy else self.epsilon_dev
         q = q.detach()
-        cur = b._order_after_current_stream(q, masks, eps, out.actions, out.explored)
-        check(b._lib.ccx_q_actions(b._h, _ptr(q), _ptr(masks), _ptr(eps), _ptr(out.actions), _ptr(out.explored)))
-        b._current_stream_waits(cur=cur)
+        b._enqueue(b._lib.ccx_q_actions, q, masks, eps, out.actions, out.explored)
         return out
 
     # ------------------------------------------------------------------ the TD loss over the rows that count
@@ -177,10 +174,8 @@ class QLearning:
 
     def _forward(self, q, actions, reward, done, qt, qo, masks_next, valid, weights, hyper, workspace, stats, td_error) -> None:
         b = self.batch
-        cur = b._order_after_current_stream(q, actions, reward, done, qt, qo, masks_next, valid, weights, workspace, stats, td_error)
-        check(b._lib.ccx_td_loss(b._h, actions.numel(), _ptr(q), _ptr(actions), _ptr(reward), _ptr(done), _ptr(qt), _ptr(qo),
-                                 _ptr(masks_next), _ptr(valid), _ptr(weights), *hyper, _ptr(workspace), _ptr(stats), _ptr(td_error)))
-        b._current_stream_waits(cur=cur)
+        b._enqueue(b._lib.ccx_td_loss, actions.numel(), q, actions, reward, done, qt, qo, masks_next, valid, weights, *hyper,
+                   workspace, stats, td_error)
 
     def td_loss(self, q: torch.Tensor, actions: torch.Tensor, reward: torch.Tensor, done: torch.Tensor,
                 q_next_target: torch.Tensor, q_next_online: torch.Tensor | None = None, masks_next: torch.Tensor | None = None,
@@ -261,12 +256,8 @@ class QLearning:
                 raise ValueError(f"grad_loss must be a torch.float32 tensor with one element (0-dim or [1]) on {b.device}")
         if q.numel():
             q = q.detach()
-            cur = b._order_after_current_stream(q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights,
-                                                stats, grad_loss, out)
-            check(b._lib.ccx_td_loss_backward(b._h, actions.numel(), _ptr(q), _ptr(actions), _ptr(reward), _ptr(done),
-                                              _ptr(q_next_target), _ptr(q_next_online), _ptr(masks_next), _ptr(valid),
-                                              _ptr(weights), *hyper, _ptr(stats), _ptr(grad_loss), _ptr(out)))
-            b._current_stream_waits(cur=cur)
+            b._enqueue(b._lib.ccx_td_loss_backward, actions.numel(), q, actions, reward, done, q_next_target, q_next_online,
+                       masks_next, valid, weights, *hyper, stats, grad_loss, out)
         return out
 
 

@@ -12,9 +12,8 @@ import numpy as np
 import torch
 
 from ._abi import SIDES_MAX_GROUPS, CcxSlotGroup
-from ._lib import check
 from .batched import scripted_slot_mask
-from .learner import MlpGradResult, MlpHead, SampleResult, _OPT, _ptr, _require, _require_all, _require_out
+from .learner import MlpGradResult, MlpHead, SampleResult, _OPT, _require, _require_all, _require_out
 
 
 def _slots_of(mask: int) -> list[int]:
@@ -41,7 +40,7 @@ class SideHeads(torch.nn.Module):
 
     Anything else than the tensors described raises ``ValueError`` before the library is called; zero rows return empty
     tensors without calling it.  Every method that enqueues keeps the stream-order contract of
-    :class:`~collectivecrossing_amd.learner.LearnerOps` through the batch's own helpers."""
+    :class:`~collectivecrossing_amd.learner.LearnerOps` through the batch's ``_enqueue``."""
 
     def __init__(self, batch, heads):
         super().__init__()
@@ -106,9 +105,8 @@ class SideHeads(torch.nn.Module):
     def _forward(self, x, y, hidden) -> None:
         b, N = self.batch, self.batch.num_agents
         table = self._table()
-        cur = b._order_after_current_stream(x, *self._param_tensors(), y, hidden)
-        check(b._lib.ccx_sides_forward(b._h, x.numel() // (N * self.L), N, *self.dims, _ptr(x), len(table), table, _ptr(y), _ptr(hidden)))
-        b._current_stream_waits(cur=cur)
+        b._enqueue(b._lib.ccx_sides_forward, x.numel() // (N * self.L), N, *self.dims, x, len(table), table, y, hidden,
+                   also=self._param_tensors())
 
     def _backward(self, x, hidden, grad_y, outs) -> None:
         """``ccx_sides_backward`` per group on checked tensors; ``outs``: one :class:`MlpGradResult` per group."""
@@ -118,12 +116,9 @@ class SideHeads(torch.nn.Module):
         for mask, head, out in zip(self.masks, self.heads, outs):
             head._check_parameters()
             todo.append((mask, head.w2.detach(), out, b._mlp_backward_workspace(self.dims, M * bin(mask).count("1"), out.workspace)))
-        cur = b._order_after_current_stream(x, hidden, grad_y, *(t for _, w2, out, ws in todo
-                                                                 for t in (w2, ws, out.w1t, out.b1, out.w2, out.b2, out.grad_a)))
         for mask, w2, out, ws in todo:
-            check(b._lib.ccx_sides_backward(b._h, M, N, mask, *self.dims, _ptr(x), _ptr(hidden), _ptr(grad_y), _ptr(w2), _ptr(ws),
-                                            _ptr(out.w1t), _ptr(out.b1), _ptr(out.w2), _ptr(out.b2), _ptr(out.grad_a)))
-        b._current_stream_waits(cur=cur)
+            b._enqueue(b._lib.ccx_sides_backward, M, N, mask, *self.dims, x, hidden, grad_y, w2, ws, out.w1t, out.b1, out.w2,
+                       out.b2, out.grad_a)
 
     def _check_rows(self, x) -> tuple:
         b = self.batch
@@ -175,11 +170,8 @@ class SideHeads(torch.nn.Module):
                      ("out.actions", out.actions, torch.uint8, (E, N)), ("out.logp", out.logp, torch.float32, (E, N), _OPT),
                      ("out.entropy", out.entropy, torch.float32, (E, N), _OPT))
         table = self._table()
-        cur = b._order_after_current_stream(obs, *self._param_tensors(), masks, logits_out, out.actions, out.logp, out.entropy)
-        check(b._lib.ccx_sides_sample_actions(b._h, self.H, self.dims[3], _ptr(obs), len(table), table, _ptr(masks),
-                                              int(bool(deterministic)), _ptr(out.actions), _ptr(out.logp), _ptr(out.entropy),
-                                              _ptr(logits_out)))
-        b._current_stream_waits(cur=cur)
+        b._enqueue(b._lib.ccx_sides_sample_actions, self.H, self.dims[3], obs, len(table), table, masks,
+                   int(bool(deterministic)), out.actions, out.logp, out.entropy, logits_out, also=self._param_tensors())
         return out
 
     # ------------------------------------------------------------------ the backward pass

@@ -3,6 +3,9 @@ BatchedCollectiveCrossing, LearnerOps, MlpHead and DeviceAdam that reaches the l
 table, in both directions on the GPU (tests/test_gpu_stream_order.py), or exempted with a one-line reason.  A new op
 cannot be added without that decision."""
 
+import re
+from pathlib import Path
+
 import _stream_order as so
 
 
@@ -25,6 +28,22 @@ def test_the_walk_finds_what_it_should():
     for name in ("BatchedCollectiveCrossing.frame_shape", "BatchedCollectiveCrossing.rows_alignment", "LearnerOps.alloc_gae",
                  "MlpHead.to_sequential", "DeviceAdam.zero_grad"):
         assert name not in flagged, name
+
+
+def test_learner_modules_reach_the_library_through_enqueue_only():
+    """In learner.py, sides.py and qlearn.py a library function is named only as the first argument of ``_enqueue(``
+    (which orders what it passes: tests/test_enqueue_host.py) or as a ``*_workspace_bytes`` query.  A new op that spells
+    entry, call and exit by hand fails here."""
+    import collectivecrossing_amd
+
+    named = re.compile(r"_lib\.(ccx_\w+)")
+    enqueued = re.compile(r"\b_enqueue\(\s*\w+\._lib\.(ccx_\w+)\s*[,)]")
+    for module in ("learner.py", "sides.py", "qlearn.py"):
+        text = (Path(collectivecrossing_amd.__file__).parent / module).read_text()
+        ok = {m.start(1) for m in enqueued.finditer(text)}
+        stray = [m.group(1) for m in named.finditer(text) if m.start(1) not in ok and not m.group(1).endswith("_workspace_bytes")]
+        assert not stray, f"{module}: {stray} must go through _enqueue"
+        assert ok, module
 
 
 def test_table_and_exemptions_name_real_public_methods():
