@@ -179,6 +179,9 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_td_workspace_bytes": (C.c_int64, [C.c_int64]),
     "ccx_td_loss": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 9 + [C.c_float] * 2 + [C.c_void_p] * 3),
     "ccx_td_loss_backward": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 9 + [C.c_float] * 2 + [C.c_void_p] * 3),
+    "ccx_replay_push": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 8),
+    "ccx_replay_sample": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 8),
+    "ccx_replay_fetch": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 9),
     "ccx_set_check_inputs":(C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),

@@ -39,8 +39,13 @@ enum : uint32_t { kSampleStream = 0x2545F491u };
 // CCX_QLEARN (include/ccx.h, ccx_qlearn.hip): the two draws of an epsilon-greedy action over Q-values -- whether the slot
 // explores, and which legal action it then takes -- are two more streams of the same word (seed_hi ^ the constant).
 enum : uint32_t { kQExploreStream = 0x68E31DA4u, kQChoiceStream = 0xB5297A4Du };
+// CCX_REPLAY (include/ccx.h, ccx_replay.hip): the two words of a replay draw are keyed (draw b, launch counter low, high,
+// 0 | 1) on one more stream of the same word.
+enum : uint32_t { kReplayStream = 0x3C6EF372u };
 static_assert(kQExploreStream != kQChoiceStream && kQExploreStream != kEpsStream && kQExploreStream != kSampleStream &&
-              kQChoiceStream != kEpsStream && kQChoiceStream != kSampleStream && kQExploreStream != 0u && kQChoiceStream != 0u,
+              kQChoiceStream != kEpsStream && kQChoiceStream != kSampleStream && kQExploreStream != 0u && kQChoiceStream != 0u &&
+              kReplayStream != kQExploreStream && kReplayStream != kQChoiceStream && kReplayStream != kEpsStream &&
+              kReplayStream != kSampleStream && kReplayStream != 0u,
               "every stream of the counter-based word has its own constant");
 __host__ __device__ inline uint32_t explore_action(uint32_t u, uint32_t free_dirs) {
     uint32_t vm = (free_dirs & 0xFu) | 0x10u;          // wait is always valid (greedy_policy.py:251)

@@ -66,8 +66,8 @@ class QLearning:
     annealed rate changes between the replays of a captured actor loop without a re-capture.  Every method that enqueues
     keeps the stream-order contract of :class:`~collectivecrossing_amd.learner.LearnerOps` through the batch's ``_enqueue``.
     Anything else than the tensors described raises ``ValueError`` before the library is called; zero rows return without
-    calling it.  Not here: a dueling combine, n-step targets, distributional heads, a replay buffer or prioritised sampling
-    (``weights`` and ``td_error`` are its hooks), the head's forward fused with the action choice, bf16 / f16."""
+    calling it.  Not here: a dueling combine, n-step targets, distributional heads, prioritised sampling (``weights`` and
+    ``td_error`` are its hooks; the replay buffer itself is :class:`~collectivecrossing_amd.replay.ReplayRing`), the head's forward fused with the action choice, bf16 / f16."""
 
     def __init__(self, batch, epsilon: float = 1.0):
         from .batched import BatchedCollectiveCrossing

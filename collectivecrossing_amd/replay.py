@@ -1,0 +1,265 @@
+"""The replay memory of an off-policy loop on the device (include/ccx.h CCX_REPLAY): a ring of COMPACT env-step records whose
+cursor lives on the device, filled from a rollout's own arrays (``ccx_replay_push``), and ONE kernel that draws a minibatch
+with the library's counter-based word and writes it as DefaultObservation rows plus the small arrays
+:meth:`~collectivecrossing_amd.qlearn.QLearning.td_loss` takes (``ccx_replay_sample`` / ``ccx_replay_fetch``).
+
+:class:`ReplayRing` is a class of its own, not a set of methods of the batch, for the reason ``sides.py`` and ``qlearn.py``
+give: the stream-order table of the batch's classes (tests/_stream_order.py) is closed, and this class brings its own proof
+(tests/test_gpu_stream_order_replay.py)."""
+
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import torch
+
+from .learner import _OPT, _require_all, _require_out
+
+EMPTY_ACTION, EMPTY_MASKS = 255, 0x10                                    # the EMPTY record's two bytes that are not zero
+_ARRAYS = ("obs_c", "next_c", "actions", "reward", "done", "valid", "masks_next")
+
+
+@dataclass
+class ReplayBatch:
+    """A minibatch of B env-step records (:meth:`ReplayRing.sample` / :meth:`ReplayRing.fetch`).  Every element is written:
+    the EMPTY record (action 255, ``valid`` 0, ``masks_next`` 0x10, rows of +0.0 compact records) where ``index`` names no
+    slot of the ring."""
+
+    obs: torch.Tensor | None        # f32 [B, N, L]: the rows the step acted on
+    next_obs: torch.Tensor | None   # f32 [B, N, L]: the rows it ended on (the terminal ones where it ended an episode)
+    actions: torch.Tensor           # u8 [B, N]
+    reward: torch.Tensor            # f64 [B, N]
+    done: torch.Tensor              # u8 [B, N]: terminated in the step (0 / 1)
+    valid: torch.Tensor             # u8 [B, N]: live in the step (0 / 4)
+    masks_next: torch.Tensor        # u8 [B, N]: the next state's legal set (0x1F where the step ended the episode)
+    index: torch.Tensor             # int64 [B]: the records drawn (-1: the ring was empty)
+
+
+def _check_geometry(steps, num_envs: int, num_agents: int) -> int:
+    """``S`` of a ring of ``steps`` steps of ``num_envs`` envs, or ``ValueError``: ``1 <= S`` and ``R = S * E < 2^31``."""
+    try:
+        S = int(steps)
+    except (TypeError, ValueError):
+        raise ValueError("steps must be an integer") from None
+    if S != steps or S < 1:
+        raise ValueError(f"steps must be an integer >= 1, got {steps!r}")
+    if S * int(num_envs) >= 1 << 31:
+        raise ValueError(f"the ring would hold {S} * {num_envs} records: R = steps * num_envs must stay below 2^31")
+    return S
+
+
+def _check_batch_size(B, num_agents: int) -> int:
+    """``B`` of a minibatch, or ``ValueError``: ``1 <= B <= 2^31 / N``."""
+    try:
+        ok = int(B) == B and 1 <= int(B) and int(B) * int(num_agents) <= 1 << 31
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f"the batch size must be an integer in 1 .. 2^31 / {num_agents}, got {B!r}")
+    return int(B)
+
+
+class ReplayRing:
+    """``ReplayRing(batch, steps=S)``: S ring steps of the batch's E envs, ``R = S * E`` records of ``44 N`` bytes each (the
+    same env-step as two rows per agent takes ``N (2 (24 + 16 N) + 12)``: 7 times as much at N = 8, 25 times at N = 32).
+
+    Storage, struct of arrays, allocated here and public (tests, checkpoints): ``obs_c`` / ``next_c`` f32 [R, N, 4],
+    ``actions`` u8, ``reward`` f64, ``done`` u8, ``valid`` u8, ``masks_next`` u8, each [R, N], and ``state`` int64 [4] =
+    {head, draws, 0, 0} ON THE DEVICE: the kernels read the cursor there, so a captured :meth:`push` or :meth:`sample`
+    advances with every replay.  The ring starts as R copies of the EMPTY record (action 255, ``valid`` = ``done`` = 0,
+    ``reward`` +0.0, ``masks_next`` 0x10, compact records +0.0), and :meth:`clear` restores that.
+
+    Every method that enqueues keeps the stream-order contract of :class:`~collectivecrossing_amd.learner.LearnerOps` through
+    the batch's ``_enqueue``; the ring's own arrays travel as arguments, so they are ordered like the caller's.  Anything else
+    than the tensors described raises ``ValueError`` before the library is called.  Not here: prioritised or recency-weighted
+    sampling (``index``, :meth:`fetch` and ``td_loss``'s ``weights`` / ``td_error`` are the hooks), sampling without
+    replacement, n-step returns, frames shared between ``obs_c`` and ``next_c``, records of single agents or sequences, a
+    ring over several GPUs (each shard has its own), rows-form storage, bf16 / f16."""
+
+    def __init__(self, batch, steps: int = 64):
+        from .batched import BatchedCollectiveCrossing
+
+        if not isinstance(batch, BatchedCollectiveCrossing):
+            raise ValueError("batch must be a BatchedCollectiveCrossing")
+        self.batch = batch
+        E, N = batch.num_envs, batch.num_agents
+        self.steps = _check_geometry(steps, E, N)
+        self.records = R = self.steps * E
+        dev, u8 = batch.device, torch.uint8
+        self.obs_c = torch.zeros((R, N, 4), dtype=torch.float32, device=dev)
+        self.next_c = torch.zeros((R, N, 4), dtype=torch.float32, device=dev)
+        self.actions = torch.full((R, N), EMPTY_ACTION, dtype=u8, device=dev)
+        self.reward = torch.zeros((R, N), dtype=torch.float64, device=dev)
+        self.done = torch.zeros((R, N), dtype=u8, device=dev)
+        self.valid = torch.zeros((R, N), dtype=u8, device=dev)
+        self.masks_next = torch.full((R, N), EMPTY_MASKS, dtype=u8, device=dev)
+        self.state = torch.zeros((4,), dtype=torch.int64, device=dev)
+
+    # ------------------------------------------------------------------ what the ring is
+    def _arrays(self) -> tuple:
+        return tuple(getattr(self, k) for k in _ARRAYS)
+
+    def _ring_args(self) -> tuple:
+        """The ring as the library takes it: S, the seven arrays, the state."""
+        return (self.steps, *self._arrays(), self.state)
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of the seven arrays: ``44 N`` per record."""
+        return sum(t.numel() * t.element_size() for t in self._arrays())
+
+    def rows_form_nbytes(self) -> int:
+        """Bytes the same R records take as two row arrays [R, N, L] f32 and the five small arrays."""
+        N = self.batch.num_agents
+        return self.records * N * (2 * 4 * self.batch.obs_len + 12)
+
+    def clear(self) -> None:
+        """Every slot back to the EMPTY record, ``head`` = ``draws`` = 0: fills on the handle's stream, ordered like a
+        launch (only enqueues)."""
+        b = self.batch
+        cur = b._order_after_current_stream(*self._arrays(), self.state)
+        with torch.cuda.stream(b._stream):
+            for t in (self.obs_c, self.next_c, self.reward, self.done, self.valid, self.state):
+                t.zero_()
+            self.actions.fill_(EMPTY_ACTION)
+            self.masks_next.fill_(EMPTY_MASKS)
+        b._current_stream_waits(cur=cur)
+
+    # ------------------------------------------------------------------ rollout arrays to records
+    def push(self, obs0_compact: torch.Tensor, actions: torch.Tensor, traj, masks_next: torch.Tensor | None = None) -> None:
+        """K >= 1 steps of a rollout become K * E records (``ccx_replay_push``, include/ccx.h CCX_REPLAY): one kernel with a
+        lane per (step, env, agent) and one plain lane behind it that advances ``head`` by K, on the handle's stream.
+
+        ``obs0_compact`` f32 [E, N, 4]: the compact observation the first step acted on; ``actions`` u8 [K, E, N];
+        ``traj``: a :class:`RolloutResult` or a ``(reward, agent_flags, env_flags, obs_compact[, final_compact])`` tuple
+        of that rollout (f64 [K, E, N], u8 [K, E, N], u8 [K, E], f32 [K, E, N, 4] twice; ``final_compact`` may be
+        ``None``); ``masks_next`` u8 [K, E, N] or ``None``: the legal set behind each step.  ``1 <= K <= steps``.  The record
+        of step s and env e goes to slot ``((head + s) mod S) * E + e``: ``obs_c`` = ``s == 0 ? obs0_compact[e] :
+        obs_compact[s - 1][e]``; where the step ended the episode (``EF_RESET``, with ``final_compact`` given) ``next_c`` is
+        ``final_compact[s][e]`` and ``masks_next`` 0x1F, else ``obs_compact[s][e]`` and the caller's byte (0x1F without
+        ``masks_next``); ``done`` = ``agent_flags & AF_TERMINATED``, ``valid`` = ``agent_flags & AF_LIVE``; actions and
+        rewards are copied.  ``head`` is read on the device: a captured push advances with every replay.  A block may wrap
+        inside itself; ``K == steps`` rewrites the whole ring.
+
+        THE CALLER'S CONTRACT: the rollout ran with ``reset_obs="next"`` (``obs_compact[s][e]`` of a restarted env is then
+        the new episode's first observation and ``final_compact[s][e]`` the one the step ended on).  The library cannot
+        see it.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
+        from .batched import RolloutResult                           # (batched imports learner; keep the import local)
+
+        b = self.batch
+        E, N = b.num_envs, b.num_agents
+        if isinstance(traj, RolloutResult):
+            reward, agent_flags, env_flags = traj.reward, traj.agent_flags, traj.env_flags
+            obs_compact, final_compact = traj.obs_compact, traj.final_compact
+        else:
+            try:
+                reward, agent_flags, env_flags, obs_compact, *rest = traj
+                final_compact, = rest or (None,)
+            except (TypeError, ValueError):
+                raise ValueError("traj must be a RolloutResult or a (reward, agent_flags, env_flags, obs_compact[, final_compact]) "
+                                 "tuple") from None
+        K = int(actions.shape[0]) if isinstance(actions, torch.Tensor) and actions.dim() == 3 else 0
+        if not 1 <= K <= self.steps:
+            raise ValueError(f"actions must be a torch.uint8 tensor [K, {E}, {N}] with 1 <= K <= steps = {self.steps}")
+        KEN, f32, u8 = (K, E, N), torch.float32, torch.uint8
+        _require_all(b.device, ("obs0_compact", obs0_compact, f32, (E, N, 4), {"align": 16}), ("actions", actions, u8, KEN),
+                     ("reward", reward, torch.float64, KEN), ("agent_flags", agent_flags, u8, KEN),
+                     ("env_flags", env_flags, u8, (K, E)),
+                     ("obs_compact", obs_compact, f32, KEN + (4,), {"align": 16, "hint": " (rollout(want_compact=True))"}),
+                     ("final_compact", final_compact, f32, KEN + (4,), {"optional": True, "align": 16}),
+                     ("masks_next", masks_next, u8, KEN, _OPT))
+        b._enqueue(b._lib.ccx_replay_push, *self._ring_args(), K, obs0_compact, actions, reward, agent_flags, env_flags, obs_compact,
+                   final_compact, masks_next)
+
+    # ------------------------------------------------------------------ records to a minibatch
+    def alloc_batch(self, B: int, want_obs: bool = True, want_next_obs: bool = True) -> ReplayBatch:
+        """Output tensors of :meth:`sample` / :meth:`fetch` for B records (static buffers for a captured graph)."""
+        b = self.batch
+        B = _check_batch_size(B, b.num_agents)
+        N, L, u8 = b.num_agents, b.obs_len, torch.uint8
+        return ReplayBatch(b._new((B, N, L), torch.float32) if want_obs else None,
+                           b._new((B, N, L), torch.float32) if want_next_obs else None,
+                           b._new((B, N), u8), b._new((B, N), torch.float64), b._new((B, N), u8), b._new((B, N), u8),
+                           b._new((B, N), u8), b._new((B,), torch.int64))
+
+    def _out(self, B: int, out, want_obs: bool, want_next_obs: bool) -> ReplayBatch:
+        b = self.batch
+        _require_out(out, ReplayBatch, "alloc_batch")
+        if out is None:
+            return self.alloc_batch(B, want_obs, want_next_obs)
+        N, L, f32, u8 = b.num_agents, b.obs_len, torch.float32, torch.uint8
+        _require_all(b.device, ("out.obs", out.obs, f32, (B, N, L), {"optional": True, "align": 16}),
+                     ("out.next_obs", out.next_obs, f32, (B, N, L), {"optional": True, "align": 16}),
+                     ("out.actions", out.actions, u8, (B, N)), ("out.reward", out.reward, torch.float64, (B, N)),
+                     ("out.done", out.done, u8, (B, N)), ("out.valid", out.valid, u8, (B, N)),
+                     ("out.masks_next", out.masks_next, u8, (B, N)), ("out.index", out.index, torch.int64, (B,)))
+        return out
+
+    @staticmethod
+    def _out_args(out: ReplayBatch) -> tuple:
+        return (out.obs, out.next_obs, out.actions, out.reward, out.done, out.valid, out.masks_next, out.index)
+
+    def sample(self, B: int, out: ReplayBatch | None = None, want_obs: bool = True, want_next_obs: bool = True) -> ReplayBatch:
+        """Draw B records and write the minibatch (``ccx_replay_sample``, include/ccx.h CCX_REPLAY): ONE kernel that draws,
+        gathers through the indices and expands the compact records into rows, and one plain lane behind it that advances
+        ``draws``, on the handle's stream.
+
+        With ``F = min(head, steps) * E`` and ``d = draws`` read on the device, ``index[b]`` is the high half of the
+        128-bit product of ``F`` and the two counter-based words of key ``(b, d)`` on the replay stream of the batch's
+        ``set_rng_seed`` -- uniform over the records pushed, with replacement, the same eager or captured and for any split
+        of the pushes into calls; nothing comes from torch's generator.  An empty ring gives ``index`` -1 and the EMPTY
+        record.  Row b of every output is a copy of record ``index[b]``; ``obs`` / ``next_obs`` are bit-equal to
+        ``expand_observations`` of its compact records.  ``out`` reuses a :class:`ReplayBatch` of the same B
+        (:meth:`alloc_batch`; its ``obs`` / ``next_obs`` decide, ``want_*`` is then ignored).
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
+        b = self.batch
+        B = _check_batch_size(B, b.num_agents)
+        out = self._out(B, out, want_obs, want_next_obs)
+        b._enqueue(b._lib.ccx_replay_sample, *self._ring_args(), B, *self._out_args(out))
+        return out
+
+    def fetch(self, index: torch.Tensor, out: ReplayBatch | None = None, want_obs: bool = True,
+              want_next_obs: bool = True) -> ReplayBatch:
+        """The kernel of :meth:`sample` on the caller's record indices, int64 [B] (``ccx_replay_fetch``): nothing is drawn
+        and ``draws`` stays.  An index outside ``[0, records)`` gives the EMPTY record and reads nothing; ``out.index``
+        receives a copy of ``index`` (it may be the same tensor).
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
+        b = self.batch
+        B = int(index.shape[0]) if isinstance(index, torch.Tensor) and index.dim() == 1 else 0
+        _require_all(b.device, ("index", index, torch.int64, (max(B, 1),)))
+        B = _check_batch_size(B, b.num_agents)
+        out = self._out(B, out, want_obs, want_next_obs)
+        b._enqueue(b._lib.ccx_replay_fetch, *self._ring_args(), B, index, *self._out_args(out))
+        return out
+
+    # ------------------------------------------------------------------ checkpoints (host-synchronous: outside the contract)
+    def state_dict(self) -> dict:
+        """Copies of the seven arrays and ``state``, and the geometry ``(S, E, N)``; waits for the handle's stream."""
+        b = self.batch
+        b.synchronize()
+        sd = {k: getattr(self, k).clone() for k in _ARRAYS}
+        sd["state"] = self.state.clone()
+        sd["geometry"] = (self.steps, b.num_envs, b.num_agents)
+        torch.cuda.synchronize(b.device)
+        return sd
+
+    def load_state_dict(self, sd: dict) -> None:
+        """Continue from a :meth:`state_dict` of a ring of the same geometry: exact copies; host-synchronous."""
+        b = self.batch
+        try:
+            geometry = tuple(int(x) for x in sd["geometry"])
+            src = {k: sd[k] for k in _ARRAYS + ("state",)}
+        except (KeyError, TypeError, ValueError):
+            raise ValueError("not a ReplayRing state_dict (keys " + ", ".join(_ARRAYS) + ", state, geometry)") from None
+        if geometry != (self.steps, b.num_envs, b.num_agents):
+            raise ValueError(f"the state_dict is of a ring of (steps, envs, agents) = {geometry}, this one is "
+                             f"{(self.steps, b.num_envs, b.num_agents)}")
+        for k, s in src.items():
+            d = getattr(self, k)
+            if not isinstance(s, torch.Tensor) or s.dtype is not d.dtype or s.shape != d.shape:
+                raise ValueError(f"state_dict {k} must be a {d.dtype} tensor of shape {tuple(d.shape)}")
+        b.synchronize()
+        for k, s in src.items():
+            getattr(self, k).copy_(s)
+        torch.cuda.synchronize(b.device)

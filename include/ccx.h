@@ -1121,8 +1121,8 @@ int ccx_sides_backward(ccx_handle* h, int64_t M, int32_t N, uint64_t slots, int3
  * a HIP graph.  Offsets are 64-bit.  A NULL handle or a NULL required pointer, rows < 1 (or so many that a grid would pass
  * 2^31 - 1 workgroups), a Q array or grad_q that is not 16-byte aligned, a workspace that is not 8-byte aligned, a gamma that
  * is not finite or lies outside [0, 1], a huber_delta that is not > 0: CCX_EINVAL with a ccx_last_error message, before any
- * launch.  Not here: a dueling combine, n-step targets, distributional heads, a replay buffer or prioritised sampling
- * (weights and td_error are its two hooks), the fusion of the head's forward with the action choice, bf16 / f16.
+ * launch.  Not here: a dueling combine, n-step targets, distributional heads, prioritised sampling (weights and td_error
+ * are its two hooks; the replay buffer itself is CCX_REPLAY), the fusion of the head's forward with the action choice, bf16 / f16.
  */
 int ccx_q_actions(ccx_handle* h, const float* q /* [E][N][5] */, const uint8_t* masks_or_null /* [E][N] */,
                   const float* epsilon_or_null /* device f32 [1]; NULL = greedy */, uint8_t* actions /* [E][N] */,
@@ -1139,6 +1139,82 @@ int ccx_td_loss_backward(ccx_handle* h, int64_t rows, const float* q /* [M][5] *
                          const uint8_t* valid_or_null /* [M] */, const float* weights_or_null /* [M] */, float gamma,
                          float huber_delta, const float* stats /* [8] */, const float* grad_loss_or_null /* [1] */,
                          float* grad_q /* [M][5] */);
+/*
+ * CCX_REPLAY: the replay memory of an off-policy loop on the device -- a ring of COMPACT env-step records whose cursor lives
+ * on the device, filled from a rollout's own arrays (ccx_replay_push), and ONE kernel that draws B records with the
+ * library's counter-based word and writes the minibatch as DefaultObservation rows plus the small arrays ccx_td_loss takes
+ * (ccx_replay_sample; ccx_replay_fetch is the same kernel on the caller's record indices).  Everything is integer work and
+ * copies: every output is bit-defined.
+ *
+ * The ring belongs to the caller and travels as arguments: ring_steps = S >= 1 steps of the handle's E envs, R = S E < 2^31
+ * records, struct of arrays -- obs_c and next_c f32 [R][N][4] (CCX_OBS_COMPACT records, 16-byte aligned), actions u8, reward
+ * f64, done u8, valid u8, masks_next u8, each [R][N], and state i64 [4] = {head, draws, 0, 0}.  One record is 44 N bytes; the
+ * same env-step as two DefaultObservation rows per agent and the small fields is N (2 (24 + 16 N) + 12) bytes (N = 8: 352
+ * against 2 528; N = 32: 1 408 against 34 688).  The EMPTY record, which the caller initialises the ring to (with head =
+ * draws = 0): actions = CCX_ACTION_ABSENT, done = valid = 0, reward = +0.0, masks_next = 0x10, both compact records +0.0.
+ *
+ * ccx_replay_push.  A block of K steps, 1 <= K <= S: obs0_compact f32 [E][N][4] (the compact observation step 0 acted on),
+ * actions u8 [K][E][N], and a rollout's reward f64 [K][E][N], agent_flags u8 [K][E][N], env_flags u8 [K][E], obs_compact f32
+ * [K][E][N][4], final_compact (the same shape) or NULL, and masks_next u8 [K][E][N] or NULL (the legal set behind each step).
+ * With head = state[0] READ ON THE DEVICE when the kernel runs, the record of step s and env e goes to slot
+ *     ((head + s) mod S) * E + e
+ * with, per agent slot,
+ *     obs_c      = s == 0 ? obs0_compact[e] : obs_compact[s - 1][e]
+ *     reset      = final_compact != NULL && (env_flags[s][e] & CCX_EF_RESET)
+ *     next_c     = reset ? final_compact[s][e] : obs_compact[s][e]
+ *     actions, reward: copied bit for bit
+ *     done       = agent_flags & CCX_AF_TERMINATED          (0 / 1)
+ *     valid      = agent_flags & CCX_AF_LIVE                (0 / 4)
+ *     masks_next = (reset || masks_next == NULL) ? 0x1F : masks_next[s][e]
+ * and then head += K.  K <= S makes the K slots distinct: a block may wrap inside itself, and K == S rewrites the whole
+ * ring.  The records mean what they say only for a rollout made with CCX_RESET_OBS_NEXT (obs_compact[s][e] of a restarted env
+ * is then the new episode's first observation, and final_compact[s][e] the one the step ended on): the caller's contract,
+ * the library cannot see it.
+ *
+ * ccx_replay_sample.  With F = min(head, S) * E and d = draws = state[1], both read on the device when the kernel runs, and
+ * the seed of ccx_set_rng_seed, for b = 0 .. B - 1 (1 <= B <= 2^31 / N):
+ *     w0 = word(seed_lo, seed_hi ^ 0x3C6EF372; (u32)b, (u32)d, (u32)(d >> 32), 0)     (the k of ccx_set_rng_seed's formula)
+ *     w1 = the same with 1 as the last key
+ *     index[b] = F == 0 ? -1 : (i64)((((u64)w0 << 32) | w1) * F >> 64)               (the high half of the 128-bit product)
+ * and then draws += 1.  The key holds neither env nor shard; draws are with replacement; the bias is below F / 2^64.  The
+ * stream constant differs from 0, 0x5BD1E995, 0x2545F491, 0x68E31DA4 and 0xB5297A4D.  The minibatch is the same for any split
+ * of the pushes into calls, eager or captured, and needs nothing from any other generator.  ccx_replay_fetch takes index
+ * i64 [B] from the caller instead (and writes it to the index output, which may be the same array) and leaves draws alone.
+ *
+ * Gather (both).  Row b of every output is a copy of the fields of record index[b], bit for bit, and every element of every
+ * output given is written: actions u8, reward f64, done u8, valid u8, masks_next u8, each [B][N], index i64 [B], and obs /
+ * next_obs f32 [B][N][ccx_obs_len(N)] (each may be NULL; 16-byte aligned), the N DefaultObservation rows of the record's
+ * obs_c / next_c: the very gather of ccx_observe and ccx_expand_observations with the handle's row constants, hence the bits
+ * of ccx_expand_observations on those compact records.  An index outside [0, R) -- the -1 of an empty ring included -- gives
+ * the EMPTY record and reads nothing; its rows are the rows of compact records of +0.0, like those of an empty slot.  An
+ * index in [F, R) reads what is there: the empty record until the ring is full.
+ *
+ * Launches: ccx_replay_push and ccx_replay_sample enqueue TWO kernels on the handle's stream -- the main one, and one plain
+ * lane behind it that adds to head / draws, so the update cannot race with the lanes that read the old value (no atomic, no
+ * last-block-done counter); ccx_replay_fetch ONE.  No host synchronisation, no allocation; everything captures into a HIP
+ * graph, and a captured push / sample advances with every replay.  Offsets are 64-bit.  A NULL handle or required pointer, S
+ * < 1 or S E >= 2^31, K outside 1..S, B outside 1..2^31 / N, a compact or row array that is not 16-byte aligned, an f64 / i64
+ * array that is not 8-byte aligned: CCX_EINVAL with a ccx_last_error message, before any launch.  Not here: prioritised or
+ * recency-weighted sampling (index, ccx_replay_fetch and ccx_td_loss's weights / td_error are the hooks), sampling without
+ * replacement, n-step returns, frames shared between obs_c and next_c, records of single agents or of sequences, a ring over
+ * several GPUs (each shard has its own), rows-form storage, bf16 / f16.
+ */
+int ccx_replay_push(ccx_handle* h, int64_t ring_steps, float* ring_obs_c /* [R][N][4] */, float* ring_next_c /* [R][N][4] */,
+                    uint8_t* ring_actions /* [R][N] */, double* ring_reward /* [R][N] */, uint8_t* ring_done /* [R][N] */,
+                    uint8_t* ring_valid /* [R][N] */, uint8_t* ring_masks_next /* [R][N] */, int64_t* ring_state /* [4] */,
+                    int64_t K, const float* obs0_compact /* [E][N][4] */, const uint8_t* actions /* [K][E][N] */,
+                    const double* reward /* [K][E][N] */, const uint8_t* agent_flags /* [K][E][N] */,
+                    const uint8_t* env_flags /* [K][E] */, const float* obs_compact /* [K][E][N][4] */,
+                    const float* final_compact_or_null /* [K][E][N][4] */, const uint8_t* masks_next_or_null /* [K][E][N] */);
+int ccx_replay_sample(ccx_handle* h, int64_t ring_steps, float* ring_obs_c, float* ring_next_c, uint8_t* ring_actions,
+                      double* ring_reward, uint8_t* ring_done, uint8_t* ring_valid, uint8_t* ring_masks_next, int64_t* ring_state,
+                      int64_t batch, float* obs_or_null /* [B][N][L] */, float* next_obs_or_null /* [B][N][L] */,
+                      uint8_t* actions /* [B][N] */, double* reward /* [B][N] */, uint8_t* done /* [B][N] */,
+                      uint8_t* valid /* [B][N] */, uint8_t* masks_next /* [B][N] */, int64_t* index /* [B] */);
+int ccx_replay_fetch(ccx_handle* h, int64_t ring_steps, float* ring_obs_c, float* ring_next_c, uint8_t* ring_actions,
+                     double* ring_reward, uint8_t* ring_done, uint8_t* ring_valid, uint8_t* ring_masks_next, int64_t* ring_state,
+                     int64_t batch, const int64_t* index_in /* [B] */, float* obs_or_null, float* next_obs_or_null,
+                     uint8_t* actions, double* reward, uint8_t* done, uint8_t* valid, uint8_t* masks_next, int64_t* index);
 /*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
