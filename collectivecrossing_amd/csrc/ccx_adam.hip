@@ -23,6 +23,7 @@
 #include "ccx_adam.h"
 
 using ccxi::fail;
+using ccxi::misaligned;
 
 static_assert(sizeof(ccx_adam::Tensor) == sizeof(ccx_adam_tensor) && sizeof(ccx_adam_tensor) == 40, "the table row is 40 bytes");
 static_assert(sizeof(ccx_adam::State) == 64 && sizeof(ccx_adam::Scalars) == 64, "state and scalars are 64 bytes each");
@@ -129,17 +130,14 @@ int ccx_adam_step(ccx_handle* h, int32_t num_tensors, const ccx_adam_tensor* ten
         if (!x.param || !x.grad || !x.m || !x.v) return fail(CCX_EINVAL, "ccx_adam_step: tensor %d has a NULL pointer", (int)k);
         if (x.numel < 1 || x.numel > (int64_t)1 << 40)
             return fail(CCX_EINVAL, "ccx_adam_step: tensor %d: numel must lie in 1..2^40, got %lld", (int)k, (long long)x.numel);
-        if ((reinterpret_cast<uintptr_t>(x.param) | reinterpret_cast<uintptr_t>(x.grad) | reinterpret_cast<uintptr_t>(x.m) |
-             reinterpret_cast<uintptr_t>(x.v)) & 15u)
+        if (misaligned(16, x.param, x.grad, x.m, x.v))
             return fail(CCX_EINVAL, "ccx_adam_step: tensor %d: param, grad, m and v must be 16-byte aligned", (int)k);
         A.tab[k] = ccx_adam::Tensor{x.param, x.grad, x.m, x.v, (long long)x.numel};
         B += ccx_adam::blocks_of(x.numel);
     }
     if (B > 0x7fffffffLL) return fail(CCX_EINVAL, "ccx_adam_step: %lld blocks of 256 elements exceed a grid of 2^31 - 1", (long long)B);
-    if ((reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(workspace)) & 7u)
-        return fail(CCX_EINVAL, "ccx_adam_step: state and workspace must be 8-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(stats) | reinterpret_cast<uintptr_t>(lr_dev_or_null)) & 3u)
-        return fail(CCX_EINVAL, "ccx_adam_step: stats and lr_dev must be 4-byte aligned");
+    if (misaligned(8, state, workspace)) return fail(CCX_EINVAL, "ccx_adam_step: state and workspace must be 8-byte aligned");
+    if (misaligned(4, stats, lr_dev_or_null)) return fail(CCX_EINVAL, "ccx_adam_step: stats and lr_dev must be 4-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     A.T = num_tensors;
     A.has_clip = max_grad_norm > 0.0f;

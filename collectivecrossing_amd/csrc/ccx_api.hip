@@ -44,6 +44,7 @@ int row_blocks(const char* who, int64_t rows, int64_t rows_per_block, unsigned& 
 }
 }  // namespace ccxi
 using ccxi::fail;
+using ccxi::misaligned;
 using ccxp::ceil_log2;
 
 namespace {
@@ -319,13 +320,11 @@ ccx::KOut kout_at(const ccx_handle* h, const ccx::KOut& ko, int s) {
     return o;
 }
 
-bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1u)) != 0; }
-
 // the kernels store rows in 16-byte units (ccx_step_finish with an odd agent count: 8) and rewards as doubles
 int check_out_align(const ccx::KOut& ko, unsigned obs_align = 16, const char* reward_what = "reward buffer") {
-    if (misaligned(ko.obs, obs_align)) return fail(CCX_EINVAL, "obs buffer must be %u-byte aligned", obs_align);
-    if (misaligned(ko.reward, 8)) return fail(CCX_EINVAL, "%s must be 8-byte aligned", reward_what);
-    if (misaligned(ko.obs_compact, 16)) return fail(CCX_EINVAL, "obs_compact buffer must be 16-byte aligned");
+    if (misaligned(obs_align, ko.obs)) return fail(CCX_EINVAL, "obs buffer must be %u-byte aligned", obs_align);
+    if (misaligned(8, ko.reward)) return fail(CCX_EINVAL, "%s must be 8-byte aligned", reward_what);
+    if (misaligned(16, ko.obs_compact)) return fail(CCX_EINVAL, "obs_compact buffer must be 16-byte aligned");
     return CCX_OK;
 }
 
@@ -481,8 +480,8 @@ int check_reset_obs(const ccx_handle* h, const ccx::KOut& ko, int auto_reset) {
         return fail(CCX_EINVAL, "CCX_RESET_OBS_NEXT: a call with auto-reset that asks for obs or obs_compact must pass env_flags "
                     "too (the restarted envs are found there)");
     const unsigned align = (h->N % 2) == 0 ? 16u : 8u;
-    if (ko.obs && misaligned(h->bound_final_obs, align)) return fail(CCX_EINVAL, "final_obs buffer must be %u-byte aligned", align);
-    if (ko.obs_compact && misaligned(h->bound_final_compact, 16))
+    if (ko.obs && misaligned(align, h->bound_final_obs)) return fail(CCX_EINVAL, "final_obs buffer must be %u-byte aligned", align);
+    if (ko.obs_compact && misaligned(16, h->bound_final_compact))
         return fail(CCX_EINVAL, "final_compact buffer must be 16-byte aligned");
     return CCX_OK;
 }
@@ -533,7 +532,7 @@ Launched run_stepwise(ccx_handle* h, const StepCall& c, const char* what, Produc
         StepCall step{1, acts, c.order ? c.order + (size_t)s * EN : nullptr, c.auto_reset, kout_at(h, c.out, s)};
         step.inputs_checked = c.inputs_checked;
         float* const obs_dst = step.out.obs;
-        const bool staged = misaligned(obs_dst, 16);
+        const bool staged = misaligned(16, obs_dst);
         if (staged) {
             if (!h->stream_obs) return fail(CCX_EINVAL, "obs buffer must be 16-byte aligned");   // (a misaligned BASE)
             step.out.obs = h->stream_obs;
@@ -749,7 +748,7 @@ int ccx_set_reset_pool(ccx_handle* h, const uint8_t* pool_xy, int64_t pool_size)
     if (!h) return fail(CCX_EINVAL, "NULL handle");
     if ((pool_xy == nullptr) != (pool_size == 0) || pool_size < 0 || pool_size >= (1ll << 31))
         return fail(CCX_EINVAL, "bad reset pool (ptr %p, size %lld)", (const void*)pool_xy, (long long)pool_size);
-    if (reinterpret_cast<uintptr_t>(pool_xy) & 1u) return fail(CCX_EINVAL, "pool must be 2-byte aligned");
+    if (misaligned(2, pool_xy)) return fail(CCX_EINVAL, "pool must be 2-byte aligned");
     h->pool = pool_xy;
     h->pool_size = pool_size;
     return choose_shape(h);
@@ -826,7 +825,7 @@ int ccx_greedy_actions(ccx_handle* h, uint8_t* actions) {
 
 int ccx_observe(ccx_handle* h, float* obs) {
     if (!h || !obs) return fail(CCX_EINVAL, "NULL argument");
-    if (reinterpret_cast<uintptr_t>(obs) & 15u) return fail(CCX_EINVAL, "obs buffer must be 16-byte aligned");
+    if (misaligned(16, obs)) return fail(CCX_EINVAL, "obs buffer must be 16-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     hipError_t e = ccx::launch_observe(h->shape, h->stream, h->kp, h->st, obs);
     if (e != hipSuccess) return fail(CCX_EHIP, "observe kernel launch failed: %s", hipGetErrorString(e));
@@ -836,7 +835,7 @@ int ccx_observe(ccx_handle* h, float* obs) {
 int ccx_expand_observations(ccx_handle* h, const float* obs_compact, int64_t rows, float* obs) {
     if (!h || !obs_compact || !obs) return fail(CCX_EINVAL, "NULL argument");
     if (rows < 0 || rows * (int64_t)h->N >= (1ll << 31)) return fail(CCX_EINVAL, "rows = %lld out of range", (long long)rows);
-    if ((reinterpret_cast<uintptr_t>(obs) | reinterpret_cast<uintptr_t>(obs_compact)) & 15u)
+    if (misaligned(16, obs, obs_compact))
         return fail(CCX_EINVAL, "obs and obs_compact must be 16-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     hipError_t e = ccx::launch_expand(h->shape, h->stream, h->kp, obs_compact, rows, obs);
@@ -870,7 +869,7 @@ int ccx_step_finish(ccx_handle* h, const double* reward, const int8_t* terminate
     const ccx::KOut ko = kout_of(out);
     // (odd agent counts write the rows in 8-byte units: csrc/ccx_split_step.hip, PAIR = false)
     rc = check_out_align(ko, (h->N % 2) == 0 ? 16 : 8, "reward buffers");
-    if (!rc && misaligned(reward, 8)) rc = fail(CCX_EINVAL, "reward buffers must be 8-byte aligned");
+    if (!rc && misaligned(8, reward)) rc = fail(CCX_EINVAL, "reward buffers must be 8-byte aligned");
     if (!rc) rc = check_reset_obs(h, ko, auto_reset);
     if (rc) return rc;
     CCX_HIP(hipSetDevice(h->device));

@@ -388,18 +388,10 @@ int ccx_episode_stats_update(ccx_handle* h, int32_t num_steps, const double* rew
                                h->stats_base, (unsigned long long*)h->stats.log_count, (long long)h->stats.log_capacity);
             break;
         case STAGE_ACCUMULATE:
-            if (plan.log && naive)
-                hipLaunchKernelGGL((stats_accumulate<true, true>), dim3(blocks), dim3(64), 0, h->stream, A, num_steps,
-                                   reward, agent_flags, env_flags, base);
-            else if (plan.log)
-                hipLaunchKernelGGL((stats_accumulate<true, false>), dim3(blocks), dim3(64), 0, h->stream, A, num_steps,
-                                   reward, agent_flags, env_flags, base);
-            else if (naive)
-                hipLaunchKernelGGL((stats_accumulate<false, true>), dim3(blocks), dim3(64), 0, h->stream, A, num_steps,
-                                   reward, agent_flags, env_flags, base);
-            else
-                hipLaunchKernelGGL((stats_accumulate<false, false>), dim3(blocks), dim3(64), 0, h->stream, A, num_steps,
-                                   reward, agent_flags, env_flags, base);
+            ccxi::with_flags([&](auto log, auto nv) {
+                hipLaunchKernelGGL((stats_accumulate<decltype(log)::value, decltype(nv)::value>), dim3(blocks), dim3(64), 0,
+                                   h->stream, A, num_steps, reward, agent_flags, env_flags, base);
+            }, plan.log, naive);
             break;
         }
     }

@@ -10,6 +10,8 @@
 #include "ccx_softmax.h"
 
 using ccxi::fail;
+using ccxi::misaligned;
+using ccxi::with_flags;
 
 namespace {
 
@@ -28,14 +30,12 @@ struct EvalArgs {
 template <bool MASK, bool ENT>
 __global__ __launch_bounds__(64) void evaluate_fwd_kernel(const EvalArgs A) {
     __shared__ float4 pieces[80];
-    const uint32_t lane = threadIdx.x;
-    const long long row = (long long)blockIdx.x * 64 + lane;
-    const long long rl = row < A.M ? row : A.M - 1;                     // the tail wave's surplus lanes load what its last row loads
+    const ccx_rows::Wave W = ccx_rows::wave_of(A.M, blockIdx.x, threadIdx.x);
+    const long long row = W.row, rl = W.rl;                             // the tail wave's surplus lanes load what its last row loads
     const uint32_t a = A.actions[rl];
     const uint32_t mbyte = MASK ? (uint32_t)A.masks[rl] : 0x1Fu;
-    const long long floats = A.M * 5, last_piece = floats / 4 - 1;      // M >= 1: at least one whole piece
     float l[5];
-    ccx_rows::load_rows(A.logits, A.M, pieces, lane, blockIdx.x, row, floats, last_piece, l);
+    ccx_rows::load_rows(A.logits, pieces, W, l);
     if (row >= A.M) return;
     float logp, entropy = 0.0f;
     ccx_softmax::evaluate_row<ENT>(l, mbyte, a, logp, entropy);
@@ -46,18 +46,16 @@ __global__ __launch_bounds__(64) void evaluate_fwd_kernel(const EvalArgs A) {
 template <bool MASK, bool GLP, bool GENT>
 __global__ __launch_bounds__(64) void evaluate_bwd_kernel(const EvalArgs A) {
     __shared__ float4 pieces[80];
-    const uint32_t lane = threadIdx.x;
-    const long long row = (long long)blockIdx.x * 64 + lane;
-    const long long rl = row < A.M ? row : A.M - 1;
+    const ccx_rows::Wave W = ccx_rows::wave_of(A.M, blockIdx.x, threadIdx.x);
+    const long long rl = W.rl;
     const uint32_t a = A.actions[rl];
     const uint32_t mbyte = MASK ? (uint32_t)A.masks[rl] : 0x1Fu;
     const float glp = GLP ? A.grad_logp[rl] : 0.0f;
     const float gent = GENT ? A.grad_entropy[rl] : 0.0f;
-    const long long floats = A.M * 5, last_piece = floats / 4 - 1;
     float l[5], g[5];
-    ccx_rows::load_rows(A.logits, A.M, pieces, lane, blockIdx.x, row, floats, last_piece, l);
+    ccx_rows::load_rows(A.logits, pieces, W, l);
     ccx_softmax::evaluate_row_backward<GLP, GENT>(l, mbyte, a, glp, gent, g);
-    ccx_rows::store_rows(A.grad_logits, A.M, pieces, lane, blockIdx.x, row, floats, last_piece, g);
+    ccx_rows::store_rows(A.grad_logits, pieces, W, g);
 }
 
 }  // namespace
@@ -71,7 +69,7 @@ int ccx_evaluate_actions(ccx_handle* h, int64_t rows, const float* logits, const
         return fail(CCX_EINVAL, "ccx_evaluate_actions: NULL argument (logits, actions and logp are required)");
     unsigned blocks = 0;
     if (int rc = ccxi::row_blocks("ccx_evaluate_actions", rows, 64, blocks)) return rc;
-    if (reinterpret_cast<uintptr_t>(logits) & 15u) return fail(CCX_EINVAL, "ccx_evaluate_actions: logits must be 16-byte aligned");
+    if (misaligned(16, logits)) return fail(CCX_EINVAL, "ccx_evaluate_actions: logits must be 16-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     EvalArgs A{};
     A.logits = logits;
@@ -81,13 +79,9 @@ int ccx_evaluate_actions(ccx_handle* h, int64_t rows, const float* logits, const
     A.entropy = entropy_or_null;
     A.M = rows;
     const dim3 grid(blocks), block(64);
-    if (masks_or_null) {
-        if (entropy_or_null) hipLaunchKernelGGL((evaluate_fwd_kernel<true, true>), grid, block, 0, h->stream, A);
-        else hipLaunchKernelGGL((evaluate_fwd_kernel<true, false>), grid, block, 0, h->stream, A);
-    } else {
-        if (entropy_or_null) hipLaunchKernelGGL((evaluate_fwd_kernel<false, true>), grid, block, 0, h->stream, A);
-        else hipLaunchKernelGGL((evaluate_fwd_kernel<false, false>), grid, block, 0, h->stream, A);
-    }
+    with_flags([&](auto mask, auto ent) {
+        hipLaunchKernelGGL((evaluate_fwd_kernel<decltype(mask)::value, decltype(ent)::value>), grid, block, 0, h->stream, A);
+    }, masks_or_null != nullptr, entropy_or_null != nullptr);
     CCX_HIP(hipGetLastError());
     return CCX_OK;
 }
@@ -102,7 +96,7 @@ int ccx_evaluate_actions_backward(ccx_handle* h, int64_t rows, const float* logi
         return fail(CCX_EINVAL, "ccx_evaluate_actions_backward: both gradients are NULL (at least one of grad_logp, grad_entropy is required)");
     unsigned blocks = 0;
     if (int rc = ccxi::row_blocks("ccx_evaluate_actions_backward", rows, 64, blocks)) return rc;
-    if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(grad_logits)) & 15u)
+    if (misaligned(16, logits, grad_logits))
         return fail(CCX_EINVAL, "ccx_evaluate_actions_backward: logits and grad_logits must be 16-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     EvalArgs A{};
@@ -114,16 +108,11 @@ int ccx_evaluate_actions_backward(ccx_handle* h, int64_t rows, const float* logi
     A.grad_logits = grad_logits;
     A.M = rows;
     const dim3 grid(blocks), block(64);
-    const int which = (grad_logp_or_null ? 1 : 0) | (grad_entropy_or_null ? 2 : 0);
-    if (masks_or_null) {
-        if (which == 3) hipLaunchKernelGGL((evaluate_bwd_kernel<true, true, true>), grid, block, 0, h->stream, A);
-        else if (which == 1) hipLaunchKernelGGL((evaluate_bwd_kernel<true, true, false>), grid, block, 0, h->stream, A);
-        else hipLaunchKernelGGL((evaluate_bwd_kernel<true, false, true>), grid, block, 0, h->stream, A);
-    } else {
-        if (which == 3) hipLaunchKernelGGL((evaluate_bwd_kernel<false, true, true>), grid, block, 0, h->stream, A);
-        else if (which == 1) hipLaunchKernelGGL((evaluate_bwd_kernel<false, true, false>), grid, block, 0, h->stream, A);
-        else hipLaunchKernelGGL((evaluate_bwd_kernel<false, false, true>), grid, block, 0, h->stream, A);
-    }
+    with_flags([&](auto mask, auto glp, auto gent) {
+        constexpr bool MASK = decltype(mask)::value, GLP = decltype(glp)::value, GENT = decltype(gent)::value;
+        if constexpr (GLP || GENT)                                      // (both null was refused above)
+            hipLaunchKernelGGL((evaluate_bwd_kernel<MASK, GLP, GENT>), grid, block, 0, h->stream, A);
+    }, masks_or_null != nullptr, grad_logp_or_null != nullptr, grad_entropy_or_null != nullptr);
     CCX_HIP(hipGetLastError());
     return CCX_OK;
 }

@@ -166,15 +166,9 @@ int ccx_gae(ccx_handle* h, int32_t num_steps, const double* reward, const uint8_
     A.gamma = gamma;
     A.gl = gamma * lam;                                             // one f32 multiply (-ffp-contract=off)
     const unsigned blocks = (unsigned)((A.EN + GAE_LANES - 1) / GAE_LANES);
-    const bool fin = final_values_or_null != nullptr, val = valid_or_null != nullptr;
-    if (fin && val)
-        hipLaunchKernelGGL((gae_kernel<true, true>), dim3(blocks), dim3(64), 0, h->stream, A);
-    else if (fin)
-        hipLaunchKernelGGL((gae_kernel<true, false>), dim3(blocks), dim3(64), 0, h->stream, A);
-    else if (val)
-        hipLaunchKernelGGL((gae_kernel<false, true>), dim3(blocks), dim3(64), 0, h->stream, A);
-    else
-        hipLaunchKernelGGL((gae_kernel<false, false>), dim3(blocks), dim3(64), 0, h->stream, A);
+    ccxi::with_flags([&](auto fin, auto val) {
+        hipLaunchKernelGGL((gae_kernel<decltype(fin)::value, decltype(val)::value>), dim3(blocks), dim3(64), 0, h->stream, A);
+    }, final_values_or_null != nullptr, valid_or_null != nullptr);
     CCX_HIP(hipGetLastError());
     return CCX_OK;
 }

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/ccx.h"
+#include "ccx_entry.h"
 #include "ccx_kernels.h"
 
 namespace ccxi {

@@ -18,6 +18,8 @@ using ccx_tile::allow_lds;
 using ccx_tile::lds_floats;
 using ccx_tile::mlp_tile;
 using ccxi::fail;
+using ccxi::misaligned;
+using ccxi::with_flags;
 
 namespace {
 
@@ -61,10 +63,8 @@ int ccx_mlp_forward(ccx_handle* h, int64_t rows, int32_t L, int32_t H, int32_t O
     if (!h) return fail(CCX_EINVAL, "NULL handle");
     if (!x || !w1t || !b1 || !w2 || !b2 || !y) return fail(CCX_EINVAL, "ccx_mlp_forward: NULL argument (only hidden may be NULL)");
     if (const int rc = check_shape("ccx_mlp_forward", rows, L, H, O, activation)) return rc;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hidden_or_null)) & 15u)
-        return fail(CCX_EINVAL, "ccx_mlp_forward: x and hidden must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(w1t) | reinterpret_cast<uintptr_t>(b1) | reinterpret_cast<uintptr_t>(w2) |
-         reinterpret_cast<uintptr_t>(b2) | reinterpret_cast<uintptr_t>(y)) & 3u)
+    if (misaligned(16, x, hidden_or_null)) return fail(CCX_EINVAL, "ccx_mlp_forward: x and hidden must be 16-byte aligned");
+    if (misaligned(4, w1t, b1, w2, b2, y))
         return fail(CCX_EINVAL, "ccx_mlp_forward: w1t, b1, w2, b2 and y must be 4-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     const MlpArgs A{x, w1t, b1, w2, b2, y, hidden_or_null, (long long)rows, L, H, O, activation};
@@ -84,30 +84,21 @@ int ccx_mlp_sample_actions(ccx_handle* h, int32_t H, int32_t activation, const f
     const int32_t L = ccx_obs_len(h->N);
     const int64_t rows = (int64_t)h->E * h->N;
     if (const int rc = check_shape("ccx_mlp_sample_actions", rows, L, H, 5, activation)) return rc;
-    if (reinterpret_cast<uintptr_t>(obs) & 15u) return fail(CCX_EINVAL, "ccx_mlp_sample_actions: obs must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(w1t) | reinterpret_cast<uintptr_t>(b1) | reinterpret_cast<uintptr_t>(w2) |
-         reinterpret_cast<uintptr_t>(b2) | reinterpret_cast<uintptr_t>(logp_or_null) | reinterpret_cast<uintptr_t>(entropy_or_null) |
-         reinterpret_cast<uintptr_t>(logits_or_null)) & 3u)
+    if (misaligned(16, obs)) return fail(CCX_EINVAL, "ccx_mlp_sample_actions: obs must be 16-byte aligned");
+    if (misaligned(4, w1t, b1, w2, b2, logp_or_null, entropy_or_null, logits_or_null))
         return fail(CCX_EINVAL, "ccx_mlp_sample_actions: w1t, b1, w2, b2, logp, entropy and logits must be 4-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     const MlpArgs A{obs, w1t, b1, w2, b2, logits_or_null, nullptr, (long long)rows, L, H, 5, activation};
     const DrawArgs D = ccx_draw::draw_args(h, masks_or_null, actions, logp_or_null, entropy_or_null);
     const size_t bytes = lds_floats(L, H, 5, true) * sizeof(float);
     const dim3 grid((unsigned)((rows + 63) / 64)), block(64 * (H / ccx_mlp::kGroup));
-    const bool stats = logp_or_null || entropy_or_null, det = deterministic != 0;
-#define CCX_MLP_DRAW(DET, STATS)                                                                  \
-    do {                                                                                          \
-        CCX_HIP(allow_lds(mlp_draw_kernel<DET, STATS>, bytes));                                   \
-        hipLaunchKernelGGL((mlp_draw_kernel<DET, STATS>), grid, block, bytes, h->stream, A, D);   \
-    } while (0)
-    if (det) {
-        if (stats) CCX_MLP_DRAW(true, true);
-        else CCX_MLP_DRAW(true, false);
-    } else {
-        if (stats) CCX_MLP_DRAW(false, true);
-        else CCX_MLP_DRAW(false, false);
-    }
-#undef CCX_MLP_DRAW
+    const int rc = with_flags([&](auto det, auto stats) -> int {
+        constexpr bool DET = decltype(det)::value, STATS = decltype(stats)::value;
+        CCX_HIP(allow_lds(mlp_draw_kernel<DET, STATS>, bytes));
+        hipLaunchKernelGGL((mlp_draw_kernel<DET, STATS>), grid, block, bytes, h->stream, A, D);
+        return CCX_OK;
+    }, deterministic != 0, logp_or_null || entropy_or_null);
+    if (rc) return rc;
     CCX_HIP(hipGetLastError());
     return CCX_OK;
 }

@@ -27,9 +27,11 @@
 // call and head_grad_final_kernel finishes them as it is.
 #include "ccx_internal.h"
 #include "ccx_mlp_grad.h"
+#include "ccx_mlp_tile.h"                                                // (the shape check only: ccx_tile::check_dims)
 #include "ccx_sides.h"
 
 using ccxi::fail;
+using ccxi::misaligned;
 namespace mg = ccx_mlp_grad;
 
 namespace {
@@ -278,15 +280,10 @@ int backward_launches(const char* who, ccx_handle* h, int64_t rows, const SideSe
         return fail(CCX_EINVAL, "%s: NULL argument (only grad_a may be NULL)", who);
     unsigned blocks = 0;
     if (int rc = ccxi::row_blocks(who, rows, mg::kBlockRows, blocks)) return rc;
-    if (!ccx_mlp::shape_ok(L, H, O, activation))
-        return fail(CCX_EINVAL, "%s: L = %d, H = %d, O = %d, activation = %d: 1 <= L <= %d, H a multiple of 16 in 16..%d, "
-                    "1 <= O <= %d and activation 0 (tanh) or 1 (relu) are required", who, L, H, O, activation, ccx_mlp::kMaxL, ccx_mlp::kMaxH,
-                    ccx_mlp::kMaxO);
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hidden) | reinterpret_cast<uintptr_t>(grad_a_or_null)) & 15u)
-        return fail(CCX_EINVAL, "%s: x, hidden and grad_a must be 16-byte aligned", who);
-    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "%s: workspace must be 8-byte aligned", who);
-    if ((reinterpret_cast<uintptr_t>(grad_y) | reinterpret_cast<uintptr_t>(w2) | reinterpret_cast<uintptr_t>(grad_w1t) |
-         reinterpret_cast<uintptr_t>(grad_b1) | reinterpret_cast<uintptr_t>(grad_w2) | reinterpret_cast<uintptr_t>(grad_b2)) & 3u)
+    if (int rc = ccx_tile::check_dims(who, L, H, O, activation)) return rc;
+    if (misaligned(16, x, hidden, grad_a_or_null)) return fail(CCX_EINVAL, "%s: x, hidden and grad_a must be 16-byte aligned", who);
+    if (misaligned(8, workspace)) return fail(CCX_EINVAL, "%s: workspace must be 8-byte aligned", who);
+    if (misaligned(4, grad_y, w2, grad_w1t, grad_b1, grad_w2, grad_b2))
         return fail(CCX_EINVAL, "%s: grad_y, w2, grad_w1t, grad_b1, grad_w2 and grad_b2 must be 4-byte aligned", who);
     CCX_HIP(hipSetDevice(h->device));
     size_t bytes = 0;

@@ -17,6 +17,8 @@
 #include "ccx_rows.h"
 
 using ccxi::fail;
+using ccxi::misaligned;
+using ccxi::with_flags;
 
 namespace {
 
@@ -53,9 +55,8 @@ __global__ __launch_bounds__(256) void ppo_partial_kernel(const PpoArgs A) {
     __shared__ float4 pieces[ccx_tree::kBlockGroups][80];
     __shared__ double groups[ccx_ppo::kSums][ccx_tree::kBlockGroups];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const long long wave = (long long)blockIdx.x * ccx_tree::kBlockGroups + w;
-    const long long row = wave * 64 + lane;
-    const long long rl = row < A.M ? row : A.M - 1;                     // surplus lanes load what the last row loads
+    const ccx_rows::Wave W = ccx_rows::wave_of(A.M, (long long)blockIdx.x * ccx_tree::kBlockGroups + w, lane);
+    const long long row = W.row, rl = W.rl;                             // surplus lanes load what the last row loads
     const uint32_t a = A.actions[rl];
     const uint32_t mbyte = MASK ? (uint32_t)A.masks[rl] : 0x1Fu;
     const bool has_valid = A.valid != nullptr, has_norm = A.norm != nullptr;
@@ -66,9 +67,8 @@ __global__ __launch_bounds__(256) void ppo_partial_kernel(const PpoArgs A) {
         mean = A.norm[0];
         denom = A.norm[1] + A.adv_eps;
     }
-    const long long floats = A.M * 5, last_piece = floats / 4 - 1;      // M >= 1: at least one whole piece
     float l[5];
-    ccx_rows::load_rows(A.logits, A.M, pieces[w], lane, wave, row, floats, last_piece, l);
+    ccx_rows::load_rows(A.logits, pieces[w], W, l);
     const bool counts = row < A.M && ccx_ppo::row_counts(has_valid, vbyte, a);
     const float an = ccx_ppo::normalised(has_norm, adv, mean, denom);
     ccx_ppo::Row t;
@@ -95,7 +95,7 @@ __global__ __launch_bounds__(64) void ppo_bwd_kernel(const PpoArgs A) {
     __shared__ float4 pieces[GL ? 80 : 1];
     const uint32_t lane = threadIdx.x;
     const long long row = (long long)blockIdx.x * 64 + lane;
-    const long long rl = row < A.M ? row : A.M - 1;
+    const long long rl = row < A.M ? row : A.M - 1;                     // (ccx_rows::Wave's row and rl: the wave's context is built where GL)
     const uint32_t a = A.actions[rl];
     const bool has_valid = A.valid != nullptr;
     const uint32_t vbyte = has_valid ? (uint32_t)A.valid[rl] : 1u;
@@ -115,14 +115,14 @@ __global__ __launch_bounds__(64) void ppo_bwd_kernel(const PpoArgs A) {
         }
         const float se = sc * A.ent_coef;
         const float gent = 0.0f - se;
-        const long long floats = A.M * 5, last_piece = floats / 4 - 1;
         float l[5], gr[5];
-        ccx_rows::load_rows(A.logits, A.M, pieces, lane, blockIdx.x, row, floats, last_piece, l);
+        const ccx_rows::Wave W = ccx_rows::wave_of(A.M, blockIdx.x, lane);
+        ccx_rows::load_rows(A.logits, pieces, W, l);
         const float an = ccx_ppo::normalised(has_norm, adv, mean, denom);
         ccx_ppo::backward_row_logits(l, mbyte, a, lpo, an, ret, val, A.lo, A.hi, sc, gent, gr);
 #pragma unroll
         for (int k = 0; k < 5; ++k) gr[k] = counts ? gr[k] : 0.0f;
-        ccx_rows::store_rows(A.grad_logits, A.M, pieces, lane, blockIdx.x, row, floats, last_piece, gr);
+        ccx_rows::store_rows(A.grad_logits, pieces, W, gr);
     }
     if constexpr (GV) {
         const float scv = sc * A.vf_coef;
@@ -185,7 +185,7 @@ int ccx_masked_moments(ccx_handle* h, int64_t rows, const float* x, const uint8_
     if (!x || !workspace || !out) return fail(CCX_EINVAL, "ccx_masked_moments: NULL argument (x, workspace and out are required)");
     unsigned blocks = 0;
     if (int rc = ccxi::row_blocks("ccx_masked_moments", rows, ccx_tree::kBlockRows, blocks)) return rc;
-    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "ccx_masked_moments: workspace must be 8-byte aligned");
+    if (misaligned(8, workspace)) return fail(CCX_EINVAL, "ccx_masked_moments: workspace must be 8-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     MomentArgs A{};
     A.x = x;
@@ -209,8 +209,8 @@ int ccx_ppo_loss(ccx_handle* h, int64_t rows, const float* logits, const uint8_t
         return fail(CCX_EINVAL, "ccx_ppo_loss: NULL argument (only masks, valid and norm may be NULL)");
     unsigned blocks = 0;
     if (int rc = ccxi::row_blocks("ccx_ppo_loss", rows, ccx_tree::kBlockRows, blocks)) return rc;
-    if (reinterpret_cast<uintptr_t>(logits) & 15u) return fail(CCX_EINVAL, "ccx_ppo_loss: logits must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "ccx_ppo_loss: workspace must be 8-byte aligned");
+    if (misaligned(16, logits)) return fail(CCX_EINVAL, "ccx_ppo_loss: logits must be 16-byte aligned");
+    if (misaligned(8, workspace)) return fail(CCX_EINVAL, "ccx_ppo_loss: workspace must be 8-byte aligned");
     if (int rc = check_hyper("ccx_ppo_loss", clip, vf_coef, ent_coef, adv_eps)) return rc;
     CCX_HIP(hipSetDevice(h->device));
     PpoArgs A{};
@@ -247,7 +247,7 @@ int ccx_ppo_loss_backward(ccx_handle* h, int64_t rows, const float* logits, cons
         return fail(CCX_EINVAL, "ccx_ppo_loss_backward: both gradient outputs are NULL (at least one of grad_logits, grad_values is required)");
     unsigned blocks = 0;
     if (int rc = ccxi::row_blocks("ccx_ppo_loss_backward", rows, 64, blocks)) return rc;
-    if ((reinterpret_cast<uintptr_t>(logits) | reinterpret_cast<uintptr_t>(grad_logits_or_null)) & 15u)
+    if (misaligned(16, logits, grad_logits_or_null))
         return fail(CCX_EINVAL, "ccx_ppo_loss_backward: logits and grad_logits must be 16-byte aligned");
     if (int rc = check_hyper("ccx_ppo_loss_backward", clip, vf_coef, ent_coef, adv_eps)) return rc;
     CCX_HIP(hipSetDevice(h->device));
@@ -268,14 +268,12 @@ int ccx_ppo_loss_backward(ccx_handle* h, int64_t rows, const float* logits, cons
     A.M = rows;
     fill_hyper(A, clip, vf_coef, ent_coef, adv_eps);
     const dim3 grid(blocks), block(64);
+    // the masks are read for the logits' gradient only: without it there is one kernel
     if (!grad_logits_or_null) hipLaunchKernelGGL((ppo_bwd_kernel<false, false, true>), grid, block, 0, h->stream, A);
-    else if (masks_or_null) {
-        if (grad_values_or_null) hipLaunchKernelGGL((ppo_bwd_kernel<true, true, true>), grid, block, 0, h->stream, A);
-        else hipLaunchKernelGGL((ppo_bwd_kernel<true, true, false>), grid, block, 0, h->stream, A);
-    } else {
-        if (grad_values_or_null) hipLaunchKernelGGL((ppo_bwd_kernel<false, true, true>), grid, block, 0, h->stream, A);
-        else hipLaunchKernelGGL((ppo_bwd_kernel<false, true, false>), grid, block, 0, h->stream, A);
-    }
+    else
+        with_flags([&](auto mask, auto gv) {
+            hipLaunchKernelGGL((ppo_bwd_kernel<decltype(mask)::value, true, decltype(gv)::value>), grid, block, 0, h->stream, A);
+        }, masks_or_null != nullptr, grad_values_or_null != nullptr);
     CCX_HIP(hipGetLastError());
     return CCX_OK;
 }

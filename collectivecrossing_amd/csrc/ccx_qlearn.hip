@@ -17,6 +17,8 @@
 
 using ccx_draw::DrawArgs;
 using ccxi::fail;
+using ccxi::misaligned;
+using ccxi::with_flags;
 
 namespace {
 
@@ -29,9 +31,9 @@ __global__ __launch_bounds__(64) void q_act_kernel(const float* q, const DrawArg
     const ccx_draw::Small v = ccx_draw::small_loads<!EPS>(D, s, MASK);
     float eps = 0.0f;
     if (EPS) eps = epsilon[0];
-    const long long floats = D.EN * 5, last_piece = floats / 4 - 1;
+    const ccx_rows::Wave W = ccx_rows::wave_of(D.EN, blockIdx.x, lane);  // (W.row is s.slot; the small loads clamp for themselves)
     float l[5];
-    ccx_rows::load_rows(q, D.EN, pieces, lane, blockIdx.x, s.slot, floats, last_piece, l);
+    ccx_rows::load_rows(q, pieces, W, l);
     if (s.slot >= D.EN) return;
     const bool dead = (v.term | v.trunc) != 0;
     const uint32_t m = ccx_qlearn::legal_set(v.mbyte);
@@ -94,15 +96,13 @@ __global__ __launch_bounds__(256) void td_partial_kernel(const TdArgs A) {
     __shared__ float4 pieces[DOUBLE ? 3 : 2][ccx_tree::kBlockGroups][80];
     __shared__ double groups[ccx_qlearn::kSums][ccx_tree::kBlockGroups];
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const long long wave = (long long)blockIdx.x * ccx_tree::kBlockGroups + w;
-    const long long row = wave * 64 + lane;
-    const long long rl = row < A.M ? row : A.M - 1;
-    const TdSmall v = td_small(A, rl);
-    const long long floats = A.M * 5, last_piece = floats / 4 - 1;      // M >= 1: at least one whole piece
+    const ccx_rows::Wave W = ccx_rows::wave_of(A.M, (long long)blockIdx.x * ccx_tree::kBlockGroups + w, lane);
+    const long long row = W.row;
+    const TdSmall v = td_small(A, W.rl);
     float q[5], qt[5], qo[5];
-    ccx_rows::load_rows(A.q, A.M, pieces[0][w], lane, wave, row, floats, last_piece, q);
-    ccx_rows::load_rows(A.q_next_target, A.M, pieces[1][w], lane, wave, row, floats, last_piece, qt);
-    if constexpr (DOUBLE) ccx_rows::load_rows(A.q_next_online, A.M, pieces[2][w], lane, wave, row, floats, last_piece, qo);
+    ccx_rows::load_rows(A.q, pieces[0][w], W, q);
+    ccx_rows::load_rows(A.q_next_target, pieces[1][w], W, qt);
+    if constexpr (DOUBLE) ccx_rows::load_rows(A.q_next_online, pieces[2][w], W, qo);
     const bool counts = row < A.M && ccx_qlearn::row_counts(v.has_valid, v.vbyte, v.a);
     const bool bad = row < A.M && ccx_qlearn::row_bad(v.has_valid, v.vbyte, v.a);
     ccx_qlearn::Row t;
@@ -129,17 +129,14 @@ __global__ __launch_bounds__(64) void td_final_kernel(const TdArgs A) {
 template <bool DOUBLE>
 __global__ __launch_bounds__(64) void td_bwd_kernel(const TdArgs A) {
     __shared__ float4 pieces[DOUBLE ? 3 : 2][80];
-    const uint32_t lane = threadIdx.x;
-    const long long row = (long long)blockIdx.x * 64 + lane;
-    const long long rl = row < A.M ? row : A.M - 1;
-    const TdSmall v = td_small(A, rl);
+    const ccx_rows::Wave W = ccx_rows::wave_of(A.M, blockIdx.x, threadIdx.x);
+    const TdSmall v = td_small(A, W.rl);
     const float n = A.stats_in[6];
     const float g = A.grad_loss ? A.grad_loss[0] : 1.0f;
-    const long long floats = A.M * 5, last_piece = floats / 4 - 1;
     float q[5], qt[5], qo[5];
-    ccx_rows::load_rows(A.q, A.M, pieces[0], lane, blockIdx.x, row, floats, last_piece, q);
-    ccx_rows::load_rows(A.q_next_target, A.M, pieces[1], lane, blockIdx.x, row, floats, last_piece, qt);
-    if constexpr (DOUBLE) ccx_rows::load_rows(A.q_next_online, A.M, pieces[2], lane, blockIdx.x, row, floats, last_piece, qo);
+    ccx_rows::load_rows(A.q, pieces[0], W, q);
+    ccx_rows::load_rows(A.q_next_target, pieces[1], W, qt);
+    if constexpr (DOUBLE) ccx_rows::load_rows(A.q_next_online, pieces[2], W, qo);
     const float sc = g / n;
     const float gw = ccx_qlearn::row_scale(v.has_w, sc, v.w);
     const bool counts = n != 0.0f && ccx_qlearn::row_counts(v.has_valid, v.vbyte, v.a);      // n == 0: every gradient +0.0f, selected
@@ -150,11 +147,11 @@ __global__ __launch_bounds__(64) void td_bwd_kernel(const TdArgs A) {
     float gr[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k) gr[k] = (counts && v.a == (uint32_t)k) ? ga : 0.0f;
-    ccx_rows::store_rows(A.grad_q, A.M, pieces[0], lane, blockIdx.x, row, floats, last_piece, gr);
+    ccx_rows::store_rows(A.grad_q, pieces[0], W, gr);
 }
 
 int check_td(const char* who, const void* q, const void* qt, const void* qo, float gamma, float huber_delta) {
-    if ((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(qt) | reinterpret_cast<uintptr_t>(qo)) & 15u)
+    if (misaligned(16, q, qt, qo))
         return fail(CCX_EINVAL, "%s: q, q_next_target and q_next_online must be 16-byte aligned", who);
     if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(CCX_EINVAL, "%s: gamma must be finite and lie in [0, 1], got %g", who, (double)gamma);
     if (!(huber_delta > 0.0f)) return fail(CCX_EINVAL, "%s: huber_delta must be > 0 (+inf: the squared error), got %g", who, (double)huber_delta);
@@ -189,18 +186,15 @@ int ccx_q_actions(ccx_handle* h, const float* q, const uint8_t* masks_or_null, c
                   uint8_t* explored_or_null) {
     if (!h) return fail(CCX_EINVAL, "NULL handle");
     if (!q || !actions) return fail(CCX_EINVAL, "ccx_q_actions: NULL argument (q and actions are required)");
-    if (reinterpret_cast<uintptr_t>(q) & 15u) return fail(CCX_EINVAL, "ccx_q_actions: q must be 16-byte aligned");
+    if (misaligned(16, q)) return fail(CCX_EINVAL, "ccx_q_actions: q must be 16-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     DrawArgs D = ccx_draw::draw_args(h, masks_or_null, actions, nullptr, nullptr);
     D.seed_hi = h->rng_hi;                                              // the kernel adds its two streams itself
     const dim3 grid((unsigned)((D.EN + 63) / 64)), block(64);           // E < 2^31, N <= 64: below 2^31
-    if (masks_or_null) {
-        if (epsilon_or_null) hipLaunchKernelGGL((q_act_kernel<true, true>), grid, block, 0, h->stream, q, D, epsilon_or_null, explored_or_null);
-        else hipLaunchKernelGGL((q_act_kernel<true, false>), grid, block, 0, h->stream, q, D, epsilon_or_null, explored_or_null);
-    } else {
-        if (epsilon_or_null) hipLaunchKernelGGL((q_act_kernel<false, true>), grid, block, 0, h->stream, q, D, epsilon_or_null, explored_or_null);
-        else hipLaunchKernelGGL((q_act_kernel<false, false>), grid, block, 0, h->stream, q, D, epsilon_or_null, explored_or_null);
-    }
+    with_flags([&](auto mask, auto eps) {
+        hipLaunchKernelGGL((q_act_kernel<decltype(mask)::value, decltype(eps)::value>), grid, block, 0, h->stream, q, D,
+                           epsilon_or_null, explored_or_null);
+    }, masks_or_null != nullptr, epsilon_or_null != nullptr);
     CCX_HIP(hipGetLastError());
     return CCX_OK;
 }
@@ -220,7 +214,7 @@ int ccx_td_loss(ccx_handle* h, int64_t rows, const float* q, const uint8_t* acti
     unsigned blocks = 0;
     if (int rc = ccxi::row_blocks("ccx_td_loss", rows, ccx_tree::kBlockRows, blocks)) return rc;
     if (int rc = check_td("ccx_td_loss", q, q_next_target, q_next_online_or_null, gamma, huber_delta)) return rc;
-    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(CCX_EINVAL, "ccx_td_loss: workspace must be 8-byte aligned");
+    if (misaligned(8, workspace)) return fail(CCX_EINVAL, "ccx_td_loss: workspace must be 8-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     TdArgs A = td_args(rows, q, actions, reward, done, q_next_target, q_next_online_or_null, masks_next_or_null, valid_or_null,
                        weights_or_null, gamma, huber_delta);
@@ -245,7 +239,7 @@ int ccx_td_loss_backward(ccx_handle* h, int64_t rows, const float* q, const uint
     unsigned blocks = 0;
     if (int rc = ccxi::row_blocks("ccx_td_loss_backward", rows, 64, blocks)) return rc;
     if (int rc = check_td("ccx_td_loss_backward", q, q_next_target, q_next_online_or_null, gamma, huber_delta)) return rc;
-    if (reinterpret_cast<uintptr_t>(grad_q) & 15u) return fail(CCX_EINVAL, "ccx_td_loss_backward: grad_q must be 16-byte aligned");
+    if (misaligned(16, grad_q)) return fail(CCX_EINVAL, "ccx_td_loss_backward: grad_q must be 16-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     TdArgs A = td_args(rows, q, actions, reward, done, q_next_target, q_next_online_or_null, masks_next_or_null, valid_or_null,
                        weights_or_null, gamma, huber_delta);

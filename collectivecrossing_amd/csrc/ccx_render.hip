@@ -238,7 +238,7 @@ static int render_launch(ccx_handle* h, const int32_t* env_ids, const float* com
     if (!h || !frames) return fail(CCX_EINVAL, "NULL argument");
     if (cell_px < 1 || cell_px > 64) return fail(CCX_EINVAL, "cell_px = %d outside 1..64", cell_px);
     if (rows < 0) return fail(CCX_EINVAL, "rows = %lld < 0", (long long)rows);
-    if (reinterpret_cast<uintptr_t>(frames) & 15u) return fail(CCX_EINVAL, "frames must be 16-byte aligned");
+    if (ccxi::misaligned(16, frames)) return fail(CCX_EINVAL, "frames must be 16-byte aligned");
     const ccx_params& P = h->params;
     ccx::RenderArgs A{};
     A.W = P.width; A.H = P.height; A.cp = cell_px; A.Wpx = P.width * cell_px; A.Hpx = P.height * cell_px;

@@ -18,6 +18,8 @@
 #include "ccx_rollout_dev.h"
 
 using ccxi::fail;
+using ccxi::misaligned;
+using ccxi::with_flags;
 
 namespace {
 
@@ -174,9 +176,8 @@ int check_ring(const char* who, const ccx_handle* h, CCX_RING_PARAMS, RingArrays
         return fail(CCX_EINVAL, "%s: NULL ring array", who);
     if (ring_steps < 1 || ring_steps >= (1ll << 31) || ring_steps * (int64_t)h->E >= (1ll << 31))
         return fail(CCX_EINVAL, "%s: ring_steps = %lld out of range (1 <= S, S * E < 2^31)", who, (long long)ring_steps);
-    if ((reinterpret_cast<uintptr_t>(ring_obs_c) | reinterpret_cast<uintptr_t>(ring_next_c)) & 15u)
-        return fail(CCX_EINVAL, "%s: the ring's compact arrays must be 16-byte aligned", who);
-    if ((reinterpret_cast<uintptr_t>(ring_reward) | reinterpret_cast<uintptr_t>(ring_state)) & 7u)
+    if (misaligned(16, ring_obs_c, ring_next_c)) return fail(CCX_EINVAL, "%s: the ring's compact arrays must be 16-byte aligned", who);
+    if (misaligned(8, ring_reward, ring_state))
         return fail(CCX_EINVAL, "%s: the ring's reward and state must be 8-byte aligned", who);
     a.obs_c = reinterpret_cast<float4*>(ring_obs_c);
     a.next_c = reinterpret_cast<float4*>(ring_next_c);
@@ -207,9 +208,8 @@ int fetch(const char* who, ccx_handle* h, CCX_RING_PARAMS, int64_t B, const int6
         return fail(CCX_EINVAL, "%s: NULL output (only obs and next_obs may be NULL)", who);
     if (!draw && !index_in) return fail(CCX_EINVAL, "%s: NULL index", who);
     if (B < 1 || B * (int64_t)h->N > (1ll << 31)) return fail(CCX_EINVAL, "%s: batch = %lld out of range (1 <= B <= 2^31 / N)", who, (long long)B);
-    if ((reinterpret_cast<uintptr_t>(out->obs) | reinterpret_cast<uintptr_t>(out->next_obs)) & 15u)
-        return fail(CCX_EINVAL, "%s: obs and next_obs must be 16-byte aligned", who);
-    if ((reinterpret_cast<uintptr_t>(out->reward) | reinterpret_cast<uintptr_t>(out->index) | reinterpret_cast<uintptr_t>(index_in)) & 7u)
+    if (misaligned(16, out->obs, out->next_obs)) return fail(CCX_EINVAL, "%s: obs and next_obs must be 16-byte aligned", who);
+    if (misaligned(8, out->reward, out->index, index_in))
         return fail(CCX_EINVAL, "%s: reward and index must be 8-byte aligned", who);
     CCX_HIP(hipSetDevice(h->device));
     const ccx::LaunchShape& ls = h->shape;
@@ -234,15 +234,11 @@ int fetch(const char* who, ccx_handle* h, CCX_RING_PARAMS, int64_t B, const int6
     A.seed_lo = h->rng_lo;
     A.seed_hi = h->rng_hi;
     const dim3 grid((unsigned)blocks), block(64 * ls.waves_per_block);
-    const bool pair = (h->N % 2) == 0;
-    if (draw) {
-        if (pair) hipLaunchKernelGGL((replay_fetch_kernel<true, true>), grid, block, ls.lds_bytes_observe, h->stream, p, A);
-        else hipLaunchKernelGGL((replay_fetch_kernel<true, false>), grid, block, ls.lds_bytes_observe, h->stream, p, A);
-        hipLaunchKernelGGL(replay_head_kernel, dim3(1), dim3(64), 0, h->stream, A.ring.state, 0ll, 1ll);
-    } else {
-        if (pair) hipLaunchKernelGGL((replay_fetch_kernel<false, true>), grid, block, ls.lds_bytes_observe, h->stream, p, A);
-        else hipLaunchKernelGGL((replay_fetch_kernel<false, false>), grid, block, ls.lds_bytes_observe, h->stream, p, A);
-    }
+    with_flags([&](auto drw, auto pair) {
+        hipLaunchKernelGGL((replay_fetch_kernel<decltype(drw)::value, decltype(pair)::value>), grid, block, ls.lds_bytes_observe,
+                           h->stream, p, A);
+    }, draw, (h->N % 2) == 0);
+    if (draw) hipLaunchKernelGGL(replay_head_kernel, dim3(1), dim3(64), 0, h->stream, A.ring.state, 0ll, 1ll);
     CCX_HIP(hipGetLastError());
     return CCX_OK;
 }
@@ -260,9 +256,9 @@ int ccx_replay_push(ccx_handle* h, CCX_RING_PARAMS, int64_t K, const float* obs0
         return fail(CCX_EINVAL, "ccx_replay_push: NULL argument (only final_compact and masks_next may be NULL)");
     if (K < 1 || K > ring_steps)
         return fail(CCX_EINVAL, "ccx_replay_push: K = %lld out of range (1 <= K <= ring_steps = %lld)", (long long)K, (long long)ring_steps);
-    if ((reinterpret_cast<uintptr_t>(obs0_compact) | reinterpret_cast<uintptr_t>(obs_compact) | reinterpret_cast<uintptr_t>(final_compact_or_null)) & 15u)
+    if (misaligned(16, obs0_compact, obs_compact, final_compact_or_null))
         return fail(CCX_EINVAL, "ccx_replay_push: obs0_compact, obs_compact and final_compact must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(reward) & 7u) return fail(CCX_EINVAL, "ccx_replay_push: reward must be 8-byte aligned");
+    if (misaligned(8, reward)) return fail(CCX_EINVAL, "ccx_replay_push: reward must be 8-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     A.obs0 = reinterpret_cast<const float4*>(obs0_compact);
     A.actions = actions;

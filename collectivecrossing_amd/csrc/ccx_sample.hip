@@ -13,6 +13,8 @@
 
 using ccx_draw::DrawArgs;
 using ccxi::fail;
+using ccxi::misaligned;
+using ccxi::with_flags;
 
 namespace {
 
@@ -23,19 +25,11 @@ __global__ __launch_bounds__(64) void sample_kernel(const float* logits, const D
     const ccx_draw::Slot s = ccx_draw::slot_of(D, lane);
     // every load is issued before the first wait: the small ones, then the wave's pieces
     const ccx_draw::Small v = ccx_draw::small_loads<DET>(D, s, MASK);
-    const long long floats = D.EN * 5, last_piece = floats / 4 - 1;
+    const ccx_rows::Wave W = ccx_rows::wave_of(D.EN, blockIdx.x, lane);  // (W.row is s.slot; the small loads clamp for themselves)
     float l[5];
-    ccx_rows::load_rows(logits, D.EN, pieces, lane, blockIdx.x, s.slot, floats, last_piece, l);
+    ccx_rows::load_rows(logits, pieces, W, l);
     if (s.slot >= D.EN) return;
     ccx_draw::finish<DET, STATS>(D, s, v, l);
-}
-
-template <bool MASK, bool DET>
-void launch(bool stats, unsigned blocks, hipStream_t stream, const float* logits, const DrawArgs& D) {
-    if (stats)
-        hipLaunchKernelGGL((sample_kernel<MASK, DET, true>), dim3(blocks), dim3(64), 0, stream, logits, D);
-    else
-        hipLaunchKernelGGL((sample_kernel<MASK, DET, false>), dim3(blocks), dim3(64), 0, stream, logits, D);
 }
 
 }  // namespace
@@ -46,18 +40,14 @@ int ccx_sample_actions(ccx_handle* h, const float* logits, const uint8_t* masks_
                        float* logp_or_null, float* entropy_or_null) {
     if (!h) return fail(CCX_EINVAL, "NULL handle");
     if (!logits || !actions) return fail(CCX_EINVAL, "ccx_sample_actions: NULL argument (logits and actions are required)");
-    if (reinterpret_cast<uintptr_t>(logits) & 15u) return fail(CCX_EINVAL, "ccx_sample_actions: logits must be 16-byte aligned");
+    if (misaligned(16, logits)) return fail(CCX_EINVAL, "ccx_sample_actions: logits must be 16-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     const DrawArgs D = ccx_draw::draw_args(h, masks_or_null, actions, logp_or_null, entropy_or_null);
     const unsigned blocks = (unsigned)((D.EN + 63) / 64);               // E < 2^31, N <= 64: below 2^31
-    const bool stats = logp_or_null || entropy_or_null, det = deterministic != 0;
-    if (masks_or_null) {
-        if (det) launch<true, true>(stats, blocks, h->stream, logits, D);
-        else launch<true, false>(stats, blocks, h->stream, logits, D);
-    } else {
-        if (det) launch<false, true>(stats, blocks, h->stream, logits, D);
-        else launch<false, false>(stats, blocks, h->stream, logits, D);
-    }
+    with_flags([&](auto mask, auto det, auto stats) {
+        hipLaunchKernelGGL((sample_kernel<decltype(mask)::value, decltype(det)::value, decltype(stats)::value>), dim3(blocks),
+                           dim3(64), 0, h->stream, logits, D);
+    }, masks_or_null != nullptr, deterministic != 0, logp_or_null || entropy_or_null);
     CCX_HIP(hipGetLastError());
     return CCX_OK;
 }

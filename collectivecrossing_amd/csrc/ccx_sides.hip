@@ -25,6 +25,8 @@
 using ccx_draw::DrawArgs;
 using ccx_tile::MlpArgs;
 using ccxi::fail;
+using ccxi::misaligned;
+using ccxi::with_flags;
 
 static_assert(sizeof(ccx_sides::Group) == sizeof(ccx_slot_group) && sizeof(ccx_slot_group) == 40, "the table row is 40 bytes");
 static_assert(ccx_sides::kMaxGroups == CCX_SIDES_MAX_GROUPS, "one limit");
@@ -156,8 +158,7 @@ int make_table(const char* who, int64_t M, int32_t N, int32_t num_groups, const 
     for (; n < num_groups; ++n) {
         const ccx_slot_group& g = groups[n];
         if (!g.w1t || !g.b1 || !g.w2 || !g.b2) return fail(CCX_EINVAL, "%s: group %d has a NULL parameter array", who, n);
-        if ((reinterpret_cast<uintptr_t>(g.w1t) | reinterpret_cast<uintptr_t>(g.b1) | reinterpret_cast<uintptr_t>(g.w2) |
-             reinterpret_cast<uintptr_t>(g.b2)) & 3u)
+        if (misaligned(4, g.w1t, g.b1, g.w2, g.b2))
             return fail(CCX_EINVAL, "%s: group %d's w1t, b1, w2 and b2 must be 4-byte aligned", who, n);
         tab.g[n] = ccx_sides::Group{g.slots, g.w1t, g.b1, g.w2, g.b2};
         owned |= g.slots;
@@ -181,9 +182,8 @@ int ccx_sides_forward(ccx_handle* h, int64_t M, int32_t N, int32_t L, int32_t H,
     if (const int rc = ccx_tile::check_dims("ccx_sides_forward", L, H, O, activation)) return rc;
     SidesArgs S{};
     if (const int rc = make_table("ccx_sides_forward", M, N, num_groups, groups, false, S.tab)) return rc;
-    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(hidden_or_null)) & 15u)
-        return fail(CCX_EINVAL, "ccx_sides_forward: x and hidden must be 16-byte aligned");
-    if (reinterpret_cast<uintptr_t>(y) & 3u) return fail(CCX_EINVAL, "ccx_sides_forward: y must be 4-byte aligned");
+    if (misaligned(16, x, hidden_or_null)) return fail(CCX_EINVAL, "ccx_sides_forward: x and hidden must be 16-byte aligned");
+    if (misaligned(4, y)) return fail(CCX_EINVAL, "ccx_sides_forward: y must be 4-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     S.x = x, S.y = y, S.hidden = hidden_or_null, S.M = M, S.N = N, S.L = L, S.H = H, S.O = O, S.activation = activation;
     const size_t bytes = ccx_tile::lds_floats(L, H, O, false) * sizeof(float) + 64 * sizeof(long long);
@@ -202,29 +202,21 @@ int ccx_sides_sample_actions(ccx_handle* h, int32_t H, int32_t activation, const
     if (const int rc = ccx_tile::check_dims("ccx_sides_sample_actions", L, H, 5, activation)) return rc;
     SidesArgs S{};
     if (const int rc = make_table("ccx_sides_sample_actions", h->E, h->N, num_groups, groups, true, S.tab)) return rc;
-    if (reinterpret_cast<uintptr_t>(obs) & 15u) return fail(CCX_EINVAL, "ccx_sides_sample_actions: obs must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(logp_or_null) | reinterpret_cast<uintptr_t>(entropy_or_null) |
-         reinterpret_cast<uintptr_t>(logits_or_null)) & 3u)
+    if (misaligned(16, obs)) return fail(CCX_EINVAL, "ccx_sides_sample_actions: obs must be 16-byte aligned");
+    if (misaligned(4, logp_or_null, entropy_or_null, logits_or_null))
         return fail(CCX_EINVAL, "ccx_sides_sample_actions: logp, entropy and logits must be 4-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
     S.x = obs, S.y = logits_or_null, S.hidden = nullptr, S.M = h->E, S.N = h->N, S.L = L, S.H = H, S.O = 5, S.activation = activation;
     const DrawArgs D = ccx_draw::draw_args(h, masks_or_null, actions, logp_or_null, entropy_or_null);
     const size_t bytes = ccx_tile::lds_floats(L, H, 5, true) * sizeof(float) + 64 * sizeof(long long);
     const dim3 grid(S.tab.first[S.tab.num]), block(64 * (H / ccx_mlp::kGroup));
-    const bool stats = logp_or_null || entropy_or_null, det = deterministic != 0;
-#define CCX_SIDES_DRAW(DET, STATS)                                                                  \
-    do {                                                                                            \
-        CCX_HIP(ccx_tile::allow_lds(sides_draw_kernel<DET, STATS>, bytes));                         \
-        hipLaunchKernelGGL((sides_draw_kernel<DET, STATS>), grid, block, bytes, h->stream, S, D);   \
-    } while (0)
-    if (det) {
-        if (stats) CCX_SIDES_DRAW(true, true);
-        else CCX_SIDES_DRAW(true, false);
-    } else {
-        if (stats) CCX_SIDES_DRAW(false, true);
-        else CCX_SIDES_DRAW(false, false);
-    }
-#undef CCX_SIDES_DRAW
+    const int rc = with_flags([&](auto det, auto stats) -> int {
+        constexpr bool DET = decltype(det)::value, STATS = decltype(stats)::value;
+        CCX_HIP(ccx_tile::allow_lds(sides_draw_kernel<DET, STATS>, bytes));
+        hipLaunchKernelGGL((sides_draw_kernel<DET, STATS>), grid, block, bytes, h->stream, S, D);
+        return CCX_OK;
+    }, deterministic != 0, logp_or_null || entropy_or_null);
+    if (rc) return rc;
     CCX_HIP(hipGetLastError());
     return CCX_OK;
 }

@@ -179,6 +179,29 @@ def test_synthetic_trajectories(batches, synthetic, N, K):
         batch.track_episodes(False)
 
 
+def test_one_load_per_step_without_a_log(batches):
+    """The accumulate kernel's fourth instantiation (no log, one dependent load per step), which the three modes above do not
+    launch: 13 envs x 5 agents (65 slots), two updates of 17 steps (one 16-step chunk and a tail), carried accumulators.
+    (The two load schedules are defined to give the same bytes, so only the log flag can show in the results: with the log
+    on by mistake the kernel would write records where none are kept.)"""
+    E, N, K = 13, 5, 17
+    batch = batches("g7_n5_odd", E)
+    assert batch.num_agents == N
+    first, second = make_trajectory(K, E, N, seed=21), make_trajectory(K, E, N, seed=22)
+    assert (first[2] & 3).any() and (second[2] & 3).any()         # episodes finish inside both updates
+    try:
+        batch.set_tunable("stats_naive", 1)
+        batch.track_episodes(0)
+        spec = StatsSpec(E, N, 0)
+        _feed(batch, spec, *first)
+        _feed(batch, spec, *second)
+        _assert_accumulators(batch, spec, "one load per step, no log")
+        assert spec.emitted > 0 and not np.isnan(spec.ret).any()
+    finally:
+        batch.set_tunable("stats_naive", 0)
+        batch.track_episodes(False)
+
+
 # (grids larger than the device holds at once, with agent counts that do not divide a wavefront: the blocks of a later
 # round start after earlier ones have stored their results, so an env whose lanes were spread over two workgroups -- or any
 # other read of a value the same launch writes -- would show here, and only here)
