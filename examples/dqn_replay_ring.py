@@ -5,7 +5,8 @@ N (2 (24 + 16 N) + 12) of two rows per agent) and keeps its cursor on the device
 network's input rows, `online(obs)` -> `q_actions` -> `rollout(reset_obs="next", want_compact=True, want_obs=False)` ->
 `ring.push` -- is ONE captured graph, and the update is a second one that begins with `ring.sample(out=)`: the draw, the
 gather and the expansion into rows are one launch keyed by `set_rng_seed`.  No `torch.randint`, no `index_select`, no ring
-position on the host.  The whole run happens twice from the same seeds: the parameters end equal bit for bit."""
+position on the host.  The whole run happens twice from the same seeds: the parameters end equal bit for bit.
+(Against the composed CPU specs, round by round at small shapes: tests/test_gpu_learner_chain.py.)"""
 
 import sys
 from pathlib import Path

@@ -3,7 +3,8 @@
 `max_grad_norm=0.5`): every link from the observation rows to the NEW PARAMETERS is a written rule, and a minibatch update is
 ONE captured graph made of library launches only -- both heads' forward with `hidden_out`, `ppo_loss`, `ppo_loss_backward`,
 two `mlp_backward(out=)` and `opt.step(grads=)` -- replayed EPOCHS x MINIBATCHES times on static buffers.  The whole iteration
-runs twice from the same seeds; the parameters and the optimiser's m and v are equal bit for bit."""
+runs twice from the same seeds; the parameters and the optimiser's m and v are equal bit for bit.
+(Against the composed CPU specs, link by link at small shapes: tests/test_gpu_learner_chain.py.)"""
 
 import sys
 from pathlib import Path
