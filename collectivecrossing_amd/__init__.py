@@ -13,14 +13,15 @@ __version__ = "0.4.0"
 __all__ = ["CollectiveCrossingConfig", "CollectiveCrossingEnv", "BatchedCollectiveCrossing", "VectorCollectiveCrossing",
            "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult", "SampleResult", "EvalResult",
            "PpoLossResult", "MlpHead", "MlpGradResult", "DeviceAdam", "SideHeads", "QLearning", "QActions",
-           "TdLossResult", "ReplayRing", "ReplayBatch"]
+           "TdLossResult", "ReplayRing", "ReplayBatch", "PrioritizedReplay", "PrioritizedBatch"]
 
 
 _LAZY = {"CollectiveCrossingEnv": "env", "BatchedCollectiveCrossing": "batched", "VectorCollectiveCrossing": "vector",
          "BatchedMultiAgentEnv": "rllib", "unpack_action_masks": "batched", "GaeResult": "learner", "SampleResult": "learner",
          "EvalResult": "learner", "PpoLossResult": "learner", "MlpHead": "learner",
          "MlpGradResult": "learner", "DeviceAdam": "learner", "SideHeads": "sides", "QLearning": "qlearn",
-         "QActions": "qlearn", "TdLossResult": "qlearn", "ReplayRing": "replay", "ReplayBatch": "replay"}
+         "QActions": "qlearn", "TdLossResult": "qlearn", "ReplayRing": "replay", "ReplayBatch": "replay",
+         "PrioritizedReplay": "prioritized", "PrioritizedBatch": "prioritized"}
 
 
 def __getattr__(name):  # lazy: importing the configs must not pull in torch

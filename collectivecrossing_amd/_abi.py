@@ -103,6 +103,8 @@ class CcxSlotGroup(C.Structure):
     _fields_ = [("slots", C.c_uint64), ("w1t", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p), ("b2", C.c_void_p)]
 
 
+PRIO_MAX_TD = 8
+
 COUNTER_FIELDS =tuple(name for name, _ in CcxCounters._fields_)
 
 _H = C.c_void_p  # ccx_handle*
@@ -182,6 +184,11 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_replay_push": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 8),
     "ccx_replay_sample": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 8),
     "ccx_replay_fetch": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 9),
+    "ccx_prio_tree_words": (C.c_int64, [C.c_int64]),
+    "ccx_prio_push": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ccx_prio_update": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
+                                  C.POINTER(C.c_void_p), C.c_float, C.c_float]),
+    "ccx_prio_sample": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_int32] + [C.c_void_p] * 3),
     "ccx_set_check_inputs":(C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),

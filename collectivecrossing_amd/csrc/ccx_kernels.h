@@ -42,6 +42,12 @@ enum : uint32_t { kQExploreStream = 0x68E31DA4u, kQChoiceStream = 0xB5297A4Du };
 // CCX_REPLAY (include/ccx.h, ccx_replay.hip): the two words of a replay draw are keyed (draw b, launch counter low, high,
 // 0 | 1) on one more stream of the same word.
 enum : uint32_t { kReplayStream = 0x3C6EF372u };
+// CCX_PRIO (include/ccx.h, ccx_prio.hip): the two words of a prioritised draw, keyed like the replay draw's (with the
+// class's own launch counter), on a stream of their own: a uniform and a prioritised draw of one seed share no word.
+enum : uint32_t { kPrioStream = 0x7F4A7C15u };
+static_assert(kPrioStream != kReplayStream && kPrioStream != kQExploreStream && kPrioStream != kQChoiceStream &&
+              kPrioStream != kEpsStream && kPrioStream != kSampleStream && kPrioStream != 0u,
+              "every stream of the counter-based word has its own constant");
 static_assert(kQExploreStream != kQChoiceStream && kQExploreStream != kEpsStream && kQExploreStream != kSampleStream &&
               kQChoiceStream != kEpsStream && kQChoiceStream != kSampleStream && kQExploreStream != 0u && kQChoiceStream != 0u &&
               kReplayStream != kQExploreStream && kReplayStream != kQChoiceStream && kReplayStream != kEpsStream &&

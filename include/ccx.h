@@ -1216,6 +1216,81 @@ int ccx_replay_fetch(ccx_handle* h, int64_t ring_steps, float* ring_obs_c, float
                      int64_t batch, const int64_t* index_in /* [B] */, float* obs_or_null, float* next_obs_or_null,
                      uint8_t* actions, double* reward, uint8_t* done, uint8_t* valid, uint8_t* masks_next, int64_t* index);
 /*
+ * CCX_PRIO: proportional prioritised replay (Schaul et al.; the scheme of RLlib's prioritised buffers) over the ring of
+ * CCX_REPLAY.  The priorities are FIXED-POINT INTEGERS, so every sum over them is exact: the total, and every partial sum
+ * the draw walks through, have the same bits for any reduction order and any tree shape, a parent is exactly the sum of its
+ * children (a descent cannot run off the end), and the whole rule is stated below in integers -- the tree is never named.
+ * The two f32 rules (update, weights) follow the discipline of CCX_SAMPLE: every line is ONE correctly rounded f32
+ * operation, nothing is fused, what a rule does not read is selected away.  exp_spec and log_spec are CCX_SAMPLE's,
+ * unchanged; this section uses log_spec on [2^-31, 2^15] (its code takes any positive normal float) and exp_spec on
+ * [-22, 11].
+ *
+ * Storage (the caller's, travelling as arguments; R = S E records of the ring): leaf i32 [R], the priority p^alpha of each
+ * record with 16 fractional bits, 1 <= leaf <= 2^31 - 1, and 0 = never pushed / not drawable (the initial value); pstate
+ * i64 [4] = {max_leaf, draws, T, min_leaf}: max_leaf the running maximum of every leaf ever written (initially 65536 =
+ * 1.0), draws this section's own launch counter (not the ring's state[1]), T the sum of all leaves and min_leaf the
+ * smallest non-zero leaf (0: none) as of the latest ccx_prio_sample; beta f32 [1] ON THE DEVICE (a rate annealed between
+ * the replays of a captured graph needs no re-capture); and tree i64 [ccx_prio_tree_words(R)], work space that every
+ * ccx_prio_sample rewrites in full before it reads it: nothing observable depends on its contents or its shape.  With R <
+ * 2^31 and leaf < 2^31, T < 2^62.  Alignment: 8 bytes for the i64 arrays, 4 for i32 and f32.
+ *
+ * ccx_prio_push(ring_steps, ring_state, K, leaf, pstate).  Enqueued directly BEHIND a ccx_replay_push of K steps into the
+ * same ring: with head' = ring_state[0] (which that push advanced by K) and max_leaf = pstate[0], both read on the device,
+ *     leaf[((head' - K + s) mod S) * E + e] = max_leaf            for s = 0 .. K - 1, e = 0 .. E - 1
+ * the K E slots that push wrote: a new record is drawn at least as often as any other until its TD error is known.  (head' -
+ * K < 0, a caller that pushed nothing, counts as 0: the stores stay inside leaf.)
+ *
+ * ccx_prio_update(index i64 [B], num_td, td_error: HOST array of num_td <= 8 device pointers f32 [B][N], alpha, eps).  The
+ * arrays are the per-side td_error outputs of ccx_td_loss (+0.0 where a row did not count).  Per b:
+ *     m = +0.0;  for every array and agent: a = |td|;  m = a > m ? a : m        (a NaN never wins; +inf does)
+ *     s = m + eps;  x = s < 2^-16 ? 2^-16 : (s > 2^15 ? 2^15 : s)
+ *     p = alpha == 0 ? 1.0f : exp_spec(alpha * log_spec(x))
+ *     f = floor(p * 65536.0f);  c = f > 0x1.fffffep+30f ? 0x1.fffffep+30f : f;  new = max((i32)c, 1)
+ * (the cast is made after the clamp: it is always in range).  Per slot: the leaf becomes the MAXIMUM of the new values of
+ * all b that name it -- duplicates are normal, the draw is with replacement; a b whose index lies outside [0, R), or names a
+ * slot whose leaf is 0, changes nothing.  Then max_leaf = max(max_leaf, every new value written).  The result does not
+ * depend on the order in which lanes run: a first launch stores -|leaf| at the named slots (every writer stores the same
+ * value), a second does a signed integer atomic max of the new values; no floating-point atomic, no last writer.
+ * 0 <= alpha <= 1 and 0 < eps < inf, by value.
+ * Against f64 pow on the same x (measured on the CPU, tests/test_prio_spec.py, the maximum doubled): p is within a relative
+ * 2.2e-6 for x in [2^-31, 2^15] and alpha in {0.3, 0.6, 1}.
+ *
+ * ccx_prio_sample(leaf, pstate, beta, tree, B, stratified) -> index i64 [B], weights f32 [B][N], leaf_drawn i32 [B].
+ *   1. T = the sum of all leaves, min_leaf = the smallest non-zero leaf (0: none); both are written to pstate.
+ *   2. per b, with d = pstate.draws read on the device and the seed of ccx_set_rng_seed:
+ *        w0 = word(seed_lo, seed_hi ^ 0x7F4A7C15; (u32)b, (u32)d, (u32)(d >> 32), 0),  w1 = the same with 1 as the last key
+ *        x  = ((u64)w0 << 32) | w1
+ *        stratified:  x' = floor((b 2^64 + x) / B)  -- t1 = ((u64)b << 32) | w0;  q1 = t1 / B;  r1 = t1 % B;
+ *                     t2 = (r1 << 32) | w1;  q2 = t2 / B;  x' = (q1 << 32) | q2  (b < B < 2^31: two 64-bit divisions);
+ *                     draw b lies in the b-th of B equal strata.   Not stratified: x' = x.
+ *        u  = (x' * T) >> 64                                           (the high half of the 128-bit product: 0 <= u < T)
+ *        index[b] = the smallest i with leaf[0] + ... + leaf[i] > u;   T == 0: index[b] = -1
+ *      With all non-zero leaves equal and in front (F of them), the unstratified index is CCX_REPLAY's (x F) >> 64 for the same words.
+ *   3. leaf_drawn[b] = leaf[index[b]] (0 for -1);  r = (f32)((f64)min_leaf / (f64)leaf_drawn[b]);  bt = beta[0] clamped to
+ *      [0, 1] (bt = beta < 0 ? 0 : (beta > 1 ? 1 : beta));  weights[b][n] = exp_spec(bt * log_spec(r)) for every n -- (p_min /
+ *      p_i)^beta, the normalisation by the largest weight in the buffer; r == 1 gives exactly 1.0; index -1 gives +0.0.
+ *   4. draws += 1.
+ * The minibatch itself is ccx_replay_fetch on index.  The stream constant differs from those of every other section.
+ *
+ * Launches: ccx_prio_push ONE kernel; ccx_prio_update TWO; ccx_prio_sample the refresh (one workgroup per 256 leaves, once
+ * more per 65 536 and per 16 777 216 where R exceeds them, then ONE final workgroup that writes T and min_leaf; no atomic, no
+ * last-block-done counter), the draw, and one plain lane behind it that advances draws.  No host synchronisation, no
+ * allocation; everything captures into a HIP graph and advances with every replay.  A NULL handle or pointer, S < 1 or S E >=
+ * 2^31, K outside 1..S, B outside 1..2^31 / N (and B < 2^31), num_td outside 1..8, alpha or eps out of range, a misaligned
+ * array: CCX_EINVAL with a ccx_last_error message, before any launch.  ccx_prio_tree_words(R) is 0 for R outside 1..2^31 - 1.
+ * Not here: rank-based prioritisation, sampling without replacement, per-agent priorities, an incrementally updated tree,
+ * priorities shared across shards or GPUs, bf16 / f16.
+ */
+int64_t ccx_prio_tree_words(int64_t records);
+int ccx_prio_push(ccx_handle* h, int64_t ring_steps, const int64_t* ring_state /* [4] */, int64_t K, int32_t* leaf /* [R] */,
+                  const int64_t* pstate /* [4] */);
+int ccx_prio_update(ccx_handle* h, int64_t ring_steps, int32_t* leaf /* [R] */, int64_t* pstate /* [4] */, int64_t batch,
+                    const int64_t* index /* [B] */, int32_t num_td, const float* const* td_error /* host [num_td] of device [B][N] */,
+                    float alpha, float eps);
+int ccx_prio_sample(ccx_handle* h, int64_t ring_steps, const int32_t* leaf /* [R] */, int64_t* pstate /* [4] */,
+                    const float* beta /* device f32 [1] */, int64_t* tree /* [ccx_prio_tree_words(R)] */, int64_t batch,
+                    int32_t stratified, int64_t* index /* [B] */, float* weights /* [B][N] */, int32_t* leaf_drawn /* [B] */);
+/*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
  * `rng_seed` of ccx_rollout).  The action of agent slot a of global env g at step t (0-based) of its episode j is
