@@ -13,7 +13,8 @@ __version__ = "0.4.0"
 __all__ = ["CollectiveCrossingConfig", "CollectiveCrossingEnv", "BatchedCollectiveCrossing", "VectorCollectiveCrossing",
            "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult", "SampleResult", "EvalResult",
            "PpoLossResult", "MlpHead", "MlpGradResult", "DeviceAdam", "SideHeads", "QLearning", "QActions",
-           "TdLossResult", "ReplayRing", "ReplayBatch", "PrioritizedReplay", "PrioritizedBatch"]
+           "TdLossResult", "ReplayRing", "ReplayBatch", "PrioritizedReplay", "PrioritizedBatch", "NStepReplay",
+           "NStepBatch"]
 
 
 _LAZY = {"CollectiveCrossingEnv": "env", "BatchedCollectiveCrossing": "batched", "VectorCollectiveCrossing": "vector",
@@ -21,7 +22,7 @@ _LAZY = {"CollectiveCrossingEnv": "env", "BatchedCollectiveCrossing": "batched",
          "EvalResult": "learner", "PpoLossResult": "learner", "MlpHead": "learner",
          "MlpGradResult": "learner", "DeviceAdam": "learner", "SideHeads": "sides", "QLearning": "qlearn",
          "QActions": "qlearn", "TdLossResult": "qlearn", "ReplayRing": "replay", "ReplayBatch": "replay",
-         "PrioritizedReplay": "prioritized", "PrioritizedBatch": "prioritized"}
+         "PrioritizedReplay": "prioritized", "PrioritizedBatch": "prioritized", "NStepReplay": "nstep", "NStepBatch": "nstep"}
 
 
 def __getattr__(name):  # lazy: importing the configs must not pull in torch

@@ -104,6 +104,7 @@ class CcxSlotGroup(C.Structure):
 
 
 PRIO_MAX_TD = 8
+NSTEP_MAX = 16
 
 COUNTER_FIELDS =tuple(name for name, _ in CcxCounters._fields_)
 
@@ -189,6 +190,12 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_prio_update": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32,
                                   C.POINTER(C.c_void_p), C.c_float, C.c_float]),
     "ccx_prio_sample": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 4 + [C.c_int64, C.c_int32] + [C.c_void_p] * 3),
+    "ccx_nstep_push": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ccx_nstep_mark_cut": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ccx_nstep_sample": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 9 + [C.c_int32, C.c_float, C.c_int64] + [C.c_void_p] * 10),
+    "ccx_nstep_fetch": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 9 + [C.c_int32, C.c_float, C.c_int64] + [C.c_void_p] * 11),
+    "ccx_td_loss_discounted": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 10 + [C.c_float] + [C.c_void_p] * 3),
+    "ccx_td_loss_discounted_backward": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 10 + [C.c_float] + [C.c_void_p] * 3),
     "ccx_set_check_inputs":(C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),

@@ -11,6 +11,8 @@
 // Two plain launches: no atomic, no last-block-done counter.
 // td_bwd_kernel: one lane one row, a workgroup is one wave; it recomputes the forward terms from the inputs and reads nothing
 // else but `stats`; every element of grad_q is written, whole 16-byte pieces through LDS.
+// tdn_partial_kernel / tdn_bwd_kernel: the same two bodies with discount[row] in the place of gamma (CCX_NSTEP:
+// ccx_td_loss_discounted and its backward); td_final_kernel serves both.
 #include "ccx_draw.h"
 #include "ccx_qlearn.h"
 #include "ccx_rows.h"
@@ -91,14 +93,16 @@ __device__ __forceinline__ TdSmall td_small(const TdArgs& A, long long rl) {
     return v;
 }
 
-template <bool DOUBLE>
-__global__ __launch_bounds__(256) void td_partial_kernel(const TdArgs A) {
-    __shared__ float4 pieces[DOUBLE ? 3 : 2][ccx_tree::kBlockGroups][80];
-    __shared__ double groups[ccx_qlearn::kSums][ccx_tree::kBlockGroups];
+// the forward of one workgroup, shared by td_partial_kernel (one gamma for the launch) and tdn_partial_kernel (discount[row]):
+// gamma_at(rl) is the row's discount, loaded at the clamped index with the small loads
+template <bool DOUBLE, class GammaAt>
+__device__ __forceinline__ void td_partial_body(const TdArgs& A, float4 (&pieces)[DOUBLE ? 3 : 2][ccx_tree::kBlockGroups][80],
+                                                double (&groups)[ccx_qlearn::kSums][ccx_tree::kBlockGroups], GammaAt gamma_at) {
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const ccx_rows::Wave W = ccx_rows::wave_of(A.M, (long long)blockIdx.x * ccx_tree::kBlockGroups + w, lane);
     const long long row = W.row;
     const TdSmall v = td_small(A, W.rl);
+    const float gamma = gamma_at(W.rl);
     float q[5], qt[5], qo[5];
     ccx_rows::load_rows(A.q, pieces[0][w], W, q);
     ccx_rows::load_rows(A.q_next_target, pieces[1][w], W, qt);
@@ -106,13 +110,27 @@ __global__ __launch_bounds__(256) void td_partial_kernel(const TdArgs A) {
     const bool counts = row < A.M && ccx_qlearn::row_counts(v.has_valid, v.vbyte, v.a);
     const bool bad = row < A.M && ccx_qlearn::row_bad(v.has_valid, v.vbyte, v.a);
     ccx_qlearn::Row t;
-    if constexpr (DOUBLE) ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qo, v.mbyte, A.gamma, A.delta, A.c, v.has_w, v.w, t);
-    else ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qt, v.mbyte, A.gamma, A.delta, A.c, v.has_w, v.w, t);
+    if constexpr (DOUBLE) ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qo, v.mbyte, gamma, A.delta, A.c, v.has_w, v.w, t);
+    else ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qt, v.mbyte, gamma, A.delta, A.c, v.has_w, v.w, t);
     if (A.td_error && row < A.M) A.td_error[row] = counts ? t.d : 0.0f;
     // rows that do not count and rows >= M enter as +0.0, selected
     double s[ccx_qlearn::kSums] = {counts ? 1.0 : 0.0,           counts ? (double)t.term : 0.0, counts ? (double)t.ad : 0.0,
                                    counts ? (double)t.qa : 0.0,  counts ? (double)t.y : 0.0,    bad ? 1.0 : 0.0};
     ccx_tree::block_sums(s, groups, A.partials, A.B);
+}
+
+template <bool DOUBLE>
+__global__ __launch_bounds__(256) void td_partial_kernel(const TdArgs A) {
+    __shared__ float4 pieces[DOUBLE ? 3 : 2][ccx_tree::kBlockGroups][80];
+    __shared__ double groups[ccx_qlearn::kSums][ccx_tree::kBlockGroups];
+    td_partial_body<DOUBLE>(A, pieces, groups, [g = A.gamma](long long) { return g; });
+}
+
+template <bool DOUBLE>
+__global__ __launch_bounds__(256) void tdn_partial_kernel(const TdArgs A, const float* discount) {
+    __shared__ float4 pieces[DOUBLE ? 3 : 2][ccx_tree::kBlockGroups][80];
+    __shared__ double groups[ccx_qlearn::kSums][ccx_tree::kBlockGroups];
+    td_partial_body<DOUBLE>(A, pieces, groups, [discount](long long rl) { return discount[rl]; });
 }
 
 __global__ __launch_bounds__(64) void td_final_kernel(const TdArgs A) {
@@ -126,11 +144,11 @@ __global__ __launch_bounds__(64) void td_final_kernel(const TdArgs A) {
     }
 }
 
-template <bool DOUBLE>
-__global__ __launch_bounds__(64) void td_bwd_kernel(const TdArgs A) {
-    __shared__ float4 pieces[DOUBLE ? 3 : 2][80];
+template <bool DOUBLE, class GammaAt>
+__device__ __forceinline__ void td_bwd_body(const TdArgs& A, float4 (&pieces)[DOUBLE ? 3 : 2][80], GammaAt gamma_at) {
     const ccx_rows::Wave W = ccx_rows::wave_of(A.M, blockIdx.x, threadIdx.x);
     const TdSmall v = td_small(A, W.rl);
+    const float gamma = gamma_at(W.rl);
     const float n = A.stats_in[6];
     const float g = A.grad_loss ? A.grad_loss[0] : 1.0f;
     float q[5], qt[5], qo[5];
@@ -141,13 +159,25 @@ __global__ __launch_bounds__(64) void td_bwd_kernel(const TdArgs A) {
     const float gw = ccx_qlearn::row_scale(v.has_w, sc, v.w);
     const bool counts = n != 0.0f && ccx_qlearn::row_counts(v.has_valid, v.vbyte, v.a);      // n == 0: every gradient +0.0f, selected
     ccx_qlearn::Row t;
-    if constexpr (DOUBLE) ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qo, v.mbyte, A.gamma, A.delta, A.c, v.has_w, v.w, t);
-    else ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qt, v.mbyte, A.gamma, A.delta, A.c, v.has_w, v.w, t);
+    if constexpr (DOUBLE) ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qo, v.mbyte, gamma, A.delta, A.c, v.has_w, v.w, t);
+    else ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qt, v.mbyte, gamma, A.delta, A.c, v.has_w, v.w, t);
     const float ga = ccx_qlearn::backward_row(t.d, t.ad, A.delta, gw);
     float gr[5];
 #pragma unroll
     for (int k = 0; k < 5; ++k) gr[k] = (counts && v.a == (uint32_t)k) ? ga : 0.0f;
     ccx_rows::store_rows(A.grad_q, pieces[0], W, gr);
+}
+
+template <bool DOUBLE>
+__global__ __launch_bounds__(64) void td_bwd_kernel(const TdArgs A) {
+    __shared__ float4 pieces[DOUBLE ? 3 : 2][80];
+    td_bwd_body<DOUBLE>(A, pieces, [g = A.gamma](long long) { return g; });
+}
+
+template <bool DOUBLE>
+__global__ __launch_bounds__(64) void tdn_bwd_kernel(const TdArgs A, const float* discount) {
+    __shared__ float4 pieces[DOUBLE ? 3 : 2][80];
+    td_bwd_body<DOUBLE>(A, pieces, [discount](long long rl) { return discount[rl]; });
 }
 
 int check_td(const char* who, const void* q, const void* qt, const void* qo, float gamma, float huber_delta) {
@@ -176,6 +206,69 @@ TdArgs td_args(int64_t rows, const float* q, const uint8_t* actions, const doubl
     A.c = 0.5f * huber_delta;                                           // computed once, one f32 operation
     A.M = rows;
     return A;
+}
+
+// ccx_td_loss (discount == NULL: one gamma) and ccx_td_loss_discounted (discount [M]): the same checks, the same two launches
+int td_forward(const char* who, ccx_handle* h, int64_t rows, const float* q, const uint8_t* actions, const double* reward,
+               const uint8_t* done, const float* q_next_target, const float* q_next_online_or_null, const uint8_t* masks_next_or_null,
+               const uint8_t* valid_or_null, const float* weights_or_null, const float* discount, float gamma, float huber_delta,
+               void* workspace, float* stats, float* td_error_or_null) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (!q || !actions || !reward || !done || !q_next_target || !workspace || !stats)
+        return fail(CCX_EINVAL, "%s: NULL argument (only q_next_online, masks_next, valid, weights and td_error may be NULL)", who);
+    unsigned blocks = 0;
+    if (int rc = ccxi::row_blocks(who, rows, ccx_tree::kBlockRows, blocks)) return rc;
+    if (int rc = check_td(who, q, q_next_target, q_next_online_or_null, gamma, huber_delta)) return rc;
+    if (misaligned(8, workspace)) return fail(CCX_EINVAL, "%s: workspace must be 8-byte aligned", who);
+    if (misaligned(4, discount)) return fail(CCX_EINVAL, "%s: discount must be 4-byte aligned", who);
+    CCX_HIP(hipSetDevice(h->device));
+    TdArgs A = td_args(rows, q, actions, reward, done, q_next_target, q_next_online_or_null, masks_next_or_null, valid_or_null,
+                       weights_or_null, gamma, huber_delta);
+    A.partials = static_cast<double*>(workspace);
+    A.stats = stats;
+    A.td_error = td_error_or_null;
+    A.B = blocks;
+    const dim3 grid(blocks), block(256);
+    if (discount) {
+        if (q_next_online_or_null) hipLaunchKernelGGL((tdn_partial_kernel<true>), grid, block, 0, h->stream, A, discount);
+        else hipLaunchKernelGGL((tdn_partial_kernel<false>), grid, block, 0, h->stream, A, discount);
+    } else {
+        if (q_next_online_or_null) hipLaunchKernelGGL((td_partial_kernel<true>), grid, block, 0, h->stream, A);
+        else hipLaunchKernelGGL((td_partial_kernel<false>), grid, block, 0, h->stream, A);
+    }
+    hipLaunchKernelGGL(td_final_kernel, dim3(1), dim3(64), 0, h->stream, A);
+    CCX_HIP(hipGetLastError());
+    return CCX_OK;
+}
+
+int td_backward(const char* who, ccx_handle* h, int64_t rows, const float* q, const uint8_t* actions, const double* reward,
+                const uint8_t* done, const float* q_next_target, const float* q_next_online_or_null, const uint8_t* masks_next_or_null,
+                const uint8_t* valid_or_null, const float* weights_or_null, const float* discount, float gamma, float huber_delta,
+                const float* stats, const float* grad_loss_or_null, float* grad_q) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (!q || !actions || !reward || !done || !q_next_target || !stats || !grad_q)
+        return fail(CCX_EINVAL, "%s: NULL argument (only q_next_online, masks_next, valid, weights and grad_loss may be NULL)", who);
+    unsigned blocks = 0;
+    if (int rc = ccxi::row_blocks(who, rows, 64, blocks)) return rc;
+    if (int rc = check_td(who, q, q_next_target, q_next_online_or_null, gamma, huber_delta)) return rc;
+    if (misaligned(16, grad_q)) return fail(CCX_EINVAL, "%s: grad_q must be 16-byte aligned", who);
+    if (misaligned(4, discount)) return fail(CCX_EINVAL, "%s: discount must be 4-byte aligned", who);
+    CCX_HIP(hipSetDevice(h->device));
+    TdArgs A = td_args(rows, q, actions, reward, done, q_next_target, q_next_online_or_null, masks_next_or_null, valid_or_null,
+                       weights_or_null, gamma, huber_delta);
+    A.stats_in = stats;
+    A.grad_loss = grad_loss_or_null;
+    A.grad_q = grad_q;
+    const dim3 grid(blocks), block(64);
+    if (discount) {
+        if (q_next_online_or_null) hipLaunchKernelGGL((tdn_bwd_kernel<true>), grid, block, 0, h->stream, A, discount);
+        else hipLaunchKernelGGL((tdn_bwd_kernel<false>), grid, block, 0, h->stream, A, discount);
+    } else {
+        if (q_next_online_or_null) hipLaunchKernelGGL((td_bwd_kernel<true>), grid, block, 0, h->stream, A);
+        else hipLaunchKernelGGL((td_bwd_kernel<false>), grid, block, 0, h->stream, A);
+    }
+    CCX_HIP(hipGetLastError());
+    return CCX_OK;
 }
 
 }  // namespace
@@ -208,48 +301,35 @@ int ccx_td_loss(ccx_handle* h, int64_t rows, const float* q, const uint8_t* acti
                 const float* q_next_target, const float* q_next_online_or_null, const uint8_t* masks_next_or_null,
                 const uint8_t* valid_or_null, const float* weights_or_null, float gamma, float huber_delta, void* workspace,
                 float* stats, float* td_error_or_null) {
-    if (!h) return fail(CCX_EINVAL, "NULL handle");
-    if (!q || !actions || !reward || !done || !q_next_target || !workspace || !stats)
-        return fail(CCX_EINVAL, "ccx_td_loss: NULL argument (only q_next_online, masks_next, valid, weights and td_error may be NULL)");
-    unsigned blocks = 0;
-    if (int rc = ccxi::row_blocks("ccx_td_loss", rows, ccx_tree::kBlockRows, blocks)) return rc;
-    if (int rc = check_td("ccx_td_loss", q, q_next_target, q_next_online_or_null, gamma, huber_delta)) return rc;
-    if (misaligned(8, workspace)) return fail(CCX_EINVAL, "ccx_td_loss: workspace must be 8-byte aligned");
-    CCX_HIP(hipSetDevice(h->device));
-    TdArgs A = td_args(rows, q, actions, reward, done, q_next_target, q_next_online_or_null, masks_next_or_null, valid_or_null,
-                       weights_or_null, gamma, huber_delta);
-    A.partials = static_cast<double*>(workspace);
-    A.stats = stats;
-    A.td_error = td_error_or_null;
-    A.B = blocks;
-    if (q_next_online_or_null) hipLaunchKernelGGL((td_partial_kernel<true>), dim3(blocks), dim3(256), 0, h->stream, A);
-    else hipLaunchKernelGGL((td_partial_kernel<false>), dim3(blocks), dim3(256), 0, h->stream, A);
-    hipLaunchKernelGGL(td_final_kernel, dim3(1), dim3(64), 0, h->stream, A);
-    CCX_HIP(hipGetLastError());
-    return CCX_OK;
+    return td_forward("ccx_td_loss", h, rows, q, actions, reward, done, q_next_target, q_next_online_or_null, masks_next_or_null,
+                      valid_or_null, weights_or_null, nullptr, gamma, huber_delta, workspace, stats, td_error_or_null);
 }
 
 int ccx_td_loss_backward(ccx_handle* h, int64_t rows, const float* q, const uint8_t* actions, const double* reward,
                          const uint8_t* done, const float* q_next_target, const float* q_next_online_or_null,
                          const uint8_t* masks_next_or_null, const uint8_t* valid_or_null, const float* weights_or_null, float gamma,
                          float huber_delta, const float* stats, const float* grad_loss_or_null, float* grad_q) {
-    if (!h) return fail(CCX_EINVAL, "NULL handle");
-    if (!q || !actions || !reward || !done || !q_next_target || !stats || !grad_q)
-        return fail(CCX_EINVAL, "ccx_td_loss_backward: NULL argument (only q_next_online, masks_next, valid, weights and grad_loss may be NULL)");
-    unsigned blocks = 0;
-    if (int rc = ccxi::row_blocks("ccx_td_loss_backward", rows, 64, blocks)) return rc;
-    if (int rc = check_td("ccx_td_loss_backward", q, q_next_target, q_next_online_or_null, gamma, huber_delta)) return rc;
-    if (misaligned(16, grad_q)) return fail(CCX_EINVAL, "ccx_td_loss_backward: grad_q must be 16-byte aligned");
-    CCX_HIP(hipSetDevice(h->device));
-    TdArgs A = td_args(rows, q, actions, reward, done, q_next_target, q_next_online_or_null, masks_next_or_null, valid_or_null,
-                       weights_or_null, gamma, huber_delta);
-    A.stats_in = stats;
-    A.grad_loss = grad_loss_or_null;
-    A.grad_q = grad_q;
-    if (q_next_online_or_null) hipLaunchKernelGGL((td_bwd_kernel<true>), dim3(blocks), dim3(64), 0, h->stream, A);
-    else hipLaunchKernelGGL((td_bwd_kernel<false>), dim3(blocks), dim3(64), 0, h->stream, A);
-    CCX_HIP(hipGetLastError());
-    return CCX_OK;
+    return td_backward("ccx_td_loss_backward", h, rows, q, actions, reward, done, q_next_target, q_next_online_or_null,
+                       masks_next_or_null, valid_or_null, weights_or_null, nullptr, gamma, huber_delta, stats, grad_loss_or_null, grad_q);
+}
+
+int ccx_td_loss_discounted(ccx_handle* h, int64_t rows, const float* q, const uint8_t* actions, const double* reward,
+                           const uint8_t* done, const float* q_next_target, const float* q_next_online_or_null,
+                           const uint8_t* masks_next_or_null, const uint8_t* valid_or_null, const float* weights_or_null,
+                           const float* discount, float huber_delta, void* workspace, float* stats, float* td_error_or_null) {
+    if (!discount) return fail(CCX_EINVAL, "ccx_td_loss_discounted: NULL discount");
+    return td_forward("ccx_td_loss_discounted", h, rows, q, actions, reward, done, q_next_target, q_next_online_or_null,
+                      masks_next_or_null, valid_or_null, weights_or_null, discount, 0.0f, huber_delta, workspace, stats, td_error_or_null);
+}
+
+int ccx_td_loss_discounted_backward(ccx_handle* h, int64_t rows, const float* q, const uint8_t* actions, const double* reward,
+                                    const uint8_t* done, const float* q_next_target, const float* q_next_online_or_null,
+                                    const uint8_t* masks_next_or_null, const uint8_t* valid_or_null, const float* weights_or_null,
+                                    const float* discount, float huber_delta, const float* stats, const float* grad_loss_or_null,
+                                    float* grad_q) {
+    if (!discount) return fail(CCX_EINVAL, "ccx_td_loss_discounted_backward: NULL discount");
+    return td_backward("ccx_td_loss_discounted_backward", h, rows, q, actions, reward, done, q_next_target, q_next_online_or_null,
+                       masks_next_or_null, valid_or_null, weights_or_null, discount, 0.0f, huber_delta, stats, grad_loss_or_null, grad_q);
 }
 
 }  // extern "C"

@@ -16,6 +16,7 @@ import torch
 
 from ._abi import PRIO_MAX_TD
 from .learner import _require_all, _require_out
+from .nstep import NStepBatch, NStepReplay
 from .replay import ReplayBatch, ReplayRing, _check_batch_size
 
 ONE = 65536                                                              # 1.0 in fixed point: 16 fractional bits
@@ -25,7 +26,7 @@ ONE = 65536                                                              # 1.0 i
 class PrioritizedBatch:
     """A prioritised minibatch (:meth:`PrioritizedReplay.sample`)."""
 
-    batch: ReplayBatch              # the records drawn (``batch.index``: int64 [B], -1 where nothing is drawable)
+    batch: ReplayBatch | NStepBatch  # the records drawn (``index``: int64 [B], -1 where nothing is drawable); an NStepBatch over an NStepReplay
     weights: torch.Tensor           # f32 [B, N]: (p_min / p_i)^beta, the same for every agent of a record; +0.0 at index -1
     leaf_drawn: torch.Tensor        # int32 [B]: the leaf of each record drawn (0 at index -1)
 
@@ -43,6 +44,10 @@ def _check_unit(name: str, value, lo_open: bool = False) -> float:
 class PrioritizedReplay:
     """``PrioritizedReplay(ring, alpha=0.6, beta=0.4, eps=1e-6)``: priorities for the R records of ``ring``.
 
+    ``ring`` is a :class:`ReplayRing`, or an :class:`~collectivecrossing_amd.nstep.NStepReplay` over one: :meth:`push` then
+    marks the cuts too, :meth:`sample` fetches through it and ``PrioritizedBatch.batch`` is an ``NStepBatch``.  ``pr.ring`` is
+    the :class:`ReplayRing` in either case, ``pr.nstep`` the ``NStepReplay`` or ``None``.
+
     Storage, allocated here and public (tests, checkpoints): ``leaf`` int32 [R], the record's priority ``p^alpha`` with 16
     fractional bits (0: never pushed, not drawable); ``pstate`` int64 [4] = {max_leaf, draws, T, min_leaf} ON THE DEVICE
     (``draws`` is this class's own launch counter; ``T`` and ``min_leaf`` are as of the latest :meth:`sample`); ``beta_dev``
@@ -53,12 +58,13 @@ class PrioritizedReplay:
     Every method that enqueues keeps the stream-order contract of :class:`~collectivecrossing_amd.learner.LearnerOps`
     through the batch's ``_enqueue``; the leaves, the tree, ``pstate`` and ``beta_dev`` travel as arguments.  Anything else
     than the tensors described raises ``ValueError`` before the library is called.  Not here: rank-based prioritisation,
-    sampling without replacement, per-agent priorities, n-step targets, priorities shared across shards or GPUs."""
+    sampling without replacement, per-agent priorities, priorities shared across shards or GPUs."""
 
-    def __init__(self, ring: ReplayRing, alpha: float = 0.6, beta: float = 0.4, eps: float = 1e-6):
-        if not isinstance(ring, ReplayRing):
-            raise ValueError("ring must be a ReplayRing")
-        self.ring = ring
+    def __init__(self, ring: ReplayRing | NStepReplay, alpha: float = 0.6, beta: float = 0.4, eps: float = 1e-6):
+        if not isinstance(ring, (ReplayRing, NStepReplay)):
+            raise ValueError("ring must be a ReplayRing or an NStepReplay")
+        self.nstep = ring if isinstance(ring, NStepReplay) else None
+        self.ring = ring = ring.ring if isinstance(ring, NStepReplay) else ring
         self.batch = b = ring.batch
         self.alpha = _check_unit("alpha", alpha)
         self.eps = _check_unit("eps", eps, lo_open=True)
@@ -92,7 +98,7 @@ class PrioritizedReplay:
             self.pstate.zero_()
             self.pstate[:1].fill_(ONE)
         b._current_stream_waits(cur=cur)
-        self.ring.clear()
+        (self.nstep or self.ring).clear()
 
     # ------------------------------------------------------------------ rollout arrays to records
     def push(self, obs0_compact: torch.Tensor, actions: torch.Tensor, traj, masks_next: torch.Tensor | None = None) -> None:
@@ -101,7 +107,10 @@ class PrioritizedReplay:
         new record is drawn at least as often as any other until its TD error is known.  A captured push advances with
         every replay.  Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         ring, b = self.ring, self.batch
-        ring.push(obs0_compact, actions, traj, masks_next=masks_next)    # (checks everything, K among it)
+        if self.nstep is None:
+            ring.push(obs0_compact, actions, traj, masks_next=masks_next)    # (checks everything, K among it)
+        else:
+            self.nstep.push(obs0_compact, actions, traj, masks_next=masks_next)      # (the ring's push, and the cuts)
         b._enqueue(b._lib.ccx_prio_push, ring.steps, ring.state, int(actions.shape[0]), self.leaf, self.pstate)
 
     # ------------------------------------------------------------------ TD errors to priorities
@@ -130,13 +139,13 @@ class PrioritizedReplay:
     def alloc_batch(self, B: int, want_obs: bool = True, want_next_obs: bool = True) -> PrioritizedBatch:
         """Output tensors of :meth:`sample` for B records (static buffers for a captured graph)."""
         b = self.batch
-        mb = self.ring.alloc_batch(B, want_obs, want_next_obs)
+        mb = (self.nstep or self.ring).alloc_batch(B, want_obs, want_next_obs)
         return PrioritizedBatch(mb, b._new((int(B), b.num_agents), torch.float32), b._new((int(B),), torch.int32))
 
     def sample(self, B: int, out: PrioritizedBatch | None = None, stratified: bool = True, want_obs: bool = True,
                want_next_obs: bool = True) -> PrioritizedBatch:
         """Draw B records in proportion to their leaves (``ccx_prio_sample``, include/ccx.h CCX_PRIO) and fetch them
-        (:meth:`ReplayRing.fetch`, the ring's own kernel).
+        (:meth:`ReplayRing.fetch`, the ring's own kernel; over an ``NStepReplay`` its :meth:`fetch`).
 
         The sums over the leaves are rebuilt first (exact integers: the same bits for any order), ``T`` and ``min_leaf`` go
         to ``pstate``.  Draw b takes the two counter-based words of key ``(b, draws)`` on this class's stream of the batch's
@@ -154,19 +163,22 @@ class PrioritizedReplay:
         _require_out(out, PrioritizedBatch, "alloc_batch")
         if out is None:
             out = self.alloc_batch(B, want_obs, want_next_obs)
-        _require_out(out.batch, ReplayBatch, "alloc_batch")
-        _require_all(b.device, ("out.batch.index", out.batch.index, torch.int64, (B,)),
+        _require_out(out.batch, ReplayBatch if self.nstep is None else NStepBatch, "alloc_batch")
+        _require_all(b.device, ("out.batch.index", out.batch.index, torch.int64, (B,)),      # (an NStepBatch hands out its records' index)
                      ("out.weights", out.weights, torch.float32, (B, b.num_agents)),
                      ("out.leaf_drawn", out.leaf_drawn, torch.int32, (B,)))
         b._enqueue(b._lib.ccx_prio_sample, self.ring.steps, self.leaf, self.pstate, self.beta_dev, self.tree, B, int(bool(stratified)),
                    out.batch.index, out.weights, out.leaf_drawn)
-        self.ring.fetch(out.batch.index, out=out.batch)
+        if self.nstep is None:
+            self.ring.fetch(out.batch.index, out=out.batch)
+        else:
+            self.nstep.fetch(out.batch.index, out=out.batch)
         return out
 
     # ------------------------------------------------------------------ checkpoints (host-synchronous: outside the contract)
     def state_dict(self) -> dict:
         """Copies of ``leaf``, ``pstate`` and ``beta``, the hyper-parameters and the ring's own dict; the tree is derived."""
-        ring = self.ring.state_dict()                                    # (waits for the handle's stream)
+        ring = (self.nstep or self.ring).state_dict()                    # (waits for the handle's stream; an NStepReplay's holds the ring's)
         sd = {"leaf": self.leaf.clone(), "pstate": self.pstate.clone(), "beta": self._beta, "alpha": self.alpha, "eps": self.eps,
               "ring": ring}
         torch.cuda.synchronize(self.batch.device)
@@ -183,7 +195,7 @@ class PrioritizedReplay:
         for k, s, d in (("leaf", leaf, self.leaf), ("pstate", pstate, self.pstate)):
             if not isinstance(s, torch.Tensor) or s.dtype is not d.dtype or s.shape != d.shape:
                 raise ValueError(f"state_dict {k} must be a {d.dtype} tensor of shape {tuple(d.shape)}")
-        self.ring.load_state_dict(ring)                                  # (checks the geometry; synchronises)
+        (self.nstep or self.ring).load_state_dict(ring)                  # (checks the geometry; synchronises)
         self.leaf.copy_(leaf)
         self.pstate.copy_(pstate)
         self.alpha, self.eps = alpha, eps

@@ -1,6 +1,6 @@
 """Q-learning on the device (include/ccx.h CCX_QLEARN): epsilon-greedy actions over the legal set from a network's Q-values
 (``ccx_q_actions``, one launch) and the double-DQN TD error with its Huber loss, its means over the rows that count and its
-gradient with respect to the Q-values (``ccx_td_loss`` / ``ccx_td_loss_backward``).  Q-values are the ``[..., 5]`` outputs of
+gradient with respect to the Q-values (``ccx_td_loss`` / ``ccx_td_loss_backward``; with a discount per row, as an n-step minibatch brings it, ``ccx_td_loss_discounted`` and its backward).  Q-values are the ``[..., 5]`` outputs of
 an :class:`~collectivecrossing_amd.learner.MlpHead` or of :class:`~collectivecrossing_amd.sides.SideHeads`; the online and the
 target network are two of them (``target.load_state_dict(online.state_dict())``).
 
@@ -46,8 +46,12 @@ class TdLossResult:
     bad = property(lambda self: self.stats[7])
 
 
-def _check_td_hyper(gamma, huber_delta):
-    """The two hyper-parameters as the f32 values the library will see, or ``ValueError``."""
+def _check_td_hyper(gamma, huber_delta, discount=None):
+    """The two hyper-parameters as the f32 values the library will see, or ``ValueError``.  ``gamma`` is 0.99 where neither
+    it nor ``discount`` is given; with ``discount`` it is not read, and giving both is refused."""
+    if discount is not None and gamma is not None:
+        raise ValueError("give gamma or discount, not both (with discount= every row brings its own)")
+    gamma = 0.99 if gamma is None or discount is not None else gamma
     try:
         gamma, huber_delta = float(np.float32(gamma)), float(np.float32(huber_delta))
     except (TypeError, ValueError):
@@ -66,7 +70,7 @@ class QLearning:
     annealed rate changes between the replays of a captured actor loop without a re-capture.  Every method that enqueues
     keeps the stream-order contract of :class:`~collectivecrossing_amd.learner.LearnerOps` through the batch's ``_enqueue``.
     Anything else than the tensors described raises ``ValueError`` before the library is called; zero rows return without
-    calling it.  Not here: a dueling combine, n-step targets, distributional heads, prioritised sampling (``weights`` and
+    calling it.  Not here: a dueling combine, distributional heads, prioritised sampling (``weights`` and
     ``td_error`` are its hooks; the replay buffer itself is :class:`~collectivecrossing_amd.replay.ReplayRing`), the head's forward fused with the action choice, bf16 / f16."""
 
     def __init__(self, batch, epsilon: float = 1.0):
@@ -153,7 +157,7 @@ class QLearning:
         return TdLossResult(stats[0], stats, b._new(shape, torch.float32) if want_td_error else None, self._workspace(rows),
                             b._new(shape + (5,), torch.float32))
 
-    def _check_td(self, q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, extra=()):
+    def _check_td(self, q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, extra=(), discount=None):
         """The input checks :meth:`td_loss` and :meth:`td_loss_backward` share; returns the leading shape."""
         dev = self.batch.device
         lead = tuple(q.shape[:-1]) if isinstance(q, torch.Tensor) else ()
@@ -165,22 +169,30 @@ class QLearning:
                      ("q_next_target", q_next_target, f, lead + (5,), {"align": 16}),
                      ("q_next_online", q_next_online, f, lead + (5,), {"optional": True, "align": 16}),
                      ("masks_next", masks_next, u8, lead, _OPT), ("valid", valid, u8, lead, _OPT),
-                     ("weights", weights, f, lead, _OPT), *extra)
+                     ("weights", weights, f, lead, _OPT), ("discount", discount, f, lead, _OPT), *extra)
+        if discount is not None and discount.requires_grad:
+            raise ValueError("discount must not require a gradient (it is a constant of the target)")
         for name, t in (("q_next_target", q_next_target), ("q_next_online", q_next_online)):
             if t is not None and t.requires_grad:
                 raise ValueError(f"{name} must not require a gradient (the target is a constant: detach it, or evaluate it "
                                  "under torch.no_grad())")
         return lead
 
-    def _forward(self, q, actions, reward, done, qt, qo, masks_next, valid, weights, hyper, workspace, stats, td_error) -> None:
+    def _forward(self, q, actions, reward, done, qt, qo, masks_next, valid, weights, hyper, workspace, stats, td_error,
+                 discount=None) -> None:
         b = self.batch
-        b._enqueue(b._lib.ccx_td_loss, actions.numel(), q, actions, reward, done, qt, qo, masks_next, valid, weights, *hyper,
-                   workspace, stats, td_error)
+        if discount is None:
+            b._enqueue(b._lib.ccx_td_loss, actions.numel(), q, actions, reward, done, qt, qo, masks_next, valid, weights, *hyper,
+                       workspace, stats, td_error)
+        else:
+            b._enqueue(b._lib.ccx_td_loss_discounted, actions.numel(), q, actions, reward, done, qt, qo, masks_next, valid, weights,
+                       discount, hyper[1], workspace, stats, td_error)
 
     def td_loss(self, q: torch.Tensor, actions: torch.Tensor, reward: torch.Tensor, done: torch.Tensor,
                 q_next_target: torch.Tensor, q_next_online: torch.Tensor | None = None, masks_next: torch.Tensor | None = None,
-                valid: torch.Tensor | None = None, weights: torch.Tensor | None = None, gamma: float = 0.99,
-                huber_delta: float = 1.0, want_td_error: bool = False, out: TdLossResult | None = None) -> TdLossResult:
+                valid: torch.Tensor | None = None, weights: torch.Tensor | None = None, gamma: float | None = None,
+                huber_delta: float = 1.0, want_td_error: bool = False, out: TdLossResult | None = None,
+                discount: torch.Tensor | None = None) -> TdLossResult:
         """The Huber loss of the (double-)DQN TD error, averaged over the rows that count, on the device (``ccx_td_loss``,
         include/ccx.h CCX_QLEARN): two kernels on the handle's stream, bit-defined (the reduction is CCX_PPO_LOSS's fixed f64
         tree), shapes static -- ``valid`` is a selection inside the kernel.
@@ -193,6 +205,10 @@ class QLearning:
         The target is ``reward + (done ? 0 : gamma * q_next_target[argmax])``.  A row counts iff its ``valid`` byte is not
         zero and its action is 0..4; an action in 5..254 is tallied in ``stats[7]``.  ``huber_delta = inf`` is the half
         squared error.  ``td_error`` (``want_td_error``, or ``out``'s) is ``q[a] - target``, +0.0 where the row does not count.
+        ``gamma`` defaults to 0.99.  ``discount`` f32 of the leading shape (``NStepBatch.discount``) gives every row its own
+        in the place of ``gamma`` (``ccx_td_loss_discounted``: the same rule, tree and outputs; an array filled with one
+        value gives the bits of that ``gamma``); ``gamma`` is then not read, giving both raises ``ValueError``, and so does a
+        ``discount`` that requires grad.
 
         When ``q.requires_grad`` and grad mode is on, the call is a ``torch.autograd.Function``: ``r.loss.backward()``
         reaches ``q`` through ``ccx_td_loss_backward`` (one kernel; rows that do not count get exactly +0.0), ``out=`` is
@@ -201,8 +217,8 @@ class QLearning:
         :meth:`alloc_td_loss`.
         Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         b = self.batch
-        hyper = _check_td_hyper(gamma, huber_delta)
-        lead = self._check_td(q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights)
+        hyper = _check_td_hyper(gamma, huber_delta, discount)
+        lead = self._check_td(q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, discount=discount)
         if q.requires_grad and torch.is_grad_enabled():
             if out is not None:
                 raise ValueError("out= cannot be used when q requires a gradient (the autograd path allocates its outputs)")
@@ -211,7 +227,7 @@ class QLearning:
                 return TdLossResult(stats[0], stats.detach(), q.new_zeros(lead) if want_td_error else None)
             td_error = b._new(lead, torch.float32) if want_td_error else None
             stats = _TdLoss.apply(self, q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, hyper,
-                                  td_error)
+                                  td_error, discount)
             return TdLossResult(stats[0], stats.detach(), td_error)
         _require_out(out, TdLossResult, "alloc_td_loss")
         if out is None:
@@ -227,37 +243,42 @@ class QLearning:
             return out
         workspace = self._workspace_arg(workspace, actions.numel())
         self._forward(q.detach(), actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, hyper,
-                      workspace, out.stats, out.td_error)
+                      workspace, out.stats, out.td_error, discount)
         return out
 
     def td_loss_backward(self, q: torch.Tensor, actions: torch.Tensor, reward: torch.Tensor, done: torch.Tensor,
                          q_next_target: torch.Tensor, q_next_online: torch.Tensor | None = None,
                          masks_next: torch.Tensor | None = None, valid: torch.Tensor | None = None,
-                         weights: torch.Tensor | None = None, gamma: float = 0.99, huber_delta: float = 1.0, *,
-                         stats: torch.Tensor, grad_loss: torch.Tensor | None = None, out=None) -> torch.Tensor:
+                         weights: torch.Tensor | None = None, gamma: float | None = None, huber_delta: float = 1.0, *,
+                         stats: torch.Tensor, grad_loss: torch.Tensor | None = None, out=None,
+                         discount: torch.Tensor | None = None) -> torch.Tensor:
         """``grad_q`` f32 [..., 5] of :meth:`td_loss`'s ``loss`` (``ccx_td_loss_backward``: one kernel that recomputes the
         forward terms from the same inputs and the forward's ``stats``).  Every element is written: the gradient sits at the
         taken action of a row that counts, +0.0 everywhere else.  ``grad_loss`` f32 [1] or 0-dim on the device (``None`` =
         1).  ``out`` reuses a f32 tensor of the shape of ``q`` (16-byte aligned) or the ``grad_q`` of an
-        :meth:`alloc_td_loss` result.
+        :meth:`alloc_td_loss` result.  ``discount`` as in :meth:`td_loss` (``ccx_td_loss_discounted_backward``).
         Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         b = self.batch
-        hyper = _check_td_hyper(gamma, huber_delta)
+        hyper = _check_td_hyper(gamma, huber_delta, discount)
         if isinstance(out, TdLossResult):
             out = out.grad_q
         if out is None and isinstance(q, torch.Tensor):
             out = torch.empty_like(q, requires_grad=False)
         lead = tuple(q.shape[:-1]) if isinstance(q, torch.Tensor) else ()
         self._check_td(q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, (
-            ("stats", stats, torch.float32, (8,)), ("out", out, torch.float32, lead + (5,), {"align": 16})))
+            ("stats", stats, torch.float32, (8,)), ("out", out, torch.float32, lead + (5,), {"align": 16})), discount=discount)
         if grad_loss is not None:                                        # (inline: one element in either of two shapes)
             if (not isinstance(grad_loss, torch.Tensor) or grad_loss.dtype is not torch.float32 or grad_loss.device != b.device
                     or grad_loss.numel() < 1 or grad_loss.dim() > 1 or not grad_loss.is_contiguous()):
                 raise ValueError(f"grad_loss must be a torch.float32 tensor with one element (0-dim or [1]) on {b.device}")
         if q.numel():
             q = q.detach()
-            b._enqueue(b._lib.ccx_td_loss_backward, actions.numel(), q, actions, reward, done, q_next_target, q_next_online,
-                       masks_next, valid, weights, *hyper, stats, grad_loss, out)
+            if discount is None:
+                b._enqueue(b._lib.ccx_td_loss_backward, actions.numel(), q, actions, reward, done, q_next_target, q_next_online,
+                           masks_next, valid, weights, *hyper, stats, grad_loss, out)
+            else:
+                b._enqueue(b._lib.ccx_td_loss_discounted_backward, actions.numel(), q, actions, reward, done, q_next_target,
+                           q_next_online, masks_next, valid, weights, discount, hyper[1], stats, grad_loss, out)
         return out
 
 
@@ -267,12 +288,12 @@ class _TdLoss(torch.autograd.Function):
     loss, is differentiable: the gradient arriving at the other seven is not read."""
 
     @staticmethod
-    def forward(ctx, ql, q, actions, reward, done, qt, qo, masks_next, valid, weights, hyper, td_error):
+    def forward(ctx, ql, q, actions, reward, done, qt, qo, masks_next, valid, weights, hyper, td_error, discount=None):
         q = q.detach()
         stats = torch.zeros((8,), dtype=torch.float32, device=ql.batch.device)
         ql._forward(q, actions, reward, done, qt, qo, masks_next, valid, weights, hyper, ql._workspace(actions.numel()), stats,
-                    td_error)
-        ctx.ql, ctx.hyper = ql, hyper
+                    td_error, discount)
+        ctx.ql, ctx.hyper, ctx.discount = ql, hyper, discount
         ctx.rest = (actions, reward, done, qt, qo, masks_next, valid, weights)
         ctx.save_for_backward(q, stats)
         return stats
@@ -281,5 +302,7 @@ class _TdLoss(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_stats):
         q, stats = ctx.saved_tensors
-        gq = ctx.ql.td_loss_backward(q, *ctx.rest, *ctx.hyper, stats=stats, grad_loss=grad_stats.contiguous())
-        return (None, gq) + (None,) * 10
+        gamma = None if ctx.discount is not None else ctx.hyper[0]
+        gq = ctx.ql.td_loss_backward(q, *ctx.rest, gamma, ctx.hyper[1], stats=stats, grad_loss=grad_stats.contiguous(),
+                                     discount=ctx.discount)
+        return (None, gq) + (None,) * 11

@@ -1121,7 +1121,7 @@ int ccx_sides_backward(ccx_handle* h, int64_t M, int32_t N, uint64_t slots, int3
  * a HIP graph.  Offsets are 64-bit.  A NULL handle or a NULL required pointer, rows < 1 (or so many that a grid would pass
  * 2^31 - 1 workgroups), a Q array or grad_q that is not 16-byte aligned, a workspace that is not 8-byte aligned, a gamma that
  * is not finite or lies outside [0, 1], a huber_delta that is not > 0: CCX_EINVAL with a ccx_last_error message, before any
- * launch.  Not here: a dueling combine, n-step targets, distributional heads, prioritised sampling (weights and td_error
+ * launch.  n-step targets are CCX_NSTEP (a discount per row: ccx_td_loss_discounted).  Not here: a dueling combine, distributional heads, prioritised sampling (weights and td_error
  * are its two hooks; the replay buffer itself is CCX_REPLAY), the fusion of the head's forward with the action choice, bf16 / f16.
  */
 int ccx_q_actions(ccx_handle* h, const float* q /* [E][N][5] */, const uint8_t* masks_or_null /* [E][N] */,
@@ -1196,7 +1196,7 @@ int ccx_td_loss_backward(ccx_handle* h, int64_t rows, const float* q /* [M][5] *
  * < 1 or S E >= 2^31, K outside 1..S, B outside 1..2^31 / N, a compact or row array that is not 16-byte aligned, an f64 / i64
  * array that is not 8-byte aligned: CCX_EINVAL with a ccx_last_error message, before any launch.  Not here: prioritised or
  * recency-weighted sampling (index, ccx_replay_fetch and ccx_td_loss's weights / td_error are the hooks), sampling without
- * replacement, n-step returns, frames shared between obs_c and next_c, records of single agents or of sequences, a ring over
+ * replacement, frames shared between obs_c and next_c, records of single agents or of sequences, a ring over
  * several GPUs (each shard has its own), rows-form storage, bf16 / f16.
  */
 int ccx_replay_push(ccx_handle* h, int64_t ring_steps, float* ring_obs_c /* [R][N][4] */, float* ring_next_c /* [R][N][4] */,
@@ -1290,6 +1290,101 @@ int ccx_prio_update(ccx_handle* h, int64_t ring_steps, int32_t* leaf /* [R] */, 
 int ccx_prio_sample(ccx_handle* h, int64_t ring_steps, const int32_t* leaf /* [R] */, int64_t* pstate /* [4] */,
                     const float* beta /* device f32 [1] */, int64_t* tree /* [ccx_prio_tree_words(R)] */, int64_t batch,
                     int32_t stratified, int64_t* index /* [B] */, float* weights /* [B][N] */, int32_t* leaf_drawn /* [B] */);
+/*
+ * CCX_NSTEP: n-step targets over the ring of CCX_REPLAY.  The ring is step-major, so the successor of a record is the same
+ * env one ring step on; one byte per record says whether the env's episode ended with it; and ONE kernel walks every drawn
+ * record forward through up to n - 1 successors and writes the minibatch of ccx_replay_fetch with the discounted n-step
+ * reward in the place of the reward, the state the window ends on in the place of the next state, and per row the discount
+ * gamma^m its bootstrap takes (ccx_td_loss_discounted reads it where ccx_td_loss reads gamma).  The integer part is exact;
+ * the f64 chain follows the discipline of CCX_QLEARN: every line is ONE correctly rounded operation, nothing is fused, what
+ * a rule does not read is SELECTED away, never multiplied by zero.
+ *
+ * Storage (the caller's, travelling as arguments): cut u8 [R], one byte per record (env-step) of the ring, initially 0.  Not
+ * zero: the episode of env e ended with this step, the record in the next ring step is not its continuation.
+ *
+ * ccx_nstep_push(ring_steps, ring_state, K, env_flags u8 [K][E], cut).  Enqueued directly BEHIND a ccx_replay_push of the same
+ * K steps into the same ring: with head' = ring_state[0] (which that push advanced by K) read on the device,
+ *     cut[((head' - K + s) mod S) * E + e] = (env_flags[s][e] & (CCX_EF_ALL_TERMINATED | CCX_EF_ALL_TRUNCATED | CCX_EF_RESET)) ? 1 : 0
+ * for s = 0 .. K - 1, e = 0 .. E - 1.  (head' - K < 0, a caller that pushed nothing, counts as 0, as in ccx_prio_push: the
+ * stores stay inside cut.)
+ *
+ * ccx_nstep_mark_cut(ring_steps, ring_state, env_mask u8 [E] or NULL, cut).  cut = 1 at the newest ring step, (head - 1) mod S,
+ * for the envs whose mask byte is not zero (NULL: all envs); nothing while head == 0.  For a caller that restarts envs between
+ * two pushes by hand (ccx_reset and its kin): the library cannot see that.
+ *
+ * ccx_nstep_fetch.  The ring of ccx_replay_fetch, cut, n with 1 <= n <= min(S, CCX_NSTEP_MAX), gamma finite in [0, 1], and
+ * index i64 [B].  Outputs: those of ccx_replay_fetch, and discount f32 [B][N] and span u8 [B][N]; every element of every
+ * output given is written.  For b with i = index[b] in [0, R): p = i / E, e = i % E, slot_k = ((p + k) mod S) * E + e, and
+ * head = ring_state[0] read on the device:
+ *     avail = head == 0 ? 0 : (head < S && p >= head) ? 0 : (head - 1 - p) mod S        (non-negative: successors that exist)
+ *     m_env = 1;  while (m_env < n && m_env <= avail && cut[slot_{m_env-1}] == 0) ++m_env;                    (per record)
+ *   per agent a:
+ *     m_a = 1;  while (m_a < m_env && done[slot_{m_a-1}][a] == 0 && valid[slot_{m_a}][a] != 0) ++m_a;
+ *     g = 1.0 (f64);  G = reward[slot_0][a];
+ *     for k = 1 .. m_a - 1:  g = g * (double)gamma;  t = g * reward[slot_k][a];  G = G + t;   (three f64 operations, k ascending)
+ *     g = g * (double)gamma;  discount = (float)g;  span = m_a;
+ *     done_out  = done[slot_{m_a-1}][a];
+ *     dropped   = m_a < m_env && done_out == 0;
+ *     valid_out = dropped ? 0 : valid[slot_0][a];
+ *     reward_out = G;   actions, index and the obs rows: record slot_0, as ccx_replay_fetch
+ *     next_obs rows and masks_next: record slot_{m_env-1}
+ * A dropped row is an agent that stopped being live inside the env's window without terminating and without an env cut --
+ * only a user truncation class can do that; the env's next state is then not this agent's bootstrap state, so the row is
+ * left out (valid 0), not given a wrong target.  next_obs and masks_next are env-level: the state every bootstrapping agent
+ * of the record continues from.  A reward beyond m_a reaches no result; a NaN inside the window goes through loudly.  An
+ * index outside [0, R) gives the EMPTY record of CCX_REPLAY with discount = (float)(double)gamma = gamma and span = 1, and
+ * reads nothing.  Every slot_k is reduced mod S (p < S and k < n <= S: one conditional subtraction), so NO access can leave
+ * the arrays, whatever head, cut or index hold.  With n == 1 every output shared with ccx_replay_fetch has its bits,
+ * discount is gamma everywhere and span is 1.
+ *
+ * ccx_nstep_sample is the same kernel drawing its own indices by exactly ccx_replay_sample's draw: the same stream constant,
+ * the same key (b, draws), F = min(head, S) * E, draws = ring_state[1], and then draws += 1 -- for equal state it names the
+ * records ccx_replay_sample names.
+ *
+ * ccx_td_loss_discounted / ccx_td_loss_discounted_backward: ccx_td_loss / ccx_td_loss_backward with discount f32 [M] (device,
+ * 4-byte aligned) in the place of gamma.  The per-row rule is CCX_QLEARN's, unchanged, with discount[i] where it says gamma:
+ * step 4 is nb = (done[i] || discount[i] == 0.0f) ? +0.0f : discount[i] * boot.  The tree, stats, td_error, the backward and
+ * the NULL combinations are the same; a discount array filled with one value gives the bits of ccx_td_loss at that gamma.
+ * The values are the caller's: they are not range-checked.
+ *
+ * Launches: ccx_nstep_push ONE kernel, ccx_nstep_mark_cut ONE, ccx_nstep_fetch ONE, ccx_nstep_sample TWO (the fetch and one
+ * plain lane behind it that advances draws); ccx_td_loss_discounted TWO, its backward ONE.  No host synchronisation, no
+ * allocation; everything captures into a HIP graph and advances with every replay.  In the fetch no successor address depends
+ * on loaded data: the loads of cut, done, valid and reward of all n records are in flight together, and the one dependent
+ * load is next_c / masks_next of record m_env - 1.  A NULL handle or required pointer, S < 1 or S E >= 2^31, K outside 1..S,
+ * n outside 1..min(S, 16), gamma not finite or outside [0, 1], B outside 1..2^31 / N, a misaligned array: CCX_EINVAL with a
+ * ccx_last_error message, before any launch.  Not here: n above 16, a per-agent next state for dropped rows,
+ * lambda-returns or Retrace, n-step inside the actor, sequences, a dueling combine, rings across GPUs, bf16 / f16.
+ */
+#define CCX_NSTEP_MAX 16
+int ccx_nstep_push(ccx_handle* h, int64_t ring_steps, const int64_t* ring_state /* [4] */, int64_t K,
+                   const uint8_t* env_flags /* [K][E] */, uint8_t* cut /* [R] */);
+int ccx_nstep_mark_cut(ccx_handle* h, int64_t ring_steps, const int64_t* ring_state /* [4] */,
+                       const uint8_t* env_mask_or_null /* [E] */, uint8_t* cut /* [R] */);
+int ccx_nstep_sample(ccx_handle* h, int64_t ring_steps, float* ring_obs_c, float* ring_next_c, uint8_t* ring_actions,
+                     double* ring_reward, uint8_t* ring_done, uint8_t* ring_valid, uint8_t* ring_masks_next, int64_t* ring_state,
+                     const uint8_t* cut /* [R] */, int32_t n, float gamma, int64_t batch, float* obs_or_null /* [B][N][L] */,
+                     float* next_obs_or_null /* [B][N][L] */, uint8_t* actions /* [B][N] */, double* reward /* [B][N] */,
+                     uint8_t* done /* [B][N] */, uint8_t* valid /* [B][N] */, uint8_t* masks_next /* [B][N] */,
+                     int64_t* index /* [B] */, float* discount /* [B][N] */, uint8_t* span /* [B][N] */);
+int ccx_nstep_fetch(ccx_handle* h, int64_t ring_steps, float* ring_obs_c, float* ring_next_c, uint8_t* ring_actions,
+                    double* ring_reward, uint8_t* ring_done, uint8_t* ring_valid, uint8_t* ring_masks_next, int64_t* ring_state,
+                    const uint8_t* cut /* [R] */, int32_t n, float gamma, int64_t batch, const int64_t* index_in /* [B] */,
+                    float* obs_or_null, float* next_obs_or_null, uint8_t* actions, double* reward, uint8_t* done, uint8_t* valid,
+                    uint8_t* masks_next, int64_t* index, float* discount, uint8_t* span);
+int ccx_td_loss_discounted(ccx_handle* h, int64_t rows, const float* q /* [M][5] */, const uint8_t* actions /* [M] */,
+                           const double* reward /* [M] */, const uint8_t* done /* [M] */, const float* q_next_target /* [M][5] */,
+                           const float* q_next_online_or_null /* [M][5] */, const uint8_t* masks_next_or_null /* [M] */,
+                           const uint8_t* valid_or_null /* [M] */, const float* weights_or_null /* [M] */,
+                           const float* discount /* [M] */, float huber_delta, void* workspace, float* stats /* [8] */,
+                           float* td_error_or_null /* [M] */);
+int ccx_td_loss_discounted_backward(ccx_handle* h, int64_t rows, const float* q /* [M][5] */, const uint8_t* actions /* [M] */,
+                                    const double* reward /* [M] */, const uint8_t* done /* [M] */,
+                                    const float* q_next_target /* [M][5] */, const float* q_next_online_or_null /* [M][5] */,
+                                    const uint8_t* masks_next_or_null /* [M] */, const uint8_t* valid_or_null /* [M] */,
+                                    const float* weights_or_null /* [M] */, const float* discount /* [M] */, float huber_delta,
+                                    const float* stats /* [8] */, const float* grad_loss_or_null /* [1] */,
+                                    float* grad_q /* [M][5] */);
 /*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
