@@ -105,6 +105,7 @@ class CcxSlotGroup(C.Structure):
 
 PRIO_MAX_TD = 8
 NSTEP_MAX = 16
+DUELING_MAX_ARRAYS = 4
 
 COUNTER_FIELDS =tuple(name for name, _ in CcxCounters._fields_)
 
@@ -196,6 +197,10 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_nstep_fetch": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 9 + [C.c_int32, C.c_float, C.c_int64] + [C.c_void_p] * 11),
     "ccx_td_loss_discounted": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 10 + [C.c_float] + [C.c_void_p] * 3),
     "ccx_td_loss_discounted_backward": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 10 + [C.c_float] + [C.c_void_p] * 3),
+    "ccx_dueling_forward": (C.c_int, [_H, C.c_int64, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "ccx_dueling_backward": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p]),
+    "ccx_mlp_q_actions": (C.c_int, [_H] + [C.c_int32] * 3 + [C.c_void_p] * 10),
+    "ccx_sides_q_actions": (C.c_int, [_H] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.POINTER(CcxSlotGroup)] + [C.c_void_p] * 5),
     "ccx_set_check_inputs":(C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),

@@ -1,7 +1,8 @@
 // ccx_qlearn.hip -- CCX_QLEARN (include/ccx.h): epsilon-greedy actions over the legal set from a network's Q-values, and the
 // double-DQN TD error with its Huber loss, its means over the rows that count and its gradient with respect to the Q-values.
 // The per-slot and per-row rules and the final values are ccx_qlearn.h; the tree is ccx_tree.h's; the slot rule (which (e, a) a
-// lane owns, its small loads, its key) is ccx_draw.h's; the rows of five f32 travel through LDS by ccx_rows.h.
+// lane owns, its small loads, its key) is ccx_draw.h's; from a slot's five Q-values to its stores is ccx_qact.h's choose (the
+// fused actor kernels of ccx_mlp.hip and ccx_sides.hip run the same); the rows of five f32 travel through LDS by ccx_rows.h.
 //
 // q_act_kernel: ccx_sample.hip's shape.  One lane owns one slot, a workgroup is one wave; every load -- the small ones, the
 // exploration rate, the wave's pieces -- is issued before the first wait.  The greedy instantiation reads neither counter.
@@ -13,8 +14,7 @@
 // else but `stats`; every element of grad_q is written, whole 16-byte pieces through LDS.
 // tdn_partial_kernel / tdn_bwd_kernel: the same two bodies with discount[row] in the place of gamma (CCX_NSTEP:
 // ccx_td_loss_discounted and its backward); td_final_kernel serves both.
-#include "ccx_draw.h"
-#include "ccx_qlearn.h"
+#include "ccx_qact.h"
 #include "ccx_rows.h"
 
 using ccx_draw::DrawArgs;
@@ -37,20 +37,7 @@ __global__ __launch_bounds__(64) void q_act_kernel(const float* q, const DrawArg
     float l[5];
     ccx_rows::load_rows(q, pieces, W, l);
     if (s.slot >= D.EN) return;
-    const bool dead = (v.term | v.trunc) != 0;
-    const uint32_t m = ccx_qlearn::legal_set(v.mbyte);
-    uint32_t action = ccx_qlearn::greedy(l, m);
-    bool explore = false;
-    if (EPS) {
-        const uint32_t g = D.genv0 + (uint32_t)s.e;
-        const uint32_t u1 = ccx::random_word(D.seed_lo, D.seed_hi ^ ccx::kQExploreStream, g, v.episode, v.step, s.a);
-        const uint32_t u2 = ccx::random_word(D.seed_lo, D.seed_hi ^ ccx::kQChoiceStream, g, v.episode, v.step, s.a);
-        explore = ccx_qlearn::explores(u1, eps);
-        const uint32_t ch = ccx_qlearn::choice(u2, m);
-        action = explore ? ch : action;
-    }
-    D.actions[s.slot] = dead ? (uint8_t)CCX_ACTION_ABSENT : (uint8_t)action;
-    if (explored) explored[s.slot] = (!dead && explore) ? (uint8_t)1 : (uint8_t)0;
+    ccx_qact::choose<EPS>(D, s, v, l, eps, explored);
 }
 
 struct TdArgs {
@@ -281,8 +268,7 @@ int ccx_q_actions(ccx_handle* h, const float* q, const uint8_t* masks_or_null, c
     if (!q || !actions) return fail(CCX_EINVAL, "ccx_q_actions: NULL argument (q and actions are required)");
     if (misaligned(16, q)) return fail(CCX_EINVAL, "ccx_q_actions: q must be 16-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
-    DrawArgs D = ccx_draw::draw_args(h, masks_or_null, actions, nullptr, nullptr);
-    D.seed_hi = h->rng_hi;                                              // the kernel adds its two streams itself
+    const DrawArgs D = ccx_qact::draw_args(h, masks_or_null, actions);
     const dim3 grid((unsigned)((D.EN + 63) / 64)), block(64);           // E < 2^31, N <= 64: below 2^31
     with_flags([&](auto mask, auto eps) {
         hipLaunchKernelGGL((q_act_kernel<decltype(mask)::value, decltype(eps)::value>), grid, block, 0, h->stream, q, D,

@@ -18,8 +18,10 @@
 // The fused draw is ccx_draw.h's small_loads / finish with the Slot taken from the map (slot = m N + a, e = m, a): the same
 // code ccx_sample.hip and ccx_mlp.hip run.  Slots that no group owns form one head-less group behind the others; its tiles
 // run no layer and store 255 / +0.0 / +0.0.
+// The fused Q choice (ccx_sides_q_actions, CCX_DUELING) is the same kernel with ccx_qact.h's from_tile behind the tile.
 #include "ccx_draw.h"
 #include "ccx_mlp_tile.h"
+#include "ccx_qact.h"
 #include "ccx_sides.h"
 
 using ccx_draw::DrawArgs;
@@ -135,6 +137,36 @@ __global__ __launch_bounds__(1024) void sides_draw_kernel(const SidesArgs S, con
     ccx_draw::finish<DET, STATS>(D, s, v, l);
 }
 
+// sides_draw_kernel with ccx_q_actions' choice (ccx_qact.h) in the place of the softmax draw, as obs_q_kernel of ccx_dueling.hip:
+// S.O = 5 takes the tile's outputs as the Q-values, S.O = 6 (DUEL) puts them through the dueling combine first; with DUEL S.y
+// is null and the COMBINED values go to q from wave 0's lanes.  Slots that no group owns get 255 / 0, no q and no layer.
+template <bool EPS, bool DUEL>
+__global__ __launch_bounds__(1024) void obs_q_groups_kernel(const SidesArgs S, const DrawArgs D, const float* epsilon, uint8_t* explored, float* q) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const uint32_t lane = threadIdx.x & 63u;
+    const bool first = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) == 0;
+    const Tile t = tile_of(S, lane);
+    const bool live = first && (int)lane < t.nr;
+    if (t.grp.w1t == nullptr) {                                           // (uniform) slots that no group owns
+        if (live) {
+            D.actions[t.rw.row] = (uint8_t)CCX_ACTION_ABSENT;
+            if (explored) explored[t.rw.row] = (uint8_t)0;
+        }
+        return;
+    }
+    const ccx_draw::Slot s{t.rw.row, t.rw.m, t.rw.a};
+    ccx_draw::Small v;
+    float eps = 0.0f;
+    if (first) {                                                          // wave 0's small loads, in flight under the layers
+        v = ccx_draw::small_loads<!EPS>(D, s, D.masks != nullptr);
+        if (EPS) eps = epsilon[0];
+    }
+    const float* y = ccx_tile::mlp_tile<true>(head_of(S, t.grp), PickedRows{t.nr, t.rw.row, flat_rows(lds, S, true)}, lds);
+    __syncthreads();
+    if (!live) return;
+    ccx_qact::from_tile<EPS, DUEL>(D, s, v, y, lane, eps, explored, q ? q + s.slot * 5 : nullptr);
+}
+
 // The table of a call from the caller's groups: checked, the prefix counts filled.  `rest`: append the head-less group of
 // the slots no group owns (the draw).
 int make_table(const char* who, int64_t M, int32_t N, int32_t num_groups, const ccx_slot_group* groups, bool rest, ccx_sides::Table& tab) {
@@ -216,6 +248,34 @@ int ccx_sides_sample_actions(ccx_handle* h, int32_t H, int32_t activation, const
         hipLaunchKernelGGL((sides_draw_kernel<DET, STATS>), grid, block, bytes, h->stream, S, D);
         return CCX_OK;
     }, deterministic != 0, logp_or_null || entropy_or_null);
+    if (rc) return rc;
+    CCX_HIP(hipGetLastError());
+    return CCX_OK;
+}
+
+int ccx_sides_q_actions(ccx_handle* h, int32_t H, int32_t activation, int32_t O, const float* obs, int32_t num_groups,
+                        const ccx_slot_group* groups, const uint8_t* masks_or_null, const float* epsilon_or_null, uint8_t* actions,
+                        uint8_t* explored_or_null, float* q_or_null) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (!obs || !actions) return fail(CCX_EINVAL, "ccx_sides_q_actions: NULL argument (obs and actions are required)");
+    if (O != 5 && O != 6) return fail(CCX_EINVAL, "ccx_sides_q_actions: O = %d, 5 (plain) or 6 (dueling) is required", (int)O);
+    const int32_t L = ccx_obs_len(h->N);
+    if (const int rc = ccx_tile::check_dims("ccx_sides_q_actions", L, H, O, activation)) return rc;
+    SidesArgs S{};
+    if (const int rc = make_table("ccx_sides_q_actions", h->E, h->N, num_groups, groups, true, S.tab)) return rc;
+    if (misaligned(16, obs)) return fail(CCX_EINVAL, "ccx_sides_q_actions: obs must be 16-byte aligned");
+    if (misaligned(4, epsilon_or_null, q_or_null)) return fail(CCX_EINVAL, "ccx_sides_q_actions: epsilon and q must be 4-byte aligned");
+    CCX_HIP(hipSetDevice(h->device));
+    S.x = obs, S.y = O == 6 ? nullptr : q_or_null, S.hidden = nullptr, S.M = h->E, S.N = h->N, S.L = L, S.H = H, S.O = O, S.activation = activation;
+    const DrawArgs D = ccx_qact::draw_args(h, masks_or_null, actions);
+    const size_t bytes = ccx_tile::lds_floats(L, H, O, true) * sizeof(float) + 64 * sizeof(long long);
+    const dim3 grid(S.tab.first[S.tab.num]), block(64 * (H / ccx_mlp::kGroup));
+    const int rc = with_flags([&](auto eps, auto duel) -> int {
+        constexpr bool EPS = decltype(eps)::value, DUEL = decltype(duel)::value;
+        CCX_HIP(ccx_tile::allow_lds(obs_q_groups_kernel<EPS, DUEL>, bytes));
+        hipLaunchKernelGGL((obs_q_groups_kernel<EPS, DUEL>), grid, block, bytes, h->stream, S, D, epsilon_or_null, explored_or_null, q_or_null);
+        return CCX_OK;
+    }, epsilon_or_null != nullptr, O == 6);
     if (rc) return rc;
     CCX_HIP(hipGetLastError());
     return CCX_OK;

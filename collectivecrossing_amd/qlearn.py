@@ -2,7 +2,9 @@
 (``ccx_q_actions``, one launch) and the double-DQN TD error with its Huber loss, its means over the rows that count and its
 gradient with respect to the Q-values (``ccx_td_loss`` / ``ccx_td_loss_backward``; with a discount per row, as an n-step minibatch brings it, ``ccx_td_loss_discounted`` and its backward).  Q-values are the ``[..., 5]`` outputs of
 an :class:`~collectivecrossing_amd.learner.MlpHead` or of :class:`~collectivecrossing_amd.sides.SideHeads`; the online and the
-target network are two of them (``target.load_state_dict(online.state_dict())``).
+target network are two of them (``target.load_state_dict(online.state_dict())``).  A head with six outputs is a dueling head
+(CCX_DUELING): its rows go through ``dueling`` to Q-values, and ``mlp_q_actions`` / ``sides_q_actions`` take observation rows
+to actions in one launch for either kind.
 
 :class:`QLearning` is a class of its own, not a set of methods of the batch, for the reason ``sides.py`` gives: the
 stream-order table of the batch's classes (tests/_stream_order.py) is closed, and this class brings its own proof
@@ -10,12 +12,15 @@ stream-order table of the batch's classes (tests/_stream_order.py) is closed, an
 
 from __future__ import annotations
 
+import ctypes as C
 from dataclasses import dataclass
 
 import numpy as np
 import torch
 
-from .learner import _OPT, _require, _require_all, _require_out
+from ._abi import DUELING_MAX_ARRAYS
+from .learner import MlpHead, _OPT, _require, _require_all, _require_out
+from .sides import SideHeads
 
 
 @dataclass
@@ -70,8 +75,10 @@ class QLearning:
     annealed rate changes between the replays of a captured actor loop without a re-capture.  Every method that enqueues
     keeps the stream-order contract of :class:`~collectivecrossing_amd.learner.LearnerOps` through the batch's ``_enqueue``.
     Anything else than the tensors described raises ``ValueError`` before the library is called; zero rows return without
-    calling it.  Not here: a dueling combine, distributional heads, prioritised sampling (``weights`` and
-    ``td_error`` are its hooks; the replay buffer itself is :class:`~collectivecrossing_amd.replay.ReplayRing`), the head's forward fused with the action choice, bf16 / f16."""
+    calling it.  The dueling combine (:meth:`dueling`, :meth:`dueling_into`, :meth:`dueling_backward`) and the head's forward
+    fused with the action choice (:meth:`mlp_q_actions`, :meth:`sides_q_actions`) are include/ccx.h CCX_DUELING.  Not here:
+    distributional heads, prioritised sampling (``weights`` and ``td_error`` are its hooks; the replay buffer itself is
+    :class:`~collectivecrossing_amd.replay.ReplayRing`), bf16 / f16."""
 
     def __init__(self, batch, epsilon: float = 1.0):
         from .batched import BatchedCollectiveCrossing
@@ -137,6 +144,122 @@ class QLearning:
         eps = None if greedy else self.epsilon_dev
         q = q.detach()
         b._enqueue(b._lib.ccx_q_actions, q, masks, eps, out.actions, out.explored)
+        return out
+
+    # ------------------------------------------------------------------ observation rows to actions (CCX_DUELING)
+    def _check_fused(self, who, net, obs, masks, q_out, want_explored, out):
+        """The checks :meth:`mlp_q_actions` and :meth:`sides_q_actions` share, behind the test of ``net`` itself; returns
+        ``out``."""
+        b = self.batch
+        E, N = b.num_envs, b.num_agents
+        if net.O not in (5, 6) or net.L != b.obs_len:
+            raise ValueError(f"{who} needs O == 5 (plain) or O == 6 (dueling) and L == obs_len == {b.obs_len}, got O = {net.O}, "
+                             f"L = {net.L}")
+        _require_out(out, QActions, "alloc_q_actions")
+        if out is None:
+            out = self.alloc_q_actions(want_explored)
+        _require_all(b.device, ("obs", obs, torch.float32, (E, N, b.obs_len), {"align": 16}), ("masks", masks, torch.uint8, (E, N), _OPT),
+                     ("q_out", q_out, torch.float32, (E, N, 5), _OPT), ("out.actions", out.actions, torch.uint8, (E, N)),
+                     ("out.explored", out.explored, torch.uint8, (E, N), _OPT))
+        return out
+
+    def mlp_q_actions(self, head, obs: torch.Tensor, masks: torch.Tensor | None = None, greedy: bool = False,
+                      want_explored: bool = False, q_out: torch.Tensor | None = None, out: QActions | None = None) -> QActions:
+        """Observation rows to epsilon-greedy actions in ONE launch (``ccx_mlp_q_actions``, include/ccx.h CCX_DUELING): by
+        definition ``q_actions(head(obs), ...)`` for a head with ``O == 5`` and ``q_actions(dueling(head(obs)), ...)`` for
+        one with ``O == 6`` -- the same key, the same rule for terminated or truncated agents, the same bits in ``actions``
+        and ``explored`` -- without the Q-values' round trip through memory and without the further launches.  ``head`` is
+        an :class:`~collectivecrossing_amd.learner.MlpHead` of this batch with ``L == obs_len``; ``obs`` f32 [E, N, L]
+        (contiguous, 16-byte aligned: the ``obs`` of ``step`` / ``rollout``); ``q_out`` f32 [E, N, 5] receives the COMBINED
+        Q-values of every slot, dead ones included.  ``masks``, ``greedy``, ``want_explored`` and ``out`` are
+        :meth:`q_actions`'.  No gradient flows through this call.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
+        b = self.batch
+        if not isinstance(head, MlpHead) or head.batch is not b:
+            raise ValueError("head must be an MlpHead of this batch (mlp_head)")
+        out = self._check_fused("mlp_q_actions", head, obs, masks, q_out, want_explored, out)
+        head._check_parameters()
+        if obs.numel() == 0:
+            return out
+        b._enqueue(b._lib.ccx_mlp_q_actions, head.H, head.activation_id, head.O, obs, head.w1t, head.b1, head.w2, head.b2, masks,
+                   None if greedy else self.epsilon_dev, out.actions, out.explored, q_out)
+        return out
+
+    def sides_q_actions(self, sides, obs: torch.Tensor, masks: torch.Tensor | None = None, greedy: bool = False,
+                        want_explored: bool = False, q_out: torch.Tensor | None = None, out: QActions | None = None) -> QActions:
+        """:meth:`mlp_q_actions` for :class:`~collectivecrossing_amd.sides.SideHeads` of this batch
+        (``ccx_sides_q_actions``): every group's slots get what :meth:`mlp_q_actions` gives with that group's head, in ONE
+        launch.  A slot that no head owns gets action 255 and ``explored`` 0 (what ``step_mixed`` expects for the slots it
+        scripts); its ``q_out`` elements are not written and it runs no layer.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
+        b = self.batch
+        if not isinstance(sides, SideHeads) or sides.batch is not b:
+            raise ValueError("sides must be SideHeads of this batch")
+        out = self._check_fused("sides_q_actions", sides, obs, masks, q_out, want_explored, out)
+        table = sides._table()
+        if obs.numel() == 0:
+            return out
+        b._enqueue(b._lib.ccx_sides_q_actions, sides.H, sides.dims[3], sides.O, obs, len(table), table, masks,
+                   None if greedy else self.epsilon_dev, out.actions, out.explored, q_out, also=sides._param_tensors())
+        return out
+
+    # ------------------------------------------------------------------ the dueling combine (CCX_DUELING)
+    def dueling_into(self, va, q) -> tuple:
+        """``q[i] = dueling(va[i])`` for 1..4 pairs of equal leading shape in ONE launch (``ccx_dueling_forward``): ``va``
+        a tuple of f32 [..., 6], ``q`` a tuple of f32 [..., 5] of the same length (a single pair may be given as two
+        tensors), all contiguous and 16-byte aligned -- the static buffers of a captured update, which combines ``q``,
+        ``q_next_target`` and ``q_next_online`` in one node.  No gradient flows through this call (:meth:`dueling` is the
+        differentiable form).  Returns ``q`` as a tuple.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
+        b = self.batch
+        vas = (va,) if isinstance(va, torch.Tensor) else tuple(va) if isinstance(va, (tuple, list)) else ()
+        qs = (q,) if isinstance(q, torch.Tensor) else tuple(q) if isinstance(q, (tuple, list)) else ()
+        if not 1 <= len(vas) <= DUELING_MAX_ARRAYS or len(qs) != len(vas):
+            raise ValueError(f"va and q must be tuples of the same length, 1 .. {DUELING_MAX_ARRAYS} tensors each")
+        lead = tuple(vas[0].shape[:-1]) if isinstance(vas[0], torch.Tensor) else ()
+        _require_all(b.device, *((f"va[{i}]", t, torch.float32, lead + (6,), {"align": 16}) for i, t in enumerate(vas)),
+                     *((f"q[{i}]", t, torch.float32, lead + (5,), {"align": 16}) for i, t in enumerate(qs)))
+        if vas[0].numel() == 0:
+            return qs
+        vas = tuple(t.detach() for t in vas)
+        table_va = (C.c_void_p * len(vas))(*(t.data_ptr() for t in vas))
+        table_q = (C.c_void_p * len(qs))(*(t.data_ptr() for t in qs))
+        b._enqueue(b._lib.ccx_dueling_forward, vas[0].numel() // 6, len(vas), table_va, table_q, also=vas + qs)
+        return qs
+
+    def dueling(self, va: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """The dueling combine (``ccx_dueling_forward``, include/ccx.h CCX_DUELING; one kernel, bit-defined): ``va`` f32
+        [..., 6] -- five advantages and the state value, the output of a head with ``O == 6`` -- to Q-values f32 [..., 5],
+        ``q_k = v + (a_k - mean(a))`` with the mean over all five actions whatever a mask says.  Both contiguous and 16-byte
+        aligned.  When ``va.requires_grad`` and grad mode is on, the call is a ``torch.autograd.Function`` whose backward is
+        :meth:`dueling_backward`, and ``out=`` is refused.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
+        b = self.batch
+        _require("va", va, torch.float32, (..., 6), b.device, align=16)
+        if va.requires_grad and torch.is_grad_enabled():
+            if out is not None:
+                raise ValueError("out= cannot be used when va requires a gradient (the autograd path allocates its output)")
+            if va.numel() == 0:
+                return va[..., :5] * 0.0
+            return _Dueling.apply(self, va)
+        if out is None:
+            out = b._new(tuple(va.shape[:-1]) + (5,), torch.float32)
+        return self.dueling_into((va,), (out,))[0]
+
+    def dueling_backward(self, grad_q: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+        """``grad_va`` f32 [..., 6] from ``grad_q`` f32 [..., 5] (``ccx_dueling_backward``; one kernel): a pure function of
+        ``grad_q``.  Every element is written; a row of five +0.0 gets six +0.0, so what :meth:`td_loss_backward` leaves at
+        rows that do not count stays exactly +0.0 down to ``backward_into``.  Both contiguous and 16-byte aligned; ``out``
+        reuses a tensor.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
+        b = self.batch
+        lead = tuple(grad_q.shape[:-1]) if isinstance(grad_q, torch.Tensor) else ()
+        if out is None and isinstance(grad_q, torch.Tensor):
+            out = b._new(lead + (6,), torch.float32)
+        _require_all(b.device, ("grad_q", grad_q, torch.float32, (..., 5), {"align": 16}),
+                     ("out", out, torch.float32, lead + (6,), {"align": 16}))
+        if grad_q.numel():
+            b._enqueue(b._lib.ccx_dueling_backward, grad_q.numel() // 5, grad_q.detach(), out)
         return out
 
     # ------------------------------------------------------------------ the TD loss over the rows that count
@@ -280,6 +403,22 @@ class QLearning:
                 b._enqueue(b._lib.ccx_td_loss_discounted_backward, actions.numel(), q, actions, reward, done, q_next_target,
                            q_next_online, masks_next, valid, weights, discount, hyper[1], stats, grad_loss, out)
         return out
+
+
+class _Dueling(torch.autograd.Function):
+    """:meth:`QLearning.dueling` for rows that require a gradient: the forward is ``ccx_dueling_forward``, the backward
+    ``ccx_dueling_backward``; nothing is saved (the backward is a pure function of the gradient)."""
+
+    @staticmethod
+    def forward(ctx, ql, va):
+        ctx.ql = ql
+        q = ql.batch._new(tuple(va.shape[:-1]) + (5,), torch.float32)
+        return ql.dueling_into((va,), (q,))[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_q):
+        return None, ctx.ql.dueling_backward(grad_q.contiguous())
 
 
 class _TdLoss(torch.autograd.Function):

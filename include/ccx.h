@@ -1121,8 +1121,8 @@ int ccx_sides_backward(ccx_handle* h, int64_t M, int32_t N, uint64_t slots, int3
  * a HIP graph.  Offsets are 64-bit.  A NULL handle or a NULL required pointer, rows < 1 (or so many that a grid would pass
  * 2^31 - 1 workgroups), a Q array or grad_q that is not 16-byte aligned, a workspace that is not 8-byte aligned, a gamma that
  * is not finite or lies outside [0, 1], a huber_delta that is not > 0: CCX_EINVAL with a ccx_last_error message, before any
- * launch.  n-step targets are CCX_NSTEP (a discount per row: ccx_td_loss_discounted).  Not here: a dueling combine, distributional heads, prioritised sampling (weights and td_error
- * are its two hooks; the replay buffer itself is CCX_REPLAY), the fusion of the head's forward with the action choice, bf16 / f16.
+ * launch.  n-step targets are CCX_NSTEP (a discount per row: ccx_td_loss_discounted).  The dueling combine and the head's forward fused with the action choice are CCX_DUELING.  Not here: distributional heads, prioritised sampling (weights and td_error
+ * are its two hooks; the replay buffer itself is CCX_REPLAY), bf16 / f16.
  */
 int ccx_q_actions(ccx_handle* h, const float* q /* [E][N][5] */, const uint8_t* masks_or_null /* [E][N] */,
                   const float* epsilon_or_null /* device f32 [1]; NULL = greedy */, uint8_t* actions /* [E][N] */,
@@ -1354,7 +1354,7 @@ int ccx_prio_sample(ccx_handle* h, int64_t ring_steps, const int32_t* leaf /* [R
  * load is next_c / masks_next of record m_env - 1.  A NULL handle or required pointer, S < 1 or S E >= 2^31, K outside 1..S,
  * n outside 1..min(S, 16), gamma not finite or outside [0, 1], B outside 1..2^31 / N, a misaligned array: CCX_EINVAL with a
  * ccx_last_error message, before any launch.  Not here: n above 16, a per-agent next state for dropped rows,
- * lambda-returns or Retrace, n-step inside the actor, sequences, a dueling combine, rings across GPUs, bf16 / f16.
+ * lambda-returns or Retrace, n-step inside the actor, sequences, rings across GPUs, bf16 / f16.
  */
 #define CCX_NSTEP_MAX 16
 int ccx_nstep_push(ccx_handle* h, int64_t ring_steps, const int64_t* ring_state /* [4] */, int64_t K,
@@ -1385,6 +1385,62 @@ int ccx_td_loss_discounted_backward(ccx_handle* h, int64_t rows, const float* q 
                                     const float* weights_or_null /* [M] */, const float* discount /* [M] */, float huber_delta,
                                     const float* stats /* [8] */, const float* grad_loss_or_null /* [1] */,
                                     float* grad_q /* [M][5] */);
+/*
+ * CCX_DUELING: the dueling combine of a Q-head, forward and backward, and the head's forward fused with ccx_q_actions' choice
+ * (the DQN actor step in ONE launch, as ccx_mlp_sample_actions is PPO's).  A dueling head is an ordinary CCX_MLP / CCX_SIDES
+ * head with O = 6: a row of its output is va f32 [6], va[k] for k = 0..4 the advantage of action k (index = action id, as
+ * everywhere), va[5] the state value.  The discipline is CCX_QLEARN's: every line below is ONE correctly rounded f32
+ * operation, nothing is fused, `/` is the correctly rounded division.
+ *     forward:   s = (((va0 + va1) + va2) + va3) + va4;   mean = s / 5.0f;
+ *                c_k = va_k - mean;   q_k = va5 + c_k                      (k = 0..4)
+ *     backward:  t = (((g0 + g1) + g2) + g3) + g4;   gm = t / 5.0f;
+ *                grad_va_k = g_k - gm   (k = 0..4);   grad_va_5 = t
+ * The mean runs over ALL five actions whatever the state's mask says: the combine is a property of the network, the mask a
+ * property of the state (it enters where an action is chosen).  The backward is a pure function of grad_q: it reads neither
+ * va nor q.  A row whose grad_q is five +0.0 gets six +0.0 -- what ccx_td_loss_backward writes at rows that do not count
+ * stays exactly +0.0 through the combine, whatever va holds there.  A NaN in a row's advantages reaches all five of its
+ * Q-values; nothing crosses rows.
+ *
+ * ccx_dueling_forward: num in 1..4 arrays of equal row count in ONE launch -- va and q are HOST arrays of num device
+ * pointers, f32 [rows][6] and f32 [rows][5]; the table travels by value in the kernel arguments, so the call captures (an
+ * update combines q, q_next_target and q_next_online in one node).  ccx_dueling_backward: grad_q f32 [rows][5] to grad_va f32
+ * [rows][6], ONE launch.  Pure functions of their arrays: the handle supplies device and stream only.  Every element of
+ * every output is written; all arrays are 16-byte aligned (rows travel in whole 16-byte pieces).
+ *
+ * ccx_mlp_q_actions / ccx_sides_q_actions: ccx_mlp_sample_actions / ccx_sides_sample_actions with the Q choice in the place
+ * of the softmax draw, ONE launch.  O = 5: a plain head; O = 6: a dueling head.  By definition
+ *     ccx_mlp_q_actions(head, obs, ..) == ccx_q_actions(O == 6 ? dueling(head(obs)) : head(obs), ..)
+ * -- the same key, the same two streams, the same rule for dead slots, the same bits in actions, explored and q;
+ * ccx_sides_q_actions likewise, per group.  q f32 [E][N][5] or NULL receives the COMBINED values of every slot, dead ones
+ * included.  masks, epsilon (device f32 [1], NULL = greedy), actions and explored are ccx_q_actions'.  In
+ * ccx_sides_q_actions a slot that no group owns gets action CCX_ACTION_ABSENT and explored 0; its q elements are not
+ * written and it runs no layer.  obs is 16-byte aligned, the other float arrays 4-byte aligned.
+ *
+ * Against IEEE f64 (measured on the CPU, tests/test_dueling_spec.py, maxima doubled), as max |err| / max(1, |f64 value|)
+ * against the textbook composition in torch f64 on the same f32 inputs (v + a - a.mean(-1), autograd of a random cotangent),
+ * advantages ~ N(0, 1) * 10^U(-3, 3), a third of the rows with a common offset of ten times their scale: q within 9.6e-04,
+ * grad_va within 1.3e-04.  Both figures are the cancellation in va_k - mean and in the sums where a row's entries are large
+ * against the result: the error of f32 inputs this large, not of the order of the operations.
+ *
+ * No host synchronisation, no allocation; everything captures into a HIP graph.  Offsets are 64-bit.  A NULL handle or
+ * required pointer, rows < 1, num outside 1..4, a misaligned pointer, a grid beyond 2^31 - 1 workgroups, O other than 5 or 6,
+ * a shape CCX_MLP refuses: CCX_EINVAL with a ccx_last_error message, before any launch.  Not here: dueling inside
+ * ccx_td_loss or inside the tile's epilogue for the learner, a masked mean or a max-combine, distributional or noisy heads,
+ * different (H, activation, O) per group, bf16 / f16.
+ */
+int ccx_dueling_forward(ccx_handle* h, int64_t rows, int32_t num /* 1..4 */,
+                        const float* const* va /* host [num] of device [rows][6] */,
+                        float* const* q /* host [num] of device [rows][5] */);
+int ccx_dueling_backward(ccx_handle* h, int64_t rows, const float* grad_q /* [rows][5] */, float* grad_va /* [rows][6] */);
+int ccx_mlp_q_actions(ccx_handle* h, int32_t H, int32_t activation, int32_t O /* 5: plain, 6: dueling */,
+                      const float* obs /* [E][N][ccx_obs_len(N)] */, const float* w1t, const float* b1, const float* w2,
+                      const float* b2, const uint8_t* masks_or_null /* [E][N] */,
+                      const float* epsilon_or_null /* device f32 [1]; NULL = greedy */, uint8_t* actions /* [E][N] */,
+                      uint8_t* explored_or_null /* [E][N] */, float* q_or_null /* [E][N][5], the COMBINED values */);
+int ccx_sides_q_actions(ccx_handle* h, int32_t H, int32_t activation, int32_t O, const float* obs /* [E][N][ccx_obs_len(N)] */,
+                        int32_t num_groups, const ccx_slot_group* groups, const uint8_t* masks_or_null /* [E][N] */,
+                        const float* epsilon_or_null, uint8_t* actions /* [E][N] */, uint8_t* explored_or_null /* [E][N] */,
+                        float* q_or_null /* [E][N][5] */);
 /*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
