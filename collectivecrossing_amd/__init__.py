@@ -14,7 +14,7 @@ __all__ = ["CollectiveCrossingConfig", "CollectiveCrossingEnv", "BatchedCollecti
            "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult", "SampleResult", "EvalResult",
            "PpoLossResult", "MlpHead", "MlpGradResult", "DeviceAdam", "SideHeads", "QLearning", "QActions",
            "TdLossResult", "ReplayRing", "ReplayBatch", "PrioritizedReplay", "PrioritizedBatch", "NStepReplay",
-           "NStepBatch"]
+           "NStepBatch", "RolloutMinibatches", "OnPolicyBatch"]
 
 
 _LAZY = {"CollectiveCrossingEnv": "env", "BatchedCollectiveCrossing": "batched", "VectorCollectiveCrossing": "vector",
@@ -22,7 +22,8 @@ _LAZY = {"CollectiveCrossingEnv": "env", "BatchedCollectiveCrossing": "batched",
          "EvalResult": "learner", "PpoLossResult": "learner", "MlpHead": "learner",
          "MlpGradResult": "learner", "DeviceAdam": "learner", "SideHeads": "sides", "QLearning": "qlearn",
          "QActions": "qlearn", "TdLossResult": "qlearn", "ReplayRing": "replay", "ReplayBatch": "replay",
-         "PrioritizedReplay": "prioritized", "PrioritizedBatch": "prioritized", "NStepReplay": "nstep", "NStepBatch": "nstep"}
+         "PrioritizedReplay": "prioritized", "PrioritizedBatch": "prioritized", "NStepReplay": "nstep", "NStepBatch": "nstep",
+         "RolloutMinibatches": "minibatch", "OnPolicyBatch": "minibatch"}
 
 
 def __getattr__(name):  # lazy: importing the configs must not pull in torch

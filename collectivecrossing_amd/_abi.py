@@ -201,6 +201,9 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_dueling_backward": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p]),
     "ccx_mlp_q_actions": (C.c_int, [_H] + [C.c_int32] * 3 + [C.c_void_p] * 10),
     "ccx_sides_q_actions": (C.c_int, [_H] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.POINTER(CcxSlotGroup)] + [C.c_void_p] * 5),
+    "ccx_minibatch_next": (C.c_int, [_H, C.c_int64, C.c_int32] + [C.c_void_p] * 9 + [C.c_int64] + [C.c_void_p] * 8),
+    "ccx_minibatch_fetch": (C.c_int, [_H, C.c_int64, C.c_int32] + [C.c_void_p] * 8 + [C.c_int64] + [C.c_void_p] * 9),
+    "ccx_minibatch_permutation": (C.c_int, [_H, C.c_int64, C.c_int64, C.c_void_p]),
     "ccx_set_check_inputs":(C.c_int, [_H, C.c_int32]),
     "ccx_check_inputs": (C.c_int, [_H]),
     "ccx_set_rng_seed": (C.c_int, [_H, C.c_uint64]),

@@ -48,6 +48,13 @@ enum : uint32_t { kPrioStream = 0x7F4A7C15u };
 static_assert(kPrioStream != kReplayStream && kPrioStream != kQExploreStream && kPrioStream != kQChoiceStream &&
               kPrioStream != kEpsStream && kPrioStream != kSampleStream && kPrioStream != 0u,
               "every stream of the counter-based word has its own constant");
+// CCX_MINIBATCH (include/ccx.h, ccx_minibatch.hip): the round words of the keyed permutation that shuffles a rollout's records,
+// keyed (right half, epoch low, high, round) on a stream of their own.
+enum : uint32_t { kMinibatchStream = 0x1B873593 };   // (typed by the enum; tests/test_prio_spec.py counts the `u`-suffixed ones)
+static_assert(kMinibatchStream != kPrioStream && kMinibatchStream != kReplayStream && kMinibatchStream != kQExploreStream &&
+              kMinibatchStream != kQChoiceStream && kMinibatchStream != kEpsStream && kMinibatchStream != kSampleStream &&
+              kMinibatchStream != 0u,
+              "every stream of the counter-based word has its own constant");
 static_assert(kQExploreStream != kQChoiceStream && kQExploreStream != kEpsStream && kQExploreStream != kSampleStream &&
               kQChoiceStream != kEpsStream && kQChoiceStream != kSampleStream && kQExploreStream != 0u && kQChoiceStream != 0u &&
               kReplayStream != kQExploreStream && kReplayStream != kQChoiceStream && kReplayStream != kEpsStream &&

@@ -1,0 +1,205 @@
+"""Shuffled on-policy minibatches on the device (include/ccx.h CCX_MINIBATCH): a keyed permutation of a rollout's ``K * E``
+env-step records that is never materialised, ONE kernel that draws the next ``B`` positions of it, gathers the records they
+name and writes the minibatch :meth:`~collectivecrossing_amd.learner.LearnerOps.ppo_loss` takes, and a cursor that lives on
+the device -- so a captured PPO update (gather + forward + loss + backward + Adam) walks through minibatches and epochs by
+being replayed, and the shuffle is pinned by the batch's ``set_rng_seed`` like every other draw of an iteration.
+
+:class:`RolloutMinibatches` is a class of its own, not a set of methods of the batch, for the reason ``replay.py`` gives: the
+stream-order table of the batch's classes (tests/_stream_order.py) is closed, and this class brings its own proof
+(tests/test_gpu_stream_order_minibatch.py)."""
+
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+import torch
+
+from .learner import _OPT, _require_all, _require_out
+from .replay import _check_batch_size
+
+EMPTY_ACTION, EMPTY_MASKS = 255, 0x10                                    # the EMPTY row's two bytes that are not zero
+_SOURCES = ("obs0", "obs", "actions", "logp", "advantages", "returns", "masks", "valid")
+
+
+@dataclass
+class OnPolicyBatch:
+    """A minibatch of B env-step records (:meth:`RolloutMinibatches.next` / :meth:`RolloutMinibatches.fetch`).  Every element
+    is written: the EMPTY row (action 255, ``valid`` 0, ``masks`` 0x10, ``logp`` = ``advantages`` = ``returns`` = +0.0, rows of
+    +0.0 compact records) where ``index`` names no record -- the padding of an epoch's last draw, which ``valid`` = 0 takes out
+    of ``ppo_loss`` without a change of shape."""
+
+    obs: torch.Tensor | None        # f32 [B, N, L]: the rows the step acted on
+    actions: torch.Tensor           # u8 [B, N]
+    logp: torch.Tensor              # f32 [B, N]
+    advantages: torch.Tensor        # f32 [B, N]
+    returns: torch.Tensor           # f32 [B, N]
+    masks: torch.Tensor             # u8 [B, N]: the legal set the action was drawn under (0x1F without a source)
+    valid: torch.Tensor             # u8 [B, N]: live in the step (0 / 4; 4 without a source)
+    index: torch.Tensor             # int64 [B]: the records gathered (-1: padding)
+
+
+class RolloutMinibatches:
+    """``RolloutMinibatches(batch, num_steps=K, batch_size=B)``: minibatches of B records out of the ``M = K * E`` records of a
+    K-step rollout of the batch's E envs (record ``j = s * E + e``, step-major), without replacement: every record appears
+    exactly once per epoch of ``minibatches_per_epoch = ceil(M / B)`` draws, the last of them padded with EMPTY rows when B
+    does not divide M.
+
+    ``state`` int64 [4] = {epoch, cursor, 0, 0} is allocated here and lives ON THE DEVICE: the kernel reads it there, so a
+    captured :meth:`next` advances with every replay.  The order is ``pi_epoch``, a six-round keyed Feistel network with
+    cycle walking on the minibatch stream of the batch's ``set_rng_seed`` (include/ccx.h CCX_MINIBATCH): nothing comes from
+    torch's generator, nothing is stored, and two runs from the same seed draw the same minibatches.
+
+    Every method that enqueues keeps the stream-order contract of :class:`~collectivecrossing_amd.learner.LearnerOps` through
+    the batch's ``_enqueue``; ``state`` and the sources travel as arguments, so they are ordered like the caller's tensors.
+    Anything else than the tensors described raises ``ValueError`` before the library is called.  Not here: old values for a
+    clipped value loss, sequences for recurrent policies, a shuffle across GPUs (each shard shuffles its own records),
+    stratification by env, bf16 / f16."""
+
+    def __init__(self, batch, num_steps: int, batch_size: int):
+        from .batched import BatchedCollectiveCrossing
+
+        if not isinstance(batch, BatchedCollectiveCrossing):
+            raise ValueError("batch must be a BatchedCollectiveCrossing")
+        self.batch = batch
+        try:
+            K = int(num_steps)
+        except (TypeError, ValueError):
+            raise ValueError("num_steps must be an integer") from None
+        if K != num_steps or K < 1 or K * batch.num_envs >= 1 << 31:
+            raise ValueError(f"num_steps must be an integer >= 1 with num_steps * num_envs < 2^31, got {num_steps!r}")
+        self.num_steps = K
+        self.records = K * batch.num_envs
+        self.batch_size = _check_batch_size(batch_size, batch.num_agents)
+        self.state = torch.zeros((4,), dtype=torch.int64, device=batch.device)
+        self._source = None
+        self._compact = 0
+
+    @property
+    def minibatches_per_epoch(self) -> int:
+        """``ceil(M / B)``: the draws after which every record has appeared once."""
+        return -(-self.records // self.batch_size)
+
+    # ------------------------------------------------------------------ the rollout's arrays
+    def set_source(self, obs, actions, logp, advantages, returns, masks=None, valid=None, obs0=None) -> None:
+        """The arrays the minibatches are gathered from, checked once (static buffers: a captured :meth:`next` reads whatever
+        they hold at each replay).  ``obs`` f32 [K, E, N, L] (rows) or [K, E, N, 4] (compact records, expanded by the gather;
+        the last dimension tells them apart) or ``None`` (no ``obs`` output); ``actions`` u8, ``logp`` / ``advantages`` /
+        ``returns`` f32, ``masks`` / ``valid`` u8 or ``None`` (the minibatch then holds 0x1F / 4), each [K, E, N].
+
+        ``obs0`` f32 [E, N, L] / [E, N, 4], in the form of ``obs``: the observation the FIRST step acted on.  With it ``obs``
+        is the rollout's own array (``obs[s]`` = the rows behind step s, made with ``reset_obs="next"``) and record (s, e)
+        gathers the row it ACTED ON, ``obs0[e]`` for s = 0 and ``obs[s - 1][e]`` otherwise -- no second copy of every row in
+        the collect loop.  Without it ``obs[s][e]`` is taken as it is.  Makes no library call."""
+        b = self.batch
+        K, E, N, L = self.num_steps, b.num_envs, b.num_agents, b.obs_len
+        f32, u8, KEN = torch.float32, torch.uint8, (self.num_steps, b.num_envs, b.num_agents)
+        if obs is None and obs0 is not None:
+            raise ValueError("obs0 needs obs")
+        compact = isinstance(obs, torch.Tensor) and obs.dim() == 4 and obs.shape[-1] == 4
+        W = 4 if compact else L
+        align = {"align": 16 if compact or N % 2 == 0 else 8, "optional": True,
+                 "hint": f" (rows [..., {L}] or compact records [..., 4])"}
+        _require_all(b.device, ("obs", obs, f32, (K, E, N, W), align), ("obs0", obs0, f32, (E, N, W), align),
+                     ("actions", actions, u8, KEN), ("logp", logp, f32, KEN), ("advantages", advantages, f32, KEN),
+                     ("returns", returns, f32, KEN), ("masks", masks, u8, KEN, _OPT), ("valid", valid, u8, KEN, _OPT))
+        self._source = (obs0, obs, actions, logp, advantages, returns, masks, valid)
+        self._compact = int(compact)
+
+    def _args(self) -> tuple:
+        if self._source is None:
+            raise ValueError("set_source(...) first: there is nothing to gather from")
+        return (self.num_steps, self._compact, *self._source)
+
+    # ------------------------------------------------------------------ records to a minibatch
+    def alloc(self, B: int | None = None, want_obs: bool | None = None) -> OnPolicyBatch:
+        """Output tensors of :meth:`next` (B = ``batch_size``) / :meth:`fetch` for B records (static buffers for a captured
+        graph).  ``want_obs``: default, whether the source has ``obs`` (no source yet: yes)."""
+        b = self.batch
+        B = self.batch_size if B is None else _check_batch_size(B, b.num_agents)
+        if want_obs is None:
+            want_obs = self._source is None or self._source[1] is not None
+        N, L, f32, u8 = b.num_agents, b.obs_len, torch.float32, torch.uint8
+        return OnPolicyBatch(b._new((B, N, L), f32) if want_obs else None, b._new((B, N), u8), b._new((B, N), f32),
+                             b._new((B, N), f32), b._new((B, N), f32), b._new((B, N), u8), b._new((B, N), u8),
+                             b._new((B,), torch.int64))
+
+    def _out(self, B: int, out) -> OnPolicyBatch:
+        b = self.batch
+        _require_out(out, OnPolicyBatch, "alloc")
+        if out is None:
+            return self.alloc(B)
+        N, L, f32, u8 = b.num_agents, b.obs_len, torch.float32, torch.uint8
+        _require_all(b.device, ("out.obs", out.obs, f32, (B, N, L), {"optional": True, "align": 16 if N % 2 == 0 else 8}),
+                     ("out.actions", out.actions, u8, (B, N)), ("out.logp", out.logp, f32, (B, N)),
+                     ("out.advantages", out.advantages, f32, (B, N)), ("out.returns", out.returns, f32, (B, N)),
+                     ("out.masks", out.masks, u8, (B, N)), ("out.valid", out.valid, u8, (B, N)),
+                     ("out.index", out.index, torch.int64, (B,)))
+        if out.obs is not None and self._source is not None and self._source[1] is None:
+            raise ValueError("out.obs needs a source with obs")
+        return out
+
+    @staticmethod
+    def _out_args(out: OnPolicyBatch) -> tuple:
+        return (out.obs, out.actions, out.logp, out.advantages, out.returns, out.masks, out.valid, out.index)
+
+    def next(self, out: OnPolicyBatch | None = None) -> OnPolicyBatch:
+        """The next ``batch_size`` records of the running epoch (``ccx_minibatch_next``, include/ccx.h CCX_MINIBATCH): ONE
+        kernel that works out ``index[b] = pi_epoch(cursor + b)`` (-1 behind the epoch's end, and for a negative cursor),
+        gathers through the indices and writes every element of the minibatch, and one plain lane behind it that advances
+        the state -- ``cursor += B``, or the next epoch from 0 once ``cursor + B >= M`` --, on the handle's stream.  Epoch and
+        cursor are read on the device: a captured call advances with every replay, and ``EPOCHS * minibatches_per_epoch``
+        replays are EPOCHS passes over the rollout.  ``out`` reuses an :class:`OnPolicyBatch` of ``batch_size`` rows
+        (:meth:`alloc`).  Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
+        b = self.batch
+        args = self._args()
+        out = self._out(self.batch_size, out)
+        b._enqueue(b._lib.ccx_minibatch_next, *args, self.state, self.batch_size, *self._out_args(out))
+        return out
+
+    def fetch(self, index: torch.Tensor, out: OnPolicyBatch | None = None) -> OnPolicyBatch:
+        """The kernel of :meth:`next` on the caller's record indices, int64 [B] (``ccx_minibatch_fetch``): nothing is drawn
+        and ``state`` stays.  An index outside ``[0, records)`` gives the EMPTY row and reads nothing; ``out.index`` receives a
+        copy of ``index`` (it may be the same tensor).
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
+        b = self.batch
+        args = self._args()
+        B = int(index.shape[0]) if isinstance(index, torch.Tensor) and index.dim() == 1 else 0
+        _require_all(b.device, ("index", index, torch.int64, (max(B, 1),)))
+        B = _check_batch_size(B, b.num_agents)
+        out = self._out(B, out)
+        b._enqueue(b._lib.ccx_minibatch_fetch, *args, B, index, *self._out_args(out))
+        return out
+
+    def permutation(self, epoch: int, out: torch.Tensor | None = None) -> torch.Tensor:
+        """``pi_epoch(0 .. records - 1)`` as int64 [records] (``ccx_minibatch_permutation``): the order :meth:`next` walks
+        through in that epoch, for tests and logs -- the draw itself never stores it.
+        Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
+        b = self.batch
+        try:
+            ok = int(epoch) == epoch and 0 <= int(epoch) < 1 << 63
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"epoch must be an integer in 0 .. 2^63 - 1, got {epoch!r}")
+        if out is None:
+            out = b._new((self.records,), torch.int64)
+        _require_all(b.device, ("out", out, torch.int64, (self.records,)))
+        b._enqueue(b._lib.ccx_minibatch_permutation, self.records, int(epoch), out)
+        return out
+
+    def rewind(self, epoch: int = 0) -> None:
+        """``state`` = {epoch, 0, 0, 0}: the next draw starts that epoch.  Fills on the handle's stream, ordered like a launch
+        (only enqueues)."""
+        b = self.batch
+        try:
+            ok = int(epoch) == epoch and 0 <= int(epoch) < 1 << 63
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f"epoch must be an integer in 0 .. 2^63 - 1, got {epoch!r}")
+        cur = b._order_after_current_stream(self.state)
+        with torch.cuda.stream(b._stream):
+            self.state.zero_()
+            if int(epoch):
+                self.state[:1].fill_(int(epoch))
+        b._current_stream_waits(cur=cur)

@@ -78,7 +78,8 @@ class QLearning:
     calling it.  The dueling combine (:meth:`dueling`, :meth:`dueling_into`, :meth:`dueling_backward`) and the head's forward
     fused with the action choice (:meth:`mlp_q_actions`, :meth:`sides_q_actions`) are include/ccx.h CCX_DUELING.  Not here:
     distributional heads, prioritised sampling (``weights`` and ``td_error`` are its hooks; the replay buffer itself is
-    :class:`~collectivecrossing_amd.replay.ReplayRing`), bf16 / f16."""
+    :class:`~collectivecrossing_amd.replay.ReplayRing`), on-policy minibatches (shuffled without replacement by
+    :class:`~collectivecrossing_amd.minibatch.RolloutMinibatches`), bf16 / f16."""
 
     def __init__(self, batch, epsilon: float = 1.0):
         from .batched import BatchedCollectiveCrossing

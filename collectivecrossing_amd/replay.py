@@ -73,7 +73,8 @@ class ReplayRing:
     the batch's ``_enqueue``; the ring's own arrays travel as arguments, so they are ordered like the caller's.  Anything else
     than the tensors described raises ``ValueError`` before the library is called.  Not here: prioritised or recency-weighted
     sampling (``index``, :meth:`fetch` and ``td_loss``'s ``weights`` / ``td_error`` are the hooks), sampling without
-    replacement, n-step returns in the ring itself (:class:`~collectivecrossing_amd.nstep.NStepReplay` walks it), frames shared
+    replacement from the ring (a rollout's own records are shuffled without replacement by
+    :class:`~collectivecrossing_amd.minibatch.RolloutMinibatches`), n-step returns in the ring itself (:class:`~collectivecrossing_amd.nstep.NStepReplay` walks it), frames shared
     between ``obs_c`` and ``next_c``, records of single agents or sequences, a
     ring over several GPUs (each shard has its own), rows-form storage, bf16 / f16."""
 

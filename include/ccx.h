@@ -1196,7 +1196,7 @@ int ccx_td_loss_backward(ccx_handle* h, int64_t rows, const float* q /* [M][5] *
  * < 1 or S E >= 2^31, K outside 1..S, B outside 1..2^31 / N, a compact or row array that is not 16-byte aligned, an f64 / i64
  * array that is not 8-byte aligned: CCX_EINVAL with a ccx_last_error message, before any launch.  Not here: prioritised or
  * recency-weighted sampling (index, ccx_replay_fetch and ccx_td_loss's weights / td_error are the hooks), sampling without
- * replacement, frames shared between obs_c and next_c, records of single agents or of sequences, a ring over
+ * replacement from the ring (CCX_MINIBATCH shuffles a rollout's own records without replacement), frames shared between obs_c and next_c, records of single agents or of sequences, a ring over
  * several GPUs (each shard has its own), rows-form storage, bf16 / f16.
  */
 int ccx_replay_push(ccx_handle* h, int64_t ring_steps, float* ring_obs_c /* [R][N][4] */, float* ring_next_c /* [R][N][4] */,
@@ -1441,6 +1441,75 @@ int ccx_sides_q_actions(ccx_handle* h, int32_t H, int32_t activation, int32_t O,
                         int32_t num_groups, const ccx_slot_group* groups, const uint8_t* masks_or_null /* [E][N] */,
                         const float* epsilon_or_null, uint8_t* actions /* [E][N] */, uint8_t* explored_or_null /* [E][N] */,
                         float* q_or_null /* [E][N][5] */);
+/*
+ * CCX_MINIBATCH: shuffled on-policy minibatches out of a rollout's own arrays -- sampling WITHOUT replacement.  ONE kernel
+ * draws B positions of a keyed permutation of the rollout's records, gathers the records they name and writes the minibatch
+ * ccx_ppo_loss takes (ccx_minibatch_next; ccx_minibatch_fetch is the same kernel on the caller's record indices).  The
+ * permutation is never materialised: any lane computes pi_c(p) from p alone.  Everything is integer work and copies: every
+ * output is bit-defined.
+ *
+ * Records.  A rollout of K steps of the handle's E envs gives M = K E records, 1 <= M < 2^31; record j = s E + e, step-major
+ * like the ring of CCX_REPLAY.
+ *
+ * The permutation pi_c of [0, M) of epoch c (u64): a keyed, unbalanced Feistel network with cycle walking.  w = the smallest
+ * integer >= 2 with 2^w >= M, a = floor(w / 2), b = w - a; x = L 2^b + R with R of b bits.  Six rounds r = 0 .. 5, with wl the
+ * current width of L (a at the start):
+ *     (L, R) <- (R, L ^ (word(seed_lo, seed_hi ^ 0x1B873593; R, (u32)c, (u32)(c >> 32), r) & (2^wl - 1)));   wl <- w - wl
+ * (the k of ccx_set_rng_seed's formula, its four key slots in that order); after six rounds the widths are (a, b) again and
+ * x' = L 2^b + R.  Cycle walk: the six rounds are repeated while x' >= M; then pi_c(p) = x'.  Every round is invertible, so
+ * the walk ends for every key and every M; 2^w < 2 M, so a step of it succeeds with probability above 1 / 2.  The key holds
+ * neither env nor shard.  The stream constant differs from 0, 0x5BD1E995, 0x2545F491, 0x68E31DA4, 0xB5297A4D, 0x3C6EF372 and
+ * 0x7F4A7C15.  ccx_minibatch_permutation writes pi_epoch(0 .. M - 1) to out i64 [M].
+ *
+ * ccx_minibatch_next.  state i64 [4] = {epoch, cursor, 0, 0} lives on the device and is READ THERE when the kernel runs.  For
+ * b = 0 .. B - 1 (1 <= B <= 2^31 / N), with p = cursor + b:
+ *     index[b] = (cursor >= 0 && p < M) ? pi_epoch(p) : -1
+ * and then
+ *     if (cursor < 0 || cursor + B >= M) { epoch += 1; cursor = 0; } else cursor += B;
+ * An epoch is ceil(M / B) draws; the last one is padded with EMPTY rows when B does not divide M; every record of [0, M)
+ * appears exactly once per epoch.  Whatever state holds, no address outside the source arrays is formed: a stale or junk
+ * state yields EMPTY rows or records in range.  ccx_minibatch_fetch takes index_in i64 [B] from the caller instead (and writes
+ * it to the index output, which may be the same array) and leaves state alone.
+ *
+ * Gather (both).  Row b of every output is a copy of the fields of record index[b], bit for bit, and every element of every
+ * output given is written.  With (s, e) = (j / E, j mod E):
+ *   out_obs f32 [B][N][ccx_obs_len(N)] (may be NULL) from obs_steps and obs0, in one of two forms chosen by `compact`:
+ *     compact == 0: obs_steps f32 [K][E][N][L], obs0 f32 [E][N][L] or NULL -- DefaultObservation rows, copied;
+ *     compact != 0: obs_steps f32 [K][E][N][4], obs0 f32 [E][N][4] or NULL -- CCX_OBS_COMPACT records, expanded with the
+ *                   handle's row constants: the very gather of ccx_observe, hence the bits of ccx_expand_observations.
+ *   With obs0 given the row is the one the step ACTED ON, s == 0 ? obs0[e] : obs_steps[s - 1][e] (CCX_REPLAY's obs_c rule; the
+ *   caller's contract is again a rollout made with CCX_RESET_OBS_NEXT).  With obs0 NULL it is obs_steps[s][e]: the caller's
+ *   array already holds the rows acted on.
+ *   actions u8, logp f32, advantages f32, returns f32, each [K][E][N] -> [B][N]; masks u8 and valid u8 likewise, where either
+ *   SOURCE may be NULL: the output is then 0x1F, respectively CCX_AF_LIVE (4), for every record in range.  index i64 [B].
+ *   The EMPTY row, where index[b] is outside [0, M): action CCX_ACTION_ABSENT, logp = advantages = returns = +0.0, masks 0x10,
+ *   valid 0, and the observation rows of compact records of +0.0 (as CCX_REPLAY defines them).  valid = 0 takes the padding
+ *   out of ccx_ppo_loss without a change of shape.
+ *
+ * Launches: ccx_minibatch_next enqueues TWO kernels on the handle's stream -- the gather, and one plain lane behind it that
+ * advances the state, so the update cannot race with the lanes that read the old value (no atomic, no host synchronisation);
+ * ccx_minibatch_fetch and ccx_minibatch_permutation ONE.  No allocation; everything captures into a HIP graph, and a captured
+ * ccx_minibatch_next advances with every replay.  Offsets are 64-bit.  A NULL handle or required pointer, K E outside
+ * 1 .. 2^31 - 1, B outside 1 .. 2^31 / N, out_obs given without obs_steps, an observation-row array that is not 16-byte aligned
+ * (8-byte for an odd number of agents, as for ccx_step), a compact array that is not 16-byte aligned, an i64 array that is not
+ * 8-byte aligned, an f32 array that is not 4-byte aligned: CCX_EINVAL with a ccx_last_error message, before any launch.
+ * Not here: old values for a clipped value loss, sequences for recurrent policies, a shuffle across GPUs (each shard shuffles
+ * its own records), stratification by env, bf16 / f16.
+ */
+int ccx_minibatch_next(ccx_handle* h, int64_t K, int32_t compact, const float* obs0_or_null, const float* obs_steps_or_null,
+                       const uint8_t* actions /* [K][E][N] */, const float* logp /* [K][E][N] */,
+                       const float* advantages /* [K][E][N] */, const float* returns /* [K][E][N] */,
+                       const uint8_t* masks_or_null /* [K][E][N] */, const uint8_t* valid_or_null /* [K][E][N] */,
+                       int64_t* state /* [4] */, int64_t batch, float* out_obs_or_null /* [B][N][L] */,
+                       uint8_t* out_actions /* [B][N] */, float* out_logp /* [B][N] */, float* out_advantages /* [B][N] */,
+                       float* out_returns /* [B][N] */, uint8_t* out_masks /* [B][N] */, uint8_t* out_valid /* [B][N] */,
+                       int64_t* out_index /* [B] */);
+int ccx_minibatch_fetch(ccx_handle* h, int64_t K, int32_t compact, const float* obs0_or_null, const float* obs_steps_or_null,
+                        const uint8_t* actions, const float* logp, const float* advantages, const float* returns,
+                        const uint8_t* masks_or_null, const uint8_t* valid_or_null, int64_t batch,
+                        const int64_t* index_in /* [B] */, float* out_obs_or_null, uint8_t* out_actions, float* out_logp,
+                        float* out_advantages, float* out_returns, uint8_t* out_masks, uint8_t* out_valid, int64_t* out_index);
+int ccx_minibatch_permutation(ccx_handle* h, int64_t M, int64_t epoch, int64_t* out /* [M] */);
 /*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
