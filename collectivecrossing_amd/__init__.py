@@ -14,7 +14,7 @@ __all__ = ["CollectiveCrossingConfig", "CollectiveCrossingEnv", "BatchedCollecti
            "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult", "SampleResult", "EvalResult",
            "PpoLossResult", "MlpHead", "MlpGradResult", "DeviceAdam", "SideHeads", "QLearning", "QActions",
            "TdLossResult", "ReplayRing", "ReplayBatch", "PrioritizedReplay", "PrioritizedBatch", "NStepReplay",
-           "NStepBatch", "RolloutMinibatches", "OnPolicyBatch"]
+           "NStepBatch", "RolloutMinibatches", "OnPolicyBatch", "CategoricalQ", "CategoricalLossResult"]
 
 
 _LAZY = {"CollectiveCrossingEnv": "env", "BatchedCollectiveCrossing": "batched", "VectorCollectiveCrossing": "vector",
@@ -23,7 +23,8 @@ _LAZY = {"CollectiveCrossingEnv": "env", "BatchedCollectiveCrossing": "batched",
          "MlpGradResult": "learner", "DeviceAdam": "learner", "SideHeads": "sides", "QLearning": "qlearn",
          "QActions": "qlearn", "TdLossResult": "qlearn", "ReplayRing": "replay", "ReplayBatch": "replay",
          "PrioritizedReplay": "prioritized", "PrioritizedBatch": "prioritized", "NStepReplay": "nstep", "NStepBatch": "nstep",
-         "RolloutMinibatches": "minibatch", "OnPolicyBatch": "minibatch"}
+         "RolloutMinibatches": "minibatch", "OnPolicyBatch": "minibatch", "CategoricalQ": "categorical",
+         "CategoricalLossResult": "categorical"}
 
 
 def __getattr__(name):  # lazy: importing the configs must not pull in torch

@@ -197,6 +197,10 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_nstep_fetch": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 9 + [C.c_int32, C.c_float, C.c_int64] + [C.c_void_p] * 11),
     "ccx_td_loss_discounted": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 10 + [C.c_float] + [C.c_void_p] * 3),
     "ccx_td_loss_discounted_backward": (C.c_int, [_H, C.c_int64] + [C.c_void_p] * 10 + [C.c_float] + [C.c_void_p] * 3),
+    "ccx_c51_workspace_bytes": (C.c_int64, [C.c_int64]),
+    "ccx_c51_q_values": (C.c_int, [_H, C.c_int64, C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "ccx_c51_loss": (C.c_int, [_H, C.c_int64, C.c_int32, C.c_float, C.c_float] + [C.c_void_p] * 10 + [C.c_float] + [C.c_void_p] * 4),
+    "ccx_c51_loss_backward": (C.c_int, [_H, C.c_int64, C.c_int32] + [C.c_void_p] * 8),
     "ccx_dueling_forward": (C.c_int, [_H, C.c_int64, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "ccx_dueling_backward": (C.c_int, [_H, C.c_int64, C.c_void_p, C.c_void_p]),
     "ccx_mlp_q_actions": (C.c_int, [_H] + [C.c_int32] * 3 + [C.c_void_p] * 10),

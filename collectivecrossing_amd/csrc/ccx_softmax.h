@@ -36,7 +36,8 @@ CCX_HD float exp_spec(float x) {
     return p * __builtin_bit_cast(float, ((int)n + 127) << 23);           // exact: |n| <= 116, the product is a normal number
 }
 
-// s in [1, 5]
+// s in [1, 64] (CCX_SAMPLE / CCX_EVALUATE use [1, 5], CCX_C51 the whole of it: within 2.6e-7 absolute of f64 log over
+// [1, 64], measured on the CPU over 2e6 points)
 CCX_HD float log_spec(float s) {
     const int bits = __builtin_bit_cast(int, s);
     float m = __builtin_bit_cast(float, (bits & 0x007FFFFF) | 0x3F000000);  // s = m * 2^e, m in [0.5, 1)

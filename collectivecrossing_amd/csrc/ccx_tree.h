@@ -119,6 +119,26 @@ __device__ __forceinline__ void block_sums(double (&s)[NQ], double (&groups)[NQ]
     }
 }
 
+// The same epilogue for a workgroup of MORE than four waves (CCX_C51: the rows of a block are worked on by sixteen waves and
+// handed over in LDS): thread t < 256 holds the terms of row t, the waves behind the fourth hold nothing and only arrive at
+// the barrier.  The tree is the one above: the same butterfly per group, the same block_partial.
+template <int NQ>
+__device__ __forceinline__ void block_sums_wide(double (&s)[NQ], double (&groups)[NQ][kBlockGroups], double* partials, long long B) {
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    if (w < (uint32_t)kBlockGroups) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            s[q] = halve_wave(s[q]);
+            if (lane == 0u) groups[q][w] = s[q];
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)NQ) {
+        const uint32_t q = threadIdx.x;
+        partials[(long long)q * B + blockIdx.x] = block_partial(groups[q][0], groups[q][1], groups[q][2], groups[q][3]);
+    }
+}
+
 // the one-quantity form: partials = [B]
 __device__ __forceinline__ void block_sums(double s, double (&groups)[kBlockGroups], double* partials) {
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;

@@ -76,8 +76,9 @@ class QLearning:
     keeps the stream-order contract of :class:`~collectivecrossing_amd.learner.LearnerOps` through the batch's ``_enqueue``.
     Anything else than the tensors described raises ``ValueError`` before the library is called; zero rows return without
     calling it.  The dueling combine (:meth:`dueling`, :meth:`dueling_into`, :meth:`dueling_backward`) and the head's forward
-    fused with the action choice (:meth:`mlp_q_actions`, :meth:`sides_q_actions`) are include/ccx.h CCX_DUELING.  Not here:
-    distributional heads, prioritised sampling (``weights`` and ``td_error`` are its hooks; the replay buffer itself is
+    fused with the action choice (:meth:`mlp_q_actions`, :meth:`sides_q_actions`) are include/ccx.h CCX_DUELING.
+    Distributional (categorical, C51) heads are :class:`~collectivecrossing_amd.categorical.CategoricalQ` (CCX_C51).  Not here:
+    prioritised sampling (``weights`` and ``td_error`` are its hooks; the replay buffer itself is
     :class:`~collectivecrossing_amd.replay.ReplayRing`), on-policy minibatches (shuffled without replacement by
     :class:`~collectivecrossing_amd.minibatch.RolloutMinibatches`), bf16 / f16."""
 

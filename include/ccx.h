@@ -1121,7 +1121,7 @@ int ccx_sides_backward(ccx_handle* h, int64_t M, int32_t N, uint64_t slots, int3
  * a HIP graph.  Offsets are 64-bit.  A NULL handle or a NULL required pointer, rows < 1 (or so many that a grid would pass
  * 2^31 - 1 workgroups), a Q array or grad_q that is not 16-byte aligned, a workspace that is not 8-byte aligned, a gamma that
  * is not finite or lies outside [0, 1], a huber_delta that is not > 0: CCX_EINVAL with a ccx_last_error message, before any
- * launch.  n-step targets are CCX_NSTEP (a discount per row: ccx_td_loss_discounted).  The dueling combine and the head's forward fused with the action choice are CCX_DUELING.  Not here: distributional heads, prioritised sampling (weights and td_error
+ * launch.  n-step targets are CCX_NSTEP (a discount per row: ccx_td_loss_discounted).  The dueling combine and the head's forward fused with the action choice are CCX_DUELING.  Distributional (categorical, C51) heads are CCX_C51.  Not here: prioritised sampling (weights and td_error
  * are its two hooks; the replay buffer itself is CCX_REPLAY), bf16 / f16.
  */
 int ccx_q_actions(ccx_handle* h, const float* q /* [E][N][5] */, const uint8_t* masks_or_null /* [E][N] */,
@@ -1425,7 +1425,8 @@ int ccx_td_loss_discounted_backward(ccx_handle* h, int64_t rows, const float* q 
  * No host synchronisation, no allocation; everything captures into a HIP graph.  Offsets are 64-bit.  A NULL handle or
  * required pointer, rows < 1, num outside 1..4, a misaligned pointer, a grid beyond 2^31 - 1 workgroups, O other than 5 or 6,
  * a shape CCX_MLP refuses: CCX_EINVAL with a ccx_last_error message, before any launch.  Not here: dueling inside
- * ccx_td_loss or inside the tile's epilogue for the learner, a masked mean or a max-combine, distributional or noisy heads,
+ * ccx_td_loss or inside the tile's epilogue for the learner, a masked mean or a max-combine, noisy heads (distributional
+ * heads are CCX_C51; dueling combined with them is not here),
  * different (H, activation, O) per group, bf16 / f16.
  */
 int ccx_dueling_forward(ccx_handle* h, int64_t rows, int32_t num /* 1..4 */,
@@ -1510,6 +1511,92 @@ int ccx_minibatch_fetch(ccx_handle* h, int64_t K, int32_t compact, const float* 
                         const int64_t* index_in /* [B] */, float* out_obs_or_null, uint8_t* out_actions, float* out_logp,
                         float* out_advantages, float* out_returns, uint8_t* out_masks, uint8_t* out_valid, int64_t* out_index);
 int ccx_minibatch_permutation(ccx_handle* h, int64_t M, int64_t epoch, int64_t* out /* [M] */);
+/*
+ * CCX_C51: categorical (C51) Q-heads -- the expected values of a network's atom logits (what ccx_q_actions chooses from), the
+ * projection of the bootstrapped target distribution onto the support, the cross-entropy loss with its means over the rows
+ * that count, and its gradient with respect to the logits.  The textbook projection is floor / ceil and two scatter-adds,
+ * which on a GPU are floating-point atomics in no fixed order; here it is a gather with a written order of additions, so
+ * every output is bit-defined, the reduction included.  The discipline is CCX_QLEARN's, unchanged: every f32 operation named
+ * below is ONE correctly rounded f32 operation (+ - * /), nothing is fused, nothing is reassociated, subnormals are kept;
+ * what a rule does not read is SELECTED away, never multiplied by zero.
+ *
+ * A = atoms, 2 <= A <= 64;  vmin < vmax finite f32;  dz = (vmax - vmin) / (float)(A - 1);  z_j = vmin + (float)j * dz;
+ * top = (float)(A - 1).  Logits are f32 [M][5][A] (action id, then atom), contiguous, and need only the alignment of an f32,
+ * 4 bytes: A = 51 gives rows of 204 bytes, so nothing wider is assumed anywhere.  butterfly(v) is the halving of
+ * CCX_PPO_LOSS's groups over 64 places in f32: for o = 32, 16, .. 1 every place j takes v_j + v_(j ^ o); places j >= A hold
+ * +0.0f.  exp_spec and log_spec are CCX_SAMPLE's (log_spec over [1, 64]: within 2.6e-7 absolute of f64 log, measured on the
+ * CPU over 2e6 points).
+ *   1. The distribution of one (row, action) with logits l_0 .. l_(A-1).  mx = their maximum by the same butterfly with
+ *      max2(a, b) = fmax(a, b) with a zero of either sign made +0.0f (a NaN beside a number gives the number; exact and the
+ *      same bits in any order).  d_j = l_j - mx;  u_j = d_j - d_j (+0.0f for a finite d_j, NaN otherwise);
+ *      e_j = d_j >= -80 ? exp_spec(d_j) : u_j;  S = butterfly(e).  So a logit far below the maximum weighs exactly +0.0f, and
+ *      a NaN, a +inf or a -inf logit makes S a NaN: every logit that is read must be finite, and one that is not is loud.
+ *      log S is log_spec(S), or S itself where S is a NaN.
+ *   2. The expected value Q = butterfly(e_j * z_j) / S: the products are summed, ONE division.  ccx_c51_q_values and the
+ *      bootstrap choice of step 3 run the same function.
+ *   3. Bootstrap (only where step 4 does not cut the target): Q_sel,k = the expected values of next_online[i][k] if given
+ *      (double-Q), else of next_target[i][k];  k* = greedy(Q_sel, m') of CCX_QLEARN with m' = CCX_SAMPLE step 2 on
+ *      masks_next;  p_j = e_j / S of next_target[i][k*].  A NaN expected value never wins.
+ *   4. Projection.  r = (float)reward[i] (one rounding);  disc = discount ? discount[i] : gamma;  cut = done[i] ||
+ *      disc == 0.0f.  A cut target reads no next-state array: p_0 = 1.0f, p_j = +0.0f (j > 0), the point mass at r.
+ *      t_j = cut ? r : r + disc * z_j;  u = t_j - t_j;  b0 = (t_j - vmin) / dz;  b1 = b0 < 0 ? u : b0;
+ *      b_j = b1 > top ? top + u : b1      (two selects; u is +0.0f for a finite t_j, so a finite target is limited to
+ *      [0, top], while an infinite or NaN reward or discount gives a NaN, not an edge atom);
+ *      w_ij = (1.0f - |b_j - (float)i|) < 0 ? +0.0f : that value      (max(+0.0f, .) as a select a NaN passes);
+ *      m_i = sum over j = 0 .. A - 1 ascending of p_j * w_ij, onto +0.0f.
+ *      Adding the exact zeros of the far atoms changes no bit: this is the floor / ceil scatter with its additions in
+ *      ascending j.
+ *   5. Loss of the row, on the distribution of logits[i][a] (step 1):  logp_i = d_i - log S;
+ *      ce = 0.0f - butterfly(m_i != 0 ? m_i * logp_i : +0.0f);  term = weights ? weights[i] * ce : ce;
+ *      qa = its expected value (step 2);  y = butterfly(m_i * z_i).
+ *   6. Which rows count and which are tallied as bad is CCX_QLEARN step 1, verbatim.  A row that does not count contributes
+ *      to no sum, reads no logits, and gets +0.0f in row_loss, in its A elements of proj and in every gradient, whatever its
+ *      inputs hold.  Six sums -- 1, term, ce, qa, y over the rows that count, 1 over the bad rows -- in f64 by the tree of
+ *      CCX_PPO_LOSS, unchanged.  stats = {S_term / n, S_ce / n, S_qa / n, S_y / n, +0.0f, +0.0f, (float)n, (float)bad};
+ *      n == 0: the first six are +0.0f.  row_loss[i] = counts ? ce : +0.0f (unweighted, >= 0: what CCX_PRIO takes as
+ *      td_error);  proj[i][.] = counts ? m : +0.0f.
+ *   7. Backward: a pure function of logits, actions, proj (the target is a constant), valid, weights, stats, grad_loss.
+ *      g = grad_loss ? grad_loss[0] : 1.0f;  sc = g / stats[6], made once;  gw = weights ? sc * weights[i] : sc;
+ *      Msum = butterfly(m);  grad_logits[i][a][j] = gw * ((e_j / S) * Msum - m_j), e and S of logits[i][a].
+ *      The other four actions of the row, rows that do not count, and stats[6] == 0 give exactly +0.0f.  Every element is
+ *      written.
+ * A non-finite logit (of logits[i][a], of next_target[i][k*]), reward or discount of a row that counts reaches row_loss and
+ * the loss as a NaN or an infinity.  A non-finite logit of an action the bootstrap does not choose is CCX_QLEARN's case: its
+ * NaN expected value never wins and reaches no result.
+ *
+ * Against IEEE f64 (measured on the CPU, tests/test_c51_spec.py, maxima doubled), as max |err| / max(1, |f64 value|) against
+ * the textbook composition in torch f64 on the same f32 inputs (softmax, expected values, masked argmax, floor / ceil
+ * projection with index_add_, cross-entropy averaged over the rows that count, autograd), logits ~ N(0, 2^2), support
+ * [-10, 10], A in {2, 3, 33, 51, 64}: proj within 1.3e-05, loss within 1.1e-07, row_loss within 1.6e-05, q within 2.1e-06,
+ * grad_logits (times n) within 1.6e-05 (rows whose two best legal expected next-values lie within 1e-4 of each other may
+ * choose another k* than f64 and are left out: under 0.5 %, asserted).  The projection's figure is ulp(b) at b near A - 1, a
+ * property of f32 positions on the support; row_loss and the gradient inherit it times |log p|.
+ *
+ * Launches: ccx_c51_q_values ONE kernel on the handle's stream, ccx_c51_loss TWO (block partials, then one final wave; no
+ * atomic, no last-block-done counter), ccx_c51_loss_backward ONE.  No host synchronisation, no allocation: the caller owns
+ * the workspace (ccx_c51_workspace_bytes(rows) bytes, 8-byte aligned; 0 for rows < 1).  Everything captures into a HIP
+ * graph.  Offsets are 64-bit.  q is f32 [M][5], 16-byte aligned (what ccx_q_actions takes); reward f64 and the workspace
+ * are 8-byte aligned; every other f32 array 4-byte aligned.  A NULL handle or a NULL required pointer, rows < 1 (or so many
+ * that a grid would pass 2^31 - 1 workgroups), atoms outside 2 .. 64, a vmin or vmax that is not finite, vmin >= vmax, a
+ * spacing that is not finite or not above zero, a gamma that is not finite or lies outside [0, 1] when discount is NULL
+ * (with discount given gamma is not read), a misaligned pointer: CCX_EINVAL with a ccx_last_error message, before any launch.
+ * The feature draws nothing: actions come from ccx_q_actions on the expected values.  Not here: a device MLP head with 5 A
+ * outputs, the obs -> action fusion for categorical heads, quantile (QR-DQN / IQN) heads, noisy layers, dueling combined
+ * with categorical heads, more than 64 atoms, bf16 / f16, the vector and RLlib adapters.
+ */
+int64_t ccx_c51_workspace_bytes(int64_t rows);
+int ccx_c51_q_values(ccx_handle* h, int64_t rows, int32_t atoms, float vmin, float vmax, const float* logits /* [M][5][A] */,
+                     float* q /* [M][5] */);
+int ccx_c51_loss(ccx_handle* h, int64_t rows, int32_t atoms, float vmin, float vmax, const float* logits /* [M][5][A] */,
+                 const uint8_t* actions /* [M] */, const double* reward /* [M] */, const uint8_t* done /* [M] */,
+                 const float* next_target /* [M][5][A] */, const float* next_online_or_null /* [M][5][A] */,
+                 const uint8_t* masks_next_or_null /* [M] */, const uint8_t* valid_or_null /* [M] */,
+                 const float* weights_or_null /* [M] */, const float* discount_or_null /* [M] */, float gamma, void* workspace,
+                 float* stats /* [8] */, float* row_loss_or_null /* [M]: ce, unweighted */, float* proj /* [M][A] */);
+int ccx_c51_loss_backward(ccx_handle* h, int64_t rows, int32_t atoms, const float* logits /* [M][5][A] */,
+                          const uint8_t* actions /* [M] */, const float* proj /* [M][A] */, const uint8_t* valid_or_null /* [M] */,
+                          const float* weights_or_null /* [M] */, const float* stats /* [8] */,
+                          const float* grad_loss_or_null /* [1] */, float* grad_logits /* [M][5][A] */);
 /*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
