@@ -6,7 +6,8 @@ advantages and a state value per row.  The actor step is ONE launch from observa
 `rollout` and `push`.  The update combines its three arrays of head outputs in ONE launch (`ql.dueling_into`) and puts
 `ql.dueling_backward` between the TD loss's gradient and `backward_into`: rows of the other side, whose gradient is +0.0, stay
 +0.0 through the combine.  Both steps are captured.  The whole run happens twice from the same seeds: the parameters AND the
-leaves end equal bit for bit."""
+leaves end equal bit for bit.  That every link of this loop is the written rule, not only that two runs agree, is what
+tests/test_gpu_rainbow_chain.py checks: the same calls at small shapes against the per-op specs composed on the CPU."""
 
 import sys
 from pathlib import Path

@@ -6,7 +6,8 @@ each record forward through up to two successors in the ring and hands back the 
 window ends on and, per row, the discount gamma^m its bootstrap takes -- `td_loss(discount=mb.discount)` reads it where it
 read `gamma`.  With a reward of -1 per step, information now travels three steps per update.  No `index_select` chain, no
 `where` over successors, nothing that knows `head` outside the library.  The whole run happens twice from the same seeds: the
-parameters AND the leaves end equal bit for bit."""
+parameters AND the leaves end equal bit for bit.  That every link of this loop (with dueling heads on top) is the written
+rule, not only that two runs agree, is what tests/test_gpu_rainbow_chain.py checks against the composed CPU specs."""
 
 import sys
 from pathlib import Path

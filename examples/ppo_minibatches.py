@@ -6,7 +6,9 @@ minibatches_per_epoch times walks through the shuffled env-steps of every epoch 
 no host work between replays.  The shuffle is over the K * E env-steps, not over whole steps, and it comes from
 `set_rng_seed`: nothing in the iteration is left to torch's generator but the initial weights.  `obs0=` makes the gather
 pick the row each step ACTED ON out of the rollout's own `obs`, so the collect loop keeps no second copy of every row.
-The whole iteration runs twice from the same seeds; the parameters and the optimiser's m and v are equal bit for bit."""
+The whole iteration runs twice from the same seeds; the parameters and the optimiser's m and v are equal bit for bit.  That
+every link of it is the written rule, not only that two runs agree, is what tests/test_gpu_ppo_minibatch_chain.py checks: the
+same calls at small shapes, with a last minibatch that is partly empty, against the per-op specs composed on the CPU."""
 
 import sys
 from pathlib import Path

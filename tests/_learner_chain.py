@@ -248,8 +248,9 @@ def side_slots(num_boarding: int):
 
 
 def sides_forward(x, heads, slots):
-    """SideHeads on rows x [..., N, L]: by definition each head's MlpHead outputs at its own slots.  (q, hidden)."""
-    q = np.zeros(x.shape[:-1] + (5,), F32)
+    """SideHeads on rows x [..., N, L]: by definition each head's MlpHead outputs at its own slots.  (q, hidden); q has the
+    heads' O columns (5: Q-values; 6: a dueling head's advantages and state value)."""
+    q = np.zeros(x.shape[:-1] + (heads[0][2].shape[0],), F32)
     hid = np.zeros(x.shape[:-1] + (H,), F32)
     for p, sl in zip(heads, slots):
         q[..., sl, :], hid[..., sl, :] = _head(np.ascontiguousarray(x[..., sl, :]), p, TANH)

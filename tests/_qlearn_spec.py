@@ -130,8 +130,10 @@ def valid_ok(valid, M):
 
 
 def td_rows(q, actions, reward, done, q_next_target, q_next_online=None, masks_next=None, valid=None, weights=None, gamma=0.99,
-            huber_delta=1.0):
-    """Steps 1-5 for every row (what rows that do not count hold is junk; ``counts`` says which do)."""
+            huber_delta=1.0, discount=None):
+    """Steps 1-5 for every row (what rows that do not count hold is junk; ``counts`` says which do).  ``discount`` f32 [M]:
+    include/ccx.h CCX_NSTEP's ``ccx_td_loss_discounted`` -- the same rule with ``discount[i]`` where it says gamma (step 4:
+    ``nb = (done[i] || discount[i] == 0) ? +0.0 : discount[i] * boot``); ``gamma`` is then not read."""
     q = np.asarray(q, F32).reshape(-1, 5)
     M = q.shape[0]
     a = np.asarray(actions, np.uint8).reshape(M).astype(np.int64)
@@ -140,7 +142,7 @@ def td_rows(q, actions, reward, done, q_next_target, q_next_online=None, masks_n
     bad = ok & (a > 4) & (a != ACTION_ABSENT)
     qt = np.asarray(q_next_target, F32).reshape(M, 5)
     sel = qt if q_next_online is None else np.asarray(q_next_online, F32).reshape(M, 5)
-    gamma, delta = F32(gamma), F32(huber_delta)
+    gamma, delta = F32(gamma) if discount is None else np.asarray(discount, F32).reshape(M), F32(huber_delta)
     with np.errstate(all="ignore"):
         c = F32(HALF * delta)
         qa = np.take_along_axis(q, np.minimum(a, 4)[:, None], -1)[:, 0]
@@ -171,9 +173,9 @@ def td_finals(S):
 
 
 def td_loss_spec(q, actions, reward, done, q_next_target, q_next_online=None, masks_next=None, valid=None, weights=None,
-                 gamma=0.99, huber_delta=1.0, details=False):
+                 gamma=0.99, huber_delta=1.0, details=False, discount=None):
     """(stats f32 [8], td_error f32 [M])."""
-    t = td_rows(q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, gamma, huber_delta)
+    t = td_rows(q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, gamma, huber_delta, discount)
     c, zero = t["counts"], F64(0.0)
     S = [tree_sum(np.where(c, F64(1.0), zero))]
     for name in ("term", "ad", "qa", "y"):
@@ -185,9 +187,9 @@ def td_loss_spec(q, actions, reward, done, q_next_target, q_next_online=None, ma
 
 
 def td_loss_backward_spec(q, actions, reward, done, q_next_target, q_next_online=None, masks_next=None, valid=None, weights=None,
-                          gamma=0.99, huber_delta=1.0, stats=None, grad_loss=None):
+                          gamma=0.99, huber_delta=1.0, stats=None, grad_loss=None, discount=None):
     """grad_q f32 [M, 5]."""
-    t = td_rows(q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, gamma, huber_delta)
+    t = td_rows(q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, gamma, huber_delta, discount)
     M, delta = t["M"], t["delta"]
     n = F32(stats[6])
     g = ONE if grad_loss is None else F32(grad_loss)

@@ -1,0 +1,387 @@
+"""Whole iterations of the two bigger loops on the CPU, composed from the per-op specs.  TEST INFRASTRUCTURE ONLY: what
+tests/test_gpu_rainbow_chain.py and tests/test_gpu_ppo_minibatch_chain.py hold the device to, bit for bit, and what
+tests/test_rainbow_chain_reference.py checks for coverage and sensitivity.  NumPy and the CPU oracle only: no torch, nothing
+of the library but the lowered config; written in the style of tests/_learner_chain.py, whose helpers are imported.
+
+``rainbow_reference``: the loop of examples/dqn_dueling.py -- per-side DUELING heads (O = 6), the fused epsilon-greedy actor
+step (by definition ``q_actions(dueling(sides(obs)))``), pushes into a ring with cut bytes and max-leaf priorities, a
+stratified prioritised draw with an annealed ``beta``, the n-step fetch, per-side TD losses with importance weights and a
+per-row discount, the dueling backward, per-side MLP backward, Adam, ``update_priorities`` with BOTH sides' ``td_error``, the
+target copy -- and one out-of-band event: at round EVENT_ROUND, between two replays, the envs are put back with
+``reset_from_pool()`` and ``mark_cut()`` is called.  ``ppo_minibatch_reference``: the iteration of examples/ppo_minibatches.py
+-- the collection, values, GAE and moments of ``ppo_reference``, then minibatches of env-steps drawn by the device's keyed
+permutation (``next_spec`` / ``gather_spec`` with ``obs0`` and the rollout's own ``obs``), the last of every epoch partly EMPTY.
+Each link is the spec its own test file compares the device with; nothing is restated here but the wiring.  ``mutate=``
+switches ONE wire to a plausible wrong one (MUTATIONS / PPO_MUTATIONS): the sensitivity test shows that each changes the
+result, so a device that made that mistake could not pass the comparison.
+
+Two additions to the example's loop, both needed for what the coverage conditions ask and both made on either side alike:
+
+- A user terminated table (``terminated_tables``; ``set_terminated_table`` on the device).  Under the built-in rule of
+  ``chain_config()`` no agent of these short episodes terminates, so ``done`` would be 0 in every record and no agent's
+  share of a window would end before the env's.  The table keeps the built-in rule -- terminated at the destination row --
+  and adds a sparse pattern of cells that terminate an agent standing on them.
+- A hand truncation (``hand_truncation``; ``set_state(truncated=)``) before round TRUNC_ROUND.  include/ccx.h CCX_NSTEP: a
+  row is DROPPED when its agent stops being live inside the env's window without terminating and without an env cut, and
+  "only a user truncation class can do that".  The built-in truncation ends the whole env, which is a cut.  So two agent
+  slots of every second env are truncated by hand between two replays: their records of the steps before are dropped in
+  the windows that reach past them.
+
+Final values (chosen on the CPU so that ``assert_rainbow_coverage`` / ``assert_ppo_minibatch_coverage`` hold for the
+``linear_init`` parameters of RAINBOW_INIT_SEEDS / PPO_INIT_SEEDS): see RAINBOW and PPO_MB below."""
+
+from __future__ import annotations
+
+import numpy as np
+from _adam_spec import adam_step_spec, new_state, state_bytes
+from _dueling_spec import dueling_backward_spec, dueling_spec
+from _gae_spec import gae_spec
+from _learner_chain import (EF_RESET, H, N, PPO, SEED, SIDES, _copy, _masks, _oracle_batch, chain_config,
+                            compact_of_rows, ppo_collect, ppo_lr, ppo_update_gradients, ppo_values, side_slots, sides_forward)
+from _minibatch_spec import draw_spec as minibatch_draw_spec
+from _minibatch_spec import advance_spec, gather_spec, next_spec
+from _mlp_backward_spec import NAMES, mlp_backward_spec
+from _mlp_spec import TANH
+from _nstep_spec import cut_push_spec, mark_cut_spec, new_cut, nstep_fetch_spec
+from _ppo_loss_spec import masked_moments_spec
+from _prio_spec import ONE_FIXED, new_pstate, push_leaf_spec, update_spec
+from _prio_spec import sample_spec as prio_sample_spec
+from _qlearn_spec import q_actions_spec, td_loss_backward_spec, td_loss_spec
+from _replay_spec import new_ring, push_spec, rows_spec
+from _reset_obs_spec import row_consts
+
+F32 = np.float32
+
+# The Rainbow loop.  E = 8 envs, a ring of 6 steps (48 records), n = 3; 2 warm-up steps and a push before each update, so
+# the first draw sees 3 steps, the ring is full from round 3 on and has wrapped from round 4 on.  40 env-steps a minibatch:
+# 320 rows per forward, more than one 256-row block of the tree.  The envs' step counters start staggered as in the DQN
+# chain.  TRUNC_ROUND / EVENT_ROUND: the hand truncation / the envs put back, before that round's actor step.  MAX_GRAD_NORM lies inside the range of the
+# twelve gradient norms (printed by tests/test_rainbow_chain_reference.py).
+RAINBOW = dict(E=8, RING_STEPS=6, N_STEP=3, WARMUP=2, ROUNDS=12, BATCH=40, TARGET_EVERY=5, ANNEAL=16, EPS=(0.9, 0.05),
+               BETA=(0.4, 1.0), ALPHA=0.6, PRIO_EPS=1e-6, GAMMA=0.99, HUBER_DELTA=1.0, LR=1e-3, MAX_GRAD_NORM=2.0,
+               EVENT_ROUND=7, TRUNC_ROUND=3, TRUNC_SLOTS=(1, 6), O=6)
+RAINBOW_INIT_SEEDS = (3, 4)                       # linear_init seeds of the boarding and the exiting head
+RAINBOW_START_STEP_COUNT = (np.arange(RAINBOW["E"], dtype=np.int32) % 4) * 3
+MB_KEYS = ("obs", "next_obs", "actions", "reward", "done", "valid", "masks_next", "index", "discount", "span")
+RAINBOW_GRAD_ORDER = tuple(f"{s}.{n}" for s in SIDES for n in NAMES)
+# what a round leaves behind, in chain order: a comparison that walks them names the first link that differs
+LINKS = (("actions", "explored", "index", "weights", "leaf_drawn") + tuple(f"mb.{k}" for k in MB_KEYS)
+         + tuple(f"td_stats.{s}" for s in SIDES) + tuple(f"td_error.{s}" for s in SIDES) + ("grad_q", "gva")
+         + tuple(f"grad.{g}" for g in RAINBOW_GRAD_ORDER) + ("adam_stats", "leaf", "pstate", "cut"))
+MUTATIONS = ("priorities_never_updated", "first_side_td_only", "weights_all_one", "scalar_gamma", "next_from_first_slot",
+             "cut_bytes_ignored", "no_mark_cut", "beta_fixed", "dueling_backward_copies")
+DRAW_SIDE_MUTATIONS = ("priorities_never_updated", "first_side_td_only", "beta_fixed")
+
+# The minibatch PPO iteration: the collection of ``ppo_reference`` (E = 12, K = 24: M = 288 env-steps), B = 80 does not divide
+# M: 4 minibatches an epoch, the last with 48 records and 32 EMPTY ones.  640 rows per forward.
+PPO_MB = dict(B=80, EPOCHS=2, MAX_GRAD_NORM=6.9)
+PPO_MUTATIONS = ("no_obs0", "epoch_not_in_permutation")
+PPO_MB_KEYS = ("obs", "actions", "logp", "advantages", "returns", "masks", "valid", "index")
+
+
+def same(got, want, msg):
+    """Equal dtype, shape and bytes (the sign of a zero included)."""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.dtype == want.dtype and got.shape == want.shape, (msg, got.dtype, want.dtype, got.shape, want.shape)
+    np.testing.assert_array_equal(got.view(np.uint8), want.view(np.uint8), err_msg=msg)
+
+
+def same_lists(got, want, names, msg):
+    assert len(got) == len(want) == len(names)
+    for g, w, name in zip(got, want, names):
+        same(g, w, f"{msg}: {name}")
+
+
+def rainbow_epsilon(u: int) -> float:
+    """The rate of round u: the formula of examples/dqn_dueling.py."""
+    start, end = RAINBOW["EPS"]
+    return max(end, start - (start - end) * u / max(1, RAINBOW["ANNEAL"]))
+
+
+def rainbow_beta(u: int) -> float:
+    start, end = RAINBOW["BETA"]
+    return min(end, start + (end - start) * u / max(1, RAINBOW["ANNEAL"]))
+
+
+def terminated_tables(config):
+    """(boarding, exiting) u8 [height + 1, width + 1]: terminated at the type's destination row (the built-in rule) and at
+    the cells with (3 x + 5 y) % 11 == 0, a ninth of the grid."""
+    shape = (config.height + 1, config.width + 1)
+    y, x = np.indices(shape)
+    sparse = (3 * x + 5 * y) % 11 == 0
+    return tuple((sparse | (y == dest)).astype(np.uint8)
+                 for dest in (config.boarding_destination_area_y, config.exiting_destination_area_y))
+
+
+def hand_truncation(truncated):
+    """u8 [E, N]: the state's ``truncated`` with slots TRUNC_SLOTS of every second env set."""
+    out = np.array(truncated, np.uint8, copy=True)
+    for a in RAINBOW["TRUNC_SLOTS"]:
+        out[::2, a] = 1
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Rainbow
+# ---------------------------------------------------------------------------------------------------------------------
+def rainbow_reference(online, mutate=None):
+    """The loop from the initial online parameters, a list of two (w1t, b1, w2, b2) with O = 6 in the order of SIDES; the
+    target starts as a copy.  Returns per actor step ``actions`` / ``explored`` (WARMUP + ROUNDS of them), per round
+    ``epsilon``, ``beta`` and ``rounds[u]``: a dict of every array of LINKS; the final ``params``, ``target``, ``m``, ``v``,
+    ``state_bytes``, ``ring_state``, ``leaf``, ``pstate``, ``cut``; ``facts``."""
+    assert mutate is None or mutate in MUTATIONS, mutate
+    R_ = RAINBOW
+    E, S, B, n = R_["E"], R_["RING_STEPS"], R_["BATCH"], R_["N_STEP"]
+    config = chain_config()
+    oracle, params_c, ob = _oracle_batch(config, E)
+    ob.set_state(step_count=RAINBOW_START_STEP_COUNT)
+    ob.set_user_tables(None, terminated_tables(config))
+    slots = side_slots(config.num_boarding_agents)
+    consts = row_consts(params_c)
+    heads = [_copy(p) for p in online]
+    assert all(p[2].shape == (R_["O"], H) for p in heads)
+    target = [_copy(p) for p in heads]
+    flat = [p for h in heads for p in h]
+    ms, vs, state = [np.zeros_like(p) for p in flat], [np.zeros_like(p) for p in flat], new_state()
+    ring, cut = new_ring(S, E, N), new_cut(S, E)
+    leaf, pstate = np.zeros(S * E, np.int32), new_pstate()
+    first_side = np.array([a in slots[0] for a in range(N)])
+    side_u8 = [np.array([a in sl for a in range(N)], np.uint8) for sl in slots]
+    out = dict(actions=[], explored=[], epsilon=[], beta=[], rounds=[], windows=[], head=[], copies=[], target_differs=[],
+               drawn_resets=[], max_leaf=[], drawn_fresh_risen=[], shortened_by_event=[], distinct_leaves=[])
+    obs_c = compact_of_rows(ob.observe())
+    reset_slots = np.zeros(S * E, bool)               # the record ends an episode
+    fresh = np.zeros(S * E, bool)                     # pushed, and no update has named it since
+    pushed_with = np.zeros(S * E, np.int64)           # max_leaf at its push
+    event = dict(slots=set(), alive_until=-1)         # slots whose cut byte the event's mark_cut raised from 0
+
+    def actor_step(eps):
+        nonlocal obs_c
+        rows = ob.observe()
+        masks = _masks(oracle, params_c, ob)
+        va, _ = sides_forward(rows, heads, slots)
+        acts, explored = q_actions_spec(dueling_spec(va), masks, ob.terminated, ob.truncated, ob.step_count.copy(), ob.episode.copy(),
+                                        seed=SEED, epsilon=F32(eps))
+        step_obs, reward, af, ef = ob.rollout(acts[None], auto_reset=True)
+        reset = (ef[0] & EF_RESET) != 0
+        next_rows = np.where(reset[:, None, None], ob.observe(), step_obs[0])        # reset_obs="next"
+        next_c, final_c = compact_of_rows(next_rows), compact_of_rows(step_obs[0])
+        masks_next = _masks(oracle, params_c, ob)
+        head = int(ring["state"][0])
+        at = slice((head % S) * E, (head % S) * E + E)
+        reset_slots[at], fresh[at], pushed_with[at] = reset, True, int(pstate[0])
+        push_spec(ring, obs_c, acts[None], reward, af, ef, next_c[None], final_c[None], masks_next[None])
+        cut_push_spec(cut, int(ring["state"][0]), S, E, ef)
+        push_leaf_spec(leaf, pstate, head, 1, S, E)
+        obs_c = next_c
+        out["actions"].append(acts)
+        out["explored"].append(explored)
+
+    for _ in range(R_["WARMUP"]):
+        actor_step(R_["EPS"][0])
+    for u in range(R_["ROUNDS"]):
+        if u == R_["TRUNC_ROUND"]:                                                   # out of band: a user truncation by hand
+            ob.set_state(truncated=hand_truncation(ob.truncated))
+        if u == R_["EVENT_ROUND"]:                                                   # out of band, between two replays
+            head_now = int(ring["state"][0])
+            ob.reset_from_pool()
+            before = cut.copy()
+            if mutate != "no_mark_cut":
+                mark_cut_spec(cut, head_now, S, E)
+            event["slots"] = set(np.flatnonzero((before == 0) & (cut != 0)).tolist())
+            event["alive_until"] = head_now - 1 + S                                  # the last head before a push overwrites them
+            obs_c = compact_of_rows(ob.observe())
+        eps, beta = float(F32(rainbow_epsilon(u))), float(F32(rainbow_beta(0 if mutate == "beta_fixed" else u)))
+        actor_step(eps)
+        head = int(ring["state"][0])
+        drawn = prio_sample_spec(leaf, pstate, SEED, B, N, beta, stratified=True)
+        index = drawn["index"]
+        mb = nstep_fetch_spec(ring, np.zeros_like(cut) if mutate == "cut_bytes_ignored" else cut, index, n, R_["GAMMA"], consts,
+                              details=True)
+        windows = mb.pop("windows")
+        if mutate == "next_from_first_slot":
+            mb["next_obs"], mb["masks_next"] = rows_spec(ring["next_c"][index], consts), ring["masks_next"][index].copy()
+        va, hid = sides_forward(mb["obs"], heads, slots)
+        vat, _ = sides_forward(mb["next_obs"], target, slots)
+        vao, _ = sides_forward(mb["next_obs"], heads, slots)
+        q, qt, qo = dueling_spec(va), dueling_spec(vat), dueling_spec(vao)
+        args = (q, mb["actions"], mb["reward"], mb["done"], qt, qo, mb["masks_next"])
+        weights = np.ones_like(drawn["weights"]) if mutate == "weights_all_one" else drawn["weights"]
+        kw = dict(weights=weights, huber_delta=R_["HUBER_DELTA"])
+        kw.update(dict(gamma=R_["GAMMA"]) if mutate == "scalar_gamma" else dict(discount=mb["discount"]))
+        stats, tds, gq_side = [], [], []
+        for side in side_u8:
+            valid = (mb["valid"] * side[None, :]).astype(np.uint8)                   # valid & side (0 / 4 times 0 / 1)
+            st, td = td_loss_spec(*args, valid=valid, **kw)
+            stats.append(st)
+            tds.append(td.reshape(B, N))
+            gq_side.append(td_loss_backward_spec(*args, valid=valid, **kw, stats=st).reshape(B, N, 5))
+        gq = np.where(first_side[None, :, None], gq_side[0], gq_side[1])             # each side keeps its own bits
+        if mutate == "dueling_backward_copies":
+            gva = np.concatenate([gq, np.zeros((B, N, 1), F32)], -1)
+        else:
+            gva = dueling_backward_spec(gq)
+        grads = []
+        for p, sl in zip(heads, slots):
+            g = mlp_backward_spec(*(np.ascontiguousarray(a[:, sl]).reshape(B * len(sl), -1) for a in (mb["obs"], hid, gva)), p[2], TANH)
+            grads += [g[k] for k in NAMES]
+        out["target_differs"].append(bool((vat.view(np.uint32) != vao.view(np.uint32)).any()))
+        adam_stats = adam_step_spec(flat, grads, ms, vs, state, R_["LR"], max_grad_norm=R_["MAX_GRAD_NORM"])
+        # ---- facts of the draw, before the update changes the leaves
+        out["distinct_leaves"].append((len(np.unique(leaf[leaf != 0])), float(drawn["weights"].min())))
+        out["drawn_fresh_risen"].append(int((fresh[index] & (pushed_with[index] > ONE_FIXED)
+                                             & (drawn["leaf_drawn"] == pushed_with[index])).sum()))
+        out["shortened_by_event"].append(sum(1 for w in windows if head <= event["alive_until"] and w["why"] == "cut"
+                                             and w["last"] in event["slots"]))
+        out["drawn_resets"].append(int(reset_slots[index].sum()))
+        if mutate != "priorities_never_updated":
+            update_spec(leaf, pstate, index, tds[:1] if mutate == "first_side_td_only" else tuple(tds), R_["ALPHA"], R_["PRIO_EPS"])
+            fresh[index] = False
+        copied = (u + 1) % R_["TARGET_EVERY"] == 0
+        if copied:
+            target = [_copy(p) for p in heads]
+        rnd = dict(actions=out["actions"][-1], explored=out["explored"][-1], index=index, weights=drawn["weights"],
+                   leaf_drawn=drawn["leaf_drawn"], grad_q=gq, gva=gva, adam_stats=adam_stats, leaf=leaf.copy(), pstate=pstate.copy(),
+                   cut=cut.copy())
+        rnd.update({f"mb.{k}": mb[k] for k in MB_KEYS})
+        for i, s in enumerate(SIDES):
+            rnd[f"td_stats.{s}"], rnd[f"td_error.{s}"] = stats[i], tds[i]
+        rnd.update({f"grad.{g}": a for g, a in zip(RAINBOW_GRAD_ORDER, grads)})
+        assert set(rnd) == set(LINKS)
+        for k, v in (("epsilon", eps), ("beta", beta), ("rounds", rnd), ("windows", windows), ("head", head), ("copies", copied),
+                     ("max_leaf", int(pstate[0]))):
+            out[k].append(v)
+    out.update(params=_copy(flat), target=[np.array(p, copy=True) for h in target for p in h], m=_copy(ms), v=_copy(vs),
+               state_bytes=state_bytes(state), ring_state=ring["state"].copy(), leaf=leaf.copy(), pstate=pstate.copy(), cut=cut.copy(),
+               capacity=S * E, consts=consts)
+    out["facts"] = rainbow_facts(out)
+    return out
+
+
+def rainbow_facts(r) -> dict:
+    wins = [w for ws in r["windows"] for w in ws if w is not None]
+    rounds = r["rounds"]
+    return dict(
+        ring_heads=r["head"], ring_steps=RAINBOW["RING_STEPS"],
+        window_spans=sorted({int(w["m_env"]) for w in wins}), agent_spans=sorted({int(s) for x in rounds for s in np.unique(x["mb.span"])}),
+        windows_ended_by={why: sum(w["why"] == why for w in wins) for why in ("n", "cut", "avail")},
+        windows_that_wrap=sum(bool(w["wraps"]) for w in wins),
+        rows_dropped=sum(int((w["dropped"] & (w["valid"] == 0) & (w["span"] < w["m_env"])).sum()) for w in wins),
+        rows_dropped_that_were_live=[int(((x["mb.valid"] == 0) & (x["mb.actions"] != 255)).sum()) for x in rounds],
+        rows_that_end_with_done=sum(int((x["mb.done"] != 0).sum()) for x in rounds),
+        drawn_records_that_end_an_episode=r["drawn_resets"], windows_shortened_by_the_event=r["shortened_by_event"],
+        rounds_with_a_duplicate_index=[u for u, x in enumerate(rounds) if len(np.unique(x["index"])) < len(x["index"])],
+        distinct_leaves_and_min_weight=r["distinct_leaves"], max_leaf=r["max_leaf"],
+        drawn_unupdated_records_pushed_with_a_risen_max_leaf=r["drawn_fresh_risen"],
+        epsilons=r["epsilon"], betas=r["beta"],
+        side_counts=[[int(x[f"td_stats.{s}"][6]) for s in SIDES] for x in rounds],
+        copies=r["copies"], target_differs=r["target_differs"],
+        adam_norms=[float(x["adam_stats"][0]) for x in rounds], adam_scales=[float(x["adam_stats"][1]) for x in rounds],
+        adam_skipped=[float(x["adam_stats"][2]) for x in rounds])
+
+
+def assert_rainbow_coverage(r) -> None:
+    f, rounds = r["facts"], RAINBOW["ROUNDS"]
+    assert max(f["ring_heads"]) > f["ring_steps"], f                                 # the head passes the capacity
+    assert f["window_spans"] == [1, 2, 3] and f["agent_spans"] == [1, 2, 3], f
+    assert all(c > 0 for c in f["windows_ended_by"].values()), f
+    assert f["windows_that_wrap"] > 0 and f["rows_dropped"] > 0 and sum(f["rows_dropped_that_were_live"]) > 0, f
+    assert sum(f["drawn_records_that_end_an_episode"]) > 0 and f["rows_that_end_with_done"] > 0, f
+    assert sum(f["windows_shortened_by_the_event"]) > 0, f
+    assert f["rounds_with_a_duplicate_index"], f
+    assert any(d >= 3 and w < 1.0 for d, w in f["distinct_leaves_and_min_weight"]), f
+    assert max(f["max_leaf"]) > ONE_FIXED and sum(f["drawn_unupdated_records_pushed_with_a_risen_max_leaf"]) > 0, f
+    assert len(set(f["epsilons"])) == rounds and len(set(f["betas"])) == rounds, f   # every round has its own f32 rates
+    assert all(c > 0 for pair in f["side_counts"] for c in pair), f
+    assert any(s < 1.0 for s in f["adam_scales"]) and any(s == 1.0 for s in f["adam_scales"]) and not any(f["adam_skipped"]), f
+    first = f["copies"].index(True)
+    # a copy between two updates, and it matters: the round behind it sees target == online, the one after that does not
+    assert first + 2 < rounds and not f["target_differs"][first + 1] and f["target_differs"][first + 2], f
+
+
+def first_difference(a, b):
+    """The first link, in chain order, at which two runs of ``rainbow_reference`` differ: "round u: name", or None."""
+    for u, (x, y) in enumerate(zip(a["rounds"], b["rounds"])):
+        for k in LINKS:
+            if x[k].shape != y[k].shape or x[k].tobytes() != y[k].tobytes():
+                return f"round {u}: {k}"
+    return None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# PPO with device-drawn minibatches
+# ---------------------------------------------------------------------------------------------------------------------
+def ppo_minibatch_reference(actor, critic, form="rows", mutate=None):
+    """One PPO iteration whose minibatches are the device's draw.  ``form``: "rows" (``obs`` f32 [K, E, N, L]) or "compact"
+    ([K, E, N, 4], expanded by the gather).  Returns the collection's arrays, values, advantages, ``norm``, ``source`` (what
+    ``set_source`` is given), per update ``index``, ``mb`` (every gathered array), ``stats``, ``grads`` (GRAD_ORDER),
+    ``adam_stats``; the final ``params`` / ``m`` / ``v`` / ``state_bytes`` and ``mb_state``; ``facts``."""
+    assert form in ("rows", "compact") and (mutate is None or mutate in PPO_MUTATIONS)
+    from collectivecrossing_amd.params import lower_config
+
+    E, K, B = PPO["E"], PPO["K"], PPO_MB["B"]
+    M = K * E
+    consts = row_consts(lower_config(chain_config()))
+    actor, critic = _copy(actor), _copy(critic)
+    col = ppo_collect(actor)
+    values, last_values, final_values = ppo_values(col, critic)
+    adv, ret, valid = gae_spec(col["reward"], col["agent_flags"], col["env_flags"], values, last_values, final_values, PPO["GAMMA"],
+                               PPO["LAM"])
+    norm = masked_moments_spec(adv, valid)
+    obs0 = col["rows"][0]                                                            # what step 0 acted on
+    obs = np.concatenate([col["rows"][1:], col["last_rows"][None]])                 # the rollout's own: rows BEHIND step s
+    if form == "compact":
+        obs0, obs = compact_of_rows(obs0), compact_of_rows(obs)
+    source = dict(obs=obs, obs0=None if mutate == "no_obs0" else obs0, actions=col["actions"], logp=col["logp"], advantages=adv,
+                  returns=ret, masks=col["masks"], valid=valid)
+    params = actor + critic
+    ms, vs, state = [np.zeros_like(p) for p in params], [np.zeros_like(p) for p in params], new_state()
+    mb_state = np.zeros(4, np.int64)
+    per_epoch = -(-M // B)
+    updates = dict(index=[], mb=[], stats=[], grads=[], adam_stats=[])
+    for step in range(PPO_MB["EPOCHS"] * per_epoch):
+        if mutate == "epoch_not_in_permutation":
+            index = minibatch_draw_spec(M, B, SEED, (0, int(mb_state[1])))
+            advance_spec(mb_state, B, M)
+        else:
+            index = next_spec(M, B, SEED, mb_state)
+        mb = gather_spec(source, index, E, consts)
+        x = mb["obs"].reshape(-1, mb["obs"].shape[-1])
+        stats, grads, _, _ = ppo_update_gradients(x, mb, actor, critic, norm)
+        adam_stats = adam_step_spec(params, grads, ms, vs, state, ppo_lr(step), weight_decay=PPO["WEIGHT_DECAY"],
+                                    max_grad_norm=PPO_MB["MAX_GRAD_NORM"])
+        for k, v in (("index", index), ("mb", mb), ("stats", stats), ("grads", grads), ("adam_stats", adam_stats)):
+            updates[k].append(v)
+    out = dict(col, values=values, last_values=last_values, final_values=final_values, advantages=adv, returns=ret, valid=valid,
+               norm=norm, source=dict(source, obs0=obs0), **updates, params=_copy(params), m=_copy(ms), v=_copy(vs),
+               state_bytes=state_bytes(state), mb_state=mb_state.copy(), per_epoch=per_epoch, records=M)
+    out["facts"] = ppo_minibatch_facts(out)
+    return out
+
+
+def ppo_minibatch_facts(r) -> dict:
+    E, per = PPO["E"], r["per_epoch"]
+    epochs = [np.concatenate(r["index"][e * per:(e + 1) * per]) for e in range(PPO_MB["EPOCHS"])]
+    return dict(
+        minibatch_counts=[int(s[6]) for s in r["stats"]], real_records=[int((i >= 0).sum()) for i in r["index"]],
+        empty_rows_run=[int(((m["actions"] == 255) & (m["valid"] == 0) & (i < 0)[:, None]).sum()) for m, i in zip(r["mb"], r["index"])],
+        step0_records_per_epoch=[int(((e >= 0) & (e < E)).sum()) for e in epochs],
+        every_epoch_is_a_permutation=all(sorted(e[e >= 0].tolist()) == list(range(r["records"])) for e in epochs),
+        permutations_differ=bool((epochs[0] != epochs[1]).any()), mb_state=r["mb_state"].tolist(),
+        adam_norms=[float(s[0]) for s in r["adam_stats"]], adam_scales=[float(s[1]) for s in r["adam_stats"]],
+        adam_skipped=[float(s[2]) for s in r["adam_stats"]], adam_lrs=[float(s[3]) for s in r["adam_stats"]])
+
+
+def assert_ppo_minibatch_coverage(r) -> None:
+    f, per, B = r["facts"], r["per_epoch"], PPO_MB["B"]
+    assert per == 4 and len(f["minibatch_counts"]) == PPO_MB["EPOCHS"] * per == 8, f
+    for e in range(PPO_MB["EPOCHS"]):
+        counts = f["minibatch_counts"][e * per:(e + 1) * per]
+        assert 0 < counts[-1] < min(counts[:-1]), f                                  # the tail counts fewer rows, and some
+        assert f["real_records"][e * per:(e + 1) * per] == [B, B, B, r["records"] - 3 * B], f
+        assert f["empty_rows_run"][(e + 1) * per - 1] == (4 * B - r["records"]) * N, f
+    assert all(c > 0 for c in f["step0_records_per_epoch"]) and f["every_epoch_is_a_permutation"] and f["permutations_differ"], f
+    assert f["mb_state"] == [PPO_MB["EPOCHS"], 0, 0, 0], f
+    assert sum(s < 1.0 for s in f["adam_scales"]) >= 2 and sum(s == 1.0 for s in f["adam_scales"]) >= 2 and not any(f["adam_skipped"]), f
+    at = PPO["LR_CHANGE_AFTER"]
+    assert f["adam_lrs"] == [float(F32(ppo_lr(s))) for s in range(8)] and f["adam_lrs"][at - 1] != f["adam_lrs"][at], f
