@@ -115,3 +115,108 @@ struct ccx_handle {
     int tun_stats_naive = 0;                                    // 1: the accumulate kernel with one dependent load per step (timing table only)
     uint32_t eps_thr = 0;                                       // epsilon * 2^32 of the scripted policies (ccx_set_policy_epsilon); the launchers copy the three into their KParams
 };
+
+// ---------------------------------------------------------------------------------------------
+// The ring of CCX_REPLAY as the ABI passes it, and the launch of a kernel that gathers a minibatch of B records, EW to a wave
+// (ccx_replay.hip, ccx_nstep.hip, ccx_prio.hip; the grid also ccx_minibatch.hip).  The device side is ccx_gather.h.
+// ---------------------------------------------------------------------------------------------
+
+// ring_steps and the eight arrays, in the order of RingArrays
+#define CCX_RING_PARAMS int64_t ring_steps, float* ring_obs_c, float* ring_next_c, uint8_t* ring_actions, double* ring_reward, \
+                        uint8_t* ring_done, uint8_t* ring_valid, uint8_t* ring_masks_next, int64_t* ring_state
+#define CCX_RING_ARGS ring_steps, ring_obs_c, ring_next_c, ring_actions, ring_reward, ring_done, ring_valid, ring_masks_next, ring_state
+
+namespace ccxi {
+
+struct RingArrays {                    // the ring's own storage, [R][N] (compact: [R][N] float4)
+    float4* obs_c;
+    float4* next_c;
+    uint8_t* actions;
+    double* reward;
+    uint8_t* done;
+    uint8_t* valid;
+    uint8_t* masks_next;
+    long long* state;                  // {head, draws, 0, 0}
+};
+
+struct BatchOut {                      // the minibatch of B records, [B][N]
+    float* obs;                        // [B][N][L] or null
+    float* next_obs;                   // [B][N][L] or null
+    uint8_t* actions;
+    double* reward;
+    uint8_t* done;
+    uint8_t* valid;
+    uint8_t* masks_next;
+    int64_t* index;                    // [B]
+};
+
+struct FetchArgs {                     // what a kernel that fetches B records of the ring takes
+    RingArrays ring;
+    const int64_t* index_in;           // [B]: read where the kernel does not draw
+    BatchOut out;
+    long long B, R;
+    int S, E, glog;
+    uint32_t seed_lo, seed_hi;
+};
+
+inline unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }     // workgroups of 256 lanes, a lane per item (n <= 2^37: R N)
+
+// the handle and the ring's S: R = S * E records are addressed with 32 bits
+inline int check_ring_steps(const char* who, const ccx_handle* h, int64_t ring_steps) {
+    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (ring_steps < 1 || ring_steps >= (1ll << 31) || ring_steps * (int64_t)h->E >= (1ll << 31))
+        return fail(CCX_EINVAL, "%s: ring_steps = %lld out of range (1 <= S, S * E < 2^31)", who, (long long)ring_steps);
+    return CCX_OK;
+}
+
+inline int check_ring(const char* who, const ccx_handle* h, CCX_RING_PARAMS, RingArrays& a) {
+    if (int rc = check_ring_steps(who, h, ring_steps)) return rc;
+    if (!ring_obs_c || !ring_next_c || !ring_actions || !ring_reward || !ring_done || !ring_valid || !ring_masks_next || !ring_state)
+        return fail(CCX_EINVAL, "%s: NULL ring array", who);
+    if (misaligned(16, ring_obs_c, ring_next_c)) return fail(CCX_EINVAL, "%s: the ring's compact arrays must be 16-byte aligned", who);
+    if (misaligned(8, ring_reward, ring_state)) return fail(CCX_EINVAL, "%s: the ring's reward and state must be 8-byte aligned", who);
+    a = RingArrays{reinterpret_cast<float4*>(ring_obs_c), reinterpret_cast<float4*>(ring_next_c), ring_actions, ring_reward, ring_done,
+                   ring_valid, ring_masks_next, reinterpret_cast<long long*>(ring_state)};
+    return CCX_OK;
+}
+
+inline int check_batch_size(const char* who, const ccx_handle* h, int64_t B) {
+    if (B < 1 || B * (int64_t)h->N > (1ll << 31)) return fail(CCX_EINVAL, "%s: batch = %lld out of range (1 <= B <= 2^31 / N)", who, (long long)B);
+    return CCX_OK;
+}
+
+// the grid of B records, EW to a wave, in workgroups of the handle's launch shape
+inline int gather_grid(const char* who, const ccx_handle* h, int64_t B, dim3& grid, dim3& block) {
+    const int64_t per_block = (int64_t)h->kp.EW * h->kp.waves_per_block;
+    const int64_t blocks = (B + per_block - 1) / per_block;
+    if (blocks > 0x7FFFFFFFll) return fail(CCX_EINVAL, "%s: batch = %lld needs too many workgroups", who, (long long)B);
+    grid = dim3((unsigned)blocks);
+    block = dim3(64 * h->shape.waves_per_block);
+    return CCX_OK;
+}
+
+// Everything ccx_replay_sample / _fetch and ccx_nstep_sample / _fetch check and pass alike: the ring, the outputs, the batch
+// and the index, the alignments, the grid.  The kernel takes the handle's kp next to A, lds_bytes_observe of LDS, and the
+// 16-byte row stores where N is even.
+inline int fetch_args(const char* who, const ccx_handle* h, CCX_RING_PARAMS, int64_t B, const int64_t* index_in, const BatchOut& out,
+                      bool draw, FetchArgs& A, dim3& grid, dim3& block) {
+    if (int rc = check_ring(who, h, CCX_RING_ARGS, A.ring)) return rc;
+    if (!out.actions || !out.reward || !out.done || !out.valid || !out.masks_next || !out.index)
+        return fail(CCX_EINVAL, "%s: NULL output (only obs and next_obs may be NULL)", who);
+    if (!draw && !index_in) return fail(CCX_EINVAL, "%s: NULL index", who);
+    if (int rc = check_batch_size(who, h, B)) return rc;
+    if (misaligned(16, out.obs, out.next_obs)) return fail(CCX_EINVAL, "%s: obs and next_obs must be 16-byte aligned", who);
+    if (misaligned(8, out.reward, out.index, index_in)) return fail(CCX_EINVAL, "%s: reward and index must be 8-byte aligned", who);
+    A.index_in = index_in;
+    A.out = out;
+    A.B = B;
+    A.R = ring_steps * (int64_t)h->E;
+    A.S = (int)ring_steps;
+    A.E = h->E;
+    A.glog = h->shape.glog;
+    A.seed_lo = h->rng_lo;
+    A.seed_hi = h->rng_hi;
+    return gather_grid(who, h, B, grid, block);
+}
+
+}  // namespace ccxi

@@ -2,15 +2,14 @@
 // draws B positions of the epoch's keyed permutation, gathers the records they name and writes the minibatch ppo_loss takes;
 // one plain lane behind it advances {epoch, cursor} on the device, so a captured update walks through minibatches and epochs by
 // being replayed.  The permutation, the draw, the state and the EMPTY row are ccx_minibatch.h's; the word is ccx_kernels.h's; the
-// rows of the compact form are written by the gather of ccx_observe / ccx_expand_observations (ccx_rollout_dev.h:
-// build_obs_table, emit_obs), called, not restated.
+// lane layout and, for the compact form, the wave's tile and the emission of the rows are ccx_gather.h's; the grid is
+// ccx_internal.h's: called, not restated.
 //
-// minibatch_gather_kernel<DRAW, COMPACT, PAIR>: replay_fetch_kernel's lane layout -- a wave takes the EW records b0 .. b0 + EW - 1
-// of the minibatch, lane (g, i) agent i of record b0 + g.  Every lane of a group works out the record's index for itself (DRAW:
-// the walk of the six-round network; else the caller's index[b]), so no lane waits for another's walk.
+// minibatch_gather_kernel<DRAW, COMPACT, PAIR>: a record-gather wave (ccx_gather.h) -- lane (g, i) is agent i of record b0 + g.
+// Every lane of a group works out the record's index for itself (DRAW: the walk of the six-round network; else the caller's
+// index[b]), so no lane waits for another's walk.
 //   COMPACT: the lane's float4 of the compact record and its six small fields are loaded THROUGH the index, all in flight before
-//   the first wait; the wave's tile takes the float4s and the rows of its EW records (ONE contiguous region of obs) leave it
-//   through emit_obs.
+//   the first wait; the small fields are stored, then the tile is set up and emit_rows writes the rows.
 //   rows: the wave's region of obs is EW N L contiguous floats, copied in 16-byte units (8-byte for an odd N: a record is then
 //   8 mod 16 bytes long).  Workgroup (x, y) copies units y 64 kUnits .. of wave x's region, kUnits per lane: the index of a
 //   unit's record comes from the lane that walked it (one ds_bpermute), and the lane's kUnits row loads and six small loads
@@ -18,8 +17,8 @@
 // minibatch_state_kernel: one lane advances the state BEHIND the launch that read it (replay_head_kernel's pattern).
 // minibatch_perm_kernel: pi_c(0 .. M - 1) of a given epoch, a lane per position.
 #include "ccx_internal.h"
+#include "ccx_gather.h"
 #include "ccx_minibatch.h"
-#include "ccx_rollout_dev.h"
 
 using ccxi::fail;
 using ccxi::misaligned;
@@ -85,13 +84,10 @@ template <bool DRAW, bool COMPACT, bool PAIR>
 __global__ __launch_bounds__(256) void minibatch_gather_kernel(const ccx::KParams p, const MbArgs A) {
     using namespace ccx;
     extern __shared__ __align__(16) unsigned char smem[];
-    const int lane = threadIdx.x & 63;
-    const int wib = threadIdx.x >> 6;
-    const long long wave = (long long)blockIdx.x * p.waves_per_block + wib;
-    const int g = lane >> A.glog, i = lane & ((1 << A.glog) - 1);
-    const long long b0 = wave * p.EW, b = b0 + g;
-    const int N = p.N, L = 6 + 4 * N;
-    const bool mine = (g < p.EW) && (b < A.B) && (i < N);
+    const ccx_gather::Lane l = ccx_gather::lane_of(p, A.glog, A.B);
+    const int lane = l.lane, i = l.i, N = l.N, L = 6 + 4 * N;
+    const long long b = l.b;
+    const bool mine = l.mine;
     const bool small = mine && blockIdx.y == 0u;                         // (rows form: the other y only copy rows)
     // the record: every lane of a group works it out for itself
     long long idx = -1;
@@ -124,14 +120,13 @@ __global__ __launch_bounds__(256) void minibatch_gather_kernel(const ccx::KParam
         mk = A.s.masks ? A.s.masks[at] : ccx_minibatch::kMasksAll;
         vl = A.s.valid ? A.s.valid[at] : ccx_minibatch::kValidLive;
     }
-    long long here = A.B - b0;
-    here = here < 0 ? 0 : (here > p.EW ? p.EW : here);
-    const size_t region = (size_t)b0 * (size_t)N * (size_t)L;             // floats in front of this wave's rows
+    const uint32_t here = (uint32_t)ccx_gather::records_here(p, l, A.B);
+    const size_t region = ccx_gather::rows_before(l);                    // (both worked out here, ahead of the branch: see DESIGN.md 3.27)
     if constexpr (!COMPACT) {
         if (A.o.obs) {
             using V = std::conditional_t<PAIR, float4, float2>;
             const uint32_t U = ((uint32_t)N * (3u + 2u * (uint32_t)N)) >> (PAIR ? 1 : 0);   // vector units of one record's rows
-            const uint32_t units = (uint32_t)here * U;
+            const uint32_t units = here * U;
             const uint32_t q0 = blockIdx.y * (64u * kUnits) + (uint32_t)lane;
             const int from = read ? (int)idx : -1;                       // (in [0, M): 31 bits)
             V v[kUnits];
@@ -177,17 +172,8 @@ __global__ __launch_bounds__(256) void minibatch_gather_kernel(const ccx::KParam
         A.o.valid[to] = vl;
         if (i == 0) A.o.index[b] = idx;
     }
-    if constexpr (COMPACT) {
-        if (A.o.obs) {
-            WaveLds* wl = reinterpret_cast<WaveLds*>(smem) + wib;
-            uint16_t* table = reinterpret_cast<uint16_t*>(smem + sizeof(WaveLds) * p.waves_per_block);
-            build_obs_table<0>(table, p);
-            init_wave_consts(wl, p, lane);
-            const int units = (int)here * N * (3 + 2 * N);
-            wl->slot[lane] = me;
-            __syncthreads();                                             // the table and the tile are in LDS
-            emit_obs<PAIR>(wl, table, reinterpret_cast<char*>(A.o.obs + region), 0, PAIR ? (units >> 1) : units, lane);
-        }
+    if constexpr (COMPACT) {                                             // (the tile is set up behind the small stores)
+        if (A.o.obs) ccx_gather::emit_rows<PAIR>(ccx_gather::tile_of(smem, p, l), p, l, A.B, A.o.obs, nullptr, me, me);
     }
 }
 
@@ -216,7 +202,7 @@ int gather(const char* who, ccx_handle* h, int64_t K, int32_t compact, const MbS
     if (draw ? !state : !index_in) return fail(CCX_EINVAL, "%s: NULL %s", who, draw ? "state" : "index");
     if (K < 1 || K > ccx_minibatch::kMaxRecords / (int64_t)h->E)
         return fail(CCX_EINVAL, "%s: K = %lld out of range (1 <= K * E < 2^31)", who, (long long)K);
-    if (B < 1 || B * (int64_t)h->N > (1ll << 31)) return fail(CCX_EINVAL, "%s: batch = %lld out of range (1 <= B <= 2^31 / N)", who, (long long)B);
+    if (int rc = ccxi::check_batch_size(who, h, B)) return rc;
     if (out.obs && !src.obs_steps) return fail(CCX_EINVAL, "%s: an obs output needs obs_steps", who);
     const bool pair = (h->N % 2) == 0;
     if (misaligned(16, compact ? src.obs0 : nullptr, compact ? src.obs_steps : nullptr))
@@ -229,9 +215,8 @@ int gather(const char* who, ccx_handle* h, int64_t K, int32_t compact, const MbS
     CCX_HIP(hipSetDevice(h->device));
     const ccx::LaunchShape& ls = h->shape;
     const ccx::KParams& p = h->kp;
-    const int64_t per_block = (int64_t)p.EW * p.waves_per_block;
-    const int64_t blocks = (B + per_block - 1) / per_block;
-    if (blocks > 0x7FFFFFFFll) return fail(CCX_EINVAL, "%s: batch = %lld needs too many workgroups", who, (long long)B);
+    dim3 grid, block;
+    if (int rc = ccxi::gather_grid(who, h, B, grid, block)) return rc;
     MbArgs A{};
     A.s = src;
     A.o = out;
@@ -247,7 +232,7 @@ int gather(const char* who, ccx_handle* h, int64_t K, int32_t compact, const MbS
     const bool rows = !compact && out.obs;
     const unsigned units_per_wave = ((unsigned)p.EW * (unsigned)h->N * (3u + 2u * (unsigned)h->N)) >> (pair ? 1 : 0);
     const unsigned chunks = rows ? (units_per_wave + 64u * kUnits - 1u) / (64u * kUnits) : 1u;      // at most 17 (64 lanes x 131 units)
-    const dim3 grid((unsigned)blocks, chunks), block(64 * ls.waves_per_block);
+    grid.y = chunks;
     with_flags([&](auto drw, auto cmp, auto pr) {
         hipLaunchKernelGGL((minibatch_gather_kernel<decltype(drw)::value, decltype(cmp)::value, decltype(pr)::value>), grid, block,
                            decltype(cmp)::value ? ls.lds_bytes_observe : 0, h->stream, p, A);
@@ -287,8 +272,7 @@ int ccx_minibatch_permutation(ccx_handle* h, int64_t M, int64_t epoch, int64_t* 
         return fail(CCX_EINVAL, "ccx_minibatch_permutation: M = %lld out of range (1 <= M < 2^31)", (long long)M);
     if (misaligned(8, out)) return fail(CCX_EINVAL, "ccx_minibatch_permutation: out must be 8-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
-    const unsigned blocks = (unsigned)((M + 255) / 256);                  // below 2^23
-    hipLaunchKernelGGL(minibatch_perm_kernel, dim3(blocks), dim3(256), 0, h->stream, reinterpret_cast<long long*>(out), (uint32_t)M,
+    hipLaunchKernelGGL(minibatch_perm_kernel, dim3(ccxi::blocks_of(M)), dim3(256), 0, h->stream, reinterpret_cast<long long*>(out), (uint32_t)M,
                        ccx_minibatch::split_of((uint32_t)M), (unsigned long long)epoch, h->rng_lo, h->rng_hi);
     CCX_HIP(hipGetLastError());
     return CCX_OK;

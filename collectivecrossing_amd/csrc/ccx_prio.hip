@@ -14,8 +14,10 @@
 // prio_draw_kernel: one lane per draw: the two words, the point, the descent, the weight.
 // prio_count_kernel: one plain lane adds 1 to draws BEHIND the draw that read it.
 #include "ccx_internal.h"
+#include "ccx_nstep.h"   // pushed_at: the head the ring's push read
 #include "ccx_prio.h"
 
+using ccxi::blocks_of;
 using ccxi::fail;
 using ccxi::misaligned;
 
@@ -31,8 +33,7 @@ __global__ __launch_bounds__(256) void prio_set_kernel(int* leaf, const long lon
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= total) return;
     const long long s = t / E, e = t - s * E;
-    long long head = ring_state[0] - K;                                   // the head the ring's push read: it has advanced by K since
-    head = head < 0 ? 0 : head;                                           // (a caller that pushed nothing: stay inside the ring)
+    const long long head = ccx_nstep::pushed_at(ring_state[0], K);        // the head the ring's push read: it has advanced by K since
     leaf[ccx_replay::slot_of(head, s, S, E, e)] = (int)pstate[0];
 }
 
@@ -165,17 +166,13 @@ __global__ __launch_bounds__(64) void prio_count_kernel(long long* pstate) {
 
 // what every entry takes: the handle, the ring's S, the leaves and pstate
 int check_prio(const char* who, const ccx_handle* h, int64_t ring_steps, const int32_t* leaf, const int64_t* pstate, int64_t& R) {
-    if (!h) return fail(CCX_EINVAL, "NULL handle");
+    if (int rc = ccxi::check_ring_steps(who, h, ring_steps)) return rc;
     if (!leaf || !pstate) return fail(CCX_EINVAL, "%s: NULL leaf or pstate", who);
-    if (ring_steps < 1 || ring_steps >= (1ll << 31) || ring_steps * (int64_t)h->E >= (1ll << 31))
-        return fail(CCX_EINVAL, "%s: ring_steps = %lld out of range (1 <= S, S * E < 2^31)", who, (long long)ring_steps);
     if (misaligned(4, leaf)) return fail(CCX_EINVAL, "%s: leaf must be 4-byte aligned", who);
     if (misaligned(8, pstate)) return fail(CCX_EINVAL, "%s: pstate must be 8-byte aligned", who);
     R = ring_steps * (int64_t)h->E;
     return CCX_OK;
 }
-
-unsigned blocks_of(int64_t n) { return (unsigned)((n + 255) / 256); }     // n < 2^31
 
 }  // namespace
 
@@ -204,8 +201,7 @@ int ccx_prio_update(ccx_handle* h, int64_t ring_steps, int32_t* leaf, int64_t* p
     int64_t R = 0;
     if (int rc = check_prio("ccx_prio_update", h, ring_steps, leaf, pstate, R)) return rc;
     if (!index || !td_error) return fail(CCX_EINVAL, "ccx_prio_update: NULL index or td_error");
-    if (batch < 1 || batch * (int64_t)h->N > (1ll << 31))
-        return fail(CCX_EINVAL, "ccx_prio_update: batch = %lld out of range (1 <= B <= 2^31 / N)", (long long)batch);
+    if (int rc = ccxi::check_batch_size("ccx_prio_update", h, batch)) return rc;
     if (num_td < 1 || num_td > ccx_prio::kMaxTd)
         return fail(CCX_EINVAL, "ccx_prio_update: num_td = %d out of range (1 .. %d)", (int)num_td, ccx_prio::kMaxTd);
     if (!(alpha >= 0.0f && alpha <= 1.0f)) return fail(CCX_EINVAL, "ccx_prio_update: alpha must lie in [0, 1]");

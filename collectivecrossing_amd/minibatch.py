@@ -15,7 +15,7 @@ from dataclasses import dataclass
 import torch
 
 from .learner import _OPT, _require_all, _require_out
-from .replay import _check_batch_size
+from .replay import _check_batch_size, _check_index
 
 EMPTY_ACTION, EMPTY_MASKS = 255, 0x10                                    # the EMPTY row's two bytes that are not zero
 _SOURCES = ("obs0", "obs", "actions", "logp", "advantages", "returns", "masks", "valid")
@@ -163,9 +163,7 @@ class RolloutMinibatches:
         Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         b = self.batch
         args = self._args()
-        B = int(index.shape[0]) if isinstance(index, torch.Tensor) and index.dim() == 1 else 0
-        _require_all(b.device, ("index", index, torch.int64, (max(B, 1),)))
-        B = _check_batch_size(B, b.num_agents)
+        B = _check_index(b.device, index, b.num_agents)
         out = self._out(B, out)
         b._enqueue(b._lib.ccx_minibatch_fetch, *args, B, index, *self._out_args(out))
         return out

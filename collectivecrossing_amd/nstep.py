@@ -11,12 +11,12 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
-import numpy as np
 import torch
 
 from ._abi import NSTEP_MAX
 from .learner import _OPT, _require_all, _require_out
-from .replay import ReplayBatch, ReplayRing, _check_batch_size
+from .qlearn import _check_gamma
+from .replay import ReplayBatch, ReplayRing, _check_batch_size, _check_index
 
 
 @dataclass
@@ -40,16 +40,6 @@ def _check_n(n, steps: int) -> int:
     if not ok:
         raise ValueError(f"n must be an integer in 1 .. min(steps, {NSTEP_MAX}) = {min(int(steps), NSTEP_MAX)}, got {n!r}")
     return int(n)
-
-
-def _check_gamma(gamma) -> float:
-    try:
-        gamma = float(np.float32(gamma))
-    except (TypeError, ValueError):
-        raise ValueError("gamma must be a number") from None
-    if not 0.0 <= gamma <= 1.0:                                          # (false for NaN)
-        raise ValueError(f"gamma must be in [0, 1], got {gamma!r}")
-    return gamma
 
 
 class NStepReplay:
@@ -154,9 +144,7 @@ class NStepReplay:
         An index outside ``[0, records)`` gives the EMPTY record with ``discount`` = ``gamma`` and ``span`` 1.
         Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         b = self.batch
-        B = int(index.shape[0]) if isinstance(index, torch.Tensor) and index.dim() == 1 else 0
-        _require_all(b.device, ("index", index, torch.int64, (max(B, 1),)))
-        B = _check_batch_size(B, b.num_agents)
+        B = _check_index(b.device, index, b.num_agents)
         out = self._out(B, out, want_obs, want_next_obs)
         b._enqueue(b._lib.ccx_nstep_fetch, *self._window_args(), B, index, *ReplayRing._out_args(out.batch), out.discount,
                    out.span)

@@ -17,7 +17,7 @@ import torch
 from ._abi import PRIO_MAX_TD
 from .learner import _require_all, _require_out
 from .nstep import NStepBatch, NStepReplay
-from .replay import ReplayBatch, ReplayRing, _check_batch_size
+from .replay import ReplayBatch, ReplayRing, _check_batch_size, _check_index
 
 ONE = 65536                                                              # 1.0 in fixed point: 16 fractional bits
 
@@ -128,10 +128,8 @@ class PrioritizedReplay:
         tds = (td_error,) if isinstance(td_error, torch.Tensor) else tuple(td_error) if isinstance(td_error, (tuple, list)) else ()
         if not 1 <= len(tds) <= PRIO_MAX_TD:
             raise ValueError(f"td_error must be a tensor or a tuple of 1 .. {PRIO_MAX_TD} tensors")
-        B = int(index.shape[0]) if isinstance(index, torch.Tensor) and index.dim() == 1 else 0
-        _require_all(b.device, ("index", index, torch.int64, (max(B, 1),)),
-                     *((f"td_error[{a}]", t, torch.float32, (max(B, 1), b.num_agents)) for a, t in enumerate(tds)))
-        B = _check_batch_size(B, b.num_agents)
+        B = _check_index(b.device, index, b.num_agents,
+                         lambda B: ((f"td_error[{a}]", t, torch.float32, (B, b.num_agents)) for a, t in enumerate(tds)))
         table = (C.c_void_p * len(tds))(*(t.data_ptr() for t in tds))
         b._enqueue(b._lib.ccx_prio_update, self.ring.steps, self.leaf, self.pstate, B, index, len(tds), table, alpha, eps, also=tds)
 

@@ -51,18 +51,29 @@ class TdLossResult:
     bad = property(lambda self: self.stats[7])
 
 
+def _check_gamma(gamma, not_a_number: str = "gamma must be a number") -> float:
+    """``gamma`` as the f32 value the library will see, or ``ValueError``: a number in [0, 1]."""
+    try:
+        gamma = float(np.float32(gamma))
+    except (TypeError, ValueError):
+        raise ValueError(not_a_number) from None
+    if not 0.0 <= gamma <= 1.0:                                          # (false for NaN)
+        raise ValueError(f"gamma must be in [0, 1], got {gamma!r}")
+    return gamma
+
+
 def _check_td_hyper(gamma, huber_delta, discount=None):
     """The two hyper-parameters as the f32 values the library will see, or ``ValueError``.  ``gamma`` is 0.99 where neither
     it nor ``discount`` is given; with ``discount`` it is not read, and giving both is refused."""
     if discount is not None and gamma is not None:
         raise ValueError("give gamma or discount, not both (with discount= every row brings its own)")
     gamma = 0.99 if gamma is None or discount is not None else gamma
+    numbers = "gamma and huber_delta must be numbers"
     try:
-        gamma, huber_delta = float(np.float32(gamma)), float(np.float32(huber_delta))
+        huber_delta = float(np.float32(huber_delta))
     except (TypeError, ValueError):
-        raise ValueError("gamma and huber_delta must be numbers") from None
-    if not 0.0 <= gamma <= 1.0:                                          # (false for NaN)
-        raise ValueError(f"gamma must be in [0, 1], got {gamma!r}")
+        raise ValueError(numbers) from None
+    gamma = _check_gamma(gamma, numbers)
     if not huber_delta > 0.0:
         raise ValueError(f"huber_delta must be > 0 (inf: the squared error), got {huber_delta!r}")
     return gamma, huber_delta

@@ -59,6 +59,14 @@ def _check_batch_size(B, num_agents: int) -> int:
     return int(B)
 
 
+def _check_index(device, index, num_agents: int, rows=lambda B: ()) -> int:
+    """``B`` of the caller's record indices, int64 [B] on ``device``, or ``ValueError``; ``rows(B)`` are further rows of the
+    same ``_require_all`` whose shapes follow B."""
+    B = int(index.shape[0]) if isinstance(index, torch.Tensor) and index.dim() == 1 else 0
+    _require_all(device, ("index", index, torch.int64, (max(B, 1),)), *rows(max(B, 1)))
+    return _check_batch_size(B, num_agents)
+
+
 class ReplayRing:
     """``ReplayRing(batch, steps=S)``: S ring steps of the batch's E envs, ``R = S * E`` records of ``44 N`` bytes each (the
     same env-step as two rows per agent takes ``N (2 (24 + 16 N) + 12)``: 7 times as much at N = 8, 25 times at N = 32).
@@ -228,9 +236,7 @@ class ReplayRing:
         receives a copy of ``index`` (it may be the same tensor).
         Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         b = self.batch
-        B = int(index.shape[0]) if isinstance(index, torch.Tensor) and index.dim() == 1 else 0
-        _require_all(b.device, ("index", index, torch.int64, (max(B, 1),)))
-        B = _check_batch_size(B, b.num_agents)
+        B = _check_index(b.device, index, b.num_agents)
         out = self._out(B, out, want_obs, want_next_obs)
         b._enqueue(b._lib.ccx_replay_fetch, *self._ring_args(), B, index, *self._out_args(out))
         return out

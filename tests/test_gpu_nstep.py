@@ -163,6 +163,24 @@ def test_sample_names_the_records_the_ring_names(world):
         assert ns.ring.state.tolist() == [int(spec["state"][0]), d + 1, 0, 0]
 
 
+def test_absent_row_outputs_leave_the_other_arrays_their_bits(world):
+    """Every array still present has the bits of the full fetch, whichever of the two row outputs is left out: a lone record
+    in a wave (B = 1), and several waves with a one-record tail (B = 65 = 4 * 16 + 1 = 8 * 8 + 1), records outside the ring
+    among them."""
+    import torch
+
+    ns = world.ns
+    assert len(INDEX[-65:]) == 65 and (65 % world.per_wave == 1 or world.per_wave == 1)
+    for idx in (INDEX[77:78], INDEX[-65:]):
+        index = torch.from_numpy(idx).cuda()
+        full = nbatch_np(ns.fetch(index))
+        assert full["obs"] is not None and full["next_obs"] is not None
+        for want_obs, want_next in ((False, True), (True, False), (False, False)):
+            mb = ns.fetch(index, want_obs=want_obs, want_next_obs=want_next)
+            assert (mb.batch.obs is None) == (not want_obs) and (mb.batch.next_obs is None) == (not want_next)
+            check(nbatch_np(mb), full, f"B {len(idx)} want_obs {want_obs} want_next_obs {want_next}:")
+
+
 # ------------------------------------------------------------------------------------------------- (d) a manual cut
 def test_mark_cut_equals_the_spec(world):
     import torch
