@@ -13,11 +13,12 @@ stream-order table of the batch's classes (tests/_stream_order.py) is closed, an
 from __future__ import annotations
 
 from dataclasses import dataclass
+from typing import ClassVar
 
 import numpy as np
 import torch
 
-from .learner import _OPT, _require_all, _require_out
+from .learner import _OPT, _alloc_loss, _check_grad_loss, _loss_over_rows, _loss_workspace, _new_stats, _require_all
 from .qlearn import _check_td_hyper
 
 MIN_ATOMS, MAX_ATOMS = 2, 64
@@ -35,6 +36,7 @@ class CategoricalLossResult:
     proj: torch.Tensor | None = None          # f32 [..., A]: the projected target distribution; +0.0 at rows that do not count
     workspace: torch.Tensor | None = None     # u8 [ccx_c51_workspace_bytes(rows)]
     grad_logits: torch.Tensor | None = None   # f32 [..., 5, A]
+    _frame: ClassVar = ("ccx_c51_workspace_bytes", "alloc_loss", "logits requires")   # (learner._loss_over_rows)
 
     mean_ce = property(lambda self: self.stats[1])
     mean_q = property(lambda self: self.stats[2])
@@ -94,19 +96,16 @@ class CategoricalQ:
 
     # ------------------------------------------------------------------ the loss over the rows that count
     def _workspace_arg(self, workspace, rows: int) -> torch.Tensor:
-        b = self.batch
-        return b._workspace_arg(int(b._lib.ccx_c51_workspace_bytes(int(rows))), workspace, "alloc_loss")
+        return _loss_workspace(self.batch, CategoricalLossResult, workspace, rows)
 
     def alloc_loss(self, shape, want_row_loss: bool = True) -> CategoricalLossResult:
         """Static buffers of :meth:`loss` / :meth:`loss_backward` for rows of the leading shape ``shape``: stats, the
         workspace, ``row_loss`` if asked for, ``proj`` and ``grad_logits`` (for a captured graph)."""
         b = self.batch
-        shape = tuple(int(x) for x in shape)
-        rows = int(np.prod(shape)) if shape else 1
-        stats = torch.zeros((8,), dtype=torch.float32, device=b.device)
+        shape, stats, workspace = _alloc_loss(b, CategoricalLossResult, shape)
         f = torch.float32
         return CategoricalLossResult(stats[0], stats, b._new(shape, f) if want_row_loss else None, b._new(shape + (self.atoms,), f),
-                                     self._workspace_arg(None, rows), b._new(shape + (5, self.atoms), f))
+                                     workspace, b._new(shape + (5, self.atoms), f))
 
     def _check_loss(self, logits, actions, reward, done, next_target, next_online, masks_next, valid, weights, discount, extra=()):
         """The input checks of :meth:`loss`; returns the leading shape."""
@@ -167,35 +166,10 @@ class CategoricalQ:
         b = self.batch
         gamma = _check_td_hyper(gamma, 1.0, discount)[0]
         lead = self._check_loss(logits, actions, reward, done, next_target, next_online, masks_next, valid, weights, discount)
-        f = torch.float32
-        if logits.requires_grad and torch.is_grad_enabled():
-            if out is not None:
-                raise ValueError("out= cannot be used when logits requires a gradient (the autograd path allocates its outputs)")
-            if logits.numel() == 0:
-                stats = torch.cat([logits.sum().reshape(1) * 0.0, torch.zeros(7, device=b.device)])
-                return CategoricalLossResult(stats[0], stats.detach(), logits.new_zeros(lead) if want_row_loss else None,
-                                             logits.new_zeros(lead + (self.atoms,)))
-            row_loss = b._new(lead, f) if want_row_loss else None
-            proj = b._new(lead + (self.atoms,), f)
-            stats = _CategoricalLoss.apply(self, logits, actions, reward, done, next_target, next_online, masks_next, valid, weights,
-                                           discount, gamma, row_loss, proj)
-            return CategoricalLossResult(stats[0], stats.detach(), row_loss, proj)
-        _require_out(out, CategoricalLossResult, "alloc_loss")
-        if out is None:
-            stats = torch.zeros((8,), dtype=f, device=b.device)
-            out = CategoricalLossResult(stats[0], stats, b._new(lead, f) if want_row_loss else None, b._new(lead + (self.atoms,), f))
-            workspace = None
-        else:
-            _require_all(b.device, ("out.stats", out.stats, f, (8,)), ("out.row_loss", out.row_loss, f, lead, {"optional": True, "align": 4}),
-                         ("out.proj", out.proj, f, lead + (self.atoms,), {"align": 4}))
-            workspace = out.workspace
-        if logits.numel() == 0:
-            out.stats.zero_()
-            return out
-        workspace = self._workspace_arg(workspace, actions.numel())
-        self._forward(logits.detach(), actions, reward, done, next_target, next_online, masks_next, valid, weights, discount, gamma,
-                      workspace, out.stats, out.row_loss, out.proj)
-        return out
+        extras = (("row_loss", lead, want_row_loss, {"optional": True, "align": 4}), ("proj", lead + (self.atoms,), True, {"align": 4}))
+        return _loss_over_rows(b, CategoricalLossResult, self, _CategoricalLoss, self._forward, (logits,),
+                               (actions, reward, done, next_target, next_online, masks_next, valid, weights, discount, gamma),
+                               actions.numel(), extras, out)
 
     def loss_backward(self, logits: torch.Tensor, actions: torch.Tensor, proj: torch.Tensor, valid: torch.Tensor | None = None,
                       weights: torch.Tensor | None = None, *, stats: torch.Tensor, grad_loss: torch.Tensor | None = None,
@@ -218,10 +192,7 @@ class CategoricalQ:
                      ("proj", proj, f, lead + (A,), {"align": 4}), ("valid", valid, u8, lead, _OPT),
                      ("weights", weights, f, lead, {"optional": True, "align": 4}), ("stats", stats, f, (8,)),
                      ("out", out, f, lead + (5, A), {"align": 4}))
-        if grad_loss is not None:                                        # (inline: one element in either of two shapes)
-            if (not isinstance(grad_loss, torch.Tensor) or grad_loss.dtype is not f or grad_loss.device != b.device
-                    or grad_loss.numel() < 1 or grad_loss.dim() > 1 or not grad_loss.is_contiguous()):
-                raise ValueError(f"grad_loss must be a torch.float32 tensor with one element (0-dim or [1]) on {b.device}")
+        _check_grad_loss(grad_loss, b.device)
         if logits.numel():
             b._enqueue(b._lib.ccx_c51_loss_backward, actions.numel(), A, logits.detach(), actions, proj.detach(), valid, weights, stats,
                        grad_loss, out)
@@ -236,7 +207,7 @@ class _CategoricalLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, cq, logits, actions, reward, done, nt, no, masks_next, valid, weights, discount, gamma, row_loss, proj):
         logits = logits.detach()
-        stats = torch.zeros((8,), dtype=torch.float32, device=cq.batch.device)
+        stats = _new_stats(cq.batch.device)
         cq._forward(logits, actions, reward, done, nt, no, masks_next, valid, weights, discount, gamma,
                     cq._workspace_arg(None, actions.numel()), stats, row_loss, proj)
         ctx.cq = cq

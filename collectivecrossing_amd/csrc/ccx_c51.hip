@@ -1,7 +1,8 @@
 // ccx_c51.hip -- CCX_C51 (include/ccx.h): categorical Q-heads.  Expected values of a [M][5][A] array of logits, the projected
 // target with the cross-entropy loss, its means over the rows that count, and the gradient with respect to the logits.  The
 // per-place rules and the wave sums are ccx_c51.h; greedy, the counting rule and the final values are ccx_qlearn.h's; the
-// f64 tree is ccx_tree.h's.
+// f64 tree is ccx_tree.h's; a row's gate, the selection into the sums, the final kernel's body, the backward's scale and the
+// forward entry are ccx_loss.h's (the frame of a loss over the rows that count).
 //
 // Everywhere a lane owns an atom and a wave works on one row at a time; a row of A floats is one coalesced run, and f32
 // alignment is all that is asked (A = 51 gives 204-byte rows).
@@ -13,9 +14,9 @@
 // reads no logits.  The projection is a gather: lane i walks j = 0 .. A - 1 with p_j and b_j broadcast from lane j, so the
 // additions of m_i stand in ascending j without an atomic.  Lane 0 leaves the row's four f32 terms in LDS; behind a barrier
 // thread t < 256 owns row t as the tree wants it, and ccx_tree::block_sums_wide writes the block's partials ([6][B] f64).
-// ONE wave then adds the partials and writes `stats`.  Two plain launches: no atomic, no last-block-done counter.
+// ONE wave then adds the partials and writes `stats`.
 // c51_bwd_kernel: a workgroup of four waves, one row each; every element of the row's 5 A gradients is written.
-#include "ccx_internal.h"
+#include "ccx_loss.h"
 
 #include "ccx_c51.h"
 
@@ -82,14 +83,13 @@ __global__ __launch_bounds__(64 * kLossWaves) void c51_partial_kernel(const CatA
     const bool live = lane < (uint32_t)At;
     const float z = ccx_c51::atom_value(A.Z.vmin, A.Z.dz, (int)lane);
     const float fi = (float)lane;
-    const bool has_valid = A.valid != nullptr, has_w = A.weights != nullptr;
+    const bool has_w = A.weights != nullptr;
     const long long base = (long long)blockIdx.x * ccx_tree::kBlockRows;
     for (uint32_t rloc = w; rloc < (uint32_t)ccx_tree::kBlockRows; rloc += kLossWaves) {
         const long long row = base + rloc;
         if (row >= A.M) break;                                            // (wave-uniform: the rows of a wave ascend)
-        const uint32_t a = A.actions[row];
-        const uint32_t vbyte = has_valid ? (uint32_t)A.valid[row] : 1u;
-        if (!ccx_qlearn::row_counts(has_valid, vbyte, a)) {               // wave-uniform: nothing of the row is read
+        const ccx_loss::Gate G = ccx_loss::gate_of(A.actions, A.valid, row);
+        if (!ccx_qlearn::row_counts(G.has_valid, G.vbyte, G.a)) {         // wave-uniform: nothing of the row is read
             if (live) A.proj[row * At + lane] = 0.0f;
             if (lane == 0u && A.row_loss) A.row_loss[row] = 0.0f;
             continue;
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(64 * kLossWaves) void c51_partial_kernel(const CatA
         const float bj = ccx_c51::target_place(r, disc, cut, z, A.Z.vmin, A.Z.dz, A.Z.top);
         float m = 0.0f;
         for (int j = 0; j < At; ++j) m = ccx_c51::project_add(m, lane_value(pj, j), lane_value(bj, j), fi);
-        const ccx_c51::Dist D = ccx_c51::wave_dist(A.logits + (row * 5 + a) * At, lane, At);
+        const ccx_c51::Dist D = ccx_c51::wave_dist(A.logits + (row * 5 + G.a) * At, lane, At);
         const float lS = ccx_c51::log_sum(D.S);
         const float ce = ccx_c51::ce_of(ccx_c51::wave_sum(ccx_c51::ce_place(m, D.d, lS, live)));
         const float qa = ccx_c51::wave_expected(D, z, live);
@@ -140,36 +140,23 @@ __global__ __launch_bounds__(64 * kLossWaves) void c51_partial_kernel(const CatA
         }
     }
     __syncthreads();
-    // thread t < 256 owns row t of the block; rows that do not count and rows >= M enter as +0.0, selected (what LDS holds
-    // for them was never written)
+    // thread t < 256 owns row t of the block (what LDS holds for a row that does not count was never written: selected away)
     double s[ccx_c51::kSums] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (threadIdx.x < (uint32_t)ccx_tree::kBlockRows) {
         const long long row = base + threadIdx.x;
-        const long long rl = row < A.M ? row : A.M - 1;
-        const uint32_t a = A.actions[rl];
-        const uint32_t vbyte = has_valid ? (uint32_t)A.valid[rl] : 1u;
-        const bool counts = row < A.M && ccx_qlearn::row_counts(has_valid, vbyte, a);
-        const bool bad = row < A.M && ccx_qlearn::row_bad(has_valid, vbyte, a);
-        const float t0 = terms[0][threadIdx.x], t1 = terms[1][threadIdx.x], t2 = terms[2][threadIdx.x], t3 = terms[3][threadIdx.x];
-        s[0] = counts ? 1.0 : 0.0;
-        s[1] = counts ? (double)t0 : 0.0;
-        s[2] = counts ? (double)t1 : 0.0;
-        s[3] = counts ? (double)t2 : 0.0;
-        s[4] = counts ? (double)t3 : 0.0;
+        const ccx_loss::Gate G = ccx_loss::gate_of(A.actions, A.valid, row < A.M ? row : A.M - 1);
+        const bool counts = row < A.M && ccx_qlearn::row_counts(G.has_valid, G.vbyte, G.a);
+        const bool bad = row < A.M && ccx_qlearn::row_bad(G.has_valid, G.vbyte, G.a);
+        const float t[4] = {terms[0][threadIdx.x], terms[1][threadIdx.x], terms[2][threadIdx.x], terms[3][threadIdx.x]};
+        ccx_loss::select_sums(counts, t, s);
         s[5] = bad ? 1.0 : 0.0;
     }
     ccx_tree::block_sums_wide(s, groups, A.partials, A.B);
 }
 
 __global__ __launch_bounds__(64) void c51_final_kernel(const CatArgs A) {
-    double s[ccx_c51::kSums];
-    ccx_tree::final_sums(A.partials, A.B, s);
-    if (threadIdx.x == 0u) {
-        float st[8];
-        ccx_qlearn::td_finals(s, st);                                     // {S_term/n, S_ce/n, S_qa/n, S_y/n, 0, 0, n, bad}
-#pragma unroll
-        for (int k = 0; k < 8; ++k) A.stats[k] = st[k];
-    }
+    // {S_term/n, S_ce/n, S_qa/n, S_y/n, 0, 0, n, bad}
+    ccx_loss::final_body<ccx_c51::kSums, 8>(A.partials, A.B, A.stats, [](const auto& s, auto& st) { ccx_qlearn::td_finals(s, st); });
 }
 
 __global__ __launch_bounds__(64 * kRowWaves) void c51_bwd_kernel(const CatArgs A) {
@@ -178,17 +165,14 @@ __global__ __launch_bounds__(64 * kRowWaves) void c51_bwd_kernel(const CatArgs A
     if (row >= A.M) return;
     const int At = A.Z.A;
     const bool live = lane < (uint32_t)At;
-    const bool has_valid = A.valid != nullptr, has_w = A.weights != nullptr;
-    const uint32_t a = A.actions[row];
-    const uint32_t vbyte = has_valid ? (uint32_t)A.valid[row] : 1u;
-    const float n = A.stats_in[6];
-    const bool counts = n != 0.0f && ccx_qlearn::row_counts(has_valid, vbyte, a);   // n == 0: every gradient +0.0f, selected
+    const bool has_w = A.weights != nullptr;
+    const ccx_loss::Gate G = ccx_loss::gate_of(A.actions, A.valid, row);
+    const bool counts = ccx_loss::any_counted(A.stats_in) && ccx_qlearn::row_counts(G.has_valid, G.vbyte, G.a);
     float g = 0.0f;
     if (counts) {                                                         // wave-uniform: a row that does not count reads nothing
-        const float gl = A.grad_loss ? A.grad_loss[0] : 1.0f;
-        const float sc = gl / n;
+        const float sc = ccx_loss::scale_of(A.stats_in, A.grad_loss).sc;
         const float gw = ccx_qlearn::row_scale(has_w, sc, has_w ? A.weights[row] : 1.0f);
-        const ccx_c51::Dist D = ccx_c51::wave_dist(A.logits + (row * 5 + a) * At, lane, At);
+        const ccx_c51::Dist D = ccx_c51::wave_dist(A.logits + (row * 5 + G.a) * At, lane, At);
         float m = 0.0f;
         if (live) m = A.proj_in[row * At + lane];
         const float Msum = ccx_c51::wave_sum(ccx_c51::live_or_zero(m, live));
@@ -196,7 +180,7 @@ __global__ __launch_bounds__(64 * kRowWaves) void c51_bwd_kernel(const CatArgs A
     }
     if (live) {
 #pragma unroll
-        for (uint32_t k = 0; k < 5u; ++k) A.grad_logits[(row * 5 + k) * At + lane] = (counts && a == k) ? g : 0.0f;
+        for (uint32_t k = 0; k < 5u; ++k) A.grad_logits[(row * 5 + k) * At + lane] = (counts && G.a == k) ? g : 0.0f;
     }
 }
 
@@ -214,10 +198,7 @@ int check_support(const char* who, int32_t atoms, float vmin, float vmax) {
 
 extern "C" {
 
-int64_t ccx_c51_workspace_bytes(int64_t rows) {
-    if (rows < 1) return 0;
-    return (int64_t)ccx_tree::blocks_of(rows) * ccx_c51::kSums * (int64_t)sizeof(double);
-}
+int64_t ccx_c51_workspace_bytes(int64_t rows) { return ccx_loss::workspace_bytes(rows, ccx_c51::kSums); }
 
 int ccx_c51_q_values(ccx_handle* h, int64_t rows, int32_t atoms, float vmin, float vmax, const float* logits, float* q) {
     const char* who = "ccx_c51_q_values";
@@ -244,43 +225,41 @@ int ccx_c51_loss(ccx_handle* h, int64_t rows, int32_t atoms, float vmin, float v
                  const uint8_t* masks_next_or_null, const uint8_t* valid_or_null, const float* weights_or_null,
                  const float* discount_or_null, float gamma, void* workspace, float* stats, float* row_loss_or_null, float* proj) {
     const char* who = "ccx_c51_loss";
-    if (!h) return fail(CCX_EINVAL, "NULL handle");
-    if (!logits || !actions || !reward || !done || !next_target || !workspace || !stats || !proj)
-        return fail(CCX_EINVAL, "%s: NULL argument (only next_online, masks_next, valid, weights, discount and row_loss may be NULL)", who);
-    unsigned blocks = 0;
-    if (int rc = ccxi::row_blocks(who, rows, ccx_tree::kBlockRows, blocks)) return rc;
-    if (int rc = check_support(who, atoms, vmin, vmax)) return rc;
-    if (!discount_or_null && !(gamma >= 0.0f && gamma <= 1.0f))
-        return fail(CCX_EINVAL, "%s: gamma must be finite and lie in [0, 1], got %g", who, (double)gamma);
-    if (misaligned(4, logits, next_target, next_online_or_null, weights_or_null, discount_or_null, stats, row_loss_or_null, proj))
-        return fail(CCX_EINVAL, "%s: the f32 arrays must be 4-byte aligned", who);
-    if (misaligned(8, reward, workspace)) return fail(CCX_EINVAL, "%s: reward and workspace must be 8-byte aligned", who);
-    CCX_HIP(hipSetDevice(h->device));
-    CatArgs A{};
-    A.logits = logits;
-    A.next_target = next_target;
-    A.next_online = next_online_or_null;
-    A.actions = actions;
-    A.reward = reward;
-    A.done = done;
-    A.masks_next = masks_next_or_null;
-    A.valid = valid_or_null;
-    A.weights = weights_or_null;
-    A.discount = discount_or_null;
-    A.gamma = discount_or_null ? 0.0f : gamma;
-    A.partials = static_cast<double*>(workspace);
-    A.stats = stats;
-    A.row_loss = row_loss_or_null;
-    A.proj = proj;
-    A.Z = ccx_c51::support_of(atoms, vmin, vmax);
-    A.M = rows;
-    A.B = blocks;
-    const dim3 grid(blocks), block(64 * kLossWaves);
-    if (next_online_or_null) hipLaunchKernelGGL((c51_partial_kernel<true>), grid, block, 0, h->stream, A);
-    else hipLaunchKernelGGL((c51_partial_kernel<false>), grid, block, 0, h->stream, A);
-    hipLaunchKernelGGL(c51_final_kernel, dim3(1), dim3(64), 0, h->stream, A);
-    CCX_HIP(hipGetLastError());
-    return CCX_OK;
+    return ccx_loss::forward(who, h, logits && actions && reward && done && next_target && workspace && stats && proj,
+                             "only next_online, masks_next, valid, weights, discount and row_loss may be NULL", rows, workspace, [&] {
+        if (int rc = check_support(who, atoms, vmin, vmax)) return rc;
+        if (!discount_or_null)
+            if (int rc = ccx_loss::check_gamma(who, gamma)) return rc;
+        if (misaligned(4, logits, next_target, next_online_or_null, weights_or_null, discount_or_null, stats, row_loss_or_null, proj))
+            return fail(CCX_EINVAL, "%s: the f32 arrays must be 4-byte aligned", who);
+        // (the workspace is named with the reward here: the frame's own refusal behind this one finds nothing left)
+        if (misaligned(8, reward, workspace)) return fail(CCX_EINVAL, "%s: reward and workspace must be 8-byte aligned", who);
+        return (int)CCX_OK;
+    }, ccx_loss::no_check, [&](double* partials, unsigned blocks) {
+        CatArgs A{};
+        A.logits = logits;
+        A.next_target = next_target;
+        A.next_online = next_online_or_null;
+        A.actions = actions;
+        A.reward = reward;
+        A.done = done;
+        A.masks_next = masks_next_or_null;
+        A.valid = valid_or_null;
+        A.weights = weights_or_null;
+        A.discount = discount_or_null;
+        A.gamma = discount_or_null ? 0.0f : gamma;
+        A.partials = partials;
+        A.stats = stats;
+        A.row_loss = row_loss_or_null;
+        A.proj = proj;
+        A.Z = ccx_c51::support_of(atoms, vmin, vmax);
+        A.M = rows;
+        A.B = blocks;
+        const dim3 grid(blocks), block(64 * kLossWaves);
+        if (next_online_or_null) hipLaunchKernelGGL((c51_partial_kernel<true>), grid, block, 0, h->stream, A);
+        else hipLaunchKernelGGL((c51_partial_kernel<false>), grid, block, 0, h->stream, A);
+        return A;
+    }, c51_final_kernel);
 }
 
 int ccx_c51_loss_backward(ccx_handle* h, int64_t rows, int32_t atoms, const float* logits, const uint8_t* actions, const float* proj,

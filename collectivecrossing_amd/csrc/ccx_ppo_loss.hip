@@ -1,8 +1,9 @@
 // ccx_ppo_loss.hip -- CCX_PPO_LOSS (include/ccx.h): the clipped-surrogate PPO loss over the rows that count, its statistics
 // and its gradient with respect to logits and values, plus the masked moments that normalise the advantages.  The per-row
 // rule and the final values are ccx_ppo.h (which calls ccx_softmax.h's evaluate_row*), the reduction tree is ccx_tree.h; the
-// logits travel through LDS by ccx_rows.h.  `valid` is a selection inside the kernels: shapes stay static, nothing is
-// compacted, nothing synchronises with the host.
+// logits travel through LDS by ccx_rows.h.  What stands around the rule -- a row's gate, the selection into the sums, the
+// final kernel's body, the backward's scale, the forward entry -- is ccx_loss.h's, shared with ccx_qlearn.hip and ccx_c51.hip.
+// `valid` is a selection inside the kernels: shapes stay static, nothing is compacted, nothing synchronises with the host.
 //
 // Forward: two launches.  ppo_partial_kernel: a workgroup of four waves takes 256 consecutive rows, one lane one row; each
 // wave reduces its 64 rows' six f64 terms by a butterfly (a group of the tree), lane 0 leaves them in LDS, and the first six
@@ -11,8 +12,9 @@
 // last-block-done counter: a kernel boundary orders the partials, and two plain launches cannot hang.
 // Backward: one launch, ppo_bwd_kernel, one lane one row, a workgroup is one wave (ccx_evaluate.hip's shape); it recomputes
 // the forward terms from the inputs and reads nothing else but `stats`.
-// The masked moments: moments_partial_kernel / moments_final_kernel, the same tree over three sums.
-#include "ccx_internal.h"
+// The masked moments: moments_partial_kernel / moments_final_kernel, the same tree over three sums (their terms are f64 and
+// they have no action byte: the partial kernel selects for itself, the final kernel and the entry are the frame's).
+#include "ccx_loss.h"
 #include "ccx_ppo.h"
 #include "ccx_rows.h"
 
@@ -57,10 +59,9 @@ __global__ __launch_bounds__(256) void ppo_partial_kernel(const PpoArgs A) {
     const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
     const ccx_rows::Wave W = ccx_rows::wave_of(A.M, (long long)blockIdx.x * ccx_tree::kBlockGroups + w, lane);
     const long long row = W.row, rl = W.rl;                             // surplus lanes load what the last row loads
-    const uint32_t a = A.actions[rl];
+    const ccx_loss::Gate G = ccx_loss::gate_of(A.actions, A.valid, rl);
     const uint32_t mbyte = MASK ? (uint32_t)A.masks[rl] : 0x1Fu;
-    const bool has_valid = A.valid != nullptr, has_norm = A.norm != nullptr;
-    const uint32_t vbyte = has_valid ? (uint32_t)A.valid[rl] : 1u;
+    const bool has_norm = A.norm != nullptr;
     const float lpo = A.logp_old[rl], adv = A.advantages[rl], ret = A.returns[rl], val = A.values[rl];
     float mean = 0.0f, denom = 1.0f;
     if (has_norm) {
@@ -69,25 +70,18 @@ __global__ __launch_bounds__(256) void ppo_partial_kernel(const PpoArgs A) {
     }
     float l[5];
     ccx_rows::load_rows(A.logits, pieces[w], W, l);
-    const bool counts = row < A.M && ccx_ppo::row_counts(has_valid, vbyte, a);
+    const bool counts = row < A.M && ccx_ppo::row_counts(G.has_valid, G.vbyte, G.a);
     const float an = ccx_ppo::normalised(has_norm, adv, mean, denom);
     ccx_ppo::Row t;
-    ccx_ppo::forward_row(l, mbyte, a, lpo, an, ret, val, A.lo, A.hi, t);
-    // rows that do not count and rows >= M enter as +0.0, selected
-    double s[ccx_ppo::kSums] = {counts ? 1.0 : 0.0,           counts ? (double)t.surr : 0.0, counts ? (double)t.vl : 0.0,
-                                counts ? (double)t.H : 0.0,   counts ? (double)t.kl : 0.0,   counts ? (double)t.cf : 0.0};
+    ccx_ppo::forward_row(l, mbyte, G.a, lpo, an, ret, val, A.lo, A.hi, t);
+    const float terms[5] = {t.surr, t.vl, t.H, t.kl, t.cf};
+    double s[ccx_ppo::kSums];
+    ccx_loss::select_sums(counts, terms, s);
     ccx_tree::block_sums(s, groups, A.partials, A.B);
 }
 
 __global__ __launch_bounds__(64) void ppo_final_kernel(const PpoArgs A) {
-    double s[ccx_ppo::kSums];
-    ccx_tree::final_sums(A.partials, A.B, s);
-    if (threadIdx.x == 0u) {
-        float st[8];
-        ccx_ppo::loss_finals(s, A.vf_coef, A.ent_coef, st);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) A.stats[k] = st[k];
-    }
+    ccx_loss::final_body<ccx_ppo::kSums, 8>(A.partials, A.B, A.stats, [&A](const auto& s, auto& st) { ccx_ppo::loss_finals(s, A.vf_coef, A.ent_coef, st); });
 }
 
 template <bool MASK, bool GL, bool GV>
@@ -96,14 +90,10 @@ __global__ __launch_bounds__(64) void ppo_bwd_kernel(const PpoArgs A) {
     const uint32_t lane = threadIdx.x;
     const long long row = (long long)blockIdx.x * 64 + lane;
     const long long rl = row < A.M ? row : A.M - 1;                     // (ccx_rows::Wave's row and rl: the wave's context is built where GL)
-    const uint32_t a = A.actions[rl];
-    const bool has_valid = A.valid != nullptr;
-    const uint32_t vbyte = has_valid ? (uint32_t)A.valid[rl] : 1u;
+    const ccx_loss::Gate G = ccx_loss::gate_of(A.actions, A.valid, rl);
     const float ret = A.returns[rl], val = A.values[rl];
-    const float n = A.stats_in[6];
-    const float g = A.grad_loss ? A.grad_loss[0] : 1.0f;
-    const float sc = g / n;
-    const bool counts = n != 0.0f && ccx_ppo::row_counts(has_valid, vbyte, a);      // n == 0: every gradient +0.0f, selected
+    const ccx_loss::Scale S = ccx_loss::scale_of(A.stats_in, A.grad_loss);
+    const bool counts = S.any && ccx_ppo::row_counts(G.has_valid, G.vbyte, G.a);
     if constexpr (GL) {
         const uint32_t mbyte = MASK ? (uint32_t)A.masks[rl] : 0x1Fu;
         const bool has_norm = A.norm != nullptr;
@@ -113,19 +103,19 @@ __global__ __launch_bounds__(64) void ppo_bwd_kernel(const PpoArgs A) {
             mean = A.norm[0];
             denom = A.norm[1] + A.adv_eps;
         }
-        const float se = sc * A.ent_coef;
+        const float se = S.sc * A.ent_coef;
         const float gent = 0.0f - se;
         float l[5], gr[5];
         const ccx_rows::Wave W = ccx_rows::wave_of(A.M, blockIdx.x, lane);
         ccx_rows::load_rows(A.logits, pieces, W, l);
         const float an = ccx_ppo::normalised(has_norm, adv, mean, denom);
-        ccx_ppo::backward_row_logits(l, mbyte, a, lpo, an, ret, val, A.lo, A.hi, sc, gent, gr);
+        ccx_ppo::backward_row_logits(l, mbyte, G.a, lpo, an, ret, val, A.lo, A.hi, S.sc, gent, gr);
 #pragma unroll
         for (int k = 0; k < 5; ++k) gr[k] = counts ? gr[k] : 0.0f;
         ccx_rows::store_rows(A.grad_logits, pieces, W, gr);
     }
     if constexpr (GV) {
-        const float scv = sc * A.vf_coef;
+        const float scv = S.sc * A.vf_coef;
         const float gv = ccx_ppo::backward_row_value(ret, val, scv);
         if (row < A.M) A.grad_values[row] = counts ? gv : 0.0f;
     }
@@ -143,14 +133,7 @@ __global__ __launch_bounds__(256) void moments_partial_kernel(const MomentArgs A
 }
 
 __global__ __launch_bounds__(64) void moments_final_kernel(const MomentArgs A) {
-    double s[ccx_ppo::kMomentSums];
-    ccx_tree::final_sums(A.partials, A.B, s);
-    if (threadIdx.x == 0u) {
-        float o[4];
-        ccx_ppo::moments_finals(s, o);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) A.out[k] = o[k];
-    }
+    ccx_loss::final_body<ccx_ppo::kMomentSums, 4>(A.partials, A.B, A.out, [](const auto& s, auto& o) { ccx_ppo::moments_finals(s, o); });
 }
 
 bool finite_nonneg(float v) { return v >= 0.0f && v < __builtin_inff(); }                // (false for NaN)
@@ -163,56 +146,10 @@ int check_hyper(const char* who, float clip, float vf_coef, float ent_coef, floa
     return CCX_OK;
 }
 
-void fill_hyper(PpoArgs& A, float clip, float vf_coef, float ent_coef, float adv_eps) {
-    A.lo = 1.0f - clip;                                                 // computed once, one f32 operation each
-    A.hi = 1.0f + clip;
-    A.vf_coef = vf_coef;
-    A.ent_coef = ent_coef;
-    A.adv_eps = adv_eps;
-}
-
-}  // namespace
-
-extern "C" {
-
-int64_t ccx_ppo_workspace_bytes(int64_t rows) {
-    if (rows < 1) return 0;
-    return (int64_t)ccx_tree::blocks_of(rows) * ccx_ppo::kSums * (int64_t)sizeof(double);
-}
-
-int ccx_masked_moments(ccx_handle* h, int64_t rows, const float* x, const uint8_t* valid_or_null, void* workspace, float* out) {
-    if (!h) return fail(CCX_EINVAL, "NULL handle");
-    if (!x || !workspace || !out) return fail(CCX_EINVAL, "ccx_masked_moments: NULL argument (x, workspace and out are required)");
-    unsigned blocks = 0;
-    if (int rc = ccxi::row_blocks("ccx_masked_moments", rows, ccx_tree::kBlockRows, blocks)) return rc;
-    if (misaligned(8, workspace)) return fail(CCX_EINVAL, "ccx_masked_moments: workspace must be 8-byte aligned");
-    CCX_HIP(hipSetDevice(h->device));
-    MomentArgs A{};
-    A.x = x;
-    A.valid = valid_or_null;
-    A.partials = static_cast<double*>(workspace);
-    A.out = out;
-    A.M = rows;
-    A.B = blocks;
-    hipLaunchKernelGGL(moments_partial_kernel, dim3(blocks), dim3(256), 0, h->stream, A);
-    hipLaunchKernelGGL(moments_final_kernel, dim3(1), dim3(64), 0, h->stream, A);
-    CCX_HIP(hipGetLastError());
-    return CCX_OK;
-}
-
-int ccx_ppo_loss(ccx_handle* h, int64_t rows, const float* logits, const uint8_t* actions, const uint8_t* masks_or_null,
-                 const float* logp_old, const float* advantages, const float* returns, const float* values,
-                 const uint8_t* valid_or_null, const float* norm_or_null, float clip, float vf_coef, float ent_coef, float adv_eps,
-                 void* workspace, float* stats) {
-    if (!h) return fail(CCX_EINVAL, "NULL handle");
-    if (!logits || !actions || !logp_old || !advantages || !returns || !values || !workspace || !stats)
-        return fail(CCX_EINVAL, "ccx_ppo_loss: NULL argument (only masks, valid and norm may be NULL)");
-    unsigned blocks = 0;
-    if (int rc = ccxi::row_blocks("ccx_ppo_loss", rows, ccx_tree::kBlockRows, blocks)) return rc;
-    if (misaligned(16, logits)) return fail(CCX_EINVAL, "ccx_ppo_loss: logits must be 16-byte aligned");
-    if (misaligned(8, workspace)) return fail(CCX_EINVAL, "ccx_ppo_loss: workspace must be 8-byte aligned");
-    if (int rc = check_hyper("ccx_ppo_loss", clip, vf_coef, ent_coef, adv_eps)) return rc;
-    CCX_HIP(hipSetDevice(h->device));
+// what ccx_ppo_loss and its backward pass alike
+PpoArgs ppo_args(int64_t rows, const float* logits, const uint8_t* actions, const uint8_t* masks_or_null, const float* logp_old,
+                 const float* advantages, const float* returns, const float* values, const uint8_t* valid_or_null,
+                 const float* norm_or_null, float clip, float vf_coef, float ent_coef, float adv_eps) {
     PpoArgs A{};
     A.logits = logits;
     A.actions = actions;
@@ -223,16 +160,54 @@ int ccx_ppo_loss(ccx_handle* h, int64_t rows, const float* logits, const uint8_t
     A.values = values;
     A.valid = valid_or_null;
     A.norm = norm_or_null;
-    A.partials = static_cast<double*>(workspace);
-    A.stats = stats;
+    A.lo = 1.0f - clip;                                                 // computed once, one f32 operation each
+    A.hi = 1.0f + clip;
+    A.vf_coef = vf_coef;
+    A.ent_coef = ent_coef;
+    A.adv_eps = adv_eps;
     A.M = rows;
-    A.B = blocks;
-    fill_hyper(A, clip, vf_coef, ent_coef, adv_eps);
-    if (masks_or_null) hipLaunchKernelGGL((ppo_partial_kernel<true>), dim3(blocks), dim3(256), 0, h->stream, A);
-    else hipLaunchKernelGGL((ppo_partial_kernel<false>), dim3(blocks), dim3(256), 0, h->stream, A);
-    hipLaunchKernelGGL(ppo_final_kernel, dim3(1), dim3(64), 0, h->stream, A);
-    CCX_HIP(hipGetLastError());
-    return CCX_OK;
+    return A;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t ccx_ppo_workspace_bytes(int64_t rows) { return ccx_loss::workspace_bytes(rows, ccx_ppo::kSums); }
+
+int ccx_masked_moments(ccx_handle* h, int64_t rows, const float* x, const uint8_t* valid_or_null, void* workspace, float* out) {
+    return ccx_loss::forward("ccx_masked_moments", h, x && workspace && out, "x, workspace and out are required", rows, workspace,
+                             ccx_loss::no_check, ccx_loss::no_check, [&](double* partials, unsigned blocks) {
+        MomentArgs A{};
+        A.x = x;
+        A.valid = valid_or_null;
+        A.partials = partials;
+        A.out = out;
+        A.M = rows;
+        A.B = blocks;
+        hipLaunchKernelGGL(moments_partial_kernel, dim3(blocks), dim3(256), 0, h->stream, A);
+        return A;
+    }, moments_final_kernel);
+}
+
+int ccx_ppo_loss(ccx_handle* h, int64_t rows, const float* logits, const uint8_t* actions, const uint8_t* masks_or_null,
+                 const float* logp_old, const float* advantages, const float* returns, const float* values,
+                 const uint8_t* valid_or_null, const float* norm_or_null, float clip, float vf_coef, float ent_coef, float adv_eps,
+                 void* workspace, float* stats) {
+    const char* who = "ccx_ppo_loss";
+    return ccx_loss::forward(who, h, logits && actions && logp_old && advantages && returns && values && workspace && stats,
+                             "only masks, valid and norm may be NULL", rows, workspace, [&] {
+        return misaligned(16, logits) ? fail(CCX_EINVAL, "%s: logits must be 16-byte aligned", who) : CCX_OK;
+    }, [&] { return check_hyper(who, clip, vf_coef, ent_coef, adv_eps); }, [&](double* partials, unsigned blocks) {
+        PpoArgs A = ppo_args(rows, logits, actions, masks_or_null, logp_old, advantages, returns, values, valid_or_null, norm_or_null,
+                             clip, vf_coef, ent_coef, adv_eps);
+        A.partials = partials;
+        A.stats = stats;
+        A.B = blocks;
+        if (masks_or_null) hipLaunchKernelGGL((ppo_partial_kernel<true>), dim3(blocks), dim3(256), 0, h->stream, A);
+        else hipLaunchKernelGGL((ppo_partial_kernel<false>), dim3(blocks), dim3(256), 0, h->stream, A);
+        return A;
+    }, ppo_final_kernel);
 }
 
 int ccx_ppo_loss_backward(ccx_handle* h, int64_t rows, const float* logits, const uint8_t* actions, const uint8_t* masks_or_null,
@@ -251,22 +226,12 @@ int ccx_ppo_loss_backward(ccx_handle* h, int64_t rows, const float* logits, cons
         return fail(CCX_EINVAL, "ccx_ppo_loss_backward: logits and grad_logits must be 16-byte aligned");
     if (int rc = check_hyper("ccx_ppo_loss_backward", clip, vf_coef, ent_coef, adv_eps)) return rc;
     CCX_HIP(hipSetDevice(h->device));
-    PpoArgs A{};
-    A.logits = logits;
-    A.actions = actions;
-    A.masks = masks_or_null;
-    A.logp_old = logp_old;
-    A.advantages = advantages;
-    A.returns = returns;
-    A.values = values;
-    A.valid = valid_or_null;
-    A.norm = norm_or_null;
+    PpoArgs A = ppo_args(rows, logits, actions, masks_or_null, logp_old, advantages, returns, values, valid_or_null, norm_or_null, clip,
+                         vf_coef, ent_coef, adv_eps);
     A.stats_in = stats;
     A.grad_loss = grad_loss_or_null;
     A.grad_logits = grad_logits_or_null;
     A.grad_values = grad_values_or_null;
-    A.M = rows;
-    fill_hyper(A, clip, vf_coef, ent_coef, adv_eps);
     const dim3 grid(blocks), block(64);
     // the masks are read for the logits' gradient only: without it there is one kernel
     if (!grad_logits_or_null) hipLaunchKernelGGL((ppo_bwd_kernel<false, false, true>), grid, block, 0, h->stream, A);

@@ -6,14 +6,13 @@
 //
 // q_act_kernel: ccx_sample.hip's shape.  One lane owns one slot, a workgroup is one wave; every load -- the small ones, the
 // exploration rate, the wave's pieces -- is issued before the first wait.  The greedy instantiation reads neither counter.
-// td_partial_kernel / td_final_kernel: ccx_ppo_loss.hip's forward.  A workgroup of four waves takes 256 consecutive rows, one
-// lane one row; each wave reduces its rows' six f64 terms by a butterfly, the first six threads add the four groups and write
-// the block's partials ([6][B] f64); ONE wave then adds the partials lane-strided, runs the same butterfly and writes `stats`.
-// Two plain launches: no atomic, no last-block-done counter.
-// td_bwd_kernel: one lane one row, a workgroup is one wave; it recomputes the forward terms from the inputs and reads nothing
-// else but `stats`; every element of grad_q is written, whole 16-byte pieces through LDS.
+// td_partial_kernel / td_final_kernel / td_bwd_kernel: the frame of a loss over the rows that count (ccx_loss.h) around
+// ccx_qlearn.h's rule, in ccx_ppo_loss.hip's shapes.  Forward: a workgroup of four waves takes 256 consecutive rows, one lane
+// one row, up to three arrays of rows through LDS; ONE wave then writes `stats`.  Backward: one lane one row, a workgroup is
+// one wave; every element of grad_q is written, whole 16-byte pieces through LDS.
 // tdn_partial_kernel / tdn_bwd_kernel: the same two bodies with discount[row] in the place of gamma (CCX_NSTEP:
 // ccx_td_loss_discounted and its backward); td_final_kernel serves both.
+#include "ccx_loss.h"
 #include "ccx_qact.h"
 #include "ccx_rows.h"
 
@@ -61,20 +60,19 @@ struct TdArgs {
 };
 
 struct TdSmall {
-    uint32_t a, mbyte, vbyte;
-    bool done, has_valid, has_w;
+    ccx_loss::Gate G;
+    uint32_t mbyte;
+    bool done, has_w;
     float r, w;
 };
 
 // what a row reads besides its rows of five: unconditional loads at a clamped index (surplus lanes load what the last row loads)
 __device__ __forceinline__ TdSmall td_small(const TdArgs& A, long long rl) {
     TdSmall v;
-    v.a = A.actions[rl];
     v.done = A.done[rl] != 0;
     v.r = (float)A.reward[rl];                                          // one rounding, as CCX_GAE does it
     v.mbyte = A.masks_next ? (uint32_t)A.masks_next[rl] : ccx_qlearn::kLegalAll;
-    v.has_valid = A.valid != nullptr;
-    v.vbyte = v.has_valid ? (uint32_t)A.valid[rl] : 1u;
+    v.G = ccx_loss::gate_of(A.actions, A.valid, rl);                    // (behind the others: the test of the valid byte waits for it)
     v.has_w = A.weights != nullptr;
     v.w = v.has_w ? A.weights[rl] : 1.0f;
     return v;
@@ -94,15 +92,16 @@ __device__ __forceinline__ void td_partial_body(const TdArgs& A, float4 (&pieces
     ccx_rows::load_rows(A.q, pieces[0][w], W, q);
     ccx_rows::load_rows(A.q_next_target, pieces[1][w], W, qt);
     if constexpr (DOUBLE) ccx_rows::load_rows(A.q_next_online, pieces[2][w], W, qo);
-    const bool counts = row < A.M && ccx_qlearn::row_counts(v.has_valid, v.vbyte, v.a);
-    const bool bad = row < A.M && ccx_qlearn::row_bad(v.has_valid, v.vbyte, v.a);
+    const bool counts = row < A.M && ccx_qlearn::row_counts(v.G.has_valid, v.G.vbyte, v.G.a);
+    const bool bad = row < A.M && ccx_qlearn::row_bad(v.G.has_valid, v.G.vbyte, v.G.a);
     ccx_qlearn::Row t;
-    if constexpr (DOUBLE) ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qo, v.mbyte, gamma, A.delta, A.c, v.has_w, v.w, t);
-    else ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qt, v.mbyte, gamma, A.delta, A.c, v.has_w, v.w, t);
+    if constexpr (DOUBLE) ccx_qlearn::forward_row(q, v.G.a, v.r, v.done, qt, qo, v.mbyte, gamma, A.delta, A.c, v.has_w, v.w, t);
+    else ccx_qlearn::forward_row(q, v.G.a, v.r, v.done, qt, qt, v.mbyte, gamma, A.delta, A.c, v.has_w, v.w, t);
     if (A.td_error && row < A.M) A.td_error[row] = counts ? t.d : 0.0f;
-    // rows that do not count and rows >= M enter as +0.0, selected
-    double s[ccx_qlearn::kSums] = {counts ? 1.0 : 0.0,           counts ? (double)t.term : 0.0, counts ? (double)t.ad : 0.0,
-                                   counts ? (double)t.qa : 0.0,  counts ? (double)t.y : 0.0,    bad ? 1.0 : 0.0};
+    const float terms[4] = {t.term, t.ad, t.qa, t.y};
+    double s[ccx_qlearn::kSums];
+    ccx_loss::select_sums(counts, terms, s);
+    s[5] = bad ? 1.0 : 0.0;
     ccx_tree::block_sums(s, groups, A.partials, A.B);
 }
 
@@ -121,14 +120,7 @@ __global__ __launch_bounds__(256) void tdn_partial_kernel(const TdArgs A, const 
 }
 
 __global__ __launch_bounds__(64) void td_final_kernel(const TdArgs A) {
-    double s[ccx_qlearn::kSums];
-    ccx_tree::final_sums(A.partials, A.B, s);
-    if (threadIdx.x == 0u) {
-        float st[8];
-        ccx_qlearn::td_finals(s, st);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) A.stats[k] = st[k];
-    }
+    ccx_loss::final_body<ccx_qlearn::kSums, 8>(A.partials, A.B, A.stats, [](const auto& s, auto& st) { ccx_qlearn::td_finals(s, st); });
 }
 
 template <bool DOUBLE, class GammaAt>
@@ -136,22 +128,20 @@ __device__ __forceinline__ void td_bwd_body(const TdArgs& A, float4 (&pieces)[DO
     const ccx_rows::Wave W = ccx_rows::wave_of(A.M, blockIdx.x, threadIdx.x);
     const TdSmall v = td_small(A, W.rl);
     const float gamma = gamma_at(W.rl);
-    const float n = A.stats_in[6];
-    const float g = A.grad_loss ? A.grad_loss[0] : 1.0f;
+    const ccx_loss::Scale S = ccx_loss::scale_of(A.stats_in, A.grad_loss);
     float q[5], qt[5], qo[5];
     ccx_rows::load_rows(A.q, pieces[0], W, q);
     ccx_rows::load_rows(A.q_next_target, pieces[1], W, qt);
     if constexpr (DOUBLE) ccx_rows::load_rows(A.q_next_online, pieces[2], W, qo);
-    const float sc = g / n;
-    const float gw = ccx_qlearn::row_scale(v.has_w, sc, v.w);
-    const bool counts = n != 0.0f && ccx_qlearn::row_counts(v.has_valid, v.vbyte, v.a);      // n == 0: every gradient +0.0f, selected
+    const float gw = ccx_qlearn::row_scale(v.has_w, S.sc, v.w);
+    const bool counts = S.any && ccx_qlearn::row_counts(v.G.has_valid, v.G.vbyte, v.G.a);
     ccx_qlearn::Row t;
-    if constexpr (DOUBLE) ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qo, v.mbyte, gamma, A.delta, A.c, v.has_w, v.w, t);
-    else ccx_qlearn::forward_row(q, v.a, v.r, v.done, qt, qt, v.mbyte, gamma, A.delta, A.c, v.has_w, v.w, t);
+    if constexpr (DOUBLE) ccx_qlearn::forward_row(q, v.G.a, v.r, v.done, qt, qo, v.mbyte, gamma, A.delta, A.c, v.has_w, v.w, t);
+    else ccx_qlearn::forward_row(q, v.G.a, v.r, v.done, qt, qt, v.mbyte, gamma, A.delta, A.c, v.has_w, v.w, t);
     const float ga = ccx_qlearn::backward_row(t.d, t.ad, A.delta, gw);
     float gr[5];
 #pragma unroll
-    for (int k = 0; k < 5; ++k) gr[k] = (counts && v.a == (uint32_t)k) ? ga : 0.0f;
+    for (int k = 0; k < 5; ++k) gr[k] = (counts && v.G.a == (uint32_t)k) ? ga : 0.0f;
     ccx_rows::store_rows(A.grad_q, pieces[0], W, gr);
 }
 
@@ -170,7 +160,7 @@ __global__ __launch_bounds__(64) void tdn_bwd_kernel(const TdArgs A, const float
 int check_td(const char* who, const void* q, const void* qt, const void* qo, float gamma, float huber_delta) {
     if (misaligned(16, q, qt, qo))
         return fail(CCX_EINVAL, "%s: q, q_next_target and q_next_online must be 16-byte aligned", who);
-    if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(CCX_EINVAL, "%s: gamma must be finite and lie in [0, 1], got %g", who, (double)gamma);
+    if (int rc = ccx_loss::check_gamma(who, gamma)) return rc;
     if (!(huber_delta > 0.0f)) return fail(CCX_EINVAL, "%s: huber_delta must be > 0 (+inf: the squared error), got %g", who, (double)huber_delta);
     return CCX_OK;
 }
@@ -200,32 +190,28 @@ int td_forward(const char* who, ccx_handle* h, int64_t rows, const float* q, con
                const uint8_t* done, const float* q_next_target, const float* q_next_online_or_null, const uint8_t* masks_next_or_null,
                const uint8_t* valid_or_null, const float* weights_or_null, const float* discount, float gamma, float huber_delta,
                void* workspace, float* stats, float* td_error_or_null) {
-    if (!h) return fail(CCX_EINVAL, "NULL handle");
-    if (!q || !actions || !reward || !done || !q_next_target || !workspace || !stats)
-        return fail(CCX_EINVAL, "%s: NULL argument (only q_next_online, masks_next, valid, weights and td_error may be NULL)", who);
-    unsigned blocks = 0;
-    if (int rc = ccxi::row_blocks(who, rows, ccx_tree::kBlockRows, blocks)) return rc;
-    if (int rc = check_td(who, q, q_next_target, q_next_online_or_null, gamma, huber_delta)) return rc;
-    if (misaligned(8, workspace)) return fail(CCX_EINVAL, "%s: workspace must be 8-byte aligned", who);
-    if (misaligned(4, discount)) return fail(CCX_EINVAL, "%s: discount must be 4-byte aligned", who);
-    CCX_HIP(hipSetDevice(h->device));
-    TdArgs A = td_args(rows, q, actions, reward, done, q_next_target, q_next_online_or_null, masks_next_or_null, valid_or_null,
-                       weights_or_null, gamma, huber_delta);
-    A.partials = static_cast<double*>(workspace);
-    A.stats = stats;
-    A.td_error = td_error_or_null;
-    A.B = blocks;
-    const dim3 grid(blocks), block(256);
-    if (discount) {
-        if (q_next_online_or_null) hipLaunchKernelGGL((tdn_partial_kernel<true>), grid, block, 0, h->stream, A, discount);
-        else hipLaunchKernelGGL((tdn_partial_kernel<false>), grid, block, 0, h->stream, A, discount);
-    } else {
-        if (q_next_online_or_null) hipLaunchKernelGGL((td_partial_kernel<true>), grid, block, 0, h->stream, A);
-        else hipLaunchKernelGGL((td_partial_kernel<false>), grid, block, 0, h->stream, A);
-    }
-    hipLaunchKernelGGL(td_final_kernel, dim3(1), dim3(64), 0, h->stream, A);
-    CCX_HIP(hipGetLastError());
-    return CCX_OK;
+    return ccx_loss::forward(who, h, q && actions && reward && done && q_next_target && workspace && stats,
+                             "only q_next_online, masks_next, valid, weights and td_error may be NULL", rows, workspace, [&] {
+        return check_td(who, q, q_next_target, q_next_online_or_null, gamma, huber_delta);
+    }, [&] {
+        return misaligned(4, discount) ? fail(CCX_EINVAL, "%s: discount must be 4-byte aligned", who) : CCX_OK;
+    }, [&](double* partials, unsigned blocks) {
+        TdArgs A = td_args(rows, q, actions, reward, done, q_next_target, q_next_online_or_null, masks_next_or_null, valid_or_null,
+                           weights_or_null, gamma, huber_delta);
+        A.partials = partials;
+        A.stats = stats;
+        A.td_error = td_error_or_null;
+        A.B = blocks;
+        const dim3 grid(blocks), block(256);
+        if (discount) {
+            if (q_next_online_or_null) hipLaunchKernelGGL((tdn_partial_kernel<true>), grid, block, 0, h->stream, A, discount);
+            else hipLaunchKernelGGL((tdn_partial_kernel<false>), grid, block, 0, h->stream, A, discount);
+        } else {
+            if (q_next_online_or_null) hipLaunchKernelGGL((td_partial_kernel<true>), grid, block, 0, h->stream, A);
+            else hipLaunchKernelGGL((td_partial_kernel<false>), grid, block, 0, h->stream, A);
+        }
+        return A;
+    }, td_final_kernel);
 }
 
 int td_backward(const char* who, ccx_handle* h, int64_t rows, const float* q, const uint8_t* actions, const double* reward,
@@ -278,10 +264,7 @@ int ccx_q_actions(ccx_handle* h, const float* q, const uint8_t* masks_or_null, c
     return CCX_OK;
 }
 
-int64_t ccx_td_workspace_bytes(int64_t rows) {
-    if (rows < 1) return 0;
-    return (int64_t)ccx_tree::blocks_of(rows) * ccx_qlearn::kSums * (int64_t)sizeof(double);
-}
+int64_t ccx_td_workspace_bytes(int64_t rows) { return ccx_loss::workspace_bytes(rows, ccx_qlearn::kSums); }
 
 int ccx_td_loss(ccx_handle* h, int64_t rows, const float* q, const uint8_t* actions, const double* reward, const uint8_t* done,
                 const float* q_next_target, const float* q_next_online_or_null, const uint8_t* masks_next_or_null,

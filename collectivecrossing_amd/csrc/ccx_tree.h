@@ -1,5 +1,6 @@
 // ccx_tree.h -- the fixed f64 reduction tree of every bit-defined learner op (CCX_PPO_LOSS and the masked moments, CCX_MLP's
-// backward, CCX_ADAM's global norm, CCX_QLEARN's TD loss), stated ONCE for the host and the device.  A group of 64 consecutive
+// backward, CCX_ADAM's global norm, CCX_QLEARN's TD loss, CCX_C51's categorical loss; the three losses through ccx_loss.h,
+// which states what stands around their per-row rules), stated ONCE for the host and the device.  A group of 64 consecutive
 // terms is halved by a butterfly; the four groups of a block of 256 are added into the block's partial; a final wave adds the
 // B partials lane-strided in ascending order onto 64 places, and a last butterfly gives the sum.  The tree is fixed by the
 // number of terms alone.  This header includes no rule: a unit that only sums takes it without ccx_softmax.h or ccx_ppo.h.

@@ -5,12 +5,14 @@ optimiser step (CCX_ADAM) of ``include/ccx.h``.
 :class:`LearnerOps` carries the methods and is mixed into :class:`~collectivecrossing_amd.batched.BatchedCollectiveCrossing`;
 the result dataclasses, :class:`MlpHead`, :class:`DeviceAdam` and the three ``torch.autograd.Function`` classes live here with it.  What a tensor
 argument must be is stated once, in :func:`_require`: a pure function of the tensor and the device, so it runs without a
-batch."""
+batch.  What stands around a loss over the rows that count -- :meth:`LearnerOps.ppo_loss`, ``QLearning.td_loss``,
+``CategoricalQ.loss`` -- is stated once too: :func:`_loss_over_rows` and the helpers in front of it."""
 
 from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
+from typing import ClassVar
 
 import numpy as np
 import torch
@@ -59,6 +61,7 @@ class PpoLossResult:
     workspace: torch.Tensor | None = None     # u8 [ccx_ppo_workspace_bytes(rows)]
     grad_logits: torch.Tensor | None = None   # f32 [..., 5]
     grad_values: torch.Tensor | None = None   # f32 [...]
+    _frame: ClassVar = ("ccx_ppo_workspace_bytes", "alloc_ppo_loss", "logits or values require")    # (_loss_over_rows)
 
     policy = property(lambda self: self.stats[1])
     value = property(lambda self: self.stats[2])
@@ -126,6 +129,72 @@ def _require_out(out, cls, alloc: str) -> None:
     """``out`` is ``None`` or a ``cls`` (what the method ``alloc`` returns)."""
     if out is not None and not isinstance(out, cls):
         raise ValueError(f"out must be {'an' if cls.__name__[0] in 'AEIOU' else 'a'} {cls.__name__} ({alloc})")
+
+
+def _check_grad_loss(grad_loss, device) -> None:
+    """``grad_loss`` of a ``*_loss_backward``: ``None`` or one f32 element in either of two shapes.  (Not :func:`_require`: it
+    names no shape.)"""
+    if grad_loss is not None and (not isinstance(grad_loss, torch.Tensor) or grad_loss.dtype is not torch.float32
+                                  or grad_loss.device != device or grad_loss.numel() < 1 or grad_loss.dim() > 1
+                                  or not grad_loss.is_contiguous()):
+        raise ValueError(f"grad_loss must be a torch.float32 tensor with one element (0-dim or [1]) on {device}")
+
+
+def _new_stats(device) -> torch.Tensor:
+    """The f32 [8] ``stats`` of a loss over the rows that count."""
+    return torch.zeros((8,), dtype=torch.float32, device=device)
+
+
+def _loss_workspace(batch, cls, workspace, rows: int) -> torch.Tensor:
+    """The workspace of the forward whose result class is ``cls`` (``cls._frame``: the library's function for its size, the
+    ``alloc_*`` that makes one, the differentiable inputs in words): the caller's, checked, or one from torch's allocator."""
+    return batch._workspace_arg(int(getattr(batch._lib, cls._frame[0])(int(rows))), workspace, cls._frame[1])
+
+
+def _alloc_loss(batch, cls, shape):
+    """What every ``alloc_*`` of a loss starts from: ``(shape as a tuple, stats, workspace)``."""
+    shape = tuple(int(x) for x in shape)
+    return shape, _new_stats(batch.device), _loss_workspace(batch, cls, None, int(np.prod(shape)) if shape else 1)
+
+
+def _loss_over_rows(batch, cls, owner, fn, forward, diff, rest, rows: int, extras, out):
+    """The frame of a loss over the rows that count behind its input checks; returns the ``cls``.  ``diff``: the inputs a
+    gradient may reach (the first one tells whether there are rows); ``rest``: every other argument, in the order in which
+    ``forward`` and ``fn.forward`` take them behind ``diff``.  ``extras``: the per-row outputs behind ``stats`` in the order
+    of ``cls``'s fields, as ``(field, shape, wanted, keywords of _require)``.  ``forward(*diff, *rest, workspace, stats,
+    *extras)`` enqueues the library's forward; ``fn`` is the loss's ``autograd.Function``, applied to ``(owner, *diff, *rest,
+    *extras)``.  With a gradient to carry, ``out=`` is refused and the workspace comes from torch's allocator inside ``fn``;
+    otherwise ``out`` is validated or allocated.  Zero rows give zero stats without calling the library, still connected to
+    ``diff``."""
+    dev, f = batch.device, torch.float32
+    if torch.is_grad_enabled() and any([t.requires_grad for t in diff]):
+        if out is not None:
+            raise ValueError(f"out= cannot be used when {cls._frame[2]} a gradient (the autograd path allocates its outputs)")
+        if rows == 0:
+            zero = diff[0].sum()
+            for t in diff[1:]:
+                zero = zero + t.sum()
+            stats = torch.cat([zero.reshape(1) * 0.0, torch.zeros(7, device=dev)])
+            made = [diff[0].new_zeros(shape) if want else None for _, shape, want, _ in extras]
+        else:
+            made = [batch._new(shape, f) if want else None for _, shape, want, _ in extras]
+            stats = fn.apply(owner, *diff, *rest, *made)
+        return cls(stats[0], stats.detach(), *made)
+    _require_out(out, cls, cls._frame[1])
+    if out is None:
+        stats = _new_stats(dev)
+        out = cls(stats[0], stats, *[batch._new(shape, f) if want else None for _, shape, want, _ in extras])
+        workspace = None
+    else:
+        _require("out.stats", out.stats, f, (8,), dev)
+        _require_all(dev, *[(f"out.{name}", getattr(out, name), f, shape, kw) for name, shape, _, kw in extras])
+        workspace = out.workspace
+    if rows == 0:
+        out.stats.zero_()
+        return out
+    forward(*[t.detach() for t in diff], *rest, _loss_workspace(batch, cls, workspace, rows), out.stats,
+            *[getattr(out, name) for name, *_ in extras])
+    return out
 
 
 _OPT = {"optional": True}
@@ -472,19 +541,11 @@ class LearnerOps:
         return out
 
     # ------------------------------------------------------------------ the PPO loss over the rows that count
-    def _ppo_workspace_arg(self, workspace, rows: int) -> torch.Tensor:
-        return self._workspace_arg(int(self._lib.ccx_ppo_workspace_bytes(int(rows))), workspace, "alloc_ppo_loss")
-
-    def _ppo_workspace(self, rows: int) -> torch.Tensor:
-        return self._ppo_workspace_arg(None, rows)
-
     def alloc_ppo_loss(self, shape, want_logits_grad: bool = True, want_values_grad: bool = True) -> PpoLossResult:
         """Static buffers of :meth:`ppo_loss` / :meth:`ppo_loss_backward` for rows of the leading shape ``shape``: stats,
         the workspace and the two gradients (for a captured graph)."""
-        shape = tuple(int(x) for x in shape)
-        rows = int(np.prod(shape)) if shape else 1
-        stats = torch.zeros((8,), dtype=torch.float32, device=self.device)
-        return PpoLossResult(stats[0], stats, self._ppo_workspace(rows),
+        shape, stats, workspace = _alloc_loss(self, PpoLossResult, shape)
+        return PpoLossResult(stats[0], stats, workspace,
                              self._new(shape + (5,), torch.float32) if want_logits_grad else None,
                              self._new(shape, torch.float32) if want_values_grad else None)
 
@@ -530,7 +591,7 @@ class LearnerOps:
         if rows == 0:
             out.copy_(torch.tensor([0.0, 0.0, 1.0, 0.0], dtype=torch.float32))
             return out
-        workspace = self._ppo_workspace_arg(workspace, rows)
+        workspace = _loss_workspace(self, PpoLossResult, workspace, rows)
         self._enqueue(self._lib.ccx_masked_moments, rows, x, valid, workspace, out)
         return out
 
@@ -563,30 +624,8 @@ class LearnerOps:
         Only enqueues (no host synchronisation); stream order: :class:`LearnerOps`."""
         hyper = self._check_ppo_hyper(clip, vf_coef, ent_coef, adv_eps)
         lead, norm = self._check_ppo(logits, values, actions, logp_old, advantages, returns, masks, valid, norm)
-        needs = [t.requires_grad for t in (logits, values)]
-        if any(needs) and torch.is_grad_enabled():
-            if out is not None:
-                raise ValueError("out= cannot be used when logits or values require a gradient (the autograd path allocates its outputs)")
-            if logits.numel() == 0:
-                stats = torch.cat([(logits.sum() + values.sum()).reshape(1) * 0.0, torch.zeros(7, device=self.device)])
-            else:
-                stats = _PpoLoss.apply(self, logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper)
-            return PpoLossResult(stats[0], stats.detach())
-        _require_out(out, PpoLossResult, "alloc_ppo_loss")
-        if out is None:
-            stats = torch.zeros((8,), dtype=torch.float32, device=self.device)
-            out = PpoLossResult(stats[0], stats)
-            workspace = None
-        else:
-            _require("out.stats", out.stats, torch.float32, (8,), self.device)
-            workspace = out.workspace
-        if logits.numel() == 0:
-            out.stats.zero_()
-            return out
-        workspace = self._ppo_workspace_arg(workspace, actions.numel())
-        self._ppo_forward(logits.detach(), values.detach(), actions, logp_old, advantages, returns, masks, valid, norm, hyper,
-                          workspace, out.stats)
-        return out
+        return _loss_over_rows(self, PpoLossResult, self, _PpoLoss, self._ppo_forward, (logits, values),
+                               (actions, logp_old, advantages, returns, masks, valid, norm, hyper), actions.numel(), (), out)
 
     def ppo_loss_backward(self, logits: torch.Tensor, values: torch.Tensor, actions: torch.Tensor, logp_old: torch.Tensor,
                           advantages: torch.Tensor, returns: torch.Tensor, masks: torch.Tensor | None = None,
@@ -602,10 +641,7 @@ class LearnerOps:
         hyper = self._check_ppo_hyper(clip, vf_coef, ent_coef, adv_eps)
         lead, norm = self._check_ppo(logits, values, actions, logp_old, advantages, returns, masks, valid, norm)
         _require("stats", stats, torch.float32, (8,), self.device)
-        if grad_loss is not None:                                    # (inline: one element in either of two shapes, any strides)
-            if (not isinstance(grad_loss, torch.Tensor) or grad_loss.dtype is not torch.float32 or grad_loss.device != self.device
-                    or grad_loss.numel() < 1 or grad_loss.dim() > 1 or not grad_loss.is_contiguous()):
-                raise ValueError(f"grad_loss must be a torch.float32 tensor with one element (0-dim or [1]) on {self.device}")
+        _check_grad_loss(grad_loss, self.device)
         _require_out(out, PpoLossResult, "alloc_ppo_loss")
         if out is None:
             gl = torch.empty_like(logits, requires_grad=False) if want_logits_grad else None
@@ -833,9 +869,9 @@ class _PpoLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, batch, logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper):
         logits, values = logits.detach(), values.detach()
-        stats = torch.zeros((8,), dtype=torch.float32, device=batch.device)
+        stats = _new_stats(batch.device)
         batch._ppo_forward(logits, values, actions, logp_old, advantages, returns, masks, valid, norm, hyper,
-                           batch._ppo_workspace(actions.numel()), stats)
+                           _loss_workspace(batch, PpoLossResult, None, actions.numel()), stats)
         ctx.batch, ctx.hyper = batch, hyper
         ctx.rest = (actions, logp_old, advantages, returns, masks, valid, norm)
         ctx.save_for_backward(logits, values, stats)

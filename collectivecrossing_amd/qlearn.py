@@ -14,12 +14,14 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
+from typing import ClassVar
 
 import numpy as np
 import torch
 
 from ._abi import DUELING_MAX_ARRAYS
-from .learner import MlpHead, _OPT, _require, _require_all, _require_out
+from .learner import (MlpHead, _OPT, _alloc_loss, _check_grad_loss, _loss_over_rows, _loss_workspace, _new_stats, _require,
+                      _require_all, _require_out)
 from .sides import SideHeads
 
 
@@ -43,6 +45,7 @@ class TdLossResult:
     td_error: torch.Tensor | None = None      # f32 [...]: q[a] - target; +0.0 at rows that do not count
     workspace: torch.Tensor | None = None     # u8 [ccx_td_workspace_bytes(rows)]
     grad_q: torch.Tensor | None = None        # f32 [..., 5]
+    _frame: ClassVar = ("ccx_td_workspace_bytes", "alloc_td_loss", "q requires")      # (learner._loss_over_rows)
 
     mean_abs_td = property(lambda self: self.stats[1])
     mean_q = property(lambda self: self.stats[2])
@@ -276,21 +279,12 @@ class QLearning:
         return out
 
     # ------------------------------------------------------------------ the TD loss over the rows that count
-    def _workspace_arg(self, workspace, rows: int) -> torch.Tensor:
-        b = self.batch
-        return b._workspace_arg(int(b._lib.ccx_td_workspace_bytes(int(rows))), workspace, "alloc_td_loss")
-
-    def _workspace(self, rows: int) -> torch.Tensor:
-        return self._workspace_arg(None, rows)
-
     def alloc_td_loss(self, shape, want_td_error: bool = True) -> TdLossResult:
         """Static buffers of :meth:`td_loss` / :meth:`td_loss_backward` for rows of the leading shape ``shape``: stats, the
         workspace, ``td_error`` if asked for, and ``grad_q`` (for a captured graph)."""
         b = self.batch
-        shape = tuple(int(x) for x in shape)
-        rows = int(np.prod(shape)) if shape else 1
-        stats = torch.zeros((8,), dtype=torch.float32, device=b.device)
-        return TdLossResult(stats[0], stats, b._new(shape, torch.float32) if want_td_error else None, self._workspace(rows),
+        shape, stats, workspace = _alloc_loss(b, TdLossResult, shape)
+        return TdLossResult(stats[0], stats, b._new(shape, torch.float32) if want_td_error else None, workspace,
                             b._new(shape + (5,), torch.float32))
 
     def _check_td(self, q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, extra=(), discount=None):
@@ -314,8 +308,8 @@ class QLearning:
                                  "under torch.no_grad())")
         return lead
 
-    def _forward(self, q, actions, reward, done, qt, qo, masks_next, valid, weights, hyper, workspace, stats, td_error,
-                 discount=None) -> None:
+    def _forward(self, q, actions, reward, done, qt, qo, masks_next, valid, weights, hyper, discount, workspace, stats,
+                 td_error) -> None:
         b = self.batch
         if discount is None:
             b._enqueue(b._lib.ccx_td_loss, actions.numel(), q, actions, reward, done, qt, qo, masks_next, valid, weights, *hyper,
@@ -355,32 +349,9 @@ class QLearning:
         b = self.batch
         hyper = _check_td_hyper(gamma, huber_delta, discount)
         lead = self._check_td(q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, discount=discount)
-        if q.requires_grad and torch.is_grad_enabled():
-            if out is not None:
-                raise ValueError("out= cannot be used when q requires a gradient (the autograd path allocates its outputs)")
-            if q.numel() == 0:
-                stats = torch.cat([q.sum().reshape(1) * 0.0, torch.zeros(7, device=b.device)])
-                return TdLossResult(stats[0], stats.detach(), q.new_zeros(lead) if want_td_error else None)
-            td_error = b._new(lead, torch.float32) if want_td_error else None
-            stats = _TdLoss.apply(self, q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, hyper,
-                                  td_error, discount)
-            return TdLossResult(stats[0], stats.detach(), td_error)
-        _require_out(out, TdLossResult, "alloc_td_loss")
-        if out is None:
-            stats = torch.zeros((8,), dtype=torch.float32, device=b.device)
-            out = TdLossResult(stats[0], stats, b._new(lead, torch.float32) if want_td_error else None)
-            workspace = None
-        else:
-            _require_all(b.device, ("out.stats", out.stats, torch.float32, (8,)),
-                         ("out.td_error", out.td_error, torch.float32, lead, _OPT))
-            workspace = out.workspace
-        if q.numel() == 0:
-            out.stats.zero_()
-            return out
-        workspace = self._workspace_arg(workspace, actions.numel())
-        self._forward(q.detach(), actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, hyper,
-                      workspace, out.stats, out.td_error, discount)
-        return out
+        return _loss_over_rows(b, TdLossResult, self, _TdLoss, self._forward, (q,),
+                               (actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, hyper, discount),
+                               actions.numel(), (("td_error", lead, want_td_error, _OPT),), out)
 
     def td_loss_backward(self, q: torch.Tensor, actions: torch.Tensor, reward: torch.Tensor, done: torch.Tensor,
                          q_next_target: torch.Tensor, q_next_online: torch.Tensor | None = None,
@@ -403,10 +374,7 @@ class QLearning:
         lead = tuple(q.shape[:-1]) if isinstance(q, torch.Tensor) else ()
         self._check_td(q, actions, reward, done, q_next_target, q_next_online, masks_next, valid, weights, (
             ("stats", stats, torch.float32, (8,)), ("out", out, torch.float32, lead + (5,), {"align": 16})), discount=discount)
-        if grad_loss is not None:                                        # (inline: one element in either of two shapes)
-            if (not isinstance(grad_loss, torch.Tensor) or grad_loss.dtype is not torch.float32 or grad_loss.device != b.device
-                    or grad_loss.numel() < 1 or grad_loss.dim() > 1 or not grad_loss.is_contiguous()):
-                raise ValueError(f"grad_loss must be a torch.float32 tensor with one element (0-dim or [1]) on {b.device}")
+        _check_grad_loss(grad_loss, b.device)
         if q.numel():
             q = q.detach()
             if discount is None:
@@ -440,11 +408,11 @@ class _TdLoss(torch.autograd.Function):
     loss, is differentiable: the gradient arriving at the other seven is not read."""
 
     @staticmethod
-    def forward(ctx, ql, q, actions, reward, done, qt, qo, masks_next, valid, weights, hyper, td_error, discount=None):
+    def forward(ctx, ql, q, actions, reward, done, qt, qo, masks_next, valid, weights, hyper, discount, td_error):
         q = q.detach()
-        stats = torch.zeros((8,), dtype=torch.float32, device=ql.batch.device)
-        ql._forward(q, actions, reward, done, qt, qo, masks_next, valid, weights, hyper, ql._workspace(actions.numel()), stats,
-                    td_error, discount)
+        stats = _new_stats(ql.batch.device)
+        ql._forward(q, actions, reward, done, qt, qo, masks_next, valid, weights, hyper, discount,
+                    _loss_workspace(ql.batch, TdLossResult, None, actions.numel()), stats, td_error)
         ctx.ql, ctx.hyper, ctx.discount = ql, hyper, discount
         ctx.rest = (actions, reward, done, qt, qo, masks_next, valid, weights)
         ctx.save_for_backward(q, stats)

@@ -251,6 +251,94 @@ def test_autograd_equals_loss_backward_and_two_runs_are_equal(batch, cases):
         cq.loss(x, *(d[k] for k in KEYS[1:4]), d["next_target"].clone().requires_grad_())
 
 
+FRAME_ROWS = (1, 63, 257, 513)                                           # inside a wave, across one, a block + a row, two + a row
+
+
+@pytest.mark.parametrize("present", (False, True), ids=("optional-absent", "optional-present"))
+@pytest.mark.parametrize("M", FRAME_ROWS)
+def test_the_three_call_forms_agree(batch, cases, M, present):
+    """Fresh outputs, ``out=`` of ``alloc_loss`` and autograd write the spec's bits, so the same ones; the gradient that
+    ``r.loss.backward()`` leaves is ``loss_backward(out=)``'s with ``grad_loss`` absent and with a 1.0f."""
+    import torch
+
+    from collectivecrossing_amd import CategoricalQ
+
+    cq = CategoricalQ(batch)
+    kw = c51_args(cases(51), present, present, present, present, present, M=M)
+    gamma = None if present else 0.97                                    # (with a discount per row there is no gamma)
+    d = cuda(kw)
+    want_stats, want_rl, want_proj = c51_loss_spec(**kw, gamma=0.99 if gamma is None else gamma, vmin=cq.vmin, vmax=cq.vmax)
+    want_grad = c51_loss_backward_spec(kw["logits"], kw["actions"], want_proj, kw["valid"], kw["weights"], want_stats, None)
+    fresh = cq.loss(*(d[k] for k in KEYS), gamma=gamma, discount=d["discount"], want_row_loss=True)
+    static = cq.alloc_loss((M,))
+    for t in (static.stats, static.row_loss, static.proj, static.grad_logits):
+        t.view(torch.uint8).fill_(FILL)
+    assert cq.loss(*(d[k] for k in KEYS), gamma=gamma, discount=d["discount"], out=static) is static
+    x = d["logits"].clone().requires_grad_()
+    auto = cq.loss(x, *(d[k] for k in KEYS[1:]), gamma=gamma, discount=d["discount"], want_row_loss=True)
+    auto.loss.backward()
+    one = torch.ones(1, device="cuda")
+    grads = [cq.loss_backward(d["logits"], d["actions"], static.proj, d["valid"], d["weights"], stats=static.stats, grad_loss=gl, out=o)
+             for gl, o in ((None, static), (one, None))]
+    batch.synchronize()
+    assert fresh.workspace is None and auto.workspace is None and grads[0] is static.grad_logits
+    for form, r in (("fresh", fresh), ("out=", static), ("autograd", auto)):
+        np.testing.assert_array_equal(bits32c(r.stats.cpu().numpy()), bits32c(want_stats), err_msg="stats " + form)
+        np.testing.assert_array_equal(bits32c(r.row_loss.cpu().numpy()), bits32c(want_rl), err_msg="row_loss " + form)
+        np.testing.assert_array_equal(bits32c(r.proj.cpu().numpy()), bits32c(want_proj), err_msg="proj " + form)
+    for form, g in (("autograd", x.grad), ("grad_loss None", grads[0]), ("grad_loss 1.0f", grads[1])):
+        np.testing.assert_array_equal(bits32c(g.cpu().numpy()), bits32c(want_grad), err_msg="grad_logits " + form)
+
+
+@pytest.mark.parametrize("why", ("valid all zero", "every action 255"))
+def test_no_row_counts(batch, cases, why):
+    """n = 0: the eight stats, every gradient element, row_loss and proj are +0.0f (all 32 bits clear), as the spec has them."""
+    from collectivecrossing_amd import CategoricalQ
+
+    cq = CategoricalQ(batch)
+    M = 257
+    kw = own(c51_args(cases(51), True, True, True, True, False, M=M))
+    if why == "valid all zero":
+        kw["valid"][:] = 0
+    else:
+        kw["actions"][:] = 255
+    want_stats, want_rl, want_proj = c51_loss_spec(**kw, gamma=0.97, vmin=cq.vmin, vmax=cq.vmax)
+    want_grad = c51_loss_backward_spec(kw["logits"], kw["actions"], want_proj, kw["valid"], kw["weights"], want_stats, None)
+    for want in (want_stats, want_rl, want_proj, want_grad):
+        assert not bits32c(want).any()
+    _q, stats, row_loss, proj, grad = run_device(cq, kw, gamma=0.97)      # (every output prefilled with a sentinel)
+    assert stats.shape == (8,) and row_loss.shape == (M,) and proj.shape == (M, 51) and grad.shape == (M, 5, 51)
+    for name, a in (("stats", stats), ("row_loss", row_loss), ("proj", proj), ("grad_logits", grad)):
+        assert not bits32c(a).any(), name
+
+
+def test_zero_rows_in_the_three_call_forms(batch, cases, monkeypatch):
+    import torch
+
+    from collectivecrossing_amd import CategoricalQ
+
+    cq = CategoricalQ(batch)
+    d = {k: (None if v is None else v[:0]) for k, v in cuda(c51_args(cases(51), True, True, True, True, False, M=4)).items()}
+    static = cq.alloc_loss((0,))
+    static.stats.fill_(float("nan"))
+
+    def called(*args, **kwargs):
+        raise AssertionError("zero rows must not reach the library")
+
+    monkeypatch.setattr(batch, "_enqueue", called)
+    fresh = cq.loss(*(d[k] for k in KEYS), want_row_loss=True)
+    assert cq.loss(*(d[k] for k in KEYS), out=static) is static
+    x = d["logits"].clone().requires_grad_()
+    auto = cq.loss(x, *(d[k] for k in KEYS[1:]), want_row_loss=True)
+    assert auto.loss.requires_grad and not auto.stats.requires_grad
+    auto.loss.backward()
+    for r in (fresh, static, auto):
+        assert r.stats.shape == (8,) and not r.stats.view(torch.int32).any()
+        assert r.row_loss.shape == (0,) and r.proj.shape == (0, 51)
+    assert x.grad.shape == (0, 5, 51)
+    assert cq.loss_backward(d["logits"], d["actions"], static.proj, stats=static.stats, out=static) is static.grad_logits
+
+
 def test_static_buffers_captured_and_replayed(cases):
     import torch
 

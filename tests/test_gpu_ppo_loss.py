@@ -284,6 +284,66 @@ def test_autograd_equals_the_backward_entry_point_and_torchs_composition(batch, 
         assert err_l <= PPO_GRAD_LOGITS_NEAR_BOUND + extra and err_v <= PPO_GRAD_VALUES_BOUND + extra
 
 
+# ------------------------------------------------------------------------------------------------- 3b. the frame of the loss
+FRAME_ROWS = (1, 63, 257, 513)                                           # inside a wave, across one, a block + a row, two + a row
+
+
+@pytest.mark.parametrize("present", (False, True), ids=("optional-absent", "optional-present"))
+@pytest.mark.parametrize("M", FRAME_ROWS)
+def test_the_three_call_forms_agree(batch, case, M, present):
+    """Fresh outputs, ``out=`` of ``alloc_ppo_loss`` and autograd write the spec's stats, so the same bits; the gradients that
+    ``r.loss.backward()`` leaves are ``ppo_loss_backward(out=)``'s with ``grad_loss`` absent and with a 1.0f."""
+    import torch
+
+    kw = case_args(case, True, True, M) if present else clean_case(case, False, M)
+    norm = NORM if present else None
+    d, dn = _dev_kw(kw), _dev(norm)
+    want = ppo_loss_spec(**kw, norm=None if norm is None else norm[1:3], **HYPER)
+    wl, wv = ppo_loss_backward_spec(**kw, norm=None if norm is None else norm[1:3], **HYPER, stats=want)
+    fresh = batch.ppo_loss(**d, norm=dn, **HYPER)
+    static = batch.alloc_ppo_loss((M,))
+    for t in (static.stats, static.grad_logits, static.grad_values):
+        t.fill_(float("nan"))
+    assert batch.ppo_loss(**d, norm=dn, **HYPER, out=static) is static
+    logits, values = d["logits"].clone().requires_grad_(), d["values"].clone().requires_grad_()
+    auto = batch.ppo_loss(**{**d, "logits": logits, "values": values}, norm=dn, **HYPER)
+    auto.loss.backward()
+    gl0, gv0 = batch.ppo_loss_backward(**d, norm=dn, **HYPER, stats=static.stats, out=static)
+    gl0, gv0 = gl0.clone(), gv0.clone()
+    gl1, gv1 = batch.ppo_loss_backward(**d, norm=dn, **HYPER, stats=static.stats, grad_loss=torch.ones(1, device="cuda"), out=static)
+    batch.synchronize()
+    assert fresh.workspace is None and auto.workspace is None and gl1 is static.grad_logits and gv1 is static.grad_values
+    for form, r in (("fresh", fresh), ("out=", static), ("autograd", auto)):
+        np.testing.assert_array_equal(bits32(r.stats.cpu().numpy()), bits32(want), err_msg="stats " + form)
+    for form, gl, gv in (("autograd", logits.grad, values.grad), ("grad_loss None", gl0, gv0), ("grad_loss 1.0f", gl1, gv1)):
+        np.testing.assert_array_equal(bits32(gl.cpu().numpy()), bits32(wl), err_msg="grad_logits " + form)
+        np.testing.assert_array_equal(bits32(gv.cpu().numpy()), bits32(wv), err_msg="grad_values " + form)
+
+
+def test_zero_rows_in_the_three_call_forms(batch, case, monkeypatch):
+    import torch
+
+    d = {k: v[:0] for k, v in _dev_kw(case_args(case, True, True, 4)).items()}
+    static = batch.alloc_ppo_loss((0,))
+    static.stats.fill_(float("nan"))
+
+    def called(*args, **kwargs):
+        raise AssertionError("zero rows must not reach the library")
+
+    monkeypatch.setattr(batch, "_enqueue", called)
+    fresh = batch.ppo_loss(**d)
+    assert batch.ppo_loss(**d, out=static) is static
+    logits, values = d["logits"].clone().requires_grad_(), d["values"].clone().requires_grad_()
+    auto = batch.ppo_loss(**{**d, "logits": logits, "values": values})
+    assert auto.loss.requires_grad and not auto.stats.requires_grad
+    auto.loss.backward()
+    for r in (fresh, static, auto):
+        assert r.stats.shape == (8,) and not r.stats.view(torch.int32).any()
+    assert logits.grad.shape == (0, 5) and values.grad.shape == (0,)
+    gl, gv = batch.ppo_loss_backward(**d, stats=static.stats, out=static)
+    assert gl is static.grad_logits and gv is static.grad_values
+
+
 # ------------------------------------------------------------------------------------------------- 4. streams and capture
 def test_another_current_stream(batch, case):
     """torch's current stream is not the handle's stream, and a blocker (tests/_stream_order.py) keeps one of the two

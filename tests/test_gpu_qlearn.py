@@ -311,6 +311,87 @@ def test_autograd_reaches_q_and_the_parameters_of_a_head(ql8, td_case):
         assert torch.equal(p.grad.view(torch.int32), g.view(torch.int32)) and torch.isfinite(p.grad).all() and p.grad.abs().sum() > 0
 
 
+# ------------------------------------------------------------------------------------------------- 4b. the frame of the loss
+FRAME_ROWS = (1, 63, 257, 513)                                           # inside a wave, across one, a block + a row, two + a row
+
+
+@pytest.mark.parametrize("present", (False, True), ids=("optional-absent", "optional-present"))
+@pytest.mark.parametrize("M", FRAME_ROWS)
+def test_the_three_call_forms_agree(ql8, td_case, M, present):
+    """Fresh outputs, ``out=`` of ``alloc_td_loss`` and autograd write the spec's bits, so the same ones; the gradient that
+    ``r.loss.backward()`` leaves is ``td_loss_backward(out=)``'s with ``grad_loss`` absent and with a 1.0f."""
+    import torch
+
+    batch, ql = ql8
+    hyper = dict(gamma=GAMMA, huber_delta=DELTA)
+    kw = td_args(td_case, present, present, present, present, M=M)
+    d = _cuda(kw)
+    want_stats, want_td = td_loss_spec(**kw, **hyper)
+    want_grad = td_loss_backward_spec(**kw, **hyper, stats=want_stats)
+    fresh = ql.td_loss(*(d[k] for k in KEYS), **hyper, want_td_error=True)
+    static = _forward(ql, d, M, **hyper)
+    q = d["q"].clone().requires_grad_()
+    auto = ql.td_loss(q, *(d[k] for k in KEYS[1:]), **hyper, want_td_error=True)
+    auto.loss.backward()
+    one = torch.ones(1, device="cuda")
+    grads = [ql.td_loss_backward(*(d[k] for k in KEYS), **hyper, stats=static.stats, grad_loss=gl, out=o)
+             for gl, o in ((None, static), (one, None))]
+    batch.synchronize()
+    assert fresh.workspace is None and auto.workspace is None and grads[0] is static.grad_q
+    for form, r in (("fresh", fresh), ("out=", static), ("autograd", auto)):
+        np.testing.assert_array_equal(bits32(r.stats.cpu().numpy()), bits32(want_stats), err_msg="stats " + form)
+        np.testing.assert_array_equal(bits32(r.td_error.cpu().numpy()), bits32(want_td), err_msg="td_error " + form)
+    for form, g in (("autograd", q.grad), ("grad_loss None", grads[0]), ("grad_loss 1.0f", grads[1])):
+        np.testing.assert_array_equal(bits32(g.cpu().numpy()), bits32(want_grad), err_msg="grad_q " + form)
+
+
+@pytest.mark.parametrize("why", ("valid all zero", "every action 255"))
+def test_no_row_counts(ql8, td_case, why):
+    """n = 0: the eight stats, every gradient element and td_error are +0.0f (all 32 bits clear), as the spec has them."""
+    batch, ql = ql8
+    M = 257
+    hyper = dict(gamma=GAMMA, huber_delta=DELTA)
+    kw = td_args(td_case, True, True, True, True, M=M)
+    if why == "valid all zero":
+        kw["valid"] = np.zeros(M, np.uint8)
+    else:
+        kw["actions"] = np.full(M, 255, np.uint8)
+    d = _cuda(kw)
+    want_stats, want_td = td_loss_spec(**kw, **hyper)
+    want_grad = td_loss_backward_spec(**kw, **hyper, stats=want_stats)
+    assert not bits32(want_stats).any() and not bits32(want_td).any() and not bits32(want_grad).any()
+    out = _forward(ql, d, M, **hyper)                                    # (every output prefilled with a sentinel)
+    g = ql.td_loss_backward(*(d[k] for k in KEYS), **hyper, stats=out.stats, out=out)
+    batch.synchronize()
+    assert out.stats.shape == (8,) and g.shape == (M, 5) and out.td_error.shape == (M,)
+    for name, t in (("stats", out.stats), ("grad_q", g), ("td_error", out.td_error)):
+        assert not bits32(t.cpu().numpy()).any(), name
+
+
+def test_zero_rows_in_the_three_call_forms(ql8, td_case, monkeypatch):
+    import torch
+
+    batch, ql = ql8
+    d = {k: v[:0] for k, v in _cuda(td_args(td_case, True, True, True, True, M=4)).items()}
+    static = ql.alloc_td_loss((0,))
+    static.stats.fill_(float("nan"))
+
+    def called(*args, **kwargs):
+        raise AssertionError("zero rows must not reach the library")
+
+    monkeypatch.setattr(batch, "_enqueue", called)
+    fresh = ql.td_loss(*(d[k] for k in KEYS), want_td_error=True)
+    assert ql.td_loss(*(d[k] for k in KEYS), out=static) is static
+    q = d["q"].clone().requires_grad_()
+    auto = ql.td_loss(q, *(d[k] for k in KEYS[1:]), want_td_error=True)
+    assert auto.loss.requires_grad and not auto.stats.requires_grad
+    auto.loss.backward()
+    for r in (fresh, static, auto):
+        assert r.stats.shape == (8,) and not r.stats.view(torch.int32).any() and r.td_error.shape == (0,)
+    assert q.grad.shape == (0, 5)
+    assert ql.td_loss_backward(*(d[k] for k in KEYS), stats=static.stats, out=static) is static.grad_q
+
+
 # ------------------------------------------------------------------------------------------------- 5. a replayed graph
 def test_static_buffers_captured_and_replayed(td_case):
     import torch
