@@ -13,7 +13,9 @@ target copy -- and one out-of-band event: at round EVENT_ROUND, between two repl
 permutation (``next_spec`` / ``gather_spec`` with ``obs0`` and the rollout's own ``obs``), the last of every epoch partly EMPTY.
 Each link is the spec its own test file compares the device with; nothing is restated here but the wiring.  ``mutate=``
 switches ONE wire to a plausible wrong one (MUTATIONS / PPO_MUTATIONS): the sensitivity test shows that each changes the
-result, so a device that made that mistake could not pass the comparison.
+result, so a device that made that mistake could not pass the comparison.  ``stop_after=`` / ``resume=`` stop either loop
+between two rounds and continue it from NumPy copies of what it carries (tests/test_resume_reference.py,
+tests/test_gpu_resume.py); with neither, both functions compute what they always did.
 
 Two additions to the example's loop, both needed for what the coverage conditions ask and both made on either side alike:
 
@@ -31,6 +33,8 @@ Final values (chosen on the CPU so that ``assert_rainbow_coverage`` / ``assert_p
 ``linear_init`` parameters of RAINBOW_INIT_SEEDS / PPO_INIT_SEEDS): see RAINBOW and PPO_MB below."""
 
 from __future__ import annotations
+
+import copy
 
 import numpy as np
 from _adam_spec import adam_step_spec, new_state, state_bytes
@@ -71,11 +75,18 @@ LINKS = (("actions", "explored", "index", "weights", "leaf_drawn") + tuple(f"mb.
 MUTATIONS = ("priorities_never_updated", "first_side_td_only", "weights_all_one", "scalar_gamma", "next_from_first_slot",
              "cut_bytes_ignored", "no_mark_cut", "beta_fixed", "dueling_backward_copies")
 DRAW_SIDE_MUTATIONS = ("priorities_never_updated", "first_side_td_only", "beta_fixed")
+# ``resume=(snapshot, omit)``: ONE component of the checkpoint left as a freshly constructed object would hold it
+OMISSIONS = ("adam_moments", "adam_state", "target", "leaf", "pstate", "pstate_draws", "cut", "episode", "step_count", "truncated",
+             "terminated", "obs_c", "ring_masks_next")
+ENV_KEYS = ("x", "y", "active", "terminated", "truncated", "step_count", "episode")          # the arrays of get_state()
+RING_KEYS = ("obs_c", "next_c", "actions", "reward", "done", "valid", "masks_next", "state")
+STEP_KEYS = ("reward", "agent_flags", "env_flags")                    # per actor step: what the episode statistics are fed
 
 # The minibatch PPO iteration: the collection of ``ppo_reference`` (E = 12, K = 24: M = 288 env-steps), B = 80 does not divide
 # M: 4 minibatches an epoch, the last with 48 records and 32 EMPTY ones.  640 rows per forward.
 PPO_MB = dict(B=80, EPOCHS=2, MAX_GRAD_NORM=6.9)
 PPO_MUTATIONS = ("no_obs0", "epoch_not_in_permutation")
+PPO_OMISSIONS = ("mb_state", "adam_state", "adam_moments")
 PPO_MB_KEYS = ("obs", "actions", "logp", "advantages", "returns", "masks", "valid", "index")
 
 
@@ -124,12 +135,24 @@ def hand_truncation(truncated):
 # ---------------------------------------------------------------------------------------------------------------------
 # Rainbow
 # ---------------------------------------------------------------------------------------------------------------------
-def rainbow_reference(online, mutate=None):
+def rainbow_reference(online, mutate=None, stop_after=None, resume=None):
     """The loop from the initial online parameters, a list of two (w1t, b1, w2, b2) with O = 6 in the order of SIDES; the
-    target starts as a copy.  Returns per actor step ``actions`` / ``explored`` (WARMUP + ROUNDS of them), per round
-    ``epsilon``, ``beta`` and ``rounds[u]``: a dict of every array of LINKS; the final ``params``, ``target``, ``m``, ``v``,
-    ``state_bytes``, ``ring_state``, ``leaf``, ``pstate``, ``cut``; ``facts``."""
+    target starts as a copy.  Returns per actor step ``actions`` / ``explored`` and the step's ``reward`` / ``agent_flags`` /
+    ``env_flags`` (WARMUP + ROUNDS of them), per round ``epsilon``, ``beta`` and ``rounds[u]``: a dict of every array of LINKS;
+    the final ``params``, ``target``, ``m``, ``v``, ``state_bytes``, ``ring_state``, ``leaf``, ``pstate``, ``cut``; ``facts``.
+
+    ``stop_after=k``: rounds 0 .. k - 1 only, and ``snapshot``: NumPy copies of everything the loop carries into round k (taken
+    before that round's out-of-band acts) -- ``env`` (ENV_KEYS), ``obs_c``, ``ring`` (RING_KEYS), ``cut``, ``leaf``, ``pstate``,
+    ``online``, ``target``, ``m``, ``v``, ``adam`` and ``book``, the lists and marks the facts are made from; ``facts`` is None.
+    ``resume=(snapshot, omit)``: every object is made as at the start (``online`` is not read), filled from the snapshot, and
+    rounds k .. ROUNDS - 1 run; what is returned covers the whole run.  ``omit``: None, or the ONE name of OMISSIONS whose
+    component stays as a freshly constructed object holds it."""
     assert mutate is None or mutate in MUTATIONS, mutate
+    assert stop_after is None or resume is None
+    snap, omit = resume if resume is not None else (None, None)
+    assert omit is None or omit in OMISSIONS, omit
+    if snap is not None:
+        online = [snap["online"][:4], snap["online"][4:]]
     R_ = RAINBOW
     E, S, B, n = R_["E"], R_["RING_STEPS"], R_["BATCH"], R_["N_STEP"]
     config = chain_config()
@@ -147,13 +170,51 @@ def rainbow_reference(online, mutate=None):
     leaf, pstate = np.zeros(S * E, np.int32), new_pstate()
     first_side = np.array([a in slots[0] for a in range(N)])
     side_u8 = [np.array([a in sl for a in range(N)], np.uint8) for sl in slots]
-    out = dict(actions=[], explored=[], epsilon=[], beta=[], rounds=[], windows=[], head=[], copies=[], target_differs=[],
-               drawn_resets=[], max_leaf=[], drawn_fresh_risen=[], shortened_by_event=[], distinct_leaves=[])
+    out = dict(actions=[], explored=[], reward=[], agent_flags=[], env_flags=[], epsilon=[], beta=[], rounds=[], windows=[], head=[],
+               copies=[], target_differs=[], drawn_resets=[], max_leaf=[], drawn_fresh_risen=[], shortened_by_event=[],
+               distinct_leaves=[])
+    lists = tuple(out)
     obs_c = compact_of_rows(ob.observe())
     reset_slots = np.zeros(S * E, bool)               # the record ends an episode
     fresh = np.zeros(S * E, bool)                     # pushed, and no update has named it since
     pushed_with = np.zeros(S * E, np.int64)           # max_leaf at its push
     event = dict(slots=set(), alive_until=-1)         # slots whose cut byte the event's mark_cut raised from 0
+    first_round = 0
+    if snap is not None:                              # in place, so that ``flat`` and ``heads`` keep naming the same arrays
+        first_round = int(snap["round"])
+        ob.set_state(**{k: np.zeros_like(v) if k == omit else v for k, v in snap["env"].items()})
+        obs_c = np.zeros_like(snap["obs_c"]) if omit == "obs_c" else snap["obs_c"].copy()
+        for k in RING_KEYS:
+            ring[k][...] = snap["ring"][k]
+        if omit == "ring_masks_next":
+            ring["masks_next"][...] = 0x1F
+        if omit != "cut":
+            cut[...] = snap["cut"]
+        leaf[...] = np.where(snap["leaf"] != 0, ONE_FIXED, 0) if omit == "leaf" else snap["leaf"]
+        if omit != "pstate":
+            pstate[...] = snap["pstate"]
+        if omit == "pstate_draws":
+            pstate[1] = 0
+        for dst, src in zip(flat, snap["online"]):
+            dst[...] = src
+        for dst, src in zip([p for h in target for p in h], snap["online" if omit == "target" else "target"]):
+            dst[...] = src
+        if omit != "adam_moments":
+            for dst, src in zip(ms + vs, snap["m"] + snap["v"]):
+                dst[...] = src
+        if omit != "adam_state":
+            state = copy.deepcopy(snap["adam"])
+        book = copy.deepcopy(snap["book"])
+        reset_slots, fresh, pushed_with, event = book["reset_slots"], book["fresh"], book["pushed_with"], book["event"]
+        out.update({k: book[k] for k in lists})
+
+    def snapshot(u):
+        book = copy.deepcopy(dict({k: out[k] for k in lists}, reset_slots=reset_slots, fresh=fresh, pushed_with=pushed_with,
+                                  event=event))
+        return dict(round=u, env={k: getattr(ob, k).copy() for k in ENV_KEYS}, obs_c=obs_c.copy(),
+                    ring={k: ring[k].copy() for k in RING_KEYS}, cut=cut.copy(), leaf=leaf.copy(), pstate=pstate.copy(),
+                    online=_copy(flat), target=_copy([p for h in target for p in h]), m=_copy(ms), v=_copy(vs),
+                    adam=copy.deepcopy(state), book=book)
 
     def actor_step(eps):
         nonlocal obs_c
@@ -174,12 +235,15 @@ def rainbow_reference(online, mutate=None):
         cut_push_spec(cut, int(ring["state"][0]), S, E, ef)
         push_leaf_spec(leaf, pstate, head, 1, S, E)
         obs_c = next_c
-        out["actions"].append(acts)
-        out["explored"].append(explored)
+        for k, v in (("actions", acts), ("explored", explored), ("reward", reward[0]), ("agent_flags", af[0]), ("env_flags", ef[0])):
+            out[k].append(v)
 
-    for _ in range(R_["WARMUP"]):
+    for _ in range(R_["WARMUP"] if snap is None else 0):
         actor_step(R_["EPS"][0])
-    for u in range(R_["ROUNDS"]):
+    for u in range(first_round, R_["ROUNDS"]):
+        if u == stop_after:
+            out["snapshot"] = snapshot(u)
+            break
         if u == R_["TRUNC_ROUND"]:                                                   # out of band: a user truncation by hand
             ob.set_state(truncated=hand_truncation(ob.truncated))
         if u == R_["EVENT_ROUND"]:                                                   # out of band, between two replays
@@ -254,7 +318,9 @@ def rainbow_reference(online, mutate=None):
     out.update(params=_copy(flat), target=[np.array(p, copy=True) for h in target for p in h], m=_copy(ms), v=_copy(vs),
                state_bytes=state_bytes(state), ring_state=ring["state"].copy(), leaf=leaf.copy(), pstate=pstate.copy(), cut=cut.copy(),
                capacity=S * E, consts=consts)
-    out["facts"] = rainbow_facts(out)
+    if stop_after == R_["ROUNDS"]:
+        out["snapshot"] = snapshot(stop_after)
+    out["facts"] = rainbow_facts(out) if len(out["rounds"]) == R_["ROUNDS"] else None
     return out
 
 
@@ -311,35 +377,71 @@ def first_difference(a, b):
 # ---------------------------------------------------------------------------------------------------------------------
 # PPO with device-drawn minibatches
 # ---------------------------------------------------------------------------------------------------------------------
-def ppo_minibatch_reference(actor, critic, form="rows", mutate=None):
+def ppo_minibatch_reference(actor, critic, form="rows", mutate=None, stop_after=None, resume=None):
     """One PPO iteration whose minibatches are the device's draw.  ``form``: "rows" (``obs`` f32 [K, E, N, L]) or "compact"
     ([K, E, N, 4], expanded by the gather).  Returns the collection's arrays, values, advantages, ``norm``, ``source`` (what
     ``set_source`` is given), per update ``index``, ``mb`` (every gathered array), ``stats``, ``grads`` (GRAD_ORDER),
-    ``adam_stats``; the final ``params`` / ``m`` / ``v`` / ``state_bytes`` and ``mb_state``; ``facts``."""
+    ``adam_stats``; the final ``params`` / ``m`` / ``v`` / ``state_bytes`` and ``mb_state``; ``facts``.
+
+    ``stop_after=k``: updates 0 .. k - 1 only, and ``snapshot``: NumPy copies of what the loop carries into update k -- ``source``,
+    ``norm``, ``mb_state``, ``params``, ``m``, ``v``, ``adam`` and ``book`` (the collection and the updates so far, for what is
+    returned); ``facts`` is None.  ``resume=(snapshot, omit)``: nothing is collected (``actor`` / ``critic`` are not read); the
+    source, the parameters and the optimiser come from the snapshot and updates k .. 7 run.  ``omit``: None, or the ONE name of
+    PPO_OMISSIONS whose component stays as a freshly constructed object holds it."""
     assert form in ("rows", "compact") and (mutate is None or mutate in PPO_MUTATIONS)
+    assert stop_after is None or resume is None
+    snap, omit = resume if resume is not None else (None, None)
+    assert omit is None or omit in PPO_OMISSIONS, omit
     from collectivecrossing_amd.params import lower_config
 
     E, K, B = PPO["E"], PPO["K"], PPO_MB["B"]
     M = K * E
     consts = row_consts(lower_config(chain_config()))
-    actor, critic = _copy(actor), _copy(critic)
-    col = ppo_collect(actor)
-    values, last_values, final_values = ppo_values(col, critic)
-    adv, ret, valid = gae_spec(col["reward"], col["agent_flags"], col["env_flags"], values, last_values, final_values, PPO["GAMMA"],
-                               PPO["LAM"])
-    norm = masked_moments_spec(adv, valid)
-    obs0 = col["rows"][0]                                                            # what step 0 acted on
-    obs = np.concatenate([col["rows"][1:], col["last_rows"][None]])                 # the rollout's own: rows BEHIND step s
-    if form == "compact":
-        obs0, obs = compact_of_rows(obs0), compact_of_rows(obs)
-    source = dict(obs=obs, obs0=None if mutate == "no_obs0" else obs0, actions=col["actions"], logp=col["logp"], advantages=adv,
-                  returns=ret, masks=col["masks"], valid=valid)
-    params = actor + critic
-    ms, vs, state = [np.zeros_like(p) for p in params], [np.zeros_like(p) for p in params], new_state()
-    mb_state = np.zeros(4, np.int64)
-    per_epoch = -(-M // B)
     updates = dict(index=[], mb=[], stats=[], grads=[], adam_stats=[])
-    for step in range(PPO_MB["EPOCHS"] * per_epoch):
+    mb_state, state, first_step = np.zeros(4, np.int64), new_state(), 0
+    if snap is None:
+        actor, critic = _copy(actor), _copy(critic)
+        col = ppo_collect(actor)
+        values, last_values, final_values = ppo_values(col, critic)
+        adv, ret, valid = gae_spec(col["reward"], col["agent_flags"], col["env_flags"], values, last_values, final_values, PPO["GAMMA"],
+                                   PPO["LAM"])
+        norm = masked_moments_spec(adv, valid)
+        obs0 = col["rows"][0]                                                        # what step 0 acted on
+        obs = np.concatenate([col["rows"][1:], col["last_rows"][None]])             # the rollout's own: rows BEHIND step s
+        if form == "compact":
+            obs0, obs = compact_of_rows(obs0), compact_of_rows(obs)
+        source = dict(obs=obs, obs0=None if mutate == "no_obs0" else obs0, actions=col["actions"], logp=col["logp"], advantages=adv,
+                      returns=ret, masks=col["masks"], valid=valid)
+        front = dict(col, values=values, last_values=last_values, final_values=final_values, advantages=adv, returns=ret, valid=valid,
+                     norm=norm, source=dict(source, obs0=obs0))
+        params = actor + critic
+        ms, vs = [np.zeros_like(p) for p in params], [np.zeros_like(p) for p in params]
+    else:
+        book = copy.deepcopy(snap["book"])
+        front, first_step = book["front"], int(snap["step"])
+        updates.update(book["updates"])
+        source, norm = copy.deepcopy(snap["source"]), snap["norm"].copy()
+        params = _copy(snap["params"])
+        actor, critic = params[:4], params[4:]
+        zero = omit == "adam_moments"
+        ms, vs = ([np.zeros_like(p) if zero else p.copy() for p in snap[k]] for k in ("m", "v"))
+        if omit != "adam_state":
+            state = copy.deepcopy(snap["adam"])
+        if omit != "mb_state":
+            mb_state = snap["mb_state"].copy()
+
+    def snapshot(step):
+        return dict(step=step, source=copy.deepcopy(source), norm=np.array(norm, copy=True), mb_state=mb_state.copy(),
+                    params=_copy(params), m=_copy(ms), v=_copy(vs), adam=copy.deepcopy(state),
+                    book=copy.deepcopy(dict(front=front, updates=updates)))
+
+    per_epoch = -(-M // B)
+    total = PPO_MB["EPOCHS"] * per_epoch
+    out = {}
+    for step in range(first_step, total):
+        if step == stop_after:
+            out["snapshot"] = snapshot(step)
+            break
         if mutate == "epoch_not_in_permutation":
             index = minibatch_draw_spec(M, B, SEED, (0, int(mb_state[1])))
             advance_spec(mb_state, B, M)
@@ -352,10 +454,11 @@ def ppo_minibatch_reference(actor, critic, form="rows", mutate=None):
                                     max_grad_norm=PPO_MB["MAX_GRAD_NORM"])
         for k, v in (("index", index), ("mb", mb), ("stats", stats), ("grads", grads), ("adam_stats", adam_stats)):
             updates[k].append(v)
-    out = dict(col, values=values, last_values=last_values, final_values=final_values, advantages=adv, returns=ret, valid=valid,
-               norm=norm, source=dict(source, obs0=obs0), **updates, params=_copy(params), m=_copy(ms), v=_copy(vs),
+    if stop_after == total:
+        out["snapshot"] = snapshot(total)
+    out.update(front, **updates, params=_copy(params), m=_copy(ms), v=_copy(vs),
                state_bytes=state_bytes(state), mb_state=mb_state.copy(), per_epoch=per_epoch, records=M)
-    out["facts"] = ppo_minibatch_facts(out)
+    out["facts"] = ppo_minibatch_facts(out) if len(out["index"]) == total else None
     return out
 
 
