@@ -19,7 +19,7 @@ ZERO, ONE = F32(0.0), F32(1.0)
 NEG_INF = F32(-np.inf)
 _J = np.arange(64)
 PLACE = _J.astype(F32)
-ATOMS = (2, 3, 33, 51, 64)
+ATOMS = (2, 3, 33, 51, 64, 8)             # 8 LAST: the atom count of the chain (tests/_c51_chain.py); the others keep their variants
 
 # Accuracy against torch f64, measured on the CPU by tests/test_c51_spec.py (the maxima it prints) and DOUBLED, as
 # max |err| / max(1, |f64 value|) against the textbook composition on the same f32 inputs, A in ATOMS, logits ~ N(0, 2^2),

@@ -1,17 +1,21 @@
-"""The device side of the two bigger loops, built from library calls only as the examples build them.  TEST INFRASTRUCTURE
-ONLY: what tests/test_gpu_rainbow_chain.py, tests/test_gpu_ppo_minibatch_chain.py and tests/test_gpu_resume.py run and hold
-to the composed CPU references of tests/_rainbow_chain.py, bit for bit.
+"""The device side of the three bigger loops, built from library calls only as the examples build them.  TEST INFRASTRUCTURE
+ONLY: what tests/test_gpu_rainbow_chain.py, tests/test_gpu_c51_chain.py, tests/test_gpu_ppo_minibatch_chain.py and
+tests/test_gpu_resume.py run and hold to the composed CPU references of tests/_rainbow_chain.py and tests/_c51_chain.py, bit for
+bit.
 
 ``RainbowLoop``: the loop of examples/dqn_dueling.py with the reference's shapes on a batch and stream of its own -- the env
 with its reset pool, terminated table and seed, the two ``SideHeads``, ring / ``NStepReplay`` / ``PrioritizedReplay``, the
 optimiser, the static buffers of ``actor_step`` and ``update``, eager or as two graphs replayed alternately.  ``start`` puts
 it at the reference's beginning; a resumed run restores a checkpoint instead (tests/test_gpu_resume.py).
+``CategoricalLoop``: the categorical double-DQN of tests/_c51_chain.py over the same env and replay, five heads per network.
 ``World`` / ``collect`` / ``values_and_advantages`` / ``MinibatchUpdates``: the iteration of examples/ppo_minibatches.py.
 Everything here runs inside ``with loop.scope():`` (the handle's stream current, no autograd)."""
 
 import contextlib
 
 import numpy as np
+from _c51_chain import C51, C51_GRAD_ORDER, C51_LINKS, C51_START_STEP_COUNT
+from _c51_chain import HEADS as C51_HEADS
 from _learner_chain import (EF_RESET, GRAD_ORDER, H, N, POOL_SEED0, POOL_SIZE, PPO, SEED, SIDES, START_STEP_COUNT, chain_config,
                             ppo_lr)
 from _rainbow_chain import (LINKS, MB_KEYS, PPO_MB, PPO_MB_KEYS, RAINBOW, RAINBOW_GRAD_ORDER, RAINBOW_START_STEP_COUNT,
@@ -37,6 +41,8 @@ class RainbowLoop:
     """Everything a run of the loop has to construct.  ``track``: ``track_episodes(log_capacity=track)`` before anything
     else.  ``start(init)`` begins the reference's run; the constructor alone leaves a fresh batch behind
     ``reset_from_pool()`` with fresh heads, replay objects and optimiser, which is what a resumed run loads into."""
+
+    CONST, LINKS = RAINBOW, LINKS                    # the loop's constants and the links a checked round compares, in chain order
 
     def __init__(self, track: int = 0):
         import torch
@@ -152,6 +158,12 @@ class RainbowLoop:
                 t.copy_(torch.from_numpy(a))
         self.target.load_state_dict(self.online.state_dict())
 
+    def online_parameters(self) -> list:
+        return list(self.online.parameters())
+
+    def target_parameters(self) -> list:
+        return list(self.target.parameters())
+
     def refresh_actor_inputs(self) -> None:
         """After the env state was put somewhere else by hand: ``obs_c`` and the masks the next actor step reads."""
         self.env.observe(out=self.obs)
@@ -159,7 +171,7 @@ class RainbowLoop:
         self.env.action_masks(out=self.masks)
 
     def warm_up(self, ref) -> None:
-        for s in range(RAINBOW["WARMUP"]):
+        for s in range(self.CONST["WARMUP"]):
             self.actor_step()
             self.stream.synchronize()
             same(_np(self.acts[0]), ref["actions"][s], f"warm-up step {s}: actions")
@@ -182,7 +194,7 @@ class RainbowLoop:
         link of every round against ``ref["rounds"][u]``, in chain order."""
         import torch
 
-        R, env, stream, ql, pr = RAINBOW, self.env, self.stream, self.ql, self.pr
+        R, env, stream, ql, pr = self.CONST, self.env, self.stream, self.ql, self.pr
         for u in range(first, last):
             if u == R["TRUNC_ROUND"]:                                # out of band, eagerly: a user truncation by hand
                 stream.synchronize()
@@ -200,17 +212,17 @@ class RainbowLoop:
                 stream.synchronize()
                 assert ql.epsilon == ref["epsilon"][u] and pr.beta == ref["beta"][u]
                 got = self.got_of_round()
-                for k in LINKS:
+                for k in self.LINKS:
                     same(_np(got[k]), ref["rounds"][u][k], f"round {u}: {k}")
             if (u + 1) % R["TARGET_EVERY"] == 0:
-                torch._foreach_copy_(list(self.target.parameters()), list(self.online.parameters()))
+                torch._foreach_copy_(self.target_parameters(), self.online_parameters())
         stream.synchronize()
 
     def final(self) -> dict:
         """The final state as NumPy arrays."""
         self.stream.synchronize()
         opt, pr = self.opt, self.pr
-        return dict(params=[_np(p) for p in opt.params], target=[_np(p) for p in self.target.parameters()], m=[_np(t) for t in opt.m],
+        return dict(params=[_np(p) for p in opt.params], target=[_np(p) for p in self.target_parameters()], m=[_np(t) for t in opt.m],
                     v=[_np(t) for t in opt.v], state_bytes=_np(opt.state), ring_state=_np(self.ring.state), leaf=_np(pr.leaf),
                     pstate=_np(pr.pstate), cut=_np(self.ns.cut))
 
@@ -226,6 +238,152 @@ def check_rainbow_final(got, ref, tag):
     for k in ("state_bytes", "ring_state", "leaf", "pstate", "cut"):
         same(got[k], ref[k], f"{tag}: {k} after the last round")
     assert got["ring_state"][:2].tolist() == [RAINBOW["WARMUP"] + RAINBOW["ROUNDS"], 0] and int(got["pstate"][1]) == RAINBOW["ROUNDS"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Categorical (C51) double-DQN over the same replay
+# ---------------------------------------------------------------------------------------------------------------------
+class CategoricalLoop(RainbowLoop):
+    """The loop of tests/_c51_chain.py from library calls only: the Rainbow loop's env, ring / ``NStepReplay`` /
+    ``PrioritizedReplay`` and out-of-band acts (``scope``, ``warm_up``, ``capture``, ``run_rounds`` and ``close`` are
+    inherited), with FIVE heads ``env.mlp_head(H, O=A)`` per network -- head k gives the atom logits of action k; A = 8 is
+    the device head's limit, not a choice about C51 -- copied into one contiguous ``[..., 5, A]`` buffer, ``CategoricalQ``
+    for the expected values, the loss and its backward, ``grad_logits[..., k, :]`` copied out for ``mlp_backward`` of head k,
+    and one Adam over the 20 parameter tensors.  Static buffers throughout: the actor step and the update capture as two
+    graphs.  ``autograd=True``: the update calls ``loss`` on a leaf logits tensor that requires a gradient (filled from the
+    heads) and reads ``logits.grad`` behind ``r.loss.backward()`` in the place of ``loss_backward(out=)``; eager only."""
+
+    CONST, LINKS = C51, C51_LINKS
+
+    def __init__(self, autograd: bool = False):
+        import torch
+
+        from collectivecrossing_amd import CategoricalQ, NStepReplay, PrioritizedReplay, QLearning, ReplayRing
+        from collectivecrossing_amd.batched import BatchedCollectiveCrossing
+        from collectivecrossing_amd.qlearn import QActions
+
+        assert torch.cuda.is_available(), "gpu tests need an MI355X"
+        C = C51
+        E, B, A = C["E"], C["BATCH"], C["ATOMS"]
+        config = chain_config()
+        self.env = env = BatchedCollectiveCrossing(config, E)
+        self.stream = stream = torch.cuda.Stream()
+        env.use_stream(stream)
+        torch.cuda.synchronize()
+        self.graphs = None
+        with self.scope():
+            env.make_reset_pool(seed0=POOL_SEED0, size=POOL_SIZE)
+            env.reset_from_pool()
+            env.synchronize()
+            env.set_terminated_table(*terminated_tables(config))
+            env.set_rng_seed(SEED)
+            dev = env.device
+            self.online = online = [env.mlp_head(H, O=A) for _ in range(C51_HEADS)]
+            self.target = target = [env.mlp_head(H, O=A) for _ in range(C51_HEADS)]
+            self.cq = cq = CategoricalQ(env, atoms=A, vmin=C["VMIN"], vmax=C["VMAX"])
+            self.ql = ql = QLearning(env, epsilon=C["EPS"][0])
+            self.opt = opt = env.adam(self.online_parameters(), lr=C["LR"], max_grad_norm=C["MAX_GRAD_NORM"])
+            self.ring = ring = ReplayRing(env, steps=C["RING_STEPS"])
+            self.ns = ns = NStepReplay(ring, n=C["N_STEP"], gamma=C["GAMMA"])
+            self.pr = pr = PrioritizedReplay(ns, alpha=C["ALPHA"], beta=C["BETA"][0], eps=C["PRIO_EPS"])
+
+            def forward(net, x, logits, scratch, hidden=None):
+                """The five heads on rows x into the contiguous [..., 5, A] buffer: exact copies of their outputs."""
+                for k, head in enumerate(net):
+                    head(x, out=scratch[k], hidden_out=None if hidden is None else hidden[k])
+                    logits[..., k, :].copy_(scratch[k])
+
+            # ---- the actor's static buffers
+            u8, f32 = torch.uint8, torch.float32
+            self.traj = traj = env.alloc_rollout(1, want_obs=False, want_compact=True, want_final=True)
+            self.acts = acts = torch.empty((1, E, N), dtype=u8, device=dev)
+            self.chosen = chosen = QActions(acts[0], torch.empty((E, N), dtype=u8, device=dev))
+            self.obs, self.masks = obs, masks = env.observe(), env.action_masks()
+            masks_next = masks.view(1, E, N)
+            self.obs_c = obs_c = compact_of_rows(obs)
+            act_scratch = [torch.empty((E, N, A), device=dev) for _ in range(C51_HEADS)]
+            act_logits = torch.empty((E, N, C51_HEADS, A), device=dev)
+            q_act = torch.empty((E, N, 5), device=dev)
+
+            def actor_step():
+                env.observe(out=obs)
+                forward(online, obs, act_logits, act_scratch)
+                cq.q_values(act_logits, out=q_act)
+                ql.q_actions(q_act, masks, out=chosen)
+                env.rollout(acts, auto_reset=True, reset_obs="next", out=traj, want_obs=False, want_compact=True, masks_out=masks)
+                pr.push(obs_c, acts, traj, masks_next=masks_next)
+                obs_c.copy_(traj.obs_compact[0])
+
+            # ---- the update's static buffers
+            lead = (B, N)
+            self.pmb = pmb = pr.alloc_batch(B)
+            mb, discount = pmb.batch.batch, pmb.batch.discount
+            scratch = [torch.empty(lead + (A,), device=dev) for _ in range(C51_HEADS)]
+            hid = [torch.empty(lead + (H,), device=dev) for _ in range(C51_HEADS)]
+            logits, next_target, next_online = (torch.empty(lead + (C51_HEADS, A), dtype=f32, device=dev) for _ in range(3))
+            loss = cq.alloc_loss(lead, want_row_loss=True)
+            seen = dict(stats=loss.stats, row_loss=loss.row_loss, proj=loss.proj, grad_logits=loss.grad_logits)
+            grads = [env.alloc_mlp_backward(head, lead) for head in online]
+            flat = [t for o in grads for t in (o.w1t, o.b1, o.w2, o.b2)]
+            if autograd:
+                logits.requires_grad_()                              # a leaf; the heads fill it under no_grad
+
+            def update():
+                pr.sample(B, out=pmb)
+                forward(online, mb.obs, logits, scratch, hid)
+                forward(target, mb.next_obs, next_target, scratch)
+                forward(online, mb.next_obs, next_online, scratch)
+                args = (logits, mb.actions, mb.reward, mb.done, next_target)
+                kw = dict(next_online=next_online, masks_next=mb.masks_next, valid=mb.valid, weights=pmb.weights, discount=discount)
+                if autograd:
+                    logits.grad = None
+                    with torch.enable_grad():
+                        r = cq.loss(*args, **kw, want_row_loss=True)
+                        r.loss.backward()
+                    seen.update(stats=r.stats, row_loss=r.row_loss, proj=r.proj, grad_logits=logits.grad)
+                else:
+                    cq.loss(*args, **kw, out=loss)
+                    cq.loss_backward(logits, mb.actions, loss.proj, mb.valid, pmb.weights, stats=loss.stats, out=loss)
+                for k, head in enumerate(online):
+                    scratch[k].copy_(seen["grad_logits"][..., k, :])
+                    env.mlp_backward(head, mb.obs, hid[k], scratch[k], out=grads[k])
+                opt.step(grads=flat)
+                pr.update_priorities(mb.index, seen["row_loss"])
+
+            def got_of_round() -> dict:
+                got = dict(actions=acts[0], explored=chosen.explored, index=pmb.batch.index, weights=pmb.weights,
+                           leaf_drawn=pmb.leaf_drawn, logits=logits, next_target=next_target, next_online=next_online, **seen,
+                           adam_stats=opt.stats, leaf=pr.leaf, pstate=pr.pstate, cut=ns.cut)
+                got.update({f"mb.{k}": getattr(mb, k) for k in MB_KEYS[:8]})
+                got.update({"mb.discount": discount, "mb.span": pmb.batch.span})
+                got.update({f"grad.{g}": t for g, t in zip(C51_GRAD_ORDER, flat)})
+                return got
+
+            self.actor_step, self.update, self.got_of_round = actor_step, update, got_of_round
+            self.step_actor, self.step_update = actor_step, update
+
+    def online_parameters(self) -> list:
+        return [t for h in self.online for t in (h.w1t, h.b1, h.w2, h.b2)]
+
+    def target_parameters(self) -> list:
+        return [t for h in self.target for t in (h.w1t, h.b1, h.w2, h.b2)]
+
+    def start(self, init) -> None:
+        """The reference's beginning: staggered step counters, the committed parameters, target := online."""
+        import torch
+
+        self.env.set_state(step_count=C51_START_STEP_COUNT)
+        for t, a in zip(self.online_parameters(), (a for par in init for a in par)):
+            t.copy_(torch.from_numpy(a))
+        torch._foreach_copy_(self.target_parameters(), self.online_parameters())
+
+
+def check_c51_final(got, ref, tag):
+    for k in ("params", "target", "m", "v"):
+        same_lists(got[k], ref[k], C51_GRAD_ORDER, f"{tag}: {k} after the last round")
+    for k in ("state_bytes", "ring_state", "leaf", "pstate", "cut"):
+        same(got[k], ref[k], f"{tag}: {k} after the last round")
+    assert got["ring_state"][:2].tolist() == [C51["WARMUP"] + C51["ROUNDS"], 0] and int(got["pstate"][1]) == C51["ROUNDS"]
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -365,10 +365,11 @@ def assert_rainbow_coverage(r) -> None:
     assert first + 2 < rounds and not f["target_differs"][first + 1] and f["target_differs"][first + 2], f
 
 
-def first_difference(a, b):
-    """The first link, in chain order, at which two runs of ``rainbow_reference`` differ: "round u: name", or None."""
+def first_difference(a, b, links=LINKS):
+    """The first link, in chain order, at which two runs of ``rainbow_reference`` (``links``: of another loop with ``rounds``)
+    differ: "round u: name", or None."""
     for u, (x, y) in enumerate(zip(a["rounds"], b["rounds"])):
-        for k in LINKS:
+        for k in links:
             if x[k].shape != y[k].shape or x[k].tobytes() != y[k].tobytes():
                 return f"round {u}: {k}"
     return None
