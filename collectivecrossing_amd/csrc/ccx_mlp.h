@@ -5,6 +5,8 @@
 // Every line is ONE f32 operation: the units that include this are compiled with -ffp-contract=off, and `/` must be the
 // correctly rounded division.
 #pragma once
+#include <stddef.h>
+
 #include "ccx_softmax.h"
 
 namespace ccx_mlp {
@@ -18,6 +20,13 @@ enum : int { kTanh = 0, kRelu = 1 };
 CCX_HD bool shape_ok(int L, int H, int O, int activation) {
     return L >= 1 && L <= kMaxL && H >= kGroup && H <= kMaxH && H % kGroup == 0 && O >= 1 && O <= kMaxO &&
            (activation == kTanh || activation == kRelu);
+}
+
+// LDS floats a workgroup of the forward needs (ccx_mlp_tile.h): the x tile of 64 rows at its odd row stride, later overlaid
+// by the partials (and y in the fused kernels, `draw`); a multiple of 64.  Above 65536 bytes (L > 255) the launch opts in.
+inline size_t lds_floats(int L, int H, int O, bool draw) {
+    const size_t tile = (size_t)64 * (size_t)(L | 1), sums = (size_t)(H / kGroup + (draw ? 1 : 0)) * 64 * (size_t)O;
+    return tile > sums ? tile : sums;
 }
 
 CCX_HD float relu_spec(float a) { return a < 0.0f ? 0.0f : a; }          // NaN stays NaN, -0.0 stays -0.0

@@ -36,8 +36,9 @@ namespace mg = ccx_mlp_grad;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr size_t kLdsBudget = 65536;
+constexpr int kThreads = mg::kThreads;
+using mg::RowImage;
+using mg::row_image;
 
 struct HeadGradArgs {
     const float* x;                    // [rows][L]
@@ -54,19 +55,6 @@ struct HeadGradArgs {
     int32_t L, H, O, activation;
     int32_t sub;                       // rows of a sub-tile
 };
-
-// the LDS image of one row, in floats: x at 0 (the constant 1 at L), ga, hidden (the constant 1 behind it), grad_y
-struct RowImage {
-    int ga, hid, gy, stride;
-};
-__host__ __device__ inline RowImage row_image(int L, int H, int O) {
-    RowImage m;
-    m.ga = (L + 4) & ~3;
-    m.hid = m.ga + H;
-    m.gy = m.hid + H + 4;
-    m.stride = m.gy + ((O + 3) & ~3);
-    return m;
-}
 
 // a quad of the LDS image: every part of a row starts at a multiple of four floats and so does the row stride, which the
 // compiler cannot see from the run-time sizes
@@ -262,16 +250,6 @@ __global__ __launch_bounds__(kThreads) void head_grad_final_kernel(const HeadGra
     (which == 0 ? A.grad_w1t : which == 1 ? A.grad_b1 : which == 2 ? A.grad_w2 : A.grad_b2)[i] = v;
 }
 
-// rows of a sub-tile: the most of 64, 32, 16, 8 whose images fit the budget beside w2 (8 always do: 33 KB + 8 KB at the limits)
-// (`per_row`: further bytes per row behind w2 -- the flat rows of the sides kernel)
-int sub_rows(int L, int H, int O, size_t& bytes, size_t per_row = 0) {
-    const size_t row = (size_t)row_image(L, H, O).stride * sizeof(float) + per_row, fixed = (size_t)O * H * sizeof(float);
-    int R = 64;
-    while (R > 8 && R * row + fixed > kLdsBudget) R >>= 1;
-    bytes = R * row + fixed;
-    return R;
-}
-
 // the checks and the two launches of both entry points; `sel`: the slot group of ccx_sides_backward (rows = M S), or null
 int backward_launches(const char* who, ccx_handle* h, int64_t rows, const SideSel* sel, int32_t L, int32_t H, int32_t O, int32_t activation,
                       const float* x, const float* hidden, const float* grad_y, const float* w2, void* workspace, float* grad_w1t,
@@ -287,13 +265,12 @@ int backward_launches(const char* who, ccx_handle* h, int64_t rows, const SideSe
         return fail(CCX_EINVAL, "%s: grad_y, w2, grad_w1t, grad_b1, grad_w2 and grad_b2 must be 4-byte aligned", who);
     CCX_HIP(hipSetDevice(h->device));
     size_t bytes = 0;
-    const int R = sub_rows(L, H, O, bytes, sel ? sizeof(long long) : 0);
+    const int R = mg::sub_rows(L, H, O, bytes, sel ? sizeof(long long) : 0);
     const HeadGradArgs A{x, hidden, grad_y, w2, static_cast<double*>(workspace), grad_w1t, grad_b1, grad_w2, grad_b2, grad_a_or_null,
                          (long long)rows, (long long)blocks, L, H, O, activation, R};
     const RowImage m = row_image(L, H, O);
-    const int tiles = (m.ga / 4) * (H / 4) + ((O + 3) / 4) * (H / 4 + 1);
     const long long elements = mg::elements_of(L, H, O);
-    const dim3 grid(blocks, (unsigned)((tiles + kThreads - 1) / kThreads));
+    const dim3 grid(blocks, mg::grid_y(L, H, O));
     if (sel) {
         SideSel G = *sel;
         G.flat_at = R * m.stride + O * H;                                // (floats; an even number: the stride and H are multiples of 4)

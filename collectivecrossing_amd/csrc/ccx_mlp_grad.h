@@ -1,11 +1,14 @@
 // ccx_mlp_grad.h -- the backward rule of CCX_MLP (include/ccx.h) as inline functions: the per-row f32 part (gh, ga), one
-// term of a block's f64 chain, the place of every output element in the workspace, and the final step over the block
+// term of a block's f64 chain, the place of every output element in the workspace, the launch shape of the blocks kernels
+// (the LDS image of a row, the rows of a sub-tile, the tile grid), and the final step over the block
 // partials, which is ccx_tree.h's (strided_partials, then the halving): the project keeps one tree.  Included by
 // ccx_mlp_backward.hip, whose kernels inline exactly these functions; it also compiles with a plain host C++ compiler
 // (tests/test_mlp_backward_host_rule.py runs backward_host against the NumPy spec bit for bit).
 // The discipline is ccx_mlp.h's and ccx_tree.h's: every line is ONE operation of the stated type, and the including units are
 // compiled with -ffp-contract=off.
 #pragma once
+#include <stddef.h>
+
 #include "ccx_mlp.h"
 #include "ccx_tree.h"
 
@@ -70,6 +73,39 @@ CCX_HD void tile_row(double (&acc)[kTile][kTile], const float (&a)[kTile], const
         for (int j = 0; j < kTile; ++j) acc[i][j] = chain_add(acc[i][j], a[i], b[j]);
     }
 }
+
+// ---- the launch shape of the blocks kernels (ccx_mlp_backward.hip), stated where a host compiler reaches it too
+// (tests/test_mlp_shape_classes.py asserts from these which shapes take which branch).
+// the LDS image of one row, in floats: x at 0 (the constant 1 at L), ga, hidden (the constant 1 behind it), grad_y
+struct RowImage {
+    int ga, hid, gy, stride;
+};
+CCX_HD RowImage row_image(int L, int H, int O) {
+    RowImage m;
+    m.ga = (L + 4) & ~3;
+    m.hid = m.ga + H;
+    m.gy = m.hid + H + 4;
+    m.stride = m.gy + ((O + 3) & ~3);
+    return m;
+}
+
+constexpr int kThreads = 256;                                            // of a blocks workgroup: one 4 x 4 tile per thread
+constexpr size_t kLdsBudget = 65536;
+
+// rows of a sub-tile: the most of 64, 32, 16, 8 whose images fit the budget beside w2 (8 always do: 33 KB + 8 KB at the limits)
+// (`per_row`: further bytes per row behind w2 -- the flat rows of the sides kernel)
+inline int sub_rows(int L, int H, int O, size_t& bytes, size_t per_row = 0) {
+    const size_t row = (size_t)row_image(L, H, O).stride * sizeof(float) + per_row, fixed = (size_t)O * H * sizeof(float);
+    int R = 64;
+    while (R > 8 && R * row + fixed > kLdsBudget) R >>= 1;
+    bytes = R * row + fixed;
+    return R;
+}
+
+// the 4 x 4 tiles of one call's elements -- those of [x | 1]^T ga, then those of grad_y^T [hidden | 1] -- and the slices of
+// 256 tiles they are cut into: grid.y of the blocks launch
+inline int tiles_of(int L, int H, int O) { return (row_image(L, H, O).ga / 4) * (H / 4) + ((O + 3) / 4) * (H / 4 + 1); }
+inline unsigned grid_y(int L, int H, int O) { return (unsigned)((tiles_of(L, H, O) + kThreads - 1) / kThreads); }
 
 // ---- the whole rule on the host, one addition at a time.  ws: workspace_bytes(...) bytes; ga: [rows][H] scratch or output.
 inline void backward_host(long long rows, int L, int H, int O, int activation, const float* x, const float* hidden,

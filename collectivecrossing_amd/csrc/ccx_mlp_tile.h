@@ -33,12 +33,7 @@ struct MlpArgs {
     int32_t L, H, O, activation;
 };
 
-// LDS floats a workgroup needs: the x tile at its odd row stride, later overlaid by the partials (and y in the fused kernels);
-// a multiple of 64
-inline size_t lds_floats(int L, int H, int O, bool draw) {
-    const size_t tile = (size_t)64 * (size_t)(L | 1), sums = (size_t)(H / ccx_mlp::kGroup + (draw ? 1 : 0)) * 64 * (size_t)O;
-    return tile > sums ? tile : sums;
-}
+using ccx_mlp::lds_floats;                                               // the LDS floats a workgroup needs (ccx_mlp.h)
 
 // The tile of workgroup blockIdx.x of a launch over ceil(rows / 64) workgroups: rows 64 b .. 64 b + 63 of the array.
 // The tile's x is 64 L contiguous floats that start at a multiple of 64 floats: its 16 L 16-byte pieces are loaded whole by

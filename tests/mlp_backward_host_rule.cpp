@@ -19,4 +19,18 @@ int host_mlp_backward(long long rows, int L, int H, int O, int activation, const
     return 0;
 }
 
+// the launch shape of the blocks kernels: the rows of a sub-tile and the dynamic LDS bytes of a workgroup (`per_row`: 0 for
+// ccx_mlp_backward, 8 for ccx_sides_backward), and grid.y; -1 / 0 for a shape outside CCX_MLP's limits
+int host_sub_rows(int L, int H, int O, int per_row, long long* bytes) {
+    if (!ccx_mlp::shape_ok(L, H, O, ccx_mlp::kTanh) || per_row < 0) return -1;
+    size_t b = 0;
+    const int R = ccx_mlp_grad::sub_rows(L, H, O, b, (size_t)per_row);
+    *bytes = (long long)b;
+    return R;
+}
+
+int host_grad_grid_y(int L, int H, int O) {
+    return ccx_mlp::shape_ok(L, H, O, ccx_mlp::kTanh) ? (int)ccx_mlp_grad::grid_y(L, H, O) : 0;
+}
+
 }  // extern "C"

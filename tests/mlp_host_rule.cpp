@@ -13,6 +13,11 @@ int host_mlp(long long rows, int L, int H, int O, int activation, const float* x
     return 0;
 }
 
+// the LDS floats of a forward workgroup (`draw`: the fused kernels keep the tile's y); -1 for a shape outside CCX_MLP's limits
+long long host_lds_floats(int L, int H, int O, int draw) {
+    return ccx_mlp::shape_ok(L, H, O, ccx_mlp::kTanh) ? (long long)ccx_mlp::lds_floats(L, H, O, draw != 0) : -1;
+}
+
 void host_activations(long long n, const float* a, float* tanh_out, float* relu_out) {
     for (long long i = 0; i < n; ++i) {
         tanh_out[i] = ccx_mlp::tanh_spec(a[i]);

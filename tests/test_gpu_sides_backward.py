@@ -149,8 +149,9 @@ def test_an_odd_row_length(batches):
 
 
 def test_the_limits(batches):
-    """L = 262, H = 256, O = 8: sub-tiles of 8 rows, the flat rows beside w2 in LDS (kernel against kernel: the spec's
-    Python loop over 69 000 elements is tests/test_mlp_backward_spec.py's business)."""
+    """L = 262, H = 256, O = 8: sub-tiles of 16 rows (ccx_mlp_grad::sub_rows; 8 rows begin at L = 372, which
+    tests/test_gpu_mlp_shapes.py runs), the flat rows beside w2 in LDS (kernel against kernel: the spec's Python loop over
+    69 000 elements is tests/test_mlp_backward_spec.py's business)."""
     batch = batches(64, 4)
     sides = make_sides(batch, (tuple(range(1, 64, 2)),), 262, 256, 8, TANH, seed=9)
     check_backward(batch, sides, 64, (5,), (), TANH, seed=10)

@@ -1,16 +1,19 @@
 """The backward rule of csrc/ccx_mlp_grad.h -- the very source the kernels of ccx_mlp_backward.hip inline -- compiled for the
 host (-O2 -ffp-contract=off) and run against the NumPy spec bit for bit: the four gradients and ga for the four shapes the
-GPU tests use, and the workspace size against its formula and at its limits.  No GPU."""
+GPU tests use and for every shape of the catalogue (tests/_mlp_shape_classes.py), which is what lets
+tests/test_gpu_mlp_shapes.py take the host rule as a reference where the spec's Python loop over the output elements is too
+slow, and the workspace size against its formula and at its limits.  No GPU."""
 
 import ctypes as C
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
-from _mlp_backward_spec import NAMES, bits32c, make_mlp_backward_case, mlp_backward_spec
+from _mlp_backward_spec import NAMES, bits32, bits32c, make_mlp_backward_case, mlp_backward_spec
+from _mlp_host_rule import compiler as _compiler
+from _mlp_host_rule import host_backward, load_backward
+from _mlp_host_rule import ptr as _p
+from _mlp_shape_classes import BACKWARD, NUMPY_SPEC_BELOW
 from _mlp_spec import SHAPES
-from test_mlp_host_rule import CSRC, _compiler, _p
 
 
 @pytest.fixture(scope="module")
@@ -18,13 +21,7 @@ def host(tmp_path_factory):
     cxx = _compiler()
     if cxx is None:
         pytest.skip("no host C++ compiler (c++, clang++ or ROCm's clang++)")
-    so = tmp_path_factory.mktemp("mlp_backward_host_rule") / "libmlp_backward_host_rule.so"
-    subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", f"-I{CSRC}",
-                    str(Path(__file__).with_name("mlp_backward_host_rule.cpp")), "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
-    lib.host_mlp_backward.restype = C.c_int
-    lib.host_mlp_backward_workspace_bytes.restype = C.c_longlong
-    return lib
+    return load_backward(cxx, tmp_path_factory.mktemp("mlp_backward_host_rule"))
 
 
 @pytest.mark.parametrize("L, H, O, act", SHAPES)
@@ -39,6 +36,21 @@ def test_gradients_equal_the_spec(host, L, H, O, act):
     assert rc == 0
     for name in NAMES + ("ga",):
         np.testing.assert_array_equal(bits32c(got[name]), bits32c(want[name]), err_msg=name)
+        assert np.isfinite(want[name]).all() and want[name].any(), name
+
+
+# every catalogue shape: two blocks (M = 258: the second of two rows) where the spec's loop over the output elements takes
+# about a second, M = 9 above; and the two-block case for one large shape, the one with a padded grad_y quad (O = 7)
+CATALOGUE = tuple((*s.dims, 258 if s.elements < NUMPY_SPEC_BELOW else 9) for s in BACKWARD) + ((511, 240, 7, 0, 258),)
+
+
+@pytest.mark.parametrize("L, H, O, act, M", CATALOGUE)
+def test_catalogue_gradients_equal_the_spec(host, L, H, O, act, M):
+    c = make_mlp_backward_case(M, L, H, O, act, seed=L + H + M)
+    want = mlp_backward_spec(c["x"], c["hidden"], c["grad_y"], c["w2"], act)
+    got = host_backward(host, c["x"], c["hidden"], c["grad_y"], c["w2"], act)
+    for name in NAMES + ("ga",):
+        np.testing.assert_array_equal(bits32(got[name]), bits32(want[name]), err_msg=name)   # finite inputs: every bit, no NaN
         assert np.isfinite(want[name]).all() and want[name].any(), name
 
 

@@ -1,26 +1,17 @@
 """The per-row rule of csrc/ccx_mlp.h -- the very source the kernels of ccx_mlp.hip inline -- compiled for the host
-(-O2 -ffp-contract=off) and run against the NumPy spec bit for bit: y and hidden for the four shapes the GPU tests use, and
-the two activations on their edge values.  No GPU."""
+(-O2 -ffp-contract=off) and run against the NumPy spec bit for bit: y and hidden for the four shapes the GPU tests use and
+for every shape of the catalogue (tests/_mlp_shape_classes.py), which is what lets tests/test_gpu_mlp_shapes.py take the
+host rule as a reference, and the two activations on their edge values.  No GPU."""
 
 import ctypes as C
-import shutil
-import subprocess
-from pathlib import Path
 
 import numpy as np
 import pytest
+from _mlp_host_rule import CSRC, host_forward, load_forward  # noqa: F401  (CSRC, _compiler and _p are imported by other tests)
+from _mlp_host_rule import compiler as _compiler
+from _mlp_host_rule import ptr as _p
+from _mlp_shape_classes import BACKWARD, EVERY_G, NUMPY_SPEC_BELOW
 from _mlp_spec import SHAPES, bits32, bits32c, make_mlp_case, mlp_spec, relu_spec, tanh_spec
-
-ROOT = Path(__file__).resolve().parent.parent
-CSRC = ROOT / "collectivecrossing_amd" / "csrc"
-
-
-def _compiler():
-    for name in ("c++", "clang++"):
-        if shutil.which(name):
-            return shutil.which(name)
-    rocm = Path("/opt/rocm/llvm/bin/clang++")
-    return str(rocm) if rocm.exists() else None
 
 
 @pytest.fixture(scope="module")
@@ -28,17 +19,7 @@ def host(tmp_path_factory):
     cxx = _compiler()
     if cxx is None:
         pytest.skip("no host C++ compiler (c++, clang++ or ROCm's clang++)")
-    so = tmp_path_factory.mktemp("mlp_host_rule") / "libmlp_host_rule.so"
-    subprocess.run([cxx, "-std=c++17", "-O2", "-ffp-contract=off", "-fPIC", "-shared", f"-I{CSRC}",
-                    str(Path(__file__).with_name("mlp_host_rule.cpp")), "-o", str(so)], check=True)
-    lib = C.CDLL(str(so))
-    lib.host_mlp.restype = C.c_int
-    lib.host_activations.restype = None
-    return lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    return load_forward(cxx, tmp_path_factory.mktemp("mlp_host_rule"))
 
 
 @pytest.mark.parametrize("L, H, O, act", SHAPES)
@@ -55,6 +36,23 @@ def test_rows_equal_the_spec(host, L, H, O, act):
         if with_hidden:
             np.testing.assert_array_equal(bits32c(hid), bits32c(want_h))
     assert np.isnan(want_y).any() and np.isfinite(want_y).any()
+
+
+# every catalogue shape at M = 258 below 20 000 output elements of the backward and at M = 9 above (the row counts of
+# tests/test_mlp_backward_host_rule.py), and the largest shape at M = 258 too; rows with NaN and infinities included
+CATALOGUE = tuple((*s.dims, 258 if s.elements < NUMPY_SPEC_BELOW else 9) for s in BACKWARD) + tuple((*d, 258) for d in EVERY_G) + ((512, 256, 8, 0, 258),)
+
+
+@pytest.mark.parametrize("L, H, O, act, M", CATALOGUE)
+def test_catalogue_rows_equal_the_spec(host, L, H, O, act, M):
+    c = make_mlp_case(M, L, H, O, seed=L + H + M)
+    want_y, want_h = mlp_spec(c["x"], c["w1t"], c["b1"], c["w2"], c["b2"], act)
+    y, hid = host_forward(host, c["x"], c["w1t"], c["b1"], c["w2"], c["b2"], act)
+    bare, none = host_forward(host, c["x"], c["w1t"], c["b1"], c["w2"], c["b2"], act, with_hidden=False)
+    np.testing.assert_array_equal(bits32c(y), bits32c(want_y))
+    np.testing.assert_array_equal(bits32c(hid), bits32c(want_h))
+    np.testing.assert_array_equal(bits32c(bare), bits32c(want_y))
+    assert none is None and np.isnan(want_y).any() and np.isfinite(want_y).any() and np.isfinite(want_h).any()
 
 
 def test_limits(host):
