@@ -171,6 +171,9 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_mlp_sample_actions": (C.c_int, [_H, C.c_int32, C.c_int32] + [C.c_void_p] * 6 + [C.c_int32] + [C.c_void_p] * 4),
     "ccx_mlp_backward_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "ccx_mlp_backward": (C.c_int, [_H, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p] * 10),
+    "ccx_mlp_wide_forward": (C.c_int, [_H, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p] * 7),
+    "ccx_mlp_wide_backward_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
+    "ccx_mlp_wide_backward": (C.c_int, [_H, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p] * 10),
     "ccx_adam_workspace_bytes": (C.c_int64, [C.c_int32, C.POINTER(C.c_int64)]),
     "ccx_adam_step": (C.c_int, [_H, C.c_int32, C.POINTER(CcxAdamTensor), C.c_float, C.c_void_p] + [C.c_float] * 5
                       + [C.c_void_p] * 3),

@@ -52,8 +52,8 @@ class CategoricalQ:
     ``z_j = vmin + (float)j * ((vmax - vmin) / (float)(A - 1))`` as the kernels compute them.  Every method that enqueues
     keeps the stream-order contract of :class:`~collectivecrossing_amd.learner.LearnerOps` through the batch's ``_enqueue``.
     Anything else than the tensors described raises ``ValueError`` before the library is called; zero rows return without
-    calling it.  Nothing is drawn here: actions are :meth:`QLearning.q_actions` on :meth:`q_values`.  Not here: a device MLP
-    head with 5 A outputs, the obs -> action fusion for categorical heads, quantile (QR-DQN / IQN) heads, noisy layers,
+    calling it.  Nothing is drawn here: actions are :meth:`QLearning.q_actions` on :meth:`q_values`.  A device network with
+    5 A outputs is :meth:`head`.  Not here: the obs -> action fusion for categorical heads, quantile (QR-DQN / IQN) heads, noisy layers,
     dueling combined with categorical heads, more than 64 atoms, bf16 / f16, the vector and RLlib adapters."""
 
     def __init__(self, batch, atoms: int = 51, vmin: float = -10.0, vmax: float = 10.0):
@@ -75,6 +75,15 @@ class CategoricalQ:
         self.atoms, self.vmin, self.vmax = int(atoms), float(lo), float(hi)
         z = (lo + (np.arange(self.atoms, dtype=np.float32) * dz).astype(np.float32)).astype(np.float32)
         self.support = torch.from_numpy(z).to(batch.device)
+
+    # ------------------------------------------------------------------ a network for the logits
+    def head(self, H: int, activation: str = "tanh", L: int | None = None, backward: str = "torch"):
+        """A :class:`~collectivecrossing_amd.wide.WideMlpHead` with ``O = 5 * atoms`` outputs shaped ``(5, atoms)``: ``head(x)``
+        on f32 [..., L] is the [..., 5, A] logits that :meth:`q_values` and :meth:`loss` take, bit-defined (include/ccx.h
+        CCX_MLP_WIDE).  The arguments are :class:`WideMlpHead`'s.  Makes no library call."""
+        from .wide import WideMlpHead
+
+        return WideMlpHead(self.batch, H, 5 * self.atoms, activation, L, backward, out_shape=(5, self.atoms))
 
     # ------------------------------------------------------------------ expected values
     def q_values(self, logits: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:

@@ -18,6 +18,11 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 // the grid of a launch over `rows` rows, rows_per_block to a workgroup: CCX_EINVAL for rows < 1 or more than 2^31 - 1 workgroups
 int row_blocks(const char* who, int64_t rows, int64_t rows_per_block, unsigned& blocks);
 
+// CCX_MLP's backward (ccx_mlp_backward.hip): enqueue head_grad_final_kernel over B block partials per element in
+// ccx_mlp_grad.h's layout -- the final step of every backward that leaves its partials so (ccx_mlp_wide.hip)
+int head_grad_final_launch(struct ::ccx_handle* h, int32_t L, int32_t H, int32_t O, double* partials, long long B, float* grad_w1t,
+                           float* grad_b1, float* grad_w2, float* grad_b2);
+
 // CCX_EPISODE_STATS (ccx_episode_stats.hip): zero the running accumulators and the latch of the masked envs on the handle's
 // stream (the resets call it while tracking is on); free the buffers (ccx_destroy)
 int episode_stats_reset(struct ::ccx_handle* h, const uint8_t* env_mask);

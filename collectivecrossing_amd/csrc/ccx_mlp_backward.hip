@@ -269,7 +269,6 @@ int backward_launches(const char* who, ccx_handle* h, int64_t rows, const SideSe
     const HeadGradArgs A{x, hidden, grad_y, w2, static_cast<double*>(workspace), grad_w1t, grad_b1, grad_w2, grad_b2, grad_a_or_null,
                          (long long)rows, (long long)blocks, L, H, O, activation, R};
     const RowImage m = row_image(L, H, O);
-    const long long elements = mg::elements_of(L, H, O);
     const dim3 grid(blocks, mg::grid_y(L, H, O));
     if (sel) {
         SideSel G = *sel;
@@ -278,13 +277,25 @@ int backward_launches(const char* who, ccx_handle* h, int64_t rows, const SideSe
     } else {
         hipLaunchKernelGGL(head_grad_blocks_kernel, grid, dim3(kThreads), bytes, h->stream, A);
     }
+    return ccxi::head_grad_final_launch(h, L, H, O, A.partials, A.B, grad_w1t, grad_b1, grad_w2, grad_b2);
+}
+
+}  // namespace
+
+// THE launch of head_grad_final_kernel, for the two entry points above and for another unit's block partials in
+// ccx_mlp_grad.h's layout (ccx_mlp_wide.hip): the kernel reads the partials, B, the sizes and the four outputs only
+int ccxi::head_grad_final_launch(ccx_handle* h, int32_t L, int32_t H, int32_t O, double* partials, long long B, float* grad_w1t,
+                                 float* grad_b1, float* grad_w2, float* grad_b2) {
+    HeadGradArgs A{};
+    A.partials = partials, A.B = B;
+    A.grad_w1t = grad_w1t, A.grad_b1 = grad_b1, A.grad_w2 = grad_w2, A.grad_b2 = grad_b2;
+    A.L = L, A.H = H, A.O = O;
+    const long long elements = mg::elements_of(L, H, O);
     hipLaunchKernelGGL(head_grad_final_kernel, dim3((unsigned)((elements + kThreads / 64 - 1) / (kThreads / 64))), dim3(kThreads), 0,
                        h->stream, A);
     CCX_HIP(hipGetLastError());
     return CCX_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

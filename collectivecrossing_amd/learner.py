@@ -893,7 +893,83 @@ MLP_ACTIVATIONS = {"tanh": 0, "relu": 1}
 MLP_BACKWARDS = ("torch", "device")
 
 
-class MlpHead(torch.nn.Module):
+class _TwoLayerHead(torch.nn.Module):
+    """What :class:`MlpHead` and :class:`~collectivecrossing_amd.wide.WideMlpHead` share, stated once: the argument checks, the
+    four parameters in the kernels' layout with ``torch.nn.Linear``'s initialisation, and the exact conversions.  No method
+    here reaches the library."""
+
+    MAX_OUTPUTS = 8
+
+    def _setup(self, batch, H, O, activation, L, backward) -> None:
+        L = batch.obs_len if L is None else L
+        for name, v, lo, hi in (("L", L, 1, 512), ("H", H, 16, 256), ("O", O, 1, self.MAX_OUTPUTS)):
+            if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
+                raise ValueError(f"{name} must be an int in {lo}..{hi}, got {v!r}")
+        if H % 16:
+            raise ValueError(f"H must be a multiple of 16, got {H}")
+        if activation not in MLP_ACTIVATIONS:
+            raise ValueError(f"activation must be one of {sorted(MLP_ACTIVATIONS)}, got {activation!r}")
+        if backward not in MLP_BACKWARDS:
+            raise ValueError(f"backward must be one of {list(MLP_BACKWARDS)}, got {backward!r}")
+        self.backward = backward
+        object.__setattr__(self, "batch", batch)                          # (not a submodule, not part of the state dict)
+        self.L, self.H, self.O, self.activation = L, H, O, activation
+        self.activation_id = MLP_ACTIVATIONS[activation]
+        self.dims = (L, H, O, self.activation_id)
+        lin1, lin2 = torch.nn.Linear(L, H), torch.nn.Linear(H, O)
+        dev = batch.device
+        self.w1t = torch.nn.Parameter(lin1.weight.detach().t().contiguous().to(dev))
+        self.b1 = torch.nn.Parameter(lin1.bias.detach().clone().to(dev))
+        self.w2 = torch.nn.Parameter(lin2.weight.detach().clone().to(dev))
+        self.b2 = torch.nn.Parameter(lin2.bias.detach().clone().to(dev))
+
+    @staticmethod
+    def _check_linear_pair(lin1, lin2) -> None:
+        if (not isinstance(lin1, torch.nn.Linear) or not isinstance(lin2, torch.nn.Linear) or lin1.bias is None
+                or lin2.bias is None or lin1.out_features != lin2.in_features or lin1.weight.dtype is not torch.float32
+                or lin2.weight.dtype is not torch.float32):
+            raise ValueError("from_linear needs two f32 torch.nn.Linear layers with biases, lin1.out_features == lin2.in_features")
+
+    def _copy_linear_pair(self, lin1, lin2):
+        with torch.no_grad():
+            self.w1t.copy_(lin1.weight.t())
+            self.b1.copy_(lin1.bias)
+            self.w2.copy_(lin2.weight)
+            self.b2.copy_(lin2.bias)
+        return self
+
+    def to_sequential(self, dtype: torch.dtype = torch.float32) -> torch.nn.Sequential:
+        """``Sequential(Linear(L, H), Tanh | ReLU, Linear(H, O))`` with exact copies of the parameters (cast to ``dtype``)."""
+        lin1 = torch.nn.Linear(self.L, self.H, device=self.w1t.device, dtype=dtype)
+        lin2 = torch.nn.Linear(self.H, self.O, device=self.w1t.device, dtype=dtype)
+        with torch.no_grad():
+            lin1.weight.copy_(self.w1t.t())
+            lin1.bias.copy_(self.b1)
+            lin2.weight.copy_(self.w2)
+            lin2.bias.copy_(self.b2)
+        return torch.nn.Sequential(lin1, torch.nn.Tanh() if self.activation == "tanh" else torch.nn.ReLU(), lin2)
+
+    def _check_parameters(self) -> None:
+        for name, shape in (("w1t", (self.L, self.H)), ("b1", (self.H,)), ("w2", (self.O, self.H)), ("b2", (self.O,))):
+            _require(name, getattr(self, name), torch.float32, shape, self.batch.device, verb="stay")
+
+
+def _torch_head_backward(relu: bool, need, gy, x, w1t, w2, hidden):
+    """The f32 torch composition of a head's backward on the saved activations (``backward="torch"``: correct to rounding, not
+    bit-defined): ``(None, grad_x, grad_w1t, grad_b1, grad_w2, grad_b2)`` as an autograd Function returns them."""
+    L, H, O = x.shape[-1], hidden.shape[-1], w2.shape[0]
+    gy, h, x2 = gy.contiguous().reshape(-1, O), hidden.reshape(-1, H), x.reshape(-1, L)
+    gh = gy @ w2
+    ga = gh * (h > 0) if relu else gh * (1.0 - h * h)
+    gx = (ga @ w1t.t()).reshape(x.shape) if need[1] else None
+    gw1t = x2.t() @ ga if need[2] else None
+    gb1 = ga.sum(0) if need[3] else None
+    gw2 = gy.t() @ h if need[4] else None
+    gb2 = gy.sum(0) if need[5] else None
+    return None, gx, gw1t, gb1, gw2, gb2
+
+
+class MlpHead(_TwoLayerHead):
     """``Linear(L, H) -> tanh | relu -> Linear(H, O)`` on the batch's device, forward in ONE kernel on the handle's stream
     (``ccx_mlp_forward``, include/ccx.h CCX_MLP).  The outputs of a row are a fixed sequence of f32 operations on that row:
     they do not depend on how many rows the call holds or where the row sits, so ``head(rows)`` on a ``[K, E, N, L]``
@@ -918,61 +994,17 @@ class MlpHead(torch.nn.Module):
     def __init__(self, batch: BatchedCollectiveCrossing, H: int, O: int = 5, activation: str = "tanh", L: int | None = None,
                  backward: str = "torch"):
         super().__init__()
-        L = batch.obs_len if L is None else L
-        for name, v, lo, hi in (("L", L, 1, 512), ("H", H, 16, 256), ("O", O, 1, 8)):
-            if not isinstance(v, int) or isinstance(v, bool) or not lo <= v <= hi:
-                raise ValueError(f"{name} must be an int in {lo}..{hi}, got {v!r}")
-        if H % 16:
-            raise ValueError(f"H must be a multiple of 16, got {H}")
-        if activation not in MLP_ACTIVATIONS:
-            raise ValueError(f"activation must be one of {sorted(MLP_ACTIVATIONS)}, got {activation!r}")
-        if backward not in MLP_BACKWARDS:
-            raise ValueError(f"backward must be one of {list(MLP_BACKWARDS)}, got {backward!r}")
-        self.backward = backward
-        object.__setattr__(self, "batch", batch)                          # (not a submodule, not part of the state dict)
-        self.L, self.H, self.O, self.activation = L, H, O, activation
-        self.activation_id = MLP_ACTIVATIONS[activation]
-        self.dims = (L, H, O, self.activation_id)
-        lin1, lin2 = torch.nn.Linear(L, H), torch.nn.Linear(H, O)
-        dev = batch.device
-        self.w1t = torch.nn.Parameter(lin1.weight.detach().t().contiguous().to(dev))
-        self.b1 = torch.nn.Parameter(lin1.bias.detach().clone().to(dev))
-        self.w2 = torch.nn.Parameter(lin2.weight.detach().clone().to(dev))
-        self.b2 = torch.nn.Parameter(lin2.bias.detach().clone().to(dev))
+        self._setup(batch, H, O, activation, L, backward)
 
     @classmethod
     def from_linear(cls, batch: BatchedCollectiveCrossing, lin1: torch.nn.Linear, lin2: torch.nn.Linear,
                     activation: str = "tanh", backward: str = "torch") -> "MlpHead":
         """The head that computes ``lin2(act(lin1(x)))``: exact copies of the two layers' f32 parameters."""
-        if (not isinstance(lin1, torch.nn.Linear) or not isinstance(lin2, torch.nn.Linear) or lin1.bias is None
-                or lin2.bias is None or lin1.out_features != lin2.in_features or lin1.weight.dtype is not torch.float32
-                or lin2.weight.dtype is not torch.float32):
-            raise ValueError("from_linear needs two f32 torch.nn.Linear layers with biases, lin1.out_features == lin2.in_features")
-        head = cls(batch, lin1.out_features, lin2.out_features, activation, lin1.in_features, backward)
-        with torch.no_grad():
-            head.w1t.copy_(lin1.weight.t())
-            head.b1.copy_(lin1.bias)
-            head.w2.copy_(lin2.weight)
-            head.b2.copy_(lin2.bias)
-        return head
-
-    def to_sequential(self, dtype: torch.dtype = torch.float32) -> torch.nn.Sequential:
-        """``Sequential(Linear(L, H), Tanh | ReLU, Linear(H, O))`` with exact copies of the parameters (cast to ``dtype``)."""
-        lin1 = torch.nn.Linear(self.L, self.H, device=self.w1t.device, dtype=dtype)
-        lin2 = torch.nn.Linear(self.H, self.O, device=self.w1t.device, dtype=dtype)
-        with torch.no_grad():
-            lin1.weight.copy_(self.w1t.t())
-            lin1.bias.copy_(self.b1)
-            lin2.weight.copy_(self.w2)
-            lin2.bias.copy_(self.b2)
-        return torch.nn.Sequential(lin1, torch.nn.Tanh() if self.activation == "tanh" else torch.nn.ReLU(), lin2)
+        cls._check_linear_pair(lin1, lin2)
+        return cls(batch, lin1.out_features, lin2.out_features, activation, lin1.in_features, backward)._copy_linear_pair(lin1, lin2)
 
     def extra_repr(self) -> str:
         return f"L={self.L}, H={self.H}, O={self.O}, activation={self.activation}, backward={self.backward}"
-
-    def _check_parameters(self) -> None:
-        for name, shape in (("w1t", (self.L, self.H)), ("b1", (self.H,)), ("w2", (self.O, self.H)), ("b2", (self.O,))):
-            _require(name, getattr(self, name), torch.float32, shape, self.batch.device, verb="stay")
 
     def forward(self, x: torch.Tensor, out: torch.Tensor | None = None, hidden_out: torch.Tensor | None = None) -> torch.Tensor:
         b = self.batch
@@ -1027,12 +1059,4 @@ class _MlpForward(torch.autograd.Function):
             gx = (out.grad_a.reshape(-1, H) @ w1t.t()).reshape(x.shape) if need[1] else None
             return (None, gx, out.w1t if need[2] else None, out.b1 if need[3] else None, out.w2 if need[4] else None,
                     out.b2 if need[5] else None)
-        gy, h, x2 = gy.contiguous().reshape(-1, O), hidden.reshape(-1, H), x.reshape(-1, L)
-        gh = gy @ w2
-        ga = gh * (h > 0) if ctx.relu else gh * (1.0 - h * h)
-        gx = (ga @ w1t.t()).reshape(x.shape) if need[1] else None
-        gw1t = x2.t() @ ga if need[2] else None
-        gb1 = ga.sum(0) if need[3] else None
-        gw2 = gy.t() @ h if need[4] else None
-        gb2 = gy.sum(0) if need[5] else None
-        return None, gx, gw1t, gb1, gw2, gb2
+        return _torch_head_backward(ctx.relu, need, gy, x, w1t, w2, hidden)

@@ -1580,8 +1580,8 @@ int ccx_minibatch_permutation(ccx_handle* h, int64_t M, int64_t epoch, int64_t* 
  * that a grid would pass 2^31 - 1 workgroups), atoms outside 2 .. 64, a vmin or vmax that is not finite, vmin >= vmax, a
  * spacing that is not finite or not above zero, a gamma that is not finite or lies outside [0, 1] when discount is NULL
  * (with discount given gamma is not read), a misaligned pointer: CCX_EINVAL with a ccx_last_error message, before any launch.
- * The feature draws nothing: actions come from ccx_q_actions on the expected values.  Not here: a device MLP head with 5 A
- * outputs, the obs -> action fusion for categorical heads, quantile (QR-DQN / IQN) heads, noisy layers, dueling combined
+ * The feature draws nothing: actions come from ccx_q_actions on the expected values.  (A device network with 5 A outputs
+ * is CCX_MLP_WIDE.)  Not here: the obs -> action fusion for categorical heads, quantile (QR-DQN / IQN) heads, noisy layers, dueling combined
  * with categorical heads, more than 64 atoms, bf16 / f16, the vector and RLlib adapters.
  */
 int64_t ccx_c51_workspace_bytes(int64_t rows);
@@ -1597,6 +1597,44 @@ int ccx_c51_loss_backward(ccx_handle* h, int64_t rows, int32_t atoms, const floa
                           const uint8_t* actions /* [M] */, const float* proj /* [M][A] */, const uint8_t* valid_or_null /* [M] */,
                           const float* weights_or_null /* [M] */, const float* stats /* [8] */,
                           const float* grad_loss_or_null /* [1] */, float* grad_logits /* [M][5][A] */);
+/*
+ * CCX_MLP_WIDE: CCX_MLP with up to 320 outputs -- the [5][A] atom logits of a categorical head (CCX_C51: 255 at A = 51, 320
+ * at A = 64) from the observation rows, and the parameter gradients from the gradient of those logits.  The rule is
+ * CCX_MLP's, forward and backward, word for word, with 1 <= O <= 320 in the place of 1 <= O <= 8: the layer-1 chain over k,
+ * the activations, the layer-2 partials over groups of 16 hidden units added in group order onto b2[o]; the gh chain over
+ * o = 0 .. O-1 ascending, ga, the f64 terms, the chains over blocks of 256 rows and CCX_PPO_LOSS's final step.  The limits
+ * on L, H and activation, the layouts (y f32 [rows][O], grad_y f32 [rows][O], w2 and grad_w2 f32 [O][H], b2 and grad_b2
+ * f32 [O]), the alignment demands (x, hidden and grad_a 16 bytes, the workspace 8, every other f32 array 4: a row of y or
+ * grad_y is 4 O bytes, 1020 at A = 51, and may start at any multiple of 4), the 64-bit offsets, the written-every-element
+ * rule and the refusals are CCX_MLP's as well.  So for O <= 8 the entry points below give the bits of ccx_mlp_forward and
+ * ccx_mlp_backward on the same arrays, and a row's outputs depend on nothing but the row and the parameters.
+ *
+ * What differs is inside: ccx_mlp_wide_forward is ONE kernel that runs layer 2 over chunks of consecutive outputs,
+ * ccx_mlp_wide_backward TWO plain launches (block partials with w2 streamed in slabs of consecutive o -- the order of the
+ * gh chain is the slabs' order --, then CCX_MLP's final step; no floating-point atomic, no last-block-done counter).  Both
+ * enqueue on the handle's stream only, neither allocates nor synchronises, both capture into a HIP graph.
+ * ccx_mlp_wide_backward_workspace_bytes(rows, L, H, O) = B * (L * H + H + O * H + O) * 8 bytes with B = ceil(rows / 256)
+ * (0 for rows < 1 or a shape outside the limits).  A shape outside the limits is CCX_EINVAL with a ccx_last_error message
+ * that names L, H, O and activation, before any launch; ccx_mlp_forward / ccx_mlp_backward / CCX_SIDES / ccx_mlp_q_actions
+ * keep their own limit of 8.
+ * Against IEEE f64 (measured on the CPU, tests/test_mlp_wide_spec.py, maxima doubled; the compositions and the measure
+ * are CCX_MLP's), L = 38, H = 64, O = 255, torch.nn.Linear's initial weights, observation-like rows, tanh and relu, M = 20 000: the logits
+ * within 4.8e-6 absolute; grad_w1t within 5.3e-4, grad_b1 1.1e-4, grad_w2 1.2e-7, grad_b2 1.14e-7 (gh sums 255 terms of a
+ * standard-normal grad_y here, 5 there: the first two figures grow with it).
+ *
+ * Not here: the fusion of obs -> head -> expected values -> epsilon-greedy action into one launch, wide heads in CCX_SIDES
+ * or CCX_DUELING, more than 320 outputs, deeper networks, a bit-defined gradient with respect to x, matrix-core (MFMA)
+ * arithmetic -- the rule is a chain of f32 operations --, bf16 / f16.
+ */
+int ccx_mlp_wide_forward(ccx_handle* h, int64_t rows, int32_t L, int32_t H, int32_t O, int32_t activation,
+                         const float* x /* [rows][L] */, const float* w1t /* [L][H] */, const float* b1 /* [H] */,
+                         const float* w2 /* [O][H] */, const float* b2 /* [O] */, float* y /* [rows][O] */,
+                         float* hidden_or_null /* [rows][H] */);
+int64_t ccx_mlp_wide_backward_workspace_bytes(int64_t rows, int32_t L, int32_t H, int32_t O);
+int ccx_mlp_wide_backward(ccx_handle* h, int64_t rows, int32_t L, int32_t H, int32_t O, int32_t activation,
+                          const float* x /* [rows][L] */, const float* hidden /* [rows][H] */, const float* grad_y /* [rows][O] */,
+                          const float* w2 /* [O][H] */, void* workspace, float* grad_w1t /* [L][H] */, float* grad_b1 /* [H] */,
+                          float* grad_w2 /* [O][H] */, float* grad_b2 /* [O] */, float* grad_a_or_null /* [rows][H] */);
 /*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
