@@ -376,7 +376,7 @@ Launched launch_short(ccx_handle* h, const StepCall& c, const ccxp::LaunchPlan& 
     uint8_t* const m = lp.masks_fused ? c.masks : nullptr;
     const ccx::StepResetObs* const r = lp.reset_obs_fused ? c.rso : nullptr;
     hipError_t e = ccx::launch_step(h->step_shape, h->stream, launch_params(h), h->st_slab, h->cell_info, c.actions, c.order, c.K,
-                                    c.auto_reset, h->pool, c.out, h->counters, c.mixed ? &pol : nullptr, m, r);
+                                    c.auto_reset, h->pool, c.out, h->counters, c.mixed ? &pol : nullptr, m, r, &h->last_key);
     if (e != hipSuccess) return fail(CCX_EHIP, "step kernel launch failed: %s", hipGetErrorString(e));
     Launched l(end_timed(h));
     l.masks_written = m != nullptr, l.reset_obs_written = r != nullptr;
@@ -417,7 +417,7 @@ int launch_paced(ccx_handle* h, const StepCall& c, const ccxp::LaunchPlan& lp, b
         shape.num_blocks = std::min(lp.per_round, num_blocks - b0);
         kp.block_base = (uint32_t)b0;
         e = ccx::launch_rollout(shape, h->stream, kp, h->st, h->cell_info, c.actions,
-                                c.order, c.K, c.auto_reset, h->pool, c.out, h->counters, c.policy, c.actions_out);
+                                c.order, c.K, c.auto_reset, h->pool, c.out, h->counters, c.policy, c.actions_out, &h->last_key);
     }
     if (e != hipSuccess) return fail(CCX_EHIP, "rollout kernel launch failed: %s", hipGetErrorString(e));
     if (lp.flip_slot) h->pace.slot ^= 1u;
@@ -827,7 +827,7 @@ int ccx_observe(ccx_handle* h, float* obs) {
     if (!h || !obs) return fail(CCX_EINVAL, "NULL argument");
     if (misaligned(16, obs)) return fail(CCX_EINVAL, "obs buffer must be 16-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
-    hipError_t e = ccx::launch_observe(h->shape, h->stream, h->kp, h->st, obs);
+    hipError_t e = ccx::launch_observe(h->shape, h->stream, h->kp, h->st, obs, &h->last_observe_key);
     if (e != hipSuccess) return fail(CCX_EHIP, "observe kernel launch failed: %s", hipGetErrorString(e));
     return CCX_OK;
 }
@@ -838,7 +838,7 @@ int ccx_expand_observations(ccx_handle* h, const float* obs_compact, int64_t row
     if (misaligned(16, obs, obs_compact))
         return fail(CCX_EINVAL, "obs and obs_compact must be 16-byte aligned");
     CCX_HIP(hipSetDevice(h->device));
-    hipError_t e = ccx::launch_expand(h->shape, h->stream, h->kp, obs_compact, rows, obs);
+    hipError_t e = ccx::launch_expand(h->shape, h->stream, h->kp, obs_compact, rows, obs, &h->last_observe_key);
     if (e != hipSuccess) return fail(CCX_EHIP, "expand kernel launch failed: %s", hipGetErrorString(e));
     return CCX_OK;
 }
@@ -1417,6 +1417,13 @@ int ccxi_handle_call_plan(const ccx_handle* h, const ccxi_call_in* call, int lau
     in.step_kernel = h->tun_step_kernel; in.max_launch_steps = h->tun_max_launch_steps; in.reset_obs_fused = h->tun_reset_obs_fused;
     if (ccxp::plan_call_out(call_facts(h), in, launch, out) != CCX_OK)
         return fail(CCX_EINVAL, "K = %d has no launch number %d", in.K, launch);
+    return CCX_OK;
+}
+
+// (ccx_keys.h)
+int ccxi_handle_last_key(const ccx_handle* h, int which, ccxi_key* out) {
+    if (!h || !out || which < 0 || which > 1) return fail(CCX_EINVAL, "bad argument");
+    *out = which ? h->last_observe_key : h->last_key;
     return CCX_OK;
 }
 

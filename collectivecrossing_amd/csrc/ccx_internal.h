@@ -118,6 +118,8 @@ struct ccx_handle {
     int32_t* stats_count = nullptr;                             // device i32 [E]: records of the current update per env (log only)
     long long* stats_base = nullptr;                            // device i64 [E]: log slot of each env's first record of the update
     int tun_stats_naive = 0;                                    // 1: the accumulate kernel with one dependent load per step (timing table only)
+    ccxi_key last_key{CCXI_KEY_NONE, {}};                       // ccx_keys.h: the instantiation the last stepping launch took, written by the launch path ...
+    ccxi_key last_observe_key{CCXI_KEY_NONE, {}};               // ... and the one of the last ccx_observe / ccx_expand_observations
     uint32_t eps_thr = 0;                                       // epsilon * 2^32 of the scripted policies (ccx_set_policy_epsilon); the launchers copy the three into their KParams
 };
 

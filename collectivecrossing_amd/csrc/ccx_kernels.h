@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ccx_keys.h"        // which instantiation a launch takes (host only)
 #include "ccx_step_rule.h"   // the cell word, the reward, the flag bytes, the pool cursor (and CCX_K_REWARD_*, CCX_K_EF_*)
 
 namespace ccx {
@@ -257,7 +258,7 @@ constexpr bool step_reset_obs_fused(int K, bool has_order, bool has_policy) { re
 hipError_t launch_step(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
                        const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K, int auto_reset,
                        const uint8_t* pool, const KOut& out, unsigned long long* counters, const StepPolicy* pol = nullptr,
-                       uint8_t* masks = nullptr, const struct StepResetObs* rso = nullptr);
+                       uint8_t* masks = nullptr, const struct StepResetObs* rso = nullptr, ccxi_key* launched = nullptr);
 // Legal-action masks (include/ccx.h: CCX_ACTION_MASKS), u8 [E][N] of the handle's current state.  launch_step writes them
 // itself (`masks`) where step_masks_fused says so -- the MSK instantiations of ccx_step.hip: ONE env-step without a move
 // order, with or without a scripted policy; every other launch is followed by launch_action_masks on the same stream.
@@ -285,14 +286,14 @@ hipError_t launch_rollout(const LaunchShape& ls, hipStream_t stream, const KPara
                           const KState& st, const unsigned long long* cell_info,
                           const uint8_t* actions, const uint8_t* order, int K,
                           int auto_reset, const uint8_t* pool, const KOut& out,
-                          unsigned long long* counters, int policy = 0, uint8_t* actions_out = nullptr);
+                          unsigned long long* counters, int policy = 0, uint8_t* actions_out = nullptr, ccxi_key* launched = nullptr);
 int rollout_blocks_per_cu(const LaunchShape& ls, int agents);
 hipError_t launch_reduce_counters(hipStream_t stream, unsigned long long* counters, int slots);
 hipError_t launch_observe(const LaunchShape& ls, hipStream_t stream, const KParams& p,
-                          const KState& st, float* obs);
+                          const KState& st, float* obs, ccxi_key* launched = nullptr);
 // DefaultObservation rows [rows][N][L] from compact rows [rows][N][4] (rows = envs x steps)
 hipError_t launch_expand(const LaunchShape& ls, hipStream_t stream, const KParams& p, const float* compact,
-                         long long rows, float* obs);
+                         long long rows, float* obs, ccxi_key* launched = nullptr);
 hipError_t launch_reset_from_pool(hipStream_t stream, const KParams& p, const KState& st,
                                   const uint8_t* env_mask, const uint8_t* pool);
 // streams `bytes` (a multiple of 16) of filler into `dst` with the rollout's own store instruction: the pace calibration probe

@@ -136,7 +136,7 @@ __global__ void reset_from_pool_kernel(const KParams p, const KState st,
 #define CCX_DECL_GLOG(n)                                                                                              \
     hipError_t launch_rollout_glog##n(const LaunchShape&, hipStream_t, const KParams&, const KState&,                 \
                                       const unsigned long long*, const uint8_t*, const uint8_t*, int, int,            \
-                                      const uint8_t*, const KOut&, unsigned long long*, int, uint8_t*);               \
+                                      const uint8_t*, const KOut&, unsigned long long*, int, uint8_t*, ccxi_key*);    \
     int blocks_per_cu_glog##n(const LaunchShape&, bool);
 CCX_DECL_GLOG(0) CCX_DECL_GLOG(1) CCX_DECL_GLOG(2) CCX_DECL_GLOG(3) CCX_DECL_GLOG(4) CCX_DECL_GLOG(5) CCX_DECL_GLOG(6)
 #undef CCX_DECL_GLOG
@@ -172,10 +172,11 @@ int rollout_blocks_per_cu(const LaunchShape& ls, int agents) {
 
 template <int GLOG>
 static hipError_t launch_observe_g(const LaunchShape& ls, hipStream_t stream, const KParams& p,
-                                   const KState& st, float* obs, const float4* compact, unsigned blocks) {
-    const bool pair = (p.N % 2) == 0;
+                                   const KState& st, float* obs, const float4* compact, unsigned blocks, ccxi_key* launched) {
+    const ObserveKey key = observe_key(GLOG, p.N);
+    if (launched) *launched = pack_key(key);
     dim3 grid(blocks), block(64 * ls.waves_per_block);
-    if (pair)
+    if (key.pair)
         hipLaunchKernelGGL((observe_kernel<GLOG, true>), grid, block, ls.lds_bytes_observe, stream, p, st, obs, compact);
     else
         hipLaunchKernelGGL((observe_kernel<GLOG, false>), grid, block, ls.lds_bytes_observe, stream, p, st, obs, compact);
@@ -186,75 +187,75 @@ hipError_t launch_rollout(const LaunchShape& ls, hipStream_t stream, const KPara
                           const KState& st, const unsigned long long* cell_info,
                           const uint8_t* actions, const uint8_t* order, int K,
                           int auto_reset, const uint8_t* pool, const KOut& out,
-                          unsigned long long* counters, int policy, uint8_t* actions_out) {
+                          unsigned long long* counters, int policy, uint8_t* actions_out, ccxi_key* launched) {
     switch (ls.glog) {
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 0
-    case 0: return launch_rollout_glog0(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out);
+    case 0: return launch_rollout_glog0(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out, launched);
 #endif
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 1
-    case 1: return launch_rollout_glog1(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out);
+    case 1: return launch_rollout_glog1(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out, launched);
 #endif
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 2
-    case 2: return launch_rollout_glog2(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out);
+    case 2: return launch_rollout_glog2(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out, launched);
 #endif
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 3
-    case 3: return launch_rollout_glog3(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out);
+    case 3: return launch_rollout_glog3(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out, launched);
 #endif
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 4
-    case 4: return launch_rollout_glog4(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out);
+    case 4: return launch_rollout_glog4(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out, launched);
 #endif
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 5
-    case 5: return launch_rollout_glog5(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out);
+    case 5: return launch_rollout_glog5(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out, launched);
 #endif
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 6
-    case 6: return launch_rollout_glog6(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out);
+    case 6: return launch_rollout_glog6(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out, launched);
 #endif
     }
     return hipErrorInvalidValue;
 }
 
 static hipError_t launch_observe_any(const LaunchShape& ls, hipStream_t stream, const KParams& p, const KState& st,
-                                     float* obs, const float4* compact, unsigned blocks) {
+                                     float* obs, const float4* compact, unsigned blocks, ccxi_key* launched) {
     switch (ls.glog) {
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 0
-    case 0: return launch_observe_g<0>(ls, stream, p, st, obs, compact, blocks);
+    case 0: return launch_observe_g<0>(ls, stream, p, st, obs, compact, blocks, launched);
 #endif
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 1
-    case 1: return launch_observe_g<1>(ls, stream, p, st, obs, compact, blocks);
+    case 1: return launch_observe_g<1>(ls, stream, p, st, obs, compact, blocks, launched);
 #endif
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 2
-    case 2: return launch_observe_g<2>(ls, stream, p, st, obs, compact, blocks);
+    case 2: return launch_observe_g<2>(ls, stream, p, st, obs, compact, blocks, launched);
 #endif
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 3
-    case 3: return launch_observe_g<3>(ls, stream, p, st, obs, compact, blocks);
+    case 3: return launch_observe_g<3>(ls, stream, p, st, obs, compact, blocks, launched);
 #endif
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 4
-    case 4: return launch_observe_g<4>(ls, stream, p, st, obs, compact, blocks);
+    case 4: return launch_observe_g<4>(ls, stream, p, st, obs, compact, blocks, launched);
 #endif
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 5
-    case 5: return launch_observe_g<5>(ls, stream, p, st, obs, compact, blocks);
+    case 5: return launch_observe_g<5>(ls, stream, p, st, obs, compact, blocks, launched);
 #endif
 #if !defined(CCX_ONLY_GLOG) || CCX_ONLY_GLOG == 6
-    case 6: return launch_observe_g<6>(ls, stream, p, st, obs, compact, blocks);
+    case 6: return launch_observe_g<6>(ls, stream, p, st, obs, compact, blocks, launched);
 #endif
     }
     return hipErrorInvalidValue;
 }
 
 hipError_t launch_observe(const LaunchShape& ls, hipStream_t stream, const KParams& p,
-                          const KState& st, float* obs) {
-    return launch_observe_any(ls, stream, p, st, obs, nullptr, (unsigned)ls.num_blocks);
+                          const KState& st, float* obs, ccxi_key* launched) {
+    return launch_observe_any(ls, stream, p, st, obs, nullptr, (unsigned)ls.num_blocks, launched);
 }
 
 hipError_t launch_expand(const LaunchShape& ls, hipStream_t stream, const KParams& p, const float* compact,
-                         long long rows, float* obs) {
+                         long long rows, float* obs, ccxi_key* launched) {
     if (rows <= 0) return hipSuccess;
     KParams q = p;                 // same lane layout, `rows` envs instead of the handle's E
     q.E = (int)rows;
     const long long per_block = (long long)p.EW * p.waves_per_block;
     const long long blocks = (rows + per_block - 1) / per_block;
     if (rows > 0x7FFFFFFFll || blocks > 0x7FFFFFFFll) return hipErrorInvalidValue;
-    return launch_observe_any(ls, stream, q, KState{}, obs, reinterpret_cast<const float4*>(compact), (unsigned)blocks);
+    return launch_observe_any(ls, stream, q, KState{}, obs, reinterpret_cast<const float4*>(compact), (unsigned)blocks, launched);
 }
 
 // Pace calibration probe (ccx_api.hip: probe_write_rate): a plain fill of the caller's own trajectory buffer -- one

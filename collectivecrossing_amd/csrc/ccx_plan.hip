@@ -734,6 +734,99 @@ size_t step_lds_bytes(int glog, int ew, int N, int cells, bool reward_table) {
 }
 }  // namespace ccx
 
+// ---- ccx_keys.h: the instantiation a launch of a call takes, from the plans and the call ----------------------------------
+namespace {
+
+struct KeyShapes {            // the two planned shapes of a handle, as far as the keys read them
+    ccxp::CallFacts f;
+    ccxp::ShapePlan sp[2];
+};
+
+KeyShapes key_shapes(const ccxi_plan_in& in, const int* blocks_per_cu) {
+    KeyShapes ks{};
+    ks.f = ccxp::CallFacts{in.E, in.N, {}};
+    for (int i = 0; i < 2; ++i) {
+        ccxp::PlanIn pin = in;
+        pin.rows = i == 0 ? 1 : 0;
+        ks.sp[i] = ccxp::plan_shape(pin);
+        const ccxp::PacePlan pp = ccxp::plan_pacing(pin, ks.sp[i], blocks_per_cu[i]);
+        ks.f.shape[i] = ccxp::CallShape{ks.sp[i].shape.num_blocks, pp.resident_blocks, pp.step_bytes, pp.paced, pp.pace_adapt,
+                                        pp.pace_min_k, pp.adapt_min_k, pp.ring_when_paced, ks.sp[i].step.ok != 0};
+    }
+    return ks;
+}
+
+// the key of the launch of k steps that begins at step k0 of the call c (what ccx_api.hip hands to launch_step / launch_rollout)
+ccxi_key launch_key(const ccxi_plan_in& in, const KeyShapes& ks, const ccxp::CallIn& c, const ccxi_key_facts& kf, int k0, int k) {
+    const ccxp::LaunchPlan lp = ccxp::plan_launch(ks.f, c, k);
+    if (lp.kernel == ccxp::KERNEL_STEP)
+        return ccx::pack_key(ccx::step_key(ks.sp[0].step.glog, in.N, k, c.order != 0, c.mixed != 0, lp.masks_fused, lp.reset_obs_fused));
+    const ccxp::ShapePlan& sp = ks.sp[lp.shape];
+    const bool has_obs = kf.obs != 0;
+    const size_t residue = ((size_t)kf.obs_residue + (size_t)k0 * ccxp::obs_bytes(in.E, in.N)) & 127u;   // (kout_at)
+    return ccx::pack_key(ccx::rollout_key(ccx::RolloutFacts{
+        sp.shape.glog, in.N, in.E, sp.kp.EW, sp.kp.units_per_wave, sp.shape.writers, sp.kp.writer0_small != 0u, sp.shape.occ != 0,
+        has_obs || kf.reward || kf.agent_flags || kf.env_flags || kf.obs_compact || c.actions_out, has_obs, (uint32_t)residue,
+        c.order != 0, c.policy != 0, in.reward_table != 0 || in.term_table != 0}));
+}
+
+int call_key(const ccxi_plan_in& in, const KeyShapes& ks, ccxp::CallIn c, const ccxi_key_facts& kf, int launch, ccxi_key* out) {
+    if (c.K < 1 || in.E < 1 || in.N < 1) return CCX_EINVAL;
+    c.writes_obs = kf.obs != 0;
+    const ccxp::CallPlan cp = ccxp::plan_call(ks.f, c);
+    *out = ccxi_key{CCXI_KEY_NONE, {}};
+    if (cp.refused) return CCX_OK;
+    if (launch < 0) launch = cp.launches - 1;          // (the last one)
+    if (launch >= cp.launches) return CCX_EINVAL;
+    const int k0 = launch * cp.steps_per_launch, k = std::min(cp.steps_per_launch, c.K - k0);
+    if (cp.stepwise) {
+        // ccx_api.hip: run_stepwise -- the one-step call of the actions the policy and merge kernels left, in the caller's order
+        ccxp::CallIn one{};
+        one.K = 1; one.actions = 1; one.order = c.order; one.writes_obs = c.writes_obs; one.capturing = c.capturing;
+        one.hand2 = c.hand2; one.round_launches = c.round_launches; one.small_shape = c.small_shape; one.step_kernel = c.step_kernel;
+        one.max_launch_steps = c.max_launch_steps; one.reset_obs_fused = c.reset_obs_fused;
+        // (a step whose slice of the tensor is not 16-byte aligned writes its rows to the aligned staging slab)
+        ccxi_key_facts kf1 = kf;
+        kf1.obs_residue = (int32_t)(((size_t)kf.obs_residue + (size_t)k0 * ccxp::obs_bytes(in.E, in.N)) & 127u);
+        if (kf1.obs_residue & 15) kf1.obs_residue = 0;
+        *out = launch_key(in, ks, one, kf1, 0, 1);
+        return CCX_OK;
+    }
+    *out = launch_key(in, ks, c, kf, k0, k);
+    return CCX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ccxi_call_key(const ccxi_plan_in* in, const int* blocks_per_cu, const ccxi_call_in* call, const ccxi_key_facts* facts, int launch,
+                  ccxi_key* out) {
+    if (!in || !blocks_per_cu || !call || !facts || !out) return CCX_EINVAL;
+    return call_key(*in, key_shapes(*in, blocks_per_cu), *call, *facts, launch, out);
+}
+
+int ccxi_call_keys(const ccxi_plan_in* in, const int* blocks_per_cu, const ccxi_call_in* calls, const ccxi_key_facts* facts, int n,
+                   ccxi_key* out) {
+    if (!in || !blocks_per_cu || !calls || !facts || !out || n < 0) return CCX_EINVAL;
+    const KeyShapes ks = key_shapes(*in, blocks_per_cu);
+    for (int i = 0; i < n; ++i) {
+        if (int rc = call_key(*in, ks, calls[i], facts[i], 0, out + 2 * i)) return rc;
+        if (int rc = call_key(*in, ks, calls[i], facts[i], -1, out + 2 * i + 1)) return rc;
+    }
+    return CCX_OK;
+}
+
+int ccxi_observe_key(const ccxi_plan_in* in, ccxi_key* out) {
+    if (!in || !out) return CCX_EINVAL;
+    ccxp::PlanIn pin = *in;
+    pin.rows = 1;
+    *out = ccx::pack_key(ccx::observe_key(ccxp::plan_shape(pin).shape.glog, in->N));
+    return CCX_OK;
+}
+
+}  // extern "C"
+
 extern "C" {
 
 const char* ccxi_plan_field_names(void) {

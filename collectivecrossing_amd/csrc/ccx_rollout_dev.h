@@ -274,7 +274,7 @@ __device__ __forceinline__ void emit_obs(const WaveLds* wl, const uint16_t* tabl
 #endif
 
 constexpr int kActBatch = 16;      // env-steps of actions fetched per global-load burst
-constexpr int kFastObsIters = 10;  // observation store iterations whose LDS addresses live in VGPRs
+// (kFastObsIters, the observation store iterations whose LDS addresses live in VGPRs: ccx_keys.h -- the dispatch reads it)
 constexpr int kObsBatch = 5;       // LDS reads issued back to back before their stores
 
 // ---------------------------------------------------------------------------------------------

@@ -32,20 +32,14 @@ static hipError_t launch_rollout_g(const LaunchShape& ls, hipStream_t stream, co
                                    const KState& st, const unsigned long long* cell_info,
                                    const uint8_t* actions, const uint8_t* order, int K,
                                    int auto_reset, const uint8_t* pool, const KOut& out,
-                                   unsigned long long* counters, int policy, uint8_t* actions_out) {
-    const bool pair = (p.N % 2) == 0;
-    const bool want_out = out.obs || out.reward || out.agent_flags || out.env_flags || out.obs_compact || actions_out;
-    // edge iterations: the tile regions of the observation output share 128-byte lines with their neighbours
-    const size_t tile_region = (size_t)p.EW * p.N * (6 + 4 * p.N) * 4u, slab = (size_t)p.E * p.N * (6 + 4 * p.N) * 4u;
-    const bool edges = out.obs && (((tile_region | slab) & 127u) != 0 || (reinterpret_cast<uintptr_t>(out.obs) & 127u) != 0);
-    // (3: the slab stride itself is not a multiple of 128 bytes -- `lead` per step, ccx_rollout_body.inc: VARLEAD -- and a row
-    //  writer has more store iterations than it caches source addresses for: 50 agents x 532 envs 0.50 -> 0.88 of the peak.  Narrow
-    //  rows, all of whose iterations are register-cached, are faster with the launch-wide layout: 3 agents 0.28 vs 0.19.)
-    const int row_writers = std::max(1, ls.writers - ((p.writer0_small && ls.writers > 1) ? 1 : 0));
-    const int its = ((p.units_per_wave >> (pair ? 1 : 0)) + 63) / 64;
-    const bool long_rows = (its + row_writers - 1) / row_writers > kFastObsIters;
-    const int outm = want_out ? (edges ? ((slab & 127u) != 0 && long_rows ? 3 : 2) : 1) : 0;
-    const bool plain = order == nullptr && policy == 0 && p.user_tables == 0u;   // (user reward / terminated tables: the general instantiations)
+                                   unsigned long long* counters, int policy, uint8_t* actions_out, ccxi_key* launched) {
+    const RolloutKey key = rollout_key(RolloutFacts{
+        GLOG, p.N, p.E, p.EW, p.units_per_wave, ls.writers, p.writer0_small != 0, ls.occ != 0,
+        out.obs || out.reward || out.agent_flags || out.env_flags || out.obs_compact || actions_out, out.obs != nullptr,
+        (uint32_t)(reinterpret_cast<uintptr_t>(out.obs) & 127u), order != nullptr, policy != 0, p.user_tables != 0u});
+    if (launched) *launched = pack_key(key);
+    const bool pair = key.pair, plain = key.plain;
+    const int outm = key.out;
 #define CCX_GO2(P_, O_, C_)                                                                                  \
     return plain ? launch_rollout_v<GLOG, P_, O_, C_, true>(ls, stream, p, st, cell_info, actions, order, K, \
                                                             auto_reset, pool, out, counters, policy, actions_out) \
@@ -58,9 +52,9 @@ static hipError_t launch_rollout_g(const LaunchShape& ls, hipStream_t stream, co
     case 1: CCX_GO2(P_, 1, C_);       \
     default: CCX_GO2(P_, 0, C_);      \
     }
-    if (pair && ls.occ) { CCX_GO(true, true) }
+    if (pair && key.occ) { CCX_GO(true, true) }
     else if (pair) { CCX_GO(true, false) }
-    else if (ls.occ) { CCX_GO(false, true) }
+    else if (key.occ) { CCX_GO(false, true) }
     else { CCX_GO(false, false) }
 #undef CCX_GO2
 #undef CCX_GO
@@ -92,8 +86,8 @@ static int blocks_per_cu_g(const LaunchShape& ls, bool pair) {
 hipError_t CCX_CAT(launch_rollout_glog, CCX_GLOG)(const LaunchShape& ls, hipStream_t stream, const KParams& p, const KState& st,
                                                  const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order,
                                                  int K, int auto_reset, const uint8_t* pool, const KOut& out,
-                                                 unsigned long long* counters, int policy, uint8_t* actions_out) {
-    return launch_rollout_g<CCX_GLOG>(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out);
+                                                 unsigned long long* counters, int policy, uint8_t* actions_out, ccxi_key* launched) {
+    return launch_rollout_g<CCX_GLOG>(ls, stream, p, st, cell_info, actions, order, K, auto_reset, pool, out, counters, policy, actions_out, launched);
 }
 int CCX_CAT(blocks_per_cu_glog, CCX_GLOG)(const LaunchShape& ls, bool pair) { return blocks_per_cu_g<CCX_GLOG>(ls, pair); }
 

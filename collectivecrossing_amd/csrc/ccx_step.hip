@@ -710,8 +710,11 @@ template <int GLOG>
 static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
                                 const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K,
                                 int auto_reset, const uint8_t* pool, const KOut& out, unsigned long long* counters,
-                                const StepPolicy* pol, uint8_t* masks, const StepResetObs* rso) {
-    const bool pair = (p.N % 2) == 0;
+                                const StepPolicy* pol, uint8_t* masks, const StepResetObs* rso, ccxi_key* launched) {
+    if (masks && !step_masks_fused(K, order != nullptr)) return hipErrorInvalidValue;
+    if (rso && !step_reset_obs_fused(K, order != nullptr, pol != nullptr)) return hipErrorInvalidValue;
+    const StepKey key = step_key(GLOG, p.N, K, order != nullptr, pol != nullptr, masks != nullptr, rso != nullptr);
+    const bool pair = key.pair;
     // the instantiations that also redirect the rows of restarted envs (step_reset_obs_fused), with or without the masks
     auto pick_rso = [&](auto msk_c) -> const void* {
         constexpr bool MSK = decltype(msk_c)::value;
@@ -726,17 +729,16 @@ static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const K
     };
     auto pick = [&](auto ord_c, auto pol_c) -> const void* {
         constexpr bool ORD = decltype(ord_c)::value, POL = decltype(pol_c)::value;
-        return K == 1 ? (pair ? reinterpret_cast<const void*>(&step_kernel<GLOG, true, true, ORD, POL>)
+        return key.k1 ? (pair ? reinterpret_cast<const void*>(&step_kernel<GLOG, true, true, ORD, POL>)
                               : reinterpret_cast<const void*>(&step_kernel<GLOG, false, true, ORD, POL>))
                       : (pair ? reinterpret_cast<const void*>(&step_kernel<GLOG, true, false, ORD, POL>)
                               : reinterpret_cast<const void*>(&step_kernel<GLOG, false, false, ORD, POL>));
     };
-    if (masks && !step_masks_fused(K, order != nullptr)) return hipErrorInvalidValue;
-    if (rso && !step_reset_obs_fused(K, order != nullptr, pol != nullptr)) return hipErrorInvalidValue;
-    const void* entry = rso ? (masks ? pick_rso(std::true_type{}) : pick_rso(std::false_type{}))
-                      : masks ? (pol ? pick_msk(std::true_type{}) : pick_msk(std::false_type{}))
-                      : pol ? (order ? pick(std::true_type{}, std::true_type{}) : pick(std::false_type{}, std::true_type{}))
-                            : (order ? pick(std::true_type{}, std::false_type{}) : pick(std::false_type{}, std::false_type{}));
+    const void* entry = key.rso ? (key.msk ? pick_rso(std::true_type{}) : pick_rso(std::false_type{}))
+                      : key.msk ? (key.pol ? pick_msk(std::true_type{}) : pick_msk(std::false_type{}))
+                      : key.pol ? (key.ord ? pick(std::true_type{}, std::true_type{}) : pick(std::false_type{}, std::true_type{}))
+                                : (key.ord ? pick(std::true_type{}, std::false_type{}) : pick(std::false_type{}, std::false_type{}));
+    if (launched) *launched = pack_key(key);
     int E = p.E;
     const int row_waves = out.obs ? ss.row_waves : 0;
     uint32_t shape = (uint32_t)p.N | ((uint32_t)p.Nb << 8) | ((uint32_t)ss.envs_per_wave << 16) | ((uint32_t)K << 24);
@@ -776,15 +778,15 @@ static hipError_t launch_step_g(const StepShape& ss, hipStream_t stream, const K
 hipError_t launch_step(const StepShape& ss, hipStream_t stream, const KParams& p, uint8_t* st_base,
                        const unsigned long long* cell_info, const uint8_t* actions, const uint8_t* order, int K, int auto_reset,
                        const uint8_t* pool, const KOut& out, unsigned long long* counters, const StepPolicy* pol, uint8_t* masks,
-                       const StepResetObs* rso) {
+                       const StepResetObs* rso, ccxi_key* launched) {
     switch (ss.glog) {
-    case 0: return launch_step_g<0>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
-    case 1: return launch_step_g<1>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
-    case 2: return launch_step_g<2>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
-    case 3: return launch_step_g<3>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
-    case 4: return launch_step_g<4>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
-    case 5: return launch_step_g<5>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
-    case 6: return launch_step_g<6>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso);
+    case 0: return launch_step_g<0>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso, launched);
+    case 1: return launch_step_g<1>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso, launched);
+    case 2: return launch_step_g<2>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso, launched);
+    case 3: return launch_step_g<3>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso, launched);
+    case 4: return launch_step_g<4>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso, launched);
+    case 5: return launch_step_g<5>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso, launched);
+    case 6: return launch_step_g<6>(ss, stream, p, st_base, cell_info, actions, order, K, auto_reset, pool, out, counters, pol, masks, rso, launched);
     }
     return hipErrorInvalidValue;
 }

@@ -30,7 +30,7 @@ def _np(t):
     return None if t is None else t.cpu().numpy()
 
 
-def _against_oracle(oracle, ccx, g, E, K, seed, *, pool_size=257, setup=None, order=False, total=None, offset=0):
+def _against_oracle(oracle, ccx, g, E, K, seed, *, pool_size=257, setup=None, order=False, total=None, offset=0, probe=None):
     from collectivecrossing_amd.reset import build_reset_pool
 
     rng = np.random.default_rng(seed)
@@ -59,6 +59,8 @@ def _against_oracle(oracle, ccx, g, E, K, seed, *, pool_size=257, setup=None, or
     c = env.counters()
     assert c == ob.counters.as_dict()
     shape = env.launch_shape()
+    if probe:
+        probe(env)                      # (the live handle behind the launch: what it launched, tests/_kernel_keys.py)
     env.close()
     return c, shape, pool, st
 

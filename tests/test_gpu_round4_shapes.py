@@ -40,12 +40,26 @@ def _cfg(w, h, n, max_steps=60):
                                       boarding_destination_area_y=h, truncated_config=C.MaxStepsTruncatedConfig(max_steps=max_steps))
 
 
-def _case(oracle, ccx, cfg, E, K, seed, order=False, setup=None):
+def _case(oracle, ccx, cfg, E, K, seed, order=False, setup=None, probe=None):
     from test_gpu_round2 import _against_oracle
 
     from collectivecrossing_amd.params import lower_config
     g = SimpleNamespace(config=cfg, params=lower_config(cfg), N=cfg.num_boarding_agents + cfg.num_exiting_agents)
-    return _against_oracle(oracle, ccx, g, E=E, K=K, seed=seed, order=order, setup=setup)
+    return _against_oracle(oracle, ccx, g, E=E, K=K, seed=seed, order=order, setup=setup, probe=probe)
+
+
+def _launched(env, step=False):
+    """The rollout-kernel (step: step-kernel) instantiation the handle launched last, as a dict of its template arguments."""
+    import ctypes as C
+
+    import _kernel_keys as kk
+    kk.bind_keys(env._lib)
+    k = kk.Key()
+    assert env._lib.ccxi_handle_last_key(env._h, 0, C.byref(k)) == 0
+    assert k.kernel == (kk.KERNEL_STEP if step else kk.KERNEL_ROLLOUT), kk.describe(k.tuple())
+    if step:
+        return dict(zip(("GLOG", "PAIR", "K1", "ORD", "POL", "MSK", "RSO"), k.tuple()[1:8]))
+    return dict(zip(("GLOG", "PAIR", "OUT", "OCC", "PLAIN"), k.tuple()[1:6]))
 
 
 @pytest.mark.parametrize("w,h,n,E,K", [(24, 16, 8, 9001, 24), (64, 48, 8, 9001, 16), (64, 48, 16, 4501, 12), (40, 30, 3, 9001, 24)])
@@ -72,7 +86,17 @@ def test_misaligned_slabs_of_long_rows_take_the_per_step_layout_and_equal_the_or
         env_probe = ccx(cfg, E)
         assert E % env_probe.rows_alignment() != 0
         env_probe.close()
-        _case(oracle, ccx, cfg, E, 14, seed=120 + E, order=order)
+        # (launches of at most 16 steps from a tensor take the short-launch kernel since it exists: the rollout kernel's per-step
+        #  layout is what this test is about, so it is asked for -- and the launched instantiation says that it ran)
+        launched = {}
+        _case(oracle, ccx, cfg, E, 14, seed=120 + E, order=order, setup=lambda env: env.set_tunable("step_kernel", 0),
+              probe=lambda env: launched.update(_launched(env)))
+        assert launched == dict(GLOG=6, PAIR=1, OUT=3, OCC=launched["OCC"], PLAIN=int(not order)), (E, launched)
+        launched.clear()
+        # the same call as it goes by default: the short-launch kernel, with or without the move order
+        _case(oracle, ccx, cfg, E, 14, seed=120 + E, order=order, probe=lambda env: launched.update(_launched(env, step=True)))
+        assert launched == dict(GLOG=6, PAIR=1, K1=0, ORD=int(order), POL=0, MSK=0, RSO=0), (E, launched)
+        launched.clear()
 
 
 def test_misaligned_fused_greedy_rollout_equals_the_oracle(oracle, ccx):
@@ -96,6 +120,8 @@ def test_misaligned_fused_greedy_rollout_equals_the_oracle(oracle, ccx):
         np.testing.assert_array_equal(res.reward.cpu().numpy().view(np.uint64), o_rew.view(np.uint64))
         np.testing.assert_array_equal(res.agent_flags.cpu().numpy(), o_af)
         np.testing.assert_array_equal(res.env_flags.cpu().numpy(), o_ef)
+        launched = _launched(env)
+        assert (launched["GLOG"], launched["PAIR"], launched["OUT"], launched["PLAIN"]) == (6, 1, 3, 0), launched
     finally:
         env.close()
 
