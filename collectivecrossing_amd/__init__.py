@@ -14,7 +14,8 @@ __all__ = ["CollectiveCrossingConfig", "CollectiveCrossingEnv", "BatchedCollecti
            "BatchedMultiAgentEnv", "unpack_action_masks", "GaeResult", "SampleResult", "EvalResult",
            "PpoLossResult", "MlpHead", "MlpGradResult", "DeviceAdam", "SideHeads", "QLearning", "QActions",
            "TdLossResult", "ReplayRing", "ReplayBatch", "PrioritizedReplay", "PrioritizedBatch", "NStepReplay",
-           "NStepBatch", "RolloutMinibatches", "OnPolicyBatch", "CategoricalQ", "CategoricalLossResult", "WideMlpHead"]
+           "NStepBatch", "RolloutMinibatches", "OnPolicyBatch", "CategoricalQ", "CategoricalLossResult", "WideMlpHead",
+           "DeepMlpHead", "DeepGradResult"]
 
 
 _LAZY = {"CollectiveCrossingEnv": "env", "BatchedCollectiveCrossing": "batched", "VectorCollectiveCrossing": "vector",
@@ -24,7 +25,8 @@ _LAZY = {"CollectiveCrossingEnv": "env", "BatchedCollectiveCrossing": "batched",
          "QActions": "qlearn", "TdLossResult": "qlearn", "ReplayRing": "replay", "ReplayBatch": "replay",
          "PrioritizedReplay": "prioritized", "PrioritizedBatch": "prioritized", "NStepReplay": "nstep", "NStepBatch": "nstep",
          "RolloutMinibatches": "minibatch", "OnPolicyBatch": "minibatch", "CategoricalQ": "categorical",
-         "CategoricalLossResult": "categorical", "WideMlpHead": "wide"}
+         "CategoricalLossResult": "categorical", "WideMlpHead": "wide", "DeepMlpHead": "deep",
+         "DeepGradResult": "deep"}
 
 
 def __getattr__(name):  # lazy: importing the configs must not pull in torch

@@ -174,6 +174,11 @@ PROTOTYPES: dict[str, tuple] = {
     "ccx_mlp_wide_forward": (C.c_int, [_H, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p] * 7),
     "ccx_mlp_wide_backward_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32, C.c_int32]),
     "ccx_mlp_wide_backward": (C.c_int, [_H, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p] * 10),
+    "ccx_mlp_deep_forward": (C.c_int, [_H, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 10),
+    "ccx_mlp_deep_sample_actions": (C.c_int, [_H] + [C.c_int32] * 3 + [C.c_void_p] * 8 + [C.c_int32] + [C.c_void_p] * 4),
+    "ccx_mlp_deep_q_actions": (C.c_int, [_H] + [C.c_int32] * 4 + [C.c_void_p] * 12),
+    "ccx_mlp_deep_backward_workspace_bytes": (C.c_int64, [C.c_int64] + [C.c_int32] * 4),
+    "ccx_mlp_deep_backward": (C.c_int, [_H, C.c_int64] + [C.c_int32] * 5 + [C.c_void_p] * 15),
     "ccx_adam_workspace_bytes": (C.c_int64, [C.c_int32, C.POINTER(C.c_int64)]),
     "ccx_adam_step": (C.c_int, [_H, C.c_int32, C.POINTER(CcxAdamTensor), C.c_float, C.c_void_p] + [C.c_float] * 5
                       + [C.c_void_p] * 3),

@@ -39,7 +39,8 @@ class WideMlpHead(_TwoLayerHead):
     requires one, a torch product on ``grad_a``).  Anything else than the tensors described raises ``ValueError`` before the
     library is called; zero rows return empty tensors without calling it.
     Only enqueues (no host synchronisation); stream order: :class:`~collectivecrossing_amd.learner.LearnerOps`.  Not here:
-    the fused obs -> action launch, wide heads in ``SideHeads`` or dueling, more than 320 outputs, deeper networks, a
+    the fused obs -> action launch, wide heads in ``SideHeads`` or dueling, more than 320 outputs, a second hidden
+    layer (``deep.py``'s :class:`~collectivecrossing_amd.deep.DeepMlpHead` has one, with up to 8 outputs), a
     bit-defined gradient with respect to ``x``, bf16 / f16, the vector and RLlib adapters."""
 
     MAX_OUTPUTS = MAX_OUTPUTS

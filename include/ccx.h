@@ -891,7 +891,7 @@ int ccx_ppo_loss_backward(ccx_handle* h, int64_t rows, const float* logits /* [M
  * hidden or grad_a not 16-byte aligned, a workspace not 8-byte aligned, or any other f32 array not 4-byte aligned: CCX_EINVAL
  * with a ccx_last_error message, before any launch.
  *
- * Not here: deeper or wider networks, bf16 / f16, the gradient with respect to x (observation rows are inputs and nothing
+ * Not here: wider networks (CCX_MLP_WIDE) or a second hidden layer (CCX_MLP_DEEP) in these entry points, bf16 / f16, the gradient with respect to x (observation rows are inputs and nothing
  * here learns upstream of them; the Python layer forms ga w1t^T in ordinary f32 torch when x requires a gradient: correct
  * to rounding, not bit-defined), the optimiser.
  */
@@ -1623,7 +1623,8 @@ int ccx_c51_loss_backward(ccx_handle* h, int64_t rows, int32_t atoms, const floa
  * standard-normal grad_y here, 5 there: the first two figures grow with it).
  *
  * Not here: the fusion of obs -> head -> expected values -> epsilon-greedy action into one launch, wide heads in CCX_SIDES
- * or CCX_DUELING, more than 320 outputs, deeper networks, a bit-defined gradient with respect to x, matrix-core (MFMA)
+ * or CCX_DUELING, more than 320 outputs, a second hidden layer under a wide output (CCX_MLP_DEEP has two hidden layers and O <= 8), a
+ * bit-defined gradient with respect to x, matrix-core (MFMA)
  * arithmetic -- the rule is a chain of f32 operations --, bf16 / f16.
  */
 int ccx_mlp_wide_forward(ccx_handle* h, int64_t rows, int32_t L, int32_t H, int32_t O, int32_t activation,
@@ -1635,6 +1636,99 @@ int ccx_mlp_wide_backward(ccx_handle* h, int64_t rows, int32_t L, int32_t H, int
                           const float* x /* [rows][L] */, const float* hidden /* [rows][H] */, const float* grad_y /* [rows][O] */,
                           const float* w2 /* [O][H] */, void* workspace, float* grad_w1t /* [L][H] */, float* grad_b1 /* [H] */,
                           float* grad_w2 /* [O][H] */, float* grad_b2 /* [O] */, float* grad_a_or_null /* [rows][H] */);
+/*
+ * CCX_MLP_DEEP: CCX_MLP with a second hidden layer -- Linear(L, H1) -> act -> Linear(H1, H2) -> act -> Linear(H2, O), one
+ * activation for both hidden layers: the fully connected net of two hidden layers that RLlib trains by default and the
+ * usual 64-64 tanh PPO baseline -- forward in ONE kernel, fused with CCX_SAMPLE and with ccx_q_actions' choice in ONE kernel
+ * each, and the six parameter gradients bit-defined.  What CCX_MLP promises holds word for word: the outputs of a row depend
+ * on (L, H1, H2, O, activation), the row and the parameters only, never on the number of rows, the row's index, the launch
+ * shape or the entry point.
+ *
+ * Parameters (device pointers): w1t f32 [L][H1] (input-major, as CCX_MLP's), b1 f32 [H1], w2t f32 [H1][H2] (input-major:
+ * torch.nn.Linear(H1, H2).weight.t().contiguous()), b2 f32 [H2], w3 f32 [O][H2] (torch's layout), b3 f32 [O].  Limits:
+ * 1 <= L <= 512; H1 and H2 each a multiple of 16 in 16..256 (they need not be equal); 1 <= O <= 8; activation 0 = tanh,
+ * 1 = relu.  The discipline is CCX_MLP's: IEEE binary32, every operation named ONE correctly rounded operation, no fma, no
+ * reassociation, subnormals kept, the sign and payload of a NaN left open.
+ *
+ * Forward, for every row on its own:
+ *   1. h1[0 .. H1-1]: CCX_MLP's steps 1 and 2 on x with (w1t, b1).
+ *   2. layer 2, for every unit j of H2: a = b2[j]; for k = 0 .. H1-1 in this order a = a + h1[k] * w2t[k][j]; h2[j] = act(a)
+ *      (CCX_MLP's layer-1 chain with h1 in the place of x).
+ *   3. the output layer: CCX_MLP's step 3 on h2 with (w3, b3) -- the partials over groups of 16 units of H2, added in group
+ *      order onto b3[o].
+ * So by definition
+ *     deep(x) == ccx_mlp_forward(L := H1, H := H2, O; x := h1, w1t := w2t, b1 := b2, w2 := w3, b2 := b3)
+ * where h1 is the `hidden` that ccx_mlp_forward writes for (x, w1t, b1) (with any w2, b2): hidden1 is that h1, hidden2 the
+ * `hidden` of the second call, y its y, bit for bit.
+ *
+ * Backward (ccx_mlp_deep_backward).  Inputs: x f32 [M][L], hidden1 f32 [M][H1], hidden2 f32 [M][H2] (what the forward wrote),
+ * grad_y f32 [M][O], w2t, w3, activation.  Per row r, in f32:
+ *   - gh2 and ga2[r][0 .. H2-1]: CCX_MLP's backward steps 1 and 2 with (grad_y, w3, hidden2).
+ *   - for every unit i of H1: gh1 = ga2[r][0] * w2t[i][0]; then for j = 1 .. H2-1 in order gh1 = gh1 + ga2[r][j] * w2t[i][j].
+ *   - ga1[r][i] from gh1 and hidden1[r][i] by step 2's activation rule.
+ * Terms, each the f64 product of two f32 values (exact):
+ *     grad_w1t[k][i] sums x[r][k] * ga1[r][i]             grad_b1[i] sums ga1[r][i]
+ *     grad_w2t[i][j] sums hidden1[r][i] * ga2[r][j]       grad_b2[j] sums ga2[r][j]
+ *     grad_w3[o][j]  sums grad_y[r][o] * hidden2[r][j]    grad_b3[o] sums grad_y[r][o]
+ * The reduction over rows is CCX_MLP's, unchanged: blocks of 256 consecutive rows, ascending chains from +0.0, CCX_PPO_LOSS's
+ * final step over the B = ceil(M / 256) partials, one rounding to f32; no floating-point atomic, no last-block-done counter.
+ * grad_a1_or_null f32 [M][H1] and grad_a2_or_null f32 [M][H2] receive ga1 and ga2 of every row.  Two identities follow, and
+ * the tests hold the kernels to them:
+ *   - (grad_w2t, grad_b2, grad_w3, grad_b3, grad_a2) == ccx_mlp_backward(L := H1, H := H2, O; x := hidden1,
+ *     hidden := hidden2, grad_y, w2 := w3): its grad_w1t is grad_w2t, its grad_b1 is grad_b2.
+ *   - (grad_w1t, grad_b1, grad_a1) == ccx_mlp_wide_backward(L, H := H1, O := H2; x, hidden := hidden1, grad_y := grad_a2,
+ *     w2 := w2t transposed to [H2][H1]).
+ * Against IEEE f64 (measured on the CPU, tests/test_mlp_deep_spec.py, maxima doubled; the textbook composition in f64 on
+ * the same f32 inputs, autograd for the gradients, the measure of CCX_MLP's backward), torch.nn.Linear's initial weights,
+ * observation-like rows, the worse of tanh and relu, M = 20 000, L = 38, O = 5.  At 64-64: the logits within 1.74e-6
+ * absolute; grad_w1t within 1.86e-4, grad_b1 6.0e-6, grad_w2t 4.1e-5, grad_b2 1.4e-6, grad_w3 1.0e-4, grad_b3 9.7e-8.  At
+ * 256-256: the logits within 2.6e-6; grad_w1t 6.5e-3, grad_b1 5.0e-4, grad_w2t 1.43e-1, grad_b2 8.1e-3, grad_w3 1.57e-4,
+ * grad_b3 9.7e-8 -- the first four of these are ONE relu unit of ONE row whose layer-2 pre-activation lies within f32
+ * rounding of zero: the f64 side forms its own masks, takes the other branch there, and that row's whole term moves the
+ * element (with tanh alone the same shape measures 3.11e-5, 2.03e-6, 8.82e-6, 3.75e-6).
+ *
+ * Entry points.  Each only enqueues on the handle's stream: no host synchronisation, no allocation, and it captures into a
+ * HIP graph.  ccx_mlp_deep_forward is ONE kernel (hidden1 / hidden2 may be NULL).  ccx_mlp_deep_sample_actions is by
+ * definition ccx_sample_actions applied to the deep head's logits (L = ccx_obs_len(N), O = 5) on obs [E][N][L], in ONE
+ * kernel: ccx_mlp_sample_actions' key, dead-slot rule and optional logits output.  ccx_mlp_deep_q_actions is
+ * ccx_mlp_q_actions with the deep head, in ONE kernel: O = 5 (plain) or 6 (dueling), the same epsilon, explored and draw.
+ * ccx_mlp_deep_backward is THREE plain launches for every shape and every input (block partials, then CCX_MLP's final
+ * kernel on each of two stretches of the workspace; a kernel boundary orders the partials).  The caller owns the workspace,
+ * 8-byte aligned: ccx_mlp_deep_backward_workspace_bytes(rows, L, H1, H2, O) =
+ * ceil(rows / 256) * (L * H1 + H1 + H1 * H2 + H2 + O * H2 + O) * 8 bytes (0 for rows < 1 or a shape outside the limits):
+ * 1.3 GB at 524 288 rows of L = 38, H1 = H2 = 256, O = 5 (77 061 elements per block; 1.26 GB exactly; 114 MB at 64-64) -- it grows with
+ * H1 * H2, so update in chunks of rows where that is too much.  A NULL handle or a NULL required pointer, rows < 1, a shape
+ * outside the limits, x / obs, hidden1, hidden2, grad_a1 or grad_a2 not 16-byte aligned, a workspace not 8-byte aligned, or
+ * any other f32 array not 4-byte aligned: CCX_EINVAL with a ccx_last_error message, before any launch.  Offsets are 64-bit.
+ *
+ * Not here: more than two hidden layers, deep heads in CCX_SIDES, wide outputs (O > 8) on deep heads, a bit-defined
+ * gradient with respect to x, matrix-core (MFMA) arithmetic, bf16 / f16.
+ */
+int ccx_mlp_deep_forward(ccx_handle* h, int64_t rows, int32_t L, int32_t H1, int32_t H2, int32_t O, int32_t activation,
+                         const float* x /* [rows][L] */, const float* w1t /* [L][H1] */, const float* b1 /* [H1] */,
+                         const float* w2t /* [H1][H2] */, const float* b2 /* [H2] */, const float* w3 /* [O][H2] */,
+                         const float* b3 /* [O] */, float* y /* [rows][O] */, float* hidden1_or_null /* [rows][H1] */,
+                         float* hidden2_or_null /* [rows][H2] */);
+int ccx_mlp_deep_sample_actions(ccx_handle* h, int32_t H1, int32_t H2, int32_t activation,
+                                const float* obs /* [E][N][ccx_obs_len(N)] */, const float* w1t /* [L][H1] */,
+                                const float* b1 /* [H1] */, const float* w2t /* [H1][H2] */, const float* b2 /* [H2] */,
+                                const float* w3 /* [5][H2] */, const float* b3 /* [5] */, const uint8_t* masks_or_null /* [E][N] */,
+                                int32_t deterministic, uint8_t* actions /* [E][N] */, float* logp_or_null /* [E][N] */,
+                                float* entropy_or_null /* [E][N] */, float* logits_or_null /* [E][N][5] */);
+int ccx_mlp_deep_q_actions(ccx_handle* h, int32_t H1, int32_t H2, int32_t activation, int32_t O /* 5: plain, 6: dueling */,
+                           const float* obs /* [E][N][ccx_obs_len(N)] */, const float* w1t /* [L][H1] */, const float* b1 /* [H1] */,
+                           const float* w2t /* [H1][H2] */, const float* b2 /* [H2] */, const float* w3 /* [O][H2] */,
+                           const float* b3 /* [O] */, const uint8_t* masks_or_null /* [E][N] */,
+                           const float* epsilon_or_null /* [1] */, uint8_t* actions /* [E][N] */,
+                           uint8_t* explored_or_null /* [E][N] */, float* q_or_null /* [E][N][5] */);
+int64_t ccx_mlp_deep_backward_workspace_bytes(int64_t rows, int32_t L, int32_t H1, int32_t H2, int32_t O);
+int ccx_mlp_deep_backward(ccx_handle* h, int64_t rows, int32_t L, int32_t H1, int32_t H2, int32_t O, int32_t activation,
+                          const float* x /* [rows][L] */, const float* hidden1 /* [rows][H1] */,
+                          const float* hidden2 /* [rows][H2] */, const float* grad_y /* [rows][O] */,
+                          const float* w2t /* [H1][H2] */, const float* w3 /* [O][H2] */, void* workspace,
+                          float* grad_w1t /* [L][H1] */, float* grad_b1 /* [H1] */, float* grad_w2t /* [H1][H2] */,
+                          float* grad_b2 /* [H2] */, float* grad_w3 /* [O][H2] */, float* grad_b3 /* [O] */,
+                          float* grad_a1_or_null /* [rows][H1] */, float* grad_a2_or_null /* [rows][H2] */);
 /*
  * CCX_POLICY_RANDOM: uniform random actions drawn on the device -- the random-action rollouts of the
  * reference's tests and demos (e.g. tests/.../test_trajectory_vcr.py) without an action tensor (SURVEY 8b:
